@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CFS iterations/s on BASELINE config 3 (5-DoF M200i, 30 waypoints, 8 obstacles, batch 1024); configs 4 and 5 on request.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4|5] [--scaling weak|strong] [--mode CFS|PSGCFS]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4|5] [--scaling weak|strong] [--mode CFS|PSGCFS] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -21,13 +21,20 @@ seed + rank); `--scaling strong`: the config's batch is FIXED and split over the
 ("sharded 8 x MI355X": 4096 -> 512 and 256 -> 32 problems per GPU; DESIGN.md section 7 says what that does to the curve).
 Rank 0 prints ONE JSON line.
 
-What is timed.  W warm-up steps (exactly the number asked for), then `--blocks` (default 5) blocks of EXACTLY K steps,
-each block bracketed by barrier + torch.cuda.synchronize() on both sides; `ms_per_step` / `value` are those of the MEDIAN
-block, the spread is in `blocks`.  Steps are independent solves of the same resident batch, `--streams` of them in
+What is timed.  W warm-up steps (exactly the number asked for), then one block of EXACTLY K steps, bracketed by barrier +
+torch.cuda.synchronize() on both sides: K is the number of timed steps and `ms_per_step` is the block's wall time / K.
+`--blocks N` (default 1) repeats the block N times (N x K timed steps); `ms_per_step` / `value` are then those of the
+MEDIAN block, the spread is in `blocks`.  Steps are independent solves of the same resident batch, `--streams` of them in
 flight (one handle + HIP stream each): `value` is that throughput.  `value_single_launch` is the config-faithful figure
 of ONE batch launch with nothing else on the GPU (median of 5): units / `config.ms_single_solve_alone`.
 `solved_problems_per_s` / `iterations_per_s_solved_only` count only problems that ended OK_CONVERGED / OK_MAXITER (a third of
 config 3's prescribed batch has an infeasible linearisation: those proofs are work, but not useful iterations).
+
+`--dump-outputs DIR` (rank 0): after the timed block(s), the output buffers of the LAST timed step of the headline solver --
+what a caller of solve_device receives (u, x_, cost_all, e_cost_all, e_u_all, iter_O, total_iter, status; with N > 1 ranks
+the all-gathered u, x_, status, iter_O, cost instead) -- are written as DIR/<name>.npy in float64 (integer fields converted
+exactly).  The inputs are seeded, so the same arguments give the same inputs on every run and two builds can be compared
+file by file.  Above 64 MB in all, a fixed seeded sample of problems is written instead and DIR/sample_rows.npy lists them.
 
 `roofline` (dominant kernel: cfs_solve_fused_kernel).  `achieved` = algorithmic bytes (585 120 B per
 problem-iteration at config 3, the dense-constraint-matrix convention) x units per launch / the kernel's average duration
@@ -49,11 +56,6 @@ import subprocess
 import sys
 import time
 
-# The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); launches that share a queue run one
-# after the other.  Independent solves are kept in flight on their own streams below, so give each its own queue (read by
-# the runtime when it initialises, i.e. before torch touches the GPU).  Measured, CFS 8 in flight: 4 queues 2.5-3.1 ms per
-# solve depending on which streams collide, 16 queues 2.05 ms.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC only on this pool: RCCL across processes needs it (already exported on the boxes)
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -76,7 +78,8 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of exactly --steps steps each (median reported)")
+    ap.add_argument("--blocks", type=int, default=1,
+                    help="timed blocks of exactly --steps steps each (median reported); the default 1 times exactly --steps steps")
     ap.add_argument("--config", type=int, default=3, choices=[3, 4, 5], help="BASELINE.json config (3 = the headline metric)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: the config's batch per GPU; strong: the config's batch split over the GPUs")
@@ -91,6 +94,8 @@ def parse_args():
     ap.add_argument("--no-other-mode", action="store_true", help="measure only --mode (profiling runs)")
     ap.add_argument("--map", default="synthetic", choices=["synthetic", "reference"],
                     help="config 5: the synthetic assembly line, or the reference's own material_traveller map (tests/golden fixture)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline solver's outputs of the last timed step as DIR/<name>.npy (float64, <= 64 MB)")
     return ap.parse_args()
 
 
@@ -248,6 +253,7 @@ def measure(ctx, mode, steps, warmup, headline):
     B_total = ex["total"]
 
     def step(i):
+        """one solve; returns what a caller of the path receives (this rank's output buffers, or the all-gathered batch)"""
         k = i % S
         with torch.cuda.stream(streams[k]):
             slvs[k].solve_device(x_init, xR1, ff, caug, obs, noise=noise, out=outs[k], stream=streams[k].cuda_stream)
@@ -256,7 +262,8 @@ def measure(ctx, mode, steps, warmup, headline):
                 loc = dict(u=o.u, x_=o.x_, status=o.status, iter_O=o.iter_O, cost=o.cost_all[:, -1].contiguous())
                 if backend != "nccl":
                     loc = {kk: v.cpu() for kk, v in loc.items()}
-                parallel.gather_results(loc, B_total)
+                return parallel.gather_results(loc, B_total)
+        return vars(outs[k])
 
     def fence():
         torch.cuda.synchronize()
@@ -273,15 +280,18 @@ def measure(ctx, mode, steps, warmup, headline):
     block_s = []
     fused_ms = gemm_ms = 0.0
     nsolves = 0
+    last = None
     for _ in range(max(1, args.blocks)):
         t0 = time.perf_counter()
         for i in range(steps):
-            step(i)
+            last = step(i)
         fence()
         block_s.append(time.perf_counter() - t0)
         for sl in slvs:              # outside the timed region; the events go back to the handle's pool, so only the first
             a, b_, n = sl.profile_read()   # block ever creates any
             fused_ms += a; gemm_ms += b_; nsolves += n
+    # the last timed step's outputs, copied before anything below launches again (outside the timed region)
+    dumped = dump_outputs(args.dump_outputs, last) if (headline and args.dump_outputs and rank == 0) else None
     # ---- one launch alone (nothing else in flight): wall latency and kernel duration, median of 5 -----------------------
     lat_ms, lone_ms = [], []
     for _ in range(5):
@@ -363,6 +373,8 @@ def measure(ctx, mode, steps, warmup, headline):
                                  "valu_f64_frac and DESIGN.md%s" % (S, "; with mesh obstacles a solve is one (mesh linearisation, fused kernel) "
                                                                    "launch pair per outer iteration and kernel_ms covers the whole sequence" if cfg == 5 else "")},
         }
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if world == 1 and headline and not args.no_cpu_baseline:
             res["cpu_baseline"], res["accuracy"] = cpu_baseline(cfg, s, bt, ex, mode, margin, out)
     for sl in slvs:
@@ -370,6 +382,29 @@ def measure(ctx, mode, steps, warmup, headline):
     if mesh is not None:
         mesh.close()
     return res
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, outputs):
+    """Write each per-problem output tensor as d/<name>.npy in float64 (int32 fields are exact in it).  Above DUMP_MAX_BYTES
+    in all, the same fixed seeded sample of problems (rows) is kept in every file and listed in d/sample_rows.npy."""
+    import numpy as np
+    arrs = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in outputs.items()}
+    B = next(iter(arrs.values())).shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrs.values())
+    budget = DUMP_MAX_BYTES - 128 * (len(arrs) + 1)             # 128: the header of one .npy file
+    rows = None
+    if row_bytes * B > budget:
+        n = max(1, budget // (row_bytes + 8))                    # + 8: the row's entry in sample_rows.npy
+        rows = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": d, "files": sorted(k + ".npy" for k in arrs), "problems": B, "rows_written": B if rows is None else int(rows.size)}
 
 
 def cpu_baseline(cfg, s, bt, ex, mode, margin, out):

@@ -7,6 +7,11 @@ not exist.  The only reference-owned datum is route_wp_200i_xori.npy = the 5x16 
 of data/200i_xori.mat (a data file, loaded with scipy.io.loadmat and re-saved as .npy).
 
 Run from the repo root:  python tests/golden/make_golden.py
+
+It also writes tests/golden/cfs_setup.npz: per problem, the cost / dynamics matrices the oracle was handed (QQ, ff, caug, Aaug,
+Baug, alpha of build_sys_info).  numpy computes them through BLAS / LAPACK, whose rounding depends on the CPU kernel the library
+picks, and the outer iterations amplify a last-bit difference in QQ to ~1e-9 rad.  The golden tests therefore solve from the
+stored matrices (reproducing the outputs bit for bit on any CPU) and check the matrices built where they run against them.
 """
 import os
 import sys
@@ -18,10 +23,16 @@ sys.path.insert(0, ROOT)
 from oracle import oracle as O  # noqa: E402
 
 out = {}
+setup = {}
+SETUP_FIELDS = ("QQ", "ff", "caug", "Aaug", "Baug", "alpha")
 
 
-def case(name, P, mode="CFS", noise=None):
+def case(name, P, mode="CFS", noise=None, problem=None):
     s = P.sys_info
+    for f in SETUP_FIELDS:
+        k, v = (problem or name) + "/" + f, np.asarray(getattr(s, f), dtype=np.float64)
+        assert k not in setup or np.array_equal(setup[k], v), k      # cases of one problem share its matrices
+        setup[k] = v
     A, b, dist, lid, grad = O.get_con(P.ROBOT, s, P.obs, s.x_, np.zeros(s.H * s.nu), mode)
     r = O.optimizer(P.ROBOT, s, P.obs, mode, noise=noise, history=True)
     out[name + "/x_init"] = s.x_
@@ -37,10 +48,10 @@ def case(name, P, mode="CFS", noise=None):
 
 
 rng = np.random.default_rng(7)
-case("main_FANUC_CFS", O.problem_main_FANUC())
-case("main_FANUC_PSGCFS", O.problem_main_FANUC(), "PSGCFS", 0.1 * rng.standard_normal((20, 150)))
-case("main_2L_CFS", O.problem_main_2L())
-case("main_2L_lim1_CFS", O.problem_main_2L(lim=(1, 1)))
+case("main_FANUC_CFS", O.problem_main_FANUC(), problem="main_FANUC")
+case("main_FANUC_PSGCFS", O.problem_main_FANUC(), "PSGCFS", 0.1 * rng.standard_normal((20, 150)), problem="main_FANUC")
+case("main_2L_CFS", O.problem_main_2L(), problem="main_2L")
+case("main_2L_lim1_CFS", O.problem_main_2L(lim=(1, 1)), problem="main_2L")      # lim enters none of the setup matrices
 rw = np.load(os.path.join(ROOT, "tests", "golden", "route_wp_200i_xori.npy"))
 case("RRTstar_CFS", O.problem_RRTstar_CFS(rw))
 
@@ -58,4 +69,5 @@ for rid, nj in (("M200i", 5), ("M16iB", 5), ("2L", 2)):
     out[f"geom_{rid}/d"], out[f"geom_{rid}/linkid"], out[f"geom_{rid}/pos"] = d, lid, pos
 
 np.savez_compressed(os.path.join(ROOT, "tests", "golden", "cfs_cases.npz"), **out)
-print("wrote", len(out), "arrays")
+np.savez_compressed(os.path.join(ROOT, "tests", "golden", "cfs_setup.npz"), **setup)
+print("wrote", len(out), "+", len(setup), "arrays")

@@ -4,8 +4,38 @@
 What pins the oracle: (1) the distLinSeg doc example, (2) KKT certificates + an independent NNLS
 solve (test_oracle_qp.py), (3) the numbers below, which SURVEY.md (N3, N8-N10) obtained with a
 separately written numpy/NNLS restatement -- two independent restatements agree.
+
+The optimizer runs from the cost / dynamics matrices the fixtures were made with (tests/golden/cfs_setup.npz), so its outputs
+are pinned bit for bit on any CPU; the matrices build_sys_info makes here are checked against those to a few ulps.  numpy
+forms them with BLAS / LAPACK, whose rounding depends on the CPU kernel picked at run time, and the outer iterations amplify a
+last-bit difference in QQ to ~1e-9 rad (tests/golden/make_golden.py).
 """
+import os
+
 import numpy as np
+import pytest
+
+SETUP_FIELDS = ("QQ", "ff", "caug", "Aaug", "Baug", "alpha")
+SETUP_RTOL = 1e-14          # max-norm relative; CPU kernels observed to differ by <= 6e-16
+
+
+@pytest.fixture(scope="module")
+def golden_setup():
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cfs_setup.npz"))
+
+
+def _stored_setup(P, golden_setup, problem):
+    """Check P's cost / dynamics matrices against the stored ones, then hand the oracle the stored ones."""
+    s = P.sys_info
+    for f in SETUP_FIELDS:
+        want = golden_setup[problem + "/" + f]
+        got = np.asarray(getattr(s, f), dtype=np.float64)
+        assert got.shape == want.shape, (problem, f, got.shape, want.shape)
+        err = float(np.abs(got - want).max()) if want.size else 0.0
+        assert err <= SETUP_RTOL * float(np.abs(want).max()), (problem, f, err)
+        setattr(s, f, want.copy() if want.ndim else float(want))
+    s.Qaug, s.paug = s.QQ, s.ff                     # build_sys_info's aliases
+    return P
 
 
 def _run(O, P, mode="CFS", noise=None):
@@ -19,8 +49,8 @@ def _check(r, g, name):
     np.testing.assert_allclose(r.cost_all, g[name + "/cost_all"], rtol=1e-12)
 
 
-def test_main_fanuc_cfs(O, golden):
-    P = O.problem_main_FANUC()
+def test_main_fanuc_cfs(O, golden, golden_setup):
+    P = _stored_setup(O.problem_main_FANUC(), golden_setup, "main_FANUC")
     r = _run(O, P)
     _check(r, golden, "main_FANUC_CFS")
     # SURVEY N3 / N8 (independent restatement): converged at step 11, costs, waypoints
@@ -36,24 +66,24 @@ def test_main_fanuc_cfs(O, golden):
     assert r.kkt[0] < 1e-12 and r.kkt[1] < 1e-12 and r.kkt[3] < 1e-9
 
 
-def test_main_fanuc_psgcfs(O, golden):
-    r = _run(O, O.problem_main_FANUC(), "PSGCFS", golden["main_FANUC_PSGCFS/noise"])
+def test_main_fanuc_psgcfs(O, golden, golden_setup):
+    r = _run(O, _stored_setup(O.problem_main_FANUC(), golden_setup, "main_FANUC"), "PSGCFS", golden["main_FANUC_PSGCFS/noise"])
     _check(r, golden, "main_FANUC_PSGCFS")
     assert r.status == 1 and r.iter_O == 21          # x_old is never refreshed -> always MAX_O_ITER
 
 
-def test_main_2l(O, golden):
-    r = _run(O, O.problem_main_2L())
+def test_main_2l(O, golden, golden_setup):
+    r = _run(O, _stored_setup(O.problem_main_2L(), golden_setup, "main_2L"))
     _check(r, golden, "main_2L_CFS")
     assert r.status == 2 and r.iter_O == 2           # the QP of outer iteration 2 is infeasible
-    P = O.problem_main_2L(lim=(1, 1))
+    P = _stored_setup(O.problem_main_2L(lim=(1, 1)), golden_setup, "main_2L")
     r = _run(O, P)
     _check(r, golden, "main_2L_lim1_CFS")
     assert r.status == 0 and r.iter_O == 9 and abs((r.cost_all - P.sys_info.caug)[-1] + 123412.5759) < 1e-3
 
 
-def test_rrtstar_cfs(O, golden, route_wp):
-    P = O.problem_RRTstar_CFS(route_wp)
+def test_rrtstar_cfs(O, golden, golden_setup, route_wp):
+    P = _stored_setup(O.problem_RRTstar_CFS(route_wp), golden_setup, "RRTstar_CFS")
     r = _run(O, P)
     _check(r, golden, "RRTstar_CFS")
     assert r.status == 0 and r.iter_O == 18 and abs((r.cost_all - P.sys_info.caug)[-1] + 73637.01) < 0.01

@@ -105,16 +105,28 @@ def test_stl_round_trip_and_map_from_stl(tmp_path):
     assert 8000 < big.shape[0] < 12000
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/map"), reason="the reference's STL maps exist only in the build container")
-def test_reference_stl_maps_parse_and_measure(O):
-    """Container-only (the reference cannot travel): the package's binary-STL reader takes the reference's own maps
-    (map/*.STL, Lib/functions/MapFromSTL.m:1-11) -- 27 396 / 12 620 / 2 156 triangles, SURVEY.md section 2 -- and the
+@pytest.fixture(scope="module")
+def reference_maps(tmp_path_factory):
+    """Directory holding the reference's map files, unpacked from the data fixture tests/golden/reference_maps.tar.xz
+    (tests/golden/make_reference_maps.py): the three binary STL maps as files, and environment_v.npy = map/environment.mat:envir.v."""
+    import tarfile
+    d = tmp_path_factory.mktemp("reference_maps")
+    with tarfile.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_maps.tar.xz")) as tf:
+        for m in tf.getmembers():
+            assert m.isfile() and os.path.basename(m.name) == m.name, m.name
+            (d / m.name).write_bytes(tf.extractfile(m).read())
+    return d
+
+
+def test_reference_stl_maps_parse_and_measure(O, reference_maps):
+    """The package's binary-STL reader takes the reference's own maps (map/*.STL, Lib/functions/MapFromSTL.m:1-11, stored
+    unchanged in tests/golden/reference_maps.tar.xz) -- 27 396 / 12 620 / 2 156 triangles, SURVEY.md section 2 -- and the
     CPU mesh oracle returns finite distances on them.  (stlread itself is an external toolbox function.)"""
     from motionplanning_5d_m_amd import mesh as M
     want = {"assembly line_Assem1.STL": 27396, "material_traveller.STL": 12620, "table.STL": 2156}
     rng = np.random.default_rng(3)
     for k, (name, nt) in enumerate(want.items()):
-        tri = M.read_stl_binary(os.path.join("/root/reference/map", name))
+        tri = M.read_stl_binary(str(reference_maps / name))
         assert tri.shape == (nt, 3, 3) and np.isfinite(tri).all()
         tri_m = M.map_from_stl(tri) / 1000.0                          # MapFromSTL.m:6-10, mm -> m
         assert np.isfinite(tri_m).all() and tri_m.min() >= -0.1 - 1e-9       # MapFromSTL.m:8 shifts one axis by -100 mm
@@ -130,25 +142,21 @@ def test_reference_stl_maps_parse_and_measure(O):
         assert off.max() < 1e-9
 
 
-def test_reference_map_fixture_is_the_reference_file(O):
-    """tests/golden/assembly_line_cell.npz holds DATA of /root/reference/map/assembly line_Assem1.STL: where the reference is
-    present (the build container) the fixture loader must reproduce, bit for bit, the triangles the package's STL reader +
-    MapFromSTL.m:6-10 + mm -> m give for the whole file, cropped to 2.5 m around robot.base."""
+def test_reference_map_fixture_is_the_reference_file(O, reference_maps):
+    """tests/golden/assembly_line_cell.npz holds DATA of the reference's map/assembly line_Assem1.STL (stored whole in
+    tests/golden/reference_maps.tar.xz): the fixture loader must reproduce, bit for bit, the triangles the package's STL
+    reader + MapFromSTL.m:6-10 + mm -> m give for the whole file, cropped to 2.5 m around robot.base."""
     import os
     from motionplanning_5d_m_amd import mesh
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     tri = mesh.load_map_fixture(os.path.join(root, "tests", "golden", "assembly_line_cell.npz"))
     assert tri.shape == (13258, 3, 3)
-    src = "/root/reference/map/assembly line_Assem1.STL"
-    if not os.path.exists(src):
-        pytest.skip("the reference is not present on this box")
-    full = mesh.map_from_stl(mesh.read_stl_binary(src)) * 1e-3
+    full = mesh.map_from_stl(mesh.read_stl_binary(str(reference_maps / "assembly line_Assem1.STL"))) * 1e-3
     base = np.array([3.150, 8.500, 0.330])
     keep = np.linalg.norm(full - base, axis=2).min(axis=1) < 2.5
     assert full.shape[0] == 27396
     np.testing.assert_array_equal(full[keep], tri)
     # the reference's own transformed copy of the same map (map/environment.mat: envir.v in mm, MapFromSTL's output) agrees
-    import scipy.io
-    env = scipy.io.loadmat("/root/reference/map/environment.mat")["envir"]["v"][0, 0]
+    env = np.load(reference_maps / "environment_v.npy")
     assert env.shape == (27396 * 3, 3)
     np.testing.assert_allclose(env.reshape(-1, 3, 3) * 1e-3, full, rtol=0, atol=1e-9)

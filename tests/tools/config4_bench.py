@@ -3,7 +3,6 @@ The batch is B perturbed copies of the logged RRT route (tests/golden/route_wp_2
 resampled on the device (cfs_build_terms_from_routes_device) and smoothed by CFS_FANUC.
 usage: python tests/tools/config4_bench.py [--batch B] [--steps K] [--warmup W] [--check N] [--streams S]"""
 import argparse, json, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")      # one hardware queue per stream (see bench.py)
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np, torch

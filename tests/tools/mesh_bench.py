@@ -2,7 +2,6 @@
 A step = one complete batched solve (mesh linearisation + fused solver, one outer iteration per launch pair).
 usage: python tests/tools/mesh_bench.py [--mode CFS|PSGCFS] [--steps K] [--warmup W] [--check N] [--streams S]"""
 import argparse, json, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")      # one hardware queue per stream (see bench.py)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
 import motionplanning_5d_m_amd as pkg

@@ -10,7 +10,6 @@ its one route.  Reported: trees/s, nodes/s, proposals/s of one B-tree launch (me
 the smoothing stage on the grown routes (the oracle checks --check of them).
 usage: python tests/tools/rrt_bench.py [--batch B] [--seeds 6] [--rounds R] [--steps K] [--check N] [--solver RRT|RRT*]"""
 import argparse, json, os, statistics, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np, torch

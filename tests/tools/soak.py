@@ -2,7 +2,6 @@
 output compared on the device with the first one of its handle -- any race between launches (spill pool, launch order buffers,
 warm-start state) would show as a differing bit.  usage: python tests/tools/soak.py [solves per handle]"""
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np, torch

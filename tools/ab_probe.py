@@ -15,7 +15,6 @@ if sys.argv[1] == "cmp":
         print(f"{k:16s} {'bit-identical' if same else 'DIFFERENT'}{extra}")
     sys.exit(0)
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # one hardware queue per stream, as bench.py
 import torch
 from motionplanning_5d_m_amd import _lib
 LIBNAME = next((a for a in sys.argv[2:] if a.endswith(".so")), "libcfs_hip.so")
