@@ -229,6 +229,14 @@ int cfs_profile_read(cfs_problem *p, double *solve_kernel_ms, double *gemm_kerne
 int cfs_dist_arm(const cfs_robot *robot, int njoint, int N, const double *theta, int nobs, const double *obs,
                  double *d, int *linkid, double *pos);
 
+/* cfs_dist_arm with the analytic gradient (the CFS_JAC_ANALYTIC contract below) for the same N configurations x nobs
+ * obstacles: extends [d,linkid] = dist_arm_all(theta,base,obs{j}.l,robot) (Lib/CFS_FANUC.m:115) by
+ * grad = d/dtheta d, the exact derivative in place of Diff = num_jac(f,theta)' (Lib/CFS_FANUC.m:112-118,
+ * Lib/functions/num_jac.m:1-17).  d and linkid are bit for bit cfs_dist_arm's; grad: N x nobs x njoint
+ * (all of d, linkid, grad required).  The same device code as the solver's analytic linearisation. */
+int cfs_dist_arm_grad(const cfs_robot *robot, int njoint, int N, const double *theta, int nobs, const double *obs,
+                      double *d, int *linkid, double *grad);
+
 /* the distance/Jacobian half of get_con (Lib/CFS_FANUC.m:110-121): for every (problem, obstacle,
  * waypoint) the distance, closest link and Diff = num_jac(f,theta)' (Lib/functions/num_jac.m:1-17,
  * literal scheme).  x_: B x (H*nstate); obs: B x nobs x 6;
@@ -250,6 +258,25 @@ int cfs_get_con(cfs_problem *p, int B, const double *x_, const double *u, const 
  * [collision (j,i) | vel+ (i,c) | vel- (i,c) | bound+ | bound-]; qp_iter, status: B. */
 int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const double *xR1,
            const double *dist, const double *grad, double *u, double *lambda, int *qp_iter, int *status);
+
+/* ---- Jacobian mode -------------------------------------------------------
+ * How the solver linearises the line obstacles: Diff in get_con (Lib/CFS_FANUC.m:112-118).
+ *   CFS_JAC_FD_LITERAL (default): num_jac (Lib/functions/num_jac.m:1-17) literally -- central differences with
+ *     eps = 1e-5 and the perturbed xp never restored, evaluated at 2*njoint+1 poses; parity with the reference.
+ *   CFS_JAC_ANALYTIC: for each (problem, obstacle, waypoint) the exact derivative with respect to theta of the branch of
+ *     dist_arm_* active at the base pose: the first-minimum link, distLinSeg (Lib/functions/distLinSeg.m:23-91)
+ *     differentiated through the branch taken (point / parallel / general, clamp then recompute: a clamped parameter
+ *     contributes nothing) and through the near-zero surrogate dis = -|c - p1e| (dist_arm_3D_200i_2.m:22-24; 0 for a
+ *     zero-length link).  Equal to the gradient of dist_arm wherever that is differentiable, the one-sided derivative
+ *     of the winning branch at kinks.  The distances and closest links are unchanged (bit for bit the literal mode's
+ *     base-pose values); the iterates differ from the literal mode's by the O(eps) of num_jac and what the outer loop
+ *     makes of it.  Mesh obstacles keep their own linearisation (cfs_problem_set_meshes) in either mode; CHOMP
+ *     (cfs_chomp_batch) is not affected.
+ * The mode applies to every later solve and piece (cfs_linearize, cfs_get_con, cfs_qp) of the handle; a handle serves one
+ * stream at a time, so set it between solves.  NULL handle or unknown mode: CFS_ERR_INVALID_ARG, nothing else happens. */
+typedef enum cfs_jacobian_mode { CFS_JAC_FD_LITERAL = 0, CFS_JAC_ANALYTIC = 1 } cfs_jacobian_mode;
+int cfs_problem_set_jacobian(cfs_problem *p, int mode);
+int cfs_problem_get_jacobian(const cfs_problem *p, int *mode);
 
 /* ---- mesh obstacles -----------------------------------------------------
  * The reference measures the arm against a surface with `[dis, points] = point2surface_dis(pos{i}.p, obs)`

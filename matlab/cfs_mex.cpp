@@ -9,9 +9,11 @@
 //   [Ainq, binq] = cfs_mex('get_con', mode, obs, sys_info, ROBOT, x_, u)   % self.get_con() (Lib/CFS_FANUC.m:101-135): dense, reference row order
 //   [u, x_, cost_all, e_cost_all, e_u_all, iter_O] = cfs_mex('chomp', obs_, sys_info, ROBOT, uref)   % CHOMP_FANUC.optimizer (Lib/CHOMP_FANUC.m:54-69);
 //        obs_ = the reference's cell: obs_{1}.num_obs followed by the obstacles (M16iB/CHOMP.m:26-29)
-//   [d, linkid] = cfs_mex('dist_arm', theta, obs_l, robot, ROBOT)  % dist_arm_3D_200i_2 / dist_arm_3D_Heu_2 / dist_arm_2L(theta, base, obs_l, robot)
+//   [d, linkid, grad] = cfs_mex('dist_arm', theta, obs_l, robot, ROBOT)  % dist_arm_3D_200i_2 / dist_arm_3D_Heu_2 / dist_arm_2L(theta, base, obs_l, robot)
 //        theta = njoint x N (one pose per column), obs_l = 3x2 obstacle axis (or 6 x nobs, one [l(:,1); l(:,2)] per column): the
-//        geometry kernel RRT_FANUC.feasible (Lib/RRT_FANUC.m:146-181) and get_con (Lib/CFS_FANUC.m:115) call; d, linkid = nobs x N
+//        geometry kernel RRT_FANUC.feasible (Lib/RRT_FANUC.m:146-181) and get_con (Lib/CFS_FANUC.m:115) call; d, linkid = nobs x N;
+//        grad (when asked for) = njoint x (nobs*N), column (n-1)*nobs+j = the analytic d(d(j,n))/d(theta(:,n)) (cfs_dist_arm_grad)
+//   'solve' and 'get_con' honour an optional sys_info.jacobian = 'fd_literal' (default, num_jac.m) | 'analytic' (include/cfs_hip.h)
 //   [route, all_nodes, total_dis, all_ee, fail, node_num] = cfs_mex('rrt', obs, sys_info, goal, region_g, region_s, sample_off, ROBOT, SOLVER, U)
 //        RRT_FANUC(obs, sys_info, goal, region_g, region_s, sample_off, ROBOT, SOLVER).find_route() (Lib/RRT_FANUC.m:48-91) grown on the GPU;
 //        U = rand(ndraw, S): MATLAB's own rand, consumed per tree exactly as find_route consumes it (one per proposal + nstate for a random
@@ -104,6 +106,13 @@ static void make_family(Family &f, int mode, const mxArray *obs, int first, int 
     d.margin = f.margin.data();
     check(cfs_problem_create(&d, &f.p));
     if (!meshes.empty()) check(cfs_problem_set_meshes(f.p, (int)meshes.size(), meshes.data()));
+    // optional sys_info.jacobian = 'fd_literal' (num_jac.m, the default) | 'analytic' (cfs_problem_set_jacobian)
+    if (const mxArray *fj = mxGetField(S, 0, "jacobian")) {
+        if (!mxIsChar(fj)) mexErrMsgIdAndTxt("cfs:field", "sys_info.jacobian must be 'fd_literal' or 'analytic'");
+        const std::string jm = mxArrayToString(fj);
+        if (jm == "analytic") check(cfs_problem_set_jacobian(f.p, CFS_JAC_ANALYTIC));
+        else if (jm != "fd_literal") mexErrMsgIdAndTxt("cfs:field", "sys_info.jacobian must be 'fd_literal' or 'analytic'");
+    }
 }
 
 static void solve(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
@@ -188,11 +197,17 @@ static void dist_arm(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     fill_robot(prhs[3], ROBOT.c_str(), nj, r);
     std::vector<double> d((size_t)N * nobs);
     std::vector<int> lid((size_t)N * nobs);
-    check(cfs_dist_arm(&r, nj, N, mxGetPr(prhs[1]), nobs, mxGetPr(prhs[2]), d.data(), lid.data(), nullptr));   // theta njoint x N column-major = N x njoint row-major
+    mxArray *og = nullptr;
+    if (nlhs > 2) {   // grad = d(d)/d(theta), njoint x nobs x N: the analytic gradient (cfs_dist_arm_grad; N x nobs x njoint row-major)
+        og = mxCreateDoubleMatrix(nj, (size_t)nobs * N, mxREAL);
+        check(cfs_dist_arm_grad(&r, nj, N, mxGetPr(prhs[1]), nobs, mxGetPr(prhs[2]), d.data(), lid.data(), mxGetPr(og)));
+    } else
+        check(cfs_dist_arm(&r, nj, N, mxGetPr(prhs[1]), nobs, mxGetPr(prhs[2]), d.data(), lid.data(), nullptr));   // theta njoint x N column-major = N x njoint row-major
     mxArray *od = mxCreateDoubleMatrix(nobs, N, mxREAL), *ol = mxCreateDoubleMatrix(nobs, N, mxREAL);
     for (size_t k = 0; k < d.size(); ++k) { mxGetPr(od)[k] = d[k]; mxGetPr(ol)[k] = lid[k]; }               // N x nobs row-major = nobs x N column-major
     plhs[0] = od;
     if (nlhs > 1) plhs[1] = ol; else mxDestroyArray(ol);
+    if (og) plhs[2] = og;
 }
 
 // RRT_FANUC.find_route for S = size(U,2) seeds (Lib/RRT_FANUC.m:63-91; Lib/functions/s_Parallel_rrt.m:16-25)

@@ -30,6 +30,7 @@ ERRORS = {-1: "CFS_ERR_INVALID_ARG", -2: "CFS_ERR_NO_DEVICE", -3: "CFS_ERR_HIP",
 STATUS = {0: "OK_CONVERGED", 1: "OK_MAXITER", 2: "QP_INFEASIBLE", 3: "NUMERIC"}
 ROBOT_KIND = {"M16iB": 0, "M200i": 1, "2L": 2}
 MODE = {"CFS": 0, "PSGCFS": 1}
+JACOBIAN = {"fd_literal": 0, "analytic": 1}   # cfs_jacobian_mode
 
 
 class CfsError(RuntimeError):
@@ -191,6 +192,9 @@ SYMBOLS = [
     ("cfs_debug_trace_read", C.c_int, [_P, _P]),
     ("cfs_debug_log_u", C.c_int, [_P, C.c_int]),
     ("cfs_debug_read_u_log", C.c_int, [_P, C.c_int, _P]),
+    ("cfs_problem_set_jacobian", C.c_int, [_P, C.c_int]),
+    ("cfs_problem_get_jacobian", C.c_int, [_P, C.POINTER(C.c_int)]),
+    ("cfs_dist_arm_grad", C.c_int, [C.POINTER(cfs_robot), C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)

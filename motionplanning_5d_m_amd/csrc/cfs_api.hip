@@ -197,6 +197,7 @@ struct cfs_problem {
     DevBuf<double> trace;                 // 8 doubles per active-set step of problem trace_b
     int trace_b = -1, trace_cap = 0;
     DevBuf<double> u_log;                 // max_batch x MAX_O_ITER x nn: u after every outer iteration (both solvers)
+    int jac = CFS_JAC_FD_LITERAL;         // cfs_problem_set_jacobian: which linearisation every later launch of this handle runs
     bool prof = false;
     std::vector<hipEvent_t> ev;   // 4 per profiled solve: gemm start/stop, fused start/stop
     std::vector<hipEvent_t> ev_free;   // recycled events: none is created inside a timed region once the pool is warm
@@ -233,12 +234,12 @@ void cfs_build_dev_robot(const cfs_robot &r, DevRobot &d) { build_dev_robot(r, d
 // 3.6 -> 2.3 ms per solve with w2s, CFS 5.8 -> 5.6 ms with w2m (its infeasibility proofs run active sets of ~100 rows).
 // w2s is compiled for the identity Hessian only (PSGCFS), w2m for QQ only (CFS), w1 for both; force_w1: CFS_DBG_TIER_W1.
 bool fused_fits(int nj, int H, int nobs) { return fused_fits_w1(nj, H, nobs); }
-hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1)
+hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1, bool analytic)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
-    if (!force_w1 && ident && fused_fits_w2s(nj, p.H, p.nobs)) return launch_fused_w2s(nj, p, s);
-    if (!force_w1 && !ident && fused_fits_w2m(nj, p.H, p.nobs)) return launch_fused_w2m(nj, p, s);
-    return launch_fused_w1(nj, p, s);
+    if (!force_w1 && ident && fused_fits_w2s(nj, p.H, p.nobs)) return analytic ? launch_fused_w2sa(nj, p, s) : launch_fused_w2s(nj, p, s);
+    if (!force_w1 && !ident && fused_fits_w2m(nj, p.H, p.nobs)) return analytic ? launch_fused_w2ma(nj, p, s) : launch_fused_w2m(nj, p, s);
+    return analytic ? launch_fused_w1a(nj, p, s) : launch_fused_w1(nj, p, s);
 }
 
 extern "C" {
@@ -593,6 +594,7 @@ static void fill_fused_family(const cfs_problem *p, FusedParams &fp, int B)
     fp.u_log = p->u_log.p;
 }
 static bool force_w1(const cfs_problem *p) { return (p->dbg_mask & CFS_DBG_TIER_W1) != 0; }
+static bool analytic(const cfs_problem *p) { return p->jac == CFS_JAC_ANALYTIC; }
 
 int cfs_set_launch_order(cfs_problem *p, const int *order, int n)
 {
@@ -680,7 +682,7 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
     }
     if (p->prof) HIPCHK(hipEventRecord(e4[2], s));   // after the launch-order pre-pass: [e4[2], e4[3]] brackets the fused kernel alone (mesh handles: the loop of launches)
     if (p->nmesh == 0) {
-        HIPCHK(launch_fused(nj, fp, s, force_w1(p)));
+        HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p)));
     } else {
         // Mesh obstacles are linearised by their own kernel (hierarchy traversals do not fit the fused kernel's register
         // budget), which needs the current iterate: one outer iteration per launch, state carried through HBM.  Every
@@ -697,7 +699,7 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
             lm.seed_prev = it > 0;
             HIPCHK(launch_linearize_mesh(nj, lm, s));
             fp.resume = it > 0;
-            HIPCHK(launch_fused(nj, fp, s, force_w1(p)));
+            HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p)));
         }
     }
     if (p->prof) HIPCHK(hipEventRecord(e4[3], s));
@@ -1103,6 +1105,7 @@ int cfs_dist_arm(const cfs_robot *robot, int njoint, int N, const double *theta,
     P.d = st.up<double>(nullptr, (size_t)N * nobs);
     P.linkid = st.up<int>(nullptr, (size_t)N * nobs);
     P.pos = pos ? st.up<double>(nullptr, (size_t)N * njoint * 6) : nullptr;
+    P.grad = nullptr;
     if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
     launch_dist_arm(P, nullptr);
     HIPCHK(hipGetLastError());
@@ -1111,6 +1114,53 @@ int cfs_dist_arm(const cfs_robot *robot, int njoint, int N, const double *theta,
     st.down(linkid, P.linkid, (size_t)N * nobs);
     if (pos) st.down(pos, P.pos, (size_t)N * njoint * 6);
     if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
+    return CFS_SUCCESS;
+}
+
+int cfs_dist_arm_grad(const cfs_robot *robot, int njoint, int N, const double *theta, int nobs, const double *obs,
+                      double *d, int *linkid, double *grad)
+{
+    int rc = check_robot(robot, njoint);
+    if (rc) return rc;
+    if (N < 0 || nobs < 0 || !theta || !obs || !d || !linkid || !grad) return fail(CFS_ERR_INVALID_ARG, "bad argument");
+    if (N == 0 || nobs == 0) return CFS_SUCCESS;
+    if (have_device() == 0) return fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
+    HIPCHK(hipSetDevice(g_device));
+    DevRobot hr;
+    build_dev_robot(*robot, hr);
+    Stage st;
+    DistArmParams P;
+    P.rb = st.up(&hr, 1);
+    P.N = N; P.nobs = nobs; P.nj = njoint;
+    P.theta = st.up(theta, (size_t)N * njoint);
+    P.obs = st.up(obs, (size_t)nobs * 6);
+    P.d = st.up<double>(nullptr, (size_t)N * nobs);
+    P.linkid = st.up<int>(nullptr, (size_t)N * nobs);
+    P.pos = nullptr;
+    P.grad = st.up<double>(nullptr, (size_t)N * nobs * njoint);
+    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
+    launch_dist_arm_grad(P, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(nullptr));
+    st.down(d, P.d, (size_t)N * nobs);
+    st.down(linkid, P.linkid, (size_t)N * nobs);
+    st.down(grad, P.grad, (size_t)N * nobs * njoint);
+    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
+    return CFS_SUCCESS;
+}
+
+int cfs_problem_set_jacobian(cfs_problem *p, int mode)
+{
+    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (mode != CFS_JAC_FD_LITERAL && mode != CFS_JAC_ANALYTIC) return fail(CFS_ERR_INVALID_ARG, "unknown jacobian mode %d", mode);
+    p->jac = mode;
+    return CFS_SUCCESS;
+}
+
+int cfs_problem_get_jacobian(const cfs_problem *p, int *mode)
+{
+    if (!p || !mode) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    *mode = p->jac;
     return CFS_SUCCESS;
 }
 
@@ -1164,7 +1214,7 @@ static int linearize_piece(cfs_problem *p, int B, const PieceBuffers &pb, double
         HIPCHK(launch_linearize_mesh(nj, lm, nullptr));
         fp.nmesh = p->nmesh; fp.ext_dist = p->dist.p; fp.ext_grad = p->grad.p;
     }
-    HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p)));
+    HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p), analytic(p)));
     return CFS_SUCCESS;
 }
 
@@ -1259,7 +1309,7 @@ int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const 
         launch_batched_gemv(g, nullptr);
         fp.x0 = p->x0.p;
     } else fp.x0 = d_lin;
-    HIPCHK(launch_fused(p->d.njoint, fp, nullptr, force_w1(p)));
+    HIPCHK(launch_fused(p->d.njoint, fp, nullptr, force_w1(p), analytic(p)));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(nullptr));
     st.down(u, d_u, (size_t)B * nn);

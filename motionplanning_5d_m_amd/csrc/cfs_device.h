@@ -44,8 +44,10 @@ struct DistArmParams {
     double *d;                   // N x nobs
     int *linkid;                 // N x nobs
     double *pos;                 // N x nj x 6 or null
+    double *grad;                // N x nobs x nj (launch_dist_arm_grad only)
 };
 void launch_dist_arm(const DistArmParams &p, hipStream_t s);
+void launch_dist_arm_grad(const DistArmParams &p, hipStream_t s);   // d, linkid and the analytic gradient (cfs_geom_dev.h)
 
 // launch order of the fused solver (cfs_geom.hip): problems whose initial trajectory violates the most (waypoint, obstacle)
 // clearances first -- those run the longest active sets (rank correlation 0.7 with the QP steps on config 3)
@@ -145,7 +147,12 @@ hipError_t launch_fused_w2s(int nj, FusedParams p, hipStream_t s);
 bool fused_fits_w1(int nj, int H, int nobs);
 bool fused_fits_w2m(int nj, int H, int nobs);
 bool fused_fits_w2s(int nj, int H, int nobs);
-hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1 = false);   // cfs_api.hip: tier by mode and capacity
+// the same tiers with the analytic Jacobian (cfs_fused.hip built with CFS_JAC=1; same LDS layout and capacities)
+hipError_t launch_fused_w1a(int nj, FusedParams p, hipStream_t s);
+hipError_t launch_fused_w2ma(int nj, FusedParams p, hipStream_t s);
+hipError_t launch_fused_w2sa(int nj, FusedParams p, hipStream_t s);
+// cfs_api.hip: tier by mode and capacity; analytic: the CFS_JAC_ANALYTIC kernels
+hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1 = false, bool analytic = false);
 bool fused_fits(int nj, int H, int nobs);
 
 struct CostHistParams {          // EVAL.get_cost / store_result for a logged u history (CFS mode)

@@ -11,7 +11,8 @@
 // therefore owns one problem for its whole life: no host round trip, no inter-problem barrier,
 // and the hardware's workgroup dispatcher load-balances the stragglers over the 256 CUs.
 //   * linearisation (FK variants, segment pairs, literal num_jac) as in cfs_geom.hip, tiled over
-//     waypoints, scratch aliased with the QP's Y storage;
+//     waypoints, scratch aliased with the QP's Y storage; objects built with CFS_JAC=1 run the analytic
+//     Jacobian instead (one chain per waypoint, one tangent sweep of the winning link: cfs_geom_dev.h);
 //   * QP: Goldfarb-Idnani dual active set in range-space form.  The inverse Gram matrix
 //     P = (N'H^{-1}N)^{-1} is kept EXPLICITLY, one row per thread in registers (it is symmetric,
 //     so column access is never needed); adding a constraint is a bordered rank-1 update,
@@ -57,6 +58,14 @@ constexpr int CERT_AT = CFS_CERT_AT;    // main-loop steps of a QP before the st
 // This file is compiled once per tier (Makefile): CFS_VARIANT names the exported launch_fused_<tier> / fused_fits_<tier>.
 #ifndef CFS_VARIANT
 #define CFS_VARIANT w1
+#endif
+#ifndef CFS_JAC
+#define CFS_JAC 0                        // 1: analytic Jacobian (CFS_JAC_ANALYTIC handles): a kernel of its own name, objects of their own
+#endif
+#if CFS_JAC
+#define CFS_FUSED_KERNEL cfs_solve_fused_analytic_kernel
+#else
+#define CFS_FUSED_KERNEL cfs_solve_fused_kernel
 #endif
 #define CFS_CAT2(a, b) a##_##b
 #define CFS_CAT(a, b) CFS_CAT2(a, b)
@@ -454,7 +463,7 @@ __host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int
 
 // ------------------------------------------------------------------------------------------------
 template <int NJ, int QB, bool IDENT>      // IDENT: the QP Hessian is the identity (PSGCFS projection)
-__global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(FusedParams P)
+__global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParams P)
 {
     constexpr int NS = 2 * NJ, NVT = nvt(NJ), NE = 2 * NJ + 1;
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -621,6 +630,61 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
         // =========================================================================================
         // get_con, distance half (CFS_FANUC.m:110-118): dist -> s_rhs, Diff -> s_g
         // =========================================================================================
+#if CFS_JAC
+        // Analytic Jacobian: Diff = the exact derivative of the branch of dist_arm active at the base pose (cfs_geom_dev.h).
+        // Same base-pose distances and first-minimum link as the literal scheme; per waypoint one sincos per joint and ONE
+        // kinematic chain (end points + joint twists), per (waypoint, obstacle) one tangent sweep of the winning link.
+        // The four phases carry prep(0..3) as the literal scheme's do.
+        (void)NE;
+        if (nseg > 0) {
+            const int W = P.lin_w;                           // tiles of the literal scheme's size: its scratch is a superset
+            double *s_sc = lds + L.lin;                      // [W][NJ][2]  sin, cos of theta (minus the joint offset)
+            double *s_en = s_sc + W * NJ * 6;                // [W][NJ][6]  capsule end points of the base pose
+            double *s_tw = s_en + W * NJ * 6;                // [W][NJ][6]  joint twists [axis; point]  (2 NJ * 6 <= NVT * 6)
+            double *s_bd = s_en + W * NVT * 6;               // [W][NJ][nobs] base-pose distance of every link
+            for (int w0 = 0; w0 < H; w0 += W) {
+                const int Wc = min(W, H - w0);
+                if (w0 == 0) prep(0);
+                for (int e = tid; e < Wc * NJ; e += FT) {
+                    const int m = e % NJ, wi = e / NJ;
+                    double x = s_x[(w0 + wi) * NS + m];
+                    x = x - rb->th_off[m];                   // dist_arm_3D_200i_2.m:11
+                    double sn, cs;
+                    sincos(x, &sn, &cs);
+                    s_sc[e * 2] = sn;
+                    s_sc[e * 2 + 1] = cs;
+                }
+                __syncthreads();
+                for (int wi = tid; wi < Wc; wi += FT) arm_chain(rb, NJ, s_sc + wi * NJ * 2, s_en + wi * NJ * 6, s_tw + wi * NJ * 6);
+                if (w0 == 0) prep(1);
+                __syncthreads();
+                STAMP(10);                                  // 10: sincos + the chain
+                for (int e = tid; e < NJ * Wc * nseg; e += FT) {
+                    const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
+                    s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, s_ob + j * 6);
+                }
+                if (w0 == 0) prep(2);
+                __syncthreads();
+                STAMP(0);                                   // 0: base distances
+                for (int e = tid; e < Wc * nseg; e += FT) {
+                    const int j = e % nseg, wi = e / nseg;
+                    double m0 = INFINITY;
+                    int lk = 0;
+#pragma unroll
+                    for (int k1 = 1; k1 <= NJ; ++k1) { const double bk = s_bd[(wi * NJ + k1 - 1) * nseg + j]; if (bk < m0) { m0 = bk; lk = k1; } }   // first minimum wins (dist_arm_3D_200i_2.m:25)
+                    if (P.dump_linkid && launched == 0) P.dump_linkid[((size_t)b * nobs + j) * H + w0 + wi] = lk;
+                    s_rhs[j * H + w0 + wi] = m0;
+                    double *g = s_g + (j * H + w0 + wi) * NJ;
+                    if (lk > 0) winner_grad(s_en + (wi * NJ + lk - 1) * 6, s_tw + wi * NJ * 6, lk - 1, NJ, s_ob + j * 6, g);
+                    else for (int m = 0; m < NJ; ++m) g[m] = 0.0;
+                }
+                if (w0 == 0) { prep(3); prepped = true; }
+                // (the next tile's first phase only writes its sin / cos table, which this one no longer reads)
+                if (w0 + W >= H) __syncthreads();
+                STAMP(11);                                  // 11: minima and the tangent sweeps of the winning links
+            }
+        }
+#else
         if (nseg > 0) {
             const int W = P.lin_w;
             double *s_sc = lds + L.lin;                      // [W][NJ][3][2] sin, cos of theta, theta+eps/2, theta-eps/2 (minus the joint offset)
@@ -756,6 +820,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                 if (w0 + W >= H) __syncthreads();
             }
         }
+#endif
         if (!prepped && P.piece != 1) {                     // nothing to ride on (mesh obstacles only, or the QP piece): four phases of their own
             prep(0); __syncthreads(); prep(1); __syncthreads(); prep(2); __syncthreads(); prep(3); __syncthreads();
         }
@@ -1516,7 +1581,7 @@ hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s)
 {
     // the function attribute is per device (handles may live on several GPUs of one process: cfs_set_device)
     static std::atomic<unsigned long long> attr_set{0ull};
-    auto kern = cfs_solve_fused_kernel<NJ, QB, IDENT>;
+    auto kern = CFS_FUSED_KERNEL<NJ, QB, IDENT>;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;

@@ -1,5 +1,6 @@
-// cfs_geom.hip -- plain dist_arm (cfs_dist_arm, RRT feasibility) and the dense Ainq / binq writer.  The linearisation
-// itself (distance + literal central-difference Jacobian) lives in cfs_fused.hip, where the solver runs it.
+// cfs_geom.hip -- plain dist_arm (cfs_dist_arm, RRT feasibility), dist_arm with its analytic gradient (cfs_dist_arm_grad)
+// and the dense Ainq / binq writer.  The linearisation itself (distance + literal central-difference Jacobian, or the
+// analytic one) lives in cfs_fused.hip, where the solver runs it.
 //
 // Reference behaviour restated (not translated):
 //   Lib/functions/CapPos.m:8-22, Lib/2L/CapPos2.m:1-31        forward kinematics
@@ -50,6 +51,40 @@ __global__ __launch_bounds__(256) void cfs_dist_arm_kernel(DistArmParams P)
         }
         P.d[(size_t)n * P.nobs + j] = d;
         if (P.linkid) P.linkid[(size_t)n * P.nobs + j] = lid;
+    }
+}
+
+// dist_arm with the analytic gradient (API entry cfs_dist_arm_grad): one thread per configuration, the same chain
+// (arm_chain) and winner tangent (winner_grad) as the solver's analytic linearisation phase (cfs_fused.hip, CFS_JAC)
+__global__ __launch_bounds__(256) void cfs_dist_arm_grad_kernel(DistArmParams P)
+{
+    __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
+    {
+        const double *src = reinterpret_cast<const double *>(P.rb);
+        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += blockDim.x) s_rb[e] = src[e];
+    }
+    __syncthreads();
+    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= P.N) return;
+    double sc[CFS_MAX_LINKS * 2], ends[CFS_MAX_LINKS * 6], tw[CFS_MAX_LINKS * 6];
+    for (int k = 0; k < P.nj; ++k) sincos(P.theta[(size_t)n * P.nj + k] - rb->th_off[k], &sc[2 * k], &sc[2 * k + 1]);
+    arm_chain(rb, P.nj, sc, ends, tw);
+    for (int j = 0; j < P.nobs; ++j) {
+        double o6[6];
+        for (int q = 0; q < 6; ++q) o6[q] = P.obs[j * 6 + q];
+        double d = INFINITY;
+        int lid = 0;
+        for (int k = 0; k < P.nj; ++k) {
+            const double dis = seg_seg_dist(ends + k * 6, o6);
+            if (dis < d) { d = dis; lid = k + 1; }       // first minimum wins (dist_arm_3D_200i_2.m:25)
+        }
+        const size_t o = (size_t)n * P.nobs + j;
+        P.d[o] = d;
+        P.linkid[o] = lid;
+        double *g = P.grad + o * P.nj;
+        if (lid > 0) winner_grad(ends + (lid - 1) * 6, tw, lid - 1, P.nj, o6, g);
+        else for (int m = 0; m < P.nj; ++m) g[m] = 0.0;
     }
 }
 
@@ -166,6 +201,12 @@ void launch_dist_arm(const DistArmParams &p, hipStream_t s)
 {
     const dim3 grid((p.N + 255) / 256), block(256);
     hipLaunchKernelGGL(cfs_dist_arm_kernel, grid, block, 0, s, p);
+}
+
+void launch_dist_arm_grad(const DistArmParams &p, hipStream_t s)
+{
+    const dim3 grid((p.N + 255) / 256), block(256);
+    hipLaunchKernelGGL(cfs_dist_arm_grad_kernel, grid, block, 0, s, p);
 }
 
 void launch_order(const OrderParams &p, hipStream_t s)

@@ -49,17 +49,27 @@ def obs_meshes(obs):
     return [o["mesh"] for o in obs if "mesh" in o]
 
 
+def _jacobian_code(jacobian):
+    if not isinstance(jacobian, str) or jacobian not in _lib.JACOBIAN:
+        raise ValueError(f"jacobian must be one of {sorted(_lib.JACOBIAN)}, not {jacobian!r}")
+    return _lib.JACOBIAN[jacobian]
+
+
 class CFSBatch:
     """A problem family (robot, horizon, cost matrix, limits, obstacle count and margins) on one GPU,
     solving batches of problems that differ in start/goal (x_init, xR1, ff, caug), obstacles and noise."""
 
-    def __init__(self, sys_info, nobs, margin, mode="CFS", max_batch=1, device=None, check_dynamics=True, use_weights="auto"):
-        """use_weights: True -> cfs_problem_create_from_weights(sys_info.weights) (the library assembles QQ, Qaug and alpha
+    def __init__(self, sys_info, nobs, margin, mode="CFS", max_batch=1, device=None, check_dynamics=True, use_weights="auto",
+                 jacobian="fd_literal"):
+        """jacobian: "fd_literal" (num_jac.m literally, the default) | "analytic" (the exact derivative of the active branch of
+        dist_arm; include/cfs_hip.h, cfs_problem_set_jacobian).
+        use_weights: True -> cfs_problem_create_from_weights(sys_info.weights) (the library assembles QQ, Qaug and alpha
         itself: neither crosses the boundary); False -> cfs_problem_create(sys_info.QQ, ...); "auto" -> the weights path, but
         only if the QQ the library assembles from sys_info.weights IS sys_info.QQ (to 1e-12 of its largest entry; checked
         with cfs_problem_family) and alpha agrees; a sys_info whose QQ / Baug were edited after build_sys_info is solved
         through the dense path with the dynamics check, exactly as given."""
         s = sys_info
+        _jacobian_code(jacobian)                         # validated before anything touches the device
         self.mode = mode
         self.H, self.nj = int(s.H), int(s.njoint)
         self.ns, self.nn, self.nx = 2 * self.nj, self.H * self.nj, self.H * 2 * self.nj
@@ -113,11 +123,23 @@ class CFSBatch:
                 # the caller's matrices are not the ones its weights assemble: solve what was given, through the dense path
                 self.close()
                 CFSBatch.__init__(self, sys_info, nobs, margin, mode=mode, max_batch=max_batch, device=device,
-                                  check_dynamics=check_dynamics_asked, use_weights=False)
+                                  check_dynamics=check_dynamics_asked, use_weights=False, jacobian=jacobian)
                 return
         else:
             _lib.check(lib.cfs_problem_create(C.byref(d), C.byref(h)))
             self._h = h
+        if jacobian != "fd_literal":
+            self.set_jacobian(jacobian)
+
+    def set_jacobian(self, jacobian):
+        """linearisation of the line obstacles for the following solves and pieces: "fd_literal" | "analytic"."""
+        _lib.check(self._lib.cfs_problem_set_jacobian(self._h, _jacobian_code(jacobian)))
+
+    @property
+    def jacobian(self):
+        m = C.c_int(0)
+        _lib.check(self._lib.cfs_problem_get_jacobian(self._h, C.byref(m)))
+        return {v: k for k, v in _lib.JACOBIAN.items()}[m.value]
 
     def _weights_match(self, s):
         """does the QQ (and alpha) the library assembled from sys_info.weights equal what sys_info carries?"""
@@ -394,9 +416,10 @@ class CFSBatch:
         return u, lam, it, st
 
 
-def dist_arm(robot, theta, obs_l, want_pos=False):
+def dist_arm(robot, theta, obs_l, want_pos=False, want_grad=False):
     """[d, linkid] = dist_arm_*(theta, base, obs_l, robot) for N configurations x nobs obstacle axes
-    (theta: (N, nj); obs_l: (nobs, 6))."""
+    (theta: (N, nj); obs_l: (nobs, 6)).  want_grad: also grad (N, nobs, nj), the analytic derivative of d with respect to
+    theta (cfs_dist_arm_grad; d and linkid are the same numbers).  Returns (d, linkid[, pos][, grad])."""
     theta, obs_l = _f64(np.atleast_2d(theta)), _f64(np.atleast_2d(obs_l))
     N, nj = theta.shape
     nobs = obs_l.shape[0]
@@ -404,6 +427,12 @@ def dist_arm(robot, theta, obs_l, want_pos=False):
     lid = np.zeros((N, nobs), np.int32)
     pos = np.zeros((N, nj, 2, 3)) if want_pos else None
     rb = to_c_robot(robot)
+    if want_grad:
+        grad = np.zeros((N, nobs, nj))
+        _lib.check(_lib.lib().cfs_dist_arm_grad(C.byref(rb), nj, N, _ptr(theta), nobs, _ptr(obs_l), _ptr(d), _ptr(lid), _ptr(grad)))
+        if want_pos:
+            _lib.check(_lib.lib().cfs_dist_arm(C.byref(rb), nj, N, _ptr(theta), nobs, _ptr(obs_l), _ptr(d), _ptr(lid), _ptr(pos)))
+        return (d, lid, pos, grad) if want_pos else (d, lid, grad)
     _lib.check(_lib.lib().cfs_dist_arm(C.byref(rb), nj, N, _ptr(theta), nobs, _ptr(obs_l), _ptr(d), _ptr(lid), _ptr(pos)))
     return (d, lid, pos) if want_pos else (d, lid)
 
@@ -468,7 +497,9 @@ class _SolverBase:
     MODE = "CFS"
     MARGIN_KEY = "epsilon"
 
-    def __init__(self, obs, sys_info, ROBOT="M16iB", device=None):
+    def __init__(self, obs, sys_info, ROBOT="M16iB", device=None, jacobian="fd_literal"):
+        """jacobian: "fd_literal" (num_jac.m, the default) | "analytic" (CFSBatch)."""
+        _jacobian_code(jacobian)
         self.obs, self.sys_info, self.ROBOT = obs, sys_info, ROBOT
         if getattr(sys_info.robot, "name", ROBOT) != ROBOT:
             raise ValueError(f"sys_info.robot is {sys_info.robot.name!r} but ROBOT={ROBOT!r}")
@@ -479,7 +510,7 @@ class _SolverBase:
         self.eval = EVAL(sys_info)
         self.iter_O, self.total_iter, self.status = 1, 0, None
         self._batch = CFSBatch(sys_info, len(obs), [o[self.MARGIN_KEY] for o in obs], mode=self.MODE, max_batch=1,
-                               device=device)
+                               device=device, jacobian=jacobian)
         meshes = obs_meshes(obs)
         if meshes:
             self._batch.set_meshes(meshes)
