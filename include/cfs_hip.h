@@ -50,7 +50,9 @@ typedef enum cfs_status {
     CFS_OK_CONVERGED = 0,  /* "Converged at stepN"  (Lib/EVAL.m:65-67) */
     CFS_OK_MAXITER = 1,    /* "MAX_ITER"            (Lib/EVAL.m:69-72) */
     CFS_QP_INFEASIBLE = 2, /* the linearised constraints of some outer iteration are infeasible */
-    CFS_NUMERIC = 3        /* the active-set solver gave up (iteration cap / breakdown)      */
+    CFS_NUMERIC = 3,       /* the active-set solver gave up (iteration cap / breakdown)      */
+    CFS_SOFT_ENDED = 4     /* CFS_INFEAS_SOFTEN handles only: the outer loop ended (stop test or MAX_O_ITER) on a softened
+                              QP; x_ violates the linearised clearance by viol_all[last] (cfs_soft_results) */
 } cfs_status;
 
 /* which dist_arm_* the class constructor selects (Lib/CFS_FANUC.m:49-54) */
@@ -277,6 +279,37 @@ int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const 
 typedef enum cfs_jacobian_mode { CFS_JAC_FD_LITERAL = 0, CFS_JAC_ANALYTIC = 1 } cfs_jacobian_mode;
 int cfs_problem_set_jacobian(cfs_problem *p, int mode);
 int cfs_problem_get_jacobian(const cfs_problem *p, int *mode);
+
+/* ---- infeasible-QP policy -----------------------------------------------------------------------
+ * What an outer iteration does when its linearised QP is proven infeasible.  The reference ignores quadprog's exitflag and
+ * carries on from whatever iterate interior-point-convex returns (Lib/CFS_FANUC.m:85-92, Lib/PSGCFS_FANUC.m:116-127).
+ *   CFS_INFEAS_STOP (default): status CFS_QP_INFEASIBLE, the solve of that problem ends (bit for bit the behaviour without
+ *     a policy).
+ *   CFS_INFEAS_SOFTEN: the same outer iteration solves the soft-constraint QP in its place,
+ *       min 1/2 u'Gu + g'u + (weight/2) sum_r s_r^2   s.t.  a_r'u - s_r <= b_r (collision rows), velocity and input rows hard,
+ *     with G, g the hard QP's own terms (QQ, ff for CFS; I, -u_ for the PSGCFS projection), and continues from its u exactly
+ *     as from a hard one (rollout, get_cost without the penalty, store_result, stop test).  Only a QP that is proven
+ *     infeasible is softened; a feasible one is solved as with STOP, bit for bit.  The soft QP is strictly convex, its slacks
+ *     are s_r = lambda_r / weight >= 0.  Should it be infeasible too (the velocity and input rows alone are; never with
+ *     v0 = 0), the status is CFS_QP_INFEASIBLE.  A problem whose outer loop ends on a softened QP reports CFS_SOFT_ENDED;
+ *     one whose last QP was hard reports CFS_OK_CONVERGED / CFS_OK_MAXITER as usual.
+ *     weight: cost units per m^2 of slack, finite and > 0.  Between 1e4 and 1e6 recommended: the max slack is then within
+ *     1e-3 m of the least violation possible; above ~1e8 the soft QP's dual becomes nearly singular (its complementarity
+ *     residual grows with the weight) and the outer loop may stall at MAX_O_ITER.
+ * cfs_qp on a SOFTEN handle runs the same two stages: status 0 for a hard solution, CFS_SOFT_ENDED for a soft one, 2 when
+ * even the soft QP is infeasible; lambda holds the multipliers of the QP that produced u (slacks: lambda / weight).
+ * The policy applies to later solves and pieces of the handle (set it between solves).  NULL handle, unknown policy or a weight
+ * that is not finite and > 0 (with either policy; STOP does not use it): CFS_ERR_INVALID_ARG, nothing changes.  Mesh obstacles are not supported in soft mode: SOFTEN on
+ * a handle with meshes, or cfs_problem_set_meshes (nmesh > 0) on a SOFTEN handle, gives CFS_ERR_INVALID_ARG.  CHOMP is not
+ * affected. */
+typedef enum cfs_infeasible_policy { CFS_INFEAS_STOP = 0, CFS_INFEAS_SOFTEN = 1 } cfs_infeasible_policy;
+int cfs_problem_set_infeasible_policy(cfs_problem *p, int policy, double weight);
+/* policy and weight as last set (CFS_INFEAS_STOP and 0 on a handle where the policy was never set) */
+int cfs_problem_get_infeasible_policy(const cfs_problem *p, int *policy, double *weight);
+/* Results of the handle's last whole solve (cfs_solve_batch or cfs_solve_batch_device; synchronises the device), host pointers:
+ * viol_all: B x MAX_O_ITER, the largest slack max_r s_r of each outer iteration's QP (0 for a hard QP and after the last
+ * iteration); n_soft: B, the number of softened outer iterations.  All zero after a solve with STOP.  Either may be NULL. */
+int cfs_soft_results(cfs_problem *p, int B, double *viol_all, int *n_soft);
 
 /* ---- mesh obstacles -----------------------------------------------------
  * The reference measures the arm against a surface with `[dis, points] = point2surface_dis(pos{i}.p, obs)`

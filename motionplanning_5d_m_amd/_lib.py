@@ -27,10 +27,11 @@ CFS_MAX_H = 64
 CFS_SUCCESS = 0
 ERRORS = {-1: "CFS_ERR_INVALID_ARG", -2: "CFS_ERR_NO_DEVICE", -3: "CFS_ERR_HIP", -4: "CFS_ERR_NOT_SPD",
           -5: "CFS_ERR_DYNAMICS", -6: "CFS_ERR_ALLOC"}
-STATUS = {0: "OK_CONVERGED", 1: "OK_MAXITER", 2: "QP_INFEASIBLE", 3: "NUMERIC"}
+STATUS = {0: "OK_CONVERGED", 1: "OK_MAXITER", 2: "QP_INFEASIBLE", 3: "NUMERIC", 4: "SOFT_ENDED"}
 ROBOT_KIND = {"M16iB": 0, "M200i": 1, "2L": 2}
 MODE = {"CFS": 0, "PSGCFS": 1}
 JACOBIAN = {"fd_literal": 0, "analytic": 1}   # cfs_jacobian_mode
+INFEASIBLE = {"stop": 0, "soften": 1}          # cfs_infeasible_policy
 
 
 class CfsError(RuntimeError):
@@ -194,6 +195,9 @@ SYMBOLS = [
     ("cfs_debug_read_u_log", C.c_int, [_P, C.c_int, _P]),
     ("cfs_problem_set_jacobian", C.c_int, [_P, C.c_int]),
     ("cfs_problem_get_jacobian", C.c_int, [_P, C.POINTER(C.c_int)]),
+    ("cfs_problem_set_infeasible_policy", C.c_int, [_P, C.c_int, C.c_double]),
+    ("cfs_problem_get_infeasible_policy", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    ("cfs_soft_results", C.c_int, [_P, C.c_int, _P, _P]),
     ("cfs_dist_arm_grad", C.c_int, [C.POINTER(cfs_robot), C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
 ]
 

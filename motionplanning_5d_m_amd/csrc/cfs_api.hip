@@ -198,6 +198,10 @@ struct cfs_problem {
     int trace_b = -1, trace_cap = 0;
     DevBuf<double> u_log;                 // max_batch x MAX_O_ITER x nn: u after every outer iteration (both solvers)
     int jac = CFS_JAC_FD_LITERAL;         // cfs_problem_set_jacobian: which linearisation every later launch of this handle runs
+    int infeas = CFS_INFEAS_STOP;         // cfs_problem_set_infeasible_policy
+    double soft_weight = 0.0;             // mu of CFS_INFEAS_SOFTEN (0: never set)
+    DevBuf<double> soft_viol;             // max_batch x MAX_O_ITER: viol_all of the last whole solve (allocated with SOFTEN)
+    DevBuf<int> soft_n;                   // max_batch: n_soft of the last whole solve
     bool prof = false;
     std::vector<hipEvent_t> ev;   // 4 per profiled solve: gemm start/stop, fused start/stop
     std::vector<hipEvent_t> ev_free;   // recycled events: none is created inside a timed region once the pool is warm
@@ -215,7 +219,7 @@ struct cfs_problem {
         linkid.release(); pool_flag.release(); meshes_d.release(); st_cost.release(); st_done.release();
         m_ends.release(); m_base.release(); m_shift.release(); m_tri.release(); m_near.release(); m_upper.release();
         m_pd.release(); m_pnd.release(); m_pi.release();
-        stamps.release(); trace.release(); u_log.release();
+        stamps.release(); trace.release(); u_log.release(); soft_viol.release(); soft_n.release();
     }
 };
 
@@ -234,9 +238,15 @@ void cfs_build_dev_robot(const cfs_robot &r, DevRobot &d) { build_dev_robot(r, d
 // 3.6 -> 2.3 ms per solve with w2s, CFS 5.8 -> 5.6 ms with w2m (its infeasibility proofs run active sets of ~100 rows).
 // w2s is compiled for the identity Hessian only (PSGCFS), w2m for QQ only (CFS), w1 for both; force_w1: CFS_DBG_TIER_W1.
 bool fused_fits(int nj, int H, int nobs) { return fused_fits_w1(nj, H, nobs); }
-hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1, bool analytic)
+hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1, bool analytic, const SoftParams *soft)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
+    if (soft) {
+        const SoftParams &sp = *soft;
+        if (!force_w1 && ident && fused_fits_w2s(nj, p.H, p.nobs)) return analytic ? launch_fused_w2sas(nj, p, s, sp) : launch_fused_w2ss(nj, p, s, sp);
+        if (!force_w1 && !ident && fused_fits_w2m(nj, p.H, p.nobs)) return analytic ? launch_fused_w2mas(nj, p, s, sp) : launch_fused_w2ms(nj, p, s, sp);
+        return analytic ? launch_fused_w1as(nj, p, s, sp) : launch_fused_w1s(nj, p, s, sp);
+    }
     if (!force_w1 && ident && fused_fits_w2s(nj, p.H, p.nobs)) return analytic ? launch_fused_w2sa(nj, p, s) : launch_fused_w2s(nj, p, s);
     if (!force_w1 && !ident && fused_fits_w2m(nj, p.H, p.nobs)) return analytic ? launch_fused_w2ma(nj, p, s) : launch_fused_w2m(nj, p, s);
     return analytic ? launch_fused_w1a(nj, p, s) : launch_fused_w1(nj, p, s);
@@ -595,6 +605,15 @@ static void fill_fused_family(const cfs_problem *p, FusedParams &fp, int B)
 }
 static bool force_w1(const cfs_problem *p) { return (p->dbg_mask & CFS_DBG_TIER_W1) != 0; }
 static bool analytic(const cfs_problem *p) { return p->jac == CFS_JAC_ANALYTIC; }
+// the soft kernels' parameters for a SOFTEN handle (null: STOP, the default kernels); whole: record viol_all / n_soft
+static const SoftParams *soft_params(const cfs_problem *p, SoftParams &sp, bool whole)
+{
+    if (p->infeas != CFS_INFEAS_SOFTEN) return nullptr;
+    sp.inv_weight = 1.0 / p->soft_weight;
+    sp.viol = whole ? p->soft_viol.p : nullptr;
+    sp.n_soft = whole ? p->soft_n.p : nullptr;
+    return &sp;
+}
 
 int cfs_set_launch_order(cfs_problem *p, const int *order, int n)
 {
@@ -680,9 +699,15 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
         launch_order(op, s);
         fp.order = p->order.p;
     }
+    SoftParams sp;
+    const SoftParams *soft = soft_params(p, sp, true);
+    if (p->soft_viol.p) {                // viol_all / n_soft of this solve (zero beyond each problem's last iteration; all zero under STOP)
+        HIPCHK(hipMemsetAsync(p->soft_viol.p, 0, (size_t)B * std::max(K, 1) * sizeof(double), s));
+        HIPCHK(hipMemsetAsync(p->soft_n.p, 0, (size_t)B * sizeof(int), s));
+    }
     if (p->prof) HIPCHK(hipEventRecord(e4[2], s));   // after the launch-order pre-pass: [e4[2], e4[3]] brackets the fused kernel alone (mesh handles: the loop of launches)
     if (p->nmesh == 0) {
-        HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p)));
+        HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), soft));
     } else {
         // Mesh obstacles are linearised by their own kernel (hierarchy traversals do not fit the fused kernel's register
         // budget), which needs the current iterate: one outer iteration per launch, state carried through HBM.  Every
@@ -1030,6 +1055,7 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
     if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
     if (nmesh < 0 || nmesh > p->d.nobs) return fail(CFS_ERR_INVALID_ARG, "nmesh %d outside 0..nobs=%d", nmesh, p->d.nobs);
     if (nmesh > 0 && !meshes) return fail(CFS_ERR_INVALID_ARG, "meshes is NULL");
+    if (nmesh > 0 && p->infeas == CFS_INFEAS_SOFTEN) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are not supported with CFS_INFEAS_SOFTEN");
     HIPCHK(hipSetDevice(p->device));
     std::vector<DevMesh> v(nmesh);
     for (int i = 0; i < nmesh; ++i) {
@@ -1164,6 +1190,51 @@ int cfs_problem_get_jacobian(const cfs_problem *p, int *mode)
     return CFS_SUCCESS;
 }
 
+int cfs_problem_set_infeasible_policy(cfs_problem *p, int policy, double weight)
+{
+    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (policy != CFS_INFEAS_STOP && policy != CFS_INFEAS_SOFTEN) return fail(CFS_ERR_INVALID_ARG, "unknown infeasible-QP policy %d", policy);
+    if (!std::isfinite(weight) || !(weight > 0.0)) return fail(CFS_ERR_INVALID_ARG, "soft weight %g is not finite and > 0", weight);
+    if (policy == CFS_INFEAS_SOFTEN && p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are not supported with CFS_INFEAS_SOFTEN");
+    if (policy == CFS_INFEAS_SOFTEN && !p->soft_viol.p) {   // handle-owned result buffers, from the first SOFTEN on
+        HIPCHK(hipSetDevice(p->device));
+        const size_t nv = (size_t)p->d.max_batch * std::max(p->d.MAX_O_ITER, 1);
+        hipError_t e = p->soft_viol.alloc(nv);
+        if (e == hipSuccess) e = p->soft_n.alloc(p->d.max_batch);
+        if (e == hipSuccess) e = hipMemset(p->soft_viol.p, 0, nv * sizeof(double));
+        if (e == hipSuccess) e = hipMemset(p->soft_n.p, 0, (size_t)p->d.max_batch * sizeof(int));
+        if (e != hipSuccess) { p->soft_viol.release(); p->soft_n.release(); return fail(CFS_ERR_HIP, "soft result buffers: %s", hipGetErrorString(e)); }
+    }
+    p->soft_weight = weight;
+    p->infeas = policy;
+    return CFS_SUCCESS;
+}
+
+int cfs_problem_get_infeasible_policy(const cfs_problem *p, int *policy, double *weight)
+{
+    if (!p || !policy || !weight) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    *policy = p->infeas;
+    *weight = p->soft_weight;
+    return CFS_SUCCESS;
+}
+
+int cfs_soft_results(cfs_problem *p, int B, double *viol_all, int *n_soft)
+{
+    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
+    const size_t nv = (size_t)B * p->d.MAX_O_ITER;
+    if (!p->soft_viol.p) {               // never softened: nothing was
+        if (viol_all) memset(viol_all, 0, nv * sizeof(double));
+        if (n_soft) memset(n_soft, 0, (size_t)B * sizeof(int));
+        return CFS_SUCCESS;
+    }
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipDeviceSynchronize());      // the last solve may have been enqueued on any stream
+    if (viol_all && nv) HIPCHK(hipMemcpy(viol_all, p->soft_viol.p, nv * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_soft) HIPCHK(hipMemcpy(n_soft, p->soft_n.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+    return CFS_SUCCESS;
+}
+
 static int check_batch(const cfs_problem *p, int B)
 {
     if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
@@ -1214,7 +1285,8 @@ static int linearize_piece(cfs_problem *p, int B, const PieceBuffers &pb, double
         HIPCHK(launch_linearize_mesh(nj, lm, nullptr));
         fp.nmesh = p->nmesh; fp.ext_dist = p->dist.p; fp.ext_grad = p->grad.p;
     }
-    HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p), analytic(p)));
+    SoftParams sp;
+    HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false)));
     return CFS_SUCCESS;
 }
 
@@ -1309,7 +1381,8 @@ int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const 
         launch_batched_gemv(g, nullptr);
         fp.x0 = p->x0.p;
     } else fp.x0 = d_lin;
-    HIPCHK(launch_fused(p->d.njoint, fp, nullptr, force_w1(p), analytic(p)));
+    SoftParams sp;
+    HIPCHK(launch_fused(p->d.njoint, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false)));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(nullptr));
     st.down(u, d_u, (size_t)B * nn);

@@ -151,8 +151,21 @@ bool fused_fits_w2s(int nj, int H, int nobs);
 hipError_t launch_fused_w1a(int nj, FusedParams p, hipStream_t s);
 hipError_t launch_fused_w2ma(int nj, FusedParams p, hipStream_t s);
 hipError_t launch_fused_w2sa(int nj, FusedParams p, hipStream_t s);
-// cfs_api.hip: tier by mode and capacity; analytic: the CFS_JAC_ANALYTIC kernels
-hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1 = false, bool analytic = false);
+// soft-constraint QP after a proven-infeasible one (CFS_INFEAS_SOFTEN handles): the second parameter block of the kernels built
+// with CFS_SOFT=1, the same six tiers again (same LDS layout and capacities)
+struct SoftParams {
+    double inv_weight;           // 1 / mu
+    double *viol;                // B x max_o_iter: max slack of every outer iteration's QP, 0 for a hard one (null: not recorded)
+    int *n_soft;                 // B: softened outer iterations (null: not recorded)
+};
+hipError_t launch_fused_w1s(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
+hipError_t launch_fused_w2ms(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
+hipError_t launch_fused_w2ss(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
+hipError_t launch_fused_w1as(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
+hipError_t launch_fused_w2mas(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
+hipError_t launch_fused_w2sas(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
+// cfs_api.hip: tier by mode and capacity; analytic: the CFS_JAC_ANALYTIC kernels; soft (non-null): the CFS_SOFT kernels
+hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1 = false, bool analytic = false, const SoftParams *soft = nullptr);
 bool fused_fits(int nj, int H, int nobs);
 
 struct CostHistParams {          // EVAL.get_cost / store_result for a logged u history (CFS mode)

@@ -13,6 +13,8 @@
 //   * linearisation (FK variants, segment pairs, literal num_jac) as in cfs_geom.hip, tiled over
 //     waypoints, scratch aliased with the QP's Y storage; objects built with CFS_JAC=1 run the analytic
 //     Jacobian instead (one chain per waypoint, one tangent sweep of the winning link: cfs_geom_dev.h);
+//   * objects built with CFS_SOFT=1 (CFS_INFEAS_SOFTEN handles) follow a QP that is proven infeasible with the
+//     soft-constraint QP of the same linearisation: 1/mu on the Gram diagonal of the collision rows;
 //   * QP: Goldfarb-Idnani dual active set in range-space form.  The inverse Gram matrix
 //     P = (N'H^{-1}N)^{-1} is kept EXPLICITLY, one row per thread in registers (it is symmetric,
 //     so column access is never needed); adding a constraint is a bordered rank-1 update,
@@ -62,10 +64,28 @@ constexpr int CERT_AT = CFS_CERT_AT;    // main-loop steps of a QP before the st
 #ifndef CFS_JAC
 #define CFS_JAC 0                        // 1: analytic Jacobian (CFS_JAC_ANALYTIC handles): a kernel of its own name, objects of their own
 #endif
-#if CFS_JAC
+#ifndef CFS_SOFT
+#define CFS_SOFT 0                       // 1: soft-constraint QP after a proven-infeasible one (CFS_INFEAS_SOFTEN handles): kernels of their own name, objects of their own
+#endif
+#if CFS_SOFT && CFS_JAC
+#define CFS_FUSED_KERNEL cfs_solve_fused_analytic_soft_kernel
+#elif CFS_SOFT
+#define CFS_FUSED_KERNEL cfs_solve_fused_soft_kernel
+#elif CFS_JAC
 #define CFS_FUSED_KERNEL cfs_solve_fused_analytic_kernel
 #else
 #define CFS_FUSED_KERNEL cfs_solve_fused_kernel
+#endif
+#if CFS_SOFT
+#define CFS_SOFT_KPARAM , SoftParams S           /* the soft kernels take a second parameter block */
+#define CFS_SOFT_LPARAM , const SoftParams &sp
+#define CFS_SOFT_ARG , sp
+#define IF_HARD(c) (!soft && (c))                /* proofs that hold for the hard QP only */
+#else
+#define CFS_SOFT_KPARAM
+#define CFS_SOFT_LPARAM
+#define CFS_SOFT_ARG
+#define IF_HARD(c) (c)
 #endif
 #define CFS_CAT2(a, b) a##_##b
 #define CFS_CAT(a, b) CFS_CAT2(a, b)
@@ -463,7 +483,7 @@ __host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int
 
 // ------------------------------------------------------------------------------------------------
 template <int NJ, int QB, bool IDENT>      // IDENT: the QP Hessian is the identity (PSGCFS projection)
-__global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParams P)
+__global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParams P CFS_SOFT_KPARAM)
 {
     constexpr int NS = 2 * NJ, NVT = nvt(NJ), NE = 2 * NJ + 1;
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -569,6 +589,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
     double cost_new = P.caug[b], cost_old = 100000.0;      // get_cost(zeros) = caug; EVAL.m:29
     int iter_O = 1, total_iter = 0, noise_row = 0, status = CFS_OK_MAXITER;
     bool done = false;
+#if CFS_SOFT
+    const double iw = S.inv_weight;                        // 1/mu: the soft QP's Gram diagonal of a collision row grows by it
+    int n_soft = 0;
+    bool last_soft = false;                                // the last QP solved was a soft one (CFS_SOFT_ENDED)
+#endif
     const int nseg = nobs - P.nmesh;                       // obstacles [nseg, nobs) are meshes, linearised by cfs_mesh.hip
     int launched = 0;
     if (P.resume) {                                        // continue a solve that is driven one outer iteration per launch
@@ -965,6 +990,10 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                 wb[k] = w0; wb[HN + k] = w1; wb[2 * HN + k] = w2;
             }
         };
+#if CFS_SOFT
+        bool soft = false;                                  // this iteration's hard QP was proven infeasible: solving the soft one
+        double viol = 0.0;                                  // max slack max_r lambda_r / mu of the soft QP (0: hard)
+#endif
         if (!skip) {
             // rhs = (d - margin) - Diff'*Bj(1:nj,:)*u   (CFS_FANUC.m:119-120), with Bpos*u from the rollout of u (s_up)
             for (int e = tid; e < ncon; e += FT) { s_flag[e] = 0; s_slot[e] = 0; }
@@ -1078,6 +1107,25 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                 return block_sum((double)hit, red, tid) > 0.0;     // (no __syncthreads_or: it would add static LDS to a kernel sized to the byte)
             };
             STAMP(1);                                       // 1: QP setup
+#if CFS_SOFT
+          // Soft-constraint QP (CFS_INFEAS_SOFTEN).  Only after the hard QP is PROVEN infeasible: min 1/2 u'Gu + g'u + mu/2 |s|^2
+          // s.t. a_r'u - s_r <= b_r on the collision rows, the velocity and input rows hard.  In (u, s) a collision row has the
+          // normal (a_r, -e_r) and the Hessian is blkdiag(G, mu I): every Gram product is the hard one plus 1/mu on the diagonal
+          // of a collision row, and s_r = lambda_r / mu.  Inactive rows have s = 0, so the scan for the most violated row is the
+          // hard one.  Cold start, no objective bound, no step-free certificate (both are proofs about the hard QP).
+          int iters_hard = 0;
+          for (;;) {
+            if (soft) {
+                iters_hard = iters; iters = 0;
+                __syncthreads();
+                for (int e = tid; e < ncon; e += FT) { s_flag[e] = 0; s_slot[e] = 0; }
+                Pr.zero(s_pt, tid, 0);
+                if (tid < QB) { s_d[tid] = 0.0; s_r[tid] = 0.0; s_rho[tid] = 0.0; s_prow[tid] = 0.0; s_lam[tid] = 0.0; s_act[tid] = -1; }
+                qhi = 0; nfree = 0; npolish = 0; qp_status = QP_OK; fgain = 0.0;
+                __syncthreads();
+                prep(0); __syncthreads(); prep(1); __syncthreads(); prep(2); __syncthreads(); prep(3); __syncthreads();
+            }
+#endif
             // ---- warm start (H = I): begin at the S-pair of the previous outer iteration's active rows ------------------------
             // Consecutive outer iterations linearise nearly the same trajectory, so the optimal active set barely changes (the
             // long problems of config 3: 8-12 rows, 80-100 % kept), yet a cold dual active set re-adds every row one full step
@@ -1085,7 +1133,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
             // multipliers are >= 0): build P for the previous rows -- Gram products only, wavefront 0 alone, no scan, no combine,
             // no block barrier --, take lambda = -P s(x0), drop rows with lambda <= 0 until none is left, set x = x0 + N lambda.
             // The optimum is the same (strictly convex QP); what changes is the number of steps.
-            if (P.piece == 0 && !(P.opt & 8) && prev_q > 0 && prev_q <= min(64, P.warm_max > 0 ? P.warm_max : min(PR, IDENT ? 64 : 24))) {
+            if (IF_HARD(P.piece == 0) && !(P.opt & 8) && prev_q > 0 && prev_q <= min(64, P.warm_max > 0 ? P.warm_max : min(PR, IDENT ? 64 : 24))) {
                 int *pub = reinterpret_cast<int *>(red_base + 62);
                 int q = 0;                                   // H = QQ: tracked by every thread (one barrier per row); H = I: by wavefront 0
                 for (int s0 = 0; s0 < (IDENT ? 1 : prev_q); ++s0) {
@@ -1201,8 +1249,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
             STAMP(3);                                       // 3: warm start (H = I) | w gather + rollout (H = QQ, inside the steps)
             int nloop = 0;
             for (;;) {
-                if (fgain > fbound) { qp_status = QP_INFEASIBLE; break; }
-                if (cert_on && nloop == CERT_AT && certificate()) { qp_status = QP_INFEASIBLE; break; }
+                if (IF_HARD(fgain > fbound)) { qp_status = QP_INFEASIBLE; break; }
+                if (IF_HARD(cert_on) && nloop == CERT_AT && certificate()) { qp_status = QP_INFEASIBLE; break; }
                 ++nloop;
                 // step 1: most violated constraint (constraints are strided over the threads; the codes of a
                 // thread's constraints never change, so they are decoded once per kernel -- no integer divisions here)
@@ -1245,7 +1293,15 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                     if (tid < qhi) {
                         const int ac = s_act[tid];
                         double sa = 0.0, bb = 0.0;
+#if CFS_SOFT
+                        if (ac >= 0) {                       // soft collision row: its slack includes s = lambda / mu
+                            sa = slack_of<NJ>(ac, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb);
+                            if (soft && (ac >> 16) == CT_COL) sa += iw * s_lam[tid];
+                            drift = fabs(sa) / (1.0 + fabs(bb));
+                        }
+#else
                         if (ac >= 0) { sa = slack_of<NJ>(ac, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb); drift = fabs(sa) / (1.0 + fabs(bb)); }
+#endif
                         s_prow[tid] = sa;
                     }
                     { double nd = -drift; int dm = 0; block_argmin(nd, dm, red, tid); drift = -nd; }   // block-wide maximum
@@ -1287,6 +1343,9 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                     if (tid < qhi) s_r[tid] = myact >= 0 ? Pr.dot(s_d, s_pt, tid, qhi) : 0.0;
                     __syncthreads();
                     }
+#if CFS_SOFT
+                    if (soft && !polish && ptype == CT_COL) spp += iw;   // n_p'H^{-1}n_p in (u, s); d is unchanged (p is not active)
+#endif
                     STAMP(4);                               // 4: d = N'w, r = P d
                     // z = w - Y'r, rollout, then iterative refinement against the true Gram matrix
                     double delta = 0.0, t1 = INFINITY;
@@ -1308,12 +1367,19 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                         }
                         if (polish) break;                             // zb = (x, Bvel x, Bpos x) after the projection
                         delta = ndot<NJ>(pc, zb, s_g, H);              // n_p'z
+#if CFS_SOFT
+                        if (soft && ptype == CT_COL) delta = fmax(delta, 0.0) + iw;   // + e_p's-part of z; >= 1/mu exactly (Schur complement)
+#endif
                         if (qhi == nfree) break;                       // empty active set: nothing to refine, t1 = inf
                         // one exchange carries the refinement diagnostics (r'rho, max|rho|, max|d|; rho_a = n_a'z is
                         // zero in exact arithmetic) and the dual step length t1 = min{lambda_a / r_a : r_a > 0}
                         double rr = 0.0, rmax = 0.0, dmax = 0.0, t1c = INFINITY;
                         if (tid < qhi && myact >= 0) {
+#if CFS_SOFT
+                            const double ra = (soft && (myact >> 16) == CT_COL) ? ndot<NJ>(myact, zb, s_g, H) - iw * s_r[tid] : ndot<NJ>(myact, zb, s_g, H), rv = s_r[tid];
+#else
                             const double ra = ndot<NJ>(myact, zb, s_g, H), rv = s_r[tid];
+#endif
                             s_prow[tid] = ra;
                             rr = rv * ra;
                             rmax = fabs(ra);
@@ -1358,7 +1424,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                         break;                                         // back to step 1: scan again
                     }
                     STAMP(5);                               // 5: z, rollout, refinement, dual step length
+#if CFS_SOFT
+                    const bool dependent = !(soft && ptype == CT_COL) && !(delta > DEP_TOL_F * spp);   // a soft collision row never is
+#else
                     const bool dependent = !(delta > DEP_TOL_F * spp);
+#endif
                     const double t2 = dependent ? INFINITY : -sp / delta;
                     const double t = fmin(t1, t2);
                     if (P.dbg && b == P.dbg_b && tid == 0) {
@@ -1432,12 +1502,33 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                         STAMP(8);                           // 8: drop
                     }
                     { double bb; sp = slack_of<NJ>(pc, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb); }
+#if CFS_SOFT
+                    if (soft && ptype == CT_COL) sp += iw * lam_p;   // the entering row's own slack s_p = lambda_p / mu
+#endif
                 }
                 if (qp_status != QP_OK) break;
             }
+#if CFS_SOFT
+            if (!soft && qp_status == QP_INFEASIBLE) { soft = true; continue; }
+            if (soft) {
+                iters += iters_hard;                        // total_iter counts the steps of both solves
+                if (qp_status == QP_OK) {                   // max slack = max over the active collision rows of lambda / mu
+                    double nv = 0.0;
+                    int dm = 0;
+                    if (tid < qhi) { const int ac = s_act[tid]; if (ac >= 0 && (ac >> 16) == CT_COL) nv = -(iw * s_lam[tid]); }
+                    block_argmin(nv, dm, red, tid);
+                    viol = -nv;
+                }
+            }
+            break;
+          }
+#endif
         }
         total_iter += iters;
         if (!skip) prev_q = qp_status == QP_OK ? qhi : 0;
+#if CFS_SOFT
+        if (soft) prev_q = 0;                               // the next hard QP starts cold
+#endif
         if (P.dump_lambda) {
             const int nlam = nobs * H + 4 * HN;
             __syncthreads();
@@ -1450,7 +1541,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
         }
         if (P.piece == 2) {
             for (int e = tid; e < HN; e += FT) P.u[(size_t)b * nn + e] = xs[e];
+#if CFS_SOFT
+            if (tid == 0) { P.total_iter[b] = iters; P.status[b] = qp_status == QP_OK ? (soft ? CFS_SOFT_ENDED : CFS_OK_CONVERGED) : (qp_status == QP_INFEASIBLE ? CFS_QP_INFEASIBLE : CFS_NUMERIC); }
+#else
             if (tid == 0) { P.total_iter[b] = iters; P.status[b] = qp_status == QP_OK ? CFS_OK_CONVERGED : (qp_status == QP_INFEASIBLE ? CFS_QP_INFEASIBLE : CFS_NUMERIC); }
+#endif
             drop_pool();
             return;
         }
@@ -1459,6 +1554,10 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
             done = true;
             break;
         }
+#if CFS_SOFT
+        if (!skip) { last_soft = soft; n_soft += soft ? 1 : 0; }
+        if (S.viol && tid == 0) S.viol[(size_t)b * P.max_o_iter + (iter_O - 1)] = viol;
+#endif
 
         // =========================================================================================
         // new u, rollout (CFS_FANUC.m:86-95), get_cost, store_result, iter_O++, stop_outer
@@ -1566,6 +1665,10 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
     __syncthreads();
     for (int e = tid; e < HN; e += FT) P.u[(size_t)b * nn + e] = s_u[e];
     for (int e = tid; e < NX; e += FT) P.x_[(size_t)b * NX + e] = s_x[e];
+#if CFS_SOFT
+    if (last_soft && (status == CFS_OK_CONVERGED || status == CFS_OK_MAXITER)) status = CFS_SOFT_ENDED;   // x_ violates the linearised clearance
+    if (tid == 0 && S.n_soft) S.n_soft[b] = n_soft;
+#endif
     if (tid == 0) { P.iter_O[b] = iter_O; P.total_iter[b] = total_iter; P.status[b] = status; }
     if (P.st_qu) {                                         // state for the next launch of a host-driven solve
         for (int e = tid; e < HN; e += FT) P.st_qu[(size_t)b * nn + e] = s_qu[e];
@@ -1577,7 +1680,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
 #undef red
 
 template <int NJ, int QB, bool IDENT>
-hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s)
+hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s CFS_SOFT_LPARAM)
 {
     // the function attribute is per device (handles may live on several GPUs of one process: cfs_set_device)
     static std::atomic<unsigned long long> attr_set{0ull};
@@ -1590,7 +1693,7 @@ hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s)
         if (e != hipSuccess) return e;
         if (dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_release);
     }
-    hipLaunchKernelGGL(kern, dim3(p.B), dim3(FT), lds, s, p);
+    hipLaunchKernelGGL(kern, dim3(p.B), dim3(FT), lds, s, p CFS_SOFT_ARG);
     return hipGetLastError();
 }
 
@@ -1599,14 +1702,14 @@ hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s)
 #define CFS_IDENT_SET 2
 #endif
 template <int NJ, int QB>
-hipError_t launch_fused_inst(const FusedParams &p, size_t lds, hipStream_t s)
+hipError_t launch_fused_inst(const FusedParams &p, size_t lds, hipStream_t s CFS_SOFT_LPARAM)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
 #if CFS_IDENT_SET != 0
-    if (ident) return launch_fused_inst2<NJ, QB, true>(p, lds, s);
+    if (ident) return launch_fused_inst2<NJ, QB, true>(p, lds, s CFS_SOFT_ARG);
 #endif
 #if CFS_IDENT_SET != 1
-    if (!ident) return launch_fused_inst2<NJ, QB, false>(p, lds, s);
+    if (!ident) return launch_fused_inst2<NJ, QB, false>(p, lds, s CFS_SOFT_ARG);
 #endif
     return hipErrorInvalidValue;
 }
@@ -1631,7 +1734,7 @@ bool CFS_CAT(fused_fits, CFS_VARIANT)(int nj, int H, int nobs)
 }
 
 // host: choose the capacities, fill qy / lin_w, launch
-hipError_t CFS_CAT(launch_fused, CFS_VARIANT)(int nj, FusedParams p, hipStream_t s)
+hipError_t CFS_CAT(launch_fused, CFS_VARIANT)(int nj, FusedParams p, hipStream_t s CFS_SOFT_LPARAM)
 {
     const int nn = p.H * nj;
     const int QB = nn <= 96 ? 96 : (nn <= 160 ? 160 : 256);
@@ -1651,20 +1754,20 @@ hipError_t CFS_CAT(launch_fused, CFS_VARIANT)(int nj, FusedParams p, hipStream_t
     const size_t need = std::max((size_t)L.total_fixed + (size_t)qy * nn, (size_t)L.lin + (size_t)w * per_wp);
     const size_t lds = need * 8;
     switch (nj * 1000 + QB) {
-    case 2096: return launch_fused_inst<2, 96>(p, lds, s);
-    case 3096: return launch_fused_inst<3, 96>(p, lds, s);
-    case 4096: return launch_fused_inst<4, 96>(p, lds, s);
-    case 5096: return launch_fused_inst<5, 96>(p, lds, s);
-    case 6096: return launch_fused_inst<6, 96>(p, lds, s);
-    case 2160: return launch_fused_inst<2, 160>(p, lds, s);
-    case 4160: return launch_fused_inst<4, 160>(p, lds, s);
-    case 5160: return launch_fused_inst<5, 160>(p, lds, s);
-    case 6160: return launch_fused_inst<6, 160>(p, lds, s);
-    case 3160: return launch_fused_inst<3, 160>(p, lds, s);
-    case 3256: return launch_fused_inst<3, 256>(p, lds, s);
-    case 4256: return launch_fused_inst<4, 256>(p, lds, s);
-    case 5256: return launch_fused_inst<5, 256>(p, lds, s);
-    case 6256: return launch_fused_inst<6, 256>(p, lds, s);
+    case 2096: return launch_fused_inst<2, 96>(p, lds, s CFS_SOFT_ARG);
+    case 3096: return launch_fused_inst<3, 96>(p, lds, s CFS_SOFT_ARG);
+    case 4096: return launch_fused_inst<4, 96>(p, lds, s CFS_SOFT_ARG);
+    case 5096: return launch_fused_inst<5, 96>(p, lds, s CFS_SOFT_ARG);
+    case 6096: return launch_fused_inst<6, 96>(p, lds, s CFS_SOFT_ARG);
+    case 2160: return launch_fused_inst<2, 160>(p, lds, s CFS_SOFT_ARG);
+    case 4160: return launch_fused_inst<4, 160>(p, lds, s CFS_SOFT_ARG);
+    case 5160: return launch_fused_inst<5, 160>(p, lds, s CFS_SOFT_ARG);
+    case 6160: return launch_fused_inst<6, 160>(p, lds, s CFS_SOFT_ARG);
+    case 3160: return launch_fused_inst<3, 160>(p, lds, s CFS_SOFT_ARG);
+    case 3256: return launch_fused_inst<3, 256>(p, lds, s CFS_SOFT_ARG);
+    case 4256: return launch_fused_inst<4, 256>(p, lds, s CFS_SOFT_ARG);
+    case 5256: return launch_fused_inst<5, 256>(p, lds, s CFS_SOFT_ARG);
+    case 6256: return launch_fused_inst<6, 256>(p, lds, s CFS_SOFT_ARG);
     default: return hipErrorInvalidValue;
     }
 }

@@ -10,6 +10,7 @@ outer dimension: stochastic seeds, RRT node pairs, start/goal/obstacle variation
 from __future__ import annotations
 
 import ctypes as C
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -55,13 +56,33 @@ def _jacobian_code(jacobian):
     return _lib.JACOBIAN[jacobian]
 
 
+def _infeasible_args(on_infeasible, soft_weight):
+    """(policy code, weight) for cfs_problem_set_infeasible_policy; ValueError for anything malformed.  "soften" needs a finite
+    soft_weight > 0; "stop" ignores a (valid) weight and passes 1.0 when there is none."""
+    if not isinstance(on_infeasible, str) or on_infeasible not in _lib.INFEASIBLE:
+        raise ValueError(f"on_infeasible must be one of {sorted(_lib.INFEASIBLE)}, not {on_infeasible!r}")
+    if soft_weight is None:
+        if on_infeasible == "soften":
+            raise ValueError('on_infeasible="soften" needs soft_weight= (cost units per m^2 of slack, finite and > 0)')
+        return _lib.INFEASIBLE[on_infeasible], 1.0
+    if isinstance(soft_weight, bool) or not isinstance(soft_weight, (int, float, np.integer, np.floating)):
+        raise ValueError(f"soft_weight must be a real number, not {soft_weight!r}")
+    w = float(soft_weight)
+    if not (math.isfinite(w) and w > 0.0):
+        raise ValueError(f"soft_weight must be finite and > 0, not {soft_weight!r}")
+    return _lib.INFEASIBLE[on_infeasible], w
+
+
 class CFSBatch:
     """A problem family (robot, horizon, cost matrix, limits, obstacle count and margins) on one GPU,
     solving batches of problems that differ in start/goal (x_init, xR1, ff, caug), obstacles and noise."""
 
     def __init__(self, sys_info, nobs, margin, mode="CFS", max_batch=1, device=None, check_dynamics=True, use_weights="auto",
-                 jacobian="fd_literal"):
-        """jacobian: "fd_literal" (num_jac.m literally, the default) | "analytic" (the exact derivative of the active branch of
+                 jacobian="fd_literal", on_infeasible="stop", soft_weight=None):
+        """on_infeasible: "stop" (the default: a proven-infeasible linearised QP ends the problem with QP_INFEASIBLE) | "soften"
+        (that outer iteration solves the soft-constraint QP with weight soft_weight instead and carries on; include/cfs_hip.h,
+        cfs_problem_set_infeasible_policy).  Results of solve() carry viol_all (B x MAX_O_ITER) and n_soft (B).
+        jacobian: "fd_literal" (num_jac.m literally, the default) | "analytic" (the exact derivative of the active branch of
         dist_arm; include/cfs_hip.h, cfs_problem_set_jacobian).
         use_weights: True -> cfs_problem_create_from_weights(sys_info.weights) (the library assembles QQ, Qaug and alpha
         itself: neither crosses the boundary); False -> cfs_problem_create(sys_info.QQ, ...); "auto" -> the weights path, but
@@ -70,6 +91,7 @@ class CFSBatch:
         through the dense path with the dynamics check, exactly as given."""
         s = sys_info
         _jacobian_code(jacobian)                         # validated before anything touches the device
+        _infeasible_args(on_infeasible, soft_weight)
         self.mode = mode
         self.H, self.nj = int(s.H), int(s.njoint)
         self.ns, self.nn, self.nx = 2 * self.nj, self.H * self.nj, self.H * 2 * self.nj
@@ -123,13 +145,35 @@ class CFSBatch:
                 # the caller's matrices are not the ones its weights assemble: solve what was given, through the dense path
                 self.close()
                 CFSBatch.__init__(self, sys_info, nobs, margin, mode=mode, max_batch=max_batch, device=device,
-                                  check_dynamics=check_dynamics_asked, use_weights=False, jacobian=jacobian)
+                                  check_dynamics=check_dynamics_asked, use_weights=False, jacobian=jacobian,
+                                  on_infeasible=on_infeasible, soft_weight=soft_weight)
                 return
         else:
             _lib.check(lib.cfs_problem_create(C.byref(d), C.byref(h)))
             self._h = h
         if jacobian != "fd_literal":
             self.set_jacobian(jacobian)
+        if on_infeasible != "stop":
+            self.set_infeasible_policy(on_infeasible, soft_weight)
+
+    def set_infeasible_policy(self, on_infeasible, soft_weight=None):
+        """what the following solves and pieces do with a proven-infeasible QP: "stop" | "soften" (with soft_weight > 0)."""
+        code, w = _infeasible_args(on_infeasible, soft_weight)
+        _lib.check(self._lib.cfs_problem_set_infeasible_policy(self._h, code, w))
+
+    @property
+    def infeasible_policy(self):
+        """(policy, soft_weight) as last set; the weight is None under "stop"."""
+        m, w = C.c_int(0), C.c_double(0.0)
+        _lib.check(self._lib.cfs_problem_get_infeasible_policy(self._h, C.byref(m), C.byref(w)))
+        name = {v: k for k, v in _lib.INFEASIBLE.items()}[m.value]
+        return name, (w.value if name == "soften" else None)
+
+    def soft_results(self, B):
+        """(viol_all (B, MAX_O_ITER), n_soft (B,)) of the last whole solve (synchronises; cfs_soft_results)."""
+        viol, ns = np.zeros((B, self.K)), np.zeros(B, np.int32)
+        _lib.check(self._lib.cfs_soft_results(self._h, B, _ptr(viol), _ptr(ns)))
+        return viol, ns
 
     def set_jacobian(self, jacobian):
         """linearisation of the line obstacles for the following solves and pieces: "fd_literal" | "analytic"."""
@@ -221,6 +265,7 @@ class CFSBatch:
         o.u, o.x_, o.cost_all, o.e_cost_all, o.e_u_all = _ptr(r.u), _ptr(r.x_), _ptr(r.cost_all), _ptr(r.e_cost_all), _ptr(r.e_u_all)
         o.iter_O, o.total_iter, o.status = _ptr(r.iter_O), _ptr(r.total_iter), _ptr(r.status)
         _lib.check(self._lib.cfs_solve_batch(self._h, C.byref(i), C.byref(o)))
+        r.viol_all, r.n_soft = self.soft_results(B)
         return r
 
     def alloc_outputs(self, B, device):
@@ -497,9 +542,13 @@ class _SolverBase:
     MODE = "CFS"
     MARGIN_KEY = "epsilon"
 
-    def __init__(self, obs, sys_info, ROBOT="M16iB", device=None, jacobian="fd_literal"):
-        """jacobian: "fd_literal" (num_jac.m, the default) | "analytic" (CFSBatch)."""
+    def __init__(self, obs, sys_info, ROBOT="M16iB", device=None, jacobian="fd_literal", on_infeasible="stop", soft_weight=None):
+        """jacobian: "fd_literal" (num_jac.m, the default) | "analytic" (CFSBatch).
+        on_infeasible: "stop" (the default) | "soften" with soft_weight= (CFSBatch); after optimizer(), viol_all and n_soft."""
         _jacobian_code(jacobian)
+        _infeasible_args(on_infeasible, soft_weight)
+        if on_infeasible == "soften" and obs_meshes(obs):
+            raise ValueError('on_infeasible="soften" does not support mesh obstacles')
         self.obs, self.sys_info, self.ROBOT = obs, sys_info, ROBOT
         if getattr(sys_info.robot, "name", ROBOT) != ROBOT:
             raise ValueError(f"sys_info.robot is {sys_info.robot.name!r} but ROBOT={ROBOT!r}")
@@ -510,7 +559,8 @@ class _SolverBase:
         self.eval = EVAL(sys_info)
         self.iter_O, self.total_iter, self.status = 1, 0, None
         self._batch = CFSBatch(sys_info, len(obs), [o[self.MARGIN_KEY] for o in obs], mode=self.MODE, max_batch=1,
-                               device=device, jacobian=jacobian)
+                               device=device, jacobian=jacobian, on_infeasible=on_infeasible, soft_weight=soft_weight)
+        self.viol_all, self.n_soft = np.zeros(0), 0
         meshes = obs_meshes(obs)
         if meshes:
             self._batch.set_meshes(meshes)
@@ -535,6 +585,7 @@ class _SolverBase:
         self.u, self.x_ = r.u[0], r.x_[0]
         self.iter_O, self.total_iter, self.status = int(r.iter_O[0]), int(r.total_iter[0]), int(r.status[0])
         self.eval.cost_all, self.eval.e_cost_all, self.eval.e_u_all = r.cost_all[0, :n], r.e_cost_all[0, :n], r.e_u_all[0, :n]
+        self.viol_all, self.n_soft = r.viol_all[0, :n], int(r.n_soft[0])
         self.eval.cost_new = float(r.cost_all[0, n - 1]) if n > 0 else float(self.sys_info.caug)
         self.eval.x_ = self.x_
         if self.status == 0:
