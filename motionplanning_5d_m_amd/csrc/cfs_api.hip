@@ -237,19 +237,19 @@ void cfs_build_dev_robot(const cfs_robot &r, DevRobot &d) { build_dev_robot(r, d
 // Tier of the fused kernel (cfs_device.h).  Two problems per CU win whenever they fit: measured on config 3, PSGCFS
 // 3.6 -> 2.3 ms per solve with w2s, CFS 5.8 -> 5.6 ms with w2m (its infeasibility proofs run active sets of ~100 rows).
 // w2s is compiled for the identity Hessian only (PSGCFS), w2m for QQ only (CFS), w1 for both; force_w1: CFS_DBG_TIER_W1.
-bool fused_fits(int nj, int H, int nobs) { return fused_fits_w1(nj, H, nobs); }
+bool fused_fits(int nj, int H, int nobs) { return fused_fits_tier<FUSED_W1>(nj, H, nobs); }
+template <FusedTier T>
+static hipError_t launch_tier(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft)
+{
+    if (soft) return analytic ? launch_fused_tier<T, true, true>(nj, p, s, soft) : launch_fused_tier<T, false, true>(nj, p, s, soft);
+    return analytic ? launch_fused_tier<T, true, false>(nj, p, s, nullptr) : launch_fused_tier<T, false, false>(nj, p, s, nullptr);
+}
 hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1, bool analytic, const SoftParams *soft)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
-    if (soft) {
-        const SoftParams &sp = *soft;
-        if (!force_w1 && ident && fused_fits_w2s(nj, p.H, p.nobs)) return analytic ? launch_fused_w2sas(nj, p, s, sp) : launch_fused_w2ss(nj, p, s, sp);
-        if (!force_w1 && !ident && fused_fits_w2m(nj, p.H, p.nobs)) return analytic ? launch_fused_w2mas(nj, p, s, sp) : launch_fused_w2ms(nj, p, s, sp);
-        return analytic ? launch_fused_w1as(nj, p, s, sp) : launch_fused_w1s(nj, p, s, sp);
-    }
-    if (!force_w1 && ident && fused_fits_w2s(nj, p.H, p.nobs)) return analytic ? launch_fused_w2sa(nj, p, s) : launch_fused_w2s(nj, p, s);
-    if (!force_w1 && !ident && fused_fits_w2m(nj, p.H, p.nobs)) return analytic ? launch_fused_w2ma(nj, p, s) : launch_fused_w2m(nj, p, s);
-    return analytic ? launch_fused_w1a(nj, p, s) : launch_fused_w1(nj, p, s);
+    if (!force_w1 && ident && fused_fits_tier<FUSED_W2S>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2S>(nj, p, s, analytic, soft);
+    if (!force_w1 && !ident && fused_fits_tier<FUSED_W2M>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2M>(nj, p, s, analytic, soft);
+    return launch_tier<FUSED_W1>(nj, p, s, analytic, soft);
 }
 
 extern "C" {

@@ -137,34 +137,23 @@ struct FusedParams {
     int *dump_linkid;            // B x nobs x H       closest link (1-based, line obstacles only)
     double *dump_lambda;         // B x (nobs*H + 4nn) multipliers of the last QP [collision (j,i) | vel+ | vel- | bound+ | bound-] (may be null)
 };
-// cfs_fused.hip is compiled into three tiers (workgroups per CU / register-resident columns of the inverse Gram matrix):
-//   w1  1 / 64  whole CU per problem: longest on-chip active sets
-//   w2m 2 / 32  two problems per CU hide each other's latencies; medium active sets stay in registers
-//   w2s 2 / 16  same, smallest register footprint (no spills): the projection QPs of PSGCFS have 2-3 active rows
-hipError_t launch_fused_w1(int nj, FusedParams p, hipStream_t s);
-hipError_t launch_fused_w2m(int nj, FusedParams p, hipStream_t s);
-hipError_t launch_fused_w2s(int nj, FusedParams p, hipStream_t s);
-bool fused_fits_w1(int nj, int H, int nobs);
-bool fused_fits_w2m(int nj, int H, int nobs);
-bool fused_fits_w2s(int nj, int H, int nobs);
-// the same tiers with the analytic Jacobian (cfs_fused.hip built with CFS_JAC=1; same LDS layout and capacities)
-hipError_t launch_fused_w1a(int nj, FusedParams p, hipStream_t s);
-hipError_t launch_fused_w2ma(int nj, FusedParams p, hipStream_t s);
-hipError_t launch_fused_w2sa(int nj, FusedParams p, hipStream_t s);
-// soft-constraint QP after a proven-infeasible one (CFS_INFEAS_SOFTEN handles): the second parameter block of the kernels built
-// with CFS_SOFT=1, the same six tiers again (same LDS layout and capacities)
+// soft-constraint QP after a proven-infeasible one (CFS_INFEAS_SOFTEN handles): the second parameter block of the SOFT kernels
 struct SoftParams {
     double inv_weight;           // 1 / mu
     double *viol;                // B x max_o_iter: max slack of every outer iteration's QP, 0 for a hard one (null: not recorded)
     int *n_soft;                 // B: softened outer iterations (null: not recorded)
 };
-hipError_t launch_fused_w1s(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
-hipError_t launch_fused_w2ms(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
-hipError_t launch_fused_w2ss(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
-hipError_t launch_fused_w1as(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
-hipError_t launch_fused_w2mas(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
-hipError_t launch_fused_w2sas(int nj, FusedParams p, hipStream_t s, const SoftParams &sp);
-// cfs_api.hip: tier by mode and capacity; analytic: the CFS_JAC_ANALYTIC kernels; soft (non-null): the CFS_SOFT kernels
+// cfs_fused.hip is compiled into three tiers (workgroups per CU / register-resident columns of the inverse Gram matrix):
+//   w1  1 / 64  whole CU per problem: longest on-chip active sets
+//   w2m 2 / 32  two problems per CU hide each other's latencies; medium active sets stay in registers
+//   w2s 2 / 16  same, smallest register footprint (no spills): the projection QPs of PSGCFS have 2-3 active rows
+// and each tier into one object per variant (Makefile): JAC, the analytic Jacobian (CFS_JAC_ANALYTIC handles), and SOFT, the soft
+// QP (sp; null without SOFT).  Every object defines its own launch_fused_tier<tier, JAC, SOFT>, the tier's default object its
+// fused_fits_tier<tier> (the variants share the LDS layout and capacities).
+enum FusedTier { FUSED_W1, FUSED_W2M, FUSED_W2S };
+template <FusedTier T, bool JAC, bool SOFT> hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftParams *sp);
+template <FusedTier T> bool fused_fits_tier(int nj, int H, int nobs);
+// cfs_api.hip: tier by mode and capacity; analytic: the JAC kernels; soft (non-null): the SOFT kernels
 hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1 = false, bool analytic = false, const SoftParams *soft = nullptr);
 bool fused_fits(int nj, int H, int nobs);
 

@@ -11,9 +11,9 @@
 // therefore owns one problem for its whole life: no host round trip, no inter-problem barrier,
 // and the hardware's workgroup dispatcher load-balances the stragglers over the 256 CUs.
 //   * linearisation (FK variants, segment pairs, literal num_jac) as in cfs_geom.hip, tiled over
-//     waypoints, scratch aliased with the QP's Y storage; objects built with CFS_JAC=1 run the analytic
-//     Jacobian instead (one chain per waypoint, one tangent sweep of the winning link: cfs_geom_dev.h);
-//   * objects built with CFS_SOFT=1 (CFS_INFEAS_SOFTEN handles) follow a QP that is proven infeasible with the
+//     waypoints, scratch aliased with the QP's Y storage; kernels instantiated with JAC (CFS_JAC_ANALYTIC handles) run the
+//     analytic Jacobian instead (one chain per waypoint, one tangent sweep of the winning link: cfs_geom_dev.h);
+//   * kernels instantiated with SOFT (CFS_INFEAS_SOFTEN handles) follow a QP that is proven infeasible with the
 //     soft-constraint QP of the same linearisation: 1/mu on the Gram diagonal of the collision rows;
 //   * QP: Goldfarb-Idnani dual active set in range-space form.  The inverse Gram matrix
 //     P = (N'H^{-1}N)^{-1} is kept EXPLICITLY, one row per thread in registers (it is symmetric,
@@ -26,10 +26,12 @@
 #include "cfs_geom_dev.h"
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 namespace {
 
-#define STAMP(k) do { if (P.stamps) { const unsigned long long t_ = clock64(); if (tid == 0) s_acc[k] += t_ - t0_; t0_ = t_; } } while (0)
+#define STAMP_IF(k) if (P.stamps) { const unsigned long long t_ = clock64(); if (tid == 0) s_acc[k] += t_ - t0_; t0_ = t_; }
+#define STAMP(k) do { STAMP_IF(k) } while (0)
 
 #ifndef CFS_CERT_AT
 #define CFS_CERT_AT 6
@@ -37,9 +39,6 @@ namespace {
 constexpr int CERT_AT = CFS_CERT_AT;    // main-loop steps of a QP before the step-free infeasibility certificate is asked
 #ifndef CFS_WG_PER_CU
 #define CFS_WG_PER_CU 1                   // workgroups resident per CU (2: half the LDS and registers each)
-#endif
-#ifndef CFS_ANGLE_ADD
-#define CFS_ANGLE_ADD 0                    // 1: sin/cos of theta +- eps/2 by angle addition (measured: no faster, and the 1e-16 differences it seeds cost parity on the chaotic minority)
 #endif
 #ifndef CFS_REF_A
 #define CFS_REF_A 1e-4                   // refinement of a step direction continues while |r'rho| > A * max(|delta|, tol * n'H^-1 n) ...
@@ -57,38 +56,6 @@ constexpr int CERT_AT = CFS_CERT_AT;    // main-loop steps of a QP before the st
 #ifndef CFS_PR
 #define CFS_PR 64                        // columns of each inverse-Gram row kept in registers
 #endif
-// This file is compiled once per tier (Makefile): CFS_VARIANT names the exported launch_fused_<tier> / fused_fits_<tier>.
-#ifndef CFS_VARIANT
-#define CFS_VARIANT w1
-#endif
-#ifndef CFS_JAC
-#define CFS_JAC 0                        // 1: analytic Jacobian (CFS_JAC_ANALYTIC handles): a kernel of its own name, objects of their own
-#endif
-#ifndef CFS_SOFT
-#define CFS_SOFT 0                       // 1: soft-constraint QP after a proven-infeasible one (CFS_INFEAS_SOFTEN handles): kernels of their own name, objects of their own
-#endif
-#if CFS_SOFT && CFS_JAC
-#define CFS_FUSED_KERNEL cfs_solve_fused_analytic_soft_kernel
-#elif CFS_SOFT
-#define CFS_FUSED_KERNEL cfs_solve_fused_soft_kernel
-#elif CFS_JAC
-#define CFS_FUSED_KERNEL cfs_solve_fused_analytic_kernel
-#else
-#define CFS_FUSED_KERNEL cfs_solve_fused_kernel
-#endif
-#if CFS_SOFT
-#define CFS_SOFT_KPARAM , SoftParams S           /* the soft kernels take a second parameter block */
-#define CFS_SOFT_LPARAM , const SoftParams &sp
-#define CFS_SOFT_ARG , sp
-#define IF_HARD(c) (!soft && (c))                /* proofs that hold for the hard QP only */
-#else
-#define CFS_SOFT_KPARAM
-#define CFS_SOFT_LPARAM
-#define CFS_SOFT_ARG
-#define IF_HARD(c) (c)
-#endif
-#define CFS_CAT2(a, b) a##_##b
-#define CFS_CAT(a, b) CFS_CAT2(a, b)
 static_assert(CFS_PR % 8 == 0 && CFS_PR >= 8, "register-resident P columns come in chunks of 8");
 constexpr int FT = 256;                  // threads per workgroup
 constexpr double DEP_TOL_F = 1e-8;       // dependent if delta <= tol * n'H^{-1}n: above the eps*cond(H) noise floor of Y = H^{-1}N
@@ -482,9 +449,15 @@ __host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int NJ, int QB, bool IDENT>      // IDENT: the QP Hessian is the identity (PSGCFS projection)
-__global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParams P CFS_SOFT_KPARAM)
+// IDENT: the QP Hessian is the identity (PSGCFS projection); JAC: analytic Jacobian (CFS_JAC_ANALYTIC handles).
+// Soft: empty for STOP handles, whose kernarg segment is FusedParams alone; SoftParams for CFS_INFEAS_SOFTEN handles (SOFT: the
+// soft-constraint QP after a proven-infeasible one, its parameters as a second block).
+template <int NJ, int QB, bool IDENT, bool JAC, class... Soft>
+__global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(FusedParams P, Soft... soft_params)
 {
+    constexpr bool SOFT = sizeof...(Soft) > 0;
+    static_assert(!SOFT || (sizeof...(Soft) == 1 && (std::is_same_v<Soft, SoftParams> && ...)), "Soft is empty or SoftParams");
+    const SoftParams S{soft_params...};
     constexpr int NS = 2 * NJ, NVT = nvt(NJ), NE = 2 * NJ + 1;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = P.order ? P.order[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;   // workgroups are dispatched in blockIdx order: longest problems first when the caller knows them
@@ -589,11 +562,9 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
     double cost_new = P.caug[b], cost_old = 100000.0;      // get_cost(zeros) = caug; EVAL.m:29
     int iter_O = 1, total_iter = 0, noise_row = 0, status = CFS_OK_MAXITER;
     bool done = false;
-#if CFS_SOFT
-    const double iw = S.inv_weight;                        // 1/mu: the soft QP's Gram diagonal of a collision row grows by it
-    int n_soft = 0;
-    bool last_soft = false;                                // the last QP solved was a soft one (CFS_SOFT_ENDED)
-#endif
+    const double iw = S.inv_weight;                        // SOFT: 1/mu, the soft QP's Gram diagonal of a collision row grows by it
+    int n_soft = 0;                                        // SOFT: softened outer iterations
+    bool last_soft = false;                                // SOFT: the last QP solved was a soft one (CFS_SOFT_ENDED)
     const int nseg = nobs - P.nmesh;                       // obstacles [nseg, nobs) are meshes, linearised by cfs_mesh.hip
     int launched = 0;
     if (P.resume) {                                        // continue a solve that is driven one outer iteration per launch
@@ -655,197 +626,183 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
         // =========================================================================================
         // get_con, distance half (CFS_FANUC.m:110-118): dist -> s_rhs, Diff -> s_g
         // =========================================================================================
-#if CFS_JAC
-        // Analytic Jacobian: Diff = the exact derivative of the branch of dist_arm active at the base pose (cfs_geom_dev.h).
-        // Same base-pose distances and first-minimum link as the literal scheme; per waypoint one sincos per joint and ONE
-        // kinematic chain (end points + joint twists), per (waypoint, obstacle) one tangent sweep of the winning link.
-        // The four phases carry prep(0..3) as the literal scheme's do.
-        (void)NE;
-        if (nseg > 0) {
-            const int W = P.lin_w;                           // tiles of the literal scheme's size: its scratch is a superset
-            double *s_sc = lds + L.lin;                      // [W][NJ][2]  sin, cos of theta (minus the joint offset)
-            double *s_en = s_sc + W * NJ * 6;                // [W][NJ][6]  capsule end points of the base pose
-            double *s_tw = s_en + W * NJ * 6;                // [W][NJ][6]  joint twists [axis; point]  (2 NJ * 6 <= NVT * 6)
-            double *s_bd = s_en + W * NVT * 6;               // [W][NJ][nobs] base-pose distance of every link
-            for (int w0 = 0; w0 < H; w0 += W) {
-                const int Wc = min(W, H - w0);
-                if (w0 == 0) prep(0);
-                for (int e = tid; e < Wc * NJ; e += FT) {
-                    const int m = e % NJ, wi = e / NJ;
-                    double x = s_x[(w0 + wi) * NS + m];
-                    x = x - rb->th_off[m];                   // dist_arm_3D_200i_2.m:11
-                    double sn, cs;
-                    sincos(x, &sn, &cs);
-                    s_sc[e * 2] = sn;
-                    s_sc[e * 2 + 1] = cs;
-                }
-                __syncthreads();
-                for (int wi = tid; wi < Wc; wi += FT) arm_chain(rb, NJ, s_sc + wi * NJ * 2, s_en + wi * NJ * 6, s_tw + wi * NJ * 6);
-                if (w0 == 0) prep(1);
-                __syncthreads();
-                STAMP(10);                                  // 10: sincos + the chain
-                for (int e = tid; e < NJ * Wc * nseg; e += FT) {
-                    const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
-                    s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, s_ob + j * 6);
-                }
-                if (w0 == 0) prep(2);
-                __syncthreads();
-                STAMP(0);                                   // 0: base distances
-                for (int e = tid; e < Wc * nseg; e += FT) {
-                    const int j = e % nseg, wi = e / nseg;
-                    double m0 = INFINITY;
-                    int lk = 0;
+        if constexpr (JAC) {
+            // Analytic Jacobian: Diff = the exact derivative of the branch of dist_arm active at the base pose (cfs_geom_dev.h).
+            // Same base-pose distances and first-minimum link as the literal scheme; per waypoint one sincos per joint and ONE
+            // kinematic chain (end points + joint twists), per (waypoint, obstacle) one tangent sweep of the winning link.
+            // The four phases carry prep(0..3) as the literal scheme's do.
+            if (nseg > 0) {
+                const int W = P.lin_w;                           // tiles of the literal scheme's size: its scratch is a superset
+                double *s_sc = lds + L.lin;                      // [W][NJ][2]  sin, cos of theta (minus the joint offset)
+                double *s_en = s_sc + W * NJ * 6;                // [W][NJ][6]  capsule end points of the base pose
+                double *s_tw = s_en + W * NJ * 6;                // [W][NJ][6]  joint twists [axis; point]  (2 NJ * 6 <= NVT * 6)
+                double *s_bd = s_en + W * NVT * 6;               // [W][NJ][nobs] base-pose distance of every link
+                for (int w0 = 0; w0 < H; w0 += W) {
+                    const int Wc = min(W, H - w0);
+                    if (w0 == 0) prep(0);
+                    for (int e = tid; e < Wc * NJ; e += FT) {
+                        const int m = e % NJ, wi = e / NJ;
+                        double x = s_x[(w0 + wi) * NS + m];
+                        x = x - rb->th_off[m];                   // dist_arm_3D_200i_2.m:11
+                        double sn, cs;
+                        sincos(x, &sn, &cs);
+                        s_sc[e * 2] = sn;
+                        s_sc[e * 2 + 1] = cs;
+                    }
+                    __syncthreads();
+                    for (int wi = tid; wi < Wc; wi += FT) arm_chain(rb, NJ, s_sc + wi * NJ * 2, s_en + wi * NJ * 6, s_tw + wi * NJ * 6);
+                    if (w0 == 0) prep(1);
+                    __syncthreads();
+                    STAMP(10);                                  // 10: sincos + the chain
+                    for (int e = tid; e < NJ * Wc * nseg; e += FT) {
+                        const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
+                        s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, s_ob + j * 6);
+                    }
+                    if (w0 == 0) prep(2);
+                    __syncthreads();
+                    STAMP(0);                                   // 0: base distances
+                    for (int e = tid; e < Wc * nseg; e += FT) {
+                        const int j = e % nseg, wi = e / nseg;
+                        double m0 = INFINITY;
+                        int lk = 0;
 #pragma unroll
-                    for (int k1 = 1; k1 <= NJ; ++k1) { const double bk = s_bd[(wi * NJ + k1 - 1) * nseg + j]; if (bk < m0) { m0 = bk; lk = k1; } }   // first minimum wins (dist_arm_3D_200i_2.m:25)
-                    if (P.dump_linkid && launched == 0) P.dump_linkid[((size_t)b * nobs + j) * H + w0 + wi] = lk;
-                    s_rhs[j * H + w0 + wi] = m0;
-                    double *g = s_g + (j * H + w0 + wi) * NJ;
-                    if (lk > 0) winner_grad(s_en + (wi * NJ + lk - 1) * 6, s_tw + wi * NJ * 6, lk - 1, NJ, s_ob + j * 6, g);
-                    else for (int m = 0; m < NJ; ++m) g[m] = 0.0;
+                        for (int k1 = 1; k1 <= NJ; ++k1) { const double bk = s_bd[(wi * NJ + k1 - 1) * nseg + j]; if (bk < m0) { m0 = bk; lk = k1; } }   // first minimum wins (dist_arm_3D_200i_2.m:25)
+                        if (P.dump_linkid && launched == 0) P.dump_linkid[((size_t)b * nobs + j) * H + w0 + wi] = lk;
+                        s_rhs[j * H + w0 + wi] = m0;
+                        double *g = s_g + (j * H + w0 + wi) * NJ;
+                        if (lk > 0) winner_grad(s_en + (wi * NJ + lk - 1) * 6, s_tw + wi * NJ * 6, lk - 1, NJ, s_ob + j * 6, g);
+                        else for (int m = 0; m < NJ; ++m) g[m] = 0.0;
+                    }
+                    if (w0 == 0) { prep(3); prepped = true; }
+                    // (the next tile's first phase only writes its sin / cos table, which this one no longer reads)
+                    if (w0 + W >= H) __syncthreads();
+                    STAMP(11);                                  // 11: minima and the tangent sweeps of the winning links
                 }
-                if (w0 == 0) { prep(3); prepped = true; }
-                // (the next tile's first phase only writes its sin / cos table, which this one no longer reads)
-                if (w0 + W >= H) __syncthreads();
-                STAMP(11);                                  // 11: minima and the tangent sweeps of the winning links
             }
-        }
-#else
-        if (nseg > 0) {
-            const int W = P.lin_w;
-            double *s_sc = lds + L.lin;                      // [W][NJ][3][2] sin, cos of theta, theta+eps/2, theta-eps/2 (minus the joint offset)
-            double *s_en = s_sc + W * NJ * 6;                // [W][NVT][6]  capsule end points of every link variant
-            double *s_bd = s_en + W * NVT * 6;               // [W][NJ][nobs] base-pose distance of every link
-            double *s_dv = s_bd + W * NJ * nseg;             // [W][nobs][NE] min over the links at every evaluation point of num_jac
-            unsigned short *s_list = reinterpret_cast<unsigned short *>(s_dv + W * nseg * NE);    // [NJ][W*nobs] (wi << 8 | obstacle)
-            int *s_cnt = s_free;                             // candidates per link (the QP's free-slot stack is idle here)
-            for (int w0 = 0; w0 < H; w0 += W) {
-                const int Wc = min(W, H - w0);
-                if (w0 == 0) prep(0);
-#if CFS_ANGLE_ADD
-                const double ch = cos(FD_EPS / 2), sh = sin(FD_EPS / 2);
-                for (int e = tid; e < Wc * NJ; e += FT) {
-                    const int m = e % NJ, wi = e / NJ;
-                    double sn, cs;
-                    sincos(s_x[(w0 + wi) * NS + m] - rb->th_off[m], &sn, &cs);   // dist_arm_3D_200i_2.m:11
-                    s_sc[e * 6] = sn;
-                    s_sc[e * 6 + 1] = cs;
-                    s_sc[e * 6 + 2] = sn * ch + cs * sh; s_sc[e * 6 + 3] = cs * ch - sn * sh;
-                    s_sc[e * 6 + 4] = sn * ch - cs * sh; s_sc[e * 6 + 5] = cs * ch + sn * sh;
-                }
-#else
-                for (int e = tid; e < Wc * NJ * 3; e += FT) {
-                    const int var = e % 3, m = (e / 3) % NJ, wi = e / (3 * NJ);
-                    double x = s_x[(w0 + wi) * NS + m];
-                    if (var == 1) x = x + FD_EPS / 2;        // num_jac.m:11
-                    else if (var == 2) x = x - FD_EPS / 2;   // num_jac.m:13
-                    x = x - rb->th_off[m];                   // dist_arm_3D_200i_2.m:11
-                    double sn, cs;
-                    sincos(x, &sn, &cs);
-                    s_sc[((wi * NJ + m) * 3 + var) * 2] = sn;
-                    s_sc[((wi * NJ + m) * 3 + var) * 2 + 1] = cs;
-                }
-#endif
-                __syncthreads();
-                // one thread per (waypoint, evaluation point of num_jac): the whole kinematic chain in registers.
-                // Evaluation point ev has joint m at +eps/2 if ev == 2m-1, at -eps/2 if ev >= 2m (num_jac.m:8-14:
-                // xp is never restored); the shifted sin/cos come from the base pair by angle addition.  Link k of
-                // evaluation ev is variant min(ev, 2k); the thread with ev <= 2k is the one that stores it.
-                for (int e = tid; e < Wc * NE; e += FT) {
-                    const int ev = e % NE, wi = e / NE;
-                    double M[12], Mn[12], e6[6];
+        } else {
+            if (nseg > 0) {
+                const int W = P.lin_w;
+                double *s_sc = lds + L.lin;                      // [W][NJ][3][2] sin, cos of theta, theta+eps/2, theta-eps/2 (minus the joint offset)
+                double *s_en = s_sc + W * NJ * 6;                // [W][NVT][6]  capsule end points of every link variant
+                double *s_bd = s_en + W * NVT * 6;               // [W][NJ][nobs] base-pose distance of every link
+                double *s_dv = s_bd + W * NJ * nseg;             // [W][nobs][NE] min over the links at every evaluation point of num_jac
+                unsigned short *s_list = reinterpret_cast<unsigned short *>(s_dv + W * nseg * NE);    // [NJ][W*nobs] (wi << 8 | obstacle)
+                int *s_cnt = s_free;                             // candidates per link (the QP's free-slot stack is idle here)
+                for (int w0 = 0; w0 < H; w0 += W) {
+                    const int Wc = min(W, H - w0);
+                    if (w0 == 0) prep(0);
+                    for (int e = tid; e < Wc * NJ * 3; e += FT) {
+                        const int var = e % 3, m = (e / 3) % NJ, wi = e / (3 * NJ);
+                        double x = s_x[(w0 + wi) * NS + m];
+                        if (var == 1) x = x + FD_EPS / 2;        // num_jac.m:11
+                        else if (var == 2) x = x - FD_EPS / 2;   // num_jac.m:13
+                        x = x - rb->th_off[m];                   // dist_arm_3D_200i_2.m:11
+                        double sn, cs;
+                        sincos(x, &sn, &cs);
+                        s_sc[((wi * NJ + m) * 3 + var) * 2] = sn;
+                        s_sc[((wi * NJ + m) * 3 + var) * 2 + 1] = cs;
+                    }
+                    __syncthreads();
+                    // one thread per (waypoint, evaluation point of num_jac): the whole kinematic chain in registers.
+                    // Evaluation point ev has joint m at +eps/2 if ev == 2m-1, at -eps/2 if ev >= 2m (num_jac.m:8-14:
+                    // xp is never restored); the shifted sin/cos come from the base pair by angle addition.  Link k of
+                    // evaluation ev is variant min(ev, 2k); the thread with ev <= 2k is the one that stores it.
+                    for (int e = tid; e < Wc * NE; e += FT) {
+                        const int ev = e % NE, wi = e / NE;
+                        double M[12], Mn[12], e6[6];
 #pragma unroll
-                    for (int k1 = 1; k1 <= NJ; ++k1) {
-                        const int avar = (ev == 2 * k1 - 1) ? 1 : (ev >= 2 * k1 ? 2 : 0);
-                        const double sn = s_sc[((wi * NJ + k1 - 1) * 3 + avar) * 2], cs = s_sc[((wi * NJ + k1 - 1) * 3 + avar) * 2 + 1];
-                        fk_step(rb, k1 - 1, sn, cs, k1 == 1 ? nullptr : M, Mn);
+                        for (int k1 = 1; k1 <= NJ; ++k1) {
+                            const int avar = (ev == 2 * k1 - 1) ? 1 : (ev >= 2 * k1 ? 2 : 0);
+                            const double sn = s_sc[((wi * NJ + k1 - 1) * 3 + avar) * 2], cs = s_sc[((wi * NJ + k1 - 1) * 3 + avar) * 2 + 1];
+                            fk_step(rb, k1 - 1, sn, cs, k1 == 1 ? nullptr : M, Mn);
 #pragma unroll
-                        for (int qq = 0; qq < 12; ++qq) M[qq] = Mn[qq];
-                        if (ev <= 2 * k1) {
-                            link_ends(rb, k1 - 1, M, e6);
-                            double *dstE = s_en + (wi * NVT + kvoff(k1) + ev) * 6;
+                            for (int qq = 0; qq < 12; ++qq) M[qq] = Mn[qq];
+                            if (ev <= 2 * k1) {
+                                link_ends(rb, k1 - 1, M, e6);
+                                double *dstE = s_en + (wi * NVT + kvoff(k1) + ev) * 6;
 #pragma unroll
-                            for (int qq = 0; qq < 6; ++qq) dstE[qq] = e6[qq];
+                                for (int qq = 0; qq < 6; ++qq) dstE[qq] = e6[qq];
+                            }
                         }
                     }
-                }
-                if (w0 == 0) prep(1);
-                __syncthreads();
-                STAMP(10);                                  // 10: sincos + link transforms
-                // Base-pose distance of every link (dist_arm_3D_200i_2.m:16-26), link index slow so the point /
-                // segment branch of distLinSeg is wave-uniform.
+                    if (w0 == 0) prep(1);
+                    __syncthreads();
+                    STAMP(10);                                  // 10: sincos + link transforms
+                    // Base-pose distance of every link (dist_arm_3D_200i_2.m:16-26), link index slow so the point /
+                    // segment branch of distLinSeg is wave-uniform.
 #if CFS_LIN_UNROLL
 #pragma unroll 2
 #endif
-                for (int e = tid; e < NJ * Wc * nseg; e += FT) {
-                    const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
-                    s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NVT + kvoff(k0 + 1)) * 6, s_ob + j * 6);
-                }
-                if (tid < NJ) s_cnt[tid] = 0;
-                if (w0 == 0) prep(2);
-                __syncthreads();
-                // num_jac only needs min over the links at 2nj shifted poses.  A link whose base distance exceeds
-                // max(min, 1e-4) by prune_tol can neither become the minimum nor reach the near-zero surrogate at any
-                // of them (see DevRobot::prune_tol), so only the other links are evaluated there: same minima, bit for bit.
-                for (int e = tid; e < Wc * nseg; e += FT) {
-                    const int j = e % nseg, wi = e / nseg;
-                    double bk[NJ], m0 = INFINITY;
-                    int lk = 0;
-#pragma unroll
-                    for (int k1 = 1; k1 <= NJ; ++k1) { bk[k1 - 1] = s_bd[(wi * NJ + k1 - 1) * nseg + j]; if (bk[k1 - 1] < m0) { m0 = bk[k1 - 1]; lk = k1; } }   // first minimum wins (dist_arm_3D_200i_2.m:25)
-                    if (P.dump_linkid && launched == 0) P.dump_linkid[((size_t)b * nobs + j) * H + w0 + wi] = lk;
-                    const double thr = P.no_prune ? INFINITY : fmax(m0, 0.0001) + rb->prune_tol;
-#pragma unroll
-                    for (int k1 = 1; k1 <= NJ; ++k1)
-                        if (bk[k1 - 1] < thr) s_list[(k1 - 1) * W * nseg + atomicAdd(&s_cnt[k1 - 1], 1)] = (unsigned short)((wi << 8) | j);
-                    s_dv[e * NE] = m0;
-#pragma unroll
-                    for (int ev = 1; ev < NE; ++ev) s_dv[e * NE + ev] = INFINITY;
-                }
-                if (w0 == 0) { prep(3); prepped = true; }
-                __syncthreads();
-                STAMP(0);                                   // 0: base distances, candidate lists (+ the minima / differences below)
-                {
-                    int offs[NJ + 1];
-                    offs[0] = 0;
-#pragma unroll
-                    for (int k1 = 1; k1 <= NJ; ++k1) offs[k1] = offs[k1 - 1] + s_cnt[k1 - 1] * 2 * k1;
-#if CFS_LIN_UNROLL
-#pragma unroll 2
-#endif
-                    for (int e = tid; e < offs[NJ]; e += FT) {
-                        int k1 = 1, ent = 0, v = 1;
-#pragma unroll
-                        for (int kk = 1; kk <= NJ; ++kk)
-                            if (e >= offs[kk - 1] && e < offs[kk]) {
-                                const int r_ = e - offs[kk - 1];
-                                k1 = kk; ent = r_ / (2 * kk); v = r_ - ent * (2 * kk) + 1;
-                            }
-                        const int item = s_list[(k1 - 1) * W * nseg + ent], wi = item >> 8, j = item & 255;
-                        const double dis = seg_seg_dist(s_en + (wi * NVT + kvoff(k1) + v) * 6, s_ob + j * 6);
-                        // link k1 is at variant min(ev, 2 k1) at evaluation point ev: v < 2 k1 serves ev = v, v = 2 k1 every ev >= v
-                        double *dv = s_dv + (wi * nseg + j) * NE;
-                        const int evhi = (v == 2 * k1) ? NE - 1 : v;
-                        for (int ev = v; ev <= evhi; ++ev)
-                            __hip_atomic_fetch_min(dv + ev, dis, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_min_f64
+                    for (int e = tid; e < NJ * Wc * nseg; e += FT) {
+                        const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
+                        s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NVT + kvoff(k0 + 1)) * 6, s_ob + j * 6);
                     }
-                }
-                __syncthreads();
-                STAMP(11);                                  // 11: segment pairs of the shifted poses
-                for (int e = tid; e < Wc * nseg; e += FT) {
-                    const int j = e % nseg, wi = e / nseg;
-                    double dev[NE];
+                    if (tid < NJ) s_cnt[tid] = 0;
+                    if (w0 == 0) prep(2);
+                    __syncthreads();
+                    // num_jac only needs min over the links at 2nj shifted poses.  A link whose base distance exceeds
+                    // max(min, 1e-4) by prune_tol can neither become the minimum nor reach the near-zero surrogate at any
+                    // of them (see DevRobot::prune_tol), so only the other links are evaluated there: same minima, bit for bit.
+                    for (int e = tid; e < Wc * nseg; e += FT) {
+                        const int j = e % nseg, wi = e / nseg;
+                        double bk[NJ], m0 = INFINITY;
+                        int lk = 0;
 #pragma unroll
-                    for (int ev = 0; ev < NE; ++ev) dev[ev] = s_dv[e * NE + ev];
-                    s_rhs[j * H + w0 + wi] = dev[0];
+                        for (int k1 = 1; k1 <= NJ; ++k1) { bk[k1 - 1] = s_bd[(wi * NJ + k1 - 1) * nseg + j]; if (bk[k1 - 1] < m0) { m0 = bk[k1 - 1]; lk = k1; } }   // first minimum wins (dist_arm_3D_200i_2.m:25)
+                        if (P.dump_linkid && launched == 0) P.dump_linkid[((size_t)b * nobs + j) * H + w0 + wi] = lk;
+                        const double thr = P.no_prune ? INFINITY : fmax(m0, 0.0001) + rb->prune_tol;
 #pragma unroll
-                    for (int m = 0; m < NJ; ++m) s_g[(j * H + w0 + wi) * NJ + m] = (dev[2 * m + 1] - dev[2 * m + 2]) / FD_EPS;
+                        for (int k1 = 1; k1 <= NJ; ++k1)
+                            if (bk[k1 - 1] < thr) s_list[(k1 - 1) * W * nseg + atomicAdd(&s_cnt[k1 - 1], 1)] = (unsigned short)((wi << 8) | j);
+                        s_dv[e * NE] = m0;
+#pragma unroll
+                        for (int ev = 1; ev < NE; ++ev) s_dv[e * NE + ev] = INFINITY;
+                    }
+                    if (w0 == 0) { prep(3); prepped = true; }
+                    __syncthreads();
+                    STAMP(0);                                   // 0: base distances, candidate lists (+ the minima / differences below)
+                    {
+                        int offs[NJ + 1];
+                        offs[0] = 0;
+#pragma unroll
+                        for (int k1 = 1; k1 <= NJ; ++k1) offs[k1] = offs[k1 - 1] + s_cnt[k1 - 1] * 2 * k1;
+#if CFS_LIN_UNROLL
+#pragma unroll 2
+#endif
+                        for (int e = tid; e < offs[NJ]; e += FT) {
+                            int k1 = 1, ent = 0, v = 1;
+#pragma unroll
+                            for (int kk = 1; kk <= NJ; ++kk)
+                                if (e >= offs[kk - 1] && e < offs[kk]) {
+                                    const int r_ = e - offs[kk - 1];
+                                    k1 = kk; ent = r_ / (2 * kk); v = r_ - ent * (2 * kk) + 1;
+                                }
+                            const int item = s_list[(k1 - 1) * W * nseg + ent], wi = item >> 8, j = item & 255;
+                            const double dis = seg_seg_dist(s_en + (wi * NVT + kvoff(k1) + v) * 6, s_ob + j * 6);
+                            // link k1 is at variant min(ev, 2 k1) at evaluation point ev: v < 2 k1 serves ev = v, v = 2 k1 every ev >= v
+                            double *dv = s_dv + (wi * nseg + j) * NE;
+                            const int evhi = (v == 2 * k1) ? NE - 1 : v;
+                            for (int ev = v; ev <= evhi; ++ev)
+                                __hip_atomic_fetch_min(dv + ev, dis, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_min_f64
+                        }
+                    }
+                    __syncthreads();
+                    STAMP(11);                                  // 11: segment pairs of the shifted poses
+                    for (int e = tid; e < Wc * nseg; e += FT) {
+                        const int j = e % nseg, wi = e / nseg;
+                        double dev[NE];
+#pragma unroll
+                        for (int ev = 0; ev < NE; ++ev) dev[ev] = s_dv[e * NE + ev];
+                        s_rhs[j * H + w0 + wi] = dev[0];
+#pragma unroll
+                        for (int m = 0; m < NJ; ++m) s_g[(j * H + w0 + wi) * NJ + m] = (dev[2 * m + 1] - dev[2 * m + 2]) / FD_EPS;
+                    }
+                    // (no barrier between tiles: the next tile's first phase only writes its sin / cos table, which these differences do
+                    // not read; its barrier covers both)
+                    if (w0 + W >= H) __syncthreads();
                 }
-                // (no barrier between tiles: the next tile's first phase only writes its sin / cos table, which these differences do
-                // not read; its barrier covers both)
-                if (w0 + W >= H) __syncthreads();
             }
         }
-#endif
         if (!prepped && P.piece != 1) {                     // nothing to ride on (mesh obstacles only, or the QP piece): four phases of their own
             prep(0); __syncthreads(); prep(1); __syncthreads(); prep(2); __syncthreads(); prep(3); __syncthreads();
         }
@@ -990,10 +947,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                 wb[k] = w0; wb[HN + k] = w1; wb[2 * HN + k] = w2;
             }
         };
-#if CFS_SOFT
-        bool soft = false;                                  // this iteration's hard QP was proven infeasible: solving the soft one
-        double viol = 0.0;                                  // max slack max_r lambda_r / mu of the soft QP (0: hard)
-#endif
+        bool soft = false;                                  // SOFT: this iteration's hard QP was proven infeasible: solving the soft one
+        double viol = 0.0;                                  // SOFT: max slack max_r lambda_r / mu of the soft QP (0: hard)
         if (!skip) {
             // rhs = (d - margin) - Diff'*Bj(1:nj,:)*u   (CFS_FANUC.m:119-120), with Bpos*u from the rollout of u (s_up)
             for (int e = tid; e < ncon; e += FT) { s_flag[e] = 0; s_slot[e] = 0; }
@@ -1106,16 +1061,20 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                 }
                 return block_sum((double)hit, red, tid) > 0.0;     // (no __syncthreads_or: it would add static LDS to a kernel sized to the byte)
             };
-            STAMP(1);                                       // 1: QP setup
-#if CFS_SOFT
-          // Soft-constraint QP (CFS_INFEAS_SOFTEN).  Only after the hard QP is PROVEN infeasible: min 1/2 u'Gu + g'u + mu/2 |s|^2
+            // 1: QP setup.  Without SOFT the stamp goes without its do/while.  Clang numbers the exits of every loop in source order,
+            // and some of those numbers reach the code as immediates.  The soft QP's retry loop below is in every instantiation, so
+            // dropping the stamp's two exits keeps the STOP kernels' instructions those of a QP without a retry loop.
+            if constexpr (SOFT) STAMP(1);
+            else { STAMP_IF(1) }
+          // Soft-constraint QP (SOFT).  Only after the hard QP is PROVEN infeasible: min 1/2 u'Gu + g'u + mu/2 |s|^2
           // s.t. a_r'u - s_r <= b_r on the collision rows, the velocity and input rows hard.  In (u, s) a collision row has the
           // normal (a_r, -e_r) and the Hessian is blkdiag(G, mu I): every Gram product is the hard one plus 1/mu on the diagonal
           // of a collision row, and s_r = lambda_r / mu.  Inactive rows have s = 0, so the scan for the most violated row is the
-          // hard one.  Cold start, no objective bound, no step-free certificate (both are proofs about the hard QP).
+          // hard one.  Cold start, no objective bound, no step-free certificate (both are proofs about the hard QP: !(SOFT && soft)).
+          // Without SOFT the loop below runs once.
           int iters_hard = 0;
           for (;;) {
-            if (soft) {
+            if (SOFT && soft) {
                 iters_hard = iters; iters = 0;
                 __syncthreads();
                 for (int e = tid; e < ncon; e += FT) { s_flag[e] = 0; s_slot[e] = 0; }
@@ -1125,7 +1084,6 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                 __syncthreads();
                 prep(0); __syncthreads(); prep(1); __syncthreads(); prep(2); __syncthreads(); prep(3); __syncthreads();
             }
-#endif
             // ---- warm start (H = I): begin at the S-pair of the previous outer iteration's active rows ------------------------
             // Consecutive outer iterations linearise nearly the same trajectory, so the optimal active set barely changes (the
             // long problems of config 3: 8-12 rows, 80-100 % kept), yet a cold dual active set re-adds every row one full step
@@ -1133,7 +1091,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
             // multipliers are >= 0): build P for the previous rows -- Gram products only, wavefront 0 alone, no scan, no combine,
             // no block barrier --, take lambda = -P s(x0), drop rows with lambda <= 0 until none is left, set x = x0 + N lambda.
             // The optimum is the same (strictly convex QP); what changes is the number of steps.
-            if (IF_HARD(P.piece == 0) && !(P.opt & 8) && prev_q > 0 && prev_q <= min(64, P.warm_max > 0 ? P.warm_max : min(PR, IDENT ? 64 : 24))) {
+            if (!(SOFT && soft) && P.piece == 0 && !(P.opt & 8) && prev_q > 0 && prev_q <= min(64, P.warm_max > 0 ? P.warm_max : min(PR, IDENT ? 64 : 24))) {
                 int *pub = reinterpret_cast<int *>(red_base + 62);
                 int q = 0;                                   // H = QQ: tracked by every thread (one barrier per row); H = I: by wavefront 0
                 for (int s0 = 0; s0 < (IDENT ? 1 : prev_q); ++s0) {
@@ -1249,8 +1207,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
             STAMP(3);                                       // 3: warm start (H = I) | w gather + rollout (H = QQ, inside the steps)
             int nloop = 0;
             for (;;) {
-                if (IF_HARD(fgain > fbound)) { qp_status = QP_INFEASIBLE; break; }
-                if (IF_HARD(cert_on) && nloop == CERT_AT && certificate()) { qp_status = QP_INFEASIBLE; break; }
+                if (!(SOFT && soft) && fgain > fbound) { qp_status = QP_INFEASIBLE; break; }
+                if (!(SOFT && soft) && cert_on && nloop == CERT_AT && certificate()) { qp_status = QP_INFEASIBLE; break; }
                 ++nloop;
                 // step 1: most violated constraint (constraints are strided over the threads; the codes of a
                 // thread's constraints never change, so they are decoded once per kernel -- no integer divisions here)
@@ -1293,15 +1251,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                     if (tid < qhi) {
                         const int ac = s_act[tid];
                         double sa = 0.0, bb = 0.0;
-#if CFS_SOFT
-                        if (ac >= 0) {                       // soft collision row: its slack includes s = lambda / mu
+                        if (ac >= 0) {
                             sa = slack_of<NJ>(ac, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb);
-                            if (soft && (ac >> 16) == CT_COL) sa += iw * s_lam[tid];
+                            if (SOFT && soft && (ac >> 16) == CT_COL) sa += iw * s_lam[tid];   // soft collision row: its slack includes s = lambda / mu
                             drift = fabs(sa) / (1.0 + fabs(bb));
                         }
-#else
-                        if (ac >= 0) { sa = slack_of<NJ>(ac, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb); drift = fabs(sa) / (1.0 + fabs(bb)); }
-#endif
                         s_prow[tid] = sa;
                     }
                     { double nd = -drift; int dm = 0; block_argmin(nd, dm, red, tid); drift = -nd; }   // block-wide maximum
@@ -1343,9 +1297,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                     if (tid < qhi) s_r[tid] = myact >= 0 ? Pr.dot(s_d, s_pt, tid, qhi) : 0.0;
                     __syncthreads();
                     }
-#if CFS_SOFT
-                    if (soft && !polish && ptype == CT_COL) spp += iw;   // n_p'H^{-1}n_p in (u, s); d is unchanged (p is not active)
-#endif
+                    if (SOFT && soft && !polish && ptype == CT_COL) spp += iw;   // n_p'H^{-1}n_p in (u, s); d is unchanged (p is not active)
                     STAMP(4);                               // 4: d = N'w, r = P d
                     // z = w - Y'r, rollout, then iterative refinement against the true Gram matrix
                     double delta = 0.0, t1 = INFINITY;
@@ -1367,19 +1319,13 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                         }
                         if (polish) break;                             // zb = (x, Bvel x, Bpos x) after the projection
                         delta = ndot<NJ>(pc, zb, s_g, H);              // n_p'z
-#if CFS_SOFT
-                        if (soft && ptype == CT_COL) delta = fmax(delta, 0.0) + iw;   // + e_p's-part of z; >= 1/mu exactly (Schur complement)
-#endif
+                        if (SOFT && soft && ptype == CT_COL) delta = fmax(delta, 0.0) + iw;   // + e_p's-part of z; >= 1/mu exactly (Schur complement)
                         if (qhi == nfree) break;                       // empty active set: nothing to refine, t1 = inf
                         // one exchange carries the refinement diagnostics (r'rho, max|rho|, max|d|; rho_a = n_a'z is
                         // zero in exact arithmetic) and the dual step length t1 = min{lambda_a / r_a : r_a > 0}
                         double rr = 0.0, rmax = 0.0, dmax = 0.0, t1c = INFINITY;
                         if (tid < qhi && myact >= 0) {
-#if CFS_SOFT
-                            const double ra = (soft && (myact >> 16) == CT_COL) ? ndot<NJ>(myact, zb, s_g, H) - iw * s_r[tid] : ndot<NJ>(myact, zb, s_g, H), rv = s_r[tid];
-#else
-                            const double ra = ndot<NJ>(myact, zb, s_g, H), rv = s_r[tid];
-#endif
+                            const double ra = (SOFT && soft && (myact >> 16) == CT_COL) ? ndot<NJ>(myact, zb, s_g, H) - iw * s_r[tid] : ndot<NJ>(myact, zb, s_g, H), rv = s_r[tid];
                             s_prow[tid] = ra;
                             rr = rv * ra;
                             rmax = fabs(ra);
@@ -1424,11 +1370,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                         break;                                         // back to step 1: scan again
                     }
                     STAMP(5);                               // 5: z, rollout, refinement, dual step length
-#if CFS_SOFT
-                    const bool dependent = !(soft && ptype == CT_COL) && !(delta > DEP_TOL_F * spp);   // a soft collision row never is
-#else
-                    const bool dependent = !(delta > DEP_TOL_F * spp);
-#endif
+                    const bool dependent = !(SOFT && soft && ptype == CT_COL) && !(delta > DEP_TOL_F * spp);   // a soft collision row never is
                     const double t2 = dependent ? INFINITY : -sp / delta;
                     const double t = fmin(t1, t2);
                     if (P.dbg && b == P.dbg_b && tid == 0) {
@@ -1502,33 +1444,29 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
                         STAMP(8);                           // 8: drop
                     }
                     { double bb; sp = slack_of<NJ>(pc, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb); }
-#if CFS_SOFT
-                    if (soft && ptype == CT_COL) sp += iw * lam_p;   // the entering row's own slack s_p = lambda_p / mu
-#endif
+                    if (SOFT && soft && ptype == CT_COL) sp += iw * lam_p;   // the entering row's own slack s_p = lambda_p / mu
                 }
                 if (qp_status != QP_OK) break;
             }
-#if CFS_SOFT
-            if (!soft && qp_status == QP_INFEASIBLE) { soft = true; continue; }
-            if (soft) {
-                iters += iters_hard;                        // total_iter counts the steps of both solves
-                if (qp_status == QP_OK) {                   // max slack = max over the active collision rows of lambda / mu
-                    double nv = 0.0;
-                    int dm = 0;
-                    if (tid < qhi) { const int ac = s_act[tid]; if (ac >= 0 && (ac >> 16) == CT_COL) nv = -(iw * s_lam[tid]); }
-                    block_argmin(nv, dm, red, tid);
-                    viol = -nv;
+            if constexpr (SOFT) {
+                if (!soft && qp_status == QP_INFEASIBLE) { soft = true; continue; }
+                if (soft) {
+                    iters += iters_hard;                    // total_iter counts the steps of both solves
+                    if (qp_status == QP_OK) {               // max slack = max over the active collision rows of lambda / mu
+                        double nv = 0.0;
+                        int dm = 0;
+                        if (tid < qhi) { const int ac = s_act[tid]; if (ac >= 0 && (ac >> 16) == CT_COL) nv = -(iw * s_lam[tid]); }
+                        block_argmin(nv, dm, red, tid);
+                        viol = -nv;
+                    }
                 }
             }
             break;
           }
-#endif
         }
         total_iter += iters;
         if (!skip) prev_q = qp_status == QP_OK ? qhi : 0;
-#if CFS_SOFT
-        if (soft) prev_q = 0;                               // the next hard QP starts cold
-#endif
+        if (SOFT && soft) prev_q = 0;                       // the next hard QP starts cold
         if (P.dump_lambda) {
             const int nlam = nobs * H + 4 * HN;
             __syncthreads();
@@ -1541,11 +1479,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
         }
         if (P.piece == 2) {
             for (int e = tid; e < HN; e += FT) P.u[(size_t)b * nn + e] = xs[e];
-#if CFS_SOFT
-            if (tid == 0) { P.total_iter[b] = iters; P.status[b] = qp_status == QP_OK ? (soft ? CFS_SOFT_ENDED : CFS_OK_CONVERGED) : (qp_status == QP_INFEASIBLE ? CFS_QP_INFEASIBLE : CFS_NUMERIC); }
-#else
-            if (tid == 0) { P.total_iter[b] = iters; P.status[b] = qp_status == QP_OK ? CFS_OK_CONVERGED : (qp_status == QP_INFEASIBLE ? CFS_QP_INFEASIBLE : CFS_NUMERIC); }
-#endif
+            if (tid == 0) { P.total_iter[b] = iters; P.status[b] = qp_status == QP_OK ? (SOFT && soft ? CFS_SOFT_ENDED : CFS_OK_CONVERGED) : (qp_status == QP_INFEASIBLE ? CFS_QP_INFEASIBLE : CFS_NUMERIC); }
             drop_pool();
             return;
         }
@@ -1554,10 +1488,10 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
             done = true;
             break;
         }
-#if CFS_SOFT
-        if (!skip) { last_soft = soft; n_soft += soft ? 1 : 0; }
-        if (S.viol && tid == 0) S.viol[(size_t)b * P.max_o_iter + (iter_O - 1)] = viol;
-#endif
+        if constexpr (SOFT) {
+            if (!skip) { last_soft = soft; n_soft += soft ? 1 : 0; }
+            if (S.viol && tid == 0) S.viol[(size_t)b * P.max_o_iter + (iter_O - 1)] = viol;
+        }
 
         // =========================================================================================
         // new u, rollout (CFS_FANUC.m:86-95), get_cost, store_result, iter_O++, stop_outer
@@ -1665,10 +1599,10 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
     __syncthreads();
     for (int e = tid; e < HN; e += FT) P.u[(size_t)b * nn + e] = s_u[e];
     for (int e = tid; e < NX; e += FT) P.x_[(size_t)b * NX + e] = s_x[e];
-#if CFS_SOFT
-    if (last_soft && (status == CFS_OK_CONVERGED || status == CFS_OK_MAXITER)) status = CFS_SOFT_ENDED;   // x_ violates the linearised clearance
-    if (tid == 0 && S.n_soft) S.n_soft[b] = n_soft;
-#endif
+    if constexpr (SOFT) {
+        if (last_soft && (status == CFS_OK_CONVERGED || status == CFS_OK_MAXITER)) status = CFS_SOFT_ENDED;   // x_ violates the linearised clearance
+        if (tid == 0 && S.n_soft) S.n_soft[b] = n_soft;
+    }
     if (tid == 0) { P.iter_O[b] = iter_O; P.total_iter[b] = total_iter; P.status[b] = status; }
     if (P.st_qu) {                                         // state for the next launch of a host-driven solve
         for (int e = tid; e < HN; e += FT) P.st_qu[(size_t)b * nn + e] = s_qu[e];
@@ -1679,12 +1613,13 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void CFS_FUSED_KERNEL(FusedParam
 
 #undef red
 
-template <int NJ, int QB, bool IDENT>
-hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s CFS_SOFT_LPARAM)
+template <int NJ, int QB, bool IDENT, bool JAC, bool SOFT>
+hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s, const SoftParams *sp)
 {
     // the function attribute is per device (handles may live on several GPUs of one process: cfs_set_device)
     static std::atomic<unsigned long long> attr_set{0ull};
-    auto kern = CFS_FUSED_KERNEL<NJ, QB, IDENT>;
+    using Kernel = std::conditional_t<SOFT, void (*)(FusedParams, SoftParams), void (*)(FusedParams)>;
+    const Kernel kern = cfs_solve_fused_kernel<NJ, QB, IDENT, JAC>;    // the pointer type fixes the parameter pack
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -1693,7 +1628,8 @@ hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s CF
         if (e != hipSuccess) return e;
         if (dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_release);
     }
-    hipLaunchKernelGGL(kern, dim3(p.B), dim3(FT), lds, s, p CFS_SOFT_ARG);
+    if constexpr (SOFT) hipLaunchKernelGGL(kern, dim3(p.B), dim3(FT), lds, s, p, *sp);
+    else hipLaunchKernelGGL(kern, dim3(p.B), dim3(FT), lds, s, p);
     return hipGetLastError();
 }
 
@@ -1701,73 +1637,89 @@ hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s CF
 #ifndef CFS_IDENT_SET
 #define CFS_IDENT_SET 2
 #endif
-template <int NJ, int QB>
-hipError_t launch_fused_inst(const FusedParams &p, size_t lds, hipStream_t s CFS_SOFT_LPARAM)
+template <int NJ, int QB, bool JAC, bool SOFT>
+hipError_t launch_fused_inst(const FusedParams &p, size_t lds, hipStream_t s, const SoftParams *sp)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
 #if CFS_IDENT_SET != 0
-    if (ident) return launch_fused_inst2<NJ, QB, true>(p, lds, s CFS_SOFT_ARG);
+    if (ident) return launch_fused_inst2<NJ, QB, true, JAC, SOFT>(p, lds, s, sp);
 #endif
 #if CFS_IDENT_SET != 1
-    if (!ident) return launch_fused_inst2<NJ, QB, false>(p, lds, s CFS_SOFT_ARG);
+    if (!ident) return launch_fused_inst2<NJ, QB, false, JAC, SOFT>(p, lds, s, sp);
 #endif
     return hipErrorInvalidValue;
 }
 
-}  // namespace
-
-// linearisation scratch per waypoint of a tile: sin/cos, link end points, base distances, minima per evaluation point, candidate lists (ushort)
-static size_t lin_doubles_per_wp(int nj, int nobs)
+// The LDS plan of a problem shape on this tier, read by both fused_fits_tier and launch_fused_tier: active-set capacity QB, layout,
+// doubles a workgroup may use (small safety margin), linearisation scratch per waypoint of a tile (sin/cos, link end points, base
+// distances, minima per evaluation point, candidate lists as ushort)
+struct FusedPlan {
+    int nn, QB;
+    FusedLayout L;
+    size_t avail, per_wp;
+};
+FusedPlan fused_plan(int nj, int H, int nobs)
 {
-    return (size_t)nj * 6 + (size_t)nvt(nj) * 6 + (size_t)nj * nobs + (size_t)nobs * (2 * nj + 1) + ((size_t)nj * nobs + 3) / 4;
+    FusedPlan q;
+    q.nn = H * nj;
+    q.QB = q.nn <= 96 ? 96 : (q.nn <= 160 ? 160 : 256);
+    q.L = fused_layout(nj, H, nobs, q.QB, q.QB < CFS_PR ? q.QB : CFS_PR);
+    q.avail = (160 * 1024 / CFS_WG_PER_CU) / 8 - 64;
+    q.per_wp = (size_t)nj * 6 + (size_t)nvt(nj) * 6 + (size_t)nj * nobs + (size_t)nobs * (2 * nj + 1) + ((size_t)nj * nobs + 3) / 4;
+    return q;
 }
 
+}  // namespace
+
 // does the fused kernel's fixed LDS footprint (+ a minimal Y / linearisation region) fit a CU?
-bool CFS_CAT(fused_fits, CFS_VARIANT)(int nj, int H, int nobs)
+template <FusedTier T>
+bool fused_fits_tier(int nj, int H, int nobs)
 {
-    const int nn = H * nj;
-    const int QB = nn <= 96 ? 96 : (nn <= 160 ? 160 : 256);
-    const FusedLayout L = fused_layout(nj, H, nobs, QB, QB < CFS_PR ? QB : CFS_PR);
-    const size_t avail = (160 * 1024 / CFS_WG_PER_CU) / 8 - 64;
-    const size_t per_wp = lin_doubles_per_wp(nj, nobs);
-    return (size_t)L.total_fixed + (size_t)4 * nn <= avail && (size_t)L.lin + per_wp <= avail;
+    const FusedPlan q = fused_plan(nj, H, nobs);
+    return (size_t)q.L.total_fixed + (size_t)4 * q.nn <= q.avail && (size_t)q.L.lin + q.per_wp <= q.avail;
 }
 
 // host: choose the capacities, fill qy / lin_w, launch
-hipError_t CFS_CAT(launch_fused, CFS_VARIANT)(int nj, FusedParams p, hipStream_t s CFS_SOFT_LPARAM)
+template <FusedTier T, bool JAC, bool SOFT>
+hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftParams *sp)
 {
-    const int nn = p.H * nj;
-    const int QB = nn <= 96 ? 96 : (nn <= 160 ? 160 : 256);
-    const FusedLayout L = fused_layout(nj, p.H, p.nobs, QB, QB < CFS_PR ? QB : CFS_PR);
-    const size_t avail = (160 * 1024 / CFS_WG_PER_CU) / 8 - 64;   // doubles per workgroup, small safety margin
+    const FusedPlan q = fused_plan(nj, p.H, p.nobs);
+    const int nn = q.nn;
+    const FusedLayout &L = q.L;
     const bool ident = p.mode == CFS_MODE_PSGCFS;          // H = I: no Y rows at all (closed-form normals)
-    if ((size_t)L.total_fixed + (ident ? 0 : 4 * nn) > avail) return hipErrorInvalidValue;
-    const size_t region = avail - L.total_fixed;
+    if ((size_t)L.total_fixed + (ident ? 0 : 4 * nn) > q.avail) return hipErrorInvalidValue;
+    const size_t region = q.avail - L.total_fixed;
     int qy = ident ? 0 : (int)(region / nn);
     if (qy > nn) qy = nn;
-    const size_t per_wp = lin_doubles_per_wp(nj, p.nobs);
-    int w = (int)((avail - L.lin) / per_wp);   // the linearisation may use the QP's work vectors too (layout)
+    int w = (int)((q.avail - L.lin) / q.per_wp);   // the linearisation may use the QP's work vectors too (layout)
     if (w < 1) return hipErrorInvalidValue;
     w = (p.H + (p.H + w - 1) / w - 1) / ((p.H + w - 1) / w);   // equal tiles: ceil(H / number of tiles)
     p.qy = qy;
     p.lin_w = w;
-    const size_t need = std::max((size_t)L.total_fixed + (size_t)qy * nn, (size_t)L.lin + (size_t)w * per_wp);
+    const size_t need = std::max((size_t)L.total_fixed + (size_t)qy * nn, (size_t)L.lin + (size_t)w * q.per_wp);
     const size_t lds = need * 8;
-    switch (nj * 1000 + QB) {
-    case 2096: return launch_fused_inst<2, 96>(p, lds, s CFS_SOFT_ARG);
-    case 3096: return launch_fused_inst<3, 96>(p, lds, s CFS_SOFT_ARG);
-    case 4096: return launch_fused_inst<4, 96>(p, lds, s CFS_SOFT_ARG);
-    case 5096: return launch_fused_inst<5, 96>(p, lds, s CFS_SOFT_ARG);
-    case 6096: return launch_fused_inst<6, 96>(p, lds, s CFS_SOFT_ARG);
-    case 2160: return launch_fused_inst<2, 160>(p, lds, s CFS_SOFT_ARG);
-    case 4160: return launch_fused_inst<4, 160>(p, lds, s CFS_SOFT_ARG);
-    case 5160: return launch_fused_inst<5, 160>(p, lds, s CFS_SOFT_ARG);
-    case 6160: return launch_fused_inst<6, 160>(p, lds, s CFS_SOFT_ARG);
-    case 3160: return launch_fused_inst<3, 160>(p, lds, s CFS_SOFT_ARG);
-    case 3256: return launch_fused_inst<3, 256>(p, lds, s CFS_SOFT_ARG);
-    case 4256: return launch_fused_inst<4, 256>(p, lds, s CFS_SOFT_ARG);
-    case 5256: return launch_fused_inst<5, 256>(p, lds, s CFS_SOFT_ARG);
-    case 6256: return launch_fused_inst<6, 256>(p, lds, s CFS_SOFT_ARG);
+    switch (nj * 1000 + q.QB) {
+    case 2096: return launch_fused_inst<2, 96, JAC, SOFT>(p, lds, s, sp);
+    case 3096: return launch_fused_inst<3, 96, JAC, SOFT>(p, lds, s, sp);
+    case 4096: return launch_fused_inst<4, 96, JAC, SOFT>(p, lds, s, sp);
+    case 5096: return launch_fused_inst<5, 96, JAC, SOFT>(p, lds, s, sp);
+    case 6096: return launch_fused_inst<6, 96, JAC, SOFT>(p, lds, s, sp);
+    case 2160: return launch_fused_inst<2, 160, JAC, SOFT>(p, lds, s, sp);
+    case 4160: return launch_fused_inst<4, 160, JAC, SOFT>(p, lds, s, sp);
+    case 5160: return launch_fused_inst<5, 160, JAC, SOFT>(p, lds, s, sp);
+    case 6160: return launch_fused_inst<6, 160, JAC, SOFT>(p, lds, s, sp);
+    case 3160: return launch_fused_inst<3, 160, JAC, SOFT>(p, lds, s, sp);
+    case 3256: return launch_fused_inst<3, 256, JAC, SOFT>(p, lds, s, sp);
+    case 4256: return launch_fused_inst<4, 256, JAC, SOFT>(p, lds, s, sp);
+    case 5256: return launch_fused_inst<5, 256, JAC, SOFT>(p, lds, s, sp);
+    case 6256: return launch_fused_inst<6, 256, JAC, SOFT>(p, lds, s, sp);
     default: return hipErrorInvalidValue;
     }
 }
+
+// The one place CFS_TIER, CFS_JAC and CFS_SOFT are read (Makefile: one object per tier and variant): this object's launcher, and,
+// in the tier's default object only, its capacity test.
+template hipError_t launch_fused_tier<CFS_TIER, CFS_JAC, CFS_SOFT>(int, FusedParams, hipStream_t, const SoftParams *);
+#if !CFS_JAC && !CFS_SOFT
+template bool fused_fits_tier<CFS_TIER>(int, int, int);
+#endif

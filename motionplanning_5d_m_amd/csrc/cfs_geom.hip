@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void cfs_dist_arm_kernel(DistArmParams P)
 }
 
 // dist_arm with the analytic gradient (API entry cfs_dist_arm_grad): one thread per configuration, the same chain
-// (arm_chain) and winner tangent (winner_grad) as the solver's analytic linearisation phase (cfs_fused.hip, CFS_JAC)
+// (arm_chain) and winner tangent (winner_grad) as the solver's analytic linearisation phase (cfs_fused.hip, JAC instantiations)
 __global__ __launch_bounds__(256) void cfs_dist_arm_grad_kernel(DistArmParams P)
 {
     __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];

@@ -1,6 +1,9 @@
 #!/bin/bash
 # Developer aid: build an A/B variant of the library next to libcfs_hip.so without touching it.
 # usage: tools/build_variant.sh <name> "<extra flags for the fused-solver objects>" ["<W2M_FLAGS>" ["<W2S_FLAGS>"]]   -> motionplanning_5d_m_amd/libcfs_<name>.so
+# FUSED_SRC / DEVICE_H: another revision of cfs_fused.hip / cfs_device.h, built with this tree's Makefile and cfs_api.o, so it must
+# share their interface (one object per tier and variant: CFS_TIER, CFS_JAC, CFS_SOFT, launch_fused_tier / fused_fits_tier).
+# Revisions from before that interface need their own Makefile and cfs_api.hip: check out the whole revision instead.
 set -e
 D=$(cd "$(dirname "$0")/../motionplanning_5d_m_amd/csrc" && pwd)
 T=$(mktemp -d)
