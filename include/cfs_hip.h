@@ -406,6 +406,36 @@ int cfs_rrt_grow(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out);
  * `stream`; routes can go straight into cfs_build_terms_from_ragged_routes_device */
 int cfs_rrt_grow_device(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out, void *stream);
 
+/* ---- best of K smoothed routes per slot ---------------------------------------------------------
+ * The reference grows num_seed RRT seeds, keeps the route with the FEWEST NODES, first seed on ties
+ * (Lib/functions/s_Parallel_rrt.m:27-28: [~, I] = min(routeL)), and runs one CFS on it (RRTstar_CFS.m:94-196).  Here all K
+ * routes of a slot are smoothed in one solve over S*K problems, stored slot-major (candidate s*K + k), and this entry keeps
+ * per slot the best SMOOTHED result instead: route length predicts neither the final cost nor whether the linearised QPs
+ * stay feasible, so ranking after the solve keeps every slot that any of its seeds can solve (the reference's pick is one
+ * of the K candidates, so the kept cost is never above it when that pick solves).  With n = iter_O - 1 (outer iterations
+ * run), the final cost is cost_all[n-1] (eval.cost_new) and the final violation viol_all[n-1]:
+ *   1. only candidates with route_ok[s*K+k] != 0 are eligible;
+ *   2. class A = status 0 or 1: the lowest final cost wins;
+ *   3. if class A is empty, class B = status 4 (CFS_SOFT_ENDED): the lowest final violation wins, then the lowest final cost;
+ *   4. if both are empty but some route was found: the found-route candidate with the lowest k, its status (2 or 3) as it
+ *      is, has_solution = 0;
+ *   5. if no route was found: selected = -1, has_solution = 0, and the slot's rows of `best` / best_viol_all are untouched;
+ *   6. ties go to the lowest k; a NaN final cost or violation, or n outside 1..MAX_O_ITER, makes a candidate ineligible
+ *      for class A / B (it can still be the candidate of rule 4).
+ * has_solution = 1 exactly when the winner comes from class A or B.  When cand_viol_all is NULL (allowed on STOP handles
+ * only) a status-4 candidate's violation counts as 0.
+ * The winner's rows are gathered into slot-major outputs: u, x_, cost_all, e_cost_all, e_u_all, viol_all (when
+ * best_viol_all is given), iter_O, total_iter, status.  One wavefront per slot, no atomics: the result is deterministic and
+ * depends on the slot's own K candidates only, not on S or on launch order.
+ * DEVICE pointers, enqueued on `stream`:  route_ok S*K;  cand: S*K rows (cfs_batch_out of the solve, all 8 arrays);
+ * cand_viol_all: S*K x MAX_O_ITER (viol_all of cfs_soft_results; required on a CFS_INFEAS_SOFTEN handle, may be NULL on a
+ * STOP one);  best: S rows (all 8 arrays), must not overlap cand;  best_viol_all: S x MAX_O_ITER or NULL (needs cand_viol_all);
+ * selected, has_solution: S.  CFS_ERR_INVALID_ARG for K outside 1..64, S < 1, a NULL handle, a NULL required array, or
+ * S*K > max_batch of the handle. */
+int cfs_select_best_device(cfs_problem *p, int S, int K, const int *route_ok, const cfs_batch_out *cand,
+                           const double *cand_viol_all, const cfs_batch_out *best, double *best_viol_all, int *selected,
+                           int *has_solution, void *stream);
+
 /* ---- developer / test entry points -------------------------------------------------------------------
  * No caller of the path needs these; they exist so that every shortcut the solver takes can be switched off and compared
  * under pytest (tests/test_gpu_shortcuts.py), and for the cycle-stamp / step-trace probes under tools/.  All state is per

@@ -199,6 +199,7 @@ SYMBOLS = [
     ("cfs_problem_get_infeasible_policy", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("cfs_soft_results", C.c_int, [_P, C.c_int, _P, _P]),
     ("cfs_dist_arm_grad", C.c_int, [C.POINTER(cfs_robot), C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
+    ("cfs_select_best_device", C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(cfs_batch_out), _P, C.POINTER(cfs_batch_out), _P, _P, _P, _P]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)

@@ -233,6 +233,10 @@ int cfs_fail(int code, const char *fmt, ...)
 }
 int cfs_current_device() { return g_device; }
 void cfs_build_dev_robot(const cfs_robot &r, DevRobot &d) { build_dev_robot(r, d); }
+void cfs_problem_shape(const cfs_problem *p, ProblemShape *out)
+{
+    *out = ProblemShape{p->device, p->d.max_batch, p->nn, p->nx, p->d.MAX_O_ITER, p->infeas};
+}
 
 // Tier of the fused kernel (cfs_device.h).  Two problems per CU win whenever they fit: measured on config 3, PSGCFS
 // 3.6 -> 2.3 ms per solve with w2s, CFS 5.8 -> 5.6 ms with w2m (its infeasibility proofs run active sets of ~100 rows).

@@ -7,6 +7,8 @@ int cfs_fail(int code, const char *fmt, ...);            // records the message 
 int cfs_current_device();                                // device chosen with cfs_set_device
 int cfs_check_robot(const cfs_robot *r, int nj);         // CFS_SUCCESS or an error code (message recorded)
 void cfs_build_dev_robot(const cfs_robot &r, DevRobot &d);
+struct ProblemShape { int device, max_batch, nn, nx, max_o_iter, infeas; };
+void cfs_problem_shape(const cfs_problem *p, ProblemShape *out);   // what entry points outside cfs_api.hip read of a handle
 
 #define CFS_HIPCHK(call)                                                                                     \
     do {                                                                                                     \

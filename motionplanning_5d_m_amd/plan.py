@@ -1,0 +1,266 @@
+"""RRTstar_CFS.m as one batched pipeline: K RRT seeds per slot, every route smoothed, the best smoothed result kept.
+
+The reference plans one start/goal pair (RRTstar_CFS.m): rounds of ``num_seed`` RRT seeds until one succeeds
+(Lib/functions/s_Parallel_rrt.m:14-28), the route with the fewest nodes (:27-28), one CFS on it (RRTstar_CFS.m:94-196).
+``RRTCFSPlanner.plan`` does that for S slots at once, entirely on the GPU:
+
+* grow   -- S*K trees in one ``cfs_rrt_grow_device`` launch; slots none of whose seeds found a route are regrown, alone, in
+            the next round (the reference's ``while all(path_fail)``);
+* build  -- one ``cfs_build_terms_from_ragged_routes_device`` call (cubic resampling to H+1 = 41 points + cost terms);
+* solve  -- one ``cfs_solve_batch_device`` over all S*K candidates (select="best") or over the S shortest routes
+            (select="shortest", the reference's rule);
+* select -- ``cfs_select_best_device``: per slot the best smoothed candidate by the rule of include/cfs_hip.h.
+
+This module packs arguments, indexes tensors (placeholder routes, the shortest route's index for select="shortest") and reads
+S fail flags per round; tree growth, resampling, the solves and the selection are HIP kernels.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import numbers
+from types import SimpleNamespace
+
+import numpy as np
+
+from . import _lib
+from .rrt import RRT_FANUC
+from .solvers import CFSBatch, _infeasible_args, _jacobian_code, _ptr, obs_to_array
+from .sysinfo import RRTstar_CFS_problem
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+SELECT = ("best", "shortest")
+MAX_SEEDS = 64               # one wavefront lane per candidate in cfs_select_best_device
+ROUND_SEED_STRIDE = 1_000_003  # R: the trees of round r use the generator seed `seed + r*R`
+
+
+def _batch_out(o):
+    b = _lib.cfs_batch_out()
+    b.u, b.x_, b.cost_all, b.e_cost_all, b.e_u_all = _ptr(o.u), _ptr(o.x_), _ptr(o.cost_all), _ptr(o.e_cost_all), _ptr(o.e_u_all)
+    b.iter_O, b.total_iter, b.status = _ptr(o.iter_O), _ptr(o.total_iter), _ptr(o.status)
+    return b
+
+
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def select_best_device(cfs, S, K, route_ok, cand, best, selected, has_solution, cand_viol_all=None, best_viol_all=None, stream=None):
+    """cfs_select_best_device on CUDA tensors: cand / best are CFSBatch.alloc_outputs-style namespaces of S*K / S rows,
+    route_ok (S*K,) int32, selected / has_solution (S,) int32, viol_all (rows, MAX_O_ITER) float64 or None."""
+    if stream is None:
+        stream = torch.cuda.current_stream(route_ok.device).cuda_stream
+    _lib.check(cfs._lib.cfs_select_best_device(cfs._h, int(S), int(K), _ptr(route_ok), C.byref(_batch_out(cand)), _ptr(cand_viol_all),
+                                               C.byref(_batch_out(best)), _ptr(best_viol_all), _ptr(selected), _ptr(has_solution),
+                                               C.c_void_p(stream)))
+
+
+class RRTCFSPlanner:
+    """RRTstar_CFS.m's pipeline for up to max_slots (start, goal) slots per call, num_seed RRT seeds per slot.
+
+    select="best": every seed's route is smoothed and the best smoothed result per slot is kept (cfs_select_best_device:
+    status 0/1 by lowest final cost, else status 4 by lowest final violation then cost).  select="shortest": the reference's
+    rule -- the route with the fewest nodes, first seed on ties (s_Parallel_rrt.m:27-28) -- then one CFS per slot.
+    The cost family is RRTstar_CFS.m:124-187's (sysinfo.RRTstar_CFS_problem: M200i, H = 40); the obstacles are `pobs`, with
+    margins obs{j}.epsilon (CFS) or obs{j}.D (PSGCFS).  Arguments are validated before anything touches the device."""
+
+    def __init__(self, pobs, sys_rrt, region_g, region_s, sample_off, ROBOT="M200i", rrt_solver="RRT", num_seed=6, mode="CFS",
+                 select="best", on_infeasible="stop", soft_weight=None, jacobian="fd_literal", max_slots=256, device=None):
+        if select not in SELECT:
+            raise ValueError(f"select must be one of {SELECT}, not {select!r}")
+        if not _is_int(num_seed) or not 1 <= num_seed <= MAX_SEEDS:
+            raise ValueError(f"num_seed must be an integer in 1..{MAX_SEEDS}, not {num_seed!r}")
+        if not _is_int(max_slots) or max_slots < 1:
+            raise ValueError(f"max_slots must be a positive integer, not {max_slots!r}")
+        if not isinstance(mode, str) or mode not in _lib.MODE:
+            raise ValueError(f"mode must be one of {sorted(_lib.MODE)}, not {mode!r}")
+        if rrt_solver not in ("RRT", "RRT*"):
+            raise ValueError(f"rrt_solver must be 'RRT' or 'RRT*', not {rrt_solver!r}")
+        if ROBOT != "M200i":
+            raise ValueError(f"the cost family is RRTstar_CFS.m's (M200i); ROBOT={ROBOT!r} is not supported")
+        if int(getattr(sys_rrt, "nstate", 0)) != 5:
+            raise ValueError("sys_rrt.nstate must be 5 (the M200i's joints)")
+        _jacobian_code(jacobian)
+        _infeasible_args(on_infeasible, soft_weight)
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch is not None and torch.cuda.is_available() else torch.device("cuda", 0)
+        elif _is_int(device):
+            device = torch.device("cuda", int(device))
+        else:
+            device = torch.device(device)
+            if device.type != "cuda":
+                raise ValueError(f"device must be a CUDA (HIP) device, not {device}")
+            if device.index is None:
+                device = torch.device("cuda", 0)
+        self.select, self.K, self.max_slots, self.mode = select, int(num_seed), int(max_slots), mode
+        self.on_infeasible, self.device, self.nj = on_infeasible, device, 5
+        self.rrt = RRT_FANUC(pobs, sys_rrt, sys_rrt.goal_th, region_g, region_s, sample_off, ROBOT, rrt_solver)
+        self.N = RRT_FANUC.MAX_ITER + 1
+        _, self.sys_cfs, _ = RRTstar_CFS_problem(np.stack([np.asarray(sys_rrt.x0, float), np.asarray(sys_rrt.goal_th, float)], axis=1))
+        margin = [o["epsilon"] if mode == "CFS" else o["D"] for o in pobs]
+        self.cfs = CFSBatch(self.sys_cfs, len(pobs), margin, mode=mode, max_batch=self.max_slots * self.K, device=device.index,
+                            jacobian=jacobian, on_infeasible=on_infeasible, soft_weight=soft_weight)
+        one = torch.tensor(obs_to_array(pobs), dtype=torch.float64, device=device)
+        self._obs = one.unsqueeze(0).expand(self.max_slots * self.K, -1, -1).contiguous()
+
+    def close(self):
+        self.cfs.close()
+
+    # ---- argument checks (no GPU call before they pass) --------------------------------------------------------------------
+    def _pair(self, x0, goal):
+        def conv(v, name):
+            if torch is not None and isinstance(v, torch.Tensor):
+                if v.device != self.device:
+                    raise ValueError(f"{name} is on {v.device}, the planner on {self.device}")
+                if not v.dtype.is_floating_point:
+                    raise ValueError(f"{name} must be a floating-point tensor, not {v.dtype}")
+                t = v.to(torch.float64)
+            else:
+                t = np.asarray(v, dtype=float)          # goes to the device once validated
+                if not np.isfinite(t).all():
+                    raise ValueError(f"{name} must be finite")
+            if tuple(t.shape[-1:]) != (self.nj,) or t.ndim not in (1, 2):
+                raise ValueError(f"{name} must have shape ({self.nj},) or (S, {self.nj}), not {tuple(t.shape)}")
+            return t
+        x0, goal = conv(x0, "x0"), conv(goal, "goal")
+        S = max(x0.shape[0] if x0.ndim == 2 else 1, goal.shape[0] if goal.ndim == 2 else 1)
+        for t, name in ((x0, "x0"), (goal, "goal")):
+            if t.ndim == 2 and t.shape[0] != S:
+                raise ValueError(f"x0 and goal disagree on S: {tuple(x0.shape)} vs {tuple(goal.shape)}")
+        if S < 1 or S > self.max_slots:
+            raise ValueError(f"S={S} outside 1..max_slots={self.max_slots}")
+        return S, x0, goal
+
+    def _on_device(self, t, S):
+        if not (torch is not None and isinstance(t, torch.Tensor)):
+            t = torch.tensor(t, dtype=torch.float64, device=self.device)
+        if t.ndim == 1:
+            t = t.unsqueeze(0).expand(S, -1)
+        return t.contiguous()
+
+    # ---- the pipeline ----------------------------------------------------------------------------------------------------
+    def plan(self, x0, goal, seed, max_rounds=50, stream=None, want_candidates=False, max_draws=None, timings=None):
+        """Plan S slots: x0, goal (S, 5) or (5,) (one shared pair), CUDA tensors on the planner's device or array-likes.
+        seed: the library's counter-based RRT generator; round r grows its trees with seed + r*ROUND_SEED_STRIDE, tree index
+        s*K + k in round 0 and (rank of slot s among the slots still open)*K + k later.  max_draws: uniforms a tree may consume
+        (cfs_rrt_desc.max_draws; default the library's).  Returns a namespace of CUDA tensors, one row per slot:
+          u, x_, cost_all, e_cost_all, e_u_all, cost (final cost cost_all[iter_O-2], NaN without one), iter_O, total_iter,
+          status (-1: no route found), has_solution (1: status 0/1, or 4 when no seed reached 0/1), selected (seed k, -1: no
+          route), route (S, MAX_ITER+1, 5) / route_len (the selected route; 0 rows without one), rounds;
+          on "soften" also viol_all, n_soft.
+        want_candidates: also .candidates -- the S*K solve outputs (select="best"), route, route_len, route_ok of every seed.
+        timings: a dict to receive the milliseconds of the grow / build / solve / select parts (events on the stream)."""
+        if not _is_int(seed) or seed < 0:
+            raise ValueError(f"seed must be a non-negative integer, not {seed!r}")
+        if not _is_int(max_rounds) or max_rounds < 1:
+            raise ValueError(f"max_rounds must be a positive integer, not {max_rounds!r}")
+        if max_draws is not None and (not _is_int(max_draws) or max_draws < 1):
+            raise ValueError(f"max_draws must be a positive integer, not {max_draws!r}")
+        if timings is not None and not isinstance(timings, dict):
+            raise ValueError("timings must be a dict")
+        S, x0, goal = self._pair(x0, goal)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        elif not isinstance(stream, torch.cuda.Stream):
+            raise ValueError("stream must be a torch.cuda.Stream")
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            return self._plan(S, self._on_device(x0, S), self._on_device(goal, S), int(seed), int(max_rounds), stream,
+                              want_candidates, max_draws, timings)
+
+    def _plan(self, S, x0, goal, seed, max_rounds, stream, want_candidates, max_draws, timings):
+        K, N, nj, dev, st = self.K, self.N, self.nj, self.device, stream.cuda_stream
+        ev = {}
+        mark = (lambda k: ev.setdefault(k, torch.cuda.Event(enable_timing=True)).record(stream)) if timings is not None else (lambda k: None)
+        i32 = dict(dtype=torch.int32, device=dev)
+        mark("grow0")
+        # ---- grow: rounds of K seeds per open slot (s_Parallel_rrt.m:14-28) ----
+        SK = S * K
+        route = torch.zeros(SK, N, nj, dtype=torch.float64, device=dev)
+        route_len = torch.zeros(SK, **i32)
+        route_ok = torch.zeros(SK, **i32)
+        rounds = torch.zeros(S, **i32)
+        open_slots = torch.arange(S, device=dev)
+        kk = torch.arange(K, device=dev)
+        for r in range(max_rounds):
+            n_open = int(open_slots.numel())
+            if n_open == 0:
+                break
+            tx0 = x0[open_slots].repeat_interleave(K, 0).contiguous()
+            tg = goal[open_slots].repeat_interleave(K, 0).contiguous()
+            g = self.rrt.grow_device(n_open * K, seed + r * ROUND_SEED_STRIDE, dev, max_draws=max_draws, x0=tx0, goal=tg, stream=st)
+            ok = (g.fail == 0).view(n_open, K)
+            slot_ok = ok.any(dim=1)
+            rounds[open_slots] = r + 1
+            dst = (open_slots[:, None] * K + kk[None, :])[slot_ok].reshape(-1)     # candidate rows of the slots done this round
+            src = (torch.arange(n_open, device=dev)[:, None] * K + kk[None, :])[slot_ok].reshape(-1)
+            route[dst] = g.route[src]
+            route_len[dst] = g.route_len[src]
+            route_ok[dst] = ok.reshape(-1)[src].to(torch.int32)
+            open_slots = open_slots[~slot_ok]                                     # boolean index: the one host read of a round
+        # failed trees: the 2-point placeholder start -> goal keeps the batch at S*K problems; they are never selected
+        bad = route_ok == 0
+        route[:, 0] = torch.where(bad[:, None], x0.repeat_interleave(K, 0), route[:, 0])
+        route[:, 1] = torch.where(bad[:, None], goal.repeat_interleave(K, 0), route[:, 1])
+        route_len = torch.where(bad, torch.full_like(route_len, 2), route_len)
+        mark("build0")
+        viol = None
+        if self.select == "best":
+            terms = self.cfs.build_terms_from_ragged_routes_device(route, route_len, stream=st)
+            mark("solve0")
+            cand = self.cfs.solve_device(*terms, self._obs[:SK], stream=st)
+            if self.on_infeasible == "soften":
+                v, ns = self.cfs.soft_results(SK)
+                viol, n_soft = torch.tensor(v, device=dev), torch.tensor(ns, device=dev)
+            mark("select0")
+            rows_ok, kpick = route_ok, None
+        else:
+            lens = torch.where(route_ok != 0, route_len, torch.full_like(route_len, torch.iinfo(torch.int32).max)).view(S, K)
+            kpick = torch.argmin(lens, dim=1)                                         # first minimum: the first seed wins ties
+            found = route_ok.view(S, K).any(dim=1)
+            pick = torch.arange(S, device=dev) * K + kpick
+            terms = self.cfs.build_terms_from_ragged_routes_device(route[pick].contiguous(), route_len[pick].contiguous(), stream=st)
+            mark("solve0")
+            cand = self.cfs.solve_device(*terms, self._obs[:S], stream=st)
+            if self.on_infeasible == "soften":
+                v, ns = self.cfs.soft_results(S)
+                viol, n_soft = torch.tensor(v, device=dev), torch.tensor(ns, device=dev)
+            mark("select0")
+            rows_ok = found.to(torch.int32)                                         # the K = 1 selection gathers the S rows
+        Kc = K if self.select == "best" else 1
+        best = self.cfs.alloc_outputs(S, dev)
+        best.status.fill_(-1)
+        selected, has_solution = torch.empty(S, **i32), torch.empty(S, **i32)
+        best_viol = torch.zeros(S, self.cfs.K, dtype=torch.float64, device=dev) if viol is not None else None
+        select_best_device(self.cfs, S, Kc, rows_ok, cand, best, selected, has_solution, viol, best_viol, stream=st)
+        mark("end")
+        if kpick is not None:                                                         # shortest: the seed is the argmin
+            selected = torch.where(selected >= 0, kpick.to(torch.int32), selected)
+        have = selected >= 0
+        crow = torch.arange(S, device=dev) * K + selected.clamp(min=0)
+        res = best
+        it = res.iter_O.long()
+        res.cost = torch.where(it >= 2, res.cost_all.gather(1, (it - 2).clamp(min=0)[:, None])[:, 0],
+                               torch.full_like(res.cost_all[:, 0], float("nan")))
+        res.has_solution, res.selected, res.rounds = has_solution, selected, rounds
+        res.route = torch.where(have[:, None, None], route[crow], torch.zeros_like(route[crow]))
+        res.route_len = torch.where(have, route_len[crow], torch.zeros_like(route_len[crow]))
+        if viol is not None:
+            res.viol_all = best_viol
+            nrow = crow if self.select == "best" else torch.arange(S, device=dev)
+            res.n_soft = torch.where(have, n_soft[nrow], torch.zeros_like(n_soft[nrow]))
+        if want_candidates:
+            c = SimpleNamespace(route=route, route_len=route_len, route_ok=route_ok)
+            if self.select == "best":
+                c.u, c.x_, c.cost_all, c.e_cost_all, c.e_u_all = cand.u, cand.x_, cand.cost_all, cand.e_cost_all, cand.e_u_all
+                c.iter_O, c.total_iter, c.status = cand.iter_O, cand.total_iter, cand.status
+                if viol is not None:
+                    c.viol_all, c.n_soft = viol, n_soft
+            res.candidates = c
+        if timings is not None:
+            stream.synchronize()
+            timings.update(grow=ev["grow0"].elapsed_time(ev["build0"]), build=ev["build0"].elapsed_time(ev["solve0"]),
+                           solve=ev["solve0"].elapsed_time(ev["select0"]), select=ev["select0"].elapsed_time(ev["end"]))
+        return res
