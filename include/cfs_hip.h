@@ -441,7 +441,7 @@ int cfs_select_best_device(cfs_problem *p, int S, int K, const int *route_ok, co
  * under pytest (tests/test_gpu_shortcuts.py), and for the cycle-stamp / step-trace probes under tools/.  All state is per
  * handle: nothing is read from the environment, nothing is process-wide.  Results with and without each switch are the
  * same optimum of the same strictly convex QPs; what the tests assert bit for bit, and what to a tolerance, is stated there. */
-#define CFS_DBG_GATHER_ROLLOUTS 1   /* H = QQ: load the precomputed rollouts of the family-matrix columns instead of prefix sums in LDS */
+/* value 1 is retired (it was CFS_DBG_GATHER_ROLLOUTS): do not reuse it */
 #define CFS_DBG_NO_REFINE 2         /* no iterative refinement of the step directions                                                  */
 #define CFS_DBG_NO_WARM_START 8     /* every QP starts from the empty active set                                                       */
 #define CFS_DBG_NO_CERTIFICATE 16   /* CFS_FANUC: no step-free infeasibility certificate (infeasible QPs are proven by the dual steps)  */

@@ -203,7 +203,7 @@ SYMBOLS = [
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)
-DBG = {"gather_rollouts": 1, "no_refine": 2, "no_warm_start": 8, "no_certificate": 16, "no_prune": 32, "no_auto_order": 64, "tier_w1": 128}
+DBG = {"no_refine": 2, "no_warm_start": 8, "no_certificate": 16, "no_prune": 32, "no_auto_order": 64, "tier_w1": 128}
 
 _lib = None
 

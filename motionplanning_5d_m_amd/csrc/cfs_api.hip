@@ -174,7 +174,6 @@ struct cfs_problem {
     DevBuf<double> F1, F2, Cq;   // per-problem cost terms from (x0, xg), set by cfs_set_state_cost
     DevBuf<DevCost> cost;        // structure of QQ (handles created from the cost weights)
     std::vector<double> QQ_host; // what cfs_problem_family hands back
-    DevBuf<double> Mr[6];   // rollouts (Bvel*, Bpos*) of the columns of M1n, M2n, Hq
     // workspace (max_batch problems)
     DevBuf<double> x0, qu, dist, grad, Yg, Pt, u_hist, qu_hist;
     DevBuf<int> noise_row, linkid, pool_flag;
@@ -212,7 +211,6 @@ struct cfs_problem {
         ev.clear(); ev_free.clear();
         rb.release(); QQ.release(); Hinv.release(); Hq.release();
         M1n.release(); M2n.release(); Pt.release(); u_hist.release(); qu_hist.release();
-        for (auto &m : Mr) m.release();
         F1.release(); F2.release(); Cq.release(); cost.release();
         lim.release(); maxin.release(); margin.release(); x0.release(); qu.release(); dist.release();
         grad.release(); Yg.release(); noise_row.release(); order.release(); okey.release(); order_user.release();
@@ -397,26 +395,6 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
         lmax_vel = lambda_max_upper(nn, G);
         if (desc->mode == CFS_MODE_CFS) lmax_H = lambda_max_upper(nn, Hs);   // not 1/alpha: alpha is the caller's PSGCFS step
     }
-    // rollouts of every family column (double integrator: Bvel w = dt*cumsum(w), Bpos w = sum (i-k+1/2) dt^2 w_k)
-    std::vector<double> Mroll[6];
-    {
-        const std::vector<double> *src[3] = {&M1n, &M2n, &Hq};
-        for (int m = 0; m < 3; ++m) {
-            Mroll[2 * m].assign((size_t)nn * nn, 0.0);
-            Mroll[2 * m + 1].assign((size_t)nn * nn, 0.0);
-            for (int col = 0; col < nn; ++col)
-                for (int c = 0; c < nj; ++c) {
-                    long double sv = 0.0L;
-                    for (int i = 0; i < H; ++i) {
-                        long double sp = 0.0L;
-                        sv += (*src[m])[(i * nj + c) + (size_t)col * nn];
-                        for (int k = 0; k <= i; ++k) sp += ((long double)(i - k) + 0.5L) * (*src[m])[(k * nj + c) + (size_t)col * nn];
-                        Mroll[2 * m][(i * nj + c) + (size_t)col * nn] = (double)((long double)dt * sv);
-                        Mroll[2 * m + 1][(i * nj + c) + (size_t)col * nn] = (double)((long double)dt * (long double)dt * sp);
-                    }
-                }
-        }
-    }
     cfs_problem *p = new (std::nothrow) cfs_problem();
     if (!p) return fail(CFS_ERR_ALLOC, "out of host memory");
     p->d = *desc;
@@ -434,7 +412,6 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
     hipError_t e = hipSetDevice(p->device);
 #define A_(buf, count) if (e == hipSuccess) e = p->buf.alloc(count)
     A_(rb, 1); A_(QQ, (size_t)nn * nn); A_(Hinv, (size_t)nn * nn);
-    for (int m = 0; m < 6; ++m) { A_(Mr[m], (size_t)nn * nn); }
     A_(M1n, (size_t)nn * nn); A_(M2n, (size_t)nn * nn); A_(Hq, (size_t)nn * nn); A_(Pt, Pn * pt_stride(nn)); A_(lim, nj); A_(maxin, nn); A_(margin, desc->nobs);
     A_(x0, Bm * nn); A_(qu, Bm * nn); A_(dist, Bm * desc->nobs * H); A_(grad, Bm * desc->nobs * H * nj);
     A_(Yg, Pn * nn * nn); A_(pool_flag, Pn * 16);
@@ -444,7 +421,6 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
 #define U_(buf, src, count) if (e == hipSuccess) e = hipMemcpy(p->buf.p, src, (count) * sizeof(*p->buf.p), hipMemcpyHostToDevice)
     U_(rb, &p->hrobot, 1); U_(QQ, desc->QQ, (size_t)nn * nn); U_(Hinv, Hinv.data(), (size_t)nn * nn);
     U_(M1n, M1n.data(), (size_t)nn * nn); U_(M2n, M2n.data(), (size_t)nn * nn); U_(Hq, Hq.data(), (size_t)nn * nn);
-    for (int m = 0; m < 6; ++m) { U_(Mr[m], Mroll[m].data(), (size_t)nn * nn); }
     U_(lim, desc->lim, nj); U_(margin, desc->margin, desc->nobs);
     if (desc->mode == CFS_MODE_CFS) { U_(maxin, desc->MAX_input, nn); }
     else if (e == hipSuccess) e = hipMemset(p->maxin.p, 0, nn * sizeof(double));
@@ -592,14 +568,11 @@ static void fill_fused_family(const cfs_problem *p, FusedParams &fp, int B)
     fp.has_bounds = p->d.mode == CFS_MODE_CFS; fp.max_o_iter = p->d.MAX_O_ITER;
     fp.dt = p->d.robot.delta_t; fp.alpha = p->d.alpha; fp.epsilon_O = p->d.epsilon_O; fp.lmax_vel = p->lmax_vel; fp.lmax_H = p->lmax_H;
     fp.M1 = p->M1n.p; fp.M2 = p->M2n.p; fp.M3 = p->Hq.p; fp.QQ = p->QQ.p; fp.cost = p->cost.p;
-    fp.M1v = p->Mr[0].p; fp.M1p = p->Mr[1].p; fp.M2v = p->Mr[2].p; fp.M2p = p->Mr[3].p; fp.M3v = p->Mr[4].p; fp.M3p = p->Mr[5].p;
     fp.lim = p->lim.p; fp.maxin = p->maxin.p; fp.margin = p->margin.p;
     fp.x0 = p->x0.p;
     fp.Yg = p->Yg.p; fp.Pt = p->Pt.p; fp.pt_stride = pt_stride(p->nn); fp.pool_flag = p->pool_flag.p; fp.pool_n = p->pool_n;
-    // kernel switch word: bit 0 = roll w = H^{-1} n_p out in LDS (the default since round 2: +2-4 % on config 3 CFS, a third of the
-    // gather's L2 loads; CFS_DBG_GATHER_ROLLOUTS loads the precomputed rollouts of the family matrices instead), bit 1 = no
-    // refinement, bit 3 = no warm start, bit 4 = no step-free certificate
-    fp.opt = ((p->dbg_mask & CFS_DBG_GATHER_ROLLOUTS) ? 0 : 1) | (p->dbg_mask & (CFS_DBG_NO_REFINE | CFS_DBG_NO_WARM_START | CFS_DBG_NO_CERTIFICATE));
+    // kernel switch word: bit 1 = no refinement, bit 3 = no warm start, bit 4 = no step-free certificate
+    fp.opt = p->dbg_mask & (CFS_DBG_NO_REFINE | CFS_DBG_NO_WARM_START | CFS_DBG_NO_CERTIFICATE);
     fp.polish_tol = p->dbg_polish_tol;
     fp.warm_max = p->dbg_warm_max;
     fp.no_prune = (p->dbg_mask & CFS_DBG_NO_PRUNE) ? 1 : 0;
@@ -851,8 +824,8 @@ int cfs_get_cost(cfs_problem *p, int B, const double *u, const double *ff, const
 int cfs_debug_set_options(cfs_problem *p, int mask, int warm_max, double polish_tol)
 {
     if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    const int known = CFS_DBG_GATHER_ROLLOUTS | CFS_DBG_NO_REFINE | CFS_DBG_NO_WARM_START | CFS_DBG_NO_CERTIFICATE | CFS_DBG_NO_PRUNE |
-                      CFS_DBG_NO_AUTO_ORDER | CFS_DBG_TIER_W1;
+    const int known = CFS_DBG_NO_REFINE | CFS_DBG_NO_WARM_START | CFS_DBG_NO_CERTIFICATE | CFS_DBG_NO_PRUNE | CFS_DBG_NO_AUTO_ORDER |
+                      CFS_DBG_TIER_W1;
     if (mask & ~known) return fail(CFS_ERR_INVALID_ARG, "unknown option bits 0x%x", mask & ~known);
     if (warm_max < 0 || warm_max > 64) return fail(CFS_ERR_INVALID_ARG, "warm_max %d outside 0..64", warm_max);
     p->dbg_mask = mask; p->dbg_warm_max = warm_max;

@@ -97,7 +97,6 @@ struct FusedParams {
     double polish_tol;           // relative drift |slack| / (1 + |bound|) of an active row at the optimum that triggers the projection
     double lmax_H;               // rigorous upper bound of lambda_max(H), H = QQ symmetrised (CFS) | I (PSGCFS projection)
     const double *M1, *M2, *M3;  // nn x nn column-major: H^{-1}Bpos', H^{-1}Bvel', H^{-1} (natural row order)
-    const double *M1v, *M1p, *M2v, *M2p, *M3v, *M3p;   // Bvel* and Bpos* of every column of M1, M2, M3
     const double *QQ;            // raw sys_info.QQ
     const DevCost *cost;         // structure of QQ (null: dense QQ only)
     const double *lim, *maxin, *margin;
@@ -114,7 +113,7 @@ struct FusedParams {
     int dbg_b, dbg_cap;
     const int *order;            // optional launch order: workgroup w solves problem order[w] (a permutation of 0..B-1); NULL = identity
     unsigned long long *stamps;  // optional: 16 cycle accumulators per problem (developer aid)
-    int opt;                     // developer A/B switches (bit 0: gather w only and roll it on the fly)
+    int opt;                     // developer A/B switches (bit 1: no refinement, bit 3: no warm start, bit 4: no certificate)
     double *u_hist;              // CFS: B x max_o_iter x nn log of u per outer iteration (cost history computed afterwards)
     double *u_log;               // test aid (cfs_debug_log_u): the same log for either solver, no effect on the solve; may be null
     // mesh obstacles: the last nmesh of the nobs obstacles; their rows come from cfs_linearize_mesh_kernel, which needs the

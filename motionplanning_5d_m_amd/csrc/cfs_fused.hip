@@ -33,25 +33,15 @@ namespace {
 #define STAMP_IF(k) if (P.stamps) { const unsigned long long t_ = clock64(); if (tid == 0) s_acc[k] += t_ - t0_; t0_ = t_; }
 #define STAMP(k) do { STAMP_IF(k) } while (0)
 
-#ifndef CFS_CERT_AT
-#define CFS_CERT_AT 6
-#endif
-constexpr int CERT_AT = CFS_CERT_AT;    // main-loop steps of a QP before the step-free infeasibility certificate is asked
+constexpr int CERT_AT = 6;              // main-loop steps of a QP before the step-free infeasibility certificate is asked
 #ifndef CFS_WG_PER_CU
 #define CFS_WG_PER_CU 1                   // workgroups resident per CU (2: half the LDS and registers each)
 #endif
-#ifndef CFS_REF_A
-#define CFS_REF_A 1e-4                   // refinement of a step direction continues while |r'rho| > A * max(|delta|, tol * n'H^-1 n) ...
-#define CFS_REF_B 1e-9                   // ... or max|rho| > B * max|d|  (rho_a = n_a'z, zero in exact arithmetic)
-#endif
-#ifndef CFS_MV_BATCH
-#define CFS_MV_BATCH 16                  // QQ*u: loads in flight per thread
-#endif
+constexpr double REF_A = 1e-4;           // refinement of a step direction continues while |r'rho| > A * max(|delta|, tol * n'H^-1 n) ...
+constexpr double REF_B = 1e-9;           // ... or max|rho| > B * max|d|  (rho_a = n_a'z, zero in exact arithmetic)
+constexpr int MV_BATCH = 16;             // QQ*u: loads in flight per thread
 #ifndef CFS_TU
 #define CFS_TU 8                         // tail columns of P / global rows of Y loaded per batch (independent loads in flight)
-#endif
-#ifndef CFS_LIN_UNROLL
-#define CFS_LIN_UNROLL 0                 // 1: two segment pairs per thread in flight in the distance loops of the linearisation
 #endif
 #ifndef CFS_PR
 #define CFS_PR 64                        // columns of each inverse-Gram row kept in registers
@@ -730,9 +720,6 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     STAMP(10);                                  // 10: sincos + link transforms
                     // Base-pose distance of every link (dist_arm_3D_200i_2.m:16-26), link index slow so the point /
                     // segment branch of distLinSeg is wave-uniform.
-#if CFS_LIN_UNROLL
-#pragma unroll 2
-#endif
                     for (int e = tid; e < NJ * Wc * nseg; e += FT) {
                         const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
                         s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NVT + kvoff(k0 + 1)) * 6, s_ob + j * 6);
@@ -766,9 +753,6 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         offs[0] = 0;
 #pragma unroll
                         for (int k1 = 1; k1 <= NJ; ++k1) offs[k1] = offs[k1 - 1] + s_cnt[k1 - 1] * 2 * k1;
-#if CFS_LIN_UNROLL
-#pragma unroll 2
-#endif
                         for (int e = tid; e < offs[NJ]; e += FT) {
                             int k1 = 1, ent = 0, v = 1;
 #pragma unroll
@@ -921,30 +905,25 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                 if (lane < H) { zb[k] = z; zb[HN + k] = sv; zb[2 * HN + k] = spo; }
             }
         };
-        // wb = (w, Bvel w, Bpos w) for w = H^{-1} n_code (H = QQ): a gather of <= NJ columns of the family matrices and of their
-        // precomputed rollouts -- no prefix sums; the caller puts a barrier behind it
+        // wb[0, HN) = w = H^{-1} n_code (H = QQ): a gather of <= NJ columns of the family matrices; the caller puts a barrier
+        // behind it and rolls w out in LDS (roll_lds: wb[HN, 3HN) = Bvel w, Bpos w)
         auto gather_w = [&](int code) {
             const int ptype_ = code >> 16, pi_ = (code >> 8) & 0xff, pj_ = code & 0xff;
             for (int k = tid; k < HN; k += FT) {
-                double w0, w1, w2;
+                double w0;
                 if (ptype_ == CT_COL) {
-                    w0 = w1 = w2 = 0.0;
+                    w0 = 0.0;
 #pragma unroll
                     for (int cs = 0; cs < NJ; ++cs) {
                         const double gc = s_g[(pj_ * H + pi_) * NJ + cs];
-                        const size_t o = (size_t)(pi_ * NJ + cs) * nn + k;
-                        w0 += gc * P.M1[o];
-                        if (!(P.opt & 1)) { w1 += gc * P.M1v[o]; w2 += gc * P.M1p[o]; }
+                        w0 += gc * P.M1[(size_t)(pi_ * NJ + cs) * nn + k];
                     }
                 } else {
                     const bool vel = ptype_ == CT_VELP || ptype_ == CT_VELM;
                     const double sg = (ptype_ == CT_VELP || ptype_ == CT_BNDP) ? -1.0 : 1.0;
-                    const size_t o = (size_t)(pi_ * NJ + pj_) * nn + k;
-                    w0 = sg * (vel ? P.M2 : P.M3)[o];
-                    w1 = w2 = 0.0;
-                    if (!(P.opt & 1)) { w1 = sg * (vel ? P.M2v : P.M3v)[o]; w2 = sg * (vel ? P.M2p : P.M3p)[o]; }
+                    w0 = sg * (vel ? P.M2 : P.M3)[(size_t)(pi_ * NJ + pj_) * nn + k];
                 }
-                wb[k] = w0; wb[HN + k] = w1; wb[2 * HN + k] = w2;
+                wb[k] = w0;
             }
         };
         bool soft = false;                                  // SOFT: this iteration's hard QP was proven infeasible: solving the soft one
@@ -1101,7 +1080,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         if (c_all < 0) continue;
                         gather_w(c_all);
                         __syncthreads();
-                        if (P.opt & 1) { roll_lds<NJ>(wb, H, dt, tid); __syncthreads(); }
+                        roll_lds<NJ>(wb, H, dt, tid);
+                        __syncthreads();
                     }
                 if (tid < 64) {
                     for (int s1 = IDENT ? 0 : s0; s1 < (IDENT ? prev_q : s0 + 1); ++s1) {
@@ -1284,9 +1264,10 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     }
                     if (!polish && !IDENT) {
                     if (!have_w) {
-                    gather_w(pc);                          // w = H^{-1} n_p with its rollouts
+                    gather_w(pc);                          // w = H^{-1} n_p, then its rollouts
                     __syncthreads();
-                    if (P.opt & 1) { roll_lds<NJ>(wb, H, dt, tid); __syncthreads(); }
+                    roll_lds<NJ>(wb, H, dt, tid);
+                    __syncthreads();
                     have_w = true;
                     }
                     STAMP(3);                               // 3: w gather + rollout
@@ -1353,7 +1334,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         for (int w = 1; w < 4; ++w)
                             if (rx[12 + w] < t1) { t1 = rx[12 + w]; l = reinterpret_cast<int *>(rx + 16)[w]; }
                         const double ref = fmax(fabs(delta), DEP_TOL_F * spp);
-                        if (pass == 3 || (P.opt & 2) || !(fabs(rr) > CFS_REF_A * ref || rmax > CFS_REF_B * (dmax + 1e-300))) break;
+                        if (pass == 3 || (P.opt & 2) || !(fabs(rr) > REF_A * ref || rmax > REF_B * (dmax + 1e-300))) break;
                         }
                         enter_at_correction = false;
                         if (tid < qhi) {                                // dr = P rho ; r += dr   (projection: lambda -= P s)
@@ -1561,12 +1542,12 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
             for (int k = tid; k < HN; k += FT) {
                 double sa[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
                 int c = 0;
-                for (; c + CFS_MV_BATCH <= HN; c += CFS_MV_BATCH) {   // independent L2 loads in flight per thread
-                    double ld[CFS_MV_BATCH];
+                for (; c + MV_BATCH <= HN; c += MV_BATCH) {   // independent L2 loads in flight per thread
+                    double ld[MV_BATCH];
 #pragma unroll
-                    for (int j = 0; j < CFS_MV_BATCH; ++j) ld[j] = P.QQ[k + (size_t)(c + j) * nn];
+                    for (int j = 0; j < MV_BATCH; ++j) ld[j] = P.QQ[k + (size_t)(c + j) * nn];
 #pragma unroll
-                    for (int j = 0; j < CFS_MV_BATCH; ++j) sa[j & 7] += ld[j] * xs[c + j];
+                    for (int j = 0; j < MV_BATCH; ++j) sa[j & 7] += ld[j] * xs[c + j];
                 }
                 for (; c < HN; ++c) sa[0] += P.QQ[k + (size_t)c * nn] * xs[c];
                 const double s = ((sa[0] + sa[1]) + (sa[2] + sa[3])) + ((sa[4] + sa[5]) + (sa[6] + sa[7]));

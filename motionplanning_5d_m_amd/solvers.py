@@ -395,8 +395,8 @@ class CFSBatch:
 
     # ---- developer / test switches (cfs_debug_*, per handle) ---------------------------------------------
     def debug_options(self, warm_max=0, polish_tol=0.0, **flags):
-        """cfs_debug_set_options: flags from _lib.DBG (gather_rollouts, no_refine, no_warm_start, no_certificate, no_prune,
-        no_auto_order, tier_w1); no flags = the defaults."""
+        """cfs_debug_set_options: flags from _lib.DBG (no_refine, no_warm_start, no_certificate, no_prune, no_auto_order,
+        tier_w1); no flags = the defaults."""
         mask = 0
         for k, v in flags.items():
             if v:
