@@ -107,7 +107,8 @@ typedef struct cfs_batch_in {
     const double *xR1;    /* B x nstate    : sys_info.xR(:,1)                                       */
     const double *ff;     /* B x nn        : sys_info.ff                                            */
     const double *caug;   /* B             : sys_info.caug                                          */
-    const double *obs;    /* B x nobs x 6  : [obs{j}.l(:,1); obs{j}.l(:,2)]                         */
+    const double *obs;    /* B x nobs x 6  : [obs{j}.l(:,1); obs{j}.l(:,2)]  (B x H x nobs x 6 on a
+                             CFS_OBS_PER_WAYPOINT handle: cfs_problem_set_obstacle_motion)          */
     const double *noise;  /* PSGCFS: B x noise_rows x nn draws of normrnd(0,0.1) (PSGCFS_FANUC.m:109),
                              one row consumed per PSG step; NULL = zeros                            */
     int noise_rows;
@@ -241,13 +242,13 @@ int cfs_dist_arm_grad(const cfs_robot *robot, int njoint, int N, const double *t
 
 /* the distance/Jacobian half of get_con (Lib/CFS_FANUC.m:110-121): for every (problem, obstacle,
  * waypoint) the distance, closest link and Diff = num_jac(f,theta)' (Lib/functions/num_jac.m:1-17,
- * literal scheme).  x_: B x (H*nstate); obs: B x nobs x 6;
+ * literal scheme).  x_: B x (H*nstate); obs: B x nobs x 6 (B x H x nobs x 6 per waypoint);
  * dist: B x nobs x H; linkid: B x nobs x H; grad: B x nobs x H x njoint. */
 int cfs_linearize(cfs_problem *p, int B, const double *x_, const double *obs, double *dist, int *linkid, double *grad);
 
 /* self.get_con() with the reference's public dense outputs self.Ainq / self.binq
  * (Lib/CFS_FANUC.m:101-135): rows = nobs*H*(1+2*njoint) in the reference's row order.
- * x_: B x (H*nstate); u: B x nn; xR1: B x nstate; obs: B x nobs x 6;
+ * x_: B x (H*nstate); u: B x nn; xR1: B x nstate; obs: B x nobs x 6 (B x H x nobs x 6 per waypoint);
  * Ainq: B x (rows x nn column-major); binq: B x rows. */
 int cfs_get_con(cfs_problem *p, int B, const double *x_, const double *u, const double *xR1, const double *obs,
                 double *Ainq, double *binq);
@@ -310,6 +311,25 @@ int cfs_problem_get_infeasible_policy(const cfs_problem *p, int *policy, double 
  * viol_all: B x MAX_O_ITER, the largest slack max_r s_r of each outer iteration's QP (0 for a hard QP and after the last
  * iteration); n_soft: B, the number of softened outer iterations.  All zero after a solve with STOP.  Either may be NULL. */
 int cfs_soft_results(cfs_problem *p, int B, double *viol_all, int *n_soft);
+
+/* ---- moving obstacles ----------------------------------------------------------------------------
+ * Obstacles given per waypoint: a predicted path of a person's forearm, a part on a conveyor, another arm.  Collision row (j, i)
+ * of get_con (Lib/CFS_FANUC.m:110-120, Lib/PSGCFS_FANUC.m:152-160) depends only on waypoint i's pose and on obstacle j, so only
+ * the obstacle that the linearisation reads for waypoint i changes; the QP, the infeasibility certificate, the warm start, the
+ * soft QP, the rollout, the costs and the stop tests are those of a static handle.
+ *   CFS_OBS_STATIC (default): every obs array the handle reads is B x nobs x 6, one axis per obstacle for the whole horizon.
+ *   CFS_OBS_PER_WAYPOINT: every obs array that cfs_solve_batch, cfs_solve_batch_device, cfs_linearize and cfs_get_con read is
+ *     B x H x nobs x 6; row [b][i][j] is obstacle j's [l(:,1); l(:,2)] at waypoint i+1, i.e. row i of x_, at time (i+1)*delta_t.
+ *     Margins stay per obstacle.  With the same row at every waypoint, every result is bit for bit the static handle's.  The
+ *     automatic launch order measures waypoint i against row i.
+ * CFS_ERR_INVALID_ARG, nothing changes: NULL handle; unknown motion; PER_WAYPOINT on a handle with meshes (nmesh > 0: meshes stay
+ * static); PER_WAYPOINT for a shape whose per-waypoint linearisation tiles (nobs*6 more doubles of LDS per waypoint) do not fit
+ * every tier of the fused solver that the static shape fits (checked here, not at launch).  On a PER_WAYPOINT handle
+ * cfs_problem_set_meshes with nmesh > 0 and cfs_chomp_batch give CFS_ERR_INVALID_ARG.  Not affected: cfs_qp (it reads no
+ * obstacles), cfs_dist_arm*, RRT, cfs_select_best_device, the cfs_build_terms* entry points.  Set it between solves. */
+typedef enum cfs_obstacle_motion { CFS_OBS_STATIC = 0, CFS_OBS_PER_WAYPOINT = 1 } cfs_obstacle_motion;
+int cfs_problem_set_obstacle_motion(cfs_problem *p, int motion);
+int cfs_problem_get_obstacle_motion(const cfs_problem *p, int *motion);
 
 /* ---- mesh obstacles -----------------------------------------------------
  * The reference measures the arm against a surface with `[dis, points] = point2surface_dis(pos{i}.p, obs)`

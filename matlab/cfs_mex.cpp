@@ -14,6 +14,8 @@
 //        geometry kernel RRT_FANUC.feasible (Lib/RRT_FANUC.m:146-181) and get_con (Lib/CFS_FANUC.m:115) call; d, linkid = nobs x N;
 //        grad (when asked for) = njoint x (nobs*N), column (n-1)*nobs+j = the analytic d(d(j,n))/d(theta(:,n)) (cfs_dist_arm_grad)
 //   'solve' and 'get_con' honour an optional sys_info.jacobian = 'fd_literal' (default, num_jac.m) | 'analytic' (include/cfs_hip.h)
+//   'solve' and 'get_con' accept moving obstacles: obs{j}.l may be 3x2xH (page i = the axis at waypoint i); any such entry makes
+//   the handle CFS_OBS_PER_WAYPOINT and the 3x2 entries are held over the horizon (include/cfs_hip.h, moving obstacles)
 //   [route, all_nodes, total_dis, all_ee, fail, node_num] = cfs_mex('rrt', obs, sys_info, goal, region_g, region_s, sample_off, ROBOT, SOLVER, U)
 //        RRT_FANUC(obs, sys_info, goal, region_g, region_s, sample_off, ROBOT, SOLVER).find_route() (Lib/RRT_FANUC.m:48-91) grown on the GPU;
 //        U = rand(ndraw, S): MATLAB's own rand, consumed per tree exactly as find_route consumes it (one per proposal + nstate for a random
@@ -65,7 +67,9 @@ struct Family {
     std::vector<double> margin, obs6, Dv, epsv;
     ~Family() { if (p) cfs_problem_destroy(p); }
 };
-static void make_family(Family &f, int mode, const mxArray *obs, int first, int nobs, const mxArray *S, const char *ROBOT, bool need_both = false)
+// moving (solve, get_con): obs{j}.l may be 3x2xH; obs6 is then H x nobs x 6 and the handle CFS_OBS_PER_WAYPOINT
+static void make_family(Family &f, int mode, const mxArray *obs, int first, int nobs, const mxArray *S, const char *ROBOT, bool need_both = false,
+                        bool moving = false)
 {
     cfs_problem_desc &d = f.d;
     memset(&d, 0, sizeof d);
@@ -80,7 +84,16 @@ static void make_family(Family &f, int mode, const mxArray *obs, int first, int 
     d.MAX_O_ITER = (int)field_scalar(S, "MAX_O_ITER");
     d.alpha = mxGetField(S, 0, "alpha") ? field_scalar(S, "alpha") : 0.0;
     d.max_batch = 1;
-    f.margin.assign(nobs, 0.0); f.obs6.assign(6 * (size_t)nobs, 0.0); f.Dv.assign(nobs, 0.0); f.epsv.assign(nobs, 0.0);
+    const size_t H = (size_t)d.H;
+    bool per_wp = false;                                   // some obs{j}.l is 3x2xH
+    if (moving && H > 1)
+        for (int j = 0; j < nobs; ++j) {
+            const mxArray *o = mxGetCell(obs, first + j);
+            const mxArray *fl = o ? mxGetField(o, 0, "l") : nullptr;
+            if (fl && !mxGetField(o, 0, "mesh") && mxGetNumberOfElements(fl) == 6 * H) per_wp = true;
+        }
+    const size_t nrow = per_wp ? H : 1;                    // obstacle rows per obstacle
+    f.margin.assign(nobs, 0.0); f.obs6.assign(6 * (size_t)nobs * nrow, 0.0); f.Dv.assign(nobs, 0.0); f.epsv.assign(nobs, 0.0);
     std::vector<const cfs_mesh *> meshes;
     for (int j = 0; j < nobs; ++j) {
         const mxArray *o = mxGetCell(obs, first + j);
@@ -99,12 +112,17 @@ static void make_family(Family &f, int mode, const mxArray *obs, int first, int 
         else if (!meshes.empty()) mexErrMsgTxt("mesh obstacles must come last in the obs cell");
         else {
             const mxArray *fl = mxGetField(o, 0, "l");
-            if (!fl || mxGetNumberOfElements(fl) != 6) mexErrMsgIdAndTxt("cfs:obs", "obs{%d}.l must be 3x2", first + j + 1);
-            memcpy(&f.obs6[6 * (size_t)j], mxGetPr(fl), sizeof(double) * 6);   // [l(:,1); l(:,2)]
+            const size_t ne = fl ? mxGetNumberOfElements(fl) : 0;
+            if (ne != 6 && !(per_wp && ne == 6 * H))
+                mexErrMsgIdAndTxt("cfs:obs", moving ? "obs{%d}.l must be 3x2 or 3x2xH" : "obs{%d}.l must be 3x2", first + j + 1);
+            for (size_t i = 0; i < nrow; ++i)                                        // row [i][j] = [l(:,1,i); l(:,2,i)]
+                memcpy(&f.obs6[6 * (i * (size_t)nobs + j)], mxGetPr(fl) + (ne == 6 ? 0 : 6 * i), sizeof(double) * 6);
         }
     }
+    if (per_wp && !meshes.empty()) mexErrMsgTxt("mesh obstacles are static: they cannot share an obs cell with 3x2xH axes");
     d.margin = f.margin.data();
     check(cfs_problem_create(&d, &f.p));
+    if (per_wp) check(cfs_problem_set_obstacle_motion(f.p, CFS_OBS_PER_WAYPOINT));
     if (!meshes.empty()) check(cfs_problem_set_meshes(f.p, (int)meshes.size(), meshes.data()));
     // optional sys_info.jacobian = 'fd_literal' (num_jac.m, the default) | 'analytic' (cfs_problem_set_jacobian)
     if (const mxArray *fj = mxGetField(S, 0, "jacobian")) {
@@ -122,7 +140,7 @@ static void solve(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     const mxArray *S = prhs[3];
     const std::string ROBOT = mxArrayToString(prhs[4]);
     Family f;
-    make_family(f, mode, prhs[2], 0, (int)mxGetNumberOfElements(prhs[2]), S, ROBOT.c_str());
+    make_family(f, mode, prhs[2], 0, (int)mxGetNumberOfElements(prhs[2]), S, ROBOT.c_str(), false, true);
     const cfs_problem_desc &d = f.d;
     const int nn = d.H * d.njoint, nx = d.H * 2 * d.njoint, K = d.MAX_O_ITER;
     double caug = field_scalar(S, "caug");
@@ -149,7 +167,7 @@ static void get_con(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     const int mode = (int)mxGetScalar(prhs[1]);
     const std::string ROBOT = mxArrayToString(prhs[4]);
     Family f;
-    make_family(f, mode, prhs[2], 0, (int)mxGetNumberOfElements(prhs[2]), prhs[3], ROBOT.c_str());
+    make_family(f, mode, prhs[2], 0, (int)mxGetNumberOfElements(prhs[2]), prhs[3], ROBOT.c_str(), false, true);
     const int nn = f.d.H * f.d.njoint, rows = f.d.nobs * f.d.H * (1 + 2 * f.d.njoint);
     mxArray *A = mxCreateDoubleMatrix(rows, nn, mxREAL), *b = mxCreateDoubleMatrix(rows, 1, mxREAL);
     check(cfs_get_con(f.p, 1, mxGetPr(prhs[5]), mxGetPr(prhs[6]), field_ptr(prhs[3], "xR"), f.obs6.data(), mxGetPr(A), mxGetPr(b)));

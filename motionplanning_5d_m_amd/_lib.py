@@ -32,6 +32,7 @@ ROBOT_KIND = {"M16iB": 0, "M200i": 1, "2L": 2}
 MODE = {"CFS": 0, "PSGCFS": 1}
 JACOBIAN = {"fd_literal": 0, "analytic": 1}   # cfs_jacobian_mode
 INFEASIBLE = {"stop": 0, "soften": 1}          # cfs_infeasible_policy
+OBSTACLES = {"static": 0, "per_waypoint": 1}    # cfs_obstacle_motion
 
 
 class CfsError(RuntimeError):
@@ -200,6 +201,8 @@ SYMBOLS = [
     ("cfs_soft_results", C.c_int, [_P, C.c_int, _P, _P]),
     ("cfs_dist_arm_grad", C.c_int, [C.POINTER(cfs_robot), C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),
     ("cfs_select_best_device", C.c_int, [_P, C.c_int, C.c_int, _P, C.POINTER(cfs_batch_out), _P, C.POINTER(cfs_batch_out), _P, _P, _P, _P]),
+    ("cfs_problem_set_obstacle_motion", C.c_int, [_P, C.c_int]),
+    ("cfs_problem_get_obstacle_motion", C.c_int, [_P, C.POINTER(C.c_int)]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)

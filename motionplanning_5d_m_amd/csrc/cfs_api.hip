@@ -198,6 +198,7 @@ struct cfs_problem {
     DevBuf<double> u_log;                 // max_batch x MAX_O_ITER x nn: u after every outer iteration (both solvers)
     int jac = CFS_JAC_FD_LITERAL;         // cfs_problem_set_jacobian: which linearisation every later launch of this handle runs
     int infeas = CFS_INFEAS_STOP;         // cfs_problem_set_infeasible_policy
+    int motion = CFS_OBS_STATIC;          // cfs_problem_set_obstacle_motion: obs arrays are B x nobs x 6 | B x H x nobs x 6
     double soft_weight = 0.0;             // mu of CFS_INFEAS_SOFTEN (0: never set)
     DevBuf<double> soft_viol;             // max_batch x MAX_O_ITER: viol_all of the last whole solve (allocated with SOFTEN)
     DevBuf<int> soft_n;                   // max_batch: n_soft of the last whole solve
@@ -240,18 +241,32 @@ void cfs_problem_shape(const cfs_problem *p, ProblemShape *out)
 // 3.6 -> 2.3 ms per solve with w2s, CFS 5.8 -> 5.6 ms with w2m (its infeasibility proofs run active sets of ~100 rows).
 // w2s is compiled for the identity Hessian only (PSGCFS), w2m for QQ only (CFS), w1 for both; force_w1: CFS_DBG_TIER_W1.
 bool fused_fits(int nj, int H, int nobs) { return fused_fits_tier<FUSED_W1>(nj, H, nobs); }
-template <FusedTier T>
-static hipError_t launch_tier(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft)
+// The tier is chosen by the static plan for either kind of handle: cfs_problem_set_obstacle_motion admits a per-waypoint handle only
+// when its plan fits every tier the static one fits (fused_fits_move), so a per-waypoint solve runs the same tier, and with constant
+// rows the same arithmetic, as the static one.
+bool fused_fits_move(int nj, int H, int nobs, int mode)
 {
-    if (soft) return analytic ? launch_fused_tier<T, true, true>(nj, p, s, soft) : launch_fused_tier<T, false, true>(nj, p, s, soft);
-    return analytic ? launch_fused_tier<T, true, false>(nj, p, s, nullptr) : launch_fused_tier<T, false, false>(nj, p, s, nullptr);
+    if (!fused_fits_tier<FUSED_W1>(nj, H, nobs, true)) return false;
+    if (mode == CFS_MODE_PSGCFS) return fused_fits_tier<FUSED_W2S>(nj, H, nobs, true) == fused_fits_tier<FUSED_W2S>(nj, H, nobs);
+    return fused_fits_tier<FUSED_W2M>(nj, H, nobs, true) == fused_fits_tier<FUSED_W2M>(nj, H, nobs);
 }
-hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1, bool analytic, const SoftParams *soft)
+template <FusedTier T, bool MOVE>
+static hipError_t launch_tier_m(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft)
+{
+    if (soft) return analytic ? launch_fused_tier<T, true, true, MOVE>(nj, p, s, soft) : launch_fused_tier<T, false, true, MOVE>(nj, p, s, soft);
+    return analytic ? launch_fused_tier<T, true, false, MOVE>(nj, p, s, nullptr) : launch_fused_tier<T, false, false, MOVE>(nj, p, s, nullptr);
+}
+template <FusedTier T>
+static hipError_t launch_tier(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft, bool move)
+{
+    return move ? launch_tier_m<T, true>(nj, p, s, analytic, soft) : launch_tier_m<T, false>(nj, p, s, analytic, soft);
+}
+hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1, bool analytic, const SoftParams *soft, bool move)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
-    if (!force_w1 && ident && fused_fits_tier<FUSED_W2S>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2S>(nj, p, s, analytic, soft);
-    if (!force_w1 && !ident && fused_fits_tier<FUSED_W2M>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2M>(nj, p, s, analytic, soft);
-    return launch_tier<FUSED_W1>(nj, p, s, analytic, soft);
+    if (!force_w1 && ident && fused_fits_tier<FUSED_W2S>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2S>(nj, p, s, analytic, soft, move);
+    if (!force_w1 && !ident && fused_fits_tier<FUSED_W2M>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2M>(nj, p, s, analytic, soft, move);
+    return launch_tier<FUSED_W1>(nj, p, s, analytic, soft, move);
 }
 
 extern "C" {
@@ -582,6 +597,9 @@ static void fill_fused_family(const cfs_problem *p, FusedParams &fp, int B)
 }
 static bool force_w1(const cfs_problem *p) { return (p->dbg_mask & CFS_DBG_TIER_W1) != 0; }
 static bool analytic(const cfs_problem *p) { return p->jac == CFS_JAC_ANALYTIC; }
+static bool moving(const cfs_problem *p) { return p->motion == CFS_OBS_PER_WAYPOINT; }
+// obstacle rows per problem in every obs array the handle reads: nobs (static) | H x nobs (per waypoint)
+static size_t obs_rows(const cfs_problem *p) { return (size_t)p->d.nobs * (moving(p) ? (size_t)p->d.H : 1); }
 // the soft kernels' parameters for a SOFTEN handle (null: STOP, the default kernels); whole: record viol_all / n_soft
 static const SoftParams *soft_params(const cfs_problem *p, SoftParams &sp, bool whole)
 {
@@ -672,6 +690,7 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
     else if (p->order_mode != 2 && !(p->dbg_mask & CFS_DBG_NO_AUTO_ORDER) && B > p->n_cu && nline > 0) {   // also when a given order is for another batch size
         OrderParams op;
         op.rb = p->rb.p; op.B = B; op.H = p->d.H; op.nj = nj; op.nobs = nline; op.obs_stride = p->d.nobs;
+        op.wp_stride = moving(p) ? p->d.nobs : 0;
         op.x_init = in->x_init; op.obs = in->obs; op.margin = p->margin.p; op.key = p->okey.p; op.order = p->order.p;
         launch_order(op, s);
         fp.order = p->order.p;
@@ -684,7 +703,7 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
     }
     if (p->prof) HIPCHK(hipEventRecord(e4[2], s));   // after the launch-order pre-pass: [e4[2], e4[3]] brackets the fused kernel alone (mesh handles: the loop of launches)
     if (p->nmesh == 0) {
-        HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), soft));
+        HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), soft, moving(p)));
     } else {
         // Mesh obstacles are linearised by their own kernel (hierarchy traversals do not fit the fused kernel's register
         // budget), which needs the current iterate: one outer iteration per launch, state carried through HBM.  Every
@@ -727,14 +746,14 @@ int cfs_solve_batch(cfs_problem *p, const cfs_batch_in *in, const cfs_batch_out 
     if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
     if (!in->x_init || !in->xR1 || !in->ff || !in->caug || !in->obs) return fail(CFS_ERR_INVALID_ARG, "NULL input array");
     HIPCHK(hipSetDevice(p->device));
-    const size_t nn = p->nn, nx = p->nx, ns = p->ns, K = p->d.MAX_O_ITER, nobs = p->d.nobs;
+    const size_t nn = p->nn, nx = p->nx, ns = p->ns, K = p->d.MAX_O_ITER;
     Stage st;
     cfs_batch_in din = *in;
     din.x_init = st.up(in->x_init, B * nx);
     din.xR1 = st.up(in->xR1, B * ns);
     din.ff = st.up(in->ff, B * nn);
     din.caug = st.up(in->caug, B);
-    din.obs = st.up(in->obs, B * nobs * 6);
+    din.obs = st.up(in->obs, B * obs_rows(p) * 6);
     din.noise = in->noise ? st.up(in->noise, (size_t)B * in->noise_rows * nn) : nullptr;
     cfs_batch_out dout;
     dout.u = st.up<double>(nullptr, B * nn);
@@ -1000,6 +1019,7 @@ int cfs_chomp_batch(cfs_problem *p, const cfs_batch_in *in, const double *u0, co
     if (!in->x_init || !in->xR1 || !in->ff || !in->caug || !in->obs) return fail(CFS_ERR_INVALID_ARG, "NULL input array");
     if (!out->u || !out->x_ || !out->cost_all || !out->e_cost_all || !out->e_u_all || !out->iter_O) return fail(CFS_ERR_INVALID_ARG, "NULL output array");
     if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC measures line obstacles only (Lib/CHOMP_FANUC.m:119)");
+    if (moving(p)) return fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC takes static obstacles only (the handle is CFS_OBS_PER_WAYPOINT)");
     if (!chomp_fits(p->d.njoint, p->d.H, p->d.nobs)) return fail(CFS_ERR_INVALID_ARG, "H x nobs too large for the CHOMP kernel's 64 KB of LDS");
     HIPCHK(hipSetDevice(p->device));
     const size_t nn = p->nn, nx = p->nx, ns = p->ns, K = p->d.MAX_O_ITER, nobs = p->d.nobs;
@@ -1033,6 +1053,7 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
     if (nmesh < 0 || nmesh > p->d.nobs) return fail(CFS_ERR_INVALID_ARG, "nmesh %d outside 0..nobs=%d", nmesh, p->d.nobs);
     if (nmesh > 0 && !meshes) return fail(CFS_ERR_INVALID_ARG, "meshes is NULL");
     if (nmesh > 0 && p->infeas == CFS_INFEAS_SOFTEN) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are not supported with CFS_INFEAS_SOFTEN");
+    if (nmesh > 0 && moving(p)) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are static: not supported on a CFS_OBS_PER_WAYPOINT handle");
     HIPCHK(hipSetDevice(p->device));
     std::vector<DevMesh> v(nmesh);
     for (int i = 0; i < nmesh; ++i) {
@@ -1187,6 +1208,27 @@ int cfs_problem_set_infeasible_policy(cfs_problem *p, int policy, double weight)
     return CFS_SUCCESS;
 }
 
+int cfs_problem_set_obstacle_motion(cfs_problem *p, int motion)
+{
+    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (motion != CFS_OBS_STATIC && motion != CFS_OBS_PER_WAYPOINT) return fail(CFS_ERR_INVALID_ARG, "unknown obstacle motion %d", motion);
+    if (motion == CFS_OBS_PER_WAYPOINT) {
+        if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are static: CFS_OBS_PER_WAYPOINT needs a handle without meshes");
+        if (!fused_fits_move(p->d.njoint, p->d.H, p->d.nobs, p->d.mode))
+            return fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d: the per-waypoint obstacle rows of a linearisation tile do not fit the "
+                        "on-chip budget of the static plan's tier", p->d.H, p->d.nobs, p->d.njoint);
+    }
+    p->motion = motion;
+    return CFS_SUCCESS;
+}
+
+int cfs_problem_get_obstacle_motion(const cfs_problem *p, int *motion)
+{
+    if (!p || !motion) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    *motion = p->motion;
+    return CFS_SUCCESS;
+}
+
 int cfs_problem_get_infeasible_policy(const cfs_problem *p, int *policy, double *weight)
 {
     if (!p || !policy || !weight) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
@@ -1228,7 +1270,7 @@ struct PieceBuffers {
 };
 static int stage_piece(cfs_problem *p, Stage &st, int B, const double *x_, const double *xR1, const double *obs, PieceBuffers &pb)
 {
-    const size_t nobs = p->d.nobs;
+    const size_t nobs = obs_rows(p);
     pb.x_ = st.up(x_, (size_t)B * p->nx);
     pb.xR1 = st.up(xR1, (size_t)B * p->ns);
     pb.ff = st.up<double>(nullptr, (size_t)B * p->nn);
@@ -1263,7 +1305,7 @@ static int linearize_piece(cfs_problem *p, int B, const PieceBuffers &pb, double
         fp.nmesh = p->nmesh; fp.ext_dist = p->dist.p; fp.ext_grad = p->grad.p;
     }
     SoftParams sp;
-    HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false)));
+    HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false), moving(p)));
     return CFS_SUCCESS;
 }
 

@@ -54,7 +54,9 @@ void launch_dist_arm_grad(const DistArmParams &p, hipStream_t s);   // d, linkid
 struct OrderParams {
     const DevRobot *rb;
     int B, H, nj, nobs;          // nobs: line obstacles only
-    int obs_stride;              // obstacles per problem in `obs` (line + mesh)
+    int obs_stride;              // obstacles per waypoint row in `obs` (line + mesh)
+    int wp_stride;               // obstacles between waypoint rows: 0 (one row for the horizon, B x obs_stride x 6) | obs_stride
+                                 // (CFS_OBS_PER_WAYPOINT: B x H x obs_stride x 6, waypoint i measured against row i)
     const double *x_init;        // B x H x 2nj
     const double *obs;           // B x obs_stride x 6
     const double *margin;        // obs_stride
@@ -147,14 +149,18 @@ struct SoftParams {
 //   w2m 2 / 32  two problems per CU hide each other's latencies; medium active sets stay in registers
 //   w2s 2 / 16  same, smallest register footprint (no spills): the projection QPs of PSGCFS have 2-3 active rows
 // and each tier into one object per variant (Makefile): JAC, the analytic Jacobian (CFS_JAC_ANALYTIC handles), and SOFT, the soft
-// QP (sp; null without SOFT).  Every object defines its own launch_fused_tier<tier, JAC, SOFT>, the tier's default object its
-// fused_fits_tier<tier> (the variants share the LDS layout and capacities).
+// QP (sp; null without SOFT), and MOVE, per-waypoint obstacles (CFS_OBS_PER_WAYPOINT handles: obs is B x H x nobs x 6, staged per
+// linearisation tile).  Every object defines its own launch_fused_tier<tier, JAC, SOFT, MOVE>, the tier's default object its
+// fused_fits_tier<tier> (the variants share the LDS layout and capacities; move: the MOVE plan, whose tiles carry the obstacle rows).
 enum FusedTier { FUSED_W1, FUSED_W2M, FUSED_W2S };
-template <FusedTier T, bool JAC, bool SOFT> hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftParams *sp);
-template <FusedTier T> bool fused_fits_tier(int nj, int H, int nobs);
-// cfs_api.hip: tier by mode and capacity; analytic: the JAC kernels; soft (non-null): the SOFT kernels
-hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1 = false, bool analytic = false, const SoftParams *soft = nullptr);
+template <FusedTier T, bool JAC, bool SOFT, bool MOVE> hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftParams *sp);
+template <FusedTier T> bool fused_fits_tier(int nj, int H, int nobs, bool move = false);
+// cfs_api.hip: tier by mode and capacity; analytic: the JAC kernels; soft (non-null): the SOFT kernels; move: the MOVE kernels
+hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1 = false, bool analytic = false, const SoftParams *soft = nullptr,
+                        bool move = false);
 bool fused_fits(int nj, int H, int nobs);
+// does the per-waypoint plan fit every tier the static one fits for this mode (same tier, hence the same arithmetic)?
+bool fused_fits_move(int nj, int H, int nobs, int mode);
 
 struct CostHistParams {          // EVAL.get_cost / store_result for a logged u history (CFS mode)
     int B, nn, max_o_iter;

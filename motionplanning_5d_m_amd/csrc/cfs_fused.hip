@@ -15,6 +15,8 @@
 //     analytic Jacobian instead (one chain per waypoint, one tangent sweep of the winning link: cfs_geom_dev.h);
 //   * kernels instantiated with SOFT (CFS_INFEAS_SOFTEN handles) follow a QP that is proven infeasible with the
 //     soft-constraint QP of the same linearisation: 1/mu on the Gram diagonal of the collision rows;
+//   * kernels instantiated with MOVE (CFS_OBS_PER_WAYPOINT handles) read obstacle row (b, i, j) of a B x H x nobs x 6 array
+//     for waypoint i, staged per linearisation tile into LDS next to the tile's scratch;
 //   * QP: Goldfarb-Idnani dual active set in range-space form.  The inverse Gram matrix
 //     P = (N'H^{-1}N)^{-1} is kept EXPLICITLY, one row per thread in registers (it is symmetric,
 //     so column access is never needed); adding a constraint is a bordered rank-1 update,
@@ -36,6 +38,9 @@ namespace {
 constexpr int CERT_AT = 6;              // main-loop steps of a QP before the step-free infeasibility certificate is asked
 #ifndef CFS_WG_PER_CU
 #define CFS_WG_PER_CU 1                   // workgroups resident per CU (2: half the LDS and registers each)
+#endif
+#ifndef CFS_MOVE
+#define CFS_MOVE 0                        // this object's variant: per-waypoint obstacles (Makefile)
 #endif
 constexpr double REF_A = 1e-4;           // refinement of a step direction continues while |r'rho| > A * max(|delta|, tol * n'H^-1 n) ...
 constexpr double REF_B = 1e-9;           // ... or max|rho| > B * max|d|  (rho_a = n_a'z, zero in exact arithmetic)
@@ -439,10 +444,11 @@ __host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int
 }
 
 // ------------------------------------------------------------------------------------------------
-// IDENT: the QP Hessian is the identity (PSGCFS projection); JAC: analytic Jacobian (CFS_JAC_ANALYTIC handles).
+// IDENT: the QP Hessian is the identity (PSGCFS projection); JAC: analytic Jacobian (CFS_JAC_ANALYTIC handles); MOVE: obstacles
+// per waypoint (CFS_OBS_PER_WAYPOINT handles: P.obs is B x H x nobs x 6, no mesh obstacles).
 // Soft: empty for STOP handles, whose kernarg segment is FusedParams alone; SoftParams for CFS_INFEAS_SOFTEN handles (SOFT: the
 // soft-constraint QP after a proven-infeasible one, its parameters as a second block).
-template <int NJ, int QB, bool IDENT, bool JAC, class... Soft>
+template <int NJ, int QB, bool IDENT, bool JAC, bool MOVE, class... Soft>
 __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(FusedParams P, Soft... soft_params)
 {
     constexpr bool SOFT = sizeof...(Soft) > 0;
@@ -524,7 +530,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
     {
         const double *src = reinterpret_cast<const double *>(P.rb);
         for (int e = tid; e < (int)(sizeof(DevRobot) / 8); e += FT) lds[L.rb + e] = src[e];
-        for (int e = tid; e < nobs * 6; e += FT) s_ob[e] = P.obs[(size_t)b * nobs * 6 + e];
+        if constexpr (!MOVE)                               // (MOVE: staged per linearisation tile, s_obw below)
+            for (int e = tid; e < nobs * 6; e += FT) s_ob[e] = P.obs[(size_t)b * nobs * 6 + e];
         for (int e = tid; e < NX; e += FT) s_x[e] = P.x_init[(size_t)b * NX + e];
         for (int e = tid; e < HN; e += FT) { s_u[e] = 0.0; s_qu[e] = 0.0; s_mx[e] = P.has_bounds ? P.maxin[e] : 0.0; }
         if (tid < NJ) {
@@ -627,9 +634,14 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                 double *s_en = s_sc + W * NJ * 6;                // [W][NJ][6]  capsule end points of the base pose
                 double *s_tw = s_en + W * NJ * 6;                // [W][NJ][6]  joint twists [axis; point]  (2 NJ * 6 <= NVT * 6)
                 double *s_bd = s_en + W * NVT * 6;               // [W][NJ][nobs] base-pose distance of every link
+                // MOVE: [W][nobs][6] the tile's obstacle rows after the base distances (FusedPlan::per_wp).  Every MOVE site is an
+                // `if constexpr` of its own, so that the other kernels are compiled from exactly the statements they had before.
+#define S_OBW (s_bd + W * NJ * nseg)
                 for (int w0 = 0; w0 < H; w0 += W) {
                     const int Wc = min(W, H - w0);
                     if (w0 == 0) prep(0);
+                    if constexpr (MOVE)                          // rows w0 .. w0+Wc-1 of problem b: contiguous (nseg == nobs)
+                        for (int e = tid; e < Wc * nseg * 6; e += FT) S_OBW[e] = P.obs[((size_t)b * H + w0) * nobs * 6 + e];
                     for (int e = tid; e < Wc * NJ; e += FT) {
                         const int m = e % NJ, wi = e / NJ;
                         double x = s_x[(w0 + wi) * NS + m];
@@ -646,7 +658,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     STAMP(10);                                  // 10: sincos + the chain
                     for (int e = tid; e < NJ * Wc * nseg; e += FT) {
                         const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
-                        s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, s_ob + j * 6);
+                        if constexpr (MOVE) s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, S_OBW + (wi * nseg + j) * 6);
+                        else s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, s_ob + j * 6);
                     }
                     if (w0 == 0) prep(2);
                     __syncthreads();
@@ -660,14 +673,22 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         if (P.dump_linkid && launched == 0) P.dump_linkid[((size_t)b * nobs + j) * H + w0 + wi] = lk;
                         s_rhs[j * H + w0 + wi] = m0;
                         double *g = s_g + (j * H + w0 + wi) * NJ;
-                        if (lk > 0) winner_grad(s_en + (wi * NJ + lk - 1) * 6, s_tw + wi * NJ * 6, lk - 1, NJ, s_ob + j * 6, g);
-                        else for (int m = 0; m < NJ; ++m) g[m] = 0.0;
+                        if constexpr (MOVE) {
+                            if (lk > 0) winner_grad(s_en + (wi * NJ + lk - 1) * 6, s_tw + wi * NJ * 6, lk - 1, NJ, S_OBW + (wi * nseg + j) * 6, g);
+                            else for (int m = 0; m < NJ; ++m) g[m] = 0.0;
+                        } else {
+                            if (lk > 0) winner_grad(s_en + (wi * NJ + lk - 1) * 6, s_tw + wi * NJ * 6, lk - 1, NJ, s_ob + j * 6, g);
+                            else for (int m = 0; m < NJ; ++m) g[m] = 0.0;
+                        }
                     }
                     if (w0 == 0) { prep(3); prepped = true; }
-                    // (the next tile's first phase only writes its sin / cos table, which this one no longer reads)
-                    if (w0 + W >= H) __syncthreads();
+                    // (the next tile's first phase only writes its sin / cos table, which this one no longer reads; MOVE: and its
+                    // obstacle rows, which the tangent sweeps above still read)
+                    if constexpr (MOVE) __syncthreads();
+                    else if (w0 + W >= H) __syncthreads();
                     STAMP(11);                                  // 11: minima and the tangent sweeps of the winning links
                 }
+#undef S_OBW
             }
         } else {
             if (nseg > 0) {
@@ -677,10 +698,13 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                 double *s_bd = s_en + W * NVT * 6;               // [W][NJ][nobs] base-pose distance of every link
                 double *s_dv = s_bd + W * NJ * nseg;             // [W][nobs][NE] min over the links at every evaluation point of num_jac
                 unsigned short *s_list = reinterpret_cast<unsigned short *>(s_dv + W * nseg * NE);    // [NJ][W*nobs] (wi << 8 | obstacle)
+#define S_OBW (s_dv + W * nseg * NE + (NJ * W * nseg + 3) / 4)   /* MOVE: [W][nobs][6] the tile's obstacle rows, after the lists */
                 int *s_cnt = s_free;                             // candidates per link (the QP's free-slot stack is idle here)
                 for (int w0 = 0; w0 < H; w0 += W) {
                     const int Wc = min(W, H - w0);
                     if (w0 == 0) prep(0);
+                    if constexpr (MOVE)                          // (the previous tile's last read of them is behind its pair-phase barrier)
+                        for (int e = tid; e < Wc * nseg * 6; e += FT) S_OBW[e] = P.obs[((size_t)b * H + w0) * nobs * 6 + e];
                     for (int e = tid; e < Wc * NJ * 3; e += FT) {
                         const int var = e % 3, m = (e / 3) % NJ, wi = e / (3 * NJ);
                         double x = s_x[(w0 + wi) * NS + m];
@@ -722,7 +746,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     // segment branch of distLinSeg is wave-uniform.
                     for (int e = tid; e < NJ * Wc * nseg; e += FT) {
                         const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
-                        s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NVT + kvoff(k0 + 1)) * 6, s_ob + j * 6);
+                        if constexpr (MOVE) s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NVT + kvoff(k0 + 1)) * 6, S_OBW + (wi * nseg + j) * 6);
+                        else s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NVT + kvoff(k0 + 1)) * 6, s_ob + j * 6);
                     }
                     if (tid < NJ) s_cnt[tid] = 0;
                     if (w0 == 0) prep(2);
@@ -762,7 +787,9 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                                     k1 = kk; ent = r_ / (2 * kk); v = r_ - ent * (2 * kk) + 1;
                                 }
                             const int item = s_list[(k1 - 1) * W * nseg + ent], wi = item >> 8, j = item & 255;
-                            const double dis = seg_seg_dist(s_en + (wi * NVT + kvoff(k1) + v) * 6, s_ob + j * 6);
+                            double dis;
+                            if constexpr (MOVE) dis = seg_seg_dist(s_en + (wi * NVT + kvoff(k1) + v) * 6, S_OBW + (wi * nseg + j) * 6);
+                            else dis = seg_seg_dist(s_en + (wi * NVT + kvoff(k1) + v) * 6, s_ob + j * 6);
                             // link k1 is at variant min(ev, 2 k1) at evaluation point ev: v < 2 k1 serves ev = v, v = 2 k1 every ev >= v
                             double *dv = s_dv + (wi * nseg + j) * NE;
                             const int evhi = (v == 2 * k1) ? NE - 1 : v;
@@ -785,6 +812,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     // not read; its barrier covers both)
                     if (w0 + W >= H) __syncthreads();
                 }
+#undef S_OBW
             }
         }
         if (!prepped && P.piece != 1) {                     // nothing to ride on (mesh obstacles only, or the QP piece): four phases of their own
@@ -1594,13 +1622,13 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
 
 #undef red
 
-template <int NJ, int QB, bool IDENT, bool JAC, bool SOFT>
+template <int NJ, int QB, bool IDENT, bool JAC, bool SOFT, bool MOVE>
 hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s, const SoftParams *sp)
 {
     // the function attribute is per device (handles may live on several GPUs of one process: cfs_set_device)
     static std::atomic<unsigned long long> attr_set{0ull};
     using Kernel = std::conditional_t<SOFT, void (*)(FusedParams, SoftParams), void (*)(FusedParams)>;
-    const Kernel kern = cfs_solve_fused_kernel<NJ, QB, IDENT, JAC>;    // the pointer type fixes the parameter pack
+    const Kernel kern = cfs_solve_fused_kernel<NJ, QB, IDENT, JAC, MOVE>;    // the pointer type fixes the parameter pack
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -1618,28 +1646,28 @@ hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s, c
 #ifndef CFS_IDENT_SET
 #define CFS_IDENT_SET 2
 #endif
-template <int NJ, int QB, bool JAC, bool SOFT>
+template <int NJ, int QB, bool JAC, bool SOFT, bool MOVE>
 hipError_t launch_fused_inst(const FusedParams &p, size_t lds, hipStream_t s, const SoftParams *sp)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
 #if CFS_IDENT_SET != 0
-    if (ident) return launch_fused_inst2<NJ, QB, true, JAC, SOFT>(p, lds, s, sp);
+    if (ident) return launch_fused_inst2<NJ, QB, true, JAC, SOFT, MOVE>(p, lds, s, sp);
 #endif
 #if CFS_IDENT_SET != 1
-    if (!ident) return launch_fused_inst2<NJ, QB, false, JAC, SOFT>(p, lds, s, sp);
+    if (!ident) return launch_fused_inst2<NJ, QB, false, JAC, SOFT, MOVE>(p, lds, s, sp);
 #endif
     return hipErrorInvalidValue;
 }
 
 // The LDS plan of a problem shape on this tier, read by both fused_fits_tier and launch_fused_tier: active-set capacity QB, layout,
 // doubles a workgroup may use (small safety margin), linearisation scratch per waypoint of a tile (sin/cos, link end points, base
-// distances, minima per evaluation point, candidate lists as ushort)
+// distances, minima per evaluation point, candidate lists as ushort; move: the waypoint's obstacle rows as well)
 struct FusedPlan {
     int nn, QB;
     FusedLayout L;
     size_t avail, per_wp;
 };
-FusedPlan fused_plan(int nj, int H, int nobs)
+FusedPlan fused_plan(int nj, int H, int nobs, bool move)
 {
     FusedPlan q;
     q.nn = H * nj;
@@ -1647,6 +1675,7 @@ FusedPlan fused_plan(int nj, int H, int nobs)
     q.L = fused_layout(nj, H, nobs, q.QB, q.QB < CFS_PR ? q.QB : CFS_PR);
     q.avail = (160 * 1024 / CFS_WG_PER_CU) / 8 - 64;
     q.per_wp = (size_t)nj * 6 + (size_t)nvt(nj) * 6 + (size_t)nj * nobs + (size_t)nobs * (2 * nj + 1) + ((size_t)nj * nobs + 3) / 4;
+    if (move) q.per_wp += (size_t)nobs * 6;
     return q;
 }
 
@@ -1654,17 +1683,18 @@ FusedPlan fused_plan(int nj, int H, int nobs)
 
 // does the fused kernel's fixed LDS footprint (+ a minimal Y / linearisation region) fit a CU?
 template <FusedTier T>
-bool fused_fits_tier(int nj, int H, int nobs)
+bool fused_fits_tier(int nj, int H, int nobs, bool move)
 {
-    const FusedPlan q = fused_plan(nj, H, nobs);
+    const FusedPlan q = fused_plan(nj, H, nobs, move);
     return (size_t)q.L.total_fixed + (size_t)4 * q.nn <= q.avail && (size_t)q.L.lin + q.per_wp <= q.avail;
 }
 
 // host: choose the capacities, fill qy / lin_w, launch
-template <FusedTier T, bool JAC, bool SOFT>
+template <FusedTier T, bool JAC, bool SOFT, bool MOVE>
 hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftParams *sp)
 {
-    const FusedPlan q = fused_plan(nj, p.H, p.nobs);
+    if (MOVE && p.nmesh > 0) return hipErrorInvalidValue;   // per-waypoint rows are line obstacles only
+    const FusedPlan q = fused_plan(nj, p.H, p.nobs, MOVE);
     const int nn = q.nn;
     const FusedLayout &L = q.L;
     const bool ident = p.mode == CFS_MODE_PSGCFS;          // H = I: no Y rows at all (closed-form normals)
@@ -1680,27 +1710,27 @@ hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftPar
     const size_t need = std::max((size_t)L.total_fixed + (size_t)qy * nn, (size_t)L.lin + (size_t)w * q.per_wp);
     const size_t lds = need * 8;
     switch (nj * 1000 + q.QB) {
-    case 2096: return launch_fused_inst<2, 96, JAC, SOFT>(p, lds, s, sp);
-    case 3096: return launch_fused_inst<3, 96, JAC, SOFT>(p, lds, s, sp);
-    case 4096: return launch_fused_inst<4, 96, JAC, SOFT>(p, lds, s, sp);
-    case 5096: return launch_fused_inst<5, 96, JAC, SOFT>(p, lds, s, sp);
-    case 6096: return launch_fused_inst<6, 96, JAC, SOFT>(p, lds, s, sp);
-    case 2160: return launch_fused_inst<2, 160, JAC, SOFT>(p, lds, s, sp);
-    case 4160: return launch_fused_inst<4, 160, JAC, SOFT>(p, lds, s, sp);
-    case 5160: return launch_fused_inst<5, 160, JAC, SOFT>(p, lds, s, sp);
-    case 6160: return launch_fused_inst<6, 160, JAC, SOFT>(p, lds, s, sp);
-    case 3160: return launch_fused_inst<3, 160, JAC, SOFT>(p, lds, s, sp);
-    case 3256: return launch_fused_inst<3, 256, JAC, SOFT>(p, lds, s, sp);
-    case 4256: return launch_fused_inst<4, 256, JAC, SOFT>(p, lds, s, sp);
-    case 5256: return launch_fused_inst<5, 256, JAC, SOFT>(p, lds, s, sp);
-    case 6256: return launch_fused_inst<6, 256, JAC, SOFT>(p, lds, s, sp);
+    case 2096: return launch_fused_inst<2, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 3096: return launch_fused_inst<3, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 4096: return launch_fused_inst<4, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 5096: return launch_fused_inst<5, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 6096: return launch_fused_inst<6, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 2160: return launch_fused_inst<2, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 4160: return launch_fused_inst<4, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 5160: return launch_fused_inst<5, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 6160: return launch_fused_inst<6, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 3160: return launch_fused_inst<3, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 3256: return launch_fused_inst<3, 256, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 4256: return launch_fused_inst<4, 256, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 5256: return launch_fused_inst<5, 256, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 6256: return launch_fused_inst<6, 256, JAC, SOFT, MOVE>(p, lds, s, sp);
     default: return hipErrorInvalidValue;
     }
 }
 
-// The one place CFS_TIER, CFS_JAC and CFS_SOFT are read (Makefile: one object per tier and variant): this object's launcher, and,
-// in the tier's default object only, its capacity test.
-template hipError_t launch_fused_tier<CFS_TIER, CFS_JAC, CFS_SOFT>(int, FusedParams, hipStream_t, const SoftParams *);
-#if !CFS_JAC && !CFS_SOFT
-template bool fused_fits_tier<CFS_TIER>(int, int, int);
+// The one place CFS_TIER, CFS_JAC, CFS_SOFT and CFS_MOVE are read (Makefile: one object per tier and variant): this object's
+// launcher, and, in the tier's default object only, its capacity test.
+template hipError_t launch_fused_tier<CFS_TIER, CFS_JAC, CFS_SOFT, CFS_MOVE>(int, FusedParams, hipStream_t, const SoftParams *);
+#if !CFS_JAC && !CFS_SOFT && !CFS_MOVE
+template bool fused_fits_tier<CFS_TIER>(int, int, int, bool);
 #endif

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void cfs_dist_arm_grad_kernel(DistArmParams P)
 }
 
 // key[b] = number of (waypoint, line obstacle) pairs of problem b whose clearance on the initial trajectory is below the
-// margin.  Eight problems per 256-thread workgroup, 32 lanes per problem, one waypoint per lane: the pre-pass runs on the
+// margin (per-waypoint obstacles: waypoint i against its own row i).  Eight problems per 256-thread workgroup, 32 lanes per problem, one waypoint per lane: the pre-pass runs on the
 // solve's stream while ANOTHER solve's fused kernel holds every compute unit (two workgroups of 256 VGPRs per lane fill
 // the register file), so each of its workgroups waits for a fused workgroup to retire -- 128 workgroups instead of 1 024 per
 // batch of 1 024: config 3 PSGCFS 1.467 -> 1.451 ms per solve, CFS 1.598 -> 1.586 (same-call A/B, two rounds; 16 grid-striding
@@ -122,9 +122,11 @@ __global__ __launch_bounds__(256, 4) void cfs_order_key_kernel(OrderParams P)
             for (int q = 0; q < 12; ++q) M[q] = Mn[q];
             link_ends(rb, k, M, ends + k * 6);
         }
+        // problem b's rows, then waypoint i's (wp_stride 0: the one row of the horizon, the key of a static handle)
+        const double *ob = P.obs + ((size_t)b * P.obs_stride * (P.wp_stride ? P.H : 1) + (size_t)i * P.wp_stride) * 6;
         for (int j = 0; j < P.nobs; ++j) {
             double o6[6];
-            for (int q = 0; q < 6; ++q) o6[q] = P.obs[((size_t)b * P.obs_stride + j) * 6 + q];
+            for (int q = 0; q < 6; ++q) o6[q] = ob[j * 6 + q];
             double d = INFINITY;
             for (int k = 0; k < P.nj; ++k) d = fmin(d, seg_seg_dist(ends + k * 6, o6));
             cnt += d < P.margin[j];

@@ -42,6 +42,28 @@ def obs_to_array(obs):
                           np.concatenate([np.asarray(o["l"], float)[:, 0], np.asarray(o["l"], float)[:, 1]]) for o in obs]))
 
 
+def obs_moving(obs):
+    """Does any line obstacle of the obs cell move, i.e. is its obs{j}.l 3x2xH (shape (3, 2, H)) instead of 3x2?"""
+    return any("mesh" not in o and np.ndim(o["l"]) == 3 for o in obs)
+
+
+def obs_traj_to_array(obs, H):
+    """obs cell -> (H, nobs, 6): row [i][j] = [l(:,1); l(:,2)] of obstacle j at waypoint i+1.  obs{j}.l may be 3x2xH (MATLAB's
+    layout: shape (3, 2, H), page i = waypoint i+1) or 3x2, which is broadcast over the horizon (CFS_OBS_PER_WAYPOINT)."""
+    H = int(H)
+    out = np.zeros((H, len(obs), 6))
+    for j, o in enumerate(obs):
+        if "mesh" in o:
+            raise ValueError("mesh obstacles are static: they cannot be given per waypoint")
+        l = np.asarray(o["l"], float)
+        if l.shape == (3, 2):
+            l = np.broadcast_to(l[:, :, None], (3, 2, H))
+        elif l.shape != (3, 2, H):
+            raise ValueError(f"obs[{j}]['l'] has shape {l.shape}: expected (3, 2) or (3, 2, H={H})")
+        out[:, j, :3], out[:, j, 3:] = l[:, 0, :].T, l[:, 1, :].T
+    return _f64(out)
+
+
 def obs_meshes(obs):
     """The Mesh objects of an obs cell; mesh obstacles must come after the line obstacles (cfs_problem_set_meshes)."""
     flags = ["mesh" in o for o in obs]
@@ -54,6 +76,12 @@ def _jacobian_code(jacobian):
     if not isinstance(jacobian, str) or jacobian not in _lib.JACOBIAN:
         raise ValueError(f"jacobian must be one of {sorted(_lib.JACOBIAN)}, not {jacobian!r}")
     return _lib.JACOBIAN[jacobian]
+
+
+def _motion_code(obstacles):
+    if not isinstance(obstacles, str) or obstacles not in _lib.OBSTACLES:
+        raise ValueError(f"obstacles must be one of {sorted(_lib.OBSTACLES)}, not {obstacles!r}")
+    return _lib.OBSTACLES[obstacles]
 
 
 def _infeasible_args(on_infeasible, soft_weight):
@@ -78,8 +106,11 @@ class CFSBatch:
     solving batches of problems that differ in start/goal (x_init, xR1, ff, caug), obstacles and noise."""
 
     def __init__(self, sys_info, nobs, margin, mode="CFS", max_batch=1, device=None, check_dynamics=True, use_weights="auto",
-                 jacobian="fd_literal", on_infeasible="stop", soft_weight=None):
-        """on_infeasible: "stop" (the default: a proven-infeasible linearised QP ends the problem with QP_INFEASIBLE) | "soften"
+                 jacobian="fd_literal", on_infeasible="stop", soft_weight=None, obstacles="static"):
+        """obstacles: "static" (the default: obs arrays are (B, nobs, 6)) | "per_waypoint" (obs arrays of solve, solve_device,
+        linearize and get_con are (B, H, nobs, 6), row [b, i, j] = obstacle j at waypoint i+1; no meshes, no chomp;
+        include/cfs_hip.h, cfs_problem_set_obstacle_motion).
+        on_infeasible: "stop" (the default: a proven-infeasible linearised QP ends the problem with QP_INFEASIBLE) | "soften"
         (that outer iteration solves the soft-constraint QP with weight soft_weight instead and carries on; include/cfs_hip.h,
         cfs_problem_set_infeasible_policy).  Results of solve() carry viol_all (B x MAX_O_ITER) and n_soft (B).
         jacobian: "fd_literal" (num_jac.m literally, the default) | "analytic" (the exact derivative of the active branch of
@@ -92,6 +123,7 @@ class CFSBatch:
         s = sys_info
         _jacobian_code(jacobian)                         # validated before anything touches the device
         _infeasible_args(on_infeasible, soft_weight)
+        _motion_code(obstacles)
         self.mode = mode
         self.H, self.nj = int(s.H), int(s.njoint)
         self.ns, self.nn, self.nx = 2 * self.nj, self.H * self.nj, self.H * 2 * self.nj
@@ -146,7 +178,7 @@ class CFSBatch:
                 self.close()
                 CFSBatch.__init__(self, sys_info, nobs, margin, mode=mode, max_batch=max_batch, device=device,
                                   check_dynamics=check_dynamics_asked, use_weights=False, jacobian=jacobian,
-                                  on_infeasible=on_infeasible, soft_weight=soft_weight)
+                                  on_infeasible=on_infeasible, soft_weight=soft_weight, obstacles=obstacles)
                 return
         else:
             _lib.check(lib.cfs_problem_create(C.byref(d), C.byref(h)))
@@ -155,6 +187,27 @@ class CFSBatch:
             self.set_jacobian(jacobian)
         if on_infeasible != "stop":
             self.set_infeasible_policy(on_infeasible, soft_weight)
+        if obstacles != "static":
+            self.set_obstacle_motion(obstacles)
+
+    def set_obstacle_motion(self, obstacles):
+        """obstacles of the following solves and pieces: "static" | "per_waypoint" (cfs_problem_set_obstacle_motion)."""
+        code = _motion_code(obstacles)
+        _lib.check(self._lib.cfs_problem_set_obstacle_motion(self._h, code))
+
+    @property
+    def obstacle_motion(self):
+        m = C.c_int(0)
+        _lib.check(self._lib.cfs_problem_get_obstacle_motion(self._h, C.byref(m)))
+        return {v: k for k, v in _lib.OBSTACLES.items()}[m.value]
+
+    def _check_obs(self, obs, B):
+        """obs must be (B, nobs, 6) on a static handle (assert, as ever) and (B, H, nobs, 6) on a per-waypoint one (ValueError)."""
+        if self.obstacle_motion == "per_waypoint":
+            if tuple(obs.shape) != (B, self.H, self.nobs, 6):
+                raise ValueError(f"obs has shape {tuple(obs.shape)}: a per-waypoint handle takes (B, H, nobs, 6) = {(B, self.H, self.nobs, 6)}")
+        else:
+            assert tuple(obs.shape) == (B, self.nobs, 6)
 
     def set_infeasible_policy(self, on_infeasible, soft_weight=None):
         """what the following solves and pieces do with a proven-infeasible QP: "stop" | "soften" (with soft_weight > 0)."""
@@ -240,6 +293,8 @@ class CFSBatch:
 
     def set_meshes(self, meshes):
         """The last len(meshes) of the nobs obstacles are these mesh.Mesh objects from now on (cfs_problem_set_meshes)."""
+        if len(meshes) and self.obstacle_motion == "per_waypoint":
+            raise ValueError("mesh obstacles are static: not supported on a per-waypoint handle")
         self._meshes = list(meshes)                      # keep them alive as long as the handle uses them
         arr = (C.c_void_p * max(len(self._meshes), 1))(*[m._h for m in self._meshes])
         _lib.check(self._lib.cfs_problem_set_meshes(self._h, len(self._meshes), arr))
@@ -250,7 +305,8 @@ class CFSBatch:
         x_init, xR1, ff, caug, obs = _f64(x_init), _f64(xR1), _f64(ff), _f64(caug).reshape(-1), _f64(obs)
         B = x_init.shape[0]
         assert x_init.shape == (B, self.nx) and xR1.shape == (B, self.ns) and ff.shape == (B, self.nn)
-        assert caug.shape == (B,) and obs.shape == (B, self.nobs, 6)
+        assert caug.shape == (B,)
+        self._check_obs(obs, B)
         i = _lib.cfs_batch_in()
         i.B = B
         i.x_init, i.xR1, i.ff, i.caug, i.obs = _ptr(x_init), _ptr(xR1), _ptr(ff), _ptr(caug), _ptr(obs)
@@ -281,6 +337,7 @@ class CFSBatch:
         B = x_init.shape[0]
         for t in (x_init, xR1, ff, caug, obs) + ((noise,) if noise is not None else ()):
             assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+        self._check_obs(obs, B)
         if out is None:
             out = self.alloc_outputs(B, x_init.device)
         i = _lib.cfs_batch_in()
@@ -299,6 +356,8 @@ class CFSBatch:
     # ---- CHOMP (row f4) ------------------------------------------------------------------------------------
     def chomp(self, x_init, xR1, ff, caug, obs, u0, D, epsilon):
         """CHOMP_FANUC.optimizer() for B problems (cfs_chomp_batch); host arrays in and out."""
+        if self.obstacle_motion == "per_waypoint":
+            raise ValueError("CHOMP_FANUC takes static obstacles only: this handle is per-waypoint")
         x_init, xR1, ff, caug, obs, u0 = _f64(x_init), _f64(xR1), _f64(ff), _f64(caug).reshape(-1), _f64(obs), _f64(u0)
         D, epsilon = _f64(np.asarray(D, float).reshape(-1)), _f64(np.asarray(epsilon, float).reshape(-1))
         B = x_init.shape[0]
@@ -436,6 +495,7 @@ class CFSBatch:
     def linearize(self, x_, obs):
         x_, obs = _f64(x_), _f64(obs)
         B = x_.shape[0]
+        self._check_obs(obs, B)
         dist = np.zeros((B, self.nobs, self.H))
         lid = np.zeros((B, self.nobs, self.H), np.int32)
         grad = np.zeros((B, self.nobs, self.H, self.nj))
@@ -445,6 +505,7 @@ class CFSBatch:
     def get_con(self, x_, u, xR1, obs):
         x_, u, xR1, obs = _f64(x_), _f64(u), _f64(xR1), _f64(obs)
         B = x_.shape[0]
+        self._check_obs(obs, B)
         A = np.zeros((B, self.nn, self.rows))  # per problem rows x nn column-major == (nn, rows) C-order
         b = np.zeros((B, self.rows))
         _lib.check(self._lib.cfs_get_con(self._h, B, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs), _ptr(A), _ptr(b)))
@@ -544,11 +605,18 @@ class _SolverBase:
 
     def __init__(self, obs, sys_info, ROBOT="M16iB", device=None, jacobian="fd_literal", on_infeasible="stop", soft_weight=None):
         """jacobian: "fd_literal" (num_jac.m, the default) | "analytic" (CFSBatch).
-        on_infeasible: "stop" (the default) | "soften" with soft_weight= (CFSBatch); after optimizer(), viol_all and n_soft."""
+        on_infeasible: "stop" (the default) | "soften" with soft_weight= (CFSBatch); after optimizer(), viol_all and n_soft.
+        obs{j}["l"] may be 3x2xH (shape (3, 2, H): the obstacle's axis at waypoints 1..H); any such entry makes the handle
+        per-waypoint, and the 3x2 entries are then held over the horizon (obs_traj_to_array)."""
         _jacobian_code(jacobian)
         _infeasible_args(on_infeasible, soft_weight)
         if on_infeasible == "soften" and obs_meshes(obs):
             raise ValueError('on_infeasible="soften" does not support mesh obstacles')
+        self._moving = obs_moving(obs)
+        if self._moving:
+            if obs_meshes(obs):
+                raise ValueError("mesh obstacles are static: an obs cell with 3x2xH axes cannot hold meshes")
+            obs_traj_to_array(obs, sys_info.H)          # shapes checked before anything touches the device
         self.obs, self.sys_info, self.ROBOT = obs, sys_info, ROBOT
         if getattr(sys_info.robot, "name", ROBOT) != ROBOT:
             raise ValueError(f"sys_info.robot is {sys_info.robot.name!r} but ROBOT={ROBOT!r}")
@@ -559,7 +627,8 @@ class _SolverBase:
         self.eval = EVAL(sys_info)
         self.iter_O, self.total_iter, self.status = 1, 0, None
         self._batch = CFSBatch(sys_info, len(obs), [o[self.MARGIN_KEY] for o in obs], mode=self.MODE, max_batch=1,
-                               device=device, jacobian=jacobian, on_infeasible=on_infeasible, soft_weight=soft_weight)
+                               device=device, jacobian=jacobian, on_infeasible=on_infeasible, soft_weight=soft_weight,
+                               obstacles="per_waypoint" if self._moving else "static")
         self.viol_all, self.n_soft = np.zeros(0), 0
         meshes = obs_meshes(obs)
         if meshes:
@@ -568,7 +637,8 @@ class _SolverBase:
     def _args(self):
         s = self.sys_info
         xR1 = np.asarray(s.xR, float).reshape(s.nstate, -1)[:, 0]
-        return xR1[None], _f64(s.ff).reshape(1, -1), np.array([s.caug], float), obs_to_array(self.obs)[None]
+        obs = obs_traj_to_array(self.obs, s.H) if self._moving else obs_to_array(self.obs)
+        return xR1[None], _f64(s.ff).reshape(1, -1), np.array([s.caug], float), obs[None]
 
     def get_con(self):
         """self.Ainq / self.binq at the current (x_, u): dense, reference row order."""
@@ -616,6 +686,8 @@ class CHOMP_FANUC:
             raise ValueError(f"sys_info.robot is {sys_info.robot.name!r} but ROBOT={ROBOT!r}")
         n = int(obs[0]["num_obs"])
         self._obstacles = list(obs[1:1 + n])
+        if obs_moving(self._obstacles):
+            raise ValueError("CHOMP_FANUC takes static obstacles only: obs_{j}.l must be 3x2")
         self.nn = sys_info.H * sys_info.nu
         self.x_ = np.asarray(sys_info.x_, float).reshape(-1).copy()
         self.u = np.asarray(uu, float).reshape(-1).copy()

@@ -14,6 +14,12 @@ Random draws, in this order, from ``numpy.random.default_rng(seed)``:
   NC=48 obstacle candidates per problem: radius U(0.35,0.75)^(B,NC), bearing U(0,2pi)^(B,NC),
   top z U(0.6,1.5)^(B,NC); the first `nobs` candidates that pass the rejection test are kept
   noise  = 0.1 * standard_normal((B, 20, nn))
+
+``config3_moving`` is config 3 with moving obstacles (CFS_OBS_PER_WAYPOINT): the same draws in the same order, then
+  heading U(0,2pi)^(B,NC): candidate c moves horizontally at `speed` m/s along (cos, sin, 0) of its heading, so that at
+  waypoint i (time i*delta_t, i = 1..H) its axis is the config-3 axis shifted by speed*i*delta_t*(cos, sin, 0);
+  the rejection test measures the start pose against the candidates at waypoint 1 and the goal pose against them at
+  waypoint H; obs is (B, H, nobs, 6).
 """
 from __future__ import annotations
 
@@ -73,6 +79,42 @@ def config3(dist_fn, B=1024, nobs=8, seed=20260101, H=30):
         obs[b] = cand[b, ok[:nobs]]
     x_init, xR1, ff, caug = _batch_terms(s, x0, xg)
     batch = SimpleNamespace(B=B, nobs=nobs, x0=x0, xg=xg, x_init=x_init, xR1=xR1, ff=ff, caug=caug, obs=obs,
+                            noise=noise, margin_cfs=np.full(nobs, 0.25), margin_psg=np.full(nobs, 0.2))
+    return s, batch
+
+
+def config3_moving(dist_fn, B=1024, nobs=8, seed=20260101, H=30, speed=0.02):
+    """config 3 with every obstacle moving at a constant horizontal velocity (module docstring): returns (sys_info family,
+    batch namespace) with batch.obs of shape (B, H, nobs, 6) and batch.vel (B, nobs, 3)."""
+    s = _family(H, FANUC_Qp, 50.0)
+    robot = s.robot
+    rng = np.random.default_rng(seed)
+    x0 = X0C + rng.uniform(-0.1, 0.1, (B, 5))
+    xg = X0C * np.array([-1.0, 1, 1, 1, 1]) + rng.uniform(-0.1, 0.1, (B, 5))
+    rad = rng.uniform(0.35, 0.75, (B, NCAND))
+    ang = rng.uniform(0.0, 2 * np.pi, (B, NCAND))
+    z2 = rng.uniform(0.6, 1.5, (B, NCAND))
+    noise = 0.1 * rng.standard_normal((B, 20, H * 5))
+    head = rng.uniform(0.0, 2 * np.pi, (B, NCAND))
+    cx = robot.base[0] + rad * np.cos(ang)
+    cy = robot.base[1] + rad * np.sin(ang)
+    cand = np.stack([cx, cy, np.full_like(cx, 0.001), cx, cy, z2], axis=2)            # (B, NC, 6) as config 3
+    vel = speed * np.stack([np.cos(head), np.sin(head), np.zeros_like(head)], axis=2)  # (B, NC, 3) m/s
+    t = robot.delta_t * np.arange(1, H + 1)                                            # waypoint i at time i*delta_t
+    shift = t[None, :, None, None] * np.concatenate([vel, vel], axis=2)[:, None]       # (B, H, NC, 6)
+    traj = cand[:, None] + shift
+    obs = np.zeros((B, H, nobs, 6))
+    vkeep = np.zeros((B, nobs, 3))
+    for b in range(B):
+        d0 = np.asarray(dist_fn(robot, x0[b][None], traj[b, 0]))                       # (1, NC)
+        d1 = np.asarray(dist_fn(robot, xg[b][None], traj[b, H - 1]))
+        ok = np.nonzero((d0 >= 0.25).all(axis=0) & (d1 >= 0.25).all(axis=0))[0]
+        if ok.size < nobs:
+            raise RuntimeError(f"problem {b}: only {ok.size} of {NCAND} obstacle candidates accepted")
+        obs[b] = traj[b][:, ok[:nobs]]
+        vkeep[b] = vel[b, ok[:nobs]]
+    x_init, xR1, ff, caug = _batch_terms(s, x0, xg)
+    batch = SimpleNamespace(B=B, nobs=nobs, x0=x0, xg=xg, x_init=x_init, xR1=xR1, ff=ff, caug=caug, obs=obs, vel=vkeep,
                             noise=noise, margin_cfs=np.full(nobs, 0.25), margin_psg=np.full(nobs, 0.2))
     return s, batch
 
