@@ -247,7 +247,10 @@ int cfs_dist_arm_grad(const cfs_robot *robot, int njoint, int N, const double *t
 int cfs_linearize(cfs_problem *p, int B, const double *x_, const double *obs, double *dist, int *linkid, double *grad);
 
 /* self.get_con() with the reference's public dense outputs self.Ainq / self.binq
- * (Lib/CFS_FANUC.m:101-135): rows = nobs*H*(1+2*njoint) in the reference's row order.
+ * (Lib/CFS_FANUC.m:101-135): rows = nobs*H*(1+2*njoint) in the reference's row order.  On a handle with joint limits
+ * (cfs_problem_set_joint_limits) rows = nobs*H*(1+2*njoint) + 2*H*njoint: the reference's rows, then +pos (i, c) for every
+ * waypoint i and joint c (Bpos row (i, c) <= hi_c - theta0_c - (i+1)*delta_t*v0_c), then -pos (i, c) (-Bpos row (i, c) <=
+ * theta0_c + (i+1)*delta_t*v0_c - lo_c), theta0 / v0 = xR1(1:njoint) / xR1(njoint+1:end); an infinite bound gives an infinite binq.
  * x_: B x (H*nstate); u: B x nn; xR1: B x nstate; obs: B x nobs x 6 (B x H x nobs x 6 per waypoint);
  * Ainq: B x (rows x nn column-major); binq: B x rows. */
 int cfs_get_con(cfs_problem *p, int B, const double *x_, const double *u, const double *xR1, const double *obs,
@@ -258,7 +261,8 @@ int cfs_get_con(cfs_problem *p, int B, const double *x_, const double *u, const 
  * (Lib/CFS_FANUC.m:85); PSGCFS mode = quadprog(I,-u_,Ainq,binq) (Lib/PSGCFS_FANUC.m:117-120) with
  * u_ passed in `lin`.  lin: B x nn (CFS: ff; PSGCFS: u_); u_lin: B x nn; xR1: B x nstate.
  * Outputs u: B x nn; lambda (optional): B x (nobs*H + 4*nn) multipliers ordered
- * [collision (j,i) | vel+ (i,c) | vel- (i,c) | bound+ | bound-]; qp_iter, status: B. */
+ * [collision (j,i) | vel+ (i,c) | vel- (i,c) | bound+ | bound-] (with joint limits B x (nobs*H + 6*nn): then | pos+ (i,c) |
+ * pos- (i,c)]); qp_iter, status: B. */
 int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const double *xR1,
            const double *dist, const double *grad, double *u, double *lambda, int *qp_iter, int *status);
 
@@ -330,6 +334,23 @@ int cfs_soft_results(cfs_problem *p, int B, double *viol_all, int *n_soft);
 typedef enum cfs_obstacle_motion { CFS_OBS_STATIC = 0, CFS_OBS_PER_WAYPOINT = 1 } cfs_obstacle_motion;
 int cfs_problem_set_obstacle_motion(cfs_problem *p, int motion);
 int cfs_problem_get_obstacle_motion(const cfs_problem *p, int *motion);
+
+/* ---- joint position limits ---------------------------------------------------------------------------
+ * The reference bounds velocities (Lib/CFS_FANUC.m:126-129, Lib/PSGCFS_FANUC.m:175-178) and, in CFS mode, inputs, never positions,
+ * although robotproperty2.m defines robot.thetamax.  With limits set, every QP of the handle (whole solves, cfs_qp, cfs_get_con) has
+ * two more hard rows per waypoint i and joint c:  lo_c <= theta0_c + (i+1)*delta_t*v0_c + (Bpos u)[i,c] <= hi_c,  i.e. row i of x_
+ * as the solver computes it (no DH offset is applied: the bounds are on x_ itself).  The rows are hard in the soft QP of
+ * CFS_INFEAS_SOFTEN too (they never get a slack and never enter viol_all).  A QP whose limits cannot be met (a start outside them by
+ * more than the velocity rows let one step cover) ends the problem with CFS_QP_INFEASIBLE under either policy.  lo / hi: njoint
+ * values each; either side may be infinite (a row that can never become active).  lo == hi == NULL clears the limits (the default:
+ * every result is then the unlimited handle's).  With rows that never bind, every result is bit for bit the unlimited handle's.
+ * CFS_ERR_INVALID_ARG, nothing changes: NULL handle; one of lo / hi NULL; a NaN; lo[c] >= hi[c]; a shape whose LDS plan with the
+ * position rows does not fit every tier of the fused solver that the plan without them fits (checked here, not at launch).  On a
+ * handle with limits cfs_chomp_batch gives CFS_ERR_INVALID_ARG (CHOMP_FANUC has no QP).  Mesh handles (cfs_problem_set_meshes) run
+ * the same QP and get the rows too.  Set them between solves.
+ * get: *on = 1 with limits, 0 without; lo / hi (njoint each, either may be NULL) receive them, -inf / +inf without limits. */
+int cfs_problem_set_joint_limits(cfs_problem *p, const double *lo, const double *hi);
+int cfs_problem_get_joint_limits(const cfs_problem *p, int *on, double *lo, double *hi);
 
 /* ---- mesh obstacles -----------------------------------------------------
  * The reference measures the arm against a surface with `[dis, points] = point2surface_dis(pos{i}.p, obs)`

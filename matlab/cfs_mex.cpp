@@ -14,6 +14,8 @@
 //        geometry kernel RRT_FANUC.feasible (Lib/RRT_FANUC.m:146-181) and get_con (Lib/CFS_FANUC.m:115) call; d, linkid = nobs x N;
 //        grad (when asked for) = njoint x (nobs*N), column (n-1)*nobs+j = the analytic d(d(j,n))/d(theta(:,n)) (cfs_dist_arm_grad)
 //   'solve' and 'get_con' honour an optional sys_info.jacobian = 'fd_literal' (default, num_jac.m) | 'analytic' (include/cfs_hip.h)
+//   'solve' and 'get_con' honour an optional sys_info.joint_limits = njoint x 2 [lo, hi] (rad, bounds on x_; cfs_problem_set_joint_limits):
+//   every QP keeps the waypoints inside, and get_con returns 2*H*njoint more rows (+pos (i,c), then -pos (i,c))
 //   'solve' and 'get_con' accept moving obstacles: obs{j}.l may be 3x2xH (page i = the axis at waypoint i); any such entry makes
 //   the handle CFS_OBS_PER_WAYPOINT and the 3x2 entries are held over the horizon (include/cfs_hip.h, moving obstacles)
 //   [route, all_nodes, total_dis, all_ee, fail, node_num] = cfs_mex('rrt', obs, sys_info, goal, region_g, region_s, sample_off, ROBOT, SOLVER, U)
@@ -131,6 +133,13 @@ static void make_family(Family &f, int mode, const mxArray *obs, int first, int 
         if (jm == "analytic") check(cfs_problem_set_jacobian(f.p, CFS_JAC_ANALYTIC));
         else if (jm != "fd_literal") mexErrMsgIdAndTxt("cfs:field", "sys_info.jacobian must be 'fd_literal' or 'analytic'");
     }
+    // optional sys_info.joint_limits = njoint x 2 [lo, hi] (cfs_problem_set_joint_limits; CHOMP_FANUC has no QP to hold them)
+    if (const mxArray *fl = need_both ? nullptr : mxGetField(S, 0, "joint_limits")) {
+        if (mxIsChar(fl) || (int)mxGetM(fl) != d.njoint || mxGetN(fl) != 2)
+            mexErrMsgIdAndTxt("cfs:field", "sys_info.joint_limits must be an njoint x 2 double matrix [lo, hi]");
+        const double *jl = mxGetPr(fl);                    // column-major: lo = column 1, hi = column 2
+        check(cfs_problem_set_joint_limits(f.p, jl, jl + d.njoint));
+    }
 }
 
 static void solve(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
@@ -168,7 +177,9 @@ static void get_con(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     const std::string ROBOT = mxArrayToString(prhs[4]);
     Family f;
     make_family(f, mode, prhs[2], 0, (int)mxGetNumberOfElements(prhs[2]), prhs[3], ROBOT.c_str(), false, true);
-    const int nn = f.d.H * f.d.njoint, rows = f.d.nobs * f.d.H * (1 + 2 * f.d.njoint);
+    int on = 0;
+    check(cfs_problem_get_joint_limits(f.p, &on, nullptr, nullptr));
+    const int nn = f.d.H * f.d.njoint, rows = f.d.nobs * f.d.H * (1 + 2 * f.d.njoint) + (on ? 2 * nn : 0);
     mxArray *A = mxCreateDoubleMatrix(rows, nn, mxREAL), *b = mxCreateDoubleMatrix(rows, 1, mxREAL);
     check(cfs_get_con(f.p, 1, mxGetPr(prhs[5]), mxGetPr(prhs[6]), field_ptr(prhs[3], "xR"), f.obs6.data(), mxGetPr(A), mxGetPr(b)));
     plhs[0] = A;

@@ -199,6 +199,8 @@ struct cfs_problem {
     int jac = CFS_JAC_FD_LITERAL;         // cfs_problem_set_jacobian: which linearisation every later launch of this handle runs
     int infeas = CFS_INFEAS_STOP;         // cfs_problem_set_infeasible_policy
     int motion = CFS_OBS_STATIC;          // cfs_problem_set_obstacle_motion: obs arrays are B x nobs x 6 | B x H x nobs x 6
+    bool limited = false;                 // cfs_problem_set_joint_limits: position rows in every QP (the LIM kernels); lim[nj, 3nj) = [lo; hi]
+    std::vector<double> jlim;             // [lo; hi] as set (2 nj; empty: no limits)
     double soft_weight = 0.0;             // mu of CFS_INFEAS_SOFTEN (0: never set)
     DevBuf<double> soft_viol;             // max_batch x MAX_O_ITER: viol_all of the last whole solve (allocated with SOFTEN)
     DevBuf<int> soft_n;                   // max_batch: n_soft of the last whole solve
@@ -244,29 +246,42 @@ bool fused_fits(int nj, int H, int nobs) { return fused_fits_tier<FUSED_W1>(nj, 
 // The tier is chosen by the static plan for either kind of handle: cfs_problem_set_obstacle_motion admits a per-waypoint handle only
 // when its plan fits every tier the static one fits (fused_fits_move), so a per-waypoint solve runs the same tier, and with constant
 // rows the same arithmetic, as the static one.
-bool fused_fits_move(int nj, int H, int nobs, int mode)
+bool fused_fits_move(int nj, int H, int nobs, int mode, bool lim)
 {
-    if (!fused_fits_tier<FUSED_W1>(nj, H, nobs, true)) return false;
-    if (mode == CFS_MODE_PSGCFS) return fused_fits_tier<FUSED_W2S>(nj, H, nobs, true) == fused_fits_tier<FUSED_W2S>(nj, H, nobs);
-    return fused_fits_tier<FUSED_W2M>(nj, H, nobs, true) == fused_fits_tier<FUSED_W2M>(nj, H, nobs);
+    if (!fused_fits_tier<FUSED_W1>(nj, H, nobs, true, lim)) return false;
+    if (mode == CFS_MODE_PSGCFS) return fused_fits_tier<FUSED_W2S>(nj, H, nobs, true, lim) == fused_fits_tier<FUSED_W2S>(nj, H, nobs);
+    return fused_fits_tier<FUSED_W2M>(nj, H, nobs, true, lim) == fused_fits_tier<FUSED_W2M>(nj, H, nobs);
 }
-template <FusedTier T, bool MOVE>
+// The same rule for joint limits: cfs_problem_set_joint_limits admits them only when the LIM plan fits every tier the plain static plan
+// fits, so a limited solve runs the same tier (and, with rows that never bind, the same arithmetic) as the unlimited one.
+bool fused_fits_lim(int nj, int H, int nobs, int mode, bool move)
+{
+    if (!fused_fits_tier<FUSED_W1>(nj, H, nobs, move, true)) return false;
+    if (mode == CFS_MODE_PSGCFS) return fused_fits_tier<FUSED_W2S>(nj, H, nobs, move, true) == fused_fits_tier<FUSED_W2S>(nj, H, nobs);
+    return fused_fits_tier<FUSED_W2M>(nj, H, nobs, move, true) == fused_fits_tier<FUSED_W2M>(nj, H, nobs);
+}
+template <FusedTier T, bool MOVE, bool LIM>
 static hipError_t launch_tier_m(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft)
 {
-    if (soft) return analytic ? launch_fused_tier<T, true, true, MOVE>(nj, p, s, soft) : launch_fused_tier<T, false, true, MOVE>(nj, p, s, soft);
-    return analytic ? launch_fused_tier<T, true, false, MOVE>(nj, p, s, nullptr) : launch_fused_tier<T, false, false, MOVE>(nj, p, s, nullptr);
+    if (soft) return analytic ? launch_fused_tier<T, true, true, MOVE, LIM>(nj, p, s, soft) : launch_fused_tier<T, false, true, MOVE, LIM>(nj, p, s, soft);
+    return analytic ? launch_fused_tier<T, true, false, MOVE, LIM>(nj, p, s, nullptr) : launch_fused_tier<T, false, false, MOVE, LIM>(nj, p, s, nullptr);
+}
+template <FusedTier T, bool LIM>
+static hipError_t launch_tier_l(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft, bool move)
+{
+    return move ? launch_tier_m<T, true, LIM>(nj, p, s, analytic, soft) : launch_tier_m<T, false, LIM>(nj, p, s, analytic, soft);
 }
 template <FusedTier T>
-static hipError_t launch_tier(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft, bool move)
+static hipError_t launch_tier(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft, bool move, bool lim)
 {
-    return move ? launch_tier_m<T, true>(nj, p, s, analytic, soft) : launch_tier_m<T, false>(nj, p, s, analytic, soft);
+    return lim ? launch_tier_l<T, true>(nj, p, s, analytic, soft, move) : launch_tier_l<T, false>(nj, p, s, analytic, soft, move);
 }
-hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1, bool analytic, const SoftParams *soft, bool move)
+hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1, bool analytic, const SoftParams *soft, bool move, bool lim)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
-    if (!force_w1 && ident && fused_fits_tier<FUSED_W2S>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2S>(nj, p, s, analytic, soft, move);
-    if (!force_w1 && !ident && fused_fits_tier<FUSED_W2M>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2M>(nj, p, s, analytic, soft, move);
-    return launch_tier<FUSED_W1>(nj, p, s, analytic, soft, move);
+    if (!force_w1 && ident && fused_fits_tier<FUSED_W2S>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2S>(nj, p, s, analytic, soft, move, lim);
+    if (!force_w1 && !ident && fused_fits_tier<FUSED_W2M>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2M>(nj, p, s, analytic, soft, move, lim);
+    return launch_tier<FUSED_W1>(nj, p, s, analytic, soft, move, lim);
 }
 
 extern "C" {
@@ -427,7 +442,7 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
     hipError_t e = hipSetDevice(p->device);
 #define A_(buf, count) if (e == hipSuccess) e = p->buf.alloc(count)
     A_(rb, 1); A_(QQ, (size_t)nn * nn); A_(Hinv, (size_t)nn * nn);
-    A_(M1n, (size_t)nn * nn); A_(M2n, (size_t)nn * nn); A_(Hq, (size_t)nn * nn); A_(Pt, Pn * pt_stride(nn)); A_(lim, nj); A_(maxin, nn); A_(margin, desc->nobs);
+    A_(M1n, (size_t)nn * nn); A_(M2n, (size_t)nn * nn); A_(Hq, (size_t)nn * nn); A_(Pt, Pn * pt_stride(nn)); A_(lim, 3 * (size_t)nj); A_(maxin, nn); A_(margin, desc->nobs);
     A_(x0, Bm * nn); A_(qu, Bm * nn); A_(dist, Bm * desc->nobs * H); A_(grad, Bm * desc->nobs * H * nj);
     A_(Yg, Pn * nn * nn); A_(pool_flag, Pn * 16);
     if (desc->mode == CFS_MODE_CFS) { A_(u_hist, Bm * (size_t)desc->MAX_O_ITER * nn); A_(qu_hist, Bm * (size_t)desc->MAX_O_ITER * nn); }
@@ -598,6 +613,7 @@ static void fill_fused_family(const cfs_problem *p, FusedParams &fp, int B)
 static bool force_w1(const cfs_problem *p) { return (p->dbg_mask & CFS_DBG_TIER_W1) != 0; }
 static bool analytic(const cfs_problem *p) { return p->jac == CFS_JAC_ANALYTIC; }
 static bool moving(const cfs_problem *p) { return p->motion == CFS_OBS_PER_WAYPOINT; }
+static bool limited(const cfs_problem *p) { return p->limited; }
 // obstacle rows per problem in every obs array the handle reads: nobs (static) | H x nobs (per waypoint)
 static size_t obs_rows(const cfs_problem *p) { return (size_t)p->d.nobs * (moving(p) ? (size_t)p->d.H : 1); }
 // the soft kernels' parameters for a SOFTEN handle (null: STOP, the default kernels); whole: record viol_all / n_soft
@@ -703,7 +719,7 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
     }
     if (p->prof) HIPCHK(hipEventRecord(e4[2], s));   // after the launch-order pre-pass: [e4[2], e4[3]] brackets the fused kernel alone (mesh handles: the loop of launches)
     if (p->nmesh == 0) {
-        HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), soft, moving(p)));
+        HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), soft, moving(p), limited(p)));
     } else {
         // Mesh obstacles are linearised by their own kernel (hierarchy traversals do not fit the fused kernel's register
         // budget), which needs the current iterate: one outer iteration per launch, state carried through HBM.  Every
@@ -720,7 +736,7 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
             lm.seed_prev = it > 0;
             HIPCHK(launch_linearize_mesh(nj, lm, s));
             fp.resume = it > 0;
-            HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p)));
+            HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), nullptr, false, limited(p)));
         }
     }
     if (p->prof) HIPCHK(hipEventRecord(e4[3], s));
@@ -1020,6 +1036,7 @@ int cfs_chomp_batch(cfs_problem *p, const cfs_batch_in *in, const double *u0, co
     if (!out->u || !out->x_ || !out->cost_all || !out->e_cost_all || !out->e_u_all || !out->iter_O) return fail(CFS_ERR_INVALID_ARG, "NULL output array");
     if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC measures line obstacles only (Lib/CHOMP_FANUC.m:119)");
     if (moving(p)) return fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC takes static obstacles only (the handle is CFS_OBS_PER_WAYPOINT)");
+    if (limited(p)) return fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC has no QP to hold joint limits (the handle has them: clear them first)");
     if (!chomp_fits(p->d.njoint, p->d.H, p->d.nobs)) return fail(CFS_ERR_INVALID_ARG, "H x nobs too large for the CHOMP kernel's 64 KB of LDS");
     HIPCHK(hipSetDevice(p->device));
     const size_t nn = p->nn, nx = p->nx, ns = p->ns, K = p->d.MAX_O_ITER, nobs = p->d.nobs;
@@ -1214,11 +1231,46 @@ int cfs_problem_set_obstacle_motion(cfs_problem *p, int motion)
     if (motion != CFS_OBS_STATIC && motion != CFS_OBS_PER_WAYPOINT) return fail(CFS_ERR_INVALID_ARG, "unknown obstacle motion %d", motion);
     if (motion == CFS_OBS_PER_WAYPOINT) {
         if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are static: CFS_OBS_PER_WAYPOINT needs a handle without meshes");
-        if (!fused_fits_move(p->d.njoint, p->d.H, p->d.nobs, p->d.mode))
+        if (!fused_fits_move(p->d.njoint, p->d.H, p->d.nobs, p->d.mode, limited(p)))
             return fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d: the per-waypoint obstacle rows of a linearisation tile do not fit the "
                         "on-chip budget of the static plan's tier", p->d.H, p->d.nobs, p->d.njoint);
     }
     p->motion = motion;
+    return CFS_SUCCESS;
+}
+
+int cfs_problem_set_joint_limits(cfs_problem *p, const double *lo, const double *hi)
+{
+    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (!lo && !hi) { p->limited = false; p->jlim.clear(); return CFS_SUCCESS; }
+    if (!lo || !hi) return fail(CFS_ERR_INVALID_ARG, "lo and hi are both given or both NULL");
+    const int nj = p->d.njoint;
+    for (int c = 0; c < nj; ++c) {
+        if (std::isnan(lo[c]) || std::isnan(hi[c])) return fail(CFS_ERR_INVALID_ARG, "joint %d: NaN limit", c);
+        if (!(lo[c] < hi[c])) return fail(CFS_ERR_INVALID_ARG, "joint %d: lo %g >= hi %g", c, lo[c], hi[c]);
+    }
+    if (!fused_fits_lim(nj, p->d.H, p->d.nobs, p->d.mode, moving(p)))
+        return fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d: the LDS plan with joint limits does not fit every tier of the fused solver "
+                    "that the plan without them fits", p->d.H, p->d.nobs, nj);
+    std::vector<double> v(lo, lo + nj);
+    v.insert(v.end(), hi, hi + nj);
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipDeviceSynchronize());      // a solve in flight may still be reading the previous limits
+    HIPCHK(hipMemcpy(p->lim.p + nj, v.data(), 2 * (size_t)nj * sizeof(double), hipMemcpyHostToDevice));
+    p->jlim = v;
+    p->limited = true;
+    return CFS_SUCCESS;
+}
+
+int cfs_problem_get_joint_limits(const cfs_problem *p, int *on, double *lo, double *hi)
+{
+    if (!p || !on) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    const int nj = p->d.njoint;
+    *on = p->limited ? 1 : 0;
+    for (int c = 0; c < nj; ++c) {
+        if (lo) lo[c] = p->limited ? p->jlim[c] : -INFINITY;
+        if (hi) hi[c] = p->limited ? p->jlim[nj + c] : INFINITY;
+    }
     return CFS_SUCCESS;
 }
 
@@ -1305,7 +1357,7 @@ static int linearize_piece(cfs_problem *p, int B, const PieceBuffers &pb, double
         fp.nmesh = p->nmesh; fp.ext_dist = p->dist.p; fp.ext_grad = p->grad.p;
     }
     SoftParams sp;
-    HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false), moving(p)));
+    HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false), moving(p), limited(p)));
     return CFS_SUCCESS;
 }
 
@@ -1341,7 +1393,7 @@ int cfs_get_con(cfs_problem *p, int B, const double *x_, const double *u, const 
     if (!x_ || !u || !xR1 || !obs || !Ainq || !binq) return fail(CFS_ERR_INVALID_ARG, "NULL array");
     HIPCHK(hipSetDevice(p->device));
     const size_t nobs = p->d.nobs, H = p->d.H, nj = p->d.njoint, nn = p->nn;
-    const size_t rows = nobs * H * (1 + 2 * nj);
+    const size_t rows = nobs * H * (1 + 2 * nj) + (limited(p) ? 2 * nn : 0);   // limited: + pos+ (i, c), pos- (i, c)
     Stage st;
     PieceBuffers pb;
     rc = stage_piece(p, st, B, x_, xR1, obs, pb);
@@ -1354,6 +1406,7 @@ int cfs_get_con(cfs_problem *p, int B, const double *x_, const double *u, const 
     dc.u = st.up(u, (size_t)B * nn);
     dc.xR1 = pb.xR1;
     dc.lim = p->lim.p; dc.margin = p->margin.p;
+    dc.plim = limited(p) ? p->lim.p + nj : nullptr;
     dc.Ainq = st.up<double>(nullptr, (size_t)B * rows * nn);
     dc.binq = st.up<double>(nullptr, (size_t)B * rows);
     if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
@@ -1376,7 +1429,7 @@ int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const 
     if (!lin || !u_lin || !xR1 || !dist || !grad || !u) return fail(CFS_ERR_INVALID_ARG, "NULL array");
     HIPCHK(hipSetDevice(p->device));
     const size_t nobs = p->d.nobs, H = p->d.H, nj = p->d.njoint, nn = p->nn;
-    const size_t nlam = nobs * H + 4 * nn;
+    const size_t nlam = nobs * H + (limited(p) ? 6 : 4) * nn;   // [collision | vel+ | vel- | bound+ | bound- (| pos+ | pos-)]
     Stage st;
     PieceBuffers pb;
     rc = stage_piece(p, st, B, nullptr, xR1, nullptr, pb);
@@ -1401,7 +1454,7 @@ int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const 
         fp.x0 = p->x0.p;
     } else fp.x0 = d_lin;
     SoftParams sp;
-    HIPCHK(launch_fused(p->d.njoint, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false)));
+    HIPCHK(launch_fused(p->d.njoint, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false), false, limited(p)));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(nullptr));
     st.down(u, d_u, (size_t)B * nn);

@@ -74,6 +74,7 @@ struct DenseConParams {
     const double *lim, *margin;
     double *Ainq;                // B x rows x nn (column-major per problem)
     double *binq;                // B x rows
+    const double *plim;          // null, or [lo; hi] (2 nj): rows += 2 H nj position rows after the reference's, +pos (i,c) then -pos (i,c)
 };
 void launch_dense_con(const DenseConParams &p, hipStream_t s);
 
@@ -136,7 +137,8 @@ struct FusedParams {
     double *dump_dist;           // B x nobs x H       distances of the first linearisation of this launch (may be null)
     double *dump_grad;           // B x nobs x H x NJ  Diff of the same
     int *dump_linkid;            // B x nobs x H       closest link (1-based, line obstacles only)
-    double *dump_lambda;         // B x (nobs*H + 4nn) multipliers of the last QP [collision (j,i) | vel+ | vel- | bound+ | bound-] (may be null)
+    double *dump_lambda;         // B x (nobs*H + 4nn) multipliers of the last QP [collision (j,i) | vel+ | vel- | bound+ | bound-] (may be null;
+                                 // LIM kernels: B x (nobs*H + 6nn), then | pos+ | pos-)
 };
 // soft-constraint QP after a proven-infeasible one (CFS_INFEAS_SOFTEN handles): the second parameter block of the SOFT kernels
 struct SoftParams {
@@ -150,17 +152,24 @@ struct SoftParams {
 //   w2s 2 / 16  same, smallest register footprint (no spills): the projection QPs of PSGCFS have 2-3 active rows
 // and each tier into one object per variant (Makefile): JAC, the analytic Jacobian (CFS_JAC_ANALYTIC handles), and SOFT, the soft
 // QP (sp; null without SOFT), and MOVE, per-waypoint obstacles (CFS_OBS_PER_WAYPOINT handles: obs is B x H x nobs x 6, staged per
-// linearisation tile).  Every object defines its own launch_fused_tier<tier, JAC, SOFT, MOVE>, the tier's default object its
-// fused_fits_tier<tier> (the variants share the LDS layout and capacities; move: the MOVE plan, whose tiles carry the obstacle rows).
+// linearisation tile), and LIM, joint position limits (handles with cfs_problem_set_joint_limits: lim is [lim; lo; hi], 3 nj; the
+// position rows are hard rows of every QP).  Every object defines its own launch_fused_tier<tier, JAC, SOFT, MOVE, LIM>, the tier's
+// default object its fused_fits_tier<tier> (the variants share the LDS layout and capacities; move: the MOVE plan, whose tiles carry
+// the obstacle rows; lim: the LIM plan, whose flag / slot arrays cover the position rows).
 enum FusedTier { FUSED_W1, FUSED_W2M, FUSED_W2S };
-template <FusedTier T, bool JAC, bool SOFT, bool MOVE> hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftParams *sp);
-template <FusedTier T> bool fused_fits_tier(int nj, int H, int nobs, bool move = false);
-// cfs_api.hip: tier by mode and capacity; analytic: the JAC kernels; soft (non-null): the SOFT kernels; move: the MOVE kernels
+template <FusedTier T, bool JAC, bool SOFT, bool MOVE, bool LIM>
+hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftParams *sp);
+template <FusedTier T> bool fused_fits_tier(int nj, int H, int nobs, bool move = false, bool lim = false);
+// cfs_api.hip: tier by mode and capacity; analytic: the JAC kernels; soft (non-null): the SOFT kernels; move: the MOVE kernels;
+// lim: the LIM kernels
 hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1 = false, bool analytic = false, const SoftParams *soft = nullptr,
-                        bool move = false);
+                        bool move = false, bool lim = false);
 bool fused_fits(int nj, int H, int nobs);
-// does the per-waypoint plan fit every tier the static one fits for this mode (same tier, hence the same arithmetic)?
-bool fused_fits_move(int nj, int H, int nobs, int mode);
+// does the per-waypoint plan fit every tier the static one fits for this mode (same tier, hence the same arithmetic)?  lim: the
+// plan with joint limits as well
+bool fused_fits_move(int nj, int H, int nobs, int mode, bool lim = false);
+// does the plan with joint limits (and per-waypoint obstacles when move) fit every tier the plain static plan fits for this mode?
+bool fused_fits_lim(int nj, int H, int nobs, int mode, bool move);
 
 struct CostHistParams {          // EVAL.get_cost / store_result for a logged u history (CFS mode)
     int B, nn, max_o_iter;

@@ -17,6 +17,8 @@
 //     soft-constraint QP of the same linearisation: 1/mu on the Gram diagonal of the collision rows;
 //   * kernels instantiated with MOVE (CFS_OBS_PER_WAYPOINT handles) read obstacle row (b, i, j) of a B x H x nobs x 6 array
 //     for waypoint i, staged per linearisation tile into LDS next to the tile's scratch;
+//   * kernels instantiated with LIM (handles with joint limits) add the position rows theta0 + (i+1) dt v0 + Bpos u in [lo, hi]
+//     per waypoint and joint as hard rows of every QP (constraint types CT_POSP / CT_POSM);
 //   * QP: Goldfarb-Idnani dual active set in range-space form.  The inverse Gram matrix
 //     P = (N'H^{-1}N)^{-1} is kept EXPLICITLY, one row per thread in registers (it is symmetric,
 //     so column access is never needed); adding a constraint is a bordered rank-1 update,
@@ -42,6 +44,9 @@ constexpr int CERT_AT = 6;              // main-loop steps of a QP before the st
 #ifndef CFS_MOVE
 #define CFS_MOVE 0                        // this object's variant: per-waypoint obstacles (Makefile)
 #endif
+#ifndef CFS_LIM
+#define CFS_LIM 0                         // this object's variant: joint position limits (Makefile)
+#endif
 constexpr double REF_A = 1e-4;           // refinement of a step direction continues while |r'rho| > A * max(|delta|, tol * n'H^-1 n) ...
 constexpr double REF_B = 1e-9;           // ... or max|rho| > B * max|d|  (rho_a = n_a'z, zero in exact arithmetic)
 constexpr int MV_BATCH = 16;             // QQ*u: loads in flight per thread
@@ -54,7 +59,8 @@ constexpr int MV_BATCH = 16;             // QQ*u: loads in flight per thread
 static_assert(CFS_PR % 8 == 0 && CFS_PR >= 8, "register-resident P columns come in chunks of 8");
 constexpr int FT = 256;                  // threads per workgroup
 constexpr double DEP_TOL_F = 1e-8;       // dependent if delta <= tol * n'H^{-1}n: above the eps*cond(H) noise floor of Y = H^{-1}N
-enum { CT_COL = 0, CT_VELP = 1, CT_VELM = 2, CT_BNDP = 3, CT_BNDM = 4 };
+// CT_POSP / CT_POSM: joint position rows theta0 + (i+1) dt v0 + (Bpos u)[i,c] <= hi_c | >= lo_c (LIM kernels only)
+enum { CT_COL = 0, CT_VELP = 1, CT_VELM = 2, CT_BNDP = 3, CT_BNDM = 4, CT_POSP = 5, CT_POSM = 6 };
 __device__ __forceinline__ int mk_code(int type, int i, int jc) { return (type << 16) | (i << 8) | jc; }
 
 // ---- DPP helpers (gfx9 row shifts / row broadcasts) ---------------------------------------------
@@ -213,10 +219,14 @@ __device__ __forceinline__ void roll_lds(double *buf, int H, double dt, int tid)
 }
 
 // inward normal of constraint `code` applied to a vector given as (v, Bvel v, Bpos v) in LDS
-template <int NJ>
+template <int NJ, bool LIM = false>
 __device__ __forceinline__ double ndot(int code, const double *buf, const double *g, int H)
 {
     const int type = code >> 16, i = (code >> 8) & 0xff, jc = code & 0xff, HN = H * NJ;
+    if constexpr (LIM) {                        // position rows: -+ Bpos row (i, jc)
+        if (type == CT_POSP) return -buf[2 * HN + i * NJ + jc];
+        if (type == CT_POSM) return buf[2 * HN + i * NJ + jc];
+    }
     switch (type) {
     case CT_COL: {
         double s = 0.0;
@@ -231,12 +241,21 @@ __device__ __forceinline__ double ndot(int code, const double *buf, const double
     }
 }
 
-// slack b - a'x of constraint `code` at the iterate xs = (x, Bvel x, Bpos x); *bnd = its right-hand side
-template <int NJ>
+// slack b - a'x of constraint `code` at the iterate xs = (x, Bvel x, Bpos x); *bnd = its right-hand side.
+// LIM: plim = [lo; hi] (2 NJ), theta0 = v0 + NJ (the small block), dt the step.
+template <int NJ, bool LIM = false>
 __device__ __forceinline__ double slack_of(int code, const double *xs, const double *g, const double *rhs,
-                                           const double *lim, const double *v0, const double *maxin, int H, double *bnd)
+                                           const double *lim, const double *v0, const double *maxin, int H, double *bnd,
+                                           double dt = 0.0, const double *plim = nullptr)
 {
     const int type = code >> 16, i = (code >> 8) & 0xff, jc = code & 0xff, HN = H * NJ;
+    if constexpr (LIM) {
+        if (type == CT_POSP || type == CT_POSM) {
+            const double pos = v0[NJ + jc] + ((double)(i + 1) * dt) * v0[jc];   // theta0 + (i+1) dt v0: x_ without Bpos u
+            if (type == CT_POSP) { const double bb = plim[NJ + jc] - pos; *bnd = bb; return bb - xs[2 * HN + i * NJ + jc]; }
+            const double bb = pos - plim[jc]; *bnd = bb; return bb + xs[2 * HN + i * NJ + jc];
+        }
+    }
     switch (type) {
     case CT_COL: {
         const double rh = rhs[jc * H + i];
@@ -269,12 +288,24 @@ __device__ __forceinline__ double ramp_dot(int a, int b, int m)   // sum_{k=0..m
     const int M = m + 1;
     return 0.25 * (double)(M * (2 * a + 1) * (2 * b + 1) - 2 * (a + b + 1) * m * M + 2 * (m * M * (2 * m + 1) / 3));
 }
-template <int NJ>
+// A position row (LIM) is a collision row whose gradient is -+e_c: n[k,c] = -+((i-k)+1/2) dt^2 for k <= i on its joint.
+template <int NJ, bool LIM = false>
 __device__ __forceinline__ double gram_ident(int ca, int cp, const double *g, int H, double dt)   // n_a' n_p
 {
     const int ta = ca >> 16, ia = (ca >> 8) & 0xff, ja = ca & 0xff;
     const int tp = cp >> 16, ip = (cp >> 8) & 0xff, jp = cp & 0xff;
     const int m = min(ia, ip);
+    if constexpr (LIM) {
+        const bool pa = ta >= CT_POSP, pp = tp >= CT_POSP;
+        if (pa || pp) {
+            const double sa = (ta == CT_POSP || ta == CT_VELP) ? -1.0 : 1.0, sp = (tp == CT_POSP || tp == CT_VELP) ? -1.0 : 1.0;
+            if (ta == CT_COL) return (sp * g[(ja * H + ia) * NJ + jp]) * ((dt * dt) * (dt * dt) * ramp_dot(ia, ip, m));
+            if (tp == CT_COL) return (sa * g[(jp * H + ip) * NJ + ja]) * ((dt * dt) * (dt * dt) * ramp_dot(ia, ip, m));
+            if (ja != jp) return 0.0;
+            if (pa && pp) return (sa * sp) * ((dt * dt) * (dt * dt) * ramp_dot(ia, ip, m));
+            return (sa * sp) * ((dt * dt * dt) * ramp_sum(pa ? ia : ip, m));   // position row against a velocity row
+        }
+    }
     if (ta == CT_COL && tp == CT_COL) {
         double dot = 0.0;
 #pragma unroll
@@ -402,7 +433,9 @@ struct PRow {
 struct FusedLayout {      // LDS offsets in doubles, computed identically on host and device
     int rb, ob, x, u, qu, g, rhs, xs, up, wb, zb, d, r, rho, lam, prow, act, fre, prev, flag, slot, code, red, small, mx, racc, cost, ptail, lin, y, total_fixed;
 };
-__host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int QB, int PR)
+// lim (LIM kernels): flag / slot cover the position rows too (nobs*H + 6HN), code only the collision rows (the only codes the
+// kernel reads back), and the small block carries [lo; hi] after the margins.  The footprint is never larger than without lim.
+__host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int QB, int PR, bool lim = false)
 {
     FusedLayout L;
     const int HN = H * NJ, NS = 2 * NJ;
@@ -419,10 +452,10 @@ __host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int
     L.act = o; o += (QB + 1) / 2;
     L.fre = o; o += (QB + 1) / 2;          // stack of freed slots
     L.prev = o; o += (QB + 1) / 2;         // active rows (codes per slot) at the end of the previous QP: the warm start
-    L.flag = o; o += (nobs * H + 4 * HN + 7) / 8;
-    L.code = o; o += (nobs * H + 4 * HN + 1) / 2;
+    L.flag = o; o += (nobs * H + (lim ? 6 : 4) * HN + 7) / 8;
+    L.code = o; o += lim ? (nobs * H + 1) / 2 : (nobs * H + 4 * HN + 1) / 2;
     L.red = o; o += 64;                    // two exchange buffers of 24 doubles + 12 stamp accumulators
-    L.small = o; o += 4 * NJ + nobs;       // lim, v0, theta0 (2NJ), margin
+    L.small = o; o += 4 * NJ + nobs + (lim ? 2 * NJ : 0);   // lim, v0, theta0 (2NJ), margin; lim: lo, hi
     L.mx = o; o += HN;                     // MAX_input
     L.racc = o; o += HN;                   // how far the input bounds let waypoint (i, c) move: dt^2 sum_k ((i-k)+1/2) MAX_input(k, c)
     L.cost = o; o += (int)(sizeof(DevCost) / 8);   // structure of QQ (handles created from the cost weights)
@@ -435,7 +468,7 @@ __host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int
     L.rho = o; o += QB;
     L.lam = o; o += QB;
     L.prow = o; o += QB;
-    L.slot = o; o += (nobs * H + 4 * HN + 3) / 4;   // constraint -> slot + 1 (0: inactive), ushort; reset at every QP setup
+    L.slot = o; o += (nobs * H + (lim ? 6 : 4) * HN + 3) / 4;   // constraint -> slot + 1 (0: inactive), ushort; reset at every QP setup
     L.ptail = o;                           // (tail columns of P live in global scratch)
     o = (o + 1) & ~1;
     L.y = o;
@@ -445,10 +478,11 @@ __host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int
 
 // ------------------------------------------------------------------------------------------------
 // IDENT: the QP Hessian is the identity (PSGCFS projection); JAC: analytic Jacobian (CFS_JAC_ANALYTIC handles); MOVE: obstacles
-// per waypoint (CFS_OBS_PER_WAYPOINT handles: P.obs is B x H x nobs x 6, no mesh obstacles).
+// per waypoint (CFS_OBS_PER_WAYPOINT handles: P.obs is B x H x nobs x 6, no mesh obstacles); LIM: joint position rows (handles
+// with joint limits: P.lim is [lim; lo; hi], 3 NJ).  Every LIM site is an `if constexpr` of its own.
 // Soft: empty for STOP handles, whose kernarg segment is FusedParams alone; SoftParams for CFS_INFEAS_SOFTEN handles (SOFT: the
 // soft-constraint QP after a proven-infeasible one, its parameters as a second block).
-template <int NJ, int QB, bool IDENT, bool JAC, bool MOVE, class... Soft>
+template <int NJ, int QB, bool IDENT, bool JAC, bool MOVE, bool LIM, class... Soft>
 __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(FusedParams P, Soft... soft_params)
 {
     constexpr bool SOFT = sizeof...(Soft) > 0;
@@ -460,7 +494,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
     const int H = P.H, nobs = P.nobs, HN = H * NJ, nn = HN, NX = H * NS;
     const double dt = P.dt;
     constexpr int PR = QB < CFS_PR ? QB : CFS_PR;   // register-resident columns of each P row (rest: global scratch)
-    const FusedLayout L = fused_layout(NJ, H, nobs, QB, PR);
+    const FusedLayout L = fused_layout(NJ, H, nobs, QB, PR, LIM);
     DevRobot *rb = reinterpret_cast<DevRobot *>(lds + L.rb);
     double *s_ob = lds + L.ob, *s_x = lds + L.x, *s_u = lds + L.u, *s_qu = lds + L.qu, *s_g = lds + L.g;
     double *s_rhs = lds + L.rhs, *xs = lds + L.xs, *s_up = lds + L.up, *wb = lds + L.wb, *zb = lds + L.zb;
@@ -475,6 +509,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
     int red_sel = 0;
 #define red (red_base + 24 * (red_sel ^= 1))      /* every use is one block-wide reduction: alternate the buffer */
     double *s_lim = lds + L.small, *s_v0 = s_lim + NJ, *s_th0 = s_v0 + NJ, *s_margin = s_th0 + 2 * NJ;
+    double *s_plim = s_margin + nobs;               // LIM: [lo; hi] of the joint positions (2 NJ)
     double *s_mx = lds + L.mx;
     double *s_racc = lds + L.racc;
     // Spill space (columns [PR,QB) of P as [b-PR][a], rows of Y beyond the LDS capacity) comes from a POOL of P.pool_n slots, one per
@@ -513,9 +548,13 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
         __syncthreads();                                   // every thread is done with the slot
         if (tid == 0) { __threadfence(); atomicExch(&P.pool_flag[pool_slot * 16], 0); }
     };
-    const int ncon = nobs * H + (P.has_bounds ? 4 : 2) * HN;
+    int ncon = nobs * H + (P.has_bounds ? 4 : 2) * HN;
+    if constexpr (LIM) ncon = nobs * H + 6 * HN;     // [collision | vel+ | vel- | bound+ | bound- | pos+ | pos-]
     const int maxit = 8 * nn + 200;                  // the oracle's longest certificates take ~2 nn steps
     // constraint codes never change: decoded once into LDS (no integer divisions in the step loop)
+    if constexpr (LIM) {                              // (only the collision rows' codes are read back: the layout has no others)
+        for (int e = tid; e < nobs * H; e += FT) { const int j = e / H; s_code[e] = mk_code(CT_COL, e - j * H, j); }
+    } else
     for (int e = tid; e < ncon; e += FT) {
         int code;
         if (e < nobs * H) { const int j = e / H; code = mk_code(CT_COL, e - j * H, j); }
@@ -540,6 +579,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
             s_th0[tid] = P.xR1[(size_t)b * NS + tid];
         }
         if (tid < nobs) s_margin[tid] = P.margin[tid];
+        if constexpr (LIM)
+            if (tid < 2 * NJ) s_plim[tid] = P.lim[NJ + tid];
         if (P.cost) {
             const double *csrc = reinterpret_cast<const double *>(P.cost);
             for (int e = tid; e < (int)(sizeof(DevCost) / 8); e += FT) lds[L.cost + e] = csrc[e];
@@ -863,6 +904,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     }
                     if (sp_) Rv -= dt * coef[sp_ - 1];
                     if (sm_) Rv += dt * coef[sm_ - 1];
+                    if constexpr (LIM) {                                // position rows: gradient -+e_c in position space
+                        const int pp_ = s_slot[nobs * H + 4 * HN + iR * NJ + c], pm_ = s_slot[nobs * H + 5 * HN + iR * NJ + c];
+                        if (pp_) Rp -= coef[pp_ - 1];
+                        if (pm_) Rp += coef[pm_ - 1];
+                    }
                 }
                 // (N coef)[k] = sum_{i>=k} (((i-k)+1/2) dt^2 Rp[i] + Rv[i]) = dt^2 (S2 - S1/2) + V1 with S1 = suffix(Rp), S2 = suffix(S1),
                 // V1 = suffix(Rv): two scans, the second one carries dt^2 S1 + Rv
@@ -877,6 +923,9 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     if (base) z0 = base[lane * NJ + c];
                     else if (ptype_ == CT_COL) z0 = lane <= pi_ ? s_g[(pj_ * H + pi_) * NJ + c] * ((dt * dt) * ((double)(pi_ - lane) + 0.5)) : 0.0;
                     else z0 = (c == pj_ && lane <= pi_) ? (ptype_ == CT_VELP ? -dt : dt) : 0.0;
+                    if constexpr (LIM)
+                        if (!base && ptype_ >= CT_POSP)
+                            z0 = (c == pj_ && lane <= pi_) ? (ptype_ == CT_POSP ? -1.0 : 1.0) * ((dt * dt) * ((double)(pi_ - lane) + 0.5)) : 0.0;
                     z0 -= nr;
                 }
                 const double sv = dt * (two ? half_scan_incl(z0) : wave_scan_incl(z0));
@@ -939,6 +988,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
             const int ptype_ = code >> 16, pi_ = (code >> 8) & 0xff, pj_ = code & 0xff;
             for (int k = tid; k < HN; k += FT) {
                 double w0;
+                if constexpr (LIM)
+                    if (ptype_ >= CT_POSP) {                // -+ column (i, c) of H^{-1} Bpos'
+                        wb[k] = (ptype_ == CT_POSP ? -1.0 : 1.0) * P.M1[(size_t)(pi_ * NJ + pj_) * nn + k];
+                        continue;
+                    }
                 if (ptype_ == CT_COL) {
                     w0 = 0.0;
 #pragma unroll
@@ -1116,9 +1170,9 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         const int c = s_prev[s1];
                         if (c < 0) continue;
                         const int mine = tid < q ? s_act[tid] : -1;
-                        const double dv = mine >= 0 ? (IDENT ? gram_ident<NJ>(mine, c, s_g, H, dt) : ndot<NJ>(mine, wb, s_g, H)) : 0.0;
+                        const double dv = mine >= 0 ? (IDENT ? gram_ident<NJ, LIM>(mine, c, s_g, H, dt) : ndot<NJ, LIM>(mine, wb, s_g, H)) : 0.0;
                         s_d[tid] = dv;
-                        const double spp_ = IDENT ? gram_ident<NJ>(c, c, s_g, H, dt) : ndot<NJ>(c, wb, s_g, H);
+                        const double spp_ = IDENT ? gram_ident<NJ, LIM>(c, c, s_g, H, dt) : ndot<NJ, LIM>(c, wb, s_g, H);
                         if (!IDENT && tid == 0) pub[0] = 0;
                         sync_rows(true);
                         const double rv = mine >= 0 ? Pr.dot(s_d, s_pt, tid, q) : 0.0;
@@ -1157,7 +1211,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     for (int round = 0;; ++round) {
                         const int mine = tid < q ? s_act[tid] : -1;
                         double bb;
-                        s0v = mine >= 0 ? slack_of<NJ>(mine, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb) : 0.0;
+                        s0v = mine >= 0 ? slack_of<NJ, LIM>(mine, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb, dt, s_plim) : 0.0;
                         s_d[tid] = s0v;
                         sync_rows(true);
                         lamv = mine >= 0 ? -Pr.dot(s_d, s_pt, tid, q) : 0.0;
@@ -1243,6 +1297,13 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         if (!s_flag[nobs * H + 2 * HN + k] && s1 < -1e-11 * (1.0 + fabs(bb)) && s1 < sbest) { sbest = s1; cbest = mk_code(CT_BNDP, i, c); }
                         if (!s_flag[nobs * H + 3 * HN + k] && s2 < -1e-11 * (1.0 + fabs(bb)) && s2 < sbest) { sbest = s2; cbest = mk_code(CT_BNDM, i, c); }
                     }
+                    if constexpr (LIM) {                        // position rows: hard in the soft QP too; infinite bounds never violated
+                        const double pos = s_th0[c] + ((double)(i + 1) * dt) * s_v0[c], y = xs[2 * HN + k];
+                        const double bp = s_plim[NJ + c] - pos, bq = pos - s_plim[c];
+                        const double s1 = bp - y, s2 = bq + y;
+                        if (!s_flag[nobs * H + 4 * HN + k] && s1 < -1e-11 * (1.0 + fabs(bp)) && s1 < sbest) { sbest = s1; cbest = mk_code(CT_POSP, i, c); }
+                        if (!s_flag[nobs * H + 5 * HN + k] && s2 < -1e-11 * (1.0 + fabs(bq)) && s2 < sbest) { sbest = s2; cbest = mk_code(CT_POSM, i, c); }
+                    }
                 }
                 block_argmin(sbest, cbest, red, tid);
                 STAMP(2);                                   // 2: step 1 (slack scan + argmin)
@@ -1260,7 +1321,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         const int ac = s_act[tid];
                         double sa = 0.0, bb = 0.0;
                         if (ac >= 0) {
-                            sa = slack_of<NJ>(ac, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb);
+                            sa = slack_of<NJ, LIM>(ac, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb, dt, s_plim);
                             if (SOFT && soft && (ac >> 16) == CT_COL) sa += iw * s_lam[tid];   // soft collision row: its slack includes s = lambda / mu
                             drift = fabs(sa) / (1.0 + fabs(bb));
                         }
@@ -1284,8 +1345,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     const int myact = tid < qhi ? s_act[tid] : -1;
                     if (!polish && IDENT) {
                         // H = I: w = n_p; d = N'n_p and n_p'n_p straight from the closed form (exactly symmetric products)
-                        spp = gram_ident<NJ>(pc, pc, s_g, H, dt);
-                        if (tid < qhi) s_d[tid] = myact >= 0 ? gram_ident<NJ>(myact, pc, s_g, H, dt) : 0.0;
+                        spp = gram_ident<NJ, LIM>(pc, pc, s_g, H, dt);
+                        if (tid < qhi) s_d[tid] = myact >= 0 ? gram_ident<NJ, LIM>(myact, pc, s_g, H, dt) : 0.0;
                         sync_rows(qhi <= 64);
                         if (tid < qhi) s_r[tid] = myact >= 0 ? Pr.dot(s_d, s_pt, tid, qhi) : 0.0;
                         __syncthreads();
@@ -1299,8 +1360,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     have_w = true;
                     }
                     STAMP(3);                               // 3: w gather + rollout
-                    spp = ndot<NJ>(pc, wb, s_g, H);
-                    if (tid < qhi) s_d[tid] = myact >= 0 ? ndot<NJ>(myact, wb, s_g, H) : 0.0;
+                    spp = ndot<NJ, LIM>(pc, wb, s_g, H);
+                    if (tid < qhi) s_d[tid] = myact >= 0 ? ndot<NJ, LIM>(myact, wb, s_g, H) : 0.0;
                     sync_rows(qhi <= 64);
                     // r = P d
                     if (tid < qhi) s_r[tid] = myact >= 0 ? Pr.dot(s_d, s_pt, tid, qhi) : 0.0;
@@ -1327,14 +1388,14 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         __syncthreads();
                         }
                         if (polish) break;                             // zb = (x, Bvel x, Bpos x) after the projection
-                        delta = ndot<NJ>(pc, zb, s_g, H);              // n_p'z
+                        delta = ndot<NJ, LIM>(pc, zb, s_g, H);              // n_p'z
                         if (SOFT && soft && ptype == CT_COL) delta = fmax(delta, 0.0) + iw;   // + e_p's-part of z; >= 1/mu exactly (Schur complement)
                         if (qhi == nfree) break;                       // empty active set: nothing to refine, t1 = inf
                         // one exchange carries the refinement diagnostics (r'rho, max|rho|, max|d|; rho_a = n_a'z is
                         // zero in exact arithmetic) and the dual step length t1 = min{lambda_a / r_a : r_a > 0}
                         double rr = 0.0, rmax = 0.0, dmax = 0.0, t1c = INFINITY;
                         if (tid < qhi && myact >= 0) {
-                            const double ra = (SOFT && soft && (myact >> 16) == CT_COL) ? ndot<NJ>(myact, zb, s_g, H) - iw * s_r[tid] : ndot<NJ>(myact, zb, s_g, H), rv = s_r[tid];
+                            const double ra = (SOFT && soft && (myact >> 16) == CT_COL) ? ndot<NJ, LIM>(myact, zb, s_g, H) - iw * s_r[tid] : ndot<NJ, LIM>(myact, zb, s_g, H), rv = s_r[tid];
                             s_prow[tid] = ra;
                             rr = rv * ra;
                             rmax = fabs(ra);
@@ -1452,7 +1513,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         __syncthreads();
                         STAMP(8);                           // 8: drop
                     }
-                    { double bb; sp = slack_of<NJ>(pc, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb); }
+                    { double bb; sp = slack_of<NJ, LIM>(pc, xs, s_g, s_rhs, s_lim, s_v0, s_mx, H, &bb, dt, s_plim); }
                     if (SOFT && soft && ptype == CT_COL) sp += iw * lam_p;   // the entering row's own slack s_p = lambda_p / mu
                 }
                 if (qp_status != QP_OK) break;
@@ -1477,7 +1538,8 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
         if (!skip) prev_q = qp_status == QP_OK ? qhi : 0;
         if (SOFT && soft) prev_q = 0;                       // the next hard QP starts cold
         if (P.dump_lambda) {
-            const int nlam = nobs * H + 4 * HN;
+            int nlam = nobs * H + 4 * HN;
+            if constexpr (LIM) nlam = nobs * H + 6 * HN;     // ... | pos+ | pos-
             __syncthreads();
             for (int e = tid; e < nlam; e += FT) P.dump_lambda[(size_t)b * nlam + e] = 0.0;
             __syncthreads();
@@ -1622,13 +1684,13 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
 
 #undef red
 
-template <int NJ, int QB, bool IDENT, bool JAC, bool SOFT, bool MOVE>
+template <int NJ, int QB, bool IDENT, bool JAC, bool SOFT, bool MOVE, bool LIM>
 hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s, const SoftParams *sp)
 {
     // the function attribute is per device (handles may live on several GPUs of one process: cfs_set_device)
     static std::atomic<unsigned long long> attr_set{0ull};
     using Kernel = std::conditional_t<SOFT, void (*)(FusedParams, SoftParams), void (*)(FusedParams)>;
-    const Kernel kern = cfs_solve_fused_kernel<NJ, QB, IDENT, JAC, MOVE>;    // the pointer type fixes the parameter pack
+    const Kernel kern = cfs_solve_fused_kernel<NJ, QB, IDENT, JAC, MOVE, LIM>;    // the pointer type fixes the parameter pack
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -1646,33 +1708,34 @@ hipError_t launch_fused_inst2(const FusedParams &p, size_t lds, hipStream_t s, c
 #ifndef CFS_IDENT_SET
 #define CFS_IDENT_SET 2
 #endif
-template <int NJ, int QB, bool JAC, bool SOFT, bool MOVE>
+template <int NJ, int QB, bool JAC, bool SOFT, bool MOVE, bool LIM>
 hipError_t launch_fused_inst(const FusedParams &p, size_t lds, hipStream_t s, const SoftParams *sp)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
 #if CFS_IDENT_SET != 0
-    if (ident) return launch_fused_inst2<NJ, QB, true, JAC, SOFT, MOVE>(p, lds, s, sp);
+    if (ident) return launch_fused_inst2<NJ, QB, true, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
 #endif
 #if CFS_IDENT_SET != 1
-    if (!ident) return launch_fused_inst2<NJ, QB, false, JAC, SOFT, MOVE>(p, lds, s, sp);
+    if (!ident) return launch_fused_inst2<NJ, QB, false, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
 #endif
     return hipErrorInvalidValue;
 }
 
 // The LDS plan of a problem shape on this tier, read by both fused_fits_tier and launch_fused_tier: active-set capacity QB, layout,
 // doubles a workgroup may use (small safety margin), linearisation scratch per waypoint of a tile (sin/cos, link end points, base
-// distances, minima per evaluation point, candidate lists as ushort; move: the waypoint's obstacle rows as well)
+// distances, minima per evaluation point, candidate lists as ushort; move: the waypoint's obstacle rows as well; lim: the layout of
+// the LIM kernels)
 struct FusedPlan {
     int nn, QB;
     FusedLayout L;
     size_t avail, per_wp;
 };
-FusedPlan fused_plan(int nj, int H, int nobs, bool move)
+FusedPlan fused_plan(int nj, int H, int nobs, bool move, bool lim = false)
 {
     FusedPlan q;
     q.nn = H * nj;
     q.QB = q.nn <= 96 ? 96 : (q.nn <= 160 ? 160 : 256);
-    q.L = fused_layout(nj, H, nobs, q.QB, q.QB < CFS_PR ? q.QB : CFS_PR);
+    q.L = fused_layout(nj, H, nobs, q.QB, q.QB < CFS_PR ? q.QB : CFS_PR, lim);
     q.avail = (160 * 1024 / CFS_WG_PER_CU) / 8 - 64;
     q.per_wp = (size_t)nj * 6 + (size_t)nvt(nj) * 6 + (size_t)nj * nobs + (size_t)nobs * (2 * nj + 1) + ((size_t)nj * nobs + 3) / 4;
     if (move) q.per_wp += (size_t)nobs * 6;
@@ -1683,14 +1746,14 @@ FusedPlan fused_plan(int nj, int H, int nobs, bool move)
 
 // does the fused kernel's fixed LDS footprint (+ a minimal Y / linearisation region) fit a CU?
 template <FusedTier T>
-bool fused_fits_tier(int nj, int H, int nobs, bool move)
+bool fused_fits_tier(int nj, int H, int nobs, bool move, bool lim)
 {
-    const FusedPlan q = fused_plan(nj, H, nobs, move);
+    const FusedPlan q = fused_plan(nj, H, nobs, move, lim);
     return (size_t)q.L.total_fixed + (size_t)4 * q.nn <= q.avail && (size_t)q.L.lin + q.per_wp <= q.avail;
 }
 
 // host: choose the capacities, fill qy / lin_w, launch
-template <FusedTier T, bool JAC, bool SOFT, bool MOVE>
+template <FusedTier T, bool JAC, bool SOFT, bool MOVE, bool LIM>
 hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftParams *sp)
 {
     if (MOVE && p.nmesh > 0) return hipErrorInvalidValue;   // per-waypoint rows are line obstacles only
@@ -1707,30 +1770,37 @@ hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftPar
     w = (p.H + (p.H + w - 1) / w - 1) / ((p.H + w - 1) / w);   // equal tiles: ceil(H / number of tiles)
     p.qy = qy;
     p.lin_w = w;
-    const size_t need = std::max((size_t)L.total_fixed + (size_t)qy * nn, (size_t)L.lin + (size_t)w * q.per_wp);
+    size_t need = std::max((size_t)L.total_fixed + (size_t)qy * nn, (size_t)L.lin + (size_t)w * q.per_wp);
+    if constexpr (LIM) {
+        // the LIM layout, with the Y rows in LDS and the tile width of the plan without limits: the same split of Y between LDS and
+        // global memory, hence the same summation order in y_combine (the LIM footprint is never larger, fused_layout)
+        const FusedPlan ql = fused_plan(nj, p.H, p.nobs, MOVE, true);
+        need = std::max((size_t)ql.L.total_fixed + (size_t)qy * nn, (size_t)ql.L.lin + (size_t)w * ql.per_wp);
+        if (need > ql.avail) return hipErrorInvalidValue;
+    }
     const size_t lds = need * 8;
     switch (nj * 1000 + q.QB) {
-    case 2096: return launch_fused_inst<2, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 3096: return launch_fused_inst<3, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 4096: return launch_fused_inst<4, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 5096: return launch_fused_inst<5, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 6096: return launch_fused_inst<6, 96, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 2160: return launch_fused_inst<2, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 4160: return launch_fused_inst<4, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 5160: return launch_fused_inst<5, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 6160: return launch_fused_inst<6, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 3160: return launch_fused_inst<3, 160, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 3256: return launch_fused_inst<3, 256, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 4256: return launch_fused_inst<4, 256, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 5256: return launch_fused_inst<5, 256, JAC, SOFT, MOVE>(p, lds, s, sp);
-    case 6256: return launch_fused_inst<6, 256, JAC, SOFT, MOVE>(p, lds, s, sp);
+    case 2096: return launch_fused_inst<2, 96, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 3096: return launch_fused_inst<3, 96, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 4096: return launch_fused_inst<4, 96, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 5096: return launch_fused_inst<5, 96, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 6096: return launch_fused_inst<6, 96, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 2160: return launch_fused_inst<2, 160, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 4160: return launch_fused_inst<4, 160, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 5160: return launch_fused_inst<5, 160, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 6160: return launch_fused_inst<6, 160, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 3160: return launch_fused_inst<3, 160, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 3256: return launch_fused_inst<3, 256, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 4256: return launch_fused_inst<4, 256, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 5256: return launch_fused_inst<5, 256, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
+    case 6256: return launch_fused_inst<6, 256, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
     default: return hipErrorInvalidValue;
     }
 }
 
-// The one place CFS_TIER, CFS_JAC, CFS_SOFT and CFS_MOVE are read (Makefile: one object per tier and variant): this object's
-// launcher, and, in the tier's default object only, its capacity test.
-template hipError_t launch_fused_tier<CFS_TIER, CFS_JAC, CFS_SOFT, CFS_MOVE>(int, FusedParams, hipStream_t, const SoftParams *);
-#if !CFS_JAC && !CFS_SOFT && !CFS_MOVE
-template bool fused_fits_tier<CFS_TIER>(int, int, int, bool);
+// The one place CFS_TIER, CFS_JAC, CFS_SOFT, CFS_MOVE and CFS_LIM are read (Makefile: one object per tier and variant): this
+// object's launcher, and, in the tier's default object only, its capacity test.
+template hipError_t launch_fused_tier<CFS_TIER, CFS_JAC, CFS_SOFT, CFS_MOVE, CFS_LIM>(int, FusedParams, hipStream_t, const SoftParams *);
+#if !CFS_JAC && !CFS_SOFT && !CFS_MOVE && !CFS_LIM
+template bool fused_fits_tier<CFS_TIER>(int, int, int, bool, bool);
 #endif

@@ -151,17 +151,18 @@ __global__ __launch_bounds__(256) void cfs_order_rank_kernel(OrderParams P)
 }
 
 // dense self.Ainq / self.binq in the reference's row order (CFS_FANUC.m:119-129), HBM-bound writer:
-// one workgroup per (problem, column), threads along the contiguous row index.
+// one workgroup per (problem, column), threads along the contiguous row index.  With joint limits (plim) the position rows follow:
+// +Bpos row (i, c) <= hi_c - theta0_c - (i+1) dt v0_c, then -Bpos row (i, c) <= theta0_c + (i+1) dt v0_c - lo_c.
 __global__ __launch_bounds__(256) void cfs_dense_con_kernel(DenseConParams P)
 {
     const int nj = P.nj, H = P.H, nn = H * nj, ns = 2 * nj;
-    const int per = 1 + 2 * nj, rows = P.nobs * H * per;
+    const int per = 1 + 2 * nj, rref = P.nobs * H * per, rows = rref + (P.plim ? 2 * nn : 0);
     const int b = blockIdx.y, col = blockIdx.x;           // col = k*nj + cc
     const int k = col / nj, cc = col % nj;
     const double dt = P.dt;
     double *A = P.Ainq + ((size_t)b * rows * nn) + (size_t)col * rows;
     const double *g = P.grad + (size_t)b * P.nobs * H * nj;
-    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
+    for (int r = threadIdx.x; r < rref; r += blockDim.x) {
         const int blk = r / per, t = r % per, j = blk / H, i = blk % H;
         double v = 0.0;
         if (k <= i) {
@@ -172,10 +173,22 @@ __global__ __launch_bounds__(256) void cfs_dense_con_kernel(DenseConParams P)
         if (v == 0.0) v = 0.0;                             // no negative zeros in the dense output
         A[r] = v;
     }
+    for (int r = rref + threadIdx.x; r < rows; r += blockDim.x) {   // position rows
+        const int q = r - rref, kk = q % nn, i = kk / nj, c = kk % nj;
+        double v = (c == cc && k <= i) ? ((double)(i - k) + 0.5) * dt * dt : 0.0;
+        if (q >= nn) v = -v;
+        if (v == 0.0) v = 0.0;
+        A[r] = v;
+    }
     if (col == 0) {
         const double *u = P.u + (size_t)b * nn;
         const double *x1 = P.xR1 + (size_t)b * ns;
-        for (int r = threadIdx.x; r < rows; r += blockDim.x) {
+        for (int r = rref + threadIdx.x; r < rows; r += blockDim.x) {
+            const int q = r - rref, kk = q % nn, i = kk / nj, c = kk % nj;
+            const double pos = x1[c] + ((double)(i + 1) * dt) * x1[nj + c];   // x_ of waypoint i without Bpos u
+            P.binq[(size_t)b * rows + r] = q < nn ? P.plim[nj + c] - pos : pos - P.plim[c];
+        }
+        for (int r = threadIdx.x; r < rref; r += blockDim.x) {
             const int blk = r / per, t = r % per, j = blk / H, i = blk % H;
             double s;
             if (t == 0) {

@@ -24,7 +24,8 @@ import numpy as np
 
 from . import _lib
 from .rrt import RRT_FANUC
-from .solvers import CFSBatch, _infeasible_args, _jacobian_code, _ptr, obs_to_array
+from .robotproperty2 import robotproperty2
+from .solvers import CFSBatch, _infeasible_args, _jacobian_code, _joint_limits_array, _ptr, obs_to_array
 from .sysinfo import RRTstar_CFS_problem
 
 try:
@@ -65,10 +66,12 @@ class RRTCFSPlanner:
     status 0/1 by lowest final cost, else status 4 by lowest final violation then cost).  select="shortest": the reference's
     rule -- the route with the fewest nodes, first seed on ties (s_Parallel_rrt.m:27-28) -- then one CFS per slot.
     The cost family is RRTstar_CFS.m:124-187's (sysinfo.RRTstar_CFS_problem: M200i, H = 40); the obstacles are `pobs`, with
-    margins obs{j}.epsilon (CFS) or obs{j}.D (PSGCFS).  Arguments are validated before anything touches the device."""
+    margins obs{j}.epsilon (CFS) or obs{j}.D (PSGCFS).  joint_limits: None | "robot" | a (5, 2) array of [lo, hi], the smoothing
+    QPs' position rows (CFSBatch; the RRT samples ignore them).  Arguments are validated before anything touches the device."""
 
     def __init__(self, pobs, sys_rrt, region_g, region_s, sample_off, ROBOT="M200i", rrt_solver="RRT", num_seed=6, mode="CFS",
-                 select="best", on_infeasible="stop", soft_weight=None, jacobian="fd_literal", max_slots=256, device=None):
+                 select="best", on_infeasible="stop", soft_weight=None, jacobian="fd_literal", max_slots=256, device=None,
+                 joint_limits=None):
         if select not in SELECT:
             raise ValueError(f"select must be one of {SELECT}, not {select!r}")
         if not _is_int(num_seed) or not 1 <= num_seed <= MAX_SEEDS:
@@ -85,6 +88,7 @@ class RRTCFSPlanner:
             raise ValueError("sys_rrt.nstate must be 5 (the M200i's joints)")
         _jacobian_code(jacobian)
         _infeasible_args(on_infeasible, soft_weight)
+        _joint_limits_array(joint_limits, robotproperty2("M200i"), 5)
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch is not None and torch.cuda.is_available() else torch.device("cuda", 0)
         elif _is_int(device):
@@ -102,7 +106,7 @@ class RRTCFSPlanner:
         _, self.sys_cfs, _ = RRTstar_CFS_problem(np.stack([np.asarray(sys_rrt.x0, float), np.asarray(sys_rrt.goal_th, float)], axis=1))
         margin = [o["epsilon"] if mode == "CFS" else o["D"] for o in pobs]
         self.cfs = CFSBatch(self.sys_cfs, len(pobs), margin, mode=mode, max_batch=self.max_slots * self.K, device=device.index,
-                            jacobian=jacobian, on_infeasible=on_infeasible, soft_weight=soft_weight)
+                            jacobian=jacobian, on_infeasible=on_infeasible, soft_weight=soft_weight, joint_limits=joint_limits)
         one = torch.tensor(obs_to_array(pobs), dtype=torch.float64, device=device)
         self._obs = one.unsqueeze(0).expand(self.max_slots * self.K, -1, -1).contiguous()
 

@@ -84,6 +84,31 @@ def _motion_code(obstacles):
     return _lib.OBSTACLES[obstacles]
 
 
+def _joint_limits_array(joint_limits, robot, nj):
+    """None | (nj, 2) float64 [lo, hi] from CFSBatch's joint_limits=: None (no position rows), "robot" (robot.thetamax[:nj]) or an
+    (nj, 2) array.  ValueError for anything malformed (wrong shape, NaN, lo >= hi), before the device is touched."""
+    if joint_limits is None:
+        return None
+    if isinstance(joint_limits, str):
+        if joint_limits != "robot":
+            raise ValueError(f'joint_limits must be None, "robot" or an (njoint, 2) array, not {joint_limits!r}')
+        tm = getattr(robot, "thetamax", None)
+        if tm is None:
+            raise ValueError('joint_limits="robot" needs sys_info.robot.thetamax')
+        joint_limits = np.asarray(tm, dtype=np.float64)[:nj]
+    try:
+        a = np.array(joint_limits, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"joint_limits must be an (njoint, 2) array of [lo, hi], not {joint_limits!r}") from None
+    if a.shape != (nj, 2):
+        raise ValueError(f"joint_limits has shape {a.shape}: it must be (njoint, 2) = {(nj, 2)}")
+    if np.isnan(a).any():
+        raise ValueError("joint_limits holds NaN")
+    if not (a[:, 0] < a[:, 1]).all():
+        raise ValueError(f"joint_limits needs lo < hi on every joint: {a.tolist()}")
+    return np.ascontiguousarray(a)
+
+
 def _infeasible_args(on_infeasible, soft_weight):
     """(policy code, weight) for cfs_problem_set_infeasible_policy; ValueError for anything malformed.  "soften" needs a finite
     soft_weight > 0; "stop" ignores a (valid) weight and passes 1.0 when there is none."""
@@ -106,8 +131,11 @@ class CFSBatch:
     solving batches of problems that differ in start/goal (x_init, xR1, ff, caug), obstacles and noise."""
 
     def __init__(self, sys_info, nobs, margin, mode="CFS", max_batch=1, device=None, check_dynamics=True, use_weights="auto",
-                 jacobian="fd_literal", on_infeasible="stop", soft_weight=None, obstacles="static"):
-        """obstacles: "static" (the default: obs arrays are (B, nobs, 6)) | "per_waypoint" (obs arrays of solve, solve_device,
+                 jacobian="fd_literal", on_infeasible="stop", soft_weight=None, obstacles="static", joint_limits=None):
+        """joint_limits: None (the default: no position rows) | "robot" (sys_info.robot.thetamax[:njoint]) | an (njoint, 2) array of
+        [lo, hi] in rad, either side possibly infinite: every QP keeps each waypoint's x_ inside (include/cfs_hip.h,
+        cfs_problem_set_joint_limits); get_con then has 2*H*njoint more rows and qp's lambda 2*nn more entries.
+        obstacles: "static" (the default: obs arrays are (B, nobs, 6)) | "per_waypoint" (obs arrays of solve, solve_device,
         linearize and get_con are (B, H, nobs, 6), row [b, i, j] = obstacle j at waypoint i+1; no meshes, no chomp;
         include/cfs_hip.h, cfs_problem_set_obstacle_motion).
         on_infeasible: "stop" (the default: a proven-infeasible linearised QP ends the problem with QP_INFEASIBLE) | "soften"
@@ -124,6 +152,7 @@ class CFSBatch:
         _jacobian_code(jacobian)                         # validated before anything touches the device
         _infeasible_args(on_infeasible, soft_weight)
         _motion_code(obstacles)
+        jl = _joint_limits_array(joint_limits, s.robot, int(s.njoint))
         self.mode = mode
         self.H, self.nj = int(s.H), int(s.njoint)
         self.ns, self.nn, self.nx = 2 * self.nj, self.H * self.nj, self.H * 2 * self.nj
@@ -178,7 +207,8 @@ class CFSBatch:
                 self.close()
                 CFSBatch.__init__(self, sys_info, nobs, margin, mode=mode, max_batch=max_batch, device=device,
                                   check_dynamics=check_dynamics_asked, use_weights=False, jacobian=jacobian,
-                                  on_infeasible=on_infeasible, soft_weight=soft_weight, obstacles=obstacles)
+                                  on_infeasible=on_infeasible, soft_weight=soft_weight, obstacles=obstacles,
+                                  joint_limits=joint_limits)
                 return
         else:
             _lib.check(lib.cfs_problem_create(C.byref(d), C.byref(h)))
@@ -189,6 +219,25 @@ class CFSBatch:
             self.set_infeasible_policy(on_infeasible, soft_weight)
         if obstacles != "static":
             self.set_obstacle_motion(obstacles)
+        if jl is not None:
+            self.set_joint_limits(jl)
+
+    def set_joint_limits(self, joint_limits):
+        """joint position limits of the following solves and pieces: None (clear) | "robot" | an (njoint, 2) array of [lo, hi]
+        (cfs_problem_set_joint_limits)."""
+        jl = _joint_limits_array(joint_limits, self.robot, self.nj)
+        if jl is None:
+            _lib.check(self._lib.cfs_problem_set_joint_limits(self._h, None, None))
+        else:
+            lo, hi = np.ascontiguousarray(jl[:, 0]), np.ascontiguousarray(jl[:, 1])
+            _lib.check(self._lib.cfs_problem_set_joint_limits(self._h, _ptr(lo), _ptr(hi)))
+        self.rows = self.nobs * self.H * (1 + 2 * self.nj) + (0 if jl is None else 2 * self.nn)
+
+    def joint_limits(self):
+        """(njoint, 2) array of [lo, hi] as set, or None without limits (cfs_problem_get_joint_limits)."""
+        on, lo, hi = C.c_int(0), np.zeros(self.nj), np.zeros(self.nj)
+        _lib.check(self._lib.cfs_problem_get_joint_limits(self._h, C.byref(on), _ptr(lo), _ptr(hi)))
+        return np.stack([lo, hi], axis=1) if on.value else None
 
     def set_obstacle_motion(self, obstacles):
         """obstacles of the following solves and pieces: "static" | "per_waypoint" (cfs_problem_set_obstacle_motion)."""
@@ -515,7 +564,8 @@ class CFSBatch:
         lin, u_lin, xR1, dist, grad = _f64(lin), _f64(u_lin), _f64(xR1), _f64(dist), _f64(grad)
         B = lin.shape[0]
         u = np.zeros((B, self.nn))
-        lam = np.zeros((B, self.nobs * self.H + 4 * self.nn)) if want_lambda else None
+        nlam = self.nobs * self.H + (4 if self.joint_limits() is None else 6) * self.nn
+        lam = np.zeros((B, nlam)) if want_lambda else None
         it, st = np.zeros(B, np.int32), np.zeros(B, np.int32)
         _lib.check(self._lib.cfs_qp(self._h, B, _ptr(lin), _ptr(u_lin), _ptr(xR1), _ptr(dist), _ptr(grad), _ptr(u),
                                     _ptr(lam), _ptr(it), _ptr(st)))
@@ -603,13 +653,16 @@ class _SolverBase:
     MODE = "CFS"
     MARGIN_KEY = "epsilon"
 
-    def __init__(self, obs, sys_info, ROBOT="M16iB", device=None, jacobian="fd_literal", on_infeasible="stop", soft_weight=None):
+    def __init__(self, obs, sys_info, ROBOT="M16iB", device=None, jacobian="fd_literal", on_infeasible="stop", soft_weight=None,
+                 joint_limits=None):
         """jacobian: "fd_literal" (num_jac.m, the default) | "analytic" (CFSBatch).
+        joint_limits: None (the default) | "robot" | an (njoint, 2) array of [lo, hi] (CFSBatch); get_con then has the position rows.
         on_infeasible: "stop" (the default) | "soften" with soft_weight= (CFSBatch); after optimizer(), viol_all and n_soft.
         obs{j}["l"] may be 3x2xH (shape (3, 2, H): the obstacle's axis at waypoints 1..H); any such entry makes the handle
         per-waypoint, and the 3x2 entries are then held over the horizon (obs_traj_to_array)."""
         _jacobian_code(jacobian)
         _infeasible_args(on_infeasible, soft_weight)
+        _joint_limits_array(joint_limits, sys_info.robot, int(sys_info.njoint))
         if on_infeasible == "soften" and obs_meshes(obs):
             raise ValueError('on_infeasible="soften" does not support mesh obstacles')
         self._moving = obs_moving(obs)
@@ -628,7 +681,7 @@ class _SolverBase:
         self.iter_O, self.total_iter, self.status = 1, 0, None
         self._batch = CFSBatch(sys_info, len(obs), [o[self.MARGIN_KEY] for o in obs], mode=self.MODE, max_batch=1,
                                device=device, jacobian=jacobian, on_infeasible=on_infeasible, soft_weight=soft_weight,
-                               obstacles="per_waypoint" if self._moving else "static")
+                               obstacles="per_waypoint" if self._moving else "static", joint_limits=joint_limits)
         self.viol_all, self.n_soft = np.zeros(0), 0
         meshes = obs_meshes(obs)
         if meshes:

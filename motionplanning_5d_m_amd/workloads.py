@@ -20,6 +20,12 @@ Random draws, in this order, from ``numpy.random.default_rng(seed)``:
   waypoint i (time i*delta_t, i = 1..H) its axis is the config-3 axis shifted by speed*i*delta_t*(cos, sin, 0);
   the rejection test measures the start pose against the candidates at waypoint 1 and the goal pose against them at
   waypoint H; obs is (B, H, nobs, 6).
+
+``CONFIG3_CELL_LIMITS`` is a work-cell joint-limit set for config 3 (CFSBatch(joint_limits=...)), (5, 2)
+[lo, hi] in rad: joint 1 narrowed to +-1.0 (a fence on either side of the sweep), a ceiling of 0.6 on joint 3 (a conveyor overhead)
+and joint 4 in [-0.4, 0.6] (a neighbouring arm); joints 2 and 5 are free.  Every start and goal of config 3 lies strictly inside
+(joint 1 within +-0.8825, joint 3 within [0.1172, 0.3172], joint 4 within [0.0444, 0.2444]), and the limits bind: see DESIGN.md
+section 16 for the share of unlimited config-3 solutions that break them.
 """
 from __future__ import annotations
 
@@ -31,6 +37,7 @@ from .robotproperty2 import robotproperty2
 from .sysinfo import FANUC_Qp, FANUC_Rblk, RRT_Qv, build_sys_info, cost_terms
 
 X0C = np.array([0.7825, 0.0284, 0.2172, 0.1444, -1.1779])  # main_FANUC.m:30
+CONFIG3_CELL_LIMITS = np.array([[-1.0, 1.0], [-np.inf, np.inf], [-np.inf, 0.6], [-0.4, 0.6], [-np.inf, np.inf]])
 NCAND = 48
 
 

@@ -1,0 +1,311 @@
+"""Joint position limits on the device (include/cfs_hip.h, cfs_problem_set_joint_limits): limits that never
+bind are bit for bit the unlimited handle; limited pieces and whole solves match the test-side reference (tests/limits_reference.py);
+the plans stay inside the limits; a start the limits cannot reach ends QP_INFEASIBLE; the shortcuts keep the answers."""
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+import limits_reference as LR
+from moving_reference import obs_cell
+from motionplanning_5d_m_amd import _lib, workloads
+
+pytestmark = pytest.mark.gpu
+FIELDS = ("u", "x_", "cost_all", "e_cost_all", "e_u_all", "iter_O", "total_iter", "status")
+MU = 1e5
+CELL = workloads.CONFIG3_CELL_LIMITS
+INF5 = np.array([[-np.inf, np.inf]] * 5)
+# Far outside every iterate: the iterates of a QP on its way to an infeasibility proof diverge (beyond 50 rad here), and a limit they
+# cross is a row the proof may take, which changes its step count (total_iter), never its outcome.
+FAR5 = np.array([[-1e6, 1e6]] * 5)
+
+
+def _dist_fn(gpu):
+    return lambda rb, th, ob: gpu.dist_arm(rb, th, ob)[0]
+
+
+@pytest.fixture(scope="module")
+def c3_256(gpu):
+    return workloads.config3(_dist_fn(gpu), B=256)
+
+
+@pytest.fixture(scope="module")
+def c3_1024(gpu):
+    return workloads.config3(_dist_fn(gpu), B=1024)
+
+
+def _inside(th, lim, tol=1e-9):
+    return (th >= lim[:, 0] - tol) & (th <= lim[:, 1] + tol)
+
+
+# ---- 1. limits that never bind are free ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["CFS", "PSGCFS"])
+@pytest.mark.parametrize("jacobian", ["fd_literal", "analytic"])
+@pytest.mark.parametrize("policy", ["stop", "soften"])
+def test_inactive_limits_are_bitwise_the_unlimited_handle(gpu, c3_256, mode, jacobian, policy):
+    import torch
+    s, bt = c3_256
+    margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
+    kw = dict(mode=mode, max_batch=bt.B, jacobian=jacobian, on_infeasible=policy, soft_weight=MU if policy == "soften" else None)
+    nz = bt.noise if mode == "PSGCFS" else None
+    h0 = gpu.CFSBatch(s, bt.nobs, margin, **kw)
+    want = h0.solve(bt.x_init, bt.xR1, bt.ff, bt.caug, bt.obs, noise=nz)
+    dev = torch.device("cuda:0")
+    t = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device=dev)  # noqa: E731
+    for lim in (INF5, FAR5):
+        h = gpu.CFSBatch(s, bt.nobs, margin, joint_limits=lim, **kw)
+        np.testing.assert_array_equal(h.joint_limits(), lim)
+        got = h.solve(bt.x_init, bt.xR1, bt.ff, bt.caug, bt.obs, noise=nz)
+        for f in FIELDS + ("viol_all", "n_soft"):
+            np.testing.assert_array_equal(getattr(got, f), getattr(want, f), err_msg=f"{f} (limits {lim[0].tolist()})")
+        out = h.solve_device(t(bt.x_init), t(bt.xR1), t(bt.ff), t(bt.caug), t(bt.obs), noise=None if nz is None else t(nz))
+        torch.cuda.synchronize()
+        for f in FIELDS:
+            np.testing.assert_array_equal(getattr(out, f).cpu().numpy(), getattr(got, f), err_msg="solve_device " + f)
+        h.close()
+    h0.close()
+
+
+@pytest.mark.parametrize("mode", ["CFS", "PSGCFS"])
+def test_inactive_limits_are_bitwise_with_per_waypoint_obstacles(gpu, mode):
+    s, bt = workloads.config3_moving(_dist_fn(gpu), B=128, seed=20260115)
+    margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
+    nz = bt.noise if mode == "PSGCFS" else None
+    h0 = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=bt.B, obstacles="per_waypoint")
+    h = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=bt.B, obstacles="per_waypoint", joint_limits=FAR5)
+    want = h0.solve(bt.x_init, bt.xR1, bt.ff, bt.caug, bt.obs, noise=nz)
+    got = h.solve(bt.x_init, bt.xR1, bt.ff, bt.caug, bt.obs, noise=nz)
+    for f in FIELDS:
+        np.testing.assert_array_equal(getattr(got, f), getattr(want, f), err_msg=f)
+    h.close()
+    h0.close()
+
+
+# ---- 2. pieces against the reference --------------------------------------------------------------------------------------------
+def test_get_con_and_qp_match_the_reference(gpu, O, c3_256):
+    s, bt = c3_256
+    H, nj, n, nn = s.H, 5, 8, s.H * 5
+    lim = CELL.copy()
+    lim[2, 1] = 0.35                                   # a low ceiling on joint 3: the position rows are active in these QPs
+    robot = O.robotproperty2("M200i")
+    h = gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n, joint_limits=lim)
+    h0 = gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n)
+    assert h.rows == h0.rows + 2 * nn
+    u = np.sin(np.arange(nn))[None] * 0.05 * np.ones((n, 1))
+    x_u = np.stack([O.rollout(H, nj, s.robot.delta_t, bt.xR1[b], u[b]) for b in range(n)])
+    A, b_ = h.get_con(x_u, u, bt.xR1[:n], bt.obs[:n])
+    assert A.shape == (n, h.rows, nn)
+    for b in range(n):
+        s2 = SimpleNamespace(**vars(s))
+        s2.xR1, s2.robot = bt.xR1[b], robot
+        Ar, br = LR.get_con_limited(O, "M200i", s2, obs_cell(bt.obs[b], bt.margin_cfs), x_u[b], u[b], "CFS", lim)
+        np.testing.assert_allclose(A[b], Ar, rtol=0, atol=5e-9)
+        np.testing.assert_allclose(b_[b], br, rtol=0, atol=5e-9)       # (infinite bounds: equal infinities)
+    # one QP per mode on the linearisation at x_init
+    dist, lid, grad = h.linearize(bt.x_init[:n], bt.obs[:n])
+    z = np.zeros((n, nn))
+    active = 0
+    for mode in ("CFS", "PSGCFS"):
+        margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
+        hm = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=n, joint_limits=lim)
+        lin = bt.ff[:n] if mode == "CFS" else np.tile(0.2 * np.cos(np.arange(nn)), (n, 1))   # PSGCFS: u_ to project
+        ug, lam, it, st = hm.qp(lin, z, bt.xR1[:n], dist, grad)
+        assert lam.shape == (n, bt.nobs * H + 6 * nn)
+        for b in range(n):
+            s2 = SimpleNamespace(**vars(s))
+            s2.xR1, s2.robot = bt.xR1[b], robot
+            Ar, br = LR.get_con_limited(O, "M200i", s2, obs_cell(bt.obs[b], margin), bt.x_init[b], z[b], mode, lim)
+            ref = len(br) - 2 * nn
+            if mode == "CFS":
+                G, g0 = s.QQ, bt.ff[b]
+                A2 = np.vstack([Ar[:ref], np.eye(nn), -np.eye(nn), Ar[ref:]])
+                b2 = np.concatenate([br[:ref], s.MAX_input, s.MAX_input, br[ref:]])
+            else:
+                G, g0, A2, b2 = np.eye(nn), -lin[b], Ar, br
+            want, lam_o, _, sto, _ = LR.qp_limited(O, G, g0, A2, b2)
+            assert (int(st[b]) == 0) == (sto == 0), (mode, b, int(st[b]), sto)
+            if sto:
+                continue
+            # test_gpu_parity.py's 1e-9, but for the most degenerate of these QPs (problem 6: 18-22 active collision and position
+            # rows, the oracle's own stationarity residual 7e-14): 1e-8 there, with feasibility checked as well
+            nact = int((lam_o > 0).sum())
+            np.testing.assert_allclose(ug[b], want, rtol=0, atol=1e-9 if nact < 16 else 1e-8)
+            assert (A2[np.isfinite(b2)] @ ug[b] - b2[np.isfinite(b2)]).max() <= 1e-9
+            per = 1 + 2 * nj
+            np.testing.assert_allclose(lam[b][:bt.nobs * H], lam_o[0:ref:per], rtol=1e-6, atol=1e-6)
+            lp = lam[b][bt.nobs * H + 4 * nn:]
+            np.testing.assert_allclose(lp, lam_o[-2 * nn:], rtol=1e-6, atol=1e-6)
+            active += int((lp > 0).sum())
+        hm.close()
+    assert active > 0                                   # the position rows did take part
+    h.close()
+    h0.close()
+
+
+# ---- 3. whole solves against the reference --------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def c3_ref(gpu, O, c3_256):
+    """first 16 problems: the limited reference's answers and its chaotic ones, per solver"""
+    s, bt = c3_256
+    idx = list(range(16))
+    cache = {}
+
+    def get(mode):
+        if mode not in cache:
+            want = LR.batch_limited(O, s, bt, mode, idx, CELL)
+            chaotic, _ = LR.chaotic_limited(O, s, bt, mode, idx, want, CELL)
+            cache[mode] = (idx, want, chaotic)
+        return cache[mode]
+    return get
+
+
+@pytest.mark.parametrize("mode,tol", [("CFS", 1e-7), ("PSGCFS", 1e-5)])
+def test_whole_solves_match_the_reference(gpu, c3_256, c3_ref, mode, tol):
+    s, bt = c3_256
+    idx, want, chaotic = c3_ref(mode)
+    margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
+    h = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=len(idx), joint_limits=CELL)
+    got = h.solve(bt.x_init[idx], bt.xR1[idx], bt.ff[idx], bt.caug[idx], bt.obs[idx], noise=bt.noise[idx] if mode == "PSGCFS" else None)
+    print(f"{mode}: excluded as chaotic (reference moves > 1e-6 under a 1e-12 kick): {[idx[k] for k in np.nonzero(chaotic)[0]]}")
+    checked = 0
+    for k, b in enumerate(idx):
+        if chaotic[k]:
+            continue
+        assert (int(got.status[k]), int(got.iter_O[k])) == (want[k].status, want[k].iter_O), b
+        assert np.abs(got.x_[k] - want[k].x_).max() < tol, b
+        checked += 1
+    assert checked >= len(idx) // 2
+    h.close()
+
+
+# ---- 4. the limits hold ----------------------------------------------------------------------------------------------------------
+def test_main_fanuc_psgcfs_stays_inside_a_joint_1_limit(gpu, golden):
+    R, s, obs = gpu.main_FANUC_problem()
+    nz = golden["main_FANUC_PSGCFS/noise"]
+    free = gpu.PSGCFS_FANUC(obs, s, R).optimizer(noise=nz)
+    th_free = free.x_.reshape(s.H, 10)[:, :5]
+    assert th_free[:, 0].max() > 1.45                  # the unlimited plan swings joint 1 out to ~1.50 rad
+    lim = INF5.copy()
+    lim[0] = [-1.2, 1.2]
+    got = gpu.PSGCFS_FANUC(obs, s, R, joint_limits=lim).optimizer(noise=nz)
+    th = got.x_.reshape(s.H, 10)[:, :5]
+    print(f"main_FANUC PSGCFS: unlimited max joint 1 {th_free[:, 0].max():.4f}; limited status {got.status} iter_O {got.iter_O}, "
+          f"max joint 1 {th[:, 0].max():.6f}")
+    assert got.status in (0, 1) and _inside(th, lim).all()
+
+
+@pytest.mark.parametrize("mode", ["CFS", "PSGCFS"])
+def test_config3_cell_limits_hold(gpu, c3_1024, mode):
+    s, bt = c3_1024
+    margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
+    nz = bt.noise if mode == "PSGCFS" else None
+    free = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=bt.B).solve(bt.x_init, bt.xR1, bt.ff, bt.caug, bt.obs, noise=nz)
+    broke = ~_inside(free.x_.reshape(bt.B, s.H, 10)[:, :, :5], CELL, 0.0).all(axis=(1, 2))
+    for policy in ("stop", "soften"):
+        h = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=bt.B, joint_limits=CELL, on_infeasible=policy,
+                         soft_weight=MU if policy == "soften" else None)
+        r = h.solve(bt.x_init, bt.xR1, bt.ff, bt.caug, bt.obs, noise=nz)
+        th = r.x_.reshape(bt.B, s.H, 10)[:, :, :5]
+        done = np.isin(r.status, (0, 1, 4))
+        ok = _inside(th, CELL).all(axis=(1, 2))
+        worst = np.maximum(th - CELL[:, 1], CELL[:, 0] - th).max(axis=(1, 2))
+        print(f"config3 {mode} {policy}: unlimited solutions outside the cell {int(broke.sum())} of {bt.B}; limited: status counts "
+              f"{np.bincount(r.status, minlength=5).tolist()}, worst excursion over status 0/1/4 {worst[done].max():.2e} rad")
+        assert broke.sum() > 0 and done.sum() >= bt.B // 2
+        assert ok[done].all(), np.nonzero(done & ~ok)[0]
+        h.close()
+
+
+# ---- 5. a start the limits cannot reach ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["CFS", "PSGCFS"])
+@pytest.mark.parametrize("policy", ["stop", "soften"])
+def test_unreachable_start_is_infeasible(gpu, golden, mode, policy):
+    R, s, obs = gpu.main_FANUC_problem()
+    lim = INF5.copy()
+    lim[0] = [-1.2, 0.3]                                # theta_1 starts at 0.78: one step covers at most dt * lim / 2 = 0.25
+    kw = dict(on_infeasible=policy, soft_weight=MU if policy == "soften" else None, joint_limits=lim)
+    cls = gpu.CFS_FANUC if mode == "CFS" else gpu.PSGCFS_FANUC
+    got = cls(obs, s, R, **kw).optimizer(**({"noise": golden["main_FANUC_PSGCFS/noise"]} if mode == "PSGCFS" else {}))
+    assert _lib.STATUS[got.status] == "QP_INFEASIBLE" and got.iter_O == 1, (got.status, got.iter_O)
+
+
+# ---- 6. the shortcuts keep the answers -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["CFS", "PSGCFS"])
+def test_shortcuts_off_keep_the_answers(gpu, c3_256, c3_ref, mode):
+    s, bt = c3_256
+    idx, _, chaotic = c3_ref(mode)
+    margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
+    nz = bt.noise[idx] if mode == "PSGCFS" else None
+
+    def run(**flags):
+        h = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=len(idx), joint_limits=CELL)
+        h.debug_options(**flags)
+        r = h.solve(bt.x_init[idx], bt.xR1[idx], bt.ff[idx], bt.caug[idx], bt.obs[idx], noise=nz)
+        h.close()
+        return r
+    base = run()
+    off = run(no_certificate=True)                       # a proof about the same QP: the same bits but for the step counts
+    for f in ("status", "iter_O", "u", "x_", "cost_all", "e_u_all"):
+        np.testing.assert_array_equal(getattr(off, f), getattr(base, f), err_msg=f)
+    pinned = ~chaotic
+    for flag in ("no_warm_start", "no_refine"):
+        r = run(**{flag: True})
+        same = (r.status == base.status) & (r.iter_O == base.iter_O)
+        err = np.abs(r.x_ - base.x_).max(axis=1)
+        print(f"{mode} {flag}: status / iteration count differ on {int((~same).sum())} of {len(idx)} ({int((~same & pinned).sum())} pinned), "
+              f"max |dx_| over the pinned ones {err[pinned].max():.2e} rad")
+        assert (r.status[pinned] == base.status[pinned]).all()
+        assert err[pinned].max() < 1e-5
+
+
+# ---- refusals and the round trip on a real handle ------------------------------------------------------------------------------
+def test_setter_round_trip_and_refusals(gpu):
+    R, s, obs = gpu.main_FANUC_problem()
+    lib = gpu.lib()
+    h = gpu.CFSBatch(s, 2, [0.25, 0.25], max_batch=1)
+    assert h.joint_limits() is None
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    lo, hi = np.array([-1.0, -2.0, -np.inf, -0.5, -3.0]), np.array([1.0, 2.0, 0.6, np.inf, 3.0])
+    assert lib.cfs_problem_set_joint_limits(h._h, p(lo), p(hi)) == 0
+    np.testing.assert_array_equal(h.joint_limits(), np.stack([lo, hi], axis=1))
+    for bad_lo, bad_hi in ((np.where(np.arange(5) == 2, np.nan, lo), hi), (lo, np.where(np.arange(5) == 1, -2.0, hi)),
+                           (np.where(np.arange(5) == 0, 1.0, lo), hi)):
+        assert lib.cfs_problem_set_joint_limits(h._h, p(bad_lo), p(bad_hi)) == -1
+    assert lib.cfs_problem_set_joint_limits(h._h, p(lo), None) == -1
+    np.testing.assert_array_equal(h.joint_limits(), np.stack([lo, hi], axis=1))     # nothing changed
+    with pytest.raises(ValueError):
+        h.set_joint_limits(np.zeros((5, 2)))
+    on, l2, h2 = C.c_int(0), np.zeros(5), np.zeros(5)
+    assert lib.cfs_problem_get_joint_limits(h._h, C.byref(on), p(l2), p(h2)) == 0 and on.value == 1
+    z = lambda *sh: np.zeros(sh)  # noqa: E731
+    x_init, xR1, ff, caug, ob, u0 = s.x_[None].copy(), z(1, 10), s.ff[None].copy(), z(1), z(1, 2, 6), z(1, s.H * 5)
+    D, ep = np.array([0.2, 0.2]), np.array([0.25, 0.25])
+    i = _lib.cfs_batch_in()
+    i.B = 1
+    i.x_init, i.xR1, i.ff, i.caug, i.obs = [a.ctypes.data_as(C.c_void_p) for a in (x_init, xR1, ff, caug, ob)]
+    r = [z(1, 150), z(1, 300), z(1, 20), z(1, 20), z(1, 20), np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)]
+    o = _lib.cfs_batch_out(*[a.ctypes.data_as(C.c_void_p) for a in r])
+    assert lib.cfs_chomp_batch(h._h, C.byref(i), p(u0), p(D), p(ep), C.byref(o)) == -1      # CHOMP_FANUC has no QP
+    h.set_joint_limits(None)
+    assert h.joint_limits() is None
+    assert lib.cfs_problem_get_joint_limits(h._h, C.byref(on), p(l2), p(h2)) == 0 and on.value == 0
+    assert np.isneginf(l2).all() and np.isposinf(h2).all()
+    h.close()
+
+
+def test_mesh_handle_solves_inside_the_limits(gpu):
+    R, s, obs = gpu.main_FANUC_problem()
+    # main_FANUC's second obstacle as a mesh far below the floor: the QP goes through the same kernel as a line handle's
+    m = gpu.Mesh(vertices=np.array([[0, 0, -5.0], [1, 0, -5.0], [0, 1, -5.0]]), faces=np.array([[0, 1, 2]], np.int32))
+    cell = [obs[0], dict(mesh=m, epsilon=0.25, D=0.2)]
+    free = gpu.CFS_FANUC(cell, s, R).optimizer()
+    th_free = free.x_.reshape(s.H, 10)[:, :5]
+    top, th3 = th_free[:, 2].max(), float(np.asarray(s.xR, float).reshape(10, -1)[2, 0])
+    assert top > th3 + 0.05                         # the plan lifts joint 3 above its start (main_FANUC: to ~1.0 rad)
+    lim = INF5.copy()
+    lim[2] = [-np.inf, 0.5 * (th3 + top)]           # a ceiling half way up
+    got = gpu.CFS_FANUC(cell, s, R, joint_limits=lim).optimizer()
+    th = got.x_.reshape(s.H, 10)[:, :5]
+    print(f"mesh handle: unlimited max joint 3 {top:.4f}; limited to {lim[2, 1]:.4f}: status {got.status}, max joint 3 {th[:, 2].max():.6f}")
+    assert got.status in (0, 1) and _inside(th, lim).all()
