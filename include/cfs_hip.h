@@ -477,6 +477,41 @@ int cfs_select_best_device(cfs_problem *p, int S, int K, const int *route_ok, co
                            const double *cand_viol_all, const cfs_batch_out *best, double *best_viol_all, int *selected,
                            int *has_solution, void *stream);
 
+/* ---- clearance audit between the waypoints ---------------------------------------------------------
+ * Every collision row of get_con is written at a waypoint (Lib/CFS_FANUC.m:110-120, Lib/PSGCFS_FANUC.m:152-160); between two
+ * waypoints the arm follows the double integrator of robotproperty2.m:136-139, and nothing in the reference -- nor any status
+ * of the solvers -- says how close that motion comes to an obstacle.  This entry measures it for B trajectories of the handle's
+ * family, S = substeps samples per interval (1..64):
+ *   interval i = 0..H-1 starts at state i-1 (xR1 for i = 0, row i-1 of x_ otherwise), has acceleration u[i] and lasts delta_t;
+ *   sample k = 0..S is the pose theta = theta_s + tau*v_s + tau^2/2*u_i at tau = k*delta_t/S, except that sample k = S is row i
+ *   of x_ itself (the waypoint values are cfs_dist_arm's on x_).  x_ must be the rollout of (xR1, u), as every solver returns it.
+ *   At every sample: dist_arm (the FK, distLinSeg, near-zero surrogate and first-minimum link of cfs_dist_arm) against every
+ *   line obstacle.  obs: B x nobs x 6; on a CFS_OBS_PER_WAYPOINT handle B x H x nobs x 6, and inside interval i >= 1 the two end
+ *   points of an obstacle are interpolated linearly between row i-1 (tau = 0) and row i (tau = delta_t); in interval 0 the
+ *   obstacle is held at row 0 (the handle has no row for t = 0).
+ * Outputs per (problem, obstacle), B x nobs each, all required:
+ *   dist_wp     min over the H waypoints;
+ *   dist_path   min over all H*(S+1) samples (<= dist_wp);
+ *   t_path, link_path   where the first such minimum occurs (lowest interval, then lowest k): seconds from the start,
+ *               (i + k/S)*delta_t, and the closest link (1-based);
+ *   dist_lower  min over all sub-intervals [k, k+1] of (d_k + d_{k+1})/2 - L*delta_t/(2*S), where L bounds |d/dtau distance| on
+ *               the sub-interval: L = max over links k of sum_{m<=k} w_m*rho[m][k] + v_obs, w_m the larger |v_m| at the two ends
+ *               (the velocity is linear in tau), rho[m][k] = sum_{j=m..k} len_j + c_k with len_j = hypot(a_j, d_j) of DH row j
+ *               (2L: the length of link j's translation) and c_k the larger norm of capsule k's end points in its link frame,
+ *               v_obs the larger end-point displacement of the obstacle over the interval divided by delta_t (0 when static or
+ *               held).  GUARANTEE: if dist_lower[b][j] > 0, obstacle j stays at least that far from every capsule axis of
+ *               problem b for all t in [0, H*delta_t] (a positive bound also rules out the near-zero surrogate, the only
+ *               discontinuity of dist_arm).  dist_path - dist_lower <= max L * delta_t/(2*S): the bound tightens as 1/S.
+ * Deterministic (no atomics); a problem's results depend on neither B nor its position in the batch.  Independent of mode,
+ * Jacobian mode, infeasible-QP policy and joint limits; reads no state of the handle that a solve writes and changes none.
+ * CFS_ERR_INVALID_ARG, nothing written: NULL handle or array, B outside 1..max_batch, substeps outside 1..64, a handle with mesh
+ * obstacles (cfs_problem_set_meshes with nmesh > 0: meshes are not audited).
+ * cfs_clearance_device: DEVICE pointers, enqueued on `stream`, no synchronisation.  cfs_clearance: HOST pointers, synchronises. */
+int cfs_clearance_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
+                         double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, void *stream);
+int cfs_clearance(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
+                  double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path);
+
 /* ---- developer / test entry points -------------------------------------------------------------------
  * No caller of the path needs these; they exist so that every shortcut the solver takes can be switched off and compared
  * under pytest (tests/test_gpu_shortcuts.py), and for the cycle-stamp / step-trace probes under tools/.  All state is per

@@ -7,6 +7,10 @@
 //        obs = the reference's obs cell (obs{j}.l 3x2, .epsilon, .D; obs{j}.mesh = handle for a mesh obstacle, last in the cell);
 //        noise = nn x rows matrix of normrnd(0,0.1) draws consumed one column per PSG step (PSGCFS_FANUC.m:109), or []
 //   [Ainq, binq] = cfs_mex('get_con', mode, obs, sys_info, ROBOT, x_, u)   % self.get_con() (Lib/CFS_FANUC.m:101-135): dense, reference row order
+//   [dist_path, dist_lower, dist_wp, t_path, link_path] = cfs_mex('clearance', mode, obs, sys_info, ROBOT, x_, u, substeps)
+//        audit of a solved trajectory (x_, u as 'solve' returns them) between its waypoints, nobs x 1 each: the smallest distance over
+//        substeps (default 16, 1..64) samples per interval, a certified lower bound over continuous time, the smallest distance at
+//        the waypoints, and when / on which link the path minimum occurs (cfs_clearance, include/cfs_hip.h); no mesh obstacles
 //   [u, x_, cost_all, e_cost_all, e_u_all, iter_O] = cfs_mex('chomp', obs_, sys_info, ROBOT, uref)   % CHOMP_FANUC.optimizer (Lib/CHOMP_FANUC.m:54-69);
 //        obs_ = the reference's cell: obs_{1}.num_obs followed by the obstacles (M16iB/CHOMP.m:26-29)
 //   [d, linkid, grad] = cfs_mex('dist_arm', theta, obs_l, robot, ROBOT)  % dist_arm_3D_200i_2 / dist_arm_3D_Heu_2 / dist_arm_2L(theta, base, obs_l, robot)
@@ -186,6 +190,25 @@ static void get_con(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     if (nlhs > 1) plhs[1] = b; else mxDestroyArray(b);
 }
 
+// clearance of a solved trajectory along the motion between its waypoints (cfs_clearance; the reference has no counterpart: its
+// collision rows, Lib/CFS_FANUC.m:110-120, are written at the waypoints only)
+static void clearance(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs < 7) mexErrMsgTxt("[dist_path, dist_lower, dist_wp, t_path, link_path] = cfs_mex('clearance', mode, obs, sys_info, ROBOT, x_, u [, substeps])");
+    const int mode = (int)mxGetScalar(prhs[1]);
+    const std::string ROBOT = mxArrayToString(prhs[4]);
+    Family f;
+    make_family(f, mode, prhs[2], 0, (int)mxGetNumberOfElements(prhs[2]), prhs[3], ROBOT.c_str(), false, true);
+    const int nobs = f.d.nobs, S = nrhs > 7 ? (int)mxGetScalar(prhs[7]) : 16;
+    mxArray *o[5];
+    for (int k = 0; k < 5; ++k) o[k] = mxCreateDoubleMatrix(nobs, 1, mxREAL);
+    std::vector<int> link(nobs, 0);
+    check(cfs_clearance(f.p, 1, S, mxGetPr(prhs[5]), mxGetPr(prhs[6]), field_ptr(prhs[3], "xR"), f.obs6.data(), mxGetPr(o[2]), mxGetPr(o[0]),
+                        mxGetPr(o[1]), mxGetPr(o[3]), link.data()));
+    for (int j = 0; j < nobs; ++j) mxGetPr(o[4])[j] = link[j];
+    for (int k = 0; k < 5; ++k) { if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]); }
+}
+
 // CHOMP_FANUC(obs_, sys_info, uref, ROBOT).optimizer()  (Lib/CHOMP_FANUC.m:34-69; Lib/functions/s_Solver.m:12-21)
 static void chomp(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
@@ -323,6 +346,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         solve(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "get_con") {
         get_con(nlhs, plhs, nrhs, prhs);
+    } else if (cmd == "clearance") {
+        clearance(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "chomp") {
         chomp(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "dist_arm") {

@@ -205,6 +205,8 @@ SYMBOLS = [
     ("cfs_problem_get_obstacle_motion", C.c_int, [_P, C.POINTER(C.c_int)]),
     ("cfs_problem_set_joint_limits", C.c_int, [_P, _P, _P]),
     ("cfs_problem_get_joint_limits", C.c_int, [_P, C.POINTER(C.c_int), _P, _P]),
+    ("cfs_clearance_device", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("cfs_clearance", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)

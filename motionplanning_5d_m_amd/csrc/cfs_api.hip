@@ -201,6 +201,7 @@ struct cfs_problem {
     int motion = CFS_OBS_STATIC;          // cfs_problem_set_obstacle_motion: obs arrays are B x nobs x 6 | B x H x nobs x 6
     bool limited = false;                 // cfs_problem_set_joint_limits: position rows in every QP (the LIM kernels); lim[nj, 3nj) = [lo; hi]
     std::vector<double> jlim;             // [lo; hi] as set (2 nj; empty: no limits)
+    double rho[CFS_MAX_LINKS * CFS_MAX_LINKS];   // cfs_clearance*: reach of capsule k about the axis of joint m (cfs_clear_build_rho)
     double soft_weight = 0.0;             // mu of CFS_INFEAS_SOFTEN (0: never set)
     DevBuf<double> soft_viol;             // max_batch x MAX_O_ITER: viol_all of the last whole solve (allocated with SOFTEN)
     DevBuf<int> soft_n;                   // max_batch: n_soft of the last whole solve
@@ -434,6 +435,7 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
     if (hipDeviceGetAttribute(&p->n_cu, hipDeviceAttributeMultiprocessorCount, g_device) != hipSuccess || p->n_cu < 1) p->n_cu = 256;
     p->nn = nn; p->ns = ns; p->nx = nx; p->lmax_vel = lmax_vel; p->lmax_H = lmax_H;
     build_dev_robot(desc->robot, p->hrobot);
+    cfs_clear_build_rho(p->hrobot, nj, p->rho);
     const size_t Bm = (size_t)desc->max_batch;
     // spill pool (rows of Y beyond LDS, columns of P beyond the registers): one slot per workgroup that can be resident at once (two per
     // compute unit), not one per problem of the batch -- config 4: 512 slots instead of 4 096 (0.4 GB instead of 3.4 GB per handle)
@@ -1461,6 +1463,52 @@ int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const 
     if (lambda) st.down(lambda, d_lam, (size_t)B * nlam);
     st.down(qp_iter, d_it, (size_t)B);
     st.down(status, d_st, (size_t)B);
+    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
+    return CFS_SUCCESS;
+}
+
+// ---- clearance audit (cfs_clear.hip) ----------------------------------------------------------------------------------------
+// Reads the family constants of the handle (robot, H, nobs, delta_t, obstacle motion) and nothing a solve writes.
+int cfs_clearance_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
+                         double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, void *stream)
+{
+    int rc = check_batch(p, B);
+    if (rc) return rc;
+    if (substeps < 1 || substeps > 64) return fail(CFS_ERR_INVALID_ARG, "substeps=%d outside 1..64", substeps);
+    if (!x_ || !u || !xR1 || !obs || !dist_wp || !dist_path || !dist_lower || !t_path || !link_path) return fail(CFS_ERR_INVALID_ARG, "NULL array");
+    if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "the clearance audit measures line obstacles only: this handle has %d mesh obstacles", p->nmesh);
+    HIPCHK(hipSetDevice(p->device));
+    ClearParams cp;
+    cp.rb = p->rb.p; cp.B = B; cp.H = p->d.H; cp.nj = p->d.njoint; cp.nobs = p->d.nobs; cp.S = substeps;
+    cp.move = moving(p) ? 1 : 0; cp.dt = p->d.robot.delta_t;
+    cp.x_ = x_; cp.u = u; cp.xR1 = xR1; cp.obs = obs;
+    cp.dist_wp = dist_wp; cp.dist_path = dist_path; cp.dist_lower = dist_lower; cp.t_path = t_path; cp.link_path = link_path;
+    memcpy(cp.rho, p->rho, sizeof cp.rho);
+    HIPCHK(launch_clearance(cp, reinterpret_cast<hipStream_t>(stream)));
+    return CFS_SUCCESS;
+}
+
+int cfs_clearance(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
+                  double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path)
+{
+    int rc = check_batch(p, B);
+    if (rc) return rc;
+    if (substeps < 1 || substeps > 64) return fail(CFS_ERR_INVALID_ARG, "substeps=%d outside 1..64", substeps);
+    if (!x_ || !u || !xR1 || !obs || !dist_wp || !dist_path || !dist_lower || !t_path || !link_path) return fail(CFS_ERR_INVALID_ARG, "NULL array");
+    if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "the clearance audit measures line obstacles only: this handle has %d mesh obstacles", p->nmesh);
+    HIPCHK(hipSetDevice(p->device));
+    const size_t n = (size_t)B * p->d.nobs;
+    Stage st;
+    const double *d_x = st.up(x_, (size_t)B * p->nx), *d_u = st.up(u, (size_t)B * p->nn), *d_x1 = st.up(xR1, (size_t)B * p->ns);
+    const double *d_obs = st.up(obs, (size_t)B * obs_rows(p) * 6);
+    double *d_wp = st.up<double>(nullptr, n), *d_path = st.up<double>(nullptr, n), *d_low = st.up<double>(nullptr, n), *d_t = st.up<double>(nullptr, n);
+    int *d_lk = st.up<int>(nullptr, n);
+    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
+    rc = cfs_clearance_device(p, B, substeps, d_x, d_u, d_x1, d_obs, d_wp, d_path, d_low, d_t, d_lk, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    st.down(dist_wp, d_wp, n); st.down(dist_path, d_path, n); st.down(dist_lower, d_low, n); st.down(t_path, d_t, n);
+    st.down(link_path, d_lk, n);
     if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
     return CFS_SUCCESS;
 }

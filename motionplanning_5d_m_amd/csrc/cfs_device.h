@@ -78,6 +78,20 @@ struct DenseConParams {
 };
 void launch_dense_con(const DenseConParams &p, hipStream_t s);
 
+// ---- clearance audit along the motion between the waypoints (cfs_clear.hip) ----------------------
+struct ClearParams {
+    const DevRobot *rb;
+    int B, H, nj, nobs, S;       // S: sub-steps per interval (1..64)
+    int move;                    // 0: obs is B x nobs x 6 | 1: B x H x nobs x 6 (CFS_OBS_PER_WAYPOINT), interpolated inside an interval
+    double dt;
+    const double *x_, *u, *xR1, *obs;      // B x H*2nj, B x H*nj, B x 2nj
+    double *dist_wp, *dist_path, *dist_lower, *t_path;   // B x nobs each
+    int *link_path;              // B x nobs (1-based)
+    double rho[CFS_MAX_LINKS * CFS_MAX_LINKS];   // rho[m*CFS_MAX_LINKS + k]: reach of capsule k about the axis of joint m (cfs_clear_build_rho)
+};
+hipError_t launch_clearance(const ClearParams &p, hipStream_t s);
+void cfs_clear_build_rho(const DevRobot &rb, int nj, double *rho);   // host, once per handle
+
 enum { QP_OK = 0, QP_INFEASIBLE = 2, QP_NUMERIC = 3 };   // outcome of one QP inside the fused kernel
 
 // ---- K3: batched dense products on the matrix cores (fp64 MFMA) --------------------------------

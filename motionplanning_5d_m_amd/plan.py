@@ -9,6 +9,8 @@ The reference plans one start/goal pair (RRTstar_CFS.m): rounds of ``num_seed`` 
 * build  -- one ``cfs_build_terms_from_ragged_routes_device`` call (cubic resampling to H+1 = 41 points + cost terms);
 * solve  -- one ``cfs_solve_batch_device`` over all S*K candidates (select="best") or over the S shortest routes
             (select="shortest", the reference's rule);
+* audit  -- optional (min_clearance=): one ``cfs_clearance_device`` launch measures every smoothed candidate along the motion
+            between its waypoints; a candidate that comes closer to an obstacle than margin - slack is not eligible;
 * select -- ``cfs_select_best_device``: per slot the best smoothed candidate by the rule of include/cfs_hip.h.
 
 This module packs arguments, indexes tensors (placeholder routes, the shortest route's index for select="shortest") and reads
@@ -17,6 +19,7 @@ S fail flags per round; tree growth, resampling, the solves and the selection ar
 from __future__ import annotations
 
 import ctypes as C
+import math
 import numbers
 from types import SimpleNamespace
 
@@ -25,7 +28,7 @@ import numpy as np
 from . import _lib
 from .rrt import RRT_FANUC
 from .robotproperty2 import robotproperty2
-from .solvers import CFSBatch, _infeasible_args, _jacobian_code, _joint_limits_array, _ptr, obs_to_array
+from .solvers import CFSBatch, _infeasible_args, _jacobian_code, _joint_limits_array, _ptr, _substeps, obs_to_array
 from .sysinfo import RRTstar_CFS_problem
 
 try:
@@ -67,11 +70,16 @@ class RRTCFSPlanner:
     rule -- the route with the fewest nodes, first seed on ties (s_Parallel_rrt.m:27-28) -- then one CFS per slot.
     The cost family is RRTstar_CFS.m:124-187's (sysinfo.RRTstar_CFS_problem: M200i, H = 40); the obstacles are `pobs`, with
     margins obs{j}.epsilon (CFS) or obs{j}.D (PSGCFS).  joint_limits: None | "robot" | a (5, 2) array of [lo, hi], the smoothing
-    QPs' position rows (CFSBatch; the RRT samples ignore them).  Arguments are validated before anything touches the device."""
+    QPs' position rows (CFSBatch; the RRT samples ignore them).
+    min_clearance: None (the default: no audit, results exactly those without the argument) | slack in metres (>= 0): after the
+    solve every candidate is audited with audit_substeps samples per interval (CFSBatch.clearance_device) and is eligible only if
+    dist_path[j] >= margin_j - slack for every obstacle j.  A slot none of whose found routes passes keeps the candidate the
+    plain rule names, with has_solution = 0.  Results then carry dist_path, dist_lower (S, nobs) and clearance_ok (S).
+    Arguments are validated before anything touches the device."""
 
     def __init__(self, pobs, sys_rrt, region_g, region_s, sample_off, ROBOT="M200i", rrt_solver="RRT", num_seed=6, mode="CFS",
                  select="best", on_infeasible="stop", soft_weight=None, jacobian="fd_literal", max_slots=256, device=None,
-                 joint_limits=None):
+                 joint_limits=None, min_clearance=None, audit_substeps=16):
         if select not in SELECT:
             raise ValueError(f"select must be one of {SELECT}, not {select!r}")
         if not _is_int(num_seed) or not 1 <= num_seed <= MAX_SEEDS:
@@ -89,6 +97,11 @@ class RRTCFSPlanner:
         _jacobian_code(jacobian)
         _infeasible_args(on_infeasible, soft_weight)
         _joint_limits_array(joint_limits, robotproperty2("M200i"), 5)
+        if min_clearance is not None:
+            if isinstance(min_clearance, bool) or not isinstance(min_clearance, numbers.Real) or not math.isfinite(min_clearance) or min_clearance < 0:
+                raise ValueError(f"min_clearance must be None or a finite slack >= 0 in metres, not {min_clearance!r}")
+        self.min_clearance = None if min_clearance is None else float(min_clearance)
+        self.audit_substeps = _substeps(audit_substeps, "audit_substeps")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch is not None and torch.cuda.is_available() else torch.device("cuda", 0)
         elif _is_int(device):
@@ -154,9 +167,11 @@ class RRTCFSPlanner:
           u, x_, cost_all, e_cost_all, e_u_all, cost (final cost cost_all[iter_O-2], NaN without one), iter_O, total_iter,
           status (-1: no route found), has_solution (1: status 0/1, or 4 when no seed reached 0/1), selected (seed k, -1: no
           route), route (S, MAX_ITER+1, 5) / route_len (the selected route; 0 rows without one), rounds;
-          on "soften" also viol_all, n_soft.
+          on "soften" also viol_all, n_soft; with min_clearance also dist_path, dist_lower (S, nobs; NaN without a route) and
+          clearance_ok (1: the kept candidate keeps margin - slack along its motion).
         want_candidates: also .candidates -- the S*K solve outputs (select="best"), route, route_len, route_ok of every seed.
-        timings: a dict to receive the milliseconds of the grow / build / solve / select parts (events on the stream)."""
+        timings: a dict to receive the milliseconds of the grow / build / solve / select parts (events on the stream; with
+        min_clearance also audit)."""
         if not _is_int(seed) or seed < 0:
             raise ValueError(f"seed must be a non-negative integer, not {seed!r}")
         if not _is_int(max_rounds) or max_rounds < 1:
@@ -218,7 +233,6 @@ class RRTCFSPlanner:
             if self.on_infeasible == "soften":
                 v, ns = self.cfs.soft_results(SK)
                 viol, n_soft = torch.tensor(v, device=dev), torch.tensor(ns, device=dev)
-            mark("select0")
             rows_ok, kpick = route_ok, None
         else:
             lens = torch.where(route_ok != 0, route_len, torch.full_like(route_len, torch.iinfo(torch.int32).max)).view(S, K)
@@ -231,15 +245,43 @@ class RRTCFSPlanner:
             if self.on_infeasible == "soften":
                 v, ns = self.cfs.soft_results(S)
                 viol, n_soft = torch.tensor(v, device=dev), torch.tensor(ns, device=dev)
-            mark("select0")
             rows_ok = found.to(torch.int32)                                         # the K = 1 selection gathers the S rows
         Kc = K if self.select == "best" else 1
-        best = self.cfs.alloc_outputs(S, dev)
-        best.status.fill_(-1)
-        selected, has_solution = torch.empty(S, **i32), torch.empty(S, **i32)
-        best_viol = torch.zeros(S, self.cfs.K, dtype=torch.float64, device=dev) if viol is not None else None
-        select_best_device(self.cfs, S, Kc, rows_ok, cand, best, selected, has_solution, viol, best_viol, stream=st)
+        aud = None
+        if self.min_clearance is not None:                                            # one launch over every solved candidate
+            mark("audit0")
+            aud = self.cfs.clearance_device(cand.x_, cand.u, terms[1], self._obs[:S * Kc], substeps=self.audit_substeps, stream=st)
+            clear_ok = (aud.dist_path >= self.cfs._margin_on(dev)[None, :] - self.min_clearance).all(dim=1)
+        mark("select0")
+
+        def pick(ok):
+            o = self.cfs.alloc_outputs(S, dev)
+            o.status.fill_(-1)
+            o.selected, o.has_solution = torch.empty(S, **i32), torch.empty(S, **i32)
+            o.viol = torch.zeros(S, self.cfs.K, dtype=torch.float64, device=dev) if viol is not None else None
+            select_best_device(self.cfs, S, Kc, ok, cand, o, o.selected, o.has_solution, viol, o.viol, stream=st)
+            return o
+        if aud is None:
+            best = pick(rows_ok)
+        else:
+            # eligible = found and clear; a slot that comes back empty although a seed found a route takes the plain rule's
+            # candidate, without a solution (cfs_select_best_device itself is unchanged)
+            best, plain = pick(rows_ok * clear_ok.to(torch.int32)), pick(rows_ok)
+            fall = (best.selected < 0) & (plain.selected >= 0)
+            for name in ("u", "x_", "cost_all", "e_cost_all", "e_u_all", "iter_O", "total_iter", "status", "selected") + (("viol",) if viol is not None else ()):
+                a, b2 = getattr(best, name), getattr(plain, name)
+                setattr(best, name, torch.where(fall.view(-1, *([1] * (a.ndim - 1))), b2, a))
+            best.has_solution = torch.where(fall, torch.zeros_like(best.has_solution), best.has_solution)
+        selected, has_solution, best_viol = best.selected, best.has_solution, best.viol
+        del best.selected, best.has_solution, best.viol
         mark("end")
+        if aud is not None:                                                           # the kept candidate's audit
+            krow = torch.arange(S, device=dev) * Kc + selected.clamp(min=0).long()
+            kept = (selected >= 0)
+            nan = torch.full((S, self.cfs.nobs), float("nan"), dtype=torch.float64, device=dev)
+            best.dist_path = torch.where(kept[:, None], aud.dist_path[krow], nan)
+            best.dist_lower = torch.where(kept[:, None], aud.dist_lower[krow], nan)
+            best.clearance_ok = (kept & clear_ok[krow]).to(torch.int32)
         if kpick is not None:                                                         # shortest: the seed is the argmin
             selected = torch.where(selected >= 0, kpick.to(torch.int32), selected)
         have = selected >= 0
@@ -262,9 +304,13 @@ class RRTCFSPlanner:
                 c.iter_O, c.total_iter, c.status = cand.iter_O, cand.total_iter, cand.status
                 if viol is not None:
                     c.viol_all, c.n_soft = viol, n_soft
+                if aud is not None:
+                    c.xR1, c.dist_path, c.dist_lower, c.clear_ok = terms[1], aud.dist_path, aud.dist_lower, clear_ok.to(torch.int32)
             res.candidates = c
         if timings is not None:
             stream.synchronize()
             timings.update(grow=ev["grow0"].elapsed_time(ev["build0"]), build=ev["build0"].elapsed_time(ev["solve0"]),
-                           solve=ev["solve0"].elapsed_time(ev["select0"]), select=ev["select0"].elapsed_time(ev["end"]))
+                           solve=ev["solve0"].elapsed_time(ev.get("audit0", ev["select0"])), select=ev["select0"].elapsed_time(ev["end"]))
+            if "audit0" in ev:
+                timings["audit"] = ev["audit0"].elapsed_time(ev["select0"])
         return res

@@ -109,6 +109,13 @@ def _joint_limits_array(joint_limits, robot, nj):
     return np.ascontiguousarray(a)
 
 
+def _substeps(substeps, name="substeps"):
+    """sub-steps per interval of the clearance audit (cfs_clearance): an integer in 1..64, else ValueError"""
+    if isinstance(substeps, bool) or not isinstance(substeps, (int, np.integer)) or not 1 <= substeps <= 64:
+        raise ValueError(f"{name} must be an integer in 1..64, not {substeps!r}")
+    return int(substeps)
+
+
 def _infeasible_args(on_infeasible, soft_weight):
     """(policy code, weight) for cfs_problem_set_infeasible_policy; ValueError for anything malformed.  "soften" needs a finite
     soft_weight > 0; "stop" ignores a (valid) weight and passes 1.0 when there is none."""
@@ -178,6 +185,7 @@ class CFSBatch:
         d.QQ, d.lim, d.margin = _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2])
         if keep[2].size != self.nobs:
             raise ValueError("margin must have one entry per obstacle")
+        self.margin = keep[2].copy()
         check_dynamics_asked = check_dynamics
         if self.from_weights:
             check_dynamics = False                       # Aaug / Baug are implied (and built) by the library
@@ -401,6 +409,72 @@ class CFSBatch:
             stream = torch.cuda.current_stream(x_init.device).cuda_stream
         _lib.check(self._lib.cfs_solve_batch_device(self._h, C.byref(i), C.byref(o), C.c_void_p(stream)))
         return out
+
+    # ---- clearance audit between the waypoints ---------------------------------------------------------
+    def _check_audit(self, substeps):
+        S = _substeps(substeps)
+        if getattr(self, "_meshes", None):
+            raise ValueError("the clearance audit measures line obstacles only: this handle has mesh obstacles")
+        return S
+
+    def clearance(self, x_, u, xR1, obs, substeps=16):
+        """Clearance of B trajectories (x_, u as a solve returns them; xR1, obs as given to it) along the motion between the
+        waypoints, `substeps` samples per interval (cfs_clearance, include/cfs_hip.h); host arrays in and out.  Returns a
+        namespace of (B, nobs) arrays dist_wp (min at the waypoints), dist_path (min over all samples), dist_lower (certified
+        lower bound over continuous time), t_path (s) / link_path (1-based) of the first path minimum, and short_by (B,) =
+        max_j(margin_j - dist_path[:, j]): how far the motion falls short of the handle's margins (<= 0: it keeps them)."""
+        S = self._check_audit(substeps)
+        x_, u, xR1, obs = _f64(x_), _f64(u), _f64(xR1), _f64(obs)
+        B = x_.shape[0]
+        if x_.shape != (B, self.nx) or u.shape != (B, self.nn) or xR1.shape != (B, self.ns):
+            raise ValueError(f"x_, u, xR1 must have shapes {(B, self.nx)}, {(B, self.nn)}, {(B, self.ns)}, not {x_.shape}, {u.shape}, {xR1.shape}")
+        self._check_obs(obs, B)
+        z = lambda dt=np.float64: np.zeros((B, self.nobs), dt)  # noqa: E731
+        r = SimpleNamespace(dist_wp=z(), dist_path=z(), dist_lower=z(), t_path=z(), link_path=z(np.int32))
+        _lib.check(self._lib.cfs_clearance(self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs), _ptr(r.dist_wp), _ptr(r.dist_path),
+                                           _ptr(r.dist_lower), _ptr(r.t_path), _ptr(r.link_path)))
+        r.short_by = (self.margin[None, :] - r.dist_path).max(axis=1)
+        return r
+
+    def alloc_clearance(self, B, device):
+        """Device-resident output buffers (torch CUDA tensors) for clearance_device."""
+        z = lambda dt=torch.float64: torch.zeros(B, self.nobs, dtype=dt, device=device)  # noqa: E731
+        return SimpleNamespace(dist_wp=z(), dist_path=z(), dist_lower=z(), t_path=z(), link_path=z(torch.int32))
+
+    def clearance_device(self, x_, u, xR1, obs, substeps=16, out=None, stream=None):
+        """clearance() on torch CUDA tensors; enqueues on `stream` (default: torch's current stream) and returns without
+        synchronising (cfs_clearance_device).  out: an alloc_clearance namespace to write into."""
+        S = self._check_audit(substeps)
+        B = x_.shape[0]
+        for t in (x_, u, xR1, obs):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+        if tuple(x_.shape) != (B, self.nx) or tuple(u.shape) != (B, self.nn) or tuple(xR1.shape) != (B, self.ns):
+            raise ValueError(f"x_, u, xR1 must have shapes {(B, self.nx)}, {(B, self.nn)}, {(B, self.ns)}")
+        self._check_obs(obs, B)
+        if out is None:
+            out = self.alloc_clearance(B, x_.device)
+        for t, dt in ((out.dist_wp, torch.float64), (out.dist_path, torch.float64), (out.dist_lower, torch.float64),
+                      (out.t_path, torch.float64), (out.link_path, torch.int32)):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (B, self.nobs)
+        cur = torch.cuda.current_stream(x_.device)
+        sp = cur.cuda_stream if stream is None else int(stream)
+        _lib.check(self._lib.cfs_clearance_device(self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs), _ptr(out.dist_wp),
+                                                  _ptr(out.dist_path), _ptr(out.dist_lower), _ptr(out.t_path), _ptr(out.link_path),
+                                                  C.c_void_p(sp)))
+        if sp == cur.cuda_stream:
+            ts = cur
+        else:                            # pointer 0 is the default stream: ExternalStream does not wrap it
+            ts = torch.cuda.default_stream(x_.device) if sp == 0 else torch.cuda.ExternalStream(sp, device=x_.device)
+        with torch.cuda.stream(ts):      # short_by on the same stream, after the audit
+            out.short_by = (self._margin_on(x_.device)[None, :] - out.dist_path).amax(dim=1)
+        return out
+
+    def _margin_on(self, device):
+        """the handle's margins as a tensor on `device` (uploaded once: no copy is enqueued by later audits)"""
+        cache = self.__dict__.setdefault("_margin_dev", {})
+        if device not in cache:
+            cache[device] = torch.tensor(self.margin, dtype=torch.float64, device=device)
+        return cache[device]
 
     # ---- CHOMP (row f4) ------------------------------------------------------------------------------------
     def chomp(self, x_init, xR1, ff, caug, obs, u0, D, epsilon):
@@ -654,8 +728,11 @@ class _SolverBase:
     MARGIN_KEY = "epsilon"
 
     def __init__(self, obs, sys_info, ROBOT="M16iB", device=None, jacobian="fd_literal", on_infeasible="stop", soft_weight=None,
-                 joint_limits=None):
+                 joint_limits=None, audit=None):
         """jacobian: "fd_literal" (num_jac.m, the default) | "analytic" (CFSBatch).
+        audit: None (the default: results are exactly those without the argument) | an integer S in 1..64: after optimizer(),
+        .clearance holds CFSBatch.clearance of the returned trajectory with S sub-steps per interval (its one problem: arrays of
+        shape (nobs,), short_by a float); line obstacles only.
         joint_limits: None (the default) | "robot" | an (njoint, 2) array of [lo, hi] (CFSBatch); get_con then has the position rows.
         on_infeasible: "stop" (the default) | "soften" with soft_weight= (CFSBatch); after optimizer(), viol_all and n_soft.
         obs{j}["l"] may be 3x2xH (shape (3, 2, H): the obstacle's axis at waypoints 1..H); any such entry makes the handle
@@ -663,6 +740,10 @@ class _SolverBase:
         _jacobian_code(jacobian)
         _infeasible_args(on_infeasible, soft_weight)
         _joint_limits_array(joint_limits, sys_info.robot, int(sys_info.njoint))
+        self.audit = None if audit is None else _substeps(audit, "audit")
+        if self.audit is not None and obs_meshes(obs):
+            raise ValueError("audit= measures line obstacles only: the obs cell holds mesh obstacles")
+        self.clearance = None
         if on_infeasible == "soften" and obs_meshes(obs):
             raise ValueError('on_infeasible="soften" does not support mesh obstacles')
         self._moving = obs_moving(obs)
@@ -711,6 +792,10 @@ class _SolverBase:
         self.viol_all, self.n_soft = r.viol_all[0, :n], int(r.n_soft[0])
         self.eval.cost_new = float(r.cost_all[0, n - 1]) if n > 0 else float(self.sys_info.caug)
         self.eval.x_ = self.x_
+        if self.audit is not None:
+            c = self._batch.clearance(r.x_, r.u, xR1, obs, substeps=self.audit)
+            self.clearance = SimpleNamespace(dist_wp=c.dist_wp[0], dist_path=c.dist_path[0], dist_lower=c.dist_lower[0],
+                                             t_path=c.t_path[0], link_path=c.link_path[0], short_by=float(c.short_by[0]))
         if self.status == 0:
             print(f"Converged at step{self.iter_O}")  # EVAL.m:66
         elif self.status == 1:
@@ -733,7 +818,9 @@ class CHOMP_FANUC:
     """Lib/CHOMP_FANUC.m -- ``CHOMP_FANUC(obs_, sys_info, uref, ROBOT).optimizer()``.  ``obs_`` is the reference's cell:
     ``obs_[0] = dict(num_obs=n)`` followed by the n obstacles (``l``, ``D``, ``epsilon``) (M16iB/CHOMP.m:26-29)."""
 
-    def __init__(self, obs, sys_info, uu, ROBOT="M16iB", device=None):
+    def __init__(self, obs, sys_info, uu, ROBOT="M16iB", device=None, audit=None):
+        if audit is not None:
+            raise ValueError("CHOMP_FANUC has no clearance audit: audit= is an option of CFS_FANUC and PSGCFS_FANUC")
         self.obs, self.sys_info, self.ROBOT = obs, sys_info, ROBOT
         if getattr(sys_info.robot, "name", ROBOT) != ROBOT:
             raise ValueError(f"sys_info.robot is {sys_info.robot.name!r} but ROBOT={ROBOT!r}")
