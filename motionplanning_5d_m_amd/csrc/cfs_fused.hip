@@ -56,6 +56,14 @@ constexpr int MV_BATCH = 16;             // QQ*u: loads in flight per thread
 #ifndef CFS_PR
 #define CFS_PR 64                        // columns of each inverse-Gram row kept in registers
 #endif
+#ifndef CFS_P_LDS
+#define CFS_P_LDS 0                      // this tier keeps the first CFS_PR columns of each inverse-Gram row in LDS, not in registers (Makefile)
+#endif
+#if CFS_P_LDS
+// ... in its kernels of at most this many rows: the 256-row kernels' block (32 KB at 16 columns) would push every shape they serve
+// out of half a CU, so they keep the columns in registers
+constexpr int P_LDS_MAX_QB = 160;
+#endif
 static_assert(CFS_PR % 8 == 0 && CFS_PR >= 8, "register-resident P columns come in chunks of 8");
 constexpr int FT = 256;                  // threads per workgroup
 constexpr double DEP_TOL_F = 1e-8;       // dependent if delta <= tol * n'H^{-1}n: above the eps*cond(H) noise floor of Y = H^{-1}N
@@ -322,7 +330,11 @@ __device__ __forceinline__ double gram_ident(int ca, int cp, const double *g, in
 // tail layout: ptail[(b-PR)*QB + a] (thread a reads consecutive addresses).  Active constraints occupy
 // SLOTS of [0,qhi); a freed slot keeps a (numerically) zero row and column, so whole 8-column chunks are
 // processed unguarded and no column is ever written through a runtime register index.
+#if CFS_P_LDS
+template <int PR, int QB, bool IN_LDS = false>   // (true: the LDS variant below)
+#else
 template <int PR, int QB>
+#endif
 struct PRow {
     static constexpr int TU = CFS_TU;    // tail columns loaded per batch
     double v[PR];
@@ -429,9 +441,136 @@ struct PRow {
         for (; b < q; ++b) dst[b] = ptail[(b - PR) * QB + a];
     }
 };
+#if CFS_P_LDS
+// LDS variant (CFS_P_LDS tiers, kernels of at most P_LDS_MAX_QB rows): columns [0,PR) of row a live in LDS at pl[b * QB + a]
+// instead of 2 PR registers of every lane --
+// column-major by slot like the tail, so the lanes of a wavefront hit consecutive banks.  Row a is read and written by thread a
+// alone (no ordering of its own), a chunk's eight loads are issued together (one LDS latency per chunk), and every expression is
+// the register variant's, in its order: the same numbers.  The block aliases the linearisation scratch (fused_layout): P is
+// zeroed at every QP setup, in the phase that resets the row vectors next to it.
+template <int PR, int QB>
+struct PRow<PR, QB, true> {
+    static constexpr int TU = CFS_TU;    // tail columns loaded per batch
+    double *pl;
+    __device__ __forceinline__ void zero(double *ptail, int a, int q)
+    {
+        if (a < QB) {
+#pragma unroll
+            for (int b = 0; b < PR; ++b) pl[b * QB + a] = 0.0;
+        }
+        for (int b = PR; b < q; ++b) ptail[(b - PR) * QB + a] = 0.0;
+    }
+    __device__ __forceinline__ double dot(const double *vec, const double *ptail, int a, int q) const
+    {
+        double s = 0.0;
+#pragma unroll
+        for (int b0 = 0; b0 < PR; b0 += 8)
+            if (b0 < q) {
+                double t[8], w[8];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) { t[jj] = pl[(b0 + jj) * QB + a]; w[jj] = vec[b0 + jj]; }
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) s += t[jj] * w[jj];
+            }
+        int b = PR;
+        for (; b + TU <= q; b += TU) {
+            double t[TU];
+#pragma unroll
+            for (int jj = 0; jj < TU; ++jj) t[jj] = ptail[(b + jj - PR) * QB + a];
+#pragma unroll
+            for (int jj = 0; jj < TU; ++jj) s += t[jj] * vec[b + jj];
+        }
+        for (; b < q; ++b) s += ptail[(b - PR) * QB + a] * vec[b];
+        return s;
+    }
+    __device__ __forceinline__ void axpy(double alpha, const double *vec, double *ptail, int a, int q)
+    {
+#pragma unroll
+        for (int b0 = 0; b0 < PR; b0 += 8)
+            if (b0 < q) {
+                double t[8], w[8];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) { t[jj] = pl[(b0 + jj) * QB + a]; w[jj] = vec[b0 + jj]; }
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) t[jj] += alpha * w[jj];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) pl[(b0 + jj) * QB + a] = t[jj];
+            }
+        int b = PR;
+        for (; b + TU <= q; b += TU) {
+            double t[TU];
+#pragma unroll
+            for (int jj = 0; jj < TU; ++jj) t[jj] = ptail[(b + jj - PR) * QB + a];
+#pragma unroll
+            for (int jj = 0; jj < TU; ++jj) ptail[(b + jj - PR) * QB + a] = t[jj] + alpha * vec[b + jj];
+        }
+        for (; b < q; ++b) ptail[(b - PR) * QB + a] += alpha * vec[b];
+    }
+    __device__ __forceinline__ void axpy_mask(double alpha, const double *vec, const double *mask, double *ptail, int a, int q)
+    {
+#pragma unroll
+        for (int b0 = 0; b0 < PR; b0 += 8)
+            if (b0 < q) {
+                double t[8], w[8], m[8];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) { t[jj] = pl[(b0 + jj) * QB + a]; w[jj] = vec[b0 + jj]; m[jj] = mask[b0 + jj]; }
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) t[jj] = (t[jj] + alpha * w[jj]) * m[jj];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) pl[(b0 + jj) * QB + a] = t[jj];
+            }
+        int b = PR;
+        for (; b + TU <= q; b += TU) {
+            double t[TU];
+#pragma unroll
+            for (int jj = 0; jj < TU; ++jj) t[jj] = ptail[(b + jj - PR) * QB + a];
+#pragma unroll
+            for (int jj = 0; jj < TU; ++jj) ptail[(b + jj - PR) * QB + a] = (t[jj] + alpha * vec[b + jj]) * mask[b + jj];
+        }
+        for (; b < q; ++b) ptail[(b - PR) * QB + a] = (ptail[(b - PR) * QB + a] + alpha * vec[b]) * mask[b];
+    }
+    __device__ __forceinline__ void set_scaled(double alpha, const double *vec, double *ptail, int a, int q)
+    {
+#pragma unroll
+        for (int b0 = 0; b0 < PR; b0 += 8)
+            if (b0 < q) {
+                double w[8];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) w[jj] = vec[b0 + jj];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) pl[(b0 + jj) * QB + a] = alpha * w[jj];
+            }
+        for (int b = PR; b < q; ++b) ptail[(b - PR) * QB + a] = alpha * vec[b];
+    }
+    __device__ __forceinline__ void store(double *dst, const double *ptail, int a, int q) const
+    {
+#pragma unroll
+        for (int b0 = 0; b0 < PR; b0 += 8)
+            if (b0 < q) {
+                double t[8];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) t[jj] = pl[(b0 + jj) * QB + a];
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) dst[b0 + jj] = t[jj];
+            }
+        int b = PR;
+        for (; b + TU <= q; b += TU) {
+            double t[TU];
+#pragma unroll
+            for (int jj = 0; jj < TU; ++jj) t[jj] = ptail[(b + jj - PR) * QB + a];
+#pragma unroll
+            for (int jj = 0; jj < TU; ++jj) dst[b + jj] = t[jj];
+        }
+        for (; b < q; ++b) dst[b] = ptail[(b - PR) * QB + a];
+    }
+};
+#endif
 
 struct FusedLayout {      // LDS offsets in doubles, computed identically on host and device
     int rb, ob, x, u, qu, g, rhs, xs, up, wb, zb, d, r, rho, lam, prow, act, fre, prev, flag, slot, code, red, small, mx, racc, cost, ptail, lin, y, total_fixed;
+#if CFS_P_LDS
+    int pl;               // QB * PR doubles: columns [0,PR) of P as [b][a] (PRow); part of the fixed footprint, aliased by the linearisation
+#endif
 };
 // lim (LIM kernels): flag / slot cover the position rows too (nobs*H + 6HN), code only the collision rows (the only codes the
 // kernel reads back), and the small block carries [lo; hi] after the margins.  The footprint is never larger than without lim.
@@ -471,6 +610,10 @@ __host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int
     L.slot = o; o += (nobs * H + (lim ? 6 : 4) * HN + 3) / 4;   // constraint -> slot + 1 (0: inactive), ushort; reset at every QP setup
     L.ptail = o;                           // (tail columns of P live in global scratch)
     o = (o + 1) & ~1;
+#if CFS_P_LDS
+    L.pl = o;                              // where the Y rows of the other tiers start: this tier's kernels (H = I) have none
+    if (QB <= P_LDS_MAX_QB) o += QB * PR;
+#endif
     L.y = o;
     L.total_fixed = o;
     return L;
@@ -623,7 +766,15 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
         __syncthreads();
     }
 
+#if CFS_P_LDS
+    PRow<PR, QB, QB <= P_LDS_MAX_QB> Pr;                   // row `tid` of P = (N'H^{-1}N)^{-1}, its first PR columns in LDS
+#else
     PRow<PR, QB> Pr;                                       // row `tid` of P = (N'H^{-1}N)^{-1}
+#endif
+#if CFS_P_LDS
+    static_assert(IDENT, "the P block takes the place of the Y rows: identity Hessian only");
+    if constexpr (QB <= P_LDS_MAX_QB) Pr.pl = lds + L.pl;
+#endif
     int prev_q = 0;                                        // slots [0, prev_q) of s_prev hold the previous QP's final active rows
 
     while (!done) {
