@@ -512,6 +512,37 @@ int cfs_clearance_device(cfs_problem *p, int B, int substeps, const double *x_, 
 int cfs_clearance(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
                   double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path);
 
+/* ---- clearance audit with mesh obstacles -----------------------------------------------------------------
+ * The audit above for a handle whose last nmesh >= 1 obstacles are meshes (cfs_problem_set_meshes; such a handle is static).  Time
+ * line, samples, first-minimum rule, t_path and link_path are the contract above word for word; all outputs are B x nobs in the
+ * handle's obstacle order (line obstacles first, the last nmesh columns are the meshes).  obs: B x nobs x 6, the rows of the mesh
+ * obstacles are not read (as in every solve of such a handle).
+ *   line columns   bit for bit what cfs_clearance returns on a line-only handle of the same robot, H, delta_t and rows;
+ *   mesh columns   the distance at a sample is cfs_dist_arm_mesh's: the same FK, the mesh contract above (exact minimum over the
+ *                  triangles, ties to the smaller axis parameter), the near-zero surrogate of dist_arm_surf_200i.m:22-24, first
+ *                  minimum over the links;
+ *   dist_lower     the same formula with v_obs = 0 in the mesh columns.  The GUARANTEE carries over unchanged: the distance from
+ *                  a segment to a fixed closed set (a union of triangles) is 1-Lipschitz in the segment's end points, and that is
+ *                  the only property of the obstacle the bound uses; a faceted surface changes which triangle is closest between
+ *                  two samples, not how fast the distance can change;
+ *   tri_path       B x nobs: the index, in the caller's triangle list (cfs_mesh_create / the STL's order), of a closest triangle
+ *                  of link link_path at the dist_path sample; -1 in line columns.  Where several triangles are equally close (a
+ *                  shared edge or vertex) any one of them may be reported; the distances do not depend on which.
+ * dist_wp, dist_path and dist_lower do not depend on the order in which a hierarchy is traversed.  Deterministic (no atomics); a
+ * problem's results depend on neither B nor its position in the batch.  Reads the handle's constants and meshes only, changes
+ * nothing, independent of mode, Jacobian mode, infeasible-QP policy and joint limits.  The first audit of a handle, and the first
+ * with more substeps than any before, allocates the per-sample workspace (max_batch x nmesh x (H*substeps + 1) records) and
+ * synchronises the device once; later audits enqueue only.
+ * CFS_ERR_INVALID_ARG, nothing written: NULL handle or array, B outside 1..max_batch, substeps outside 1..64, a handle without
+ * meshes (use cfs_clearance).  cfs_clearance and cfs_clearance_device keep refusing handles with meshes.
+ * cfs_clearance_mesh_device: DEVICE pointers, enqueued on `stream`, no synchronisation.  cfs_clearance_mesh: HOST pointers,
+ * synchronises. */
+int cfs_clearance_mesh_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1,
+                              const double *obs, double *dist_wp, double *dist_path, double *dist_lower, double *t_path,
+                              int *link_path, int *tri_path, void *stream);
+int cfs_clearance_mesh(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
+                       double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, int *tri_path);
+
 /* ---- developer / test entry points -------------------------------------------------------------------
  * No caller of the path needs these; they exist so that every shortcut the solver takes can be switched off and compared
  * under pytest (tests/test_gpu_shortcuts.py), and for the cycle-stamp / step-trace probes under tools/.  All state is per
@@ -524,6 +555,8 @@ int cfs_clearance(cfs_problem *p, int B, int substeps, const double *x_, const d
 #define CFS_DBG_NO_PRUNE 32         /* num_jac evaluates every link at every evaluation point (no candidate pruning)                    */
 #define CFS_DBG_NO_AUTO_ORDER 64    /* no automatic launch order                                                                       */
 #define CFS_DBG_TIER_W1 128         /* one workgroup per compute unit (64 register-resident columns of the inverse Gram matrix)         */
+#define CFS_DBG_CLEAR_NO_BOUND 256  /* cfs_clearance_mesh*: every link's hierarchy query starts unbounded (not from the running minimum)   */
+#define CFS_DBG_CLEAR_SEED 512      /* cfs_clearance_mesh*: waypoint poses first, sub-samples seeded with their winning triangles       */
 /* mask: OR of CFS_DBG_*; warm_max: largest previous active set a warm start takes (0 = default: 24 rows for CFS_FANUC, the
  * register-resident columns for PSGCFS_FANUC; <= 64); polish_tol: relative drift of an active row at the optimum that
  * triggers the projection (<= 0 = default 1e-11).  Applies to the following solves / pieces of this handle. */

@@ -207,10 +207,13 @@ SYMBOLS = [
     ("cfs_problem_get_joint_limits", C.c_int, [_P, C.POINTER(C.c_int), _P, _P]),
     ("cfs_clearance_device", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("cfs_clearance", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("cfs_clearance_mesh_device", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("cfs_clearance_mesh", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)
-DBG = {"no_refine": 2, "no_warm_start": 8, "no_certificate": 16, "no_prune": 32, "no_auto_order": 64, "tier_w1": 128}
+DBG = {"no_refine": 2, "no_warm_start": 8, "no_certificate": 16, "no_prune": 32, "no_auto_order": 64, "tier_w1": 128,
+       "clear_no_bound": 256, "clear_seed": 512}
 
 _lib = None
 

@@ -188,6 +188,10 @@ struct cfs_problem {
     DevBuf<DevMesh> meshes_d;
     DevBuf<double> st_cost, m_ends, m_base, m_shift, m_upper, m_pd, m_pnd;
     DevBuf<int> st_done, m_tri, m_near, m_pi;
+    // cfs_clearance_mesh*: per-sample workspace for cm_S sub-steps (grown by the first audit that needs more) and rho on the device
+    DevBuf<double> cm_d, cm_L, cm_rho;
+    DevBuf<int> cm_lk, cm_tri, cm_seed;
+    int cm_S = 0;
     // developer / test switches (cfs_debug_*, include/cfs_hip.h): per handle, no process-wide state
     int dbg_mask = 0, dbg_warm_max = 0;
     double dbg_polish_tol = 1e-11;        // = the constraint scan's own feasibility tolerance
@@ -208,6 +212,11 @@ struct cfs_problem {
     bool prof = false;
     std::vector<hipEvent_t> ev;   // 4 per profiled solve: gemm start/stop, fused start/stop
     std::vector<hipEvent_t> ev_free;   // recycled events: none is created inside a timed region once the pool is warm
+    void release_clear_mesh()
+    {
+        cm_d.release(); cm_L.release(); cm_rho.release(); cm_lk.release(); cm_tri.release(); cm_seed.release();
+        cm_S = 0;
+    }
     void release_all()
     {
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
@@ -220,7 +229,7 @@ struct cfs_problem {
         grad.release(); Yg.release(); noise_row.release(); order.release(); okey.release(); order_user.release();
         linkid.release(); pool_flag.release(); meshes_d.release(); st_cost.release(); st_done.release();
         m_ends.release(); m_base.release(); m_shift.release(); m_tri.release(); m_near.release(); m_upper.release();
-        m_pd.release(); m_pnd.release(); m_pi.release();
+        m_pd.release(); m_pnd.release(); m_pi.release(); release_clear_mesh();
         stamps.release(); trace.release(); u_log.release(); soft_viol.release(); soft_n.release();
     }
 };
@@ -862,7 +871,7 @@ int cfs_debug_set_options(cfs_problem *p, int mask, int warm_max, double polish_
 {
     if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
     const int known = CFS_DBG_NO_REFINE | CFS_DBG_NO_WARM_START | CFS_DBG_NO_CERTIFICATE | CFS_DBG_NO_PRUNE | CFS_DBG_NO_AUTO_ORDER |
-                      CFS_DBG_TIER_W1;
+                      CFS_DBG_TIER_W1 | CFS_DBG_CLEAR_NO_BOUND | CFS_DBG_CLEAR_SEED;
     if (mask & ~known) return fail(CFS_ERR_INVALID_ARG, "unknown option bits 0x%x", mask & ~known);
     if (warm_max < 0 || warm_max > 64) return fail(CFS_ERR_INVALID_ARG, "warm_max %d outside 0..64", warm_max);
     p->dbg_mask = mask; p->dbg_warm_max = warm_max;
@@ -1082,7 +1091,7 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
     }
     p->meshes_d.release(); p->st_cost.release(); p->st_done.release();
     p->m_ends.release(); p->m_base.release(); p->m_shift.release(); p->m_tri.release(); p->m_near.release(); p->m_upper.release();
-    p->m_pd.release(); p->m_pnd.release(); p->m_pi.release();
+    p->m_pd.release(); p->m_pnd.release(); p->m_pi.release(); p->release_clear_mesh();
     p->nmesh = 0;
     if (nmesh > 0) {
         size_t we, wb, ws, wn, wpd, wpi, wpn;
@@ -1483,6 +1492,7 @@ int cfs_clearance_device(cfs_problem *p, int B, int substeps, const double *x_, 
     cp.move = moving(p) ? 1 : 0; cp.dt = p->d.robot.delta_t;
     cp.x_ = x_; cp.u = u; cp.xR1 = xR1; cp.obs = obs;
     cp.dist_wp = dist_wp; cp.dist_path = dist_path; cp.dist_lower = dist_lower; cp.t_path = t_path; cp.link_path = link_path;
+    cp.obs_stride = (int)obs_rows(p); cp.out_stride = p->d.nobs;
     memcpy(cp.rho, p->rho, sizeof cp.rho);
     HIPCHK(launch_clearance(cp, reinterpret_cast<hipStream_t>(stream)));
     return CFS_SUCCESS;
@@ -1509,6 +1519,85 @@ int cfs_clearance(cfs_problem *p, int B, int substeps, const double *x_, const d
     HIPCHK(hipStreamSynchronize(nullptr));
     st.down(dist_wp, d_wp, n); st.down(dist_path, d_path, n); st.down(dist_lower, d_low, n); st.down(t_path, d_t, n);
     st.down(link_path, d_lk, n);
+    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
+    return CFS_SUCCESS;
+}
+
+// ---- clearance audit with mesh obstacles (cfs_clear_mesh.hip) ---------------------------------------------------------------
+static int check_clearance_mesh(cfs_problem *p, int B, int substeps, const void *const *arrays, int n)
+{
+    int rc = check_batch(p, B);
+    if (rc) return rc;
+    if (substeps < 1 || substeps > 64) return fail(CFS_ERR_INVALID_ARG, "substeps=%d outside 1..64", substeps);
+    for (int i = 0; i < n; ++i)
+        if (!arrays[i]) return fail(CFS_ERR_INVALID_ARG, "NULL array");
+    if (p->nmesh < 1) return fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh needs a handle with mesh obstacles (cfs_problem_set_meshes): use cfs_clearance");
+    return CFS_SUCCESS;
+}
+
+int cfs_clearance_mesh_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1,
+                              const double *obs, double *dist_wp, double *dist_path, double *dist_lower, double *t_path,
+                              int *link_path, int *tri_path, void *stream)
+{
+    const void *arrays[] = {x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, tri_path};
+    int rc = check_clearance_mesh(p, B, substeps, arrays, 10);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    const int nline = p->d.nobs - p->nmesh;
+    if (substeps > p->cm_S) {                        // grow the workspace (hipFree waits for whatever still reads the old one)
+        const size_t G = (size_t)p->d.H * substeps + 1, mb = (size_t)p->d.max_batch;
+        p->release_clear_mesh();
+        HIPCHK(p->cm_d.alloc(mb * G * p->nmesh)); HIPCHK(p->cm_L.alloc(mb * G));
+        HIPCHK(p->cm_lk.alloc(mb * G * p->nmesh)); HIPCHK(p->cm_tri.alloc(mb * G * p->nmesh));
+        HIPCHK(p->cm_seed.alloc(mb * (size_t)(p->d.H + 1) * p->d.njoint * p->nmesh));
+        HIPCHK(p->cm_rho.alloc(CFS_MAX_LINKS * CFS_MAX_LINKS));
+        HIPCHK(hipMemcpy(p->cm_rho.p, p->rho, sizeof p->rho, hipMemcpyHostToDevice));
+        p->cm_S = substeps;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (nline > 0) {                                 // the line columns: cfs_clearance's kernel on the first nline rows and columns
+        ClearParams cp;
+        cp.rb = p->rb.p; cp.B = B; cp.H = p->d.H; cp.nj = p->d.njoint; cp.nobs = nline; cp.S = substeps;
+        cp.move = 0; cp.dt = p->d.robot.delta_t;
+        cp.x_ = x_; cp.u = u; cp.xR1 = xR1; cp.obs = obs;
+        cp.dist_wp = dist_wp; cp.dist_path = dist_path; cp.dist_lower = dist_lower; cp.t_path = t_path; cp.link_path = link_path;
+        cp.obs_stride = p->d.nobs; cp.out_stride = p->d.nobs;
+        memcpy(cp.rho, p->rho, sizeof cp.rho);
+        HIPCHK(launch_clearance(cp, s));
+    }
+    ClearMeshParams cm;
+    cm.rb = p->rb.p; cm.B = B; cm.H = p->d.H; cm.nj = p->d.njoint; cm.nobs = p->d.nobs; cm.nmesh = p->nmesh; cm.S = substeps;
+    cm.opt = ((p->dbg_mask & CFS_DBG_CLEAR_NO_BOUND) ? 0 : CLEAR_MESH_BOUND) | ((p->dbg_mask & CFS_DBG_CLEAR_SEED) ? CLEAR_MESH_SEED : 0);
+    cm.dt = p->d.robot.delta_t;
+    cm.meshes = p->meshes_d.p;
+    cm.x_ = x_; cm.u = u; cm.xR1 = xR1;
+    cm.dist_wp = dist_wp; cm.dist_path = dist_path; cm.dist_lower = dist_lower; cm.t_path = t_path;
+    cm.link_path = link_path; cm.tri_path = tri_path;
+    cm.ws_d = p->cm_d.p; cm.ws_L = p->cm_L.p; cm.ws_lk = p->cm_lk.p; cm.ws_tri = p->cm_tri.p; cm.ws_seed = p->cm_seed.p;
+    cm.rho = p->cm_rho.p;
+    HIPCHK(launch_clearance_mesh(cm, s));
+    return CFS_SUCCESS;
+}
+
+int cfs_clearance_mesh(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
+                       double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, int *tri_path)
+{
+    const void *arrays[] = {x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, tri_path};
+    int rc = check_clearance_mesh(p, B, substeps, arrays, 10);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    const size_t n = (size_t)B * p->d.nobs;
+    Stage st;
+    const double *d_x = st.up(x_, (size_t)B * p->nx), *d_u = st.up(u, (size_t)B * p->nn), *d_x1 = st.up(xR1, (size_t)B * p->ns);
+    const double *d_obs = st.up(obs, n * 6);
+    double *d_wp = st.up<double>(nullptr, n), *d_path = st.up<double>(nullptr, n), *d_low = st.up<double>(nullptr, n), *d_t = st.up<double>(nullptr, n);
+    int *d_lk = st.up<int>(nullptr, n), *d_tri = st.up<int>(nullptr, n);
+    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
+    rc = cfs_clearance_mesh_device(p, B, substeps, d_x, d_u, d_x1, d_obs, d_wp, d_path, d_low, d_t, d_lk, d_tri, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    st.down(dist_wp, d_wp, n); st.down(dist_path, d_path, n); st.down(dist_lower, d_low, n); st.down(t_path, d_t, n);
+    st.down(link_path, d_lk, n); st.down(tri_path, d_tri, n);
     if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
     return CFS_SUCCESS;
 }

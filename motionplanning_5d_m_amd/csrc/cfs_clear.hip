@@ -20,6 +20,7 @@
 //            words -- updates the lane's running minima (waypoints, all samples with their first arg-min, sub-interval bounds).
 // The parts of an obstacle meet once, after the last pass, in LDS; ties go to the lowest g.  No atomics: every output is a
 // minimum over values that do not depend on P, on B or on the launch, so neither does the result.
+#include "cfs_clear_dev.h"
 #include "cfs_geom_dev.h"
 #include "cfs_host.h"
 #include <algorithm>
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(CLEAR_MAX_P) void cfs_clearance_kernel(ClearParams 
         for (int e = t; e < nn; e += P) s_u[e] = C.u[(size_t)b * nn + e];
         for (int e = t; e < ns; e += P) s_x1[e] = C.xR1[(size_t)b * ns + e];
         const int no = (move ? H : 1) * nobs * 6;
-        for (int e = t; e < no; e += P) s_obs[e] = C.obs[(size_t)b * no + e];
+        for (int e = t; e < no; e += P) s_obs[e] = C.obs[(size_t)b * C.obs_stride * 6 + e];
     }
     __syncthreads();
     const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
@@ -111,9 +112,8 @@ __global__ __launch_bounds__(CLEAR_MAX_P) void cfs_clearance_kernel(ClearParams 
         // ---- phase A: sample g = g0 + t ----
         const int g = g0 + t;
         if (g < G) {
-            const int i = g == 0 ? 0 : (g - 1) / S, k = g == 0 ? 0 : (g - 1) % S + 1;      // g = i*S + k, k = 1..S (g = 0: k = 0)
-            const double *xs = i == 0 ? s_x1 : s_x + (size_t)(i - 1) * ns;                  // state the interval starts from
-            const double tau = (double)k * C.dt / (double)S;
+            int i, k;                                                                       // g = i*S + k, k = 1..S (g = 0: k = 0)
+            clear_sample_ik(g, S, i, k);
             const double *oa = s_obs, *ob = s_obs;                                          // obstacle rows: a + wo (b - a)
             double wo = 0.0;
             if (move) {
@@ -124,10 +124,7 @@ __global__ __launch_bounds__(CLEAR_MAX_P) void cfs_clearance_kernel(ClearParams 
             // one link: its transform from the parent's (none for link 0), then its distance to every obstacle
             double M[12];
             auto link = [&](int kk, const double *par) {
-                double th;
-                if (k == S) th = s_x[(size_t)i * ns + kk];                                  // the waypoint itself: row i of x_
-                else if (k == 0) th = xs[kk];
-                else th = xs[kk] + tau * xs[nj + kk] + tau * tau / 2.0 * s_u[i * nj + kk];
+                const double th = clear_sample_theta(s_x, s_u, s_x1, nj, S, C.dt, i, k, kk);
                 double sn, cs, Mn[12], e6[6];
                 sincos(th - rb->th_off[kk], &sn, &cs);
                 fk_step(rb, kk, sn, cs, par, Mn);
@@ -144,23 +141,8 @@ __global__ __launch_bounds__(CLEAR_MAX_P) void cfs_clearance_kernel(ClearParams 
             };
             link(0, nullptr);
             for (int kk = 1; kk < nj; ++kk) link(kk, M);
-            // arm's share of |d/dtau distance| on sub-interval [g, g+1]: no point of link kk moves faster than
-            // sum_{m<=kk} |v_m| rho[m][kk], and |v_m| is largest at an end of the sub-interval (v is linear in tau)
-            double L = 0.0;
-            if (g < G - 1) {
-                const int i2 = g / S, k2 = g % S;
-                const double *x2 = i2 == 0 ? s_x1 : s_x + (size_t)(i2 - 1) * ns;
-                const double t0 = (double)k2 * C.dt / (double)S, t1 = (double)(k2 + 1) * C.dt / (double)S;
-                for (int kk = 0; kk < nj; ++kk) {
-                    double sum = 0.0;
-                    for (int m = 0; m <= kk; ++m) {
-                        const double v0 = x2[nj + m], uu = s_u[i2 * nj + m];
-                        sum += fmax(fabs(v0 + t0 * uu), fabs(v0 + t1 * uu)) * s_rho[m * CFS_MAX_LINKS + kk];
-                    }
-                    L = fmax(L, sum);
-                }
-            }
-            s_L[t] = L;
+            // arm's share of |d/dtau distance| on sub-interval [g, g+1] (cfs_clear_dev.h)
+            s_L[t] = g < G - 1 ? clear_arm_speed(s_x, s_u, s_x1, s_rho, nj, S, C.dt, g) : 0.0;
         }
         __syncthreads();
         // ---- phase B: obstacle jB, samples [pB*chunk, (pB+1)*chunk) of the pass ----
@@ -192,7 +174,7 @@ __global__ __launch_bounds__(CLEAR_MAX_P) void cfs_clearance_kernel(ClearParams 
             if (r_path[e] < m_path || (r_path[e] == m_path && r_g[e] < m_g)) { m_path = r_path[e]; m_g = r_g[e]; m_lk = r_lk[e]; }
         }
         const int i = m_g == 0 ? 0 : (m_g - 1) / S, k = m_g == 0 ? 0 : (m_g - 1) % S + 1;
-        const size_t o = (size_t)b * nobs + t;
+        const size_t o = (size_t)b * C.out_stride + t;
         C.dist_wp[o] = m_wp;
         C.dist_path[o] = m_path;
         C.dist_lower[o] = m_low;

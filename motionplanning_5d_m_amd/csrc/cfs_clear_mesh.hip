@@ -1,0 +1,152 @@
+// cfs_clear_mesh.hip -- clearance audit against mesh obstacles along the motion between the waypoints (cfs_clearance_mesh_device).
+//
+// The contract is cfs_clear.hip's (time line, samples, first minimum, t_path, link_path, lower bound) with the distance of
+// cfs_dist_arm_mesh: same FK, the exact segment-triangle minimum over the hierarchy (cfs_mesh_dev.h), the near-zero surrogate of
+// dist_arm_surf_200i.m:22-24, first-minimum link.  A mesh does not move, so the bound's v_obs is 0: the distance from a segment to
+// a fixed closed set is 1-Lipschitz in the segment's end points, which is all the argument of DESIGN.md section 17 uses.
+//
+// MI355X mapping.  A sample costs nj * nmesh hierarchy traversals of unequal length -- three orders of
+// magnitude more than a line sample -- so a problem is spread over ceil(G / 64) workgroups instead of one, and the per-sample
+// results travel through a workspace in HBM (B x nmesh x G distances, links, triangles; B x G arm speeds):
+//   sample kernel  one lane per sample, a wavefront per workgroup: the 64 lanes hold consecutive samples of one problem, poses that
+//                  differ by one sub-step, so their traversals take nearly the same path (little divergence, shared L2 lines).  The
+//                  lane walks the links in order (one transform in registers) and queries every mesh per link; its private
+//                  (node, bound) stack is strided in LDS as in cfs_mesh_seg_kernel (64 x 20 x 8 B = 10 KB per workgroup).
+//   scan kernel    one workgroup per (problem, mesh): lanes stride over the samples (consecutive words), keep the waypoint minimum,
+//                  the path minimum with its first arg-min and the sub-interval bounds, and meet once in LDS; ties go to the lowest g.
+// No atomics; every output is a minimum over per-sample values that depend on the sample alone, so neither B nor the position in the
+// batch nor the launch shape changes a bit.
+//
+// Time coherence, two independent switches (ClearMeshParams::opt; both leave every distance bit-identical to cold, unbounded queries
+// because mesh_query returns the lexicographic minimum (distance, axis parameter) over a rigorously pruned set whatever it starts from):
+//   bound  link k's query starts from the incumbent max(running minimum of links < k, 1e-4): a link with nothing closer can neither
+//          become the (first) minimum nor reach the surrogate -- the argument of the solver's candidate pruning;
+//   seed   the H + 1 waypoint poses are queried first, then every sub-sample's query tests the winning triangle of its interval's
+//          start before it descends (seed_tri of mesh_query).
+#include "cfs_clear_dev.h"
+#include "cfs_mesh_dev.h"
+
+namespace {
+
+constexpr int CM_THREADS = 64;                       // sample kernel: one wavefront of consecutive samples
+constexpr int CM_SCAN = 256;
+
+// which samples a launch of the sample kernel covers
+enum { CM_ALL = 0, CM_WAYPOINTS = 1, CM_BETWEEN = 2 };
+
+template <bool BOUND>
+__global__ __launch_bounds__(CM_THREADS) void cfs_clear_mesh_sample_kernel(ClearMeshParams C, int phase)
+{
+    __shared__ int s_stack[MESH_STACK * CM_THREADS];
+    __shared__ float s_lbs[MESH_STACK * CM_THREADS];
+    const int t = threadIdx.x, b = blockIdx.y;
+    const int H = C.H, nj = C.nj, ns = 2 * nj, S = C.S, nmesh = C.nmesh, G = H * S + 1;
+    const int e = blockIdx.x * CM_THREADS + t;
+    int g;                                           // this lane's sample
+    if (phase == CM_ALL) g = e;
+    else if (phase == CM_WAYPOINTS) g = e <= H ? e * S : G;
+    else g = e < H * (S - 1) ? (e / (S - 1)) * S + e % (S - 1) + 1 : G;
+    if (g >= G) return;
+    const double *x = C.x_ + (size_t)b * H * ns, *u = C.u + (size_t)b * H * nj, *x1 = C.xR1 + (size_t)b * ns;
+    const DevRobot *rb = C.rb;
+    int i, k;
+    clear_sample_ik(g, S, i, k);
+    // workspace rows of this sample: [b][mesh][g]; seeds [b][waypoint 0..H][link][mesh] (hierarchy order, -1: none)
+    double *w_d = C.ws_d + (size_t)b * nmesh * G + g;
+    int *w_lk = C.ws_lk + (size_t)b * nmesh * G + g, *w_tri = C.ws_tri + (size_t)b * nmesh * G + g;
+    const bool seeded = phase == CM_BETWEEN, seeding = phase == CM_WAYPOINTS;
+    // a sub-sample g = i*S + k, 0 < k < S, starts from waypoint pose i (g = 0 is pose 0, g = i*S is pose i)
+    int *w_seed = C.ws_seed + ((size_t)b * (H + 1) + (seeding ? g / S : i)) * nj * nmesh;
+    for (int jm = 0; jm < nmesh; ++jm) { w_d[(size_t)jm * G] = INFINITY; w_lk[(size_t)jm * G] = 0; w_tri[(size_t)jm * G] = -1; }
+    double M[12];
+    // one link: its transform from the parent's (none for link 0), then its distance to every mesh
+    auto link = [&](int kk, const double *par) {
+        const double th = clear_sample_theta(x, u, x1, nj, S, C.dt, i, k, kk);
+        double sn, cs, Mn[12], e6[6];
+        sincos(th - rb->th_off[kk], &sn, &cs);
+        fk_step(rb, kk, sn, cs, par, Mn);
+#pragma unroll
+        for (int q = 0; q < 12; ++q) M[q] = Mn[q];
+        link_ends(rb, kk, M, e6);
+        for (int jm = 0; jm < nmesh; ++jm) {
+            const double cur = w_d[(size_t)jm * G];
+            const int seed = seeded ? w_seed[kk * nmesh + jm] : -1;
+            Best bq;
+            mesh_query<CM_THREADS, false>(C.meshes[jm], e6, e6 + 3, seed, s_stack + t, s_lbs + t, bq, nullptr,
+                                          BOUND ? fmax(cur, 0.0001) : INFINITY);
+            if (seeding) w_seed[kk * nmesh + jm] = bq.tri;
+            if (bq.tri < 0) continue;                // nothing closer than the bound: not the minimum
+            const double dis = with_surrogate(bq, e6);
+            if (dis < cur) {                         // first minimum wins
+                w_d[(size_t)jm * G] = dis; w_lk[(size_t)jm * G] = kk + 1; w_tri[(size_t)jm * G] = C.meshes[jm].orig[bq.tri];
+            }
+        }
+    };
+    link(0, nullptr);
+#pragma unroll 1
+    for (int kk = 1; kk < nj; ++kk) link(kk, M);
+    if (g < G - 1) C.ws_L[(size_t)b * G + g] = clear_arm_speed(x, u, x1, C.rho, nj, S, C.dt, g);
+}
+
+__global__ __launch_bounds__(CM_SCAN) void cfs_clear_mesh_scan_kernel(ClearMeshParams C)
+{
+    __shared__ double r_wp[CM_SCAN], r_path[CM_SCAN], r_low[CM_SCAN];
+    __shared__ int r_g[CM_SCAN];
+    const int t = threadIdx.x, jm = blockIdx.x, b = blockIdx.y;
+    const int S = C.S, G = C.H * S + 1, nline = C.nobs - C.nmesh;
+    const double *d = C.ws_d + ((size_t)b * C.nmesh + jm) * G, *L = C.ws_L + (size_t)b * G;
+    double a_wp = INFINITY, a_path = INFINITY, a_low = INFINITY;
+    int a_g = 0;
+    for (int g = t; g < G; g += CM_SCAN) {           // g rises: a strict < keeps the lane's lowest arg-min
+        const double d0 = d[g];
+        if (d0 < a_path) { a_path = d0; a_g = g; }
+        if (g > 0 && g % S == 0) a_wp = fmin(a_wp, d0);
+        if (g + 1 < G) a_low = fmin(a_low, (d0 + d[g + 1]) / 2.0 - L[g] * C.dt / (2.0 * (double)S));   // v_obs = 0
+    }
+    r_wp[t] = a_wp; r_path[t] = a_path; r_low[t] = a_low; r_g[t] = a_g;
+    __syncthreads();
+    if (t == 0) {                                    // the lanes meet: lowest distance, then lowest g
+        double m_wp = INFINITY, m_path = INFINITY, m_low = INFINITY;
+        int m_g = 0;
+        for (int q = 0; q < CM_SCAN; ++q) {
+            m_wp = fmin(m_wp, r_wp[q]);
+            m_low = fmin(m_low, r_low[q]);
+            if (r_path[q] < m_path || (r_path[q] == m_path && r_g[q] < m_g)) { m_path = r_path[q]; m_g = r_g[q]; }
+        }
+        int i, k;
+        clear_sample_ik(m_g, S, i, k);
+        const size_t o = (size_t)b * C.nobs + nline + jm, w = ((size_t)b * C.nmesh + jm) * G + m_g;
+        C.dist_wp[o] = m_wp;
+        C.dist_path[o] = m_path;
+        C.dist_lower[o] = m_low;
+        C.t_path[o] = ((double)i + (double)k / (double)S) * C.dt;
+        C.link_path[o] = C.ws_lk[w];
+        C.tri_path[o] = C.ws_tri[w];
+    }
+    if (jm == 0)                                     // line columns have no triangle
+        for (int j = t; j < nline; j += CM_SCAN) C.tri_path[(size_t)b * C.nobs + j] = -1;
+}
+
+template <bool BOUND>
+void launch_samples(const ClearMeshParams &p, int phase, int n, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(cfs_clear_mesh_sample_kernel<BOUND>, dim3((n + CM_THREADS - 1) / CM_THREADS, p.B), dim3(CM_THREADS), 0, s, p, phase);
+}
+
+}  // namespace
+
+hipError_t launch_clearance_mesh(const ClearMeshParams &p, hipStream_t s)
+{
+    const int G = p.H * p.S + 1;
+    const bool bound = (p.opt & CLEAR_MESH_BOUND) != 0;
+    auto samples = [&](int phase, int n) { if (bound) launch_samples<true>(p, phase, n, s); else launch_samples<false>(p, phase, n, s); };
+    if (p.opt & CLEAR_MESH_SEED) {
+        samples(CM_WAYPOINTS, p.H + 1);
+        samples(CM_BETWEEN, p.H * (p.S - 1));
+    } else {
+        samples(CM_ALL, G);
+    }
+    hipLaunchKernelGGL(cfs_clear_mesh_scan_kernel, dim3(p.nmesh, p.B), dim3(CM_SCAN), 0, s, p);
+    return hipGetLastError();
+}

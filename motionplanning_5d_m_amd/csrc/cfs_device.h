@@ -87,6 +87,8 @@ struct ClearParams {
     const double *x_, *u, *xR1, *obs;      // B x H*2nj, B x H*nj, B x 2nj
     double *dist_wp, *dist_path, *dist_lower, *t_path;   // B x nobs each
     int *link_path;              // B x nobs (1-based)
+    int obs_stride, out_stride;  // obstacle rows per problem in `obs`, columns per problem in the outputs: (move ? H : 1) * nobs and nobs, or more
+                                 // when the nobs line obstacles are the first columns of a handle with meshes (cfs_clear_mesh.hip)
     double rho[CFS_MAX_LINKS * CFS_MAX_LINKS];   // rho[m*CFS_MAX_LINKS + k]: reach of capsule k about the axis of joint m (cfs_clear_build_rho)
 };
 hipError_t launch_clearance(const ClearParams &p, hipStream_t s);

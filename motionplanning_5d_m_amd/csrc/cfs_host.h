@@ -67,6 +67,24 @@ hipError_t launch_linearize_mesh(int nj, const LinMeshParams &p, hipStream_t s);
 void linearize_mesh_workspace(int nj, int nmesh, size_t *ends, size_t *base, size_t *shift, size_t *near, size_t *piece_d, size_t *piece_i,
                               size_t *piece_nd);
 
+// ---- clearance audit against mesh obstacles (cfs_clear_mesh.hip) ---------------------------------------
+enum { CLEAR_MESH_BOUND = 1, CLEAR_MESH_SEED = 2 };      // ClearMeshParams::opt
+struct ClearMeshParams {
+    const DevRobot *rb;
+    int B, H, nj, nobs, nmesh, S;                        // nobs: all obstacles of the handle (output stride); the meshes are the last nmesh
+    int opt;                                             // CLEAR_MESH_*: how the queries use the time coherence (same results either way)
+    double dt;
+    const DevMesh *meshes;                               // device array [nmesh]
+    const double *x_, *u, *xR1;                          // B x H*2nj, B x H*nj, B x 2nj
+    double *dist_wp, *dist_path, *dist_lower, *t_path;   // B x nobs each: columns nobs - nmesh .. nobs - 1 are written
+    int *link_path, *tri_path;                           // B x nobs; tri_path: every column (-1 in the line columns)
+    // workspace of the handle, G = H*S + 1 samples per problem
+    double *ws_d, *ws_L;                                 // B x nmesh x G per-sample distance; B x G arm's share of the Lipschitz bound
+    int *ws_lk, *ws_tri, *ws_seed;                       // B x nmesh x G closest link / triangle; B x (H+1) x nj x nmesh waypoint winners
+    const double *rho;                                   // device, CFS_MAX_LINKS^2 (cfs_clear_build_rho)
+};
+hipError_t launch_clearance_mesh(const ClearMeshParams &p, hipStream_t s);
+
 // ---- CHOMP_FANUC (cfs_chomp.hip) -----------------------------------------------------------------------
 struct ChompParams {
     const DevRobot *rb;

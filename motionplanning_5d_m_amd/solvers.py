@@ -469,6 +469,66 @@ class CFSBatch:
             out.short_by = (self._margin_on(x_.device)[None, :] - out.dist_path).amax(dim=1)
         return out
 
+    # ---- clearance audit with mesh obstacles --------------------------------------------------------------
+    def _check_audit_mesh(self, substeps):
+        S = _substeps(substeps)
+        if not getattr(self, "_meshes", None):
+            raise ValueError("clearance_mesh needs a handle with mesh obstacles (set_meshes): use clearance for line obstacles")
+        return S
+
+    def clearance_mesh(self, x_, u, xR1, obs, substeps=16):
+        """clearance() for a handle with mesh obstacles (cfs_clearance_mesh, include/cfs_hip.h); host arrays in and out.  The
+        (B, nobs) arrays are in the handle's obstacle order (lines first, then the meshes): dist_wp, dist_path, dist_lower,
+        t_path, link_path as in clearance(), and tri_path, the index in the caller's triangle list of a closest triangle at the
+        dist_path sample (-1 in line columns); short_by (B,) = max_j(margin_j - dist_path[:, j]) over all columns."""
+        S = self._check_audit_mesh(substeps)
+        x_, u, xR1, obs = _f64(x_), _f64(u), _f64(xR1), _f64(obs)
+        B = x_.shape[0]
+        if x_.shape != (B, self.nx) or u.shape != (B, self.nn) or xR1.shape != (B, self.ns) or obs.shape != (B, self.nobs, 6):
+            raise ValueError(f"x_, u, xR1, obs must have shapes {(B, self.nx)}, {(B, self.nn)}, {(B, self.ns)}, {(B, self.nobs, 6)}, "
+                             f"not {x_.shape}, {u.shape}, {xR1.shape}, {obs.shape}")
+        z = lambda dt=np.float64: np.zeros((B, self.nobs), dt)  # noqa: E731
+        r = SimpleNamespace(dist_wp=z(), dist_path=z(), dist_lower=z(), t_path=z(), link_path=z(np.int32), tri_path=z(np.int32))
+        _lib.check(self._lib.cfs_clearance_mesh(self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs), _ptr(r.dist_wp),
+                                                _ptr(r.dist_path), _ptr(r.dist_lower), _ptr(r.t_path), _ptr(r.link_path),
+                                                _ptr(r.tri_path)))
+        r.short_by = (self.margin[None, :] - r.dist_path).max(axis=1)
+        return r
+
+    def alloc_clearance_mesh(self, B, device):
+        """Device-resident output buffers (torch CUDA tensors) for clearance_mesh_device."""
+        out = self.alloc_clearance(B, device)
+        out.tri_path = torch.zeros(B, self.nobs, dtype=torch.int32, device=device)
+        return out
+
+    def clearance_mesh_device(self, x_, u, xR1, obs, substeps=16, out=None, stream=None):
+        """clearance_mesh() on torch CUDA tensors; enqueues on `stream` (default: torch's current stream) and returns without
+        synchronising (cfs_clearance_mesh_device).  out: an alloc_clearance_mesh namespace to write into."""
+        S = self._check_audit_mesh(substeps)
+        B = x_.shape[0]
+        for t in (x_, u, xR1, obs):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+        if (tuple(x_.shape) != (B, self.nx) or tuple(u.shape) != (B, self.nn) or tuple(xR1.shape) != (B, self.ns)
+                or tuple(obs.shape) != (B, self.nobs, 6)):
+            raise ValueError(f"x_, u, xR1, obs must have shapes {(B, self.nx)}, {(B, self.nn)}, {(B, self.ns)}, {(B, self.nobs, 6)}")
+        if out is None:
+            out = self.alloc_clearance_mesh(B, x_.device)
+        for t, dt in ((out.dist_wp, torch.float64), (out.dist_path, torch.float64), (out.dist_lower, torch.float64),
+                      (out.t_path, torch.float64), (out.link_path, torch.int32), (out.tri_path, torch.int32)):
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (B, self.nobs)
+        cur = torch.cuda.current_stream(x_.device)
+        sp = cur.cuda_stream if stream is None else int(stream)
+        _lib.check(self._lib.cfs_clearance_mesh_device(self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs), _ptr(out.dist_wp),
+                                                       _ptr(out.dist_path), _ptr(out.dist_lower), _ptr(out.t_path),
+                                                       _ptr(out.link_path), _ptr(out.tri_path), C.c_void_p(sp)))
+        if sp == cur.cuda_stream:
+            ts = cur
+        else:                            # pointer 0 is the default stream: ExternalStream does not wrap it
+            ts = torch.cuda.default_stream(x_.device) if sp == 0 else torch.cuda.ExternalStream(sp, device=x_.device)
+        with torch.cuda.stream(ts):      # short_by on the same stream, after the audit
+            out.short_by = (self._margin_on(x_.device)[None, :] - out.dist_path).amax(dim=1)
+        return out
+
     def _margin_on(self, device):
         """the handle's margins as a tensor on `device` (uploaded once: no copy is enqueued by later audits)"""
         cache = self.__dict__.setdefault("_margin_dev", {})
@@ -578,7 +638,7 @@ class CFSBatch:
     # ---- developer / test switches (cfs_debug_*, per handle) ---------------------------------------------
     def debug_options(self, warm_max=0, polish_tol=0.0, **flags):
         """cfs_debug_set_options: flags from _lib.DBG (no_refine, no_warm_start, no_certificate, no_prune, no_auto_order,
-        tier_w1); no flags = the defaults."""
+        tier_w1, clear_no_bound, clear_seed); no flags = the defaults."""
         mask = 0
         for k, v in flags.items():
             if v:
@@ -728,11 +788,13 @@ class _SolverBase:
     MARGIN_KEY = "epsilon"
 
     def __init__(self, obs, sys_info, ROBOT="M16iB", device=None, jacobian="fd_literal", on_infeasible="stop", soft_weight=None,
-                 joint_limits=None, audit=None):
+                 joint_limits=None, audit=None, audit_mesh=None):
         """jacobian: "fd_literal" (num_jac.m, the default) | "analytic" (CFSBatch).
         audit: None (the default: results are exactly those without the argument) | an integer S in 1..64: after optimizer(),
         .clearance holds CFSBatch.clearance of the returned trajectory with S sub-steps per interval (its one problem: arrays of
         shape (nobs,), short_by a float); line obstacles only.
+        audit_mesh: the same for an obs cell with at least one mesh: None (the default) | S in 1..64: after optimizer(),
+        .clearance_mesh holds CFSBatch.clearance_mesh of the returned trajectory (all columns, lines first, with tri_path).
         joint_limits: None (the default) | "robot" | an (njoint, 2) array of [lo, hi] (CFSBatch); get_con then has the position rows.
         on_infeasible: "stop" (the default) | "soften" with soft_weight= (CFSBatch); after optimizer(), viol_all and n_soft.
         obs{j}["l"] may be 3x2xH (shape (3, 2, H): the obstacle's axis at waypoints 1..H); any such entry makes the handle
@@ -744,6 +806,10 @@ class _SolverBase:
         if self.audit is not None and obs_meshes(obs):
             raise ValueError("audit= measures line obstacles only: the obs cell holds mesh obstacles")
         self.clearance = None
+        self.audit_mesh = None if audit_mesh is None else _substeps(audit_mesh, "audit_mesh")
+        if self.audit_mesh is not None and not obs_meshes(obs):
+            raise ValueError("audit_mesh= needs an obs cell with at least one mesh obstacle: audit= measures line obstacles")
+        self.clearance_mesh = None
         if on_infeasible == "soften" and obs_meshes(obs):
             raise ValueError('on_infeasible="soften" does not support mesh obstacles')
         self._moving = obs_moving(obs)
@@ -796,6 +862,11 @@ class _SolverBase:
             c = self._batch.clearance(r.x_, r.u, xR1, obs, substeps=self.audit)
             self.clearance = SimpleNamespace(dist_wp=c.dist_wp[0], dist_path=c.dist_path[0], dist_lower=c.dist_lower[0],
                                              t_path=c.t_path[0], link_path=c.link_path[0], short_by=float(c.short_by[0]))
+        if self.audit_mesh is not None:
+            c = self._batch.clearance_mesh(r.x_, r.u, xR1, obs, substeps=self.audit_mesh)
+            self.clearance_mesh = SimpleNamespace(dist_wp=c.dist_wp[0], dist_path=c.dist_path[0], dist_lower=c.dist_lower[0],
+                                                  t_path=c.t_path[0], link_path=c.link_path[0], tri_path=c.tri_path[0],
+                                                  short_by=float(c.short_by[0]))
         if self.status == 0:
             print(f"Converged at step{self.iter_O}")  # EVAL.m:66
         elif self.status == 1:
@@ -818,9 +889,11 @@ class CHOMP_FANUC:
     """Lib/CHOMP_FANUC.m -- ``CHOMP_FANUC(obs_, sys_info, uref, ROBOT).optimizer()``.  ``obs_`` is the reference's cell:
     ``obs_[0] = dict(num_obs=n)`` followed by the n obstacles (``l``, ``D``, ``epsilon``) (M16iB/CHOMP.m:26-29)."""
 
-    def __init__(self, obs, sys_info, uu, ROBOT="M16iB", device=None, audit=None):
+    def __init__(self, obs, sys_info, uu, ROBOT="M16iB", device=None, audit=None, audit_mesh=None):
         if audit is not None:
             raise ValueError("CHOMP_FANUC has no clearance audit: audit= is an option of CFS_FANUC and PSGCFS_FANUC")
+        if audit_mesh is not None:
+            raise ValueError("CHOMP_FANUC has no clearance audit: audit_mesh= is an option of CFS_FANUC and PSGCFS_FANUC")
         self.obs, self.sys_info, self.ROBOT = obs, sys_info, ROBOT
         if getattr(sys_info.robot, "name", ROBOT) != ROBOT:
             raise ValueError(f"sys_info.robot is {sys_info.robot.name!r} but ROBOT={ROBOT!r}")
