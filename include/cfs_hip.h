@@ -447,6 +447,29 @@ int cfs_rrt_grow(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out);
  * `stream`; routes can go straight into cfs_build_terms_from_ragged_routes_device */
 int cfs_rrt_grow_device(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out, void *stream);
 
+/* The same trees in a cell that also holds mesh obstacles.  feasible() (Lib/RRT_FANUC.m:146-181) is extended
+ * the way M200i/dist_arm_surf_200i.m:21-24 extends dist_arm: the line obstacles of the descriptor are tested first, as above; then,
+ * for every mesh j and link i, dis = the mesh distance of the link axis under the mesh contract ("mesh obstacles" above), if
+ * |dis| < 1e-4 then dis = -|points(:,1) - p(:,2)|, and the node is rejected if dis < D_mesh[j].  Equivalently: mesh j rejects the
+ * node exactly when some triangle lies closer than max(D_mesh[j], 1e-4) to some link axis; the hierarchy is walked as a threshold
+ * query that may stop at the first such triangle, and the decision does not depend on the traversal order.  Everything else (draws
+ * per proposal, nearest node, extension, addNode, arrangeNode, goal test, failure codes, route, all_ee) is cfs_rrt_grow's;
+ * nmesh = 0 gives exactly what cfs_rrt_grow* gives.  The geometry is evaluated without FMA contraction, like the tree arithmetic,
+ * so a proposal within rounding of its threshold may be decided differently from a cfs_dist_arm_mesh call.
+ * meshes: nmesh handles created on the current device (cfs_set_device); they must outlive the launch.  D_mesh: HOST, nmesh
+ * margins, finite and > 0.  d->nobs + nmesh <= CFS_MAX_OBS.  CFS_ERR_INVALID_ARG, with nothing launched, for any violation of
+ * these, for unknown flags, for a MAX_ITER whose tree no longer fits into 64 KB of LDS next to the mesh scratch, and for every
+ * argument cfs_rrt_grow refuses.
+ * flags: 0, or a developer switch like the CFS_DBG_CLEAR_* ones below (RRT has no handle to carry them; results are bit-identical
+ * under every value): */
+#define CFS_RRT_MESH_PER_LANE 1        /* variant A: one (mesh, link) pair per lane, private threshold query (the correctness baseline)     */
+#define CFS_RRT_MESH_WAVE 2            /* variant B: one wave-cooperative traversal over a shared frontier in LDS (the default: 2.7-3.7x A) */
+#define CFS_RRT_MESH_SMALL_FRONTIER 4  /* variant B with a frontier of 8 entries: its overflow path (decided by variant A) under test        */
+int cfs_rrt_grow_mesh(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int S,
+                      const cfs_rrt_out *out);
+int cfs_rrt_grow_mesh_device(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh /* HOST, nmesh */,
+                             int flags, int S, const cfs_rrt_out *out, void *stream);
+
 /* ---- best of K smoothed routes per slot ---------------------------------------------------------
  * The reference grows num_seed RRT seeds, keeps the route with the FEWEST NODES, first seed on ties
  * (Lib/functions/s_Parallel_rrt.m:27-28: [~, I] = min(routeL)), and runs one CFS on it (RRTstar_CFS.m:94-196).  Here all K
@@ -572,6 +595,10 @@ int cfs_debug_trace_read(cfs_problem *p, double *out);
  * max_batch x MAX_O_ITER x nn doubles; cfs_debug_read_u_log copies the first B problems to `out` (HOST) */
 int cfs_debug_log_u(cfs_problem *p, int on);
 int cfs_debug_read_u_log(cfs_problem *p, int B, double *out);
+/* cfs_rrt_grow_mesh*, variant B: proposals of the current device, since the last reset, whose frontier overflowed its capacity and
+ * that variant A decided instead (one counter per device and process; HOST pointer, may be NULL; synchronises the device).
+ * With CFS_RRT_MESH_SMALL_FRONTIER it shows that the overflow path ran. */
+int cfs_debug_rrt_frontier_overflows(unsigned long long *count, int reset);
 
 #ifdef __cplusplus
 }

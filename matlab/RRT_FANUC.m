@@ -2,6 +2,8 @@
 % Same constructor and find_route() as Lib/RRT_FANUC.m:48,63; same outputs (route, all_nodes, total_dis, all_ee, fail, node_num).
 % rand stays MATLAB's: find_route draws the uniforms here and the kernel consumes them exactly as Lib/RRT_FANUC.m:108,111 do
 % (one per proposal for the goal bias, nstate more when the sample is random).
+% The obs cell may end with mesh obstacles, struct('mesh', h, 'D', D) with h from cfs_mex('mesh_load_stl', ...): it is passed
+% through as it is and feasible() then also keeps every link axis max(D, 1e-4) away from the mesh (cfs_rrt_grow_mesh).
 classdef RRT_FANUC
    properties
        obs cell; sys_info struct; goal; region_g; region_s; sample_off; ROBOT = 'M16iB'; SOLVER = 'RRT*'

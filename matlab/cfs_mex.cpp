@@ -26,6 +26,7 @@
 //   'solve' and 'get_con' accept moving obstacles: obs{j}.l may be 3x2xH (page i = the axis at waypoint i); any such entry makes
 //   the handle CFS_OBS_PER_WAYPOINT and the 3x2 entries are held over the horizon (include/cfs_hip.h, moving obstacles)
 //   [route, all_nodes, total_dis, all_ee, fail, node_num] = cfs_mex('rrt', obs, sys_info, goal, region_g, region_s, sample_off, ROBOT, SOLVER, U)
+//        obs may end with mesh obstacles (obs{j}.mesh, obs{j}.D), received as 'clearance_mesh' receives them: cfs_rrt_grow_mesh
 //        RRT_FANUC(obs, sys_info, goal, region_g, region_s, sample_off, ROBOT, SOLVER).find_route() (Lib/RRT_FANUC.m:48-91) grown on the GPU;
 //        U = rand(ndraw, S): MATLAB's own rand, consumed per tree exactly as find_route consumes it (one per proposal + nstate for a random
 //        sample); S > 1 grows S seeds at once (s_Parallel_rrt.m:16's parfor) and the outputs become cells
@@ -298,15 +299,25 @@ static void rrt(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     d.max_iter = 400; d.bi = 0.5; d.rewire = 0.2;                                   // class property defaults (Lib/RRT_FANUC.m:37-38, :135)
     d.x0 = field_ptr(S_, "x0"); d.goal_th = field_ptr(S_, "goal_th"); d.ratial = field_ptr(S_, "ratial");
     d.goal = mxGetPr(prhs[3]); d.region_g = mxGetPr(prhs[4]); d.region_s = mxGetPr(prhs[5]); d.sample_off = mxGetPr(prhs[6]);
-    const int nobs = (int)mxGetNumberOfElements(obs);
-    std::vector<double> obs6(6 * (size_t)nobs), D(nobs);
-    for (int j = 0; j < nobs; ++j) {
-        const mxArray *o = mxGetCell(obs, j), *fl = o ? mxGetField(o, 0, "l") : nullptr, *fD = o ? mxGetField(o, 0, "D") : nullptr;
+    // line obstacles (.l, .D) first, then mesh obstacles (.mesh = a handle of cfs_mex('mesh_create' ...), .D): cfs_rrt_grow_mesh
+    const int ncell = (int)mxGetNumberOfElements(obs);
+    std::vector<double> obs6, D, D_mesh;
+    std::vector<const cfs_mesh *> meshes;
+    for (int j = 0; j < ncell; ++j) {
+        const mxArray *o = mxGetCell(obs, j), *fD = o ? mxGetField(o, 0, "D") : nullptr, *mh = o ? mxGetField(o, 0, "mesh") : nullptr;
+        if (mh) {
+            if (!fD) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .mesh and .D", j + 1);
+            meshes.push_back(mesh_of(mh));
+            D_mesh.push_back(mxGetScalar(fD));
+            continue;
+        }
+        if (!meshes.empty()) mexErrMsgTxt("mesh obstacles must come last in the obs cell");
+        const mxArray *fl = o ? mxGetField(o, 0, "l") : nullptr;
         if (!fl || !fD || mxGetNumberOfElements(fl) != 6) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .l (3x2) and .D", j + 1);
-        memcpy(&obs6[6 * (size_t)j], mxGetPr(fl), sizeof(double) * 6);
-        D[j] = mxGetScalar(fD);
+        obs6.insert(obs6.end(), mxGetPr(fl), mxGetPr(fl) + 6);
+        D.push_back(mxGetScalar(fD));
     }
-    d.nobs = nobs; d.obs = obs6.data(); d.D = D.data();
+    d.nobs = (int)D.size(); d.obs = obs6.data(); d.D = D.data();
     const int ndraw = (int)mxGetM(prhs[9]), S = (int)mxGetN(prhs[9]);
     d.uniforms = mxGetPr(prhs[9]); d.ndraw = ndraw;                                 // ndraw x S column-major = S x ndraw row-major
     const size_t N = (size_t)d.max_iter + 1, nj = d.nstate;
@@ -316,7 +327,8 @@ static void rrt(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     memset(&o, 0, sizeof o);
     o.node_num = node_num.data(); o.fail = fail.data(); o.route_len = route_len.data(); o.parent = parent.data();
     o.nodes = nodes.data(); o.total_dis = total_dis.data(); o.all_ee = all_ee.data(); o.route = route.data();
-    check(cfs_rrt_grow(&d, S, &o));
+    if (meshes.empty()) check(cfs_rrt_grow(&d, S, &o));
+    else check(cfs_rrt_grow_mesh(&d, (int)meshes.size(), meshes.data(), D_mesh.data(), 0, S, &o));
     mxArray *outs[6];
     for (int k = 0; k < 4; ++k) outs[k] = S > 1 ? mxCreateCellMatrix(1, S) : nullptr;
     outs[4] = mxCreateDoubleMatrix(1, S, mxREAL); outs[5] = mxCreateDoubleMatrix(1, S, mxREAL);

@@ -186,6 +186,8 @@ SYMBOLS = [
     ("cfs_build_terms_from_ragged_routes_device", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("cfs_rrt_grow", C.c_int, [C.POINTER(cfs_rrt_desc), C.c_int, C.POINTER(cfs_rrt_out)]),
     ("cfs_rrt_grow_device", C.c_int, [C.POINTER(cfs_rrt_desc), C.c_int, C.POINTER(cfs_rrt_out), _P]),
+    ("cfs_rrt_grow_mesh", C.c_int, [C.POINTER(cfs_rrt_desc), C.c_int, _P, _P, C.c_int, C.c_int, C.POINTER(cfs_rrt_out)]),
+    ("cfs_rrt_grow_mesh_device", C.c_int, [C.POINTER(cfs_rrt_desc), C.c_int, _P, _P, C.c_int, C.c_int, C.POINTER(cfs_rrt_out), _P]),
     ("cfs_cost_b", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("cfs_get_cost", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("cfs_debug_set_options", C.c_int, [_P, C.c_int, C.c_int, C.c_double]),
@@ -194,6 +196,7 @@ SYMBOLS = [
     ("cfs_debug_trace_read", C.c_int, [_P, _P]),
     ("cfs_debug_log_u", C.c_int, [_P, C.c_int]),
     ("cfs_debug_read_u_log", C.c_int, [_P, C.c_int, _P]),
+    ("cfs_debug_rrt_frontier_overflows", C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     ("cfs_problem_set_jacobian", C.c_int, [_P, C.c_int]),
     ("cfs_problem_get_jacobian", C.c_int, [_P, C.POINTER(C.c_int)]),
     ("cfs_problem_set_infeasible_policy", C.c_int, [_P, C.c_int, C.c_double]),
@@ -214,6 +217,9 @@ SYMBOLS = [
 # cfs_debug_set_options mask bits (include/cfs_hip.h)
 DBG = {"no_refine": 2, "no_warm_start": 8, "no_certificate": 16, "no_prune": 32, "no_auto_order": 64, "tier_w1": 128,
        "clear_no_bound": 256, "clear_seed": 512}
+
+# cfs_rrt_grow_mesh* flags (include/cfs_hip.h): developer switches, bit-identical trees under every value
+RRT_MESH = {"per_lane": 1, "wave": 2, "small_frontier": 4}
 
 _lib = None
 

@@ -119,3 +119,20 @@ struct RrtParams {
 };
 hipError_t launch_rrt(int nj, const RrtParams &p, hipStream_t s);
 size_t rrt_lds_bytes(int nj, int max_iter);
+// mesh obstacles of the feasibility test (cfs_rrt_grow_mesh*): by value as well, a second kernel argument of the mesh kernels only
+enum { RRT_MESH_NONE = 0, RRT_MESH_PER_LANE = 1, RRT_MESH_WAVE = 2 };   // variant A | variant B
+constexpr int RRT_MESH_DEFAULT = RRT_MESH_WAVE;          // flags == 0: the variant the measurement of DESIGN.md section 19 names
+constexpr int RRT_FRONTIER_CAP = 512;                    // variant B: (pair, node) entries of the wave's frontier
+constexpr int RRT_FRONTIER_SMALL = 8;                    // CFS_RRT_MESH_SMALL_FRONTIER: forces the overflow path under test
+struct RrtMeshEntry {
+    const BvhNode *nodes;
+    const double *tri;                                   // nt x 9, hierarchy order
+    double thr;                                          // max(D_j, 1e-4): a triangle closer than this rejects the node
+    int nt, pad;
+};
+struct RrtMeshArgs {
+    int nmesh, cap;                                      // cap: variant B's frontier capacity (<= RRT_FRONTIER_CAP)
+    RrtMeshEntry m[CFS_MAX_OBS];
+};
+hipError_t launch_rrt_mesh(int nj, int variant, const RrtParams &p, const RrtMeshArgs &ma, hipStream_t s);
+size_t rrt_mesh_lds_bytes(int nj, int max_iter, int variant);      // rrt_lds_bytes + the variant's mesh scratch

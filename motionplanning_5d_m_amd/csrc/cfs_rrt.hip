@@ -26,8 +26,29 @@
 // This translation unit is compiled with -ffp-contract=off (Makefile): tree arithmetic (weighted norms, the 0.1-rad extension,
 // cost sums) is then plain IEEE mul / add / div / sqrt in the order written here, so that parents, nodes, costs and routes are
 // BIT-identical to the CPU restatement (oracle/rrt_oracle.py); only sin / cos differ from libm by <= 1 ulp (all_ee: 1e-14).
+//
+// Mesh obstacles (cfs_rrt_grow_mesh*).  feasible() is extended the way M200i/dist_arm_surf_200i.m:21-24
+// extends dist_arm: after the line obstacles, for every mesh j and link i, dis = mesh distance of the link axis (contract:
+// cfs_mesh.hip's head comment), |dis| < 1e-4 -> dis = -|points(:,1) - p(:,2)|, reject if dis < D_j.  The surrogate is negative and
+// D_j > 0, so mesh j rejects the node exactly when SOME triangle lies closer than thr_j = max(D_j, 1e-4) to SOME link axis: an
+// existence question.  The traversal prunes a hierarchy node whose rigorous lower bound is not below thr_j and may stop at the
+// first triangle below it; the decision does not depend on the order.  The mesh test runs only when the lines have passed (the
+// same decision, fewer traversals).  Two variants, bit-identical trees:
+//   A (RRT_MESH_PER_LANE)  lane p < nmesh*NJ owns one (mesh, link) pair and runs mesh_query<64, false>(bound = thr_j); the vote
+//                          is a ballot of b.tri >= 0.  Private stacks in LDS (MESH_STACK*64*8 B = 10 KB).
+//   B (RRT_MESH_WAVE)      one frontier of (pair, inner node) entries in LDS shared by the wave: each round the lanes take up to
+//                          64 entries from its end, each lane bounds both children of its node, inner children that survive are
+//                          appended by ballot + prefix count, the triangles of surviving leaves are tested exactly, and a
+//                          ballot ends the test on the first hit.  A proposal whose frontier would overflow its capacity is
+//                          decided by variant A (same decision by construction).
+// Exact distances and lower bounds are cfs_mesh_dev.h's functions.  They are compiled here WITHOUT FMA contraction (the flag
+// above covers the whole translation unit), so a distance may differ in its last bits from cfs_dist_arm_mesh, whose translation
+// unit contracts: a proposal within rounding of its threshold may be decided differently from a cfs_dist_arm_mesh call.
+// The line-only kernel (cfs_rrt_kernel) keeps its code path: the mesh code is compiled out of it.
+#include "cfs_mesh_dev.h"
 #include "cfs_geom_dev.h"
 #include "cfs_host.h"
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -45,9 +66,113 @@ __device__ __forceinline__ double rrt_uniform(const RrtParams &P, int tree, unsi
     return (double)(z >> 11) * 0x1.0p-53;
 }
 
+// proposals of variant B whose frontier overflowed and that variant A decided (cfs_debug_rrt_frontier_overflows): one vector atomic
+// by lane 0 per such proposal, none on the normal path
+__device__ unsigned long long g_rrt_frontier_overflows = 0ull;
+
+// link k's axis out of the FK result, without dynamic indexing of the register array
 template <int NJ>
-__global__ __launch_bounds__(WV) void cfs_rrt_kernel(const RrtParams P)
+__device__ __forceinline__ void pick_link(const double *ends, int k, double *a6)
 {
+#pragma unroll
+    for (int kk = 0; kk < NJ; ++kk)
+        if (kk == k) {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) a6[q] = ends[kk * 6 + q];
+        }
+}
+
+// variant A: one (mesh, link) pair per lane, threshold query with a private stack
+template <int NJ>
+__device__ __forceinline__ bool mesh_hit_per_lane(const RrtMeshArgs &MA, const double *ends, int lane, int *stack, float *lbs)
+{
+    bool hit = false;
+    const int npair = MA.nmesh * NJ;
+    for (int p = lane; p < npair; p += WV) {
+        const int j = p / NJ, k = p - j * NJ;
+        double a6[6];
+        pick_link<NJ>(ends, k, a6);
+        const DevMesh m{MA.m[j].nodes, MA.m[j].tri, nullptr, 0, MA.m[j].nt, nullptr, nullptr, 0, 0};
+        Best b;
+        mesh_query<WV, false>(m, a6, a6 + 3, -1, stack + lane, lbs + lane, b, nullptr, MA.m[j].thr);
+        hit = hit || (b.tri >= 0 && b.d < MA.m[j].thr);       // take() also accepts a tie with the bound: the rule is strict (dis < D)
+    }
+    return __ballot(hit) != 0ull;
+}
+
+// variant B: wave-cooperative threshold traversal.  1: some triangle is below its threshold; 0: none; -1: the frontier overflowed
+template <int NJ>
+__device__ __forceinline__ int mesh_hit_wave(const RrtMeshArgs &MA, const double *ends, int lane, int *f_pair, int *f_node)
+{
+    const int npair = MA.nmesh * NJ, cap = MA.cap;
+    if (npair > cap) return -1;
+    for (int p = lane; p < npair; p += WV) { f_pair[p] = p; f_node[p] = 0; }      // the root is always an inner node (upload_mesh)
+    int count = npair;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    while (count > 0) {
+        const int n = count < WV ? count : WV;                // from the end: depth first in blocks of 64, the frontier stays short
+        count -= n;
+        const bool live = lane < n;
+        int p = 0, node = 0;
+        if (live) { p = f_pair[count + lane]; node = f_node[count + lane]; }
+        __builtin_amdgcn_wave_barrier();
+        bool hit = false, push0 = false, push1 = false;
+        int c0 = 0, c1 = 0;
+        if (live) {
+            const int j = p / NJ, k = p - j * NJ;
+            double a6[6];
+            pick_link<NJ>(ends, k, a6);
+            const double thr = MA.m[j].thr;
+            const double *tri = MA.m[j].tri;
+            if (MA.m[j].nt > 0) {
+                const BvhNode nd = MA.m[j].nodes[node];       // one load: both children's boxes
+                const double l0 = node_lower_bound(a6, a6 + 3, nd.lo[0], nd.hi[0]);
+                const double l1 = node_lower_bound(a6, a6 + 3, nd.lo[1], nd.hi[1]);
+                c0 = nd.child[0]; c1 = nd.child[1];
+                const bool s0 = l0 < thr, s1 = l1 < thr;      // an empty child's bound is +inf or NaN: never below
+                push0 = s0 && c0 >= 0; push1 = s1 && c1 >= 0;
+                const int leaf0 = (s0 && c0 < 0) ? c0 : 0, leaf1 = (s1 && c1 < 0) ? c1 : 0;
+#pragma unroll 1
+                for (int it = 0; it < 2; ++it) {
+                    const int lf = it == 0 ? leaf0 : leaf1;
+                    if (lf < 0) {
+                        const int code = -(lf + 1), first = code >> 3, cnt = code & 7;
+                        Best b;
+                        b.d = thr; b.t = INFINITY; b.tri = -1;
+                        for (int q = first; q < first + cnt; ++q) seg_tri_update(a6, a6 + 3, tri + 9 * (size_t)q, q, b);
+                        hit = hit || (b.tri >= 0 && b.d < thr);       // strict, as in variant A
+                    }
+                }
+            }
+        }
+        if (__ballot(hit) != 0ull) return 1;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long m0 = __ballot(push0);
+        if (push0) { const int pos = count + __popcll(m0 & below); if (pos < cap) { f_pair[pos] = p; f_node[pos] = c0; } }
+        count += __popcll(m0);
+        const unsigned long long m1 = __ballot(push1);
+        if (push1) { const int pos = count + __popcll(m1 & below); if (pos < cap) { f_pair[pos] = p; f_node[pos] = c1; } }
+        count += __popcll(m1);
+        if (count > cap) return -1;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    return 0;
+}
+
+// kernel arguments: the mesh table exists only in the mesh kernels' parameter block
+template <int MESH> struct RrtArgs { RrtParams P; RrtMeshArgs MA; };
+template <> struct RrtArgs<RRT_MESH_NONE> { RrtParams P; };
+
+// MESH: RRT_MESH_NONE (the line-only kernel: the mesh code is compiled out) | RRT_MESH_PER_LANE | RRT_MESH_WAVE
+
+template <int NJ, int MESH>
+__global__ __launch_bounds__(WV) void cfs_rrt_kernel(const RrtArgs<MESH> A)
+{
+    const RrtParams &P = A.P;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int t = blockIdx.x, lane = threadIdx.x;
     const int NMAX = P.max_iter + 1;                          // node_num may reach MAX_ITER + 1 before the failure test fires (:201)
@@ -55,6 +180,13 @@ __global__ __launch_bounds__(WV) void cfs_rrt_kernel(const RrtParams P)
     double *s_tot = s_nodes + (size_t)NMAX * NJ;              // total_dis
     double *s_to = s_tot + NMAX;                              // toNode_dis of the current proposal
     int *s_par = reinterpret_cast<int *>(s_to + NMAX);        // parent (1-based, -1 for the root), all_nodes(1,:)
+    int *s_stack = nullptr, *s_fpair = nullptr, *s_fnode = nullptr;   // mesh scratch behind the tree (rrt_mesh_lds_bytes)
+    float *s_lbs = nullptr;
+    if constexpr (MESH != RRT_MESH_NONE) {
+        s_stack = s_par + ((NMAX + 1) & ~1);
+        s_lbs = reinterpret_cast<float *>(s_stack + MESH_STACK * WV);
+        if constexpr (MESH == RRT_MESH_WAVE) { s_fpair = s_stack + 2 * MESH_STACK * WV; s_fnode = s_fpair + RRT_FRONTIER_CAP; }
+    }
     const DevRobot *rb = &P.rb;                               // robot constants travel in the kernel's parameter block (scalar loads)
     const double *x0 = P.x0 + (P.per_tree ? (size_t)t * NJ : 0), *goal = P.goal + (P.per_tree ? (size_t)t * NJ : 0);
     const double *goal_th = P.goal_th + (P.per_tree ? (size_t)t * NJ : 0);
@@ -152,7 +284,16 @@ __global__ __launch_bounds__(WV) void cfs_rrt_kernel(const RrtParams P)
                 const double dis = seg_seg_dist(a6, o6);
                 hit = hit || (dis < P.D[j]);
             }
-            const bool infeasible = __ballot(hit) != 0ull;
+            bool infeasible = __ballot(hit) != 0ull;
+            if constexpr (MESH == RRT_MESH_PER_LANE) {
+                if (!infeasible) infeasible = mesh_hit_per_lane<NJ>(A.MA, ends, lane, s_stack, s_lbs);
+            } else if constexpr (MESH == RRT_MESH_WAVE) {
+                if (!infeasible) {
+                    const int h = mesh_hit_wave<NJ>(A.MA, ends, lane, s_fpair, s_fnode);
+                    if (h < 0 && lane == 0) atomicAdd(&g_rrt_frontier_overflows, 1ull);
+                    infeasible = h < 0 ? mesh_hit_per_lane<NJ>(A.MA, ends, lane, s_stack, s_lbs) : h != 0;
+                }
+            }
             e_first[0] = ends[(NJ - 1) * 6]; e_first[1] = ends[(NJ - 1) * 6 + 1]; e_first[2] = ends[(NJ - 1) * 6 + 2];   // pos{nstate}.p(:,1) (:186)
             if (!infeasible) break;
         }
@@ -222,16 +363,44 @@ size_t rrt_lds_bytes(int nj, int max_iter)
     return NMAX * nj * 8 + NMAX * 8 * 2 + ((NMAX * 4 + 7) & ~(size_t)7);
 }
 
+size_t rrt_mesh_lds_bytes(int nj, int max_iter, int variant)
+{
+    size_t b = rrt_lds_bytes(nj, max_iter);
+    if (variant != RRT_MESH_NONE) b += (size_t)MESH_STACK * WV * 8;                  // variant A's stacks (B falls back to A)
+    if (variant == RRT_MESH_WAVE) b += (size_t)RRT_FRONTIER_CAP * 8;                 // variant B's frontier
+    return b;
+}
+
+hipError_t launch_rrt_mesh(int nj, int variant, const RrtParams &p, const RrtMeshArgs &ma, hipStream_t s)
+{
+    const size_t lds = rrt_mesh_lds_bytes(nj, p.max_iter, variant);
+    if (lds > 64 * 1024 || (variant != RRT_MESH_PER_LANE && variant != RRT_MESH_WAVE)) return hipErrorInvalidValue;
+    const RrtArgs<RRT_MESH_PER_LANE> aa{p, ma};
+    const RrtArgs<RRT_MESH_WAVE> ab{p, ma};
+#define RRT_MESH_LAUNCH(NJ_)                                                                                                   \
+    case NJ_:                                                                                                                  \
+        if (variant == RRT_MESH_PER_LANE) hipLaunchKernelGGL((cfs_rrt_kernel<NJ_, RRT_MESH_PER_LANE>), dim3(p.S), dim3(WV), lds, s, aa); \
+        else hipLaunchKernelGGL((cfs_rrt_kernel<NJ_, RRT_MESH_WAVE>), dim3(p.S), dim3(WV), lds, s, ab);                           \
+        break;
+    switch (nj) {
+        RRT_MESH_LAUNCH(2) RRT_MESH_LAUNCH(3) RRT_MESH_LAUNCH(4) RRT_MESH_LAUNCH(5) RRT_MESH_LAUNCH(6)
+    default: return hipErrorInvalidValue;
+    }
+#undef RRT_MESH_LAUNCH
+    return hipGetLastError();
+}
+
 hipError_t launch_rrt(int nj, const RrtParams &p, hipStream_t s)
 {
     const size_t lds = rrt_lds_bytes(nj, p.max_iter);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
+    const RrtArgs<RRT_MESH_NONE> a{p};
     switch (nj) {
-    case 2: hipLaunchKernelGGL(cfs_rrt_kernel<2>, dim3(p.S), dim3(WV), lds, s, p); break;
-    case 3: hipLaunchKernelGGL(cfs_rrt_kernel<3>, dim3(p.S), dim3(WV), lds, s, p); break;
-    case 4: hipLaunchKernelGGL(cfs_rrt_kernel<4>, dim3(p.S), dim3(WV), lds, s, p); break;
-    case 5: hipLaunchKernelGGL(cfs_rrt_kernel<5>, dim3(p.S), dim3(WV), lds, s, p); break;
-    case 6: hipLaunchKernelGGL(cfs_rrt_kernel<6>, dim3(p.S), dim3(WV), lds, s, p); break;
+    case 2: hipLaunchKernelGGL((cfs_rrt_kernel<2, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
+    case 3: hipLaunchKernelGGL((cfs_rrt_kernel<3, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
+    case 4: hipLaunchKernelGGL((cfs_rrt_kernel<4, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
+    case 5: hipLaunchKernelGGL((cfs_rrt_kernel<5, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
+    case 6: hipLaunchKernelGGL((cfs_rrt_kernel<6, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -255,14 +424,49 @@ int check_rrt(const cfs_rrt_desc *d, int S)
     if (d->uniforms && d->ndraw < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "ndraw must be >= 1");
     return CFS_SUCCESS;
 }
-}  // namespace
 
-extern "C" int cfs_rrt_grow_device(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out, void *stream)
+// the meshes of a cfs_rrt_grow_mesh* call -> kernel argument + variant; nothing is launched or allocated here
+int check_rrt_mesh(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, RrtMeshArgs &ma, int &variant)
+{
+    variant = RRT_MESH_NONE;
+    memset(&ma, 0, sizeof ma);
+    if (nmesh < 0 || d->nobs + nmesh > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d + nmesh %d outside 0..%d", d->nobs, nmesh, CFS_MAX_OBS);
+    if (flags & ~(CFS_RRT_MESH_PER_LANE | CFS_RRT_MESH_WAVE | CFS_RRT_MESH_SMALL_FRONTIER)) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if ((flags & CFS_RRT_MESH_PER_LANE) && (flags & (CFS_RRT_MESH_WAVE | CFS_RRT_MESH_SMALL_FRONTIER)))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "CFS_RRT_MESH_PER_LANE excludes the other flags");
+    if (nmesh == 0) return CFS_SUCCESS;
+    if (!meshes || !D_mesh) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes / D_mesh must be given");
+    for (int j = 0; j < nmesh; ++j) {
+        if (!meshes[j]) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d is NULL", j);
+        if (!std::isfinite(D_mesh[j]) || !(D_mesh[j] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "D_mesh[%d] must be finite and > 0", j);
+        if (meshes[j]->device != cfs_current_device())
+            return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d lives on device %d, the current device is %d", j, meshes[j]->device, cfs_current_device());
+        ma.m[j].nodes = meshes[j]->nodes_d; ma.m[j].tri = meshes[j]->tri_d; ma.m[j].nt = meshes[j]->nt;
+        ma.m[j].thr = D_mesh[j] > 0.0001 ? D_mesh[j] : 0.0001;                         // dist_arm_surf_200i.m:22-24 folded into the threshold
+    }
+    ma.nmesh = nmesh;
+    variant = (flags & CFS_RRT_MESH_PER_LANE) ? RRT_MESH_PER_LANE : (flags & (CFS_RRT_MESH_WAVE | CFS_RRT_MESH_SMALL_FRONTIER)) ? RRT_MESH_WAVE : RRT_MESH_DEFAULT;
+    ma.cap = (flags & CFS_RRT_MESH_SMALL_FRONTIER) ? RRT_FRONTIER_SMALL : RRT_FRONTIER_CAP;
+    if (rrt_mesh_lds_bytes(d->nstate, d->max_iter, variant) > 64 * 1024)
+        return cfs_fail(CFS_ERR_INVALID_ARG, "MAX_ITER %d does not fit next to the mesh scratch (%zu B of LDS, limit 65536)", d->max_iter,
+                        rrt_mesh_lds_bytes(d->nstate, d->max_iter, variant));
+    return CFS_SUCCESS;
+}
+
+bool out_complete(const cfs_rrt_out *out)
+{
+    return out && out->node_num && out->fail && out->parent && out->nodes && out->total_dis && out->route_len && out->route;
+}
+
+int grow_device(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int S, const cfs_rrt_out *out, void *stream)
 {
     int rc = check_rrt(d, S);
     if (rc) return rc;
-    if (!out || !out->node_num || !out->fail || !out->parent || !out->nodes || !out->total_dis || !out->route_len || !out->route)
-        return cfs_fail(CFS_ERR_INVALID_ARG, "NULL output array");
+    RrtMeshArgs ma;
+    int variant;
+    rc = check_rrt_mesh(d, nmesh, meshes, D_mesh, flags, ma, variant);
+    if (rc) return rc;
+    if (!out_complete(out)) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL output array");
     if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
     CFS_HIPCHK(hipSetDevice(cfs_current_device()));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -276,17 +480,22 @@ extern "C" int cfs_rrt_grow_device(const cfs_rrt_desc *d, int S, const cfs_rrt_o
     P.node_num = out->node_num; P.fail = out->fail; P.parent = out->parent; P.route_len = out->route_len;
     P.nodes = out->nodes; P.total_dis = out->total_dis; P.all_ee = out->all_ee; P.route = out->route;
     P.draws_used = out->draws_used; P.proposals = out->proposals;
-    hipError_t e = launch_rrt(d->nstate, P, s);
+    hipError_t e = variant == RRT_MESH_NONE ? launch_rrt(d->nstate, P, s) : launch_rrt_mesh(d->nstate, variant, P, ma, s);
     if (e != hipSuccess) return cfs_fail(CFS_ERR_HIP, "RRT launch failed: %s", hipGetErrorString(e));
     return CFS_SUCCESS;
 }
 
-extern "C" int cfs_rrt_grow(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out)
+int grow_host(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int S, const cfs_rrt_out *out)
 {
     int rc = check_rrt(d, S);
     if (rc) return rc;
-    if (!out || !out->node_num || !out->fail || !out->parent || !out->nodes || !out->total_dis || !out->route_len || !out->route)
-        return cfs_fail(CFS_ERR_INVALID_ARG, "NULL output array");
+    {   // refuse before anything is staged on the device; grow_device checks again and keeps the table (host work only, no launch)
+        RrtMeshArgs ma;
+        int variant;
+        rc = check_rrt_mesh(d, nmesh, meshes, D_mesh, flags, ma, variant);
+        if (rc) return rc;
+    }
+    if (!out_complete(out)) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL output array");
     if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
     CFS_HIPCHK(hipSetDevice(cfs_current_device()));
     const size_t nj = d->nstate, N = (size_t)d->max_iter + 1, per = d->per_tree ? (size_t)S : 1;
@@ -321,7 +530,7 @@ extern "C" int cfs_rrt_grow(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out
     if (err == hipSuccess) err = hipMemset(o.route, 0, S * N * nj * 8);
     if (err == hipSuccess && o.all_ee) err = hipMemset(o.all_ee, 0, (size_t)S * d->max_iter * 3 * 8);
     if (err == hipSuccess) {
-        rc = cfs_rrt_grow_device(&dd, S, &o, nullptr);
+        rc = grow_device(&dd, nmesh, meshes, D_mesh, flags, S, &o, nullptr);
         if (rc == CFS_SUCCESS) err = hipStreamSynchronize(nullptr);
     }
     auto down = [&](void *h, const void *dv, size_t bytes) { if (err == hipSuccess && h) err = hipMemcpy(h, dv, bytes, hipMemcpyDeviceToHost); };
@@ -336,5 +545,42 @@ extern "C" int cfs_rrt_grow(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out
     for (void *p : bufs) (void)hipFree(p);
     if (rc) return rc;
     if (err != hipSuccess) return cfs_fail(CFS_ERR_HIP, "RRT staging failed: %s", hipGetErrorString(err));
+    return CFS_SUCCESS;
+}
+}  // namespace
+
+extern "C" int cfs_rrt_grow_device(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out, void *stream)
+{
+    return grow_device(d, 0, nullptr, nullptr, 0, S, out, stream);
+}
+
+extern "C" int cfs_rrt_grow(const cfs_rrt_desc *d, int S, const cfs_rrt_out *out)
+{
+    return grow_host(d, 0, nullptr, nullptr, 0, S, out);
+}
+
+extern "C" int cfs_rrt_grow_mesh_device(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int S,
+                                        const cfs_rrt_out *out, void *stream)
+{
+    return grow_device(d, nmesh, meshes, D_mesh, flags, S, out, stream);
+}
+
+extern "C" int cfs_rrt_grow_mesh(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int S,
+                                 const cfs_rrt_out *out)
+{
+    return grow_host(d, nmesh, meshes, D_mesh, flags, S, out);
+}
+
+extern "C" int cfs_debug_rrt_frontier_overflows(unsigned long long *count, int reset)
+{
+    if (!count && !reset) return cfs_fail(CFS_ERR_INVALID_ARG, "nothing to do: count is NULL and reset is 0");
+    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
+    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
+    CFS_HIPCHK(hipDeviceSynchronize());
+    if (count) CFS_HIPCHK(hipMemcpyFromSymbol(count, HIP_SYMBOL(g_rrt_frontier_overflows), sizeof *count));
+    if (reset) {
+        const unsigned long long zero = 0ull;
+        CFS_HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_rrt_frontier_overflows), &zero, sizeof zero));
+    }
     return CFS_SUCCESS;
 }

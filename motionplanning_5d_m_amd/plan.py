@@ -4,8 +4,8 @@ The reference plans one start/goal pair (RRTstar_CFS.m): rounds of ``num_seed`` 
 (Lib/functions/s_Parallel_rrt.m:14-28), the route with the fewest nodes (:27-28), one CFS on it (RRTstar_CFS.m:94-196).
 ``RRTCFSPlanner.plan`` does that for S slots at once, entirely on the GPU:
 
-* grow   -- S*K trees in one ``cfs_rrt_grow_device`` launch; slots none of whose seeds found a route are regrown, alone, in
-            the next round (the reference's ``while all(path_fail)``);
+* grow   -- S*K trees in one ``cfs_rrt_grow_device`` launch (``cfs_rrt_grow_mesh_device`` in a cell with mesh obstacles); slots
+            none of whose seeds found a route are regrown, alone, in the next round (the reference's ``while all(path_fail)``);
 * build  -- one ``cfs_build_terms_from_ragged_routes_device`` call (cubic resampling to H+1 = 41 points + cost terms);
 * solve  -- one ``cfs_solve_batch_device`` over all S*K candidates (select="best") or over the S shortest routes
             (select="shortest", the reference's rule);
@@ -28,7 +28,7 @@ import numpy as np
 from . import _lib
 from .rrt import RRT_FANUC
 from .robotproperty2 import robotproperty2
-from .solvers import CFSBatch, _infeasible_args, _jacobian_code, _joint_limits_array, _ptr, _substeps, obs_to_array
+from .solvers import CFSBatch, _infeasible_args, _jacobian_code, _joint_limits_array, _ptr, _substeps, obs_meshes, obs_to_array
 from .sysinfo import RRTstar_CFS_problem
 
 try:
@@ -75,6 +75,11 @@ class RRTCFSPlanner:
     solve every candidate is audited with audit_substeps samples per interval (CFSBatch.clearance_device) and is eligible only if
     dist_path[j] >= margin_j - slack for every obstacle j.  A slot none of whose found routes passes keeps the candidate the
     plain rule names, with has_solution = 0.  Results then carry dist_path, dist_lower (S, nobs) and clearance_ok (S).
+    Mesh obstacles: `pobs` may end with dict(mesh=Mesh, D=..., epsilon=...) entries (after the line obstacles, as for CFS_FANUC):
+    the trees then grow around the meshes (cfs_rrt_grow_mesh_device), the smoothing handle measures them (set_meshes; their rows of
+    the obs tensor are zero) and min_clearance audits with clearance_mesh_device.  What the handle refuses is refused here: meshes
+    with on_infeasible="soften", a mesh before a line obstacle, a mesh margin that is not finite and > 0.  Without meshes the
+    planner is exactly the line-obstacle one.
     Arguments are validated before anything touches the device."""
 
     def __init__(self, pobs, sys_rrt, region_g, region_s, sample_off, ROBOT="M200i", rrt_solver="RRT", num_seed=6, mode="CFS",
@@ -97,6 +102,12 @@ class RRTCFSPlanner:
         _jacobian_code(jacobian)
         _infeasible_args(on_infeasible, soft_weight)
         _joint_limits_array(joint_limits, robotproperty2("M200i"), 5)
+        meshes = obs_meshes(pobs)                                                   # ValueError: a mesh before a line obstacle
+        if meshes and on_infeasible == "soften":
+            raise ValueError('on_infeasible="soften" does not support mesh obstacles')
+        for o in pobs:
+            if "mesh" in o and not all(isinstance(o.get(k), numbers.Real) and math.isfinite(o[k]) and o[k] > 0 for k in ("D", "epsilon")):
+                raise ValueError("a mesh obstacle needs finite D and epsilon > 0")
         if min_clearance is not None:
             if isinstance(min_clearance, bool) or not isinstance(min_clearance, numbers.Real) or not math.isfinite(min_clearance) or min_clearance < 0:
                 raise ValueError(f"min_clearance must be None or a finite slack >= 0 in metres, not {min_clearance!r}")
@@ -122,6 +133,9 @@ class RRTCFSPlanner:
                             jacobian=jacobian, on_infeasible=on_infeasible, soft_weight=soft_weight, joint_limits=joint_limits)
         one = torch.tensor(obs_to_array(pobs), dtype=torch.float64, device=device)
         self._obs = one.unsqueeze(0).expand(self.max_slots * self.K, -1, -1).contiguous()
+        self._meshes = meshes
+        if meshes:
+            self.cfs.set_meshes(meshes)
 
     def close(self):
         self.cfs.close()
@@ -250,7 +264,8 @@ class RRTCFSPlanner:
         aud = None
         if self.min_clearance is not None:                                            # one launch over every solved candidate
             mark("audit0")
-            aud = self.cfs.clearance_device(cand.x_, cand.u, terms[1], self._obs[:S * Kc], substeps=self.audit_substeps, stream=st)
+            audit = self.cfs.clearance_mesh_device if self._meshes else self.cfs.clearance_device
+            aud = audit(cand.x_, cand.u, terms[1], self._obs[:S * Kc], substeps=self.audit_substeps, stream=st)
             clear_ok = (aud.dist_path >= self.cfs._margin_on(dev)[None, :] - self.min_clearance).all(dim=1)
         mark("select0")
 

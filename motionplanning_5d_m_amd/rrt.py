@@ -15,6 +15,11 @@ Quirks kept (csrc/cfs_rrt.hip): the edge cost added is the pa
 re-parents nodes within 0.2 of the SAMPLE without propagating cost changes (:134-142); failure when node_num > MAX_ITER = 400
 (:201-205).  The near-zero branch of the reference's feasibility test is ill-formed (6x1 minus 3x1, :170); it is defined as in
 dist_arm_3D_200i_2.m:23.
+
+Mesh obstacles: the obs cell may end with ``dict(mesh=Mesh, D=...)`` entries (after the line obstacles, the convention of
+``CFS_FANUC`` and ``solvers.obs_meshes``).  feasible() then also rejects a node when a link axis comes closer to mesh j than
+``max(D_j, 1e-4)`` (M200i/dist_arm_surf_200i.m:21-24 applied to RRT_FANUC.m:146-181; include/cfs_hip.h, cfs_rrt_grow_mesh), and
+every entry point below routes to ``cfs_rrt_grow_mesh*``.  ``mesh_flags`` is the developer switch of that entry (_lib.RRT_MESH).
 """
 from __future__ import annotations
 
@@ -25,7 +30,7 @@ import numpy as np
 
 from . import _lib
 from .robotproperty2 import to_c_robot
-from .solvers import _f64, _ptr, obs_to_array
+from .solvers import _f64, _ptr, obs_meshes, obs_to_array
 
 try:
     import torch
@@ -47,8 +52,16 @@ class RRT_FANUC:
         self.ROBOT, self.SOLVER = ROBOT, SOLVER
         if SOLVER not in ("RRT", "RRT*"):
             raise ValueError("SOLVER must be 'RRT' or 'RRT*'")
-        self._obs_arr = obs_to_array(obs) if len(obs) else np.zeros((0, 6))
-        self._D = _f64([o["D"] for o in obs])
+        self._meshes = obs_meshes(obs)                       # ValueError when a mesh precedes a line obstacle
+        lines = [o for o in obs if "mesh" not in o]
+        self._obs_arr = obs_to_array(lines) if len(lines) else np.zeros((0, 6))
+        self._D = _f64([o["D"] for o in lines])
+        self._D_mesh = _f64([o["D"] for o in obs if "mesh" in o])
+        if self._meshes:
+            if not (np.isfinite(self._D_mesh).all() and (self._D_mesh > 0).all()):
+                raise ValueError("the D of a mesh obstacle must be finite and > 0")
+            if len(obs) > _lib.CFS_MAX_OBS:
+                raise ValueError(f"{len(obs)} obstacles: at most {_lib.CFS_MAX_OBS}")
 
     # ---- argument packing ----------------------------------------------------------------------------------------
     def _desc(self, conv, x0=None, goal=None, goal_th=None, per_tree=False):
@@ -67,8 +80,16 @@ class RRT_FANUC:
         d.nobs = int(self._obs_arr.shape[0])
         return d, keep
 
-    # ---- S trees, host arrays in and out (cfs_rrt_grow) -----------------------------------------------------------------
-    def grow(self, rngs=None, *, uniforms=None, seed=None, S=None, ndraw=None, max_draws=None, x0=None, goal=None, goal_th=None):
+    def _mesh_args(self, mesh_flags):
+        """(nmesh, handle array, D_mesh pointer, flags) of cfs_rrt_grow_mesh*"""
+        if isinstance(mesh_flags, bool) or not isinstance(mesh_flags, (int, np.integer)) or mesh_flags & ~sum(_lib.RRT_MESH.values()):
+            raise ValueError(f"mesh_flags must be an OR of {_lib.RRT_MESH}, not {mesh_flags!r}")
+        arr = (C.c_void_p * len(self._meshes))(*[m._h for m in self._meshes])
+        return len(self._meshes), arr, _ptr(self._D_mesh), int(mesh_flags)
+
+    # ---- S trees, host arrays in and out (cfs_rrt_grow / cfs_rrt_grow_mesh) ------------------------------------------------
+    def grow(self, rngs=None, *, uniforms=None, seed=None, S=None, ndraw=None, max_draws=None, x0=None, goal=None, goal_th=None,
+             mesh_flags=0):
         """find_route for S independent trees; returns one result per tree with the reference's field names.
         rngs: numpy Generators (ndraw uniforms are drawn from each); or uniforms: (S, ndraw) array; or seed + S: the library's
         counter-based generator.  x0 / goal / goal_th: optional (S, nstate) per-tree start and goal (default: shared)."""
@@ -100,7 +121,11 @@ class RRT_FANUC:
         o = _lib.cfs_rrt_out()
         for k in ("node_num", "fail", "parent", "nodes", "total_dis", "all_ee", "route_len", "route", "draws_used", "proposals"):
             setattr(o, k, _ptr(getattr(r, k)))
-        _lib.check(_lib.lib().cfs_rrt_grow(C.byref(d), S, C.byref(o)))
+        if self._meshes:
+            nm, arr, Dm, fl = self._mesh_args(mesh_flags)
+            _lib.check(_lib.lib().cfs_rrt_grow_mesh(C.byref(d), nm, arr, Dm, fl, S, C.byref(o)))
+        else:
+            _lib.check(_lib.lib().cfs_rrt_grow(C.byref(d), S, C.byref(o)))
         out = []
         for t in range(S):
             n, L = int(r.node_num[t]), int(r.route_len[t])
@@ -111,7 +136,7 @@ class RRT_FANUC:
         return out
 
     # ---- S trees, device-resident results (cfs_rrt_grow_device) ----------------------------------------------------------
-    def grow_device(self, S, seed, device, max_draws=None, x0=None, goal=None, goal_th=None, stream=None, want_tree=False):
+    def grow_device(self, S, seed, device, max_draws=None, x0=None, goal=None, goal_th=None, stream=None, want_tree=False, mesh_flags=0):
         """S trees from the library's generator with everything left on the GPU: returns a namespace of CUDA tensors
         (route (S, MAX_ITER+1, nstate), route_len, fail, node_num, proposals [, parent, nodes, total_dis]) -- routes go straight
         into CFSBatch.build_terms_from_ragged_routes_device.  x0 / goal [/ goal_th]: optional (S, nstate) CUDA tensors."""
@@ -133,7 +158,11 @@ class RRT_FANUC:
             setattr(o, k, _ptr(getattr(r, k)))
         if stream is None:
             stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(_lib.lib().cfs_rrt_grow_device(C.byref(d), S, C.byref(o), C.c_void_p(stream)))
+        if self._meshes:
+            nm, arr, Dm, fl = self._mesh_args(mesh_flags)
+            _lib.check(_lib.lib().cfs_rrt_grow_mesh_device(C.byref(d), nm, arr, Dm, fl, S, C.byref(o), C.c_void_p(stream)))
+        else:
+            _lib.check(_lib.lib().cfs_rrt_grow_device(C.byref(d), S, C.byref(o), C.c_void_p(stream)))
         if not want_tree:
             r.parent = r.nodes = r.total_dis = None
         return r

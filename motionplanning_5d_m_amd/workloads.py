@@ -185,3 +185,28 @@ def config5_reference_map(B=256, seed=20260105, H=50, fixture=None):
     s, batch, tri = config5(B=B, seed=seed, H=H, tri=load_map_fixture(fixture))
     batch.margin_cfs, batch.margin_psg = np.full(1, 0.25), np.full(1, 0.2)
     return s, batch, tri
+
+
+def rrt_reference_map(S=256, seed=20260105, fixture=None):
+    """A planner workload on the reference-map cell of `config5_reference_map`: S (start, goal) pairs drawn exactly as that function
+    draws them (the same generator, the same order: start = X0C + U(-0.1,0.1)^(S,5), then goal = mirror_joint1(X0C) + U(-0.1,0.1)^(S,5)),
+    the map's triangles in metres, and main_FANUC.m:59-60's margins (D = 0.2, epsilon = 0.25).  The RRT side is RRTstar_CFS.m's:
+    goal and sampling regions of ``rrt.RRTstar_problem`` (:52-64), sample_off = 0, ratial (:27); sys_rrt.x0 / goal_th are the centres.
+    Returns a namespace: S, x0, goal (S, 5), tri (nt, 3, 3), D, epsilon, sys_rrt, region_g, region_s, sample_off; ``obs_cell(mesh)``
+    gives the obs cell [dict(mesh=mesh, D=D, epsilon=epsilon)] for RRT_FANUC / RRTCFSPlanner."""
+    import os
+    from .mesh import load_map_fixture
+    if fixture is None:
+        fixture = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "assembly_line_cell.npz")
+    robot = robotproperty2("M200i")
+    mirror = X0C * np.array([-1.0, 1, 1, 1, 1])
+    rng = np.random.default_rng(seed)
+    x0 = X0C + rng.uniform(-0.1, 0.1, (S, 5))
+    goal = mirror + rng.uniform(-0.1, 0.1, (S, 5))
+    sys_rrt = SimpleNamespace(robot=robot, DH=robot.DH, nstate=5, base=robot.base, x0=X0C.copy(), goal_th=mirror,
+                              ratial=np.array([1, 1, 0.5, 0.1, 0.1]))
+    w = SimpleNamespace(S=S, x0=x0, goal=goal, tri=load_map_fixture(fixture), D=0.2, epsilon=0.25, sys_rrt=sys_rrt,
+                        region_g=np.array([np.pi / 20, np.pi / 20, np.pi / 10, np.pi / 2, np.pi / 2]),
+                        region_s=np.array([np.pi / 2, np.pi / 2, np.pi / 2, np.pi / 1.5, np.pi / 1.5]), sample_off=np.zeros(5))
+    w.obs_cell = lambda mesh: [dict(mesh=mesh, D=w.D, epsilon=w.epsilon)]
+    return w
