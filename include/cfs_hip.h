@@ -584,6 +584,12 @@ int cfs_clearance_mesh(cfs_problem *p, int B, int substeps, const double *x_, co
  * register-resident columns for PSGCFS_FANUC; <= 64); polish_tol: relative drift of an active row at the optimum that
  * triggers the projection (<= 0 = default 1e-11).  Applies to the following solves / pieces of this handle. */
 int cfs_debug_set_options(cfs_problem *p, int mask, int warm_max, double polish_tol);
+/* which tier of the fused solver a solve of this shape runs (no handle, no device touched): *tier = 0 w1 (one workgroup per compute
+ * unit), 1 w2m (two per unit, CFS_FANUC), 2 w2s (two per unit, PSGCFS_FANUC); force_w1 != 0: as under CFS_DBG_TIER_W1.
+ * per_waypoint / limits != 0: a CFS_OBS_PER_WAYPOINT handle / one with joint limits, which run the tier of the plain static shape
+ * or are refused.  CFS_ERR_INVALID_ARG, *tier unwritten, for a NULL tier, njoint outside 2..6, H outside 1..CFS_MAX_H, nobs outside
+ * 1..CFS_MAX_OBS, an unknown mode, or a shape whose handle would be refused for the on-chip budget. */
+int cfs_debug_fused_tier(int njoint, int H, int nobs, int mode, int per_waypoint, int limits, int force_w1, int *tier);
 /* cycle stamps: B > 0, out == NULL: enable for the next solves of <= B problems; out != NULL: read 12 accumulators per
  * problem (HOST pointer, synchronises); B <= 0, out == NULL: off */
 int cfs_debug_stamps(cfs_problem *p, int B, unsigned long long *out);

@@ -191,6 +191,7 @@ SYMBOLS = [
     ("cfs_cost_b", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("cfs_get_cost", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("cfs_debug_set_options", C.c_int, [_P, C.c_int, C.c_int, C.c_double]),
+    ("cfs_debug_fused_tier", C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int)]),
     ("cfs_debug_stamps", C.c_int, [_P, C.c_int, _P]),
     ("cfs_debug_trace_begin", C.c_int, [_P, C.c_int, C.c_int]),
     ("cfs_debug_trace_read", C.c_int, [_P, _P]),

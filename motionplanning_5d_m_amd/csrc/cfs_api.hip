@@ -286,12 +286,21 @@ static hipError_t launch_tier(int nj, const FusedParams &p, hipStream_t s, bool 
 {
     return lim ? launch_tier_l<T, true>(nj, p, s, analytic, soft, move) : launch_tier_l<T, false>(nj, p, s, analytic, soft, move);
 }
+// the one rule: read by launch_fused and by cfs_debug_fused_tier
+static FusedTier fused_tier(int nj, int H, int nobs, int mode, bool force_w1)
+{
+    const bool ident = mode == CFS_MODE_PSGCFS;
+    if (!force_w1 && ident && fused_fits_tier<FUSED_W2S>(nj, H, nobs)) return FUSED_W2S;
+    if (!force_w1 && !ident && fused_fits_tier<FUSED_W2M>(nj, H, nobs)) return FUSED_W2M;
+    return FUSED_W1;
+}
 hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1, bool analytic, const SoftParams *soft, bool move, bool lim)
 {
-    const bool ident = p.mode == CFS_MODE_PSGCFS;
-    if (!force_w1 && ident && fused_fits_tier<FUSED_W2S>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2S>(nj, p, s, analytic, soft, move, lim);
-    if (!force_w1 && !ident && fused_fits_tier<FUSED_W2M>(nj, p.H, p.nobs)) return launch_tier<FUSED_W2M>(nj, p, s, analytic, soft, move, lim);
-    return launch_tier<FUSED_W1>(nj, p, s, analytic, soft, move, lim);
+    switch (fused_tier(nj, p.H, p.nobs, p.mode, force_w1)) {
+    case FUSED_W2S: return launch_tier<FUSED_W2S>(nj, p, s, analytic, soft, move, lim);
+    case FUSED_W2M: return launch_tier<FUSED_W2M>(nj, p, s, analytic, soft, move, lim);
+    default: return launch_tier<FUSED_W1>(nj, p, s, analytic, soft, move, lim);
+    }
 }
 
 extern "C" {
@@ -876,6 +885,24 @@ int cfs_debug_set_options(cfs_problem *p, int mask, int warm_max, double polish_
     if (warm_max < 0 || warm_max > 64) return fail(CFS_ERR_INVALID_ARG, "warm_max %d outside 0..64", warm_max);
     p->dbg_mask = mask; p->dbg_warm_max = warm_max;
     p->dbg_polish_tol = polish_tol > 0.0 ? polish_tol : 1e-11;
+    return CFS_SUCCESS;
+}
+
+int cfs_debug_fused_tier(int njoint, int H, int nobs, int mode, int per_waypoint, int limits, int force_w1, int *tier)
+{
+    if (!tier) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (njoint < 2 || njoint > 6) return fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", njoint);
+    if (H < 1 || H > CFS_MAX_H) return fail(CFS_ERR_INVALID_ARG, "H %d outside 1..%d", H, CFS_MAX_H);
+    if (nobs < 1 || nobs > CFS_MAX_OBS) return fail(CFS_ERR_INVALID_ARG, "nobs %d outside 1..%d", nobs, CFS_MAX_OBS);
+    if (mode != CFS_MODE_CFS && mode != CFS_MODE_PSGCFS) return fail(CFS_ERR_INVALID_ARG, "unknown mode %d", mode);
+    if (!fused_fits(njoint, H, nobs))
+        return fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d exceeds the 160 KB on-chip budget of one problem", H, nobs, njoint);
+    // the admission rules of cfs_problem_set_obstacle_motion and cfs_problem_set_joint_limits, in either order of the two calls
+    if (per_waypoint && !fused_fits_move(njoint, H, nobs, mode, limits != 0))
+        return fail(CFS_ERR_INVALID_ARG, "per-waypoint obstacles: H=%d x nobs=%d x njoint=%d exceeds the on-chip budget of this shape's tier", H, nobs, njoint);
+    if (limits && !fused_fits_lim(njoint, H, nobs, mode, per_waypoint != 0))
+        return fail(CFS_ERR_INVALID_ARG, "joint limits: H=%d x nobs=%d x njoint=%d exceeds the on-chip budget of this shape's tier", H, nobs, njoint);
+    *tier = (int)fused_tier(njoint, H, nobs, mode, force_w1 != 0);
     return CFS_SUCCESS;
 }
 

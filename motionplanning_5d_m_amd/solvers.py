@@ -706,6 +706,18 @@ class CFSBatch:
         return u, lam, it, st
 
 
+FUSED_TIERS = ("w1", "w2m", "w2s")
+
+
+def fused_tier(nj, H, nobs, mode="CFS", per_waypoint=False, limits=False, force_w1=False):
+    """cfs_debug_fused_tier: index into FUSED_TIERS of the fused solver's tier that a solve of this shape runs (host only, no
+    device); CfsError for a shape no handle can have."""
+    tier = C.c_int(-1)
+    _lib.check(_lib.lib().cfs_debug_fused_tier(int(nj), int(H), int(nobs), _lib.MODE[mode], int(bool(per_waypoint)), int(bool(limits)),
+                                               int(bool(force_w1)), C.byref(tier)))
+    return tier.value
+
+
 def dist_arm(robot, theta, obs_l, want_pos=False, want_grad=False):
     """[d, linkid] = dist_arm_*(theta, base, obs_l, robot) for N configurations x nobs obstacle axes
     (theta: (N, nj); obs_l: (nobs, 6)).  want_grad: also grad (N, nobs, nj), the analytic derivative of d with respect to

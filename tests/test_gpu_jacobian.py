@@ -183,13 +183,20 @@ KINK = 1e-9
 
 @pytest.mark.parametrize("mode", ["CFS", "PSGCFS"])
 def test_every_iteration_uses_the_analytic_linearisation(gpu, O, c3, mode):
+    check_every_iteration(gpu, O, c3, mode, "default")
+
+
+def check_every_iteration(gpu, O, c3, mode, tier, idx=None, **kw):
+    """the body of the test below; tier "w1": on the w1 tier, idx: other problems, kw: further handle options"""
     s, bt = c3
-    idx = np.arange(64)
+    idx = np.arange(64) if idx is None else np.asarray(idx)
     n, H, nj = idx.size, s.H, 5
     nn = H * nj
     margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
     nz = bt.noise[idx] if (mode == "PSGCFS" and bt.noise is not None) else None
-    slv = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=n, jacobian="analytic")
+    slv = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=n, jacobian="analytic", **kw)
+    if tier == "w1":                                                 # config 3's shape runs the half-CU tiers by default
+        slv.debug_options(tier_w1=True)
     plain = slv.solve(bt.x_init[idx], bt.xR1[idx], bt.ff[idx], bt.caug[idx], bt.obs[idx], noise=nz)
     slv.log_u(True)
     got = slv.solve(bt.x_init[idx], bt.xR1[idx], bt.ff[idx], bt.caug[idx], bt.obs[idx], noise=nz)
@@ -237,7 +244,7 @@ def test_every_iteration_uses_the_analytic_linearisation(gpu, O, c3, mode):
         sens.append(np.abs(w2 - want).max() / sc if (st == 0 and st2 == 0) else np.inf)
     err, sens = np.array(err), np.array(sens)
     kink = ~(sens <= KINK)
-    print(f"[{mode}] {len(jobs)} outer iterations of {n} analytic solves: {int(kink.sum())} kinked; un-kinked max {err[~kink].max():.1e}, "
+    print(f"[{mode} {tier}] {len(jobs)} outer iterations of {n} analytic solves: {int(kink.sum())} kinked; un-kinked max {err[~kink].max():.1e}, "
           f"median {np.median(err[~kink]):.1e}")
     assert len(jobs) >= n
     assert (~kink).sum() >= 0.8 * len(jobs)

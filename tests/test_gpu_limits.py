@@ -35,6 +35,13 @@ def c3_1024(gpu):
     return workloads.config3(_dist_fn(gpu), B=1024)
 
 
+def _tier(h, tier):
+    """tier "w1": the handle's fused kernels run on the w1 tier (config 3's shape runs the half-CU tiers by default)"""
+    if tier == "w1":
+        h.debug_options(tier_w1=True)
+    return h
+
+
 def _inside(th, lim, tol=1e-9):
     return (th >= lim[:, 0] - tol) & (th <= lim[:, 1] + tol)
 
@@ -84,13 +91,18 @@ def test_inactive_limits_are_bitwise_with_per_waypoint_obstacles(gpu, mode):
 
 # ---- 2. pieces against the reference --------------------------------------------------------------------------------------------
 def test_get_con_and_qp_match_the_reference(gpu, O, c3_256):
+    check_get_con_and_qp(gpu, O, c3_256, "default")
+
+
+def check_get_con_and_qp(gpu, O, c3_256, tier):
+    """the body of the test below; tier "w1": on the w1 tier"""
     s, bt = c3_256
     H, nj, n, nn = s.H, 5, 8, s.H * 5
     lim = CELL.copy()
     lim[2, 1] = 0.35                                   # a low ceiling on joint 3: the position rows are active in these QPs
     robot = O.robotproperty2("M200i")
-    h = gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n, joint_limits=lim)
-    h0 = gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n)
+    h = _tier(gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n, joint_limits=lim), tier)
+    h0 = _tier(gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n), tier)
     assert h.rows == h0.rows + 2 * nn
     u = np.sin(np.arange(nn))[None] * 0.05 * np.ones((n, 1))
     x_u = np.stack([O.rollout(H, nj, s.robot.delta_t, bt.xR1[b], u[b]) for b in range(n)])
@@ -108,7 +120,7 @@ def test_get_con_and_qp_match_the_reference(gpu, O, c3_256):
     active = 0
     for mode in ("CFS", "PSGCFS"):
         margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
-        hm = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=n, joint_limits=lim)
+        hm = _tier(gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=n, joint_limits=lim), tier)
         lin = bt.ff[:n] if mode == "CFS" else np.tile(0.2 * np.cos(np.arange(nn)), (n, 1))   # PSGCFS: u_ to project
         ug, lam, it, st = hm.qp(lin, z, bt.xR1[:n], dist, grad)
         assert lam.shape == (n, bt.nobs * H + 6 * nn)
@@ -162,10 +174,15 @@ def c3_ref(gpu, O, c3_256):
 
 @pytest.mark.parametrize("mode,tol", [("CFS", 1e-7), ("PSGCFS", 1e-5)])
 def test_whole_solves_match_the_reference(gpu, c3_256, c3_ref, mode, tol):
+    check_whole_solves(gpu, c3_256, c3_ref, mode, tol, "default")
+
+
+def check_whole_solves(gpu, c3_256, c3_ref, mode, tol, tier):
+    """the body of the test below; tier "w1": on the w1 tier"""
     s, bt = c3_256
     idx, want, chaotic = c3_ref(mode)
     margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
-    h = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=len(idx), joint_limits=CELL)
+    h = _tier(gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=len(idx), joint_limits=CELL), tier)
     got = h.solve(bt.x_init[idx], bt.xR1[idx], bt.ff[idx], bt.caug[idx], bt.obs[idx], noise=bt.noise[idx] if mode == "PSGCFS" else None)
     print(f"{mode}: excluded as chaotic (reference moves > 1e-6 under a 1e-12 kick): {[idx[k] for k in np.nonzero(chaotic)[0]]}")
     checked = 0

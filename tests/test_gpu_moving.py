@@ -19,6 +19,13 @@ def _dist_fn(gpu):
     return lambda rb, th, ob: gpu.dist_arm(rb, th, ob)[0]
 
 
+def _tier(h, tier):
+    """tier "w1": the handle's fused kernels run on the w1 tier (config 3's shape runs the half-CU tiers by default)"""
+    if tier == "w1":
+        h.debug_options(tier_w1=True)
+    return h
+
+
 def _const_rows(obs, H):
     return np.ascontiguousarray(np.broadcast_to(obs[:, None], (obs.shape[0], H) + obs.shape[1:]))
 
@@ -63,9 +70,14 @@ def test_constant_rows_are_bitwise_the_static_handle(gpu, c3_256, mode, jacobian
 
 # ---- 2. pieces against the reference's per-waypoint get_con ------------------------------------------------------------------
 def test_linearize_and_get_con_match_the_reference(gpu, O, c3m):
+    check_linearize_and_get_con(gpu, O, c3m, "default")
+
+
+def check_linearize_and_get_con(gpu, O, c3m, tier):
+    """the body of the test below; tier "w1": on the w1 tier"""
     s, bt = c3m
     H, nj, n = s.H, 5, 4
-    h = gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n, obstacles="per_waypoint")
+    h = _tier(gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n, obstacles="per_waypoint"), tier)
     dist, lid, grad = h.linearize(bt.x_init[:n], bt.obs[:n])
     u = np.sin(np.arange(H * nj))[None] * 0.05 * np.ones((n, 1))
     x_u = np.stack([O.rollout(H, nj, s.robot.delta_t, bt.xR1[b], u[b]) for b in range(n)])
@@ -84,7 +96,7 @@ def test_linearize_and_get_con_match_the_reference(gpu, O, c3m):
         np.testing.assert_allclose(A1[b], Ar, rtol=0, atol=5e-9)
         np.testing.assert_allclose(b1[b], br, rtol=0, atol=5e-9)
     # a static handle given the rows of waypoint 1 only disagrees wherever the obstacles have moved
-    hs = gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n)
+    hs = _tier(gpu.CFSBatch(s, bt.nobs, bt.margin_cfs, max_batch=n), tier)
     ds, _, _ = hs.linearize(bt.x_init[:n], np.ascontiguousarray(bt.obs[:n, 0]))
     np.testing.assert_array_equal(ds[:, :, 0], dist[:, :, 0])
     assert np.abs(ds[:, :, -1] - dist[:, :, -1]).max() > 1e-3
@@ -95,10 +107,15 @@ def test_linearize_and_get_con_match_the_reference(gpu, O, c3m):
 # ---- 3. whole solves against the reference -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode,tol", [("CFS", 1e-7), ("PSGCFS", 1e-5)])
 def test_whole_solves_match_the_reference(gpu, O, c3m, mode, tol):
+    check_whole_solves(gpu, O, c3m, mode, tol, "default")
+
+
+def check_whole_solves(gpu, O, c3m, mode, tol, tier):
+    """the body of the test below; tier "w1": on the w1 tier"""
     s, bt = c3m
     idx = list(range(16))
     margin = bt.margin_cfs if mode == "CFS" else bt.margin_psg
-    h = gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=len(idx), obstacles="per_waypoint")
+    h = _tier(gpu.CFSBatch(s, bt.nobs, margin, mode=mode, max_batch=len(idx), obstacles="per_waypoint"), tier)
     got = h.solve(bt.x_init[idx], bt.xR1[idx], bt.ff[idx], bt.caug[idx], bt.obs[idx],
                   noise=bt.noise[idx] if mode == "PSGCFS" else None)
     want = MR.batch_moving(O, s, bt, mode, idx)

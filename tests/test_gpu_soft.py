@@ -172,12 +172,18 @@ def _config3_cases(gpu, O, s, bt, mode, idx, **kw):
 
 @pytest.mark.parametrize("mode", ["CFS", "PSGCFS"])
 def test_config3_infeasible_problems_one_step_at_a_time(gpu, O, c3, mode):
+    check_infeasible_problems_one_step_at_a_time(gpu, O, c3, mode, "default")
+
+
+def check_infeasible_problems_one_step_at_a_time(gpu, O, c3, mode, tier, n=256):
+    """the body of the test above; tier "w1": on the w1 tier, n: the first n problems"""
     s, bt = c3
-    d = _solve(gpu, s, bt, mode, np.arange(256))
+    dbg = dict(tier_w1=True) if tier == "w1" else None              # config 3's shape runs the half-CU tiers by default
+    d = _solve(gpu, s, bt, mode, np.arange(n), dbg=dbg)
     idx = np.nonzero(d.status == 2)[0]
     assert idx.size > 0
-    cases, _ = _config3_cases(gpu, O, s, bt, mode, idx)
-    _check_steps(O, cases, f"config3 {mode}")
+    cases, _ = _config3_cases(gpu, O, s, bt, mode, idx, dbg=dbg)
+    _check_steps(O, cases, f"config3 {mode} {tier}")
 
 
 @pytest.mark.parametrize("mode", ["CFS", "PSGCFS"])
