@@ -566,6 +566,81 @@ int cfs_clearance_mesh_device(cfs_problem *p, int B, int substeps, const double 
 int cfs_clearance_mesh(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
                        double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, int *tri_path);
 
+/* ---- inverse kinematics -------------------------------------------------------------------------------
+ * Every entry point above that takes a goal takes a joint vector, as the reference's drivers type it in (xg, main_FANUC.m:30,
+ * RRTstar_CFS.m:43).  This entry finds, for T Cartesian targets at once, the configuration inside the joint limits that reaches the
+ * target, passes RRT's feasible() against the line obstacles, and is nearest to a reference configuration.  No handle.
+ *   pose(theta)  FK of the chain cfs_dist_arm runs for robot.kind (theta(2) - pi/2 for M200i), then
+ *                pos = M_njoint * tool + base (as link_ends adds it) and dir = R_njoint * tool_axis; tool_axis is normalised on entry.
+ *                tool = robot.cap{njoint}.p(:,1) gives the reference's end effector all_ee (Lib/RRT_FANUC.m:186).
+ *   residual     r = [pos - target_pos] (3 rows, use_axis = 0) or [pos - target_pos; dir - target_axis] (6 rows, use_axis = 1;
+ *                every target_axis row is normalised on entry); F = r'r; e_pos / e_axis = the 2-norms of the two halves (e_axis = 0
+ *                when use_axis = 0).
+ *   Jacobian     analytic: column c = [w_c x (pos - q_c); w_c x dir] with (w_c, q_c) the axis of joint c and a point on it.
+ * One wavefront per target, one lane per restart k = 0..restarts-1.  Restart 0 starts at theta_ref clamped into [lo, hi]; restart
+ * k >= 1 at theta_c = lo_c + u*(hi_c - lo_c), u = the RRT generator above with tree = k and counter = c (the joint), so every target
+ * of a call, wherever it stands in the batch, tries the same starts.  Then, with lambda = 1e-2 and it = 0, the restart repeats:
+ *   1. F not finite (NaN or inf): state 3, end;
+ *   2. e_pos <= tol_pos and (use_axis = 0 or e_axis <= tol_axis): converged, end;
+ *   3. it == max_iter: state 1, end;
+ *   4. delta = -(J'J + lambda*I)^-1 J'r by Cholesky (a pivot that is not finite and > 0: state 3, end);
+ *   5. s = max_c |delta_c|; if s > 0.5 (rad): delta = delta*(0.5/s);
+ *   6. trial_c = theta_c + delta_c, set to lo_c if below it and to hi_c if above it;
+ *   7. if F(trial) < F (false for a NaN): theta = trial, lambda = max(lambda/10, 1e-9); else lambda = min(10*lambda, 1e9);
+ *   8. it = it + 1.
+ * A converged restart is inside the limits by construction.  Its clearance is min_j (d_j - D_j), d_j = min over the links of
+ * seg_seg_dist (distLinSeg with the near-zero surrogate: cfs_dist_arm's d), +inf when nobs = 0; it collides exactly when feasible()
+ * (Lib/RRT_FANUC.m:146-181) rejects it: some link's distance to obstacle j is < D_j, i.e. clearance < 0.
+ * States of a restart (cand_status): 0 converged and free | 1 max_iter reached | 2 converged but in collision | 3 numeric.
+ * Per target: among the restarts in state 0 the one with the smallest sum_c weight_c*((theta_c - theta_ref_c)^2) wins (plain IEEE
+ * products and sums in joint order, so a host can restate the cost to the last bit), ties to the lowest restart (a wave reduction
+ * on (cost, lane), no atomics).  status: 0 solved | 1 no restart converged | 2 every converged restart
+ * collides.  selected = the winning restart or -1; n_ok = restarts in state 0; theta, err_pos, err_axis, clearance = the winner's
+ * (rows of targets with status != 0 hold NaN, selected = -1).  cand_theta (T x restarts x njoint: where each restart ended),
+ * cand_status, cand_iter (T x restarts: `it` when it ended).  A target's results depend on neither T nor its position in the batch.
+ * CFS_ERR_INVALID_ARG, nothing written: a NULL descriptor, out, out->theta or out->status; a robot / njoint cfs_dist_arm refuses or
+ * njoint < 2; use_axis not 0 / 1; restarts outside 1..64; max_iter outside 1..1000; nobs outside 0..CFS_MAX_OBS; tolerances, tool,
+ * lo, hi, weight that are not finite, lo >= hi, weight <= 0, tol <= 0; a tool_axis that is not finite or (use_axis = 1) zero;
+ * T < 1; NULL target_pos or theta_ref; use_axis = 1 with a NULL target_axis; nobs > 0 with NULL obs or D; and, in cfs_ik_solve,
+ * whose arrays the host can read: a non-finite target_pos, target_axis, theta_ref, obs or D, a zero target_axis row.
+ * cfs_ik_solve: HOST pointers throughout, synchronises.  cfs_ik_solve_device: lo, hi, weight stay HOST pointers (njoint values, read
+ * at the call); obs, D, target_pos, target_axis, theta_ref and every array of `out` are DEVICE pointers; enqueued on `stream`, no
+ * synchronisation.  A non-finite value in a device array ends the restarts that read it in state 3. */
+typedef struct cfs_ik_desc {
+    cfs_robot robot;
+    int njoint;                 /* 2..6: the chain of cfs_dist_arm for robot.kind                                        */
+    double tool[3];             /* a point in the frame of link njoint                                                   */
+    double tool_axis[3];        /* a direction in the same frame (normalised on entry)                                   */
+    int use_axis;               /* 0: position only (3 rows) | 1: position + direction (6 rows)                          */
+    const double *lo, *hi;      /* njoint each, finite, lo < hi                                                          */
+    const double *weight;       /* njoint, > 0, or NULL = ones: the norm of "nearest to theta_ref"                       */
+    int restarts;               /* 1..64, one lane each                                                                  */
+    int max_iter;               /* 1..1000                                                                               */
+    double tol_pos, tol_axis;   /* metres / norm of the direction difference; finite, > 0                                */
+    int nobs;                   /* 0..CFS_MAX_OBS line obstacles                                                         */
+    const double *obs;          /* nobs x 6: [obs{j}.l(:,1); obs{j}.l(:,2)]                                              */
+    const double *D;            /* nobs: obs{j}.D (Lib/RRT_FANUC.m:174)                                                  */
+    unsigned long long seed;
+} cfs_ik_desc;
+typedef struct cfs_ik_out {
+    double *theta;              /* T x njoint                                                                            */
+    int *status;                /* T                                                                                     */
+    int *selected, *n_ok;       /* T (may be NULL)                                                                       */
+    double *err_pos, *err_axis, *clearance;   /* T (may be NULL)                                                         */
+    double *cand_theta;         /* T x restarts x njoint (may be NULL)                                                   */
+    int *cand_status, *cand_iter;             /* T x restarts (may be NULL)                                              */
+} cfs_ik_out;
+/* target_pos: T x 3; target_axis: T x 3 (read when use_axis = 1; may be NULL otherwise); theta_ref: T x njoint */
+int cfs_ik_solve(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+                 const cfs_ik_out *out);
+int cfs_ik_solve_device(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+                        const cfs_ik_out *out, void *stream);
+/* pose(theta) and its Jacobian for N configurations, the device functions the solver runs (HOST pointers, like cfs_dist_arm).
+ * theta: N x njoint; pos, dir: N x 3; jac: N x 6 x njoint (rows 0-2 d pos / d theta, rows 3-5 d dir / d theta; may be NULL).
+ * tool_axis must be finite and not zero.  With tool = robot.cap{njoint}.p(:,1), pos is cfs_dist_arm's pos of that end point. */
+int cfs_tool_pose(const cfs_robot *robot, int njoint, const double *tool, const double *tool_axis, int N, const double *theta,
+                  double *pos, double *dir, double *jac);
+
 /* ---- developer / test entry points -------------------------------------------------------------------
  * No caller of the path needs these; they exist so that every shortcut the solver takes can be switched off and compared
  * under pytest (tests/test_gpu_shortcuts.py), and for the cycle-stamp / step-trace probes under tools/.  All state is per

@@ -30,6 +30,12 @@
 //        RRT_FANUC(obs, sys_info, goal, region_g, region_s, sample_off, ROBOT, SOLVER).find_route() (Lib/RRT_FANUC.m:48-91) grown on the GPU;
 //        U = rand(ndraw, S): MATLAB's own rand, consumed per tree exactly as find_route consumes it (one per proposal + nstate for a random
 //        sample); S > 1 grows S seeds at once (s_Parallel_rrt.m:16's parfor) and the outputs become cells
+//   [theta, status, err_pos, clearance, selected, n_ok, err_axis] = cfs_mex('ik', obs, robot, ROBOT, target_pos, target_axis, theta_ref, opts)
+//        goal configurations for Cartesian targets (cfs_ik_solve, include/cfs_hip.h "inverse kinematics"): target_pos 3 x T, target_axis
+//        3 x T or [] (position only), theta_ref njoint x T (njoint = its rows); obs = line obstacles (.l, .D; may be {}), a mesh obstacle
+//        is refused; opts (optional struct): lo, hi (default robot.thetamax(1:njoint,:)), tool, tool_axis (default robot.cap{njoint}.p(:,1)
+//        and the unit vector towards p(:,2)), weight, restarts (64), max_iter (100), tol_pos (1e-6), tol_axis (1e-6), seed (0).
+//        theta njoint x T (NaN columns where status ~= 0), the others 1 x T; selected is 1-based (0: none)
 //   Cost_b = cfs_mex('cost_b', sys_info, ROBOT)                    % EVAL.get_Cost_b (Lib/EVAL.m:75-78, main_FANUC.m:131-132)
 //   h = cfs_mex('mesh_load_stl', path, scale, map_from_stl)        % Lib/functions/MapFromSTL.m
 //   [dis, points] = cfs_mex('mesh_segment_distance', h, seg6)      % point2surface_dis (M200i/dist_arm_surf_200i.m:21)
@@ -350,6 +356,67 @@ static void rrt(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     for (int k = 0; k < 6; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
 }
 
+// goal configurations for Cartesian targets (cfs_ik_solve; the reference's drivers type xg in, main_FANUC.m:30, RRTstar_CFS.m:43)
+static void ik(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs < 7) mexErrMsgTxt("[theta, status, err_pos, clearance, selected, n_ok, err_axis] = cfs_mex('ik', obs, robot, ROBOT, target_pos, target_axis, theta_ref [, opts])");
+    const mxArray *obs = prhs[1], *robot = prhs[2], *opts = nrhs > 7 ? prhs[7] : nullptr;
+    const std::string ROBOT = mxArrayToString(prhs[3]);
+    const int nj = (int)mxGetM(prhs[6]), T = (int)mxGetN(prhs[4]);
+    if (mxGetM(prhs[4]) != 3 || (int)mxGetN(prhs[6]) != T) mexErrMsgTxt("target_pos must be 3 x T and theta_ref njoint x T");
+    const bool use_axis = !mxIsEmpty(prhs[5]);
+    if (use_axis && (mxGetM(prhs[5]) != 3 || (int)mxGetN(prhs[5]) != T)) mexErrMsgTxt("target_axis must be 3 x T or []");
+    cfs_ik_desc d;
+    memset(&d, 0, sizeof d);
+    fill_robot(robot, ROBOT.c_str(), nj, d.robot);
+    d.njoint = nj; d.use_axis = use_axis ? 1 : 0;
+    auto opt = [&](const char *name) -> const mxArray * { const mxArray *f = opts ? mxGetField(opts, 0, name) : nullptr; return f && !mxIsEmpty(f) ? f : nullptr; };
+    auto num = [&](const char *name, double dflt) { const mxArray *f = opt(name); return f ? mxGetScalar(f) : dflt; };
+    // joint ranges: opts.lo / opts.hi, else robot.thetamax(1:njoint,:) (nlink x 2 column-major)
+    std::vector<double> lo(nj), hi(nj);
+    const mxArray *tm = mxGetField(robot, 0, "thetamax");
+    for (int c = 0; c < nj; ++c) {
+        if (opt("lo") && opt("hi")) { lo[c] = mxGetPr(opt("lo"))[c]; hi[c] = mxGetPr(opt("hi"))[c]; }
+        else if (tm && (int)mxGetM(tm) >= nj) { lo[c] = mxGetPr(tm)[c]; hi[c] = mxGetPr(tm)[mxGetM(tm) + c]; }
+        else mexErrMsgTxt("joint ranges: give opts.lo and opts.hi, or robot.thetamax");
+    }
+    d.lo = lo.data(); d.hi = hi.data();
+    d.weight = opt("weight") ? mxGetPr(opt("weight")) : nullptr;
+    // tool: opts.tool / opts.tool_axis, else the end effector of Lib/RRT_FANUC.m:186 and the axis of its capsule
+    const double *cp = d.robot.cap + 6 * (nj - 1);
+    double ax[3] = {cp[3] - cp[0], cp[4] - cp[1], cp[5] - cp[2]};
+    if (ax[0] == 0.0 && ax[1] == 0.0 && ax[2] == 0.0) ax[2] = 1.0;
+    for (int q = 0; q < 3; ++q) {
+        d.tool[q] = opt("tool") ? mxGetPr(opt("tool"))[q] : cp[q];
+        d.tool_axis[q] = opt("tool_axis") ? mxGetPr(opt("tool_axis"))[q] : ax[q];
+    }
+    d.restarts = (int)num("restarts", 64); d.max_iter = (int)num("max_iter", 100);
+    d.tol_pos = num("tol_pos", 1e-6); d.tol_axis = num("tol_axis", 1e-6);
+    d.seed = (unsigned long long)num("seed", 0);
+    std::vector<double> obs6, D;
+    const int ncell = (int)mxGetNumberOfElements(obs);
+    for (int j = 0; j < ncell; ++j) {
+        const mxArray *o = mxGetCell(obs, j), *fl = o ? mxGetField(o, 0, "l") : nullptr, *fD = o ? mxGetField(o, 0, "D") : nullptr;
+        if (o && mxGetField(o, 0, "mesh")) mexErrMsgTxt("'ik' reads line obstacles only: mesh obstacles are not supported");
+        if (!fl || !fD || mxGetNumberOfElements(fl) != 6) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .l (3x2) and .D", j + 1);
+        obs6.insert(obs6.end(), mxGetPr(fl), mxGetPr(fl) + 6);
+        D.push_back(mxGetScalar(fD));
+    }
+    d.nobs = (int)D.size(); d.obs = obs6.data(); d.D = D.data();
+    mxArray *o_th = mxCreateDoubleMatrix(nj, T, mxREAL);                              // T x njoint row-major = njoint x T column-major
+    mxArray *o_d[3] = {mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL)};
+    std::vector<int> status(T), selected(T), n_ok(T);
+    cfs_ik_out o;
+    memset(&o, 0, sizeof o);
+    o.theta = mxGetPr(o_th); o.status = status.data(); o.selected = selected.data(); o.n_ok = n_ok.data();
+    o.err_pos = mxGetPr(o_d[0]); o.clearance = mxGetPr(o_d[1]); o.err_axis = mxGetPr(o_d[2]);
+    check(cfs_ik_solve(&d, T, mxGetPr(prhs[4]), use_axis ? mxGetPr(prhs[5]) : nullptr, mxGetPr(prhs[6]), &o));
+    mxArray *o_i[3] = {mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL)};
+    for (int t = 0; t < T; ++t) { mxGetPr(o_i[0])[t] = status[t]; mxGetPr(o_i[1])[t] = selected[t] + 1; mxGetPr(o_i[2])[t] = n_ok[t]; }
+    mxArray *outs[7] = {o_th, o_i[0], o_d[0], o_d[1], o_i[1], o_i[2], o_d[2]};
+    for (int k = 0; k < 7; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
+}
+
 // Cost_b = EVAL(sys_info).get_Cost_b()  (Lib/EVAL.m:75-78)
 static void cost_b(mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
@@ -390,6 +457,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         dist_arm(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "rrt") {
         rrt(nlhs, plhs, nrhs, prhs);
+    } else if (cmd == "ik") {
+        ik(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "cost_b") {
         cost_b(plhs, nrhs, prhs);
     } else if (cmd == "mesh_load_stl") {

@@ -33,6 +33,8 @@ MODE = {"CFS": 0, "PSGCFS": 1}
 JACOBIAN = {"fd_literal": 0, "analytic": 1}   # cfs_jacobian_mode
 INFEASIBLE = {"stop": 0, "soften": 1}          # cfs_infeasible_policy
 OBSTACLES = {"static": 0, "per_waypoint": 1}    # cfs_obstacle_motion
+IK_STATUS = {0: "SOLVED", 1: "NOT_CONVERGED", 2: "IN_COLLISION"}                       # cfs_ik_out.status
+IK_CAND_STATUS = {0: "CONVERGED", 1: "MAX_ITER", 2: "IN_COLLISION", 3: "NUMERIC"}      # cfs_ik_out.cand_status
 
 
 class CfsError(RuntimeError):
@@ -152,6 +154,42 @@ class cfs_rrt_out(C.Structure):
     ]
 
 
+class cfs_ik_desc(C.Structure):
+    _fields_ = [
+        ("robot", cfs_robot),
+        ("njoint", C.c_int),
+        ("tool", C.c_double * 3),
+        ("tool_axis", C.c_double * 3),
+        ("use_axis", C.c_int),
+        ("lo", C.c_void_p),
+        ("hi", C.c_void_p),
+        ("weight", C.c_void_p),
+        ("restarts", C.c_int),
+        ("max_iter", C.c_int),
+        ("tol_pos", C.c_double),
+        ("tol_axis", C.c_double),
+        ("nobs", C.c_int),
+        ("obs", C.c_void_p),
+        ("D", C.c_void_p),
+        ("seed", C.c_ulonglong),
+    ]
+
+
+class cfs_ik_out(C.Structure):
+    _fields_ = [
+        ("theta", C.c_void_p),
+        ("status", C.c_void_p),
+        ("selected", C.c_void_p),
+        ("n_ok", C.c_void_p),
+        ("err_pos", C.c_void_p),
+        ("err_axis", C.c_void_p),
+        ("clearance", C.c_void_p),
+        ("cand_theta", C.c_void_p),
+        ("cand_status", C.c_void_p),
+        ("cand_iter", C.c_void_p),
+    ]
+
+
 # every symbol include/cfs_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -213,6 +251,9 @@ SYMBOLS = [
     ("cfs_clearance", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("cfs_clearance_mesh_device", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("cfs_clearance_mesh", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("cfs_ik_solve", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out)]),
+    ("cfs_ik_solve_device", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out), _P]),
+    ("cfs_tool_pose", C.c_int, [C.POINTER(cfs_robot), C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)

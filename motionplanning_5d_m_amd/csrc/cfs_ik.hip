@@ -1,0 +1,555 @@
+// cfs_ik.hip -- batched collision-aware inverse kinematics (include/cfs_hip.h, "inverse kinematics").
+//
+// The reference has no inverse kinematics: its drivers type the goal in as a joint vector (xg, main_FANUC.m:30, RRTstar_CFS.m:43).
+// What it does define is used as it is: the chain of CapPos.m:13-20 / CapPos2.m:19-28 (fk_step), the end effector
+// all_ee = pos{nstate}.p(:,1) (Lib/RRT_FANUC.m:186), feasible() (Lib/RRT_FANUC.m:146-181) and the joint ranges robot.thetamax.
+//
+// MI355X mapping.  One 64-lane wavefront owns one target, one lane one restart of a damped least-squares (Levenberg-Marquardt)
+// iteration, the contract's steps 1-8 literally.  A lane keeps theta, the 3x4 chain, the 6 x NJ Jacobian, the NJ x NJ normal
+// matrix and its Cholesky factor in registers (every loop over joints is unrolled at compile time: NJ is a template parameter);
+// the robot, the obstacle rows and their margins are staged once per workgroup (4 waves = 4 targets) in LDS.  Restarts of one
+// target end at different iterations: a lane that has ended idles under the EXEC mask until a ballot says that none is running,
+// so every lane reaches the selection, a wave argmin on (cost, lane) by xor shuffles.  No atomics, no block barrier after the
+// staging, no host round trip.  Everything is fp64.
+#include "cfs_geom_dev.h"
+#include "cfs_host.h"
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+namespace {
+
+constexpr int WV = 64;
+constexpr int IK_WAVES = 4;                                   // targets per workgroup
+constexpr double IK_LAMBDA0 = 1e-2, IK_LAMBDA_MIN = 1e-9, IK_LAMBDA_MAX = 1e9, IK_STEP_CAP = 0.5;
+
+struct IkParams {
+    DevRobot rb;                                              // by value, as in RrtParams: no device allocation in the _device entry
+    int T, R, nobs, use_axis, max_iter;
+    double tool[3], axis[3];                                  // axis normalised on the host
+    double lo[6], hi[6], w[6];
+    double tol_pos, tol_axis;
+    unsigned long long seed;
+    const double *obs, *D;                                    // nobs x 6, nobs
+    const double *target_pos, *target_axis, *theta_ref;       // T x 3, T x 3 (use_axis), T x NJ
+    double *theta;                                            // T x NJ
+    int *status, *selected, *n_ok;                            // T
+    double *err_pos, *err_axis, *clearance;                   // T
+    double *cand_theta;                                       // T x R x NJ
+    int *cand_status, *cand_iter;                             // T x R
+};
+
+struct PoseParams {
+    DevRobot rb;
+    int N;
+    double tool[3], axis[3];
+    const double *theta;                                      // N x NJ
+    double *pos, *dir, *jac;                                  // N x 3, N x 3, N x 6 x NJ (may be null)
+};
+
+// the RRT generator (include/cfs_hip.h, "RRT / RRT*") with tree = restart, counter = joint
+__device__ __forceinline__ double ik_uniform(unsigned long long seed, int restart, int joint)
+{
+    unsigned long long z = seed + (unsigned long long)restart * 0x9E3779B97F4A7C15ull + ((unsigned long long)joint + 1ull) * 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (double)(z >> 11) * 0x1.0p-53;
+}
+
+// pose(theta): tool point (link_ends' expression, base added) and tool direction in the world frame, and the twist of every joint
+template <int NJ>
+__device__ __forceinline__ void ik_pose(const DevRobot *rb, const double *tool, const double *axis, const double *th, double *p, double *a,
+                                        double *tw)
+{
+    double M[12], Mn[12];
+#pragma unroll
+    for (int k = 0; k < NJ; ++k) {
+        joint_twist(rb, k, k == 0 ? nullptr : M, tw + k * 6);
+        double sn, cs;
+        sincos(th[k] - rb->th_off[k], &sn, &cs);
+        fk_step(rb, k, sn, cs, k == 0 ? nullptr : M, Mn);
+#pragma unroll
+        for (int q = 0; q < 12; ++q) M[q] = Mn[q];
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        p[r] = (M[r * 4 + 0] * tool[0] + M[r * 4 + 1] * tool[1] + M[r * 4 + 2] * tool[2]) + M[r * 4 + 3] + rb->base[r];
+        a[r] = M[r * 4 + 0] * axis[0] + M[r * 4 + 1] * axis[1] + M[r * 4 + 2] * axis[2];
+    }
+}
+
+// column c of the Jacobian: [w x (p - q); w x a]
+__device__ __forceinline__ void ik_jac_col(const double *tw6, const double *p, const double *a, double *j6)
+{
+    const double wx = tw6[0], wy = tw6[1], wz = tw6[2];
+    const double rx = p[0] - tw6[3], ry = p[1] - tw6[4], rz = p[2] - tw6[5];
+    j6[0] = wy * rz - wz * ry; j6[1] = wz * rx - wx * rz; j6[2] = wx * ry - wy * rx;
+    j6[3] = wy * a[2] - wz * a[1]; j6[4] = wz * a[0] - wx * a[2]; j6[5] = wx * a[1] - wy * a[0];
+}
+
+// A = J'J (full symmetric, row-major) and g = J'r over the first M rows (3 | 6)
+template <int NJ>
+__device__ __forceinline__ void ik_normal(const double *tw, const double *p, const double *a, const double *r, bool use_axis, double *A, double *g)
+{
+    double J[NJ * 6];
+#pragma unroll
+    for (int c = 0; c < NJ; ++c) {
+        ik_jac_col(tw + c * 6, p, a, J + c * 6);
+        if (!use_axis) { J[c * 6 + 3] = 0.0; J[c * 6 + 4] = 0.0; J[c * 6 + 5] = 0.0; }
+    }
+#pragma unroll
+    for (int c = 0; c < NJ; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) s += J[c * 6 + q] * r[q];
+        g[c] = s;
+#pragma unroll
+        for (int e = 0; e <= c; ++e) {
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) v += J[c * 6 + q] * J[e * 6 + q];
+            A[c * NJ + e] = v; A[e * NJ + c] = v;
+        }
+    }
+}
+
+// delta = -(A + lam I)^-1 g by Cholesky; false when a pivot is not finite and > 0
+template <int NJ>
+__device__ __forceinline__ bool ik_solve_step(const double *A, const double *g, double lam, double *delta)
+{
+    double L[NJ * NJ];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        double s = A[j * NJ + j] + lam;
+#pragma unroll
+        for (int k = 0; k < j; ++k) s -= L[j * NJ + k] * L[j * NJ + k];
+        ok = ok && (s > 0.0) && (s < INFINITY);
+        const double dj = sqrt(s);
+        L[j * NJ + j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < NJ; ++i) {
+            double t = A[i * NJ + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) t -= L[i * NJ + k] * L[j * NJ + k];
+            L[i * NJ + j] = t / dj;
+        }
+    }
+    double y[NJ];
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) {
+        double t = -g[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) t -= L[i * NJ + k] * y[k];
+        y[i] = t / L[i * NJ + i];
+    }
+#pragma unroll
+    for (int i = NJ - 1; i >= 0; --i) {
+        double t = y[i];
+#pragma unroll
+        for (int k = i + 1; k < NJ; ++k) t -= L[k * NJ + i] * delta[k];
+        delta[i] = t / L[i * NJ + i];
+    }
+    return ok;
+}
+
+__device__ __forceinline__ void ik_residual(const double *p, const double *a, const double *tp, const double *ta, bool use_axis, double *r,
+                                            double *F)
+{
+    r[0] = p[0] - tp[0]; r[1] = p[1] - tp[1]; r[2] = p[2] - tp[2];
+    r[3] = use_axis ? a[0] - ta[0] : 0.0; r[4] = use_axis ? a[1] - ta[1] : 0.0; r[5] = use_axis ? a[2] - ta[2] : 0.0;
+    *F = (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) + (r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+}
+
+// min_j (d_j - D_j), d_j = cfs_dist_arm's distance to obstacle j; +inf without obstacles
+template <int NJ>
+__device__ __forceinline__ double ik_clearance(const DevRobot *rb, const double *th, int nobs, const double *obs, const double *D)
+{
+    double ends[NJ * 6], M[12], Mn[12];
+#pragma unroll
+    for (int k = 0; k < NJ; ++k) {
+        double sn, cs;
+        sincos(th[k] - rb->th_off[k], &sn, &cs);
+        fk_step(rb, k, sn, cs, k == 0 ? nullptr : M, Mn);
+#pragma unroll
+        for (int q = 0; q < 12; ++q) M[q] = Mn[q];
+        link_ends(rb, k, M, ends + k * 6);
+    }
+    double c = INFINITY;
+    for (int j = 0; j < nobs; ++j) {
+        double o6[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) o6[q] = obs[j * 6 + q];
+        double d = INFINITY;
+#pragma unroll
+        for (int k = 0; k < NJ; ++k) {
+            const double dis = seg_seg_dist(ends + k * 6, o6);
+            if (dis < d) d = dis;
+        }
+        const double m = d - D[j];
+        if (m < c || m != m) c = m;                           // a NaN sticks: the restart then counts as colliding
+    }
+    return c;
+}
+
+template <int NJ>
+__global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkParams P)
+{
+    __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
+    __shared__ double s_obs[CFS_MAX_OBS * 6];
+    __shared__ double s_D[CFS_MAX_OBS];
+    {
+        const double *src = reinterpret_cast<const double *>(&P.rb);
+        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += WV * IK_WAVES) s_rb[e] = src[e];
+        for (int e = threadIdx.x; e < P.nobs * 6; e += WV * IK_WAVES) s_obs[e] = P.obs[e];
+        for (int e = threadIdx.x; e < P.nobs; e += WV * IK_WAVES) s_D[e] = P.D[e];
+    }
+    __syncthreads();                                          // the only block barrier: whole waves may leave after it
+    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    const int lane = threadIdx.x % WV, t = blockIdx.x * IK_WAVES + threadIdx.x / WV;
+    if (t >= P.T) return;
+    const bool use_axis = P.use_axis != 0;
+    const bool active = lane < P.R;                           // lanes >= restarts idle and enter the reductions with neutral values
+
+    double tp[3], ta[3] = {0.0, 0.0, 0.0}, tref[NJ], th[NJ];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) tp[q] = P.target_pos[(size_t)t * 3 + q];
+    if (use_axis) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) ta[q] = P.target_axis[(size_t)t * 3 + q];
+        const double n = sqrt(ta[0] * ta[0] + ta[1] * ta[1] + ta[2] * ta[2]);
+        ta[0] = ta[0] / n; ta[1] = ta[1] / n; ta[2] = ta[2] / n;
+    }
+#pragma unroll
+    for (int c = 0; c < NJ; ++c) {
+        tref[c] = P.theta_ref[(size_t)t * NJ + c];
+        const double x = lane == 0 ? tref[c] : P.lo[c] + ik_uniform(P.seed, lane, c) * (P.hi[c] - P.lo[c]);
+        th[c] = x < P.lo[c] ? P.lo[c] : (x > P.hi[c] ? P.hi[c] : x);          // a NaN passes: state 3 below
+    }
+
+    double p[3], a[3], tw[NJ * 6], r[6], F = 0.0, A[NJ * NJ], g[NJ], lam = IK_LAMBDA0;
+    int st = active ? -1 : 1, it = 0;                         // -1: running
+#pragma unroll
+    for (int q = 0; q < 6; ++q) r[q] = 0.0;
+    if (active) {
+        ik_pose<NJ>(rb, P.tool, P.axis, th, p, a, tw);
+        ik_residual(p, a, tp, ta, use_axis, r, &F);
+        ik_normal<NJ>(tw, p, a, r, use_axis, A, g);
+    }
+    for (;;) {
+        if (st < 0) {
+            const double ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+            if (!(F < INFINITY)) st = 3;                                                        // step 1
+            else if (ep <= P.tol_pos && (!use_axis || ea <= P.tol_axis)) st = 0;                // step 2
+            else if (it >= P.max_iter) st = 1;                                                  // step 3
+        }
+        if (__ballot(st < 0) == 0ull) break;
+        if (st < 0) {
+            double delta[NJ], trial[NJ];
+            if (!ik_solve_step<NJ>(A, g, lam, delta)) st = 3;                                   // step 4
+            else {
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < NJ; ++c) s = fabs(delta[c]) > s ? fabs(delta[c]) : s;
+                const double sc = s > IK_STEP_CAP ? IK_STEP_CAP / s : 1.0;                      // step 5
+#pragma unroll
+                for (int c = 0; c < NJ; ++c) {
+                    const double x = th[c] + (s > IK_STEP_CAP ? delta[c] * sc : delta[c]);
+                    trial[c] = x < P.lo[c] ? P.lo[c] : (x > P.hi[c] ? P.hi[c] : x);            // step 6
+                }
+                double p2[3], a2[3], tw2[NJ * 6], r2[6], F2;
+                ik_pose<NJ>(rb, P.tool, P.axis, trial, p2, a2, tw2);
+                ik_residual(p2, a2, tp, ta, use_axis, r2, &F2);
+                if (F2 < F) {                                                                   // step 7
+#pragma unroll
+                    for (int c = 0; c < NJ; ++c) th[c] = trial[c];
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) r[q] = r2[q];
+                    F = F2;
+                    ik_normal<NJ>(tw2, p2, a2, r2, use_axis, A, g);
+                    lam = lam / 10.0 > IK_LAMBDA_MIN ? lam / 10.0 : IK_LAMBDA_MIN;
+                } else {
+                    lam = lam * 10.0 < IK_LAMBDA_MAX ? lam * 10.0 : IK_LAMBDA_MAX;
+                }
+                ++it;                                                                           // step 8
+            }
+        }
+    }
+
+    // ---- collision, cost, selection ---------------------------------------------------------------------------------------
+    const double ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+    double clear = INFINITY, cost = INFINITY;
+    if (st == 0) {
+        clear = ik_clearance<NJ>(rb, th, P.nobs, s_obs, s_D);
+        if (!(clear >= 0.0)) st = 2;
+    }
+    if (st == 0) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) {                        // w*(d*d), summed in joint order, no FMA: the contract's cost to the last bit
+            const double dlt = th[c] - tref[c];
+            s = __dadd_rn(s, __dmul_rn(P.w[c], __dmul_rn(dlt, dlt)));
+        }
+        if (s < INFINITY) cost = s; else st = 3;
+    }
+    if (active) {
+        const size_t row = (size_t)t * P.R + lane;
+        if (P.cand_theta) {
+#pragma unroll
+            for (int c = 0; c < NJ; ++c) P.cand_theta[row * NJ + c] = th[c];
+        }
+        if (P.cand_status) P.cand_status[row] = st;
+        if (P.cand_iter) P.cand_iter[row] = it;
+    }
+    const int n_ok = __popcll(__ballot(st == 0));
+    const bool any_hit = __ballot(st == 2) != 0ull;
+    double bc = cost;
+    int bl = lane;
+#pragma unroll
+    for (int m = 1; m < WV; m <<= 1) {
+        const double oc = __shfl_xor(bc, m, WV);
+        const int ol = __shfl_xor(bl, m, WV);
+        if (oc < bc || (oc == bc && ol < bl)) { bc = oc; bl = ol; }
+    }
+    const double nan = __builtin_nan("");
+    if (n_ok > 0 ? lane == bl : lane == 0) {
+        const bool ok = n_ok > 0;
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) P.theta[(size_t)t * NJ + c] = ok ? th[c] : nan;
+        P.status[t] = ok ? 0 : (any_hit ? 2 : 1);
+        if (P.selected) P.selected[t] = ok ? lane : -1;
+        if (P.n_ok) P.n_ok[t] = n_ok;
+        if (P.err_pos) P.err_pos[t] = ok ? ep : nan;
+        if (P.err_axis) P.err_axis[t] = ok ? ea : nan;
+        if (P.clearance) P.clearance[t] = ok ? clear : nan;
+    }
+}
+
+// cfs_tool_pose: one thread per configuration, the solver's own device functions
+template <int NJ>
+__global__ __launch_bounds__(256) void cfs_tool_pose_kernel(const PoseParams P)
+{
+    __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
+    {
+        const double *src = reinterpret_cast<const double *>(&P.rb);
+        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += 256) s_rb[e] = src[e];
+    }
+    __syncthreads();
+    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= P.N) return;
+    double th[NJ], p[3], a[3], tw[NJ * 6];
+#pragma unroll
+    for (int c = 0; c < NJ; ++c) th[c] = P.theta[(size_t)n * NJ + c];
+    ik_pose<NJ>(rb, P.tool, P.axis, th, p, a, tw);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { P.pos[(size_t)n * 3 + q] = p[q]; P.dir[(size_t)n * 3 + q] = a[q]; }
+    if (P.jac) {
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) {
+            double j6[6];
+            ik_jac_col(tw + c * 6, p, a, j6);
+#pragma unroll
+            for (int q = 0; q < 6; ++q) P.jac[((size_t)n * 6 + q) * NJ + c] = j6[q];
+        }
+    }
+}
+
+hipError_t launch_ik(int nj, const IkParams &p, hipStream_t s)
+{
+    const dim3 grid((p.T + IK_WAVES - 1) / IK_WAVES), block(WV * IK_WAVES);
+    switch (nj) {
+    case 2: hipLaunchKernelGGL(cfs_ik_kernel<2>, grid, block, 0, s, p); break;
+    case 3: hipLaunchKernelGGL(cfs_ik_kernel<3>, grid, block, 0, s, p); break;
+    case 4: hipLaunchKernelGGL(cfs_ik_kernel<4>, grid, block, 0, s, p); break;
+    case 5: hipLaunchKernelGGL(cfs_ik_kernel<5>, grid, block, 0, s, p); break;
+    case 6: hipLaunchKernelGGL(cfs_ik_kernel<6>, grid, block, 0, s, p); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_tool_pose(int nj, const PoseParams &p, hipStream_t s)
+{
+    const dim3 grid((p.N + 255) / 256), block(256);
+    switch (nj) {
+    case 2: hipLaunchKernelGGL(cfs_tool_pose_kernel<2>, grid, block, 0, s, p); break;
+    case 3: hipLaunchKernelGGL(cfs_tool_pose_kernel<3>, grid, block, 0, s, p); break;
+    case 4: hipLaunchKernelGGL(cfs_tool_pose_kernel<4>, grid, block, 0, s, p); break;
+    case 5: hipLaunchKernelGGL(cfs_tool_pose_kernel<5>, grid, block, 0, s, p); break;
+    case 6: hipLaunchKernelGGL(cfs_tool_pose_kernel<6>, grid, block, 0, s, p); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ---- C ABI (include/cfs_hip.h, "inverse kinematics") ----------------------------------------------------------------------------
+bool finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+bool all_finite(const double *v, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+// everything of a call that is host memory in both entries; fills the by-value part of the kernel's parameter block
+int check_ik(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref, const cfs_ik_out *out,
+             IkParams &P)
+{
+    if (!d) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL descriptor");
+    int rc = cfs_check_robot(&d->robot, d->njoint);
+    if (rc) return rc;
+    const int nj = d->njoint;
+    if (nj < 2) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", nj);
+    if (d->use_axis != 0 && d->use_axis != 1) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis must be 0 or 1, not %d", d->use_axis);
+    if (d->restarts < 1 || d->restarts > WV) return cfs_fail(CFS_ERR_INVALID_ARG, "restarts %d outside 1..%d", d->restarts, WV);
+    if (d->max_iter < 1 || d->max_iter > 1000) return cfs_fail(CFS_ERR_INVALID_ARG, "max_iter %d outside 1..1000", d->max_iter);
+    if (d->nobs < 0 || d->nobs > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d outside 0..%d", d->nobs, CFS_MAX_OBS);
+    if (d->nobs > 0 && (!d->obs || !d->D)) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be given");
+    if (!(std::isfinite(d->tol_pos) && d->tol_pos > 0.0 && std::isfinite(d->tol_axis) && d->tol_axis > 0.0))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "tol_pos / tol_axis must be finite and > 0");
+    if (!finite3(d->tool) || !finite3(d->tool_axis)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool / tool_axis must be finite");
+    const double an = std::sqrt(d->tool_axis[0] * d->tool_axis[0] + d->tool_axis[1] * d->tool_axis[1] + d->tool_axis[2] * d->tool_axis[2]);
+    if (d->use_axis && !(an > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool_axis is zero");
+    if (!d->lo || !d->hi) return cfs_fail(CFS_ERR_INVALID_ARG, "lo / hi must be given");
+    for (int c = 0; c < nj; ++c) {
+        if (!std::isfinite(d->lo[c]) || !std::isfinite(d->hi[c]) || !(d->lo[c] < d->hi[c]))
+            return cfs_fail(CFS_ERR_INVALID_ARG, "joint %d: lo / hi must be finite with lo < hi", c);
+        if (d->weight && !(std::isfinite(d->weight[c]) && d->weight[c] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "weight[%d] must be finite and > 0", c);
+    }
+    if (T < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "at least one target is needed");
+    if (!target_pos || !theta_ref) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL target_pos / theta_ref");
+    if (d->use_axis && !target_axis) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis = 1 needs target_axis");
+    if (!out || !out->theta || !out->status) return cfs_fail(CFS_ERR_INVALID_ARG, "out, out->theta and out->status must be given");
+    memset(&P, 0, sizeof P);
+    cfs_build_dev_robot(d->robot, P.rb);
+    P.T = T; P.R = d->restarts; P.nobs = d->nobs; P.use_axis = d->use_axis; P.max_iter = d->max_iter;
+    for (int q = 0; q < 3; ++q) { P.tool[q] = d->tool[q]; P.axis[q] = an > 0.0 ? d->tool_axis[q] / an : 0.0; }
+    for (int c = 0; c < nj; ++c) { P.lo[c] = d->lo[c]; P.hi[c] = d->hi[c]; P.w[c] = d->weight ? d->weight[c] : 1.0; }
+    P.tol_pos = d->tol_pos; P.tol_axis = d->tol_axis; P.seed = d->seed;
+    return CFS_SUCCESS;
+}
+
+void ik_point(IkParams &P, const double *obs, const double *D, const double *target_pos, const double *target_axis, const double *theta_ref,
+              const cfs_ik_out *o)
+{
+    P.obs = obs; P.D = D; P.target_pos = target_pos; P.target_axis = target_axis; P.theta_ref = theta_ref;
+    P.theta = o->theta; P.status = o->status; P.selected = o->selected; P.n_ok = o->n_ok;
+    P.err_pos = o->err_pos; P.err_axis = o->err_axis; P.clearance = o->clearance;
+    P.cand_theta = o->cand_theta; P.cand_status = o->cand_status; P.cand_iter = o->cand_iter;
+}
+}  // namespace
+
+extern "C" int cfs_ik_solve_device(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+                                   const cfs_ik_out *out, void *stream)
+{
+    static_assert(sizeof(IkParams) <= 4096, "the parameter block travels as a kernel argument");
+    IkParams P;
+    int rc = check_ik(d, T, target_pos, target_axis, theta_ref, out, P);
+    if (rc) return rc;
+    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
+    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
+    ik_point(P, d->obs, d->D, target_pos, target_axis, theta_ref, out);
+    hipError_t e = launch_ik(d->njoint, P, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return cfs_fail(CFS_ERR_HIP, "IK launch failed: %s", hipGetErrorString(e));
+    return CFS_SUCCESS;
+}
+
+extern "C" int cfs_ik_solve(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+                            const cfs_ik_out *out)
+{
+    IkParams P;
+    int rc = check_ik(d, T, target_pos, target_axis, theta_ref, out, P);
+    if (rc) return rc;
+    const size_t nj = d->njoint, R = d->restarts, nobs = d->nobs;
+    if (!all_finite(target_pos, (size_t)T * 3) || !all_finite(theta_ref, (size_t)T * nj)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_pos / theta_ref must be finite");
+    if (nobs && (!all_finite(d->obs, nobs * 6) || !all_finite(d->D, nobs))) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be finite");
+    if (d->use_axis) {
+        if (!all_finite(target_axis, (size_t)T * 3)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis must be finite");
+        for (int t = 0; t < T; ++t) {
+            const double *v = target_axis + (size_t)t * 3;
+            if (!(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis row %d is zero", t);
+        }
+    }
+    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
+    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
+    std::vector<void *> bufs;
+    hipError_t err = hipSuccess;
+    auto up = [&](const void *h, size_t bytes) -> void * {
+        if (err != hipSuccess) return nullptr;
+        void *p = nullptr;
+        err = hipMalloc(&p, bytes ? bytes : 8);
+        if (err != hipSuccess) return nullptr;
+        bufs.push_back(p);
+        if (h && bytes) err = hipMemcpy(p, h, bytes, hipMemcpyHostToDevice);
+        return p;
+    };
+    cfs_ik_out o;
+    memset(&o, 0, sizeof o);
+    const double *obs_d = (const double *)up(d->obs, nobs * 6 * 8), *D_d = (const double *)up(d->D, nobs * 8);
+    const double *tp_d = (const double *)up(target_pos, (size_t)T * 3 * 8);
+    const double *ta_d = d->use_axis ? (const double *)up(target_axis, (size_t)T * 3 * 8) : nullptr;
+    const double *tr_d = (const double *)up(theta_ref, (size_t)T * nj * 8);
+    o.theta = (double *)up(nullptr, (size_t)T * nj * 8); o.status = (int *)up(nullptr, (size_t)T * 4);
+    if (out->selected) o.selected = (int *)up(nullptr, (size_t)T * 4);
+    if (out->n_ok) o.n_ok = (int *)up(nullptr, (size_t)T * 4);
+    if (out->err_pos) o.err_pos = (double *)up(nullptr, (size_t)T * 8);
+    if (out->err_axis) o.err_axis = (double *)up(nullptr, (size_t)T * 8);
+    if (out->clearance) o.clearance = (double *)up(nullptr, (size_t)T * 8);
+    if (out->cand_theta) o.cand_theta = (double *)up(nullptr, (size_t)T * R * nj * 8);
+    if (out->cand_status) o.cand_status = (int *)up(nullptr, (size_t)T * R * 4);
+    if (out->cand_iter) o.cand_iter = (int *)up(nullptr, (size_t)T * R * 4);
+    if (err == hipSuccess) {
+        ik_point(P, obs_d, D_d, tp_d, ta_d, tr_d, &o);
+        err = launch_ik(d->njoint, P, nullptr);
+        if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+    }
+    auto down = [&](void *h, const void *dv, size_t bytes) { if (err == hipSuccess && h) err = hipMemcpy(h, dv, bytes, hipMemcpyDeviceToHost); };
+    down(out->theta, o.theta, (size_t)T * nj * 8); down(out->status, o.status, (size_t)T * 4);
+    down(out->selected, o.selected, (size_t)T * 4); down(out->n_ok, o.n_ok, (size_t)T * 4);
+    down(out->err_pos, o.err_pos, (size_t)T * 8); down(out->err_axis, o.err_axis, (size_t)T * 8); down(out->clearance, o.clearance, (size_t)T * 8);
+    down(out->cand_theta, o.cand_theta, (size_t)T * R * nj * 8); down(out->cand_status, o.cand_status, (size_t)T * R * 4);
+    down(out->cand_iter, o.cand_iter, (size_t)T * R * 4);
+    for (void *p : bufs) (void)hipFree(p);
+    if (err != hipSuccess) return cfs_fail(CFS_ERR_HIP, "IK staging or launch failed: %s", hipGetErrorString(err));
+    return CFS_SUCCESS;
+}
+
+extern "C" int cfs_tool_pose(const cfs_robot *robot, int njoint, const double *tool, const double *tool_axis, int N, const double *theta,
+                             double *pos, double *dir, double *jac)
+{
+    int rc = cfs_check_robot(robot, njoint);
+    if (rc) return rc;
+    if (njoint < 2) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", njoint);
+    if (N < 0 || !tool || !tool_axis || !theta || !pos || !dir) return cfs_fail(CFS_ERR_INVALID_ARG, "bad argument");
+    if (!finite3(tool) || !finite3(tool_axis)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool / tool_axis must be finite");
+    const double an = std::sqrt(tool_axis[0] * tool_axis[0] + tool_axis[1] * tool_axis[1] + tool_axis[2] * tool_axis[2]);
+    if (!(an > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool_axis is zero");
+    if (N == 0) return CFS_SUCCESS;
+    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
+    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
+    PoseParams P;
+    memset(&P, 0, sizeof P);
+    cfs_build_dev_robot(*robot, P.rb);
+    P.N = N;
+    for (int q = 0; q < 3; ++q) { P.tool[q] = tool[q]; P.axis[q] = tool_axis[q] / an; }
+    const size_t nj = njoint;
+    double *th_d = nullptr, *pos_d = nullptr, *dir_d = nullptr, *jac_d = nullptr;
+    hipError_t err = hipMalloc(&th_d, (size_t)N * nj * 8);
+    if (err == hipSuccess) err = hipMalloc(&pos_d, (size_t)N * 3 * 8);
+    if (err == hipSuccess) err = hipMalloc(&dir_d, (size_t)N * 3 * 8);
+    if (err == hipSuccess && jac) err = hipMalloc(&jac_d, (size_t)N * 6 * nj * 8);
+    if (err == hipSuccess) err = hipMemcpy(th_d, theta, (size_t)N * nj * 8, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        P.theta = th_d; P.pos = pos_d; P.dir = dir_d; P.jac = jac_d;
+        err = launch_tool_pose(njoint, P, nullptr);
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+    if (err == hipSuccess) err = hipMemcpy(pos, pos_d, (size_t)N * 3 * 8, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(dir, dir_d, (size_t)N * 3 * 8, hipMemcpyDeviceToHost);
+    if (err == hipSuccess && jac) err = hipMemcpy(jac, jac_d, (size_t)N * 6 * nj * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(th_d); (void)hipFree(pos_d); (void)hipFree(dir_d); (void)hipFree(jac_d);
+    if (err != hipSuccess) return cfs_fail(CFS_ERR_HIP, "cfs_tool_pose: %s", hipGetErrorString(err));
+    return CFS_SUCCESS;
+}

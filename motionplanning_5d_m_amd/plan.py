@@ -26,6 +26,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _lib
+from .ik import IKSolver
 from .rrt import RRT_FANUC
 from .robotproperty2 import robotproperty2
 from .solvers import CFSBatch, _infeasible_args, _jacobian_code, _joint_limits_array, _ptr, _substeps, obs_meshes, obs_to_array
@@ -101,7 +102,9 @@ class RRTCFSPlanner:
             raise ValueError("sys_rrt.nstate must be 5 (the M200i's joints)")
         _jacobian_code(jacobian)
         _infeasible_args(on_infeasible, soft_weight)
-        _joint_limits_array(joint_limits, robotproperty2("M200i"), 5)
+        lim = _joint_limits_array(joint_limits, robotproperty2("M200i"), 5)
+        self._ik_limits = lim if lim is not None else "robot"                       # plan_to_pose: the planner's ranges, else robot.thetamax
+        self._pobs, self._sys_rrt, self._ik = list(pobs), sys_rrt, {}
         meshes = obs_meshes(pobs)                                                   # ValueError: a mesh before a line obstacle
         if meshes and on_infeasible == "soften":
             raise ValueError('on_infeasible="soften" does not support mesh obstacles')
@@ -171,6 +174,77 @@ class RRTCFSPlanner:
         if t.ndim == 1:
             t = t.unsqueeze(0).expand(S, -1)
         return t.contiguous()
+
+    # ---- Cartesian goals ---------------------------------------------------------------------------------------------------
+    def plan_to_pose(self, x0, target_pos, target_axis=None, seed=0, ik_options=None, **plan_kwargs):
+        """plan() towards Cartesian targets: one inverse-kinematics launch (ik.IKSolver.solve_device: theta_ref = x0, the planner's
+        line obstacles with their D, the planner's joint_limits if it has them, else robot.thetamax; generator seed `seed`), then
+        plan(x0, goal, seed, **plan_kwargs) with the configurations it found.  x0: (S, 5) or (5,); target_pos: (S, 3) or (3,):
+        where the tool point goes (default tool: the reference's end effector cap{5}.p(:,1)); target_axis: (S, 3), (3,) or None
+        (position only): where the tool axis points.  CUDA tensors on the planner's device or array-likes.  ik_options: keyword
+        arguments of IKSolver (tool, tool_axis, restarts, max_iter, tol_pos, tol_axis, weight).
+        Returns plan()'s namespace plus goal (S, 5; NaN rows without an IK solution), ik_status (0 solved | 1 no restart converged
+        | 2 every converged restart collides), ik_err_pos, ik_clearance.  A slot without an IK solution is planned with goal = x0
+        (the batch keeps its shape) and then masked: status = -2, has_solution = 0, selected = -1.
+        A planner with mesh obstacles refuses: the IK collision test reads line obstacles only."""
+        if self._meshes:
+            raise ValueError("plan_to_pose is not available with mesh obstacles: the IK collision test reads line obstacles only")
+        if not _is_int(seed) or seed < 0:
+            raise ValueError(f"seed must be a non-negative integer, not {seed!r}")
+        if ik_options is None:
+            ik_options = {}
+        if not isinstance(ik_options, dict) or set(ik_options) - {"tool", "tool_axis", "restarts", "max_iter", "tol_pos", "tol_axis", "weight"}:
+            raise ValueError("ik_options must be a dict of IKSolver's tool, tool_axis, restarts, max_iter, tol_pos, tol_axis, weight")
+        stream = plan_kwargs.get("stream")
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise ValueError("stream must be a torch.cuda.Stream")
+
+        def conv(v, name, cols, nonzero=False):
+            if torch is not None and isinstance(v, torch.Tensor):
+                if v.device != self.device:
+                    raise ValueError(f"{name} is on {v.device}, the planner on {self.device}")
+                if not v.dtype.is_floating_point:
+                    raise ValueError(f"{name} must be a floating-point tensor, not {v.dtype}")
+                t = v.to(torch.float64)
+            else:
+                try:
+                    t = np.array(v, dtype=float)
+                except (TypeError, ValueError):
+                    raise ValueError(f"{name} must be numeric") from None
+                if not np.isfinite(t).all():
+                    raise ValueError(f"{name} must be finite")
+                if nonzero and t.ndim in (1, 2) and t.shape[-1] == cols and not (np.linalg.norm(t.reshape(-1, cols), axis=1) > 0).all():
+                    raise ValueError(f"a {name} row is zero")
+            if t.ndim not in (1, 2) or t.shape[-1] != cols:
+                raise ValueError(f"{name} must have shape ({cols},) or (S, {cols}), not {tuple(t.shape)}")
+            return t
+        args = [conv(x0, "x0", self.nj), conv(target_pos, "target_pos", 3)]
+        if target_axis is not None:
+            args.append(conv(target_axis, "target_axis", 3, nonzero=True))
+        rows = {a.shape[0] for a in args if a.ndim == 2}
+        if len(rows) > 1:
+            raise ValueError(f"x0, target_pos and target_axis disagree on S: {sorted(rows)}")
+        S = rows.pop() if rows else 1
+        if S < 1 or S > self.max_slots:
+            raise ValueError(f"S={S} outside 1..max_slots={self.max_slots}")
+        key = tuple(sorted((k, repr(v)) for k, v in ik_options.items()))
+        if key not in self._ik:                                                     # validates ik_options; no device call
+            self._ik[key] = IKSolver(self._sys_rrt.robot, [o for o in self._pobs], joint_limits=self._ik_limits, njoint=self.nj,
+                                     device=self.device, **ik_options)
+        ik = self._ik[key]
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            dev = [self._on_device(a, S) for a in args]
+            sol = ik.solve_device(dev[1], dev[2] if len(dev) > 2 else None, dev[0], seed=int(seed), stream=stream)
+            ok = sol.status == 0
+            goal = torch.where(ok[:, None], sol.theta, dev[0])
+            res = self.plan(dev[0], goal, seed, **dict(plan_kwargs, stream=stream))
+            res.status = torch.where(ok, res.status, torch.full_like(res.status, -2))
+            res.has_solution = torch.where(ok, res.has_solution, torch.zeros_like(res.has_solution))
+            res.selected = torch.where(ok, res.selected, torch.full_like(res.selected, -1))
+            res.goal, res.ik_status, res.ik_err_pos, res.ik_clearance = sol.theta, sol.status, sol.err_pos, sol.clearance
+        return res
 
     # ---- the pipeline ----------------------------------------------------------------------------------------------------
     def plan(self, x0, goal, seed, max_rounds=50, stream=None, want_candidates=False, max_draws=None, timings=None):
