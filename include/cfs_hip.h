@@ -635,6 +635,32 @@ int cfs_ik_solve(const cfs_ik_desc *d, int T, const double *target_pos, const do
                  const cfs_ik_out *out);
 int cfs_ik_solve_device(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
                         const cfs_ik_out *out, void *stream);
+/* The same inverse kinematics in a cell that also holds mesh obstacles.  The contract is "inverse kinematics"
+ * above word for word, with these changes.  After the line test, a restart that converged and passed the lines is tested against the
+ * meshes with exactly the decision of cfs_rrt_grow_mesh: it takes state 2 when some triangle of some mesh j lies strictly closer
+ * than thr_j = max(D_mesh[j], 1e-4) to some link axis, and stays in state 0 otherwise (an existence test: the traversal order does
+ * not matter).  State 2 therefore means "converged but in collision with a line obstacle or a mesh", and status 2 "every converged
+ * restart collides with a line obstacle or a mesh".  Every converged restart is tested, so n_ok and cand_status keep their meaning.
+ * clearance = min(line clearance, min_j (dm_j - D_mesh[j])), dm_j = the exact mesh distance (the mesh contract above) of the nearest
+ * link axis of the winner; the winner is free, so dm_j >= thr_j and the near-zero surrogate cannot apply.  cand_theta and cand_iter
+ * do not depend on the meshes: starts, steps 1-8, the line test, the cost and the selection are cfs_ik_solve's.  A target's results
+ * depend on neither T nor its position in the batch; there are no atomics on the normal path.
+ * The geometry is evaluated WITH FMA contraction, as cfs_dist_arm_mesh evaluates it and cfs_rrt_grow_mesh does not: a pose within
+ * rounding of a threshold may be decided differently here than by cfs_rrt_grow_mesh; the clearance agrees with cfs_dist_arm_mesh.
+ * meshes: nmesh >= 1 handles created on the current device (cfs_set_device); they must outlive the launch.  D_mesh: HOST in both
+ * entries, nmesh margins, finite and > 0.  CFS_ERR_INVALID_ARG, with nothing written, for everything cfs_ik_solve (cfs_ik_solve_mesh)
+ * or cfs_ik_solve_device (cfs_ik_solve_mesh_device) refuses; nmesh < 1; d->nobs + nmesh > CFS_MAX_OBS; NULL meshes, a NULL entry or
+ * NULL D_mesh; a D_mesh that is not finite and > 0; a mesh of another device; unknown flag bits; both variant bits set (or
+ * CFS_IK_MESH_PER_LANE with CFS_IK_MESH_SMALL_FRONTIER).  flags: 0 (the default variant), or a developer switch with the value and
+ * the meaning of RRT's (results are bit-identical under every value): */
+#define CFS_IK_MESH_PER_LANE 1        /* variant A: one (mesh, link) pair per lane, private threshold query                              */
+#define CFS_IK_MESH_WAVE 2            /* variant B: one wave-cooperative traversal over a shared frontier in LDS (the default)           */
+#define CFS_IK_MESH_SMALL_FRONTIER 4  /* variant B with a frontier of 8 entries: its overflow path (decided by variant A) under test      */
+int cfs_ik_solve_mesh(const cfs_ik_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
+                      const double *target_pos, const double *target_axis, const double *theta_ref, const cfs_ik_out *out);
+int cfs_ik_solve_mesh_device(const cfs_ik_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh /* HOST, nmesh */,
+                             int flags, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+                             const cfs_ik_out *out, void *stream);
 /* pose(theta) and its Jacobian for N configurations, the device functions the solver runs (HOST pointers, like cfs_dist_arm).
  * theta: N x njoint; pos, dir: N x 3; jac: N x 6 x njoint (rows 0-2 d pos / d theta, rows 3-5 d dir / d theta; may be NULL).
  * tool_axis must be finite and not zero.  With tool = robot.cap{njoint}.p(:,1), pos is cfs_dist_arm's pos of that end point. */
@@ -680,6 +706,8 @@ int cfs_debug_read_u_log(cfs_problem *p, int B, double *out);
  * that variant A decided instead (one counter per device and process; HOST pointer, may be NULL; synchronises the device).
  * With CFS_RRT_MESH_SMALL_FRONTIER it shows that the overflow path ran. */
 int cfs_debug_rrt_frontier_overflows(unsigned long long *count, int reset);
+/* cfs_ik_solve_mesh*, variant B: the same counter for candidate poses (restarts) whose frontier overflowed */
+int cfs_debug_ik_frontier_overflows(unsigned long long *count, int reset);
 
 #ifdef __cplusplus
 }

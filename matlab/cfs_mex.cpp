@@ -36,6 +36,9 @@
 //        is refused; opts (optional struct): lo, hi (default robot.thetamax(1:njoint,:)), tool, tool_axis (default robot.cap{njoint}.p(:,1)
 //        and the unit vector towards p(:,2)), weight, restarts (64), max_iter (100), tol_pos (1e-6), tol_axis (1e-6), seed (0).
 //        theta njoint x T (NaN columns where status ~= 0), the others 1 x T; selected is 1-based (0: none)
+//   [theta, status, err_pos, clearance, selected, n_ok, err_axis] = cfs_mex('ik_mesh', obs, robot, ROBOT, target_pos, target_axis, theta_ref, opts)
+//        'ik' in a cell that ends with mesh obstacles (obs{j}.mesh, obs{j}.D), received as 'rrt' receives them: cfs_ik_solve_mesh.  A
+//        converged restart is also rejected when a link axis comes closer to mesh j than max(D_j, 1e-4); clearance counts the meshes
 //   Cost_b = cfs_mex('cost_b', sys_info, ROBOT)                    % EVAL.get_Cost_b (Lib/EVAL.m:75-78, main_FANUC.m:131-132)
 //   h = cfs_mex('mesh_load_stl', path, scale, map_from_stl)        % Lib/functions/MapFromSTL.m
 //   [dis, points] = cfs_mex('mesh_segment_distance', h, seg6)      % point2surface_dis (M200i/dist_arm_surf_200i.m:21)
@@ -417,6 +420,78 @@ static void ik(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     for (int k = 0; k < 7; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
 }
 
+// 'ik' in a cell that ends with mesh obstacles (cfs_ik_solve_mesh): the same arguments and outputs, the obs cell as 'rrt' takes it
+static void ik_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs < 7) mexErrMsgTxt("[theta, status, err_pos, clearance, selected, n_ok, err_axis] = cfs_mex('ik_mesh', obs, robot, ROBOT, target_pos, target_axis, theta_ref [, opts])");
+    const mxArray *obs = prhs[1], *robot = prhs[2], *opts = nrhs > 7 ? prhs[7] : nullptr;
+    const std::string ROBOT = mxArrayToString(prhs[3]);
+    const int nj = (int)mxGetM(prhs[6]), T = (int)mxGetN(prhs[4]);
+    if (mxGetM(prhs[4]) != 3 || (int)mxGetN(prhs[6]) != T) mexErrMsgTxt("target_pos must be 3 x T and theta_ref njoint x T");
+    const bool use_axis = !mxIsEmpty(prhs[5]);
+    if (use_axis && (mxGetM(prhs[5]) != 3 || (int)mxGetN(prhs[5]) != T)) mexErrMsgTxt("target_axis must be 3 x T or []");
+    cfs_ik_desc d;
+    memset(&d, 0, sizeof d);
+    fill_robot(robot, ROBOT.c_str(), nj, d.robot);
+    d.njoint = nj; d.use_axis = use_axis ? 1 : 0;
+    auto opt = [&](const char *name) -> const mxArray * { const mxArray *f = opts ? mxGetField(opts, 0, name) : nullptr; return f && !mxIsEmpty(f) ? f : nullptr; };
+    auto num = [&](const char *name, double dflt) { const mxArray *f = opt(name); return f ? mxGetScalar(f) : dflt; };
+    // joint ranges: opts.lo / opts.hi, else robot.thetamax(1:njoint,:) (nlink x 2 column-major)
+    std::vector<double> lo(nj), hi(nj);
+    const mxArray *tm = mxGetField(robot, 0, "thetamax");
+    for (int c = 0; c < nj; ++c) {
+        if (opt("lo") && opt("hi")) { lo[c] = mxGetPr(opt("lo"))[c]; hi[c] = mxGetPr(opt("hi"))[c]; }
+        else if (tm && (int)mxGetM(tm) >= nj) { lo[c] = mxGetPr(tm)[c]; hi[c] = mxGetPr(tm)[mxGetM(tm) + c]; }
+        else mexErrMsgTxt("joint ranges: give opts.lo and opts.hi, or robot.thetamax");
+    }
+    d.lo = lo.data(); d.hi = hi.data();
+    d.weight = opt("weight") ? mxGetPr(opt("weight")) : nullptr;
+    // tool: opts.tool / opts.tool_axis, else the end effector of Lib/RRT_FANUC.m:186 and the axis of its capsule
+    const double *cp = d.robot.cap + 6 * (nj - 1);
+    double ax[3] = {cp[3] - cp[0], cp[4] - cp[1], cp[5] - cp[2]};
+    if (ax[0] == 0.0 && ax[1] == 0.0 && ax[2] == 0.0) ax[2] = 1.0;
+    for (int q = 0; q < 3; ++q) {
+        d.tool[q] = opt("tool") ? mxGetPr(opt("tool"))[q] : cp[q];
+        d.tool_axis[q] = opt("tool_axis") ? mxGetPr(opt("tool_axis"))[q] : ax[q];
+    }
+    d.restarts = (int)num("restarts", 64); d.max_iter = (int)num("max_iter", 100);
+    d.tol_pos = num("tol_pos", 1e-6); d.tol_axis = num("tol_axis", 1e-6);
+    d.seed = (unsigned long long)num("seed", 0);
+    // line obstacles (.l, .D) first, then mesh obstacles (.mesh = a handle of cfs_mex('mesh_load_stl' ...), .D), as in 'rrt'
+    std::vector<double> obs6, D, D_mesh;
+    std::vector<const cfs_mesh *> meshes;
+    const int ncell = (int)mxGetNumberOfElements(obs);
+    for (int j = 0; j < ncell; ++j) {
+        const mxArray *o = mxGetCell(obs, j), *fl = o ? mxGetField(o, 0, "l") : nullptr, *fD = o ? mxGetField(o, 0, "D") : nullptr;
+        const mxArray *mh = o ? mxGetField(o, 0, "mesh") : nullptr;
+        if (mh) {
+            if (!fD) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .mesh and .D", j + 1);
+            meshes.push_back(mesh_of(mh));
+            D_mesh.push_back(mxGetScalar(fD));
+            continue;
+        }
+        if (!meshes.empty()) mexErrMsgTxt("mesh obstacles must come last in the obs cell");
+        if (!fl || !fD || mxGetNumberOfElements(fl) != 6) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .l (3x2) and .D", j + 1);
+        obs6.insert(obs6.end(), mxGetPr(fl), mxGetPr(fl) + 6);
+        D.push_back(mxGetScalar(fD));
+    }
+    if (meshes.empty()) mexErrMsgTxt("'ik_mesh' needs at least one mesh obstacle at the end of the obs cell: use 'ik' for line obstacles only");
+    d.nobs = (int)D.size(); d.obs = obs6.data(); d.D = D.data();
+    mxArray *o_th = mxCreateDoubleMatrix(nj, T, mxREAL);                              // T x njoint row-major = njoint x T column-major
+    mxArray *o_d[3] = {mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL)};
+    std::vector<int> status(T), selected(T), n_ok(T);
+    cfs_ik_out o;
+    memset(&o, 0, sizeof o);
+    o.theta = mxGetPr(o_th); o.status = status.data(); o.selected = selected.data(); o.n_ok = n_ok.data();
+    o.err_pos = mxGetPr(o_d[0]); o.clearance = mxGetPr(o_d[1]); o.err_axis = mxGetPr(o_d[2]);
+    check(cfs_ik_solve_mesh(&d, (int)meshes.size(), meshes.data(), D_mesh.data(), 0, T, mxGetPr(prhs[4]), use_axis ? mxGetPr(prhs[5]) : nullptr,
+                            mxGetPr(prhs[6]), &o));
+    mxArray *o_i[3] = {mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL)};
+    for (int t = 0; t < T; ++t) { mxGetPr(o_i[0])[t] = status[t]; mxGetPr(o_i[1])[t] = selected[t] + 1; mxGetPr(o_i[2])[t] = n_ok[t]; }
+    mxArray *outs[7] = {o_th, o_i[0], o_d[0], o_d[1], o_i[1], o_i[2], o_d[2]};
+    for (int k = 0; k < 7; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
+}
+
 // Cost_b = EVAL(sys_info).get_Cost_b()  (Lib/EVAL.m:75-78)
 static void cost_b(mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
@@ -459,6 +534,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         rrt(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "ik") {
         ik(nlhs, plhs, nrhs, prhs);
+    } else if (cmd == "ik_mesh") {
+        ik_mesh(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "cost_b") {
         cost_b(plhs, nrhs, prhs);
     } else if (cmd == "mesh_load_stl") {

@@ -254,6 +254,9 @@ SYMBOLS = [
     ("cfs_ik_solve", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out)]),
     ("cfs_ik_solve_device", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out), _P]),
     ("cfs_tool_pose", C.c_int, [C.POINTER(cfs_robot), C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
+    ("cfs_ik_solve_mesh", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out)]),
+    ("cfs_ik_solve_mesh_device", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out), _P]),
+    ("cfs_debug_ik_frontier_overflows", C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)
@@ -262,6 +265,8 @@ DBG = {"no_refine": 2, "no_warm_start": 8, "no_certificate": 16, "no_prune": 32,
 
 # cfs_rrt_grow_mesh* flags (include/cfs_hip.h): developer switches, bit-identical trees under every value
 RRT_MESH = {"per_lane": 1, "wave": 2, "small_frontier": 4}
+# cfs_ik_solve_mesh* flags: the same switches with the same values (IKSolver's mesh_variant)
+IK_MESH = {"per_lane": 1, "wave": 2, "small_frontier": 4}
 
 _lib = None
 

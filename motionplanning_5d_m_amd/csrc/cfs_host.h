@@ -136,3 +136,6 @@ struct RrtMeshArgs {
 };
 hipError_t launch_rrt_mesh(int nj, int variant, const RrtParams &p, const RrtMeshArgs &ma, hipStream_t s);
 size_t rrt_mesh_lds_bytes(int nj, int max_iter, int variant);      // rrt_lds_bytes + the variant's mesh scratch
+// cfs_ik_solve_mesh* (cfs_ik.hip) runs the same two variants on its candidates; flags == 0: the variant the measurement of DESIGN.md
+// section 21 names
+constexpr int IK_MESH_DEFAULT = RRT_MESH_WAVE;

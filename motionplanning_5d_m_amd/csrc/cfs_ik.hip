@@ -11,6 +11,20 @@
 // target end at different iterations: a lane that has ended idles under the EXEC mask until a ballot says that none is running,
 // so every lane reaches the selection, a wave argmin on (cost, lane) by xor shuffles.  No atomics, no block barrier after the
 // staging, no host round trip.  Everything is fp64.
+//
+// Mesh obstacles (cfs_ik_solve_mesh*).  cfs_ik_kernel<NJ, MESH> with MESH != RRT_MESH_NONE puts the decision of
+// cfs_rrt_grow_mesh between the line test and the cost: a restart that converged and passed the lines takes state 2 when some
+// triangle of some mesh j lies strictly closer than thr_j = max(D_mesh[j], 1e-4) to some link axis.  A lane holds one candidate
+// pose, but the traversals of cfs_mesh_hit_dev.h want a whole wave on ONE pose, so the wave serialises its candidates:
+// mask = ballot(st == 0); the lowest lane's NJ x 6 link ends (ik_clearance hands them out) are broadcast by v_readlane, the wave
+// runs the threshold test on them (variant A: one (mesh, link) pair per lane; variant B: the shared frontier in LDS, variant A
+// deciding a pose whose frontier overflows), that lane takes state 2 on a hit, and the mask loses its lowest bit.  All of it is
+// wave-uniform.  After the selection the winner's link ends are broadcast once more and lanes p < nmesh*NJ run one exact unbounded
+// query each; a wave min gives the mesh part of the clearance.  The mesh code is compiled out of the line-only instantiation
+// (MESH == RRT_MESH_NONE), which keeps its code, its registers and its bits.  This translation unit contracts into FMAs, as
+// cfs_mesh.hip does and cfs_rrt.hip does not: a pose within rounding of a threshold may be decided differently here than by
+// cfs_rrt_grow_mesh; the clearance agrees with cfs_dist_arm_mesh (the same functions under the same flags).
+#include "cfs_mesh_hit_dev.h"
 #include "cfs_geom_dev.h"
 #include "cfs_host.h"
 #include <cmath>
@@ -21,6 +35,9 @@ namespace {
 
 constexpr int WV = 64;
 constexpr int IK_WAVES = 4;                                   // targets per workgroup
+// mesh kernels, dynamic LDS per wave: the private stacks of variant A and of the winner's exact query (MESH_STACK*64 ints + as many
+// floats = 10 KB), then variant B's frontier (RRT_FRONTIER_CAP pairs + as many nodes = 4 KB)
+constexpr int IK_STACK_WORDS = 2 * MESH_STACK * WV, IK_FRONTIER_WORDS = 2 * RRT_FRONTIER_CAP;
 constexpr double IK_LAMBDA0 = 1e-2, IK_LAMBDA_MIN = 1e-9, IK_LAMBDA_MAX = 1e9, IK_STEP_CAP = 0.5;
 
 struct IkParams {
@@ -38,6 +55,27 @@ struct IkParams {
     double *cand_theta;                                       // T x R x NJ
     int *cand_status, *cand_iter;                             // T x R
 };
+
+// the mesh table of a cfs_ik_solve_mesh* call: RRT's (thresholds, frontier capacity) and the margins for the winner's clearance
+struct IkMeshArgs {
+    RrtMeshArgs MA;
+    double D[CFS_MAX_OBS];
+};
+template <int MESH> struct IkArgs { IkParams P; IkMeshArgs M; };
+template <> struct IkArgs<RRT_MESH_NONE> { IkParams P; };
+
+// candidates of variant B whose frontier overflowed and that variant A decided (cfs_debug_ik_frontier_overflows): one vector atomic
+// by lane 0 per such candidate, none on the normal path
+__device__ unsigned long long g_ik_frontier_overflows = 0ull;
+
+// lane l's value in every lane (l is wave-uniform): two v_readlane
+__device__ __forceinline__ double ik_bcast(double v, int l)
+{
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffll), l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)b >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 
 struct PoseParams {
     DevRobot rb;
@@ -162,11 +200,13 @@ __device__ __forceinline__ void ik_residual(const double *p, const double *a, co
     *F = (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) + (r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
 }
 
-// min_j (d_j - D_j), d_j = cfs_dist_arm's distance to obstacle j; +inf without obstacles
-template <int NJ>
-__device__ __forceinline__ double ik_clearance(const DevRobot *rb, const double *th, int nobs, const double *obs, const double *D)
+// min_j (d_j - D_j), d_j = cfs_dist_arm's distance to obstacle j; +inf without obstacles.  ENDS: the NJ x 6 link ends go to ends_out
+template <int NJ, bool ENDS = false>
+__device__ __forceinline__ double ik_clearance(const DevRobot *rb, const double *th, int nobs, const double *obs, const double *D,
+                                               double *ends_out = nullptr)
 {
-    double ends[NJ * 6], M[12], Mn[12];
+    double ends_loc[NJ * 6], M[12], Mn[12];
+    double *ends = ENDS ? ends_out : ends_loc;
 #pragma unroll
     for (int k = 0; k < NJ; ++k) {
         double sn, cs;
@@ -193,9 +233,11 @@ __device__ __forceinline__ double ik_clearance(const DevRobot *rb, const double 
     return c;
 }
 
-template <int NJ>
-__global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkParams P)
+// MESH: RRT_MESH_NONE (the line-only kernel: the mesh code is compiled out) | RRT_MESH_PER_LANE | RRT_MESH_WAVE
+template <int NJ, int MESH>
+__global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkArgs<MESH> A_)
 {
+    const IkParams &P = A_.P;
     __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
     __shared__ double s_obs[CFS_MAX_OBS * 6];
     __shared__ double s_D[CFS_MAX_OBS];
@@ -280,9 +322,43 @@ __global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkParams P)
     // ---- collision, cost, selection ---------------------------------------------------------------------------------------
     const double ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
     double clear = INFINITY, cost = INFINITY;
-    if (st == 0) {
-        clear = ik_clearance<NJ>(rb, th, P.nobs, s_obs, s_D);
-        if (!(clear >= 0.0)) st = 2;
+    [[maybe_unused]] double ends[MESH == RRT_MESH_NONE ? 1 : NJ * 6];          // the candidate's link ends (mesh kernels only)
+    if constexpr (MESH == RRT_MESH_NONE) {
+        if (st == 0) {
+            clear = ik_clearance<NJ>(rb, th, P.nobs, s_obs, s_D);
+            if (!(clear >= 0.0)) st = 2;
+        }
+    } else {
+        // the wave's slice of the dynamic LDS (launch_ik_mesh sizes it)
+        extern __shared__ __attribute__((aligned(16))) int s_mesh[];
+        const int wave = threadIdx.x / WV;
+        int *s_stack = s_mesh + wave * IK_STACK_WORDS;
+        float *s_lbs = reinterpret_cast<float *>(s_stack + MESH_STACK * WV);
+        int *s_fpair = s_mesh + IK_WAVES * IK_STACK_WORDS + wave * IK_FRONTIER_WORDS, *s_fnode = s_fpair + RRT_FRONTIER_CAP;
+        const RrtMeshArgs &MA = A_.M.MA;
+        for (int q = 0; q < NJ * 6; ++q) ends[q] = 0.0;
+        if (st == 0) {
+            clear = ik_clearance<NJ, true>(rb, th, P.nobs, s_obs, s_D, ends);
+            if (!(clear >= 0.0)) st = 2;
+        }
+        // every converged restart that passed the lines, lowest lane first: the whole wave on that one pose
+        unsigned long long todo = __ballot(st == 0);
+        while (todo != 0ull) {
+            const int l = __ffsll((long long)todo) - 1;
+            todo &= todo - 1ull;
+            double pe[NJ * 6];
+#pragma unroll
+            for (int q = 0; q < NJ * 6; ++q) pe[q] = ik_bcast(ends[q], l);
+            bool hit;
+            if constexpr (MESH == RRT_MESH_PER_LANE) {
+                hit = mesh_hit_per_lane<NJ>(MA, pe, lane, s_stack, s_lbs);
+            } else {
+                const int h = mesh_hit_wave<NJ>(MA, pe, lane, s_fpair, s_fnode);
+                if (h < 0 && lane == 0) atomicAdd(&g_ik_frontier_overflows, 1ull);
+                hit = h < 0 ? mesh_hit_per_lane<NJ>(MA, pe, lane, s_stack, s_lbs) : h != 0;
+            }
+            if (hit && lane == l) st = 2;
+        }
     }
     if (st == 0) {
         double s = 0.0;
@@ -311,6 +387,36 @@ __global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkParams P)
         const double oc = __shfl_xor(bc, m, WV);
         const int ol = __shfl_xor(bl, m, WV);
         if (oc < bc || (oc == bc && ol < bl)) { bc = oc; bl = ol; }
+    }
+    if constexpr (MESH != RRT_MESH_NONE) {
+        // the winner's clearance: one exact, unbounded query per (mesh, link) pair, min_j (dm_j - D_mesh[j]) by a wave min
+        // (subtracting D_j is monotone, so the minimum over the links may be taken after it)
+        if (n_ok > 0) {
+            extern __shared__ __attribute__((aligned(16))) int s_mesh[];
+            int *s_stack = s_mesh + (threadIdx.x / WV) * IK_STACK_WORDS;
+            float *s_lbs = reinterpret_cast<float *>(s_stack + MESH_STACK * WV);
+            const RrtMeshArgs &MA = A_.M.MA;
+            double pe[NJ * 6];
+#pragma unroll
+            for (int q = 0; q < NJ * 6; ++q) pe[q] = ik_bcast(ends[q], bl);
+            double mm = INFINITY;
+            for (int pr = lane; pr < MA.nmesh * NJ; pr += WV) {
+                const int j = pr / NJ, k = pr - j * NJ;
+                double a6[6];
+                pick_link<NJ>(pe, k, a6);
+                const DevMesh m{MA.m[j].nodes, MA.m[j].tri, nullptr, 0, MA.m[j].nt, nullptr, nullptr, 0, 0};
+                Best b;
+                mesh_query<WV, false>(m, a6, a6 + 3, -1, s_stack + lane, s_lbs + lane, b, nullptr);
+                const double v = b.d - A_.M.D[j];
+                if (v < mm) mm = v;
+            }
+#pragma unroll
+            for (int m = 1; m < WV; m <<= 1) {
+                const double om = __shfl_xor(mm, m, WV);
+                if (om < mm) mm = om;
+            }
+            if (mm < clear) clear = mm;                       // only the winner's `clear` is written
+        }
     }
     const double nan = __builtin_nan("");
     if (n_ok > 0 ? lane == bl : lane == 0) {
@@ -359,14 +465,40 @@ __global__ __launch_bounds__(256) void cfs_tool_pose_kernel(const PoseParams P)
 hipError_t launch_ik(int nj, const IkParams &p, hipStream_t s)
 {
     const dim3 grid((p.T + IK_WAVES - 1) / IK_WAVES), block(WV * IK_WAVES);
+    const IkArgs<RRT_MESH_NONE> a{p};
     switch (nj) {
-    case 2: hipLaunchKernelGGL(cfs_ik_kernel<2>, grid, block, 0, s, p); break;
-    case 3: hipLaunchKernelGGL(cfs_ik_kernel<3>, grid, block, 0, s, p); break;
-    case 4: hipLaunchKernelGGL(cfs_ik_kernel<4>, grid, block, 0, s, p); break;
-    case 5: hipLaunchKernelGGL(cfs_ik_kernel<5>, grid, block, 0, s, p); break;
-    case 6: hipLaunchKernelGGL(cfs_ik_kernel<6>, grid, block, 0, s, p); break;
+    case 2: hipLaunchKernelGGL((cfs_ik_kernel<2, RRT_MESH_NONE>), grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((cfs_ik_kernel<3, RRT_MESH_NONE>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((cfs_ik_kernel<4, RRT_MESH_NONE>), grid, block, 0, s, a); break;
+    case 5: hipLaunchKernelGGL((cfs_ik_kernel<5, RRT_MESH_NONE>), grid, block, 0, s, a); break;
+    case 6: hipLaunchKernelGGL((cfs_ik_kernel<6, RRT_MESH_NONE>), grid, block, 0, s, a); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+size_t ik_mesh_lds_bytes(int variant)
+{
+    return (size_t)IK_WAVES * (IK_STACK_WORDS + (variant == RRT_MESH_WAVE ? IK_FRONTIER_WORDS : 0)) * 4;
+}
+
+hipError_t launch_ik_mesh(int nj, int variant, const IkParams &p, const IkMeshArgs &m, hipStream_t s)
+{
+    if (variant != RRT_MESH_PER_LANE && variant != RRT_MESH_WAVE) return hipErrorInvalidValue;
+    const dim3 grid((p.T + IK_WAVES - 1) / IK_WAVES), block(WV * IK_WAVES);
+    const size_t lds = ik_mesh_lds_bytes(variant);
+    const IkArgs<RRT_MESH_PER_LANE> aa{p, m};
+    const IkArgs<RRT_MESH_WAVE> ab{p, m};
+#define IK_MESH_LAUNCH(NJ_)                                                                                          \
+    case NJ_:                                                                                                        \
+        if (variant == RRT_MESH_PER_LANE) hipLaunchKernelGGL((cfs_ik_kernel<NJ_, RRT_MESH_PER_LANE>), grid, block, lds, s, aa); \
+        else hipLaunchKernelGGL((cfs_ik_kernel<NJ_, RRT_MESH_WAVE>), grid, block, lds, s, ab);                        \
+        break;
+    switch (nj) {
+        IK_MESH_LAUNCH(2) IK_MESH_LAUNCH(3) IK_MESH_LAUNCH(4) IK_MESH_LAUNCH(5) IK_MESH_LAUNCH(6)
+    default: return hipErrorInvalidValue;
+    }
+#undef IK_MESH_LAUNCH
     return hipGetLastError();
 }
 
@@ -439,29 +571,72 @@ void ik_point(IkParams &P, const double *obs, const double *D, const double *tar
     P.err_pos = o->err_pos; P.err_axis = o->err_axis; P.clearance = o->clearance;
     P.cand_theta = o->cand_theta; P.cand_status = o->cand_status; P.cand_iter = o->cand_iter;
 }
-}  // namespace
 
-extern "C" int cfs_ik_solve_device(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
-                                   const cfs_ik_out *out, void *stream)
+// the meshes of a cfs_ik_solve_mesh* call -> kernel argument + variant; host work only, nothing is launched or allocated.  The device
+// of a handle is compared last, so that every other refusal is the same with and without a device.
+struct IkMeshCall { int nmesh; const cfs_mesh *const *meshes; const double *D_mesh; int flags; };
+int check_ik_mesh(const cfs_ik_desc *d, const IkMeshCall &c, IkMeshArgs &m, int &variant)
+{
+    variant = RRT_MESH_NONE;
+    memset(&m, 0, sizeof m);
+    if (c.nmesh < 1 || d->nobs + c.nmesh > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d + nmesh %d outside 1..%d", d->nobs, c.nmesh, CFS_MAX_OBS);
+    if (c.flags & ~(CFS_IK_MESH_PER_LANE | CFS_IK_MESH_WAVE | CFS_IK_MESH_SMALL_FRONTIER)) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown flags 0x%x", c.flags);
+    if ((c.flags & CFS_IK_MESH_PER_LANE) && (c.flags & (CFS_IK_MESH_WAVE | CFS_IK_MESH_SMALL_FRONTIER)))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "CFS_IK_MESH_PER_LANE excludes the other flags");
+    if (!c.meshes || !c.D_mesh) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes / D_mesh must be given");
+    for (int j = 0; j < c.nmesh; ++j) {
+        if (!c.meshes[j]) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d is NULL", j);
+        if (!std::isfinite(c.D_mesh[j]) || !(c.D_mesh[j] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "D_mesh[%d] must be finite and > 0", j);
+    }
+    for (int j = 0; j < c.nmesh; ++j) {
+        if (c.meshes[j]->device != cfs_current_device())
+            return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d lives on device %d, the current device is %d", j, c.meshes[j]->device, cfs_current_device());
+        m.MA.m[j].nodes = c.meshes[j]->nodes_d; m.MA.m[j].tri = c.meshes[j]->tri_d; m.MA.m[j].nt = c.meshes[j]->nt;
+        m.MA.m[j].thr = c.D_mesh[j] > 0.0001 ? c.D_mesh[j] : 0.0001;                   // dist_arm_surf_200i.m:22-24 folded into the threshold
+        m.D[j] = c.D_mesh[j];
+    }
+    m.MA.nmesh = c.nmesh;
+    variant = (c.flags & CFS_IK_MESH_PER_LANE) ? RRT_MESH_PER_LANE : (c.flags & (CFS_IK_MESH_WAVE | CFS_IK_MESH_SMALL_FRONTIER)) ? RRT_MESH_WAVE : IK_MESH_DEFAULT;
+    m.MA.cap = (c.flags & CFS_IK_MESH_SMALL_FRONTIER) ? RRT_FRONTIER_SMALL : RRT_FRONTIER_CAP;
+    return CFS_SUCCESS;
+}
+
+// mc == nullptr: the line-only call
+int ik_device(const cfs_ik_desc *d, const IkMeshCall *mc, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+              const cfs_ik_out *out, void *stream)
 {
     static_assert(sizeof(IkParams) <= 4096, "the parameter block travels as a kernel argument");
+    static_assert(sizeof(IkArgs<RRT_MESH_WAVE>) <= 4096, "the parameter block and the mesh table travel as a kernel argument");
     IkParams P;
     int rc = check_ik(d, T, target_pos, target_axis, theta_ref, out, P);
     if (rc) return rc;
+    IkMeshArgs M;
+    int variant = RRT_MESH_NONE;
+    if (mc) {
+        rc = check_ik_mesh(d, *mc, M, variant);
+        if (rc) return rc;
+    }
     if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
     CFS_HIPCHK(hipSetDevice(cfs_current_device()));
     ik_point(P, d->obs, d->D, target_pos, target_axis, theta_ref, out);
-    hipError_t e = launch_ik(d->njoint, P, reinterpret_cast<hipStream_t>(stream));
+    hipError_t e = mc ? launch_ik_mesh(d->njoint, variant, P, M, reinterpret_cast<hipStream_t>(stream))
+                      : launch_ik(d->njoint, P, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return cfs_fail(CFS_ERR_HIP, "IK launch failed: %s", hipGetErrorString(e));
     return CFS_SUCCESS;
 }
 
-extern "C" int cfs_ik_solve(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
-                            const cfs_ik_out *out)
+int ik_host(const cfs_ik_desc *d, const IkMeshCall *mc, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+            const cfs_ik_out *out)
 {
     IkParams P;
     int rc = check_ik(d, T, target_pos, target_axis, theta_ref, out, P);
     if (rc) return rc;
+    IkMeshArgs M;
+    int variant = RRT_MESH_NONE;
+    if (mc) {   // refuse before anything is staged on the device
+        rc = check_ik_mesh(d, *mc, M, variant);
+        if (rc) return rc;
+    }
     const size_t nj = d->njoint, R = d->restarts, nobs = d->nobs;
     if (!all_finite(target_pos, (size_t)T * 3) || !all_finite(theta_ref, (size_t)T * nj)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_pos / theta_ref must be finite");
     if (nobs && (!all_finite(d->obs, nobs * 6) || !all_finite(d->D, nobs))) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be finite");
@@ -502,7 +677,7 @@ extern "C" int cfs_ik_solve(const cfs_ik_desc *d, int T, const double *target_po
     if (out->cand_iter) o.cand_iter = (int *)up(nullptr, (size_t)T * R * 4);
     if (err == hipSuccess) {
         ik_point(P, obs_d, D_d, tp_d, ta_d, tr_d, &o);
-        err = launch_ik(d->njoint, P, nullptr);
+        err = mc ? launch_ik_mesh(d->njoint, variant, P, M, nullptr) : launch_ik(d->njoint, P, nullptr);
         if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
     }
     auto down = [&](void *h, const void *dv, size_t bytes) { if (err == hipSuccess && h) err = hipMemcpy(h, dv, bytes, hipMemcpyDeviceToHost); };
@@ -513,6 +688,48 @@ extern "C" int cfs_ik_solve(const cfs_ik_desc *d, int T, const double *target_po
     down(out->cand_iter, o.cand_iter, (size_t)T * R * 4);
     for (void *p : bufs) (void)hipFree(p);
     if (err != hipSuccess) return cfs_fail(CFS_ERR_HIP, "IK staging or launch failed: %s", hipGetErrorString(err));
+    return CFS_SUCCESS;
+}
+}  // namespace
+
+extern "C" int cfs_ik_solve_device(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+                                   const cfs_ik_out *out, void *stream)
+{
+    return ik_device(d, nullptr, T, target_pos, target_axis, theta_ref, out, stream);
+}
+
+extern "C" int cfs_ik_solve(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+                            const cfs_ik_out *out)
+{
+    return ik_host(d, nullptr, T, target_pos, target_axis, theta_ref, out);
+}
+
+extern "C" int cfs_ik_solve_mesh_device(const cfs_ik_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
+                                        const double *target_pos, const double *target_axis, const double *theta_ref, const cfs_ik_out *out,
+                                        void *stream)
+{
+    const IkMeshCall mc{nmesh, meshes, D_mesh, flags};
+    return ik_device(d, &mc, T, target_pos, target_axis, theta_ref, out, stream);
+}
+
+extern "C" int cfs_ik_solve_mesh(const cfs_ik_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
+                                 const double *target_pos, const double *target_axis, const double *theta_ref, const cfs_ik_out *out)
+{
+    const IkMeshCall mc{nmesh, meshes, D_mesh, flags};
+    return ik_host(d, &mc, T, target_pos, target_axis, theta_ref, out);
+}
+
+extern "C" int cfs_debug_ik_frontier_overflows(unsigned long long *count, int reset)
+{
+    if (!count && !reset) return cfs_fail(CFS_ERR_INVALID_ARG, "nothing to do: count is NULL and reset is 0");
+    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
+    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
+    CFS_HIPCHK(hipDeviceSynchronize());
+    if (count) CFS_HIPCHK(hipMemcpyFromSymbol(count, HIP_SYMBOL(g_ik_frontier_overflows), sizeof *count));
+    if (reset) {
+        const unsigned long long zero = 0ull;
+        CFS_HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_ik_frontier_overflows), &zero, sizeof zero));
+    }
     return CFS_SUCCESS;
 }
 

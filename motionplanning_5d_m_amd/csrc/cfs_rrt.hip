@@ -31,7 +31,7 @@
 // extends dist_arm: after the line obstacles, for every mesh j and link i, dis = mesh distance of the link axis (contract:
 // cfs_mesh.hip's head comment), |dis| < 1e-4 -> dis = -|points(:,1) - p(:,2)|, reject if dis < D_j.  The surrogate is negative and
 // D_j > 0, so mesh j rejects the node exactly when SOME triangle lies closer than thr_j = max(D_j, 1e-4) to SOME link axis: an
-// existence question.  The traversal prunes a hierarchy node whose rigorous lower bound is not below thr_j and may stop at the
+// existence question (cfs_mesh_hit_dev.h holds the two traversals; cfs_ik.hip asks it too).  The traversal prunes a hierarchy node whose rigorous lower bound is not below thr_j and may stop at the
 // first triangle below it; the decision does not depend on the order.  The mesh test runs only when the lines have passed (the
 // same decision, fewer traversals).  Two variants, bit-identical trees:
 //   A (RRT_MESH_PER_LANE)  lane p < nmesh*NJ owns one (mesh, link) pair and runs mesh_query<64, false>(bound = thr_j); the vote
@@ -45,7 +45,7 @@
 // above covers the whole translation unit), so a distance may differ in its last bits from cfs_dist_arm_mesh, whose translation
 // unit contracts: a proposal within rounding of its threshold may be decided differently from a cfs_dist_arm_mesh call.
 // The line-only kernel (cfs_rrt_kernel) keeps its code path: the mesh code is compiled out of it.
-#include "cfs_mesh_dev.h"
+#include "cfs_mesh_hit_dev.h"
 #include "cfs_geom_dev.h"
 #include "cfs_host.h"
 #include <cmath>
@@ -69,99 +69,6 @@ __device__ __forceinline__ double rrt_uniform(const RrtParams &P, int tree, unsi
 // proposals of variant B whose frontier overflowed and that variant A decided (cfs_debug_rrt_frontier_overflows): one vector atomic
 // by lane 0 per such proposal, none on the normal path
 __device__ unsigned long long g_rrt_frontier_overflows = 0ull;
-
-// link k's axis out of the FK result, without dynamic indexing of the register array
-template <int NJ>
-__device__ __forceinline__ void pick_link(const double *ends, int k, double *a6)
-{
-#pragma unroll
-    for (int kk = 0; kk < NJ; ++kk)
-        if (kk == k) {
-#pragma unroll
-            for (int q = 0; q < 6; ++q) a6[q] = ends[kk * 6 + q];
-        }
-}
-
-// variant A: one (mesh, link) pair per lane, threshold query with a private stack
-template <int NJ>
-__device__ __forceinline__ bool mesh_hit_per_lane(const RrtMeshArgs &MA, const double *ends, int lane, int *stack, float *lbs)
-{
-    bool hit = false;
-    const int npair = MA.nmesh * NJ;
-    for (int p = lane; p < npair; p += WV) {
-        const int j = p / NJ, k = p - j * NJ;
-        double a6[6];
-        pick_link<NJ>(ends, k, a6);
-        const DevMesh m{MA.m[j].nodes, MA.m[j].tri, nullptr, 0, MA.m[j].nt, nullptr, nullptr, 0, 0};
-        Best b;
-        mesh_query<WV, false>(m, a6, a6 + 3, -1, stack + lane, lbs + lane, b, nullptr, MA.m[j].thr);
-        hit = hit || (b.tri >= 0 && b.d < MA.m[j].thr);       // take() also accepts a tie with the bound: the rule is strict (dis < D)
-    }
-    return __ballot(hit) != 0ull;
-}
-
-// variant B: wave-cooperative threshold traversal.  1: some triangle is below its threshold; 0: none; -1: the frontier overflowed
-template <int NJ>
-__device__ __forceinline__ int mesh_hit_wave(const RrtMeshArgs &MA, const double *ends, int lane, int *f_pair, int *f_node)
-{
-    const int npair = MA.nmesh * NJ, cap = MA.cap;
-    if (npair > cap) return -1;
-    for (int p = lane; p < npair; p += WV) { f_pair[p] = p; f_node[p] = 0; }      // the root is always an inner node (upload_mesh)
-    int count = npair;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    while (count > 0) {
-        const int n = count < WV ? count : WV;                // from the end: depth first in blocks of 64, the frontier stays short
-        count -= n;
-        const bool live = lane < n;
-        int p = 0, node = 0;
-        if (live) { p = f_pair[count + lane]; node = f_node[count + lane]; }
-        __builtin_amdgcn_wave_barrier();
-        bool hit = false, push0 = false, push1 = false;
-        int c0 = 0, c1 = 0;
-        if (live) {
-            const int j = p / NJ, k = p - j * NJ;
-            double a6[6];
-            pick_link<NJ>(ends, k, a6);
-            const double thr = MA.m[j].thr;
-            const double *tri = MA.m[j].tri;
-            if (MA.m[j].nt > 0) {
-                const BvhNode nd = MA.m[j].nodes[node];       // one load: both children's boxes
-                const double l0 = node_lower_bound(a6, a6 + 3, nd.lo[0], nd.hi[0]);
-                const double l1 = node_lower_bound(a6, a6 + 3, nd.lo[1], nd.hi[1]);
-                c0 = nd.child[0]; c1 = nd.child[1];
-                const bool s0 = l0 < thr, s1 = l1 < thr;      // an empty child's bound is +inf or NaN: never below
-                push0 = s0 && c0 >= 0; push1 = s1 && c1 >= 0;
-                const int leaf0 = (s0 && c0 < 0) ? c0 : 0, leaf1 = (s1 && c1 < 0) ? c1 : 0;
-#pragma unroll 1
-                for (int it = 0; it < 2; ++it) {
-                    const int lf = it == 0 ? leaf0 : leaf1;
-                    if (lf < 0) {
-                        const int code = -(lf + 1), first = code >> 3, cnt = code & 7;
-                        Best b;
-                        b.d = thr; b.t = INFINITY; b.tri = -1;
-                        for (int q = first; q < first + cnt; ++q) seg_tri_update(a6, a6 + 3, tri + 9 * (size_t)q, q, b);
-                        hit = hit || (b.tri >= 0 && b.d < thr);       // strict, as in variant A
-                    }
-                }
-            }
-        }
-        if (__ballot(hit) != 0ull) return 1;
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const unsigned long long m0 = __ballot(push0);
-        if (push0) { const int pos = count + __popcll(m0 & below); if (pos < cap) { f_pair[pos] = p; f_node[pos] = c0; } }
-        count += __popcll(m0);
-        const unsigned long long m1 = __ballot(push1);
-        if (push1) { const int pos = count + __popcll(m1 & below); if (pos < cap) { f_pair[pos] = p; f_node[pos] = c1; } }
-        count += __popcll(m1);
-        if (count > cap) return -1;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    return 0;
-}
 
 // kernel arguments: the mesh table exists only in the mesh kernels' parameter block
 template <int MESH> struct RrtArgs { RrtParams P; RrtMeshArgs MA; };

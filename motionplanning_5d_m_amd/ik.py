@@ -7,8 +7,12 @@ nearest such configuration to a reference pose.  One wavefront per target, one l
 and unpacks results, the iteration and the selection are HIP kernels (csrc/cfs_ik.hip).
 
 The tool defaults to the reference's end effector: ``tool = robot.cap{njoint}.p(:,1)`` (``all_ee``, Lib/RRT_FANUC.m:186) and
-``tool_axis = unit(p(:,2) - p(:,1))`` of the same capsule.  Mesh obstacles are not read: the collision test is the one of
-line obstacles only.
+``tool_axis = unit(p(:,2) - p(:,1))`` of the same capsule.
+
+Mesh obstacles: the obs cell may end with ``dict(mesh=Mesh, D=...)`` entries (after the line obstacles, the convention of
+``RRT_FANUC`` and ``solvers.obs_meshes``).  A converged restart that passed the lines is then also rejected when a link axis comes
+closer to mesh j than ``max(D_j, 1e-4)`` -- the decision of ``cfs_rrt_grow_mesh`` -- and ``solve`` / ``solve_device`` route to
+``cfs_ik_solve_mesh*`` (include/cfs_hip.h).
 """
 from __future__ import annotations
 
@@ -21,7 +25,8 @@ import numpy as np
 
 from . import _lib
 from .robotproperty2 import to_c_robot
-from .solvers import _f64, _joint_limits_array, _ptr, obs_to_array
+from .mesh import Mesh
+from .solvers import _f64, _joint_limits_array, _ptr, obs_meshes, obs_to_array
 
 try:
     import torch
@@ -94,9 +99,12 @@ def tool_pose(robot, theta, njoint=None, tool=None, tool_axis=None, want_jac=Fal
 
 
 class IKSolver:
-    """Batched inverse kinematics for one robot, one set of line obstacles and one set of joint ranges.
+    """Batched inverse kinematics for one robot, one set of obstacles and one set of joint ranges.
 
-    robot: robotproperty2(id).  obs: None or an obs cell of line obstacles (dict(l=3x2, D=...)); a mesh obstacle is refused.
+    robot: robotproperty2(id).  obs: None or an obs cell of line obstacles (dict(l=3x2, D=...)), which may end with mesh obstacles
+    (dict(mesh=Mesh, D=...), D finite and > 0); a mesh before a line obstacle is refused.  mesh_variant: None (the library's
+    default) or a key of _lib.IK_MESH ("per_lane" | "wave" | "small_frontier"): the developer switch of cfs_ik_solve_mesh*, with
+    bit-identical results under every value.
     joint_limits: "robot" (robot.thetamax[:njoint]) or an (njoint, 2) array of finite [lo, hi].  tool / tool_axis: a point and a
     direction in the frame of link njoint (defaults: default_tool).  restarts: 1..64 starts per target, restart 0 at theta_ref,
     the others drawn in the joint ranges from `seed`.  tol_pos (m) / tol_axis (norm of the difference of unit vectors): what
@@ -105,7 +113,7 @@ class IKSolver:
     Arguments are validated here, before anything touches the device."""
 
     def __init__(self, robot, obs=None, joint_limits="robot", tool=None, tool_axis=None, restarts=64, max_iter=100, tol_pos=1e-6,
-                 tol_axis=1e-6, weight=None, device=None, njoint=None):
+                 tol_axis=1e-6, weight=None, device=None, njoint=None, mesh_variant=None):
         self.robot, self.nj = robot, _njoint(robot, njoint)
         nj = self.nj
         if joint_limits is None:
@@ -135,10 +143,21 @@ class IKSolver:
                 raise ValueError(f"weight must be {nj} finite numbers > 0, not {weight!r}")
             self.weight = _f64(w)
         obs = [] if obs is None else list(obs)
-        if any("mesh" in o for o in obs):
-            raise ValueError("the IK collision test reads line obstacles only: mesh obstacles are not supported")
         if len(obs) > _lib.CFS_MAX_OBS:
             raise ValueError(f"{len(obs)} obstacles: at most {_lib.CFS_MAX_OBS}")
+        self._meshes = obs_meshes(obs)                        # ValueError when a mesh precedes a line obstacle
+        for j, o in enumerate(obs):
+            if "mesh" not in o:
+                continue
+            if not isinstance(o["mesh"], Mesh):
+                raise ValueError(f"obs[{j}]['mesh'] must be a Mesh, not {type(o['mesh']).__name__}")
+            if isinstance(o.get("D"), bool) or not isinstance(o.get("D"), numbers.Real) or not math.isfinite(o["D"]) or not o["D"] > 0:
+                raise ValueError(f"obs[{j}]['D'] (a mesh obstacle) must be a finite real number > 0")
+        self._D_mesh = _f64([o["D"] for o in obs if "mesh" in o])
+        if mesh_variant is not None and (not isinstance(mesh_variant, str) or mesh_variant not in _lib.IK_MESH):
+            raise ValueError(f"mesh_variant must be None or one of {sorted(_lib.IK_MESH)}, not {mesh_variant!r}")
+        self.mesh_variant = mesh_variant
+        obs = [o for o in obs if "mesh" not in o]
         for j, o in enumerate(obs):
             if np.shape(o["l"]) != (3, 2) or not np.isfinite(np.asarray(o["l"], float)).all():
                 raise ValueError(f"obs[{j}]['l'] must be a finite 3x2 array")
@@ -213,12 +232,18 @@ class IKSolver:
         d.seed = seed
         return d
 
+    def _mesh_args(self):
+        """(nmesh, handle array, D_mesh pointer, flags) of cfs_ik_solve_mesh*"""
+        arr = (C.c_void_p * len(self._meshes))(*[m._h for m in self._meshes])
+        return len(self._meshes), arr, _ptr(self._D_mesh), 0 if self.mesh_variant is None else _lib.IK_MESH[self.mesh_variant]
+
     # ---- host arrays in and out (cfs_ik_solve) -----------------------------------------------------------------------------
     def solve(self, target_pos, target_axis=None, theta_ref=None, seed=0, want_candidates=False):
         """Solve T targets: target_pos (T, 3) or (3,); target_axis (T, 3), (3,) or None (position only); theta_ref (T, njoint),
         (njoint,) or None (the middle of the joint ranges).  Returns a namespace of numpy arrays, one row per target: theta
         (T, njoint), status (0 solved | 1 no restart converged | 2 every converged restart collides), selected (the winning restart,
-        -1 without one), n_ok, err_pos, err_axis, clearance (min over the obstacles of distance - D, +inf without obstacles); rows
+        -1 without one), n_ok, err_pos, err_axis, clearance (min over the obstacles, meshes included, of distance - D; +inf without
+        obstacles); rows
         of unsolved targets hold NaN.  want_candidates: also cand_theta (T, restarts, njoint), cand_status, cand_iter."""
         seed = self._seed(seed)
         T, tp, ta, tr = self._targets(target_pos, target_axis, theta_ref)
@@ -231,7 +256,11 @@ class IKSolver:
         for k in vars(r):
             setattr(o, k, _ptr(getattr(r, k)))
         d = self._desc(ta is not None, seed, self.obs, self.D)
-        _lib.check(_lib.lib().cfs_ik_solve(C.byref(d), T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o)))
+        if self._meshes:
+            nm, arr, Dm, fl = self._mesh_args()
+            _lib.check(_lib.lib().cfs_ik_solve_mesh(C.byref(d), nm, arr, Dm, fl, T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o)))
+        else:
+            _lib.check(_lib.lib().cfs_ik_solve(C.byref(d), T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o)))
         return r
 
     # ---- CUDA tensors in and out (cfs_ik_solve_device) ---------------------------------------------------------------------
@@ -280,7 +309,12 @@ class IKSolver:
             for k in vars(r):
                 setattr(o, k, _ptr(getattr(r, k)))
             d = self._desc(ta is not None, seed, self._dev[1], self._dev[2])
-            _lib.check(_lib.lib().cfs_ik_solve_device(C.byref(d), T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o), C.c_void_p(stream.cuda_stream)))
+            if self._meshes:
+                nm, arr, Dm, fl = self._mesh_args()
+                _lib.check(_lib.lib().cfs_ik_solve_mesh_device(C.byref(d), nm, arr, Dm, fl, T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o),
+                                                               C.c_void_p(stream.cuda_stream)))
+            else:
+                _lib.check(_lib.lib().cfs_ik_solve_device(C.byref(d), T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o), C.c_void_p(stream.cuda_stream)))
             for t in (tp, ta, tr, self._dev[1], self._dev[2]):
                 if t is not None:
                     t.record_stream(stream)

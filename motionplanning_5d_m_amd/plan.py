@@ -176,9 +176,10 @@ class RRTCFSPlanner:
         return t.contiguous()
 
     # ---- Cartesian goals ---------------------------------------------------------------------------------------------------
-    def plan_to_pose(self, x0, target_pos, target_axis=None, seed=0, ik_options=None, **plan_kwargs):
+    def plan_to_pose(self, x0, target_pos, target_axis=None, seed=0, ik_options=None, ik_meshes=False, **plan_kwargs):
         """plan() towards Cartesian targets: one inverse-kinematics launch (ik.IKSolver.solve_device: theta_ref = x0, the planner's
-        line obstacles with their D, the planner's joint_limits if it has them, else robot.thetamax; generator seed `seed`), then
+        obstacles with their D -- its line obstacles, and with ik_meshes=True its mesh obstacles too --, the planner's joint_limits if
+        it has them, else robot.thetamax; generator seed `seed`), then
         plan(x0, goal, seed, **plan_kwargs) with the configurations it found.  x0: (S, 5) or (5,); target_pos: (S, 3) or (3,):
         where the tool point goes (default tool: the reference's end effector cap{5}.p(:,1)); target_axis: (S, 3), (3,) or None
         (position only): where the tool axis points.  CUDA tensors on the planner's device or array-likes.  ik_options: keyword
@@ -186,9 +187,15 @@ class RRTCFSPlanner:
         Returns plan()'s namespace plus goal (S, 5; NaN rows without an IK solution), ik_status (0 solved | 1 no restart converged
         | 2 every converged restart collides), ik_err_pos, ik_clearance.  A slot without an IK solution is planned with goal = x0
         (the batch keeps its shape) and then masked: status = -2, has_solution = 0, selected = -1.
-        A planner with mesh obstacles refuses: the IK collision test reads line obstacles only."""
-        if self._meshes:
-            raise ValueError("plan_to_pose is not available with mesh obstacles: the IK collision test reads line obstacles only")
+        ik_meshes: False (the default) keeps the line-only IK collision test, and a planner with mesh obstacles then refuses;
+        True builds the solver from the planner's whole cell -- the lines with their D and the meshes with their D, the numbers
+        cfs_rrt_grow_mesh_device gets -- so that goals are free of the meshes too (cfs_ik_solve_mesh_device).  On a planner without
+        meshes ik_meshes=True is the default path."""
+        if not isinstance(ik_meshes, bool):
+            raise ValueError(f"ik_meshes must be True or False, not {ik_meshes!r}")
+        if self._meshes and not ik_meshes:
+            raise ValueError("plan_to_pose on a planner with mesh obstacles needs ik_meshes=True: the default IK collision test reads "
+                             "line obstacles only")
         if not _is_int(seed) or seed < 0:
             raise ValueError(f"seed must be a non-negative integer, not {seed!r}")
         if ik_options is None:
