@@ -1,8 +1,7 @@
 // cfs_api.hip -- host side of libcfs_hip.so: the C ABI declared in include/cfs_hip.h.
 // Owns the problem-family handle (device constants + workspace) and enqueues the kernels of one
 // solve on a caller-supplied stream without any host round trip inside the outer loop.
-#include "cfs_device.h"
-#include "cfs_host.h"
+#include "cfs_problem.h"
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -16,95 +15,12 @@ namespace {
 thread_local char g_err[512] = "";
 int g_device = 0;
 
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIPCHK(call)                                                                                  \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return fail(CFS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
 int have_device()
 {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
-
-void build_dev_robot(const cfs_robot &r, DevRobot &d)
-{
-    memset(&d, 0, sizeof d);
-    d.kind = r.kind;
-    d.nlink = r.nlink;
-    for (int i = 0; i < r.nlink && i < CFS_MAX_LINKS; ++i) {
-        d.dh_d[i] = r.DH[i + 1 * r.nlink];
-        d.dh_a[i] = r.DH[i + 2 * r.nlink];
-        const double al = r.DH[i + 3 * r.nlink];
-        d.ca[i] = cos(al);
-        d.sa[i] = sin(al);
-        d.th_off[i] = 0.0;
-        for (int e = 0; e < 6; ++e) d.cap[i * 6 + e] = r.cap[i * 6 + e];
-    }
-    if (r.kind == CFS_ROBOT_M200I) d.th_off[1] = M_PI / 2;   // dist_arm_3D_200i_2.m:11
-    for (int e = 0; e < 3; ++e) d.base[e] = r.base[e];
-    if (r.kind == CFS_ROBOT_2L)
-        for (int i = 0; i + 1 < 3 && i < CFS_MAX_LINKS; ++i)   // link i uses robot.T(:,i+2) (1-based), CapPos2.m:25
-            for (int e = 0; e < 3; ++e) d.t2l[i * 3 + e] = r.T[(i + 1) * 3 + e];
-    // every point of the arm stays within `reach` of every joint axis; an evaluation point of num_jac moves each joint
-    // by at most eps/2, so no link-obstacle distance changes by more than nlink*eps/2*reach (the segment distance is
-    // 1-Lipschitz in the end points).  The pruning margin of the linearisation is a generous multiple of that.
-    double reach = 0.0, capmax = 0.0;
-    for (int i = 0; i < r.nlink && i < CFS_MAX_LINKS; ++i) {
-        reach += (r.kind == CFS_ROBOT_2L) ? sqrt(d.t2l[i * 3] * d.t2l[i * 3] + d.t2l[i * 3 + 1] * d.t2l[i * 3 + 1] + d.t2l[i * 3 + 2] * d.t2l[i * 3 + 2])
-                                          : fabs(d.dh_a[i]) + fabs(d.dh_d[i]);
-        for (int k = 0; k < 2; ++k) {
-            const double *c = d.cap + i * 6 + k * 3;
-            capmax = std::max(capmax, sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]));
-        }
-    }
-    d.shift_bound = r.nlink * (1e-5 / 2) * (reach + capmax);
-    d.prune_tol = 1e-3 + 8.0 * d.shift_bound;
-}
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count)
-    {
-        n = count;
-        return hipMalloc(reinterpret_cast<void **>(&p), (count ? count : 1) * sizeof(T));
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
-
-// device staging of host arrays for the host-pointer entry points
-struct Stage {
-    std::vector<void *> ptrs;
-    hipError_t err = hipSuccess;
-    template <class T> T *up(const T *h, size_t n)
-    {
-        if (err != hipSuccess) return nullptr;
-        void *d = nullptr;
-        err = hipMalloc(&d, (n ? n : 1) * sizeof(T));
-        if (err != hipSuccess) return nullptr;
-        ptrs.push_back(d);
-        if (h) err = hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
-        return static_cast<T *>(d);
-    }
-    template <class T> void down(T *h, const T *d, size_t n)
-    {
-        if (err == hipSuccess && h) err = hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost);
-    }
-    ~Stage() { for (void *q : ptrs) (void)hipFree(q); }
-};
 
 // symmetric positive definite inverse in extended precision (once per problem family)
 // lambda_max(G) <= ||G^(2^k)||_inf^(1/2^k) for symmetric G: five squarings are within n^(1/32) of it (+ margin for fp64 rounding)
@@ -125,6 +41,15 @@ double lambda_max_upper(int nn, std::vector<double> G)
     double nrm = 0.0;
     for (int i = 0; i < nn; ++i) { double s = 0.0; for (int j = 0; j < nn; ++j) s += fabs(G[i + (size_t)j * nn]); if (s > nrm) nrm = s; }
     return exp((logscale + log(nrm)) / 32.0) * 1.001;
+}
+
+// (QQ + QQ') / 2: quadprog symmetrises its Hessian silently
+std::vector<double> symmetrise(int nn, const double *QQ)
+{
+    std::vector<double> sym((size_t)nn * nn);
+    for (int j = 0; j < nn; ++j)
+        for (int i = 0; i < nn; ++i) sym[i + (size_t)j * nn] = 0.5 * (QQ[i + (size_t)j * nn] + QQ[j + (size_t)i * nn]);
+    return sym;
 }
 
 bool spd_inverse(int n, const double *Asym, std::vector<double> &inv, std::vector<long double> &Li)
@@ -163,77 +88,6 @@ bool spd_inverse(int n, const double *Asym, std::vector<double> &inv, std::vecto
 
 }  // namespace
 
-struct cfs_problem {
-    cfs_problem_desc d;
-    int device;
-    int nn, ns, nx;
-    double lmax_vel, lmax_H;
-    DevRobot hrobot;
-    DevBuf<DevRobot> rb;
-    DevBuf<double> QQ, Hinv, Hq, M1n, M2n, lim, maxin, margin;
-    DevBuf<double> F1, F2, Cq;   // per-problem cost terms from (x0, xg), set by cfs_set_state_cost
-    DevBuf<DevCost> cost;        // structure of QQ (handles created from the cost weights)
-    std::vector<double> QQ_host; // what cfs_problem_family hands back
-    // workspace (max_batch problems)
-    DevBuf<double> x0, qu, dist, grad, Yg, Pt, u_hist, qu_hist;
-    DevBuf<int> noise_row, linkid, pool_flag;
-    bool pool_dirty = false;   // a solve of this handle failed to enqueue: clear the spill-pool flags before the next one
-    int pool_n = 1;            // slots of the spill pool (Yg / Pt): one per workgroup that can be resident at once, never more than max_batch
-    DevBuf<int> order, okey;   // launch order of the fused solver, automatic: violation count of the initial trajectory -> rank
-    DevBuf<int> order_user;    // the caller's permutation (cfs_set_launch_order); a solve of another batch size falls back to the automatic order
-    int n_cu = 256;            // compute units of the handle's device: a batch of at most n_cu problems starts all at once
-    int order_mode = 0, order_n = 0;   // 0 automatic, 1 given (order_n entries), 2 identity
-    // mesh obstacles (cfs_problem_set_meshes): the last nmesh of the nobs obstacles
-    int nmesh = 0;
-    DevBuf<DevMesh> meshes_d;
-    DevBuf<double> st_cost, m_ends, m_base, m_shift, m_upper, m_pd, m_pnd;
-    DevBuf<int> st_done, m_tri, m_near, m_pi;
-    // cfs_clearance_mesh*: per-sample workspace for cm_S sub-steps (grown by the first audit that needs more) and rho on the device
-    DevBuf<double> cm_d, cm_L, cm_rho;
-    DevBuf<int> cm_lk, cm_tri, cm_seed;
-    int cm_S = 0;
-    // developer / test switches (cfs_debug_*, include/cfs_hip.h): per handle, no process-wide state
-    int dbg_mask = 0, dbg_warm_max = 0;
-    double dbg_polish_tol = 1e-11;        // = the constraint scan's own feasibility tolerance
-    DevBuf<unsigned long long> stamps;    // 12 cycle accumulators per problem
-    int stamps_B = 0;
-    DevBuf<double> trace;                 // 8 doubles per active-set step of problem trace_b
-    int trace_b = -1, trace_cap = 0;
-    DevBuf<double> u_log;                 // max_batch x MAX_O_ITER x nn: u after every outer iteration (both solvers)
-    int jac = CFS_JAC_FD_LITERAL;         // cfs_problem_set_jacobian: which linearisation every later launch of this handle runs
-    int infeas = CFS_INFEAS_STOP;         // cfs_problem_set_infeasible_policy
-    int motion = CFS_OBS_STATIC;          // cfs_problem_set_obstacle_motion: obs arrays are B x nobs x 6 | B x H x nobs x 6
-    bool limited = false;                 // cfs_problem_set_joint_limits: position rows in every QP (the LIM kernels); lim[nj, 3nj) = [lo; hi]
-    std::vector<double> jlim;             // [lo; hi] as set (2 nj; empty: no limits)
-    double rho[CFS_MAX_LINKS * CFS_MAX_LINKS];   // cfs_clearance*: reach of capsule k about the axis of joint m (cfs_clear_build_rho)
-    double soft_weight = 0.0;             // mu of CFS_INFEAS_SOFTEN (0: never set)
-    DevBuf<double> soft_viol;             // max_batch x MAX_O_ITER: viol_all of the last whole solve (allocated with SOFTEN)
-    DevBuf<int> soft_n;                   // max_batch: n_soft of the last whole solve
-    bool prof = false;
-    std::vector<hipEvent_t> ev;   // 4 per profiled solve: gemm start/stop, fused start/stop
-    std::vector<hipEvent_t> ev_free;   // recycled events: none is created inside a timed region once the pool is warm
-    void release_clear_mesh()
-    {
-        cm_d.release(); cm_L.release(); cm_rho.release(); cm_lk.release(); cm_tri.release(); cm_seed.release();
-        cm_S = 0;
-    }
-    void release_all()
-    {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ev_free) (void)hipEventDestroy(e);
-        ev.clear(); ev_free.clear();
-        rb.release(); QQ.release(); Hinv.release(); Hq.release();
-        M1n.release(); M2n.release(); Pt.release(); u_hist.release(); qu_hist.release();
-        F1.release(); F2.release(); Cq.release(); cost.release();
-        lim.release(); maxin.release(); margin.release(); x0.release(); qu.release(); dist.release();
-        grad.release(); Yg.release(); noise_row.release(); order.release(); okey.release(); order_user.release();
-        linkid.release(); pool_flag.release(); meshes_d.release(); st_cost.release(); st_done.release();
-        m_ends.release(); m_base.release(); m_shift.release(); m_tri.release(); m_near.release(); m_upper.release();
-        m_pd.release(); m_pnd.release(); m_pi.release(); release_clear_mesh();
-        stamps.release(); trace.release(); u_log.release(); soft_viol.release(); soft_n.release();
-    }
-};
-
 int cfs_fail(int code, const char *fmt, ...)
 {
     va_list ap;
@@ -243,48 +97,90 @@ int cfs_fail(int code, const char *fmt, ...)
     return code;
 }
 int cfs_current_device() { return g_device; }
-void cfs_build_dev_robot(const cfs_robot &r, DevRobot &d) { build_dev_robot(r, d); }
-void cfs_problem_shape(const cfs_problem *p, ProblemShape *out)
+int cfs_use_device(int device)
 {
-    *out = ProblemShape{p->device, p->d.max_batch, p->nn, p->nx, p->d.MAX_O_ITER, p->infeas};
+    if (have_device() == 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
+    CFS_HIPCHK(hipSetDevice(device));
+    return CFS_SUCCESS;
+}
+int cfs_frontier_overflows(const void *symbol, unsigned long long *count, int reset)
+{
+    if (!count && !reset) return cfs_fail(CFS_ERR_INVALID_ARG, "nothing to do: count is NULL and reset is 0");
+    int rc = cfs_use_device(g_device);
+    if (rc) return rc;
+    CFS_HIPCHK(hipDeviceSynchronize());
+    if (count) CFS_HIPCHK(hipMemcpyFromSymbol(count, symbol, sizeof *count));
+    if (reset) {
+        const unsigned long long zero = 0ull;
+        CFS_HIPCHK(hipMemcpyToSymbol(symbol, &zero, sizeof zero));
+    }
+    return CFS_SUCCESS;
+}
+void cfs_build_dev_robot(const cfs_robot &r, DevRobot &d)
+{
+    memset(&d, 0, sizeof d);
+    d.kind = r.kind;
+    d.nlink = r.nlink;
+    for (int i = 0; i < r.nlink && i < CFS_MAX_LINKS; ++i) {
+        d.dh_d[i] = r.DH[i + 1 * r.nlink];
+        d.dh_a[i] = r.DH[i + 2 * r.nlink];
+        const double al = r.DH[i + 3 * r.nlink];
+        d.ca[i] = cos(al);
+        d.sa[i] = sin(al);
+        d.th_off[i] = 0.0;
+        for (int e = 0; e < 6; ++e) d.cap[i * 6 + e] = r.cap[i * 6 + e];
+    }
+    if (r.kind == CFS_ROBOT_M200I) d.th_off[1] = M_PI / 2;   // dist_arm_3D_200i_2.m:11
+    for (int e = 0; e < 3; ++e) d.base[e] = r.base[e];
+    if (r.kind == CFS_ROBOT_2L)
+        for (int i = 0; i + 1 < 3 && i < CFS_MAX_LINKS; ++i)   // link i uses robot.T(:,i+2) (1-based), CapPos2.m:25
+            for (int e = 0; e < 3; ++e) d.t2l[i * 3 + e] = r.T[(i + 1) * 3 + e];
+    // every point of the arm stays within `reach` of every joint axis; an evaluation point of num_jac moves each joint
+    // by at most eps/2, so no link-obstacle distance changes by more than nlink*eps/2*reach (the segment distance is
+    // 1-Lipschitz in the end points).  The pruning margin of the linearisation is a generous multiple of that.
+    double reach = 0.0, capmax = 0.0;
+    for (int i = 0; i < r.nlink && i < CFS_MAX_LINKS; ++i) {
+        reach += (r.kind == CFS_ROBOT_2L) ? sqrt(d.t2l[i * 3] * d.t2l[i * 3] + d.t2l[i * 3 + 1] * d.t2l[i * 3 + 1] + d.t2l[i * 3 + 2] * d.t2l[i * 3 + 2])
+                                          : fabs(d.dh_a[i]) + fabs(d.dh_d[i]);
+        for (int k = 0; k < 2; ++k) {
+            const double *c = d.cap + i * 6 + k * 3;
+            capmax = std::max(capmax, sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]));
+        }
+    }
+    d.shift_bound = r.nlink * (1e-5 / 2) * (reach + capmax);
+    d.prune_tol = 1e-3 + 8.0 * d.shift_bound;
+}
+int cfs_check_robot(const cfs_robot *r, int nj)
+{
+    if (!r) return cfs_fail(CFS_ERR_INVALID_ARG, "robot is NULL");
+    if (r->kind < CFS_ROBOT_M16IB || r->kind > CFS_ROBOT_2L) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown robot kind %d", r->kind);
+    if (r->nlink < 1 || r->nlink > CFS_MAX_LINKS) return cfs_fail(CFS_ERR_INVALID_ARG, "robot.nlink %d outside 1..%d", r->nlink, CFS_MAX_LINKS);
+    if (nj < 1 || nj > 6 || nj > r->nlink) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (1..6, <= nlink)", nj);
+    if (r->kind == CFS_ROBOT_2L && nj > 2) return cfs_fail(CFS_ERR_INVALID_ARG, "the 2L model has 2 joints");
+    return CFS_SUCCESS;
 }
 
 // Tier of the fused kernel (cfs_device.h).  Two problems per CU win whenever they fit: measured on config 3, PSGCFS
 // 3.6 -> 2.3 ms per solve with w2s, CFS 5.8 -> 5.6 ms with w2m (its infeasibility proofs run active sets of ~100 rows).
 // w2s is compiled for the identity Hessian only (PSGCFS), w2m for QQ only (CFS), w1 for both; force_w1: CFS_DBG_TIER_W1.
 bool fused_fits(int nj, int H, int nobs) { return fused_fits_tier<FUSED_W1>(nj, H, nobs); }
-// The tier is chosen by the static plan for either kind of handle: cfs_problem_set_obstacle_motion admits a per-waypoint handle only
-// when its plan fits every tier the static one fits (fused_fits_move), so a per-waypoint solve runs the same tier, and with constant
-// rows the same arithmetic, as the static one.
-bool fused_fits_move(int nj, int H, int nobs, int mode, bool lim)
+// The tier is chosen by the plain static plan for every kind of handle: cfs_problem_set_obstacle_motion and cfs_problem_set_joint_limits
+// admit a handle only when its plan (move: per-waypoint obstacle rows in the tiles; lim: position rows) fits every tier the plain plan
+// fits, so its solves run the same tier and, with constant rows / limits that never bind, the same arithmetic as the plain handle's.
+static bool fused_keeps_tier(int nj, int H, int nobs, int mode, bool move, bool lim)
 {
-    if (!fused_fits_tier<FUSED_W1>(nj, H, nobs, true, lim)) return false;
-    if (mode == CFS_MODE_PSGCFS) return fused_fits_tier<FUSED_W2S>(nj, H, nobs, true, lim) == fused_fits_tier<FUSED_W2S>(nj, H, nobs);
-    return fused_fits_tier<FUSED_W2M>(nj, H, nobs, true, lim) == fused_fits_tier<FUSED_W2M>(nj, H, nobs);
+    if (!fused_fits_tier<FUSED_W1>(nj, H, nobs, move, lim)) return false;
+    if (mode == CFS_MODE_PSGCFS) return fused_fits_tier<FUSED_W2S>(nj, H, nobs, move, lim) == fused_fits_tier<FUSED_W2S>(nj, H, nobs);
+    return fused_fits_tier<FUSED_W2M>(nj, H, nobs, move, lim) == fused_fits_tier<FUSED_W2M>(nj, H, nobs);
 }
-// The same rule for joint limits: cfs_problem_set_joint_limits admits them only when the LIM plan fits every tier the plain static plan
-// fits, so a limited solve runs the same tier (and, with rows that never bind, the same arithmetic) as the unlimited one.
-bool fused_fits_lim(int nj, int H, int nobs, int mode, bool move)
-{
-    if (!fused_fits_tier<FUSED_W1>(nj, H, nobs, move, true)) return false;
-    if (mode == CFS_MODE_PSGCFS) return fused_fits_tier<FUSED_W2S>(nj, H, nobs, move, true) == fused_fits_tier<FUSED_W2S>(nj, H, nobs);
-    return fused_fits_tier<FUSED_W2M>(nj, H, nobs, move, true) == fused_fits_tier<FUSED_W2M>(nj, H, nobs);
-}
-template <FusedTier T, bool MOVE, bool LIM>
-static hipError_t launch_tier_m(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft)
-{
-    if (soft) return analytic ? launch_fused_tier<T, true, true, MOVE, LIM>(nj, p, s, soft) : launch_fused_tier<T, false, true, MOVE, LIM>(nj, p, s, soft);
-    return analytic ? launch_fused_tier<T, true, false, MOVE, LIM>(nj, p, s, nullptr) : launch_fused_tier<T, false, false, MOVE, LIM>(nj, p, s, nullptr);
-}
-template <FusedTier T, bool LIM>
-static hipError_t launch_tier_l(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft, bool move)
-{
-    return move ? launch_tier_m<T, true, LIM>(nj, p, s, analytic, soft) : launch_tier_m<T, false, LIM>(nj, p, s, analytic, soft);
-}
+// the four switches of a handle -> the template arguments of its kernels
+template <class F> static hipError_t for_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 template <FusedTier T>
 static hipError_t launch_tier(int nj, const FusedParams &p, hipStream_t s, bool analytic, const SoftParams *soft, bool move, bool lim)
 {
-    return lim ? launch_tier_l<T, true>(nj, p, s, analytic, soft, move) : launch_tier_l<T, false>(nj, p, s, analytic, soft, move);
+    return for_bool(analytic, [&](auto J) { return for_bool(soft != nullptr, [&](auto S) { return for_bool(move, [&](auto M) { return for_bool(lim, [&](auto L) {
+        return launch_fused_tier<T, decltype(J)::value, decltype(S)::value, decltype(M)::value, decltype(L)::value>(nj, p, s, soft);
+    }); }); }); });
 }
 // the one rule: read by launch_fused and by cfs_debug_fused_tier
 static FusedTier fused_tier(int nj, int H, int nobs, int mode, bool force_w1)
@@ -312,8 +208,8 @@ int cfs_device_count(void) { return have_device(); }
 int cfs_set_device(int device)
 {
     const int n = have_device();
-    if (n == 0) return fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= n) return fail(CFS_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, n - 1);
+    if (n == 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= n) return cfs_fail(CFS_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, n - 1);
     g_device = device;
     return CFS_SUCCESS;
 }
@@ -321,39 +217,25 @@ int cfs_set_device(int device)
 static size_t pt_stride(int nn) { return nn > 160 ? (size_t)256 * 256 : (nn > 96 ? (size_t)160 * 160 : (size_t)96 * 96); }   // QB*QB >= (QB-PR)*QB in every tier
 
 
-static int check_robot(const cfs_robot *r, int nj)
-{
-    if (!r) return fail(CFS_ERR_INVALID_ARG, "robot is NULL");
-    if (r->kind < CFS_ROBOT_M16IB || r->kind > CFS_ROBOT_2L) return fail(CFS_ERR_INVALID_ARG, "unknown robot kind %d", r->kind);
-    if (r->nlink < 1 || r->nlink > CFS_MAX_LINKS) return fail(CFS_ERR_INVALID_ARG, "robot.nlink %d outside 1..%d", r->nlink, CFS_MAX_LINKS);
-    if (nj < 1 || nj > 6 || nj > r->nlink) return fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (1..6, <= nlink)", nj);
-    if (r->kind == CFS_ROBOT_2L && nj > 2) return fail(CFS_ERR_INVALID_ARG, "the 2L model has 2 joints");
-    return CFS_SUCCESS;
-}
-
-}  // extern "C"
-int cfs_check_robot(const cfs_robot *r, int nj) { return check_robot(r, nj); }
-extern "C" {
-
 int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
 {
-    if (!desc || !out) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!desc || !out) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
     const int nj = desc->njoint, H = desc->H;
-    int rc = check_robot(&desc->robot, nj);
+    int rc = cfs_check_robot(&desc->robot, nj);
     if (rc) return rc;
-    if (nj < 2) return fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", nj);
-    if (H < 1 || H > CFS_MAX_H) return fail(CFS_ERR_INVALID_ARG, "H %d outside 1..%d", H, CFS_MAX_H);
-    if (desc->nobs < 1 || desc->nobs > CFS_MAX_OBS) return fail(CFS_ERR_INVALID_ARG, "nobs %d outside 1..%d", desc->nobs, CFS_MAX_OBS);
-    if (desc->mode != CFS_MODE_CFS && desc->mode != CFS_MODE_PSGCFS) return fail(CFS_ERR_INVALID_ARG, "unknown mode %d", desc->mode);
-    if (!desc->QQ || !desc->lim || !desc->margin) return fail(CFS_ERR_INVALID_ARG, "QQ/lim/margin must be given");
-    if (desc->mode == CFS_MODE_CFS && !desc->MAX_input) return fail(CFS_ERR_INVALID_ARG, "MAX_input must be given in CFS mode");
-    if (desc->max_batch < 1) return fail(CFS_ERR_INVALID_ARG, "max_batch must be >= 1");
+    if (nj < 2) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", nj);
+    if (H < 1 || H > CFS_MAX_H) return cfs_fail(CFS_ERR_INVALID_ARG, "H %d outside 1..%d", H, CFS_MAX_H);
+    if (desc->nobs < 1 || desc->nobs > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d outside 1..%d", desc->nobs, CFS_MAX_OBS);
+    if (desc->mode != CFS_MODE_CFS && desc->mode != CFS_MODE_PSGCFS) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown mode %d", desc->mode);
+    if (!desc->QQ || !desc->lim || !desc->margin) return cfs_fail(CFS_ERR_INVALID_ARG, "QQ/lim/margin must be given");
+    if (desc->mode == CFS_MODE_CFS && !desc->MAX_input) return cfs_fail(CFS_ERR_INVALID_ARG, "MAX_input must be given in CFS mode");
+    if (desc->max_batch < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "max_batch must be >= 1");
     if (!fused_fits(nj, H, desc->nobs))
-        return fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d exceeds the 160 KB on-chip budget of one problem (nobs*H*njoint*8 B of gradients must fit next to the solver state)", H, desc->nobs, nj);
-    if (desc->MAX_O_ITER < 0) return fail(CFS_ERR_INVALID_ARG, "MAX_O_ITER must be >= 0");
+        return cfs_fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d exceeds the 160 KB on-chip budget of one problem (nobs*H*njoint*8 B of gradients must fit next to the solver state)", H, desc->nobs, nj);
+    if (desc->MAX_O_ITER < 0) return cfs_fail(CFS_ERR_INVALID_ARG, "MAX_O_ITER must be >= 0");
     const double dt = desc->robot.delta_t;
-    if (!(dt > 0)) return fail(CFS_ERR_INVALID_ARG, "robot.delta_t must be positive");
+    if (!(dt > 0)) return cfs_fail(CFS_ERR_INVALID_ARG, "robot.delta_t must be positive");
     const int nn = H * nj, ns = 2 * nj, nx = H * ns;
 
     // sys_info.Aaug / Baug must be the double integrator of robot.A / robot.B
@@ -367,7 +249,7 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
                         if (k <= i && (r % nj) == c) want = r < nj ? ((double)(i - k) + 0.5) * dt * dt : dt;
                         const double got = desc->Baug[(i * ns + r) + (size_t)(k * nj + c) * nx];
                         if (fabs(got - want) > 1e-12 * (1.0 + fabs(want)))
-                            return fail(CFS_ERR_DYNAMICS, "Baug(%d,%d)=%.17g, double integrator expects %.17g", i * ns + r + 1, k * nj + c + 1, got, want);
+                            return cfs_fail(CFS_ERR_DYNAMICS, "Baug(%d,%d)=%.17g, double integrator expects %.17g", i * ns + r + 1, k * nj + c + 1, got, want);
                     }
     }
     if (desc->Aaug) {
@@ -378,21 +260,17 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
                     if (r < nj && c == r + nj) want = (double)(i + 1) * dt;
                     const double got = desc->Aaug[(i * ns + r) + (size_t)c * nx];
                     if (fabs(got - want) > 1e-12 * (1.0 + fabs(want)))
-                        return fail(CFS_ERR_DYNAMICS, "Aaug(%d,%d)=%.17g, double integrator expects %.17g", i * ns + r + 1, c + 1, got, want);
+                        return cfs_fail(CFS_ERR_DYNAMICS, "Aaug(%d,%d)=%.17g, double integrator expects %.17g", i * ns + r + 1, c + 1, got, want);
                 }
     }
-    if (have_device() == 0) return fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
+    if (have_device() == 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
 
     // H^{-1} of the QP Hessian: QQ symmetrised (quadprog does so silently) for CFS, identity for the
     // PSGCFS projection (PSGCFS_FANUC.m:117)
     std::vector<double> Hinv;
     std::vector<long double> Li;            // L^{-1} (lower), H = L L'
-    {
-        std::vector<double> sym((size_t)nn * nn);
-        for (int j = 0; j < nn; ++j)
-            for (int i = 0; i < nn; ++i) sym[i + (size_t)j * nn] = 0.5 * (desc->QQ[i + (size_t)j * nn] + desc->QQ[j + (size_t)i * nn]);
-        if (!spd_inverse(nn, sym.data(), Hinv, Li)) return fail(CFS_ERR_NOT_SPD, "QQ is not positive definite");
-    }
+    const std::vector<double> sym = symmetrise(nn, desc->QQ);
+    if (!spd_inverse(nn, sym.data(), Hinv, Li)) return cfs_fail(CFS_ERR_NOT_SPD, "QQ is not positive definite");
     std::vector<double> Hq;   // Hessian inverse used by the QP
     if (desc->mode == CFS_MODE_CFS) Hq = Hinv;
     else {
@@ -428,10 +306,8 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
     // that u = D s/dt for s = Bvel u), H = the QP Hessian (QQ symmetrised | I): the early infeasibility test of the fused kernel
     double lmax_vel = 0.0, lmax_H = 1.0;
     {
-        std::vector<double> Hs((size_t)nn * nn), G((size_t)nn * nn);
-        for (int j = 0; j < nn; ++j)
-            for (int i = 0; i < nn; ++i)
-                Hs[i + (size_t)j * nn] = desc->mode == CFS_MODE_CFS ? 0.5 * ((double)desc->QQ[i + (size_t)j * nn] + desc->QQ[j + (size_t)i * nn]) : (i == j ? 1.0 : 0.0);
+        const std::vector<double> &Hs = desc->mode == CFS_MODE_CFS ? sym : Hq;   // Hq is the identity for PSGCFS
+        std::vector<double> G;
         auto Dt = [&](std::vector<double> &M, bool left) {     // M <- D'M (left) or M D (right): row/col k minus row/col k+nj
             for (int o = 0; o < nn; ++o)
                 for (int k = 0; k + nj < nn; ++k) {
@@ -445,14 +321,14 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
         if (desc->mode == CFS_MODE_CFS) lmax_H = lambda_max_upper(nn, Hs);   // not 1/alpha: alpha is the caller's PSGCFS step
     }
     cfs_problem *p = new (std::nothrow) cfs_problem();
-    if (!p) return fail(CFS_ERR_ALLOC, "out of host memory");
+    if (!p) return cfs_fail(CFS_ERR_ALLOC, "out of host memory");
     p->d = *desc;
     p->QQ_host.assign(desc->QQ, desc->QQ + (size_t)nn * nn);
     p->d.QQ = p->d.Aaug = p->d.Baug = p->d.lim = p->d.MAX_input = p->d.margin = nullptr;
     p->device = g_device;
     if (hipDeviceGetAttribute(&p->n_cu, hipDeviceAttributeMultiprocessorCount, g_device) != hipSuccess || p->n_cu < 1) p->n_cu = 256;
     p->nn = nn; p->ns = ns; p->nx = nx; p->lmax_vel = lmax_vel; p->lmax_H = lmax_H;
-    build_dev_robot(desc->robot, p->hrobot);
+    cfs_build_dev_robot(desc->robot, p->hrobot);
     cfs_clear_build_rho(p->hrobot, nj, p->rho);
     const size_t Bm = (size_t)desc->max_batch;
     // spill pool (rows of Y beyond LDS, columns of P beyond the registers): one slot per workgroup that can be resident at once (two per
@@ -479,7 +355,7 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
     if (e != hipSuccess) {
         p->release_all();
         delete p;
-        return fail(CFS_ERR_HIP, "device setup failed: %s", hipGetErrorString(e));
+        return cfs_fail(CFS_ERR_HIP, "device setup failed: %s", hipGetErrorString(e));
     }
     *out = p;
     return CFS_SUCCESS;
@@ -495,7 +371,7 @@ void cfs_problem_destroy(cfs_problem *p)
 
 int cfs_problem_family(const cfs_problem *p, double *QQ, double *alpha)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
     if (QQ) memcpy(QQ, p->QQ_host.data(), p->QQ_host.size() * sizeof(double));
     if (alpha) *alpha = p->d.alpha;
     return CFS_SUCCESS;
@@ -535,13 +411,13 @@ static double sym_lambda_max(int n, std::vector<double> A)
 
 int cfs_problem_create_from_weights(const cfs_problem_desc *desc, const cfs_cost_weights *w, cfs_problem **out)
 {
-    if (!desc || !w || !out) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!desc || !w || !out) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
-    if (!w->Qp || !w->Qv || !w->Rblk) return fail(CFS_ERR_INVALID_ARG, "Qp/Qv/Rblk must be given");
+    if (!w->Qp || !w->Qv || !w->Rblk) return cfs_fail(CFS_ERR_INVALID_ARG, "Qp/Qv/Rblk must be given");
     const int nj = desc->njoint, H = desc->H;
-    if (nj < 2 || nj > 6 || H < 1 || H > CFS_MAX_H) return fail(CFS_ERR_INVALID_ARG, "njoint %d / H %d unsupported", nj, H);
+    if (nj < 2 || nj > 6 || H < 1 || H > CFS_MAX_H) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d / H %d unsupported", nj, H);
     const double dt = desc->robot.delta_t;
-    if (!(dt > 0)) return fail(CFS_ERR_INVALID_ARG, "robot.delta_t must be positive");
+    if (!(dt > 0)) return cfs_fail(CFS_ERR_INVALID_ARG, "robot.delta_t must be positive");
     const int ns = 2 * nj, nn = H * nj, nx = H * ns;
     // Q = [Qp qc*I; qc*I Qv] (main_FANUC.m:65-77), Qaug = blkdiag(Q*w_stage, ..., Q*w_terminal) (:81-84)
     std::vector<double> Q((size_t)ns * ns, 0.0), Qaug((size_t)nx * nx, 0.0);
@@ -591,10 +467,7 @@ int cfs_problem_create_from_weights(const cfs_problem_desc *desc, const cfs_cost
     d2.QQ = QQ.data();
     d2.Aaug = d2.Baug = nullptr;                           // implied: the double integrator
     if (d2.alpha == 0.0 && d2.mode == CFS_MODE_PSGCFS) {   // alpha = 1/max(svd(QQ))  (main_FANUC.m:120)
-        std::vector<double> sym((size_t)nn * nn);
-        for (int j = 0; j < nn; ++j)
-            for (int i = 0; i < nn; ++i) sym[i + (size_t)j * nn] = 0.5 * (QQ[i + (size_t)j * nn] + QQ[j + (size_t)i * nn]);
-        d2.alpha = 1.0 / sym_lambda_max(nn, sym);
+        d2.alpha = 1.0 / sym_lambda_max(nn, symmetrise(nn, QQ.data()));
     }
     cfs_problem *p = nullptr;
     int rc = cfs_problem_create(&d2, &p);
@@ -603,7 +476,7 @@ int cfs_problem_create_from_weights(const cfs_problem_desc *desc, const cfs_cost
     if (rc == CFS_SUCCESS) {
         hipError_t e = p->cost.alloc(1);
         if (e == hipSuccess) e = hipMemcpy(p->cost.p, &hc, sizeof hc, hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = fail(CFS_ERR_HIP, "device setup failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = cfs_fail(CFS_ERR_HIP, "device setup failed: %s", hipGetErrorString(e));
     }
     if (rc) { cfs_problem_destroy(p); return rc; }
     *out = p;
@@ -632,10 +505,7 @@ static void fill_fused_family(const cfs_problem *p, FusedParams &fp, int B)
 }
 static bool force_w1(const cfs_problem *p) { return (p->dbg_mask & CFS_DBG_TIER_W1) != 0; }
 static bool analytic(const cfs_problem *p) { return p->jac == CFS_JAC_ANALYTIC; }
-static bool moving(const cfs_problem *p) { return p->motion == CFS_OBS_PER_WAYPOINT; }
 static bool limited(const cfs_problem *p) { return p->limited; }
-// obstacle rows per problem in every obs array the handle reads: nobs (static) | H x nobs (per waypoint)
-static size_t obs_rows(const cfs_problem *p) { return (size_t)p->d.nobs * (moving(p) ? (size_t)p->d.H : 1); }
 // the soft kernels' parameters for a SOFTEN handle (null: STOP, the default kernels); whole: record viol_all / n_soft
 static const SoftParams *soft_params(const cfs_problem *p, SoftParams &sp, bool whole)
 {
@@ -648,32 +518,43 @@ static const SoftParams *soft_params(const cfs_problem *p, SoftParams &sp, bool 
 
 int cfs_set_launch_order(cfs_problem *p, const int *order, int n)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     if (!order) { p->order_mode = n < 0 ? 2 : 0; p->order_n = 0; return CFS_SUCCESS; }
-    if (n < 1 || n > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "n=%d outside 1..max_batch=%d", n, p->d.max_batch);
+    if (n < 1 || n > p->d.max_batch) return cfs_fail(CFS_ERR_INVALID_ARG, "n=%d outside 1..max_batch=%d", n, p->d.max_batch);
     std::vector<char> seen((size_t)n, 0);
     for (int i = 0; i < n; ++i) {
-        if (order[i] < 0 || order[i] >= n || seen[order[i]]) return fail(CFS_ERR_INVALID_ARG, "order is not a permutation of 0..%d (entry %d)", n - 1, i);
+        if (order[i] < 0 || order[i] >= n || seen[order[i]]) return cfs_fail(CFS_ERR_INVALID_ARG, "order is not a permutation of 0..%d (entry %d)", n - 1, i);
         seen[order[i]] = 1;
     }
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());      // a solve in flight may still be reading the previous order
-    HIPCHK(hipMemcpy(p->order_user.p, order, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    CFS_HIPCHK(hipSetDevice(p->device));
+    CFS_HIPCHK(hipDeviceSynchronize());      // a solve in flight may still be reading the previous order
+    CFS_HIPCHK(hipMemcpy(p->order_user.p, order, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
     p->order_mode = 1; p->order_n = n;
     return CFS_SUCCESS;
 }
 
 static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch_out *out, hipStream_t s, hipEvent_t *e4);
 
+// the handle's part of the mesh linearisation's parameter block (the caller sets x_, status_done and seed_prev)
+static LinMeshParams lin_mesh_params(const cfs_problem *p, int B)
+{
+    LinMeshParams lm;
+    lm.rb = p->rb.p; lm.B = B; lm.H = p->d.H; lm.nmesh = p->nmesh; lm.meshes = p->meshes_d.p;
+    lm.dist = p->dist.p; lm.grad = p->grad.p;
+    lm.ends = p->m_ends.p; lm.base_d = p->m_base.p; lm.upper_d = p->m_upper.p; lm.base_t = p->m_tri.p; lm.shift_d = p->m_shift.p;
+    lm.near = p->m_near.p; lm.piece_d = p->m_pd.p; lm.piece_i = p->m_pi.p; lm.piece_nd = p->m_pnd.p;
+    return lm;
+}
+
 int cfs_solve_batch_device(cfs_problem *p, const cfs_batch_in *in, const cfs_batch_out *out, void *stream)
 {
-    if (!p || !in || !out) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p || !in || !out) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     const int B = in->B;
-    if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
-    if (!in->x_init || !in->xR1 || !in->ff || !in->caug || !in->obs) return fail(CFS_ERR_INVALID_ARG, "NULL input array");
+    if (int rc = cfs_check_batch(p, B)) return rc;
+    if (!in->x_init || !in->xR1 || !in->ff || !in->caug || !in->obs) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL input array");
     if (!out->u || !out->x_ || !out->cost_all || !out->e_cost_all || !out->e_u_all || !out->iter_O || !out->total_iter || !out->status)
-        return fail(CFS_ERR_INVALID_ARG, "NULL output array");
-    HIPCHK(hipSetDevice(p->device));
+        return cfs_fail(CFS_ERR_INVALID_ARG, "NULL output array");
+    CFS_HIPCHK(hipSetDevice(p->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 
     hipEvent_t e4[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -681,7 +562,7 @@ int cfs_solve_batch_device(cfs_problem *p, const cfs_batch_in *in, const cfs_bat
     if (p->prof)
         for (int k = 0; k < 4 && rc == CFS_SUCCESS; ++k) {
             if (!p->ev_free.empty()) { e4[k] = p->ev_free.back(); p->ev_free.pop_back(); }
-            else if (hipEventCreate(&e4[k]) != hipSuccess) { e4[k] = nullptr; rc = fail(CFS_ERR_HIP, "hipEventCreate failed"); }
+            else if (hipEventCreate(&e4[k]) != hipSuccess) { e4[k] = nullptr; rc = cfs_fail(CFS_ERR_HIP, "hipEventCreate failed"); }
         }
     if (rc == CFS_SUCCESS) {
         rc = enqueue_solve(p, in, out, s, e4);
@@ -700,16 +581,16 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
     // cleared at creation and again after a solve whose enqueue failed half way -- not per solve: with the chip held by another
     // solve's fused workgroups even a memset node waits ~0.08 ms for a slot on this stream.
     if (p->pool_dirty) {
-        HIPCHK(hipMemsetAsync(p->pool_flag.p, 0, (size_t)p->pool_n * 16 * sizeof(int), s));
+        CFS_HIPCHK(hipMemsetAsync(p->pool_flag.p, 0, (size_t)p->pool_n * 16 * sizeof(int), s));
         p->pool_dirty = false;
     }
-    if (p->prof) HIPCHK(hipEventRecord(e4[0], s));
+    if (p->prof) CFS_HIPCHK(hipEventRecord(e4[0], s));
     if (p->d.mode == CFS_MODE_CFS) {     // unconstrained minimiser -H^{-1} ff (MFMA), constant over the outer loop
         GemvParams g;
         g.B = B; g.nn = nn; g.M = p->Hinv.p; g.X = in->ff; g.Y = p->x0.p; g.scale = -1.0;
         launch_batched_gemv(g, s);
     }
-    if (p->prof) HIPCHK(hipEventRecord(e4[1], s));
+    if (p->prof) CFS_HIPCHK(hipEventRecord(e4[1], s));
     FusedParams fp;
     fill_fused_family(p, fp, B);
     fp.noise_rows = in->noise ? in->noise_rows : 0;
@@ -726,7 +607,7 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
     else if (p->order_mode != 2 && !(p->dbg_mask & CFS_DBG_NO_AUTO_ORDER) && B > p->n_cu && nline > 0) {   // also when a given order is for another batch size
         OrderParams op;
         op.rb = p->rb.p; op.B = B; op.H = p->d.H; op.nj = nj; op.nobs = nline; op.obs_stride = p->d.nobs;
-        op.wp_stride = moving(p) ? p->d.nobs : 0;
+        op.wp_stride = cfs_moving(p) ? p->d.nobs : 0;
         op.x_init = in->x_init; op.obs = in->obs; op.margin = p->margin.p; op.key = p->okey.p; op.order = p->order.p;
         launch_order(op, s);
         fp.order = p->order.p;
@@ -734,32 +615,29 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
     SoftParams sp;
     const SoftParams *soft = soft_params(p, sp, true);
     if (p->soft_viol.p) {                // viol_all / n_soft of this solve (zero beyond each problem's last iteration; all zero under STOP)
-        HIPCHK(hipMemsetAsync(p->soft_viol.p, 0, (size_t)B * std::max(K, 1) * sizeof(double), s));
-        HIPCHK(hipMemsetAsync(p->soft_n.p, 0, (size_t)B * sizeof(int), s));
+        CFS_HIPCHK(hipMemsetAsync(p->soft_viol.p, 0, (size_t)B * std::max(K, 1) * sizeof(double), s));
+        CFS_HIPCHK(hipMemsetAsync(p->soft_n.p, 0, (size_t)B * sizeof(int), s));
     }
-    if (p->prof) HIPCHK(hipEventRecord(e4[2], s));   // after the launch-order pre-pass: [e4[2], e4[3]] brackets the fused kernel alone (mesh handles: the loop of launches)
+    if (p->prof) CFS_HIPCHK(hipEventRecord(e4[2], s));   // after the launch-order pre-pass: [e4[2], e4[3]] brackets the fused kernel alone (mesh handles: the loop of launches)
     if (p->nmesh == 0) {
-        HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), soft, moving(p), limited(p)));
+        CFS_HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), soft, cfs_moving(p), limited(p)));
     } else {
         // Mesh obstacles are linearised by their own kernel (hierarchy traversals do not fit the fused kernel's register
         // budget), which needs the current iterate: one outer iteration per launch, state carried through HBM.  Every
         // launch is enqueued up front; finished problems return at once, so there is still no host round trip.
-        LinMeshParams lm;
-        lm.rb = p->rb.p; lm.B = B; lm.H = p->d.H; lm.nmesh = p->nmesh; lm.meshes = p->meshes_d.p;
-        lm.dist = p->dist.p; lm.grad = p->grad.p;
-        lm.ends = p->m_ends.p; lm.base_d = p->m_base.p; lm.upper_d = p->m_upper.p; lm.base_t = p->m_tri.p; lm.shift_d = p->m_shift.p; lm.near = p->m_near.p; lm.piece_d = p->m_pd.p; lm.piece_i = p->m_pi.p; lm.piece_nd = p->m_pnd.p;
+        LinMeshParams lm = lin_mesh_params(p, B);
         fp.nmesh = p->nmesh; fp.ext_dist = p->dist.p; fp.ext_grad = p->grad.p; fp.max_launch_iters = 1;
         fp.st_qu = p->qu.p; fp.st_cost = p->st_cost.p; fp.st_noise = p->noise_row.p; fp.st_done = p->st_done.p;
         for (int it = 0; it < std::max(K, 1); ++it) {
             lm.x_ = it == 0 ? in->x_init : out->x_;
             lm.status_done = it == 0 ? nullptr : p->st_done.p;
             lm.seed_prev = it > 0;
-            HIPCHK(launch_linearize_mesh(nj, lm, s));
+            CFS_HIPCHK(launch_linearize_mesh(nj, lm, s));
             fp.resume = it > 0;
-            HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), nullptr, false, limited(p)));
+            CFS_HIPCHK(launch_fused(nj, fp, s, force_w1(p), analytic(p), nullptr, false, limited(p)));
         }
     }
-    if (p->prof) HIPCHK(hipEventRecord(e4[3], s));
+    if (p->prof) CFS_HIPCHK(hipEventRecord(e4[3], s));
     if (fp.u_hist) {                     // CFS cost history: QQ * (all logged u) on the matrix cores, then the dots
         if (p->u_hist.n) {
             GemvParams g;
@@ -771,17 +649,17 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
             launch_cost_history(ch, s);
         }
     }
-    HIPCHK(hipGetLastError());
+    CFS_HIPCHK(hipGetLastError());
     return CFS_SUCCESS;
 }
 
 int cfs_solve_batch(cfs_problem *p, const cfs_batch_in *in, const cfs_batch_out *out)
 {
-    if (!p || !in || !out) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p || !in || !out) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     const int B = in->B;
-    if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
-    if (!in->x_init || !in->xR1 || !in->ff || !in->caug || !in->obs) return fail(CFS_ERR_INVALID_ARG, "NULL input array");
-    HIPCHK(hipSetDevice(p->device));
+    if (int rc = cfs_check_batch(p, B)) return rc;
+    if (!in->x_init || !in->xR1 || !in->ff || !in->caug || !in->obs) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL input array");
+    CFS_HIPCHK(hipSetDevice(p->device));
     const size_t nn = p->nn, nx = p->nx, ns = p->ns, K = p->d.MAX_O_ITER;
     Stage st;
     cfs_batch_in din = *in;
@@ -789,24 +667,21 @@ int cfs_solve_batch(cfs_problem *p, const cfs_batch_in *in, const cfs_batch_out 
     din.xR1 = st.up(in->xR1, B * ns);
     din.ff = st.up(in->ff, B * nn);
     din.caug = st.up(in->caug, B);
-    din.obs = st.up(in->obs, B * obs_rows(p) * 6);
+    din.obs = st.up(in->obs, B * cfs_obs_rows(p) * 6);
     din.noise = in->noise ? st.up(in->noise, (size_t)B * in->noise_rows * nn) : nullptr;
     cfs_batch_out dout;
-    dout.u = st.up<double>(nullptr, B * nn);
-    dout.x_ = st.up<double>(nullptr, B * nx);
-    dout.cost_all = st.up<double>(nullptr, B * K);
-    dout.e_cost_all = st.up<double>(nullptr, B * K);
-    dout.e_u_all = st.up<double>(nullptr, B * K);
-    dout.iter_O = st.up<int>(nullptr, B);
-    dout.total_iter = st.up<int>(nullptr, B);
-    dout.status = st.up<int>(nullptr, B);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
-    HIPCHK(hipMemset(dout.cost_all, 0, B * K * sizeof(double)));
-    HIPCHK(hipMemset(dout.e_cost_all, 0, B * K * sizeof(double)));
-    HIPCHK(hipMemset(dout.e_u_all, 0, B * K * sizeof(double)));
+    dout.u = st.out<double>(B * nn);
+    dout.x_ = st.out<double>(B * nx);
+    dout.cost_all = st.zeros<double>(B * K);
+    dout.e_cost_all = st.zeros<double>(B * K);
+    dout.e_u_all = st.zeros<double>(B * K);
+    dout.iter_O = st.out<int>(B);
+    dout.total_iter = st.out<int>(B);
+    dout.status = st.out<int>(B);
+    if (st.err != hipSuccess) return st.result("staging");
     int rc = cfs_solve_batch_device(p, &din, &dout, nullptr);
     if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
     st.down(out->u, dout.u, B * nn);
     st.down(out->x_, dout.x_, B * nx);
     st.down(out->cost_all, dout.cost_all, B * K);
@@ -815,8 +690,7 @@ int cfs_solve_batch(cfs_problem *p, const cfs_batch_in *in, const cfs_batch_out 
     st.down(out->iter_O, dout.iter_O, B);
     st.down(out->total_iter, dout.total_iter, B);
     st.down(out->status, dout.status, B);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
+    return st.result("copy back");
 }
 
 // ---- EVAL.get_Cost_b (Lib/EVAL.m:75-78; main_FANUC.m:131-132) ----------------------------------------------------------
@@ -824,14 +698,14 @@ int cfs_solve_batch(cfs_problem *p, const cfs_batch_in *in, const cfs_batch_out 
 // two products on the matrix cores (the first is the one every CFS solve starts with) and one dot per problem.
 int cfs_cost_b(cfs_problem *p, int B, const double *ff, const double *caug, double *cost_b, double *u_b)
 {
-    if (!p || !ff || !caug || !cost_b) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
-    if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
-    HIPCHK(hipSetDevice(p->device));
+    if (!p || !ff || !caug || !cost_b) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = cfs_check_batch(p, B)) return rc;
+    CFS_HIPCHK(hipSetDevice(p->device));
     const size_t nn = p->nn;
     Stage st;
     const double *d_ff = st.up(ff, B * nn), *d_caug = st.up(caug, (size_t)B);
-    double *d_cost = st.up<double>(nullptr, (size_t)B);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
+    double *d_cost = st.out<double>((size_t)B);
+    if (st.err != hipSuccess) return st.result("staging");
     GemvParams g;
     g.B = B; g.nn = (int)nn; g.M = p->Hinv.p; g.X = d_ff; g.Y = p->x0.p; g.scale = -1.0;
     launch_batched_gemv(g, nullptr);
@@ -842,25 +716,24 @@ int cfs_cost_b(cfs_problem *p, int B, const double *ff, const double *caug, doub
     ch.B = B; ch.nn = (int)nn; ch.max_o_iter = 1; ch.u_hist = p->x0.p; ch.qu_hist = p->qu.p; ch.ff = d_ff; ch.caug = d_caug;
     ch.iter_O = nullptr; ch.cost_all = d_cost; ch.e_cost_all = nullptr;      // iter_O == NULL: one logged iterate per problem
     launch_cost_history(ch, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(nullptr));
+    CFS_HIPCHK(hipGetLastError());
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
     st.down(cost_b, d_cost, (size_t)B);
     if (u_b) st.down(u_b, p->x0.p, B * nn);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
+    return st.result("copy back");
 }
 
 // cost = self.eval.get_cost(u) (Lib/EVAL.m:51-53) for B given u: QQ*u on the matrix cores, one dot per problem
 int cfs_get_cost(cfs_problem *p, int B, const double *u, const double *ff, const double *caug, double *cost)
 {
-    if (!p || !u || !ff || !caug || !cost) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
-    if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
-    HIPCHK(hipSetDevice(p->device));
+    if (!p || !u || !ff || !caug || !cost) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = cfs_check_batch(p, B)) return rc;
+    CFS_HIPCHK(hipSetDevice(p->device));
     const size_t nn = p->nn;
     Stage st;
     const double *d_u = st.up(u, B * nn), *d_ff = st.up(ff, B * nn), *d_caug = st.up(caug, (size_t)B);
-    double *d_cost = st.up<double>(nullptr, (size_t)B);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
+    double *d_cost = st.out<double>((size_t)B);
+    if (st.err != hipSuccess) return st.result("staging");
     GemvParams g;
     g.B = B; g.nn = (int)nn; g.M = p->QQ.p; g.X = d_u; g.Y = p->qu.p; g.scale = 1.0;
     launch_batched_gemv(g, nullptr);
@@ -868,21 +741,20 @@ int cfs_get_cost(cfs_problem *p, int B, const double *u, const double *ff, const
     memset(&ch, 0, sizeof ch);
     ch.B = B; ch.nn = (int)nn; ch.max_o_iter = 1; ch.u_hist = d_u; ch.qu_hist = p->qu.p; ch.ff = d_ff; ch.caug = d_caug; ch.cost_all = d_cost;
     launch_cost_history(ch, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(nullptr));
+    CFS_HIPCHK(hipGetLastError());
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
     st.down(cost, d_cost, (size_t)B);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
+    return st.result("copy back");
 }
 
 // ---- developer / test entry points (declared in include/cfs_hip.h; per handle) --------------------------------------------
 int cfs_debug_set_options(cfs_problem *p, int mask, int warm_max, double polish_tol)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
     const int known = CFS_DBG_NO_REFINE | CFS_DBG_NO_WARM_START | CFS_DBG_NO_CERTIFICATE | CFS_DBG_NO_PRUNE | CFS_DBG_NO_AUTO_ORDER |
                       CFS_DBG_TIER_W1 | CFS_DBG_CLEAR_NO_BOUND | CFS_DBG_CLEAR_SEED;
-    if (mask & ~known) return fail(CFS_ERR_INVALID_ARG, "unknown option bits 0x%x", mask & ~known);
-    if (warm_max < 0 || warm_max > 64) return fail(CFS_ERR_INVALID_ARG, "warm_max %d outside 0..64", warm_max);
+    if (mask & ~known) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown option bits 0x%x", mask & ~known);
+    if (warm_max < 0 || warm_max > 64) return cfs_fail(CFS_ERR_INVALID_ARG, "warm_max %d outside 0..64", warm_max);
     p->dbg_mask = mask; p->dbg_warm_max = warm_max;
     p->dbg_polish_tol = polish_tol > 0.0 ? polish_tol : 1e-11;
     return CFS_SUCCESS;
@@ -890,93 +762,93 @@ int cfs_debug_set_options(cfs_problem *p, int mask, int warm_max, double polish_
 
 int cfs_debug_fused_tier(int njoint, int H, int nobs, int mode, int per_waypoint, int limits, int force_w1, int *tier)
 {
-    if (!tier) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
-    if (njoint < 2 || njoint > 6) return fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", njoint);
-    if (H < 1 || H > CFS_MAX_H) return fail(CFS_ERR_INVALID_ARG, "H %d outside 1..%d", H, CFS_MAX_H);
-    if (nobs < 1 || nobs > CFS_MAX_OBS) return fail(CFS_ERR_INVALID_ARG, "nobs %d outside 1..%d", nobs, CFS_MAX_OBS);
-    if (mode != CFS_MODE_CFS && mode != CFS_MODE_PSGCFS) return fail(CFS_ERR_INVALID_ARG, "unknown mode %d", mode);
+    if (!tier) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (njoint < 2 || njoint > 6) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", njoint);
+    if (H < 1 || H > CFS_MAX_H) return cfs_fail(CFS_ERR_INVALID_ARG, "H %d outside 1..%d", H, CFS_MAX_H);
+    if (nobs < 1 || nobs > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d outside 1..%d", nobs, CFS_MAX_OBS);
+    if (mode != CFS_MODE_CFS && mode != CFS_MODE_PSGCFS) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown mode %d", mode);
     if (!fused_fits(njoint, H, nobs))
-        return fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d exceeds the 160 KB on-chip budget of one problem", H, nobs, njoint);
+        return cfs_fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d exceeds the 160 KB on-chip budget of one problem", H, nobs, njoint);
     // the admission rules of cfs_problem_set_obstacle_motion and cfs_problem_set_joint_limits, in either order of the two calls
-    if (per_waypoint && !fused_fits_move(njoint, H, nobs, mode, limits != 0))
-        return fail(CFS_ERR_INVALID_ARG, "per-waypoint obstacles: H=%d x nobs=%d x njoint=%d exceeds the on-chip budget of this shape's tier", H, nobs, njoint);
-    if (limits && !fused_fits_lim(njoint, H, nobs, mode, per_waypoint != 0))
-        return fail(CFS_ERR_INVALID_ARG, "joint limits: H=%d x nobs=%d x njoint=%d exceeds the on-chip budget of this shape's tier", H, nobs, njoint);
+    if (per_waypoint && !fused_keeps_tier(njoint, H, nobs, mode, true, limits != 0))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "per-waypoint obstacles: H=%d x nobs=%d x njoint=%d exceeds the on-chip budget of this shape's tier", H, nobs, njoint);
+    if (limits && !fused_keeps_tier(njoint, H, nobs, mode, per_waypoint != 0, true))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "joint limits: H=%d x nobs=%d x njoint=%d exceeds the on-chip budget of this shape's tier", H, nobs, njoint);
     *tier = (int)fused_tier(njoint, H, nobs, mode, force_w1 != 0);
     return CFS_SUCCESS;
 }
 
 int cfs_debug_stamps(cfs_problem *p, int B, unsigned long long *out)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    HIPCHK(hipSetDevice(p->device));
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    CFS_HIPCHK(hipSetDevice(p->device));
     if (out) {
-        if (!p->stamps.p) return fail(CFS_ERR_INVALID_ARG, "stamps are not enabled");
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(out, p->stamps.p, (size_t)p->stamps_B * 12 * 8, hipMemcpyDeviceToHost));
+        if (!p->stamps.p) return cfs_fail(CFS_ERR_INVALID_ARG, "stamps are not enabled");
+        CFS_HIPCHK(hipDeviceSynchronize());
+        CFS_HIPCHK(hipMemcpy(out, p->stamps.p, (size_t)p->stamps_B * 12 * 8, hipMemcpyDeviceToHost));
         return CFS_SUCCESS;
     }
-    HIPCHK(hipDeviceSynchronize());
+    CFS_HIPCHK(hipDeviceSynchronize());
     p->stamps.release(); p->stamps_B = 0;
     if (B <= 0) return CFS_SUCCESS;
-    if (B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d exceeds max_batch=%d", B, p->d.max_batch);
-    HIPCHK(p->stamps.alloc((size_t)B * 12));
-    HIPCHK(hipMemset(p->stamps.p, 0, (size_t)B * 12 * 8));
+    if (B > p->d.max_batch) return cfs_fail(CFS_ERR_INVALID_ARG, "B=%d exceeds max_batch=%d", B, p->d.max_batch);
+    CFS_HIPCHK(p->stamps.alloc((size_t)B * 12));
+    CFS_HIPCHK(hipMemset(p->stamps.p, 0, (size_t)B * 12 * 8));
     p->stamps_B = B;
     return CFS_SUCCESS;
 }
 
 int cfs_debug_trace_begin(cfs_problem *p, int b, int cap)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    CFS_HIPCHK(hipSetDevice(p->device));
+    CFS_HIPCHK(hipDeviceSynchronize());
     p->trace.release(); p->trace_b = -1; p->trace_cap = 0;
     if (cap <= 0) return CFS_SUCCESS;
-    HIPCHK(p->trace.alloc((size_t)(cap + 1) * 8));
-    HIPCHK(hipMemset(p->trace.p, 0, (size_t)(cap + 1) * 8 * sizeof(double)));
+    CFS_HIPCHK(p->trace.alloc((size_t)(cap + 1) * 8));
+    CFS_HIPCHK(hipMemset(p->trace.p, 0, (size_t)(cap + 1) * 8 * sizeof(double)));
     p->trace_b = b; p->trace_cap = cap;
     return CFS_SUCCESS;
 }
 
 int cfs_debug_trace_read(cfs_problem *p, double *out)
 {
-    if (!p || !out) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
-    if (!p->trace.p) return fail(CFS_ERR_INVALID_ARG, "no trace was begun");
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, p->trace.p, (size_t)(p->trace_cap + 1) * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (!p || !out) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p->trace.p) return cfs_fail(CFS_ERR_INVALID_ARG, "no trace was begun");
+    CFS_HIPCHK(hipSetDevice(p->device));
+    CFS_HIPCHK(hipDeviceSynchronize());
+    CFS_HIPCHK(hipMemcpy(out, p->trace.p, (size_t)(p->trace_cap + 1) * 8 * sizeof(double), hipMemcpyDeviceToHost));
     return CFS_SUCCESS;
 }
 
 int cfs_debug_log_u(cfs_problem *p, int on)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    CFS_HIPCHK(hipSetDevice(p->device));
+    CFS_HIPCHK(hipDeviceSynchronize());
     p->u_log.release();
     if (!on || p->d.MAX_O_ITER < 1) return CFS_SUCCESS;
     const size_t n = (size_t)p->d.max_batch * p->d.MAX_O_ITER * p->nn;
-    HIPCHK(p->u_log.alloc(n));
-    HIPCHK(hipMemset(p->u_log.p, 0, n * sizeof(double)));
+    CFS_HIPCHK(p->u_log.alloc(n));
+    CFS_HIPCHK(hipMemset(p->u_log.p, 0, n * sizeof(double)));
     return CFS_SUCCESS;
 }
 
 int cfs_debug_read_u_log(cfs_problem *p, int B, double *out)
 {
-    if (!p || !out) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
-    if (!p->u_log.p) return fail(CFS_ERR_INVALID_ARG, "the u log is not enabled");
-    if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, p->u_log.p, (size_t)B * p->d.MAX_O_ITER * p->nn * sizeof(double), hipMemcpyDeviceToHost));
+    if (!p || !out) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p->u_log.p) return cfs_fail(CFS_ERR_INVALID_ARG, "the u log is not enabled");
+    if (int rc = cfs_check_batch(p, B)) return rc;
+    CFS_HIPCHK(hipSetDevice(p->device));
+    CFS_HIPCHK(hipDeviceSynchronize());
+    CFS_HIPCHK(hipMemcpy(out, p->u_log.p, (size_t)B * p->d.MAX_O_ITER * p->nn * sizeof(double), hipMemcpyDeviceToHost));
     return CFS_SUCCESS;
 }
 
 int cfs_set_state_cost(cfs_problem *p, const double *Qaug)
 {
-    if (!p || !Qaug) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(p->device));
+    if (!p || !Qaug) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    CFS_HIPCHK(hipSetDevice(p->device));
     const int H = p->d.H, nj = p->d.njoint, ns = 2 * nj, nn = p->nn, nx = p->nx;
     const double dt = p->d.robot.delta_t;
     // E = [Aaug(:,1:nj), -G] (nx x 2nj): state error per unit of x0 / xg;  QE = Qaug*E;  F = Baug'*QE;  Cq = E'*QE
@@ -1009,74 +881,65 @@ int cfs_set_state_cost(cfs_problem *p, const double *Qaug)
         }
     }
     p->F1.release(); p->F2.release(); p->Cq.release();
-    HIPCHK(p->F1.alloc(F1.size())); HIPCHK(p->F2.alloc(F2.size())); HIPCHK(p->Cq.alloc(Cq.size()));
-    HIPCHK(hipMemcpy(p->F1.p, F1.data(), F1.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->F2.p, F2.data(), F2.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->Cq.p, Cq.data(), Cq.size() * 8, hipMemcpyHostToDevice));
+    CFS_HIPCHK(p->F1.alloc(F1.size())); CFS_HIPCHK(p->F2.alloc(F2.size())); CFS_HIPCHK(p->Cq.alloc(Cq.size()));
+    CFS_HIPCHK(hipMemcpy(p->F1.p, F1.data(), F1.size() * 8, hipMemcpyHostToDevice));
+    CFS_HIPCHK(hipMemcpy(p->F2.p, F2.data(), F2.size() * 8, hipMemcpyHostToDevice));
+    CFS_HIPCHK(hipMemcpy(p->Cq.p, Cq.data(), Cq.size() * 8, hipMemcpyHostToDevice));
+    return CFS_SUCCESS;
+}
+
+// x0 / xg (route == NULL), or routes of nwp rows (nwp_b == NULL), or ragged routes (nwp_b[b] of nwp_stride rows each)
+static int build_terms(cfs_problem *p, int B, const double *x0, const double *xg, const double *route, int nwp, const int *nwp_b, int nwp_stride,
+                       double *x_init, double *xR1, double *ff, double *caug, void *stream)
+{
+    if (!p->F1.p) return cfs_fail(CFS_ERR_INVALID_ARG, "call cfs_set_state_cost first");
+    CFS_HIPCHK(hipSetDevice(p->device));
+    TermsParams t;
+    t.B = B; t.H = p->d.H; t.nj = p->d.njoint; t.F1 = p->F1.p; t.F2 = p->F2.p; t.Cq = p->Cq.p;
+    t.x0 = x0; t.xg = xg; t.route = route; t.nwp = nwp; t.nwp_b = nwp_b; t.nwp_stride = nwp_stride; t.dt = p->d.robot.delta_t;
+    t.x_init = x_init; t.xR1 = xR1; t.ff = ff; t.caug = caug;
+    launch_build_terms(t, reinterpret_cast<hipStream_t>(stream));
+    CFS_HIPCHK(hipGetLastError());
     return CFS_SUCCESS;
 }
 
 int cfs_build_terms_device(cfs_problem *p, int B, const double *x0, const double *xg,
                            double *x_init, double *xR1, double *ff, double *caug, void *stream)
 {
-    if (!p || !x0 || !xg || !x_init || !xR1 || !ff || !caug) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
-    if (B < 1) return fail(CFS_ERR_INVALID_ARG, "B must be >= 1");
-    if (!p->F1.p) return fail(CFS_ERR_INVALID_ARG, "call cfs_set_state_cost first");
-    HIPCHK(hipSetDevice(p->device));
-    TermsParams t;
-    t.B = B; t.H = p->d.H; t.nj = p->d.njoint; t.F1 = p->F1.p; t.F2 = p->F2.p; t.Cq = p->Cq.p;
-    t.x0 = x0; t.xg = xg; t.route = nullptr; t.nwp = 0; t.nwp_b = nullptr; t.nwp_stride = 0; t.dt = p->d.robot.delta_t;
-    t.x_init = x_init; t.xR1 = xR1; t.ff = ff; t.caug = caug;
-    launch_build_terms(t, reinterpret_cast<hipStream_t>(stream));
-    HIPCHK(hipGetLastError());
-    return CFS_SUCCESS;
+    if (!p || !x0 || !xg || !x_init || !xR1 || !ff || !caug) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (B < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "B must be >= 1");
+    return build_terms(p, B, x0, xg, nullptr, 0, nullptr, 0, x_init, xR1, ff, caug, stream);
 }
 
 int cfs_build_terms_from_routes_device(cfs_problem *p, int B, const double *routes, int nwp,
                                        double *x_init, double *xR1, double *ff, double *caug, void *stream)
 {
-    if (!p || !routes || !x_init || !xR1 || !ff || !caug) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
-    if (B < 1 || nwp < 2) return fail(CFS_ERR_INVALID_ARG, "B >= 1 and at least two route waypoints are needed");
-    if (!p->F1.p) return fail(CFS_ERR_INVALID_ARG, "call cfs_set_state_cost first");
-    HIPCHK(hipSetDevice(p->device));
-    TermsParams t;
-    t.B = B; t.H = p->d.H; t.nj = p->d.njoint; t.F1 = p->F1.p; t.F2 = p->F2.p; t.Cq = p->Cq.p;
-    t.x0 = nullptr; t.xg = nullptr; t.route = routes; t.nwp = nwp; t.nwp_b = nullptr; t.nwp_stride = 0; t.dt = p->d.robot.delta_t;
-    t.x_init = x_init; t.xR1 = xR1; t.ff = ff; t.caug = caug;
-    launch_build_terms(t, reinterpret_cast<hipStream_t>(stream));
-    HIPCHK(hipGetLastError());
-    return CFS_SUCCESS;
+    if (!p || !routes || !x_init || !xR1 || !ff || !caug) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (B < 1 || nwp < 2) return cfs_fail(CFS_ERR_INVALID_ARG, "B >= 1 and at least two route waypoints are needed");
+    return build_terms(p, B, nullptr, nullptr, routes, nwp, nullptr, 0, x_init, xR1, ff, caug, stream);
 }
 
 int cfs_build_terms_from_ragged_routes_device(cfs_problem *p, int B, const double *routes, int nwp_stride, const int *nwp,
                                               double *x_init, double *xR1, double *ff, double *caug, void *stream)
 {
-    if (!p || !routes || !nwp || !x_init || !xR1 || !ff || !caug) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
-    if (B < 1 || nwp_stride < 1) return fail(CFS_ERR_INVALID_ARG, "B >= 1 and nwp_stride >= 1 are needed");
-    if (!p->F1.p) return fail(CFS_ERR_INVALID_ARG, "call cfs_set_state_cost first");
-    HIPCHK(hipSetDevice(p->device));
-    TermsParams t;
-    t.B = B; t.H = p->d.H; t.nj = p->d.njoint; t.F1 = p->F1.p; t.F2 = p->F2.p; t.Cq = p->Cq.p;
-    t.x0 = nullptr; t.xg = nullptr; t.route = routes; t.nwp = nwp_stride; t.nwp_b = nwp; t.nwp_stride = nwp_stride; t.dt = p->d.robot.delta_t;
-    t.x_init = x_init; t.xR1 = xR1; t.ff = ff; t.caug = caug;
-    launch_build_terms(t, reinterpret_cast<hipStream_t>(stream));
-    HIPCHK(hipGetLastError());
-    return CFS_SUCCESS;
+    if (!p || !routes || !nwp || !x_init || !xR1 || !ff || !caug) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (B < 1 || nwp_stride < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "B >= 1 and nwp_stride >= 1 are needed");
+    return build_terms(p, B, nullptr, nullptr, routes, nwp_stride, nwp, nwp_stride, x_init, xR1, ff, caug, stream);
 }
 
 int cfs_chomp_batch(cfs_problem *p, const cfs_batch_in *in, const double *u0, const double *D, const double *epsilon,
                     const cfs_batch_out *out)
 {
-    if (!p || !in || !out || !u0 || !D || !epsilon) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p || !in || !out || !u0 || !D || !epsilon) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     const int B = in->B;
-    if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
-    if (!in->x_init || !in->xR1 || !in->ff || !in->caug || !in->obs) return fail(CFS_ERR_INVALID_ARG, "NULL input array");
-    if (!out->u || !out->x_ || !out->cost_all || !out->e_cost_all || !out->e_u_all || !out->iter_O) return fail(CFS_ERR_INVALID_ARG, "NULL output array");
-    if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC measures line obstacles only (Lib/CHOMP_FANUC.m:119)");
-    if (moving(p)) return fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC takes static obstacles only (the handle is CFS_OBS_PER_WAYPOINT)");
-    if (limited(p)) return fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC has no QP to hold joint limits (the handle has them: clear them first)");
-    if (!chomp_fits(p->d.njoint, p->d.H, p->d.nobs)) return fail(CFS_ERR_INVALID_ARG, "H x nobs too large for the CHOMP kernel's 64 KB of LDS");
-    HIPCHK(hipSetDevice(p->device));
+    if (int rc = cfs_check_batch(p, B)) return rc;
+    if (!in->x_init || !in->xR1 || !in->ff || !in->caug || !in->obs) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL input array");
+    if (!out->u || !out->x_ || !out->cost_all || !out->e_cost_all || !out->e_u_all || !out->iter_O) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL output array");
+    if (p->nmesh > 0) return cfs_fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC measures line obstacles only (Lib/CHOMP_FANUC.m:119)");
+    if (cfs_moving(p)) return cfs_fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC takes static obstacles only (the handle is CFS_OBS_PER_WAYPOINT)");
+    if (limited(p)) return cfs_fail(CFS_ERR_INVALID_ARG, "CHOMP_FANUC has no QP to hold joint limits (the handle has them: clear them first)");
+    if (!chomp_fits(p->d.njoint, p->d.H, p->d.nobs)) return cfs_fail(CFS_ERR_INVALID_ARG, "H x nobs too large for the CHOMP kernel's 64 KB of LDS");
+    CFS_HIPCHK(hipSetDevice(p->device));
     const size_t nn = p->nn, nx = p->nx, ns = p->ns, K = p->d.MAX_O_ITER, nobs = p->d.nobs;
     Stage st;
     ChompParams c;
@@ -1085,35 +948,32 @@ int cfs_chomp_batch(cfs_problem *p, const cfs_batch_in *in, const double *u0, co
     c.dt = p->d.robot.delta_t; c.alpha = p->d.alpha; c.epsilon_O = p->d.epsilon_O; c.QQ = p->QQ.p;
     c.x_init = st.up(in->x_init, B * nx); c.xR1 = st.up(in->xR1, B * ns); c.ff = st.up(in->ff, B * nn); c.caug = st.up(in->caug, B);
     c.obs = st.up(in->obs, B * nobs * 6); c.u0 = st.up(u0, B * nn); c.D = st.up(D, nobs); c.eps = st.up(epsilon, nobs);
-    c.u = st.up<double>(nullptr, B * nn); c.x_ = st.up<double>(nullptr, B * nx);
-    c.cost_all = st.up<double>(nullptr, B * std::max<size_t>(K, 1)); c.e_cost_all = st.up<double>(nullptr, B * std::max<size_t>(K, 1));
-    c.e_u_all = st.up<double>(nullptr, B * std::max<size_t>(K, 1));
-    c.iter_O = st.up<int>(nullptr, B); c.total_iter = st.up<int>(nullptr, B); c.status = st.up<int>(nullptr, B);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
-    HIPCHK(hipMemset(c.cost_all, 0, B * std::max<size_t>(K, 1) * 8)); HIPCHK(hipMemset(c.e_cost_all, 0, B * std::max<size_t>(K, 1) * 8));
-    HIPCHK(hipMemset(c.e_u_all, 0, B * std::max<size_t>(K, 1) * 8));
+    c.u = st.out<double>(B * nn); c.x_ = st.out<double>(B * nx);
+    const size_t nlog = B * std::max<size_t>(K, 1);
+    c.cost_all = st.zeros<double>(nlog); c.e_cost_all = st.zeros<double>(nlog); c.e_u_all = st.zeros<double>(nlog);
+    c.iter_O = st.out<int>(B); c.total_iter = st.out<int>(B); c.status = st.out<int>(B);
+    if (st.err != hipSuccess) return st.result("staging");
     chomp_derivest_tables(c);
-    HIPCHK(launch_chomp(p->d.njoint, c, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
+    CFS_HIPCHK(launch_chomp(p->d.njoint, c, nullptr));
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
     st.down(out->u, c.u, B * nn); st.down(out->x_, c.x_, B * nx);
     st.down(out->cost_all, c.cost_all, B * K); st.down(out->e_cost_all, c.e_cost_all, B * K); st.down(out->e_u_all, c.e_u_all, B * K);
     st.down(out->iter_O, c.iter_O, B); st.down(out->total_iter, c.total_iter, B); st.down(out->status, c.status, B);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
+    return st.result("copy back");
 }
 
 int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *meshes)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    if (nmesh < 0 || nmesh > p->d.nobs) return fail(CFS_ERR_INVALID_ARG, "nmesh %d outside 0..nobs=%d", nmesh, p->d.nobs);
-    if (nmesh > 0 && !meshes) return fail(CFS_ERR_INVALID_ARG, "meshes is NULL");
-    if (nmesh > 0 && p->infeas == CFS_INFEAS_SOFTEN) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are not supported with CFS_INFEAS_SOFTEN");
-    if (nmesh > 0 && moving(p)) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are static: not supported on a CFS_OBS_PER_WAYPOINT handle");
-    HIPCHK(hipSetDevice(p->device));
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (nmesh < 0 || nmesh > p->d.nobs) return cfs_fail(CFS_ERR_INVALID_ARG, "nmesh %d outside 0..nobs=%d", nmesh, p->d.nobs);
+    if (nmesh > 0 && !meshes) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes is NULL");
+    if (nmesh > 0 && p->infeas == CFS_INFEAS_SOFTEN) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh obstacles are not supported with CFS_INFEAS_SOFTEN");
+    if (nmesh > 0 && cfs_moving(p)) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh obstacles are static: not supported on a CFS_OBS_PER_WAYPOINT handle");
+    CFS_HIPCHK(hipSetDevice(p->device));
     std::vector<DevMesh> v(nmesh);
     for (int i = 0; i < nmesh; ++i) {
-        if (!meshes[i]) return fail(CFS_ERR_INVALID_ARG, "meshes[%d] is NULL", i);
-        if (meshes[i]->device != p->device) return fail(CFS_ERR_INVALID_ARG, "meshes[%d] lives on device %d, the problem on %d", i, meshes[i]->device, p->device);
+        if (!meshes[i]) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes[%d] is NULL", i);
+        if (meshes[i]->device != p->device) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes[%d] lives on device %d, the problem on %d", i, meshes[i]->device, p->device);
         v[i] = meshes[i]->view();
     }
     p->meshes_d.release(); p->st_cost.release(); p->st_done.release();
@@ -1124,12 +984,12 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
         size_t we, wb, ws, wn, wpd, wpi, wpn;
         linearize_mesh_workspace(p->d.njoint, nmesh, &we, &wb, &ws, &wn, &wpd, &wpi, &wpn);
         const size_t bh = (size_t)p->d.max_batch * p->d.H;
-        HIPCHK(p->m_ends.alloc(bh * we)); HIPCHK(p->m_base.alloc(bh * wb)); HIPCHK(p->m_upper.alloc(bh * wb)); HIPCHK(p->m_tri.alloc(bh * wb)); HIPCHK(p->m_shift.alloc(bh * ws)); HIPCHK(p->m_near.alloc(bh * wn));
-        HIPCHK(p->m_pd.alloc(bh * wpd)); HIPCHK(p->m_pi.alloc(bh * wpi)); HIPCHK(p->m_pnd.alloc(bh * wpn));
-        HIPCHK(p->meshes_d.alloc(nmesh));
-        HIPCHK(p->st_cost.alloc(2 * (size_t)p->d.max_batch));
-        HIPCHK(p->st_done.alloc(p->d.max_batch));
-        HIPCHK(hipMemcpy(p->meshes_d.p, v.data(), sizeof(DevMesh) * nmesh, hipMemcpyHostToDevice));
+        CFS_HIPCHK(p->m_ends.alloc(bh * we)); CFS_HIPCHK(p->m_base.alloc(bh * wb)); CFS_HIPCHK(p->m_upper.alloc(bh * wb)); CFS_HIPCHK(p->m_tri.alloc(bh * wb)); CFS_HIPCHK(p->m_shift.alloc(bh * ws)); CFS_HIPCHK(p->m_near.alloc(bh * wn));
+        CFS_HIPCHK(p->m_pd.alloc(bh * wpd)); CFS_HIPCHK(p->m_pi.alloc(bh * wpi)); CFS_HIPCHK(p->m_pnd.alloc(bh * wpn));
+        CFS_HIPCHK(p->meshes_d.alloc(nmesh));
+        CFS_HIPCHK(p->st_cost.alloc(2 * (size_t)p->d.max_batch));
+        CFS_HIPCHK(p->st_done.alloc(p->d.max_batch));
+        CFS_HIPCHK(hipMemcpy(p->meshes_d.p, v.data(), sizeof(DevMesh) * nmesh, hipMemcpyHostToDevice));
         p->nmesh = nmesh;
     }
     return CFS_SUCCESS;
@@ -1137,23 +997,23 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
 
 int cfs_profile_enable(cfs_problem *p, int on)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
     p->prof = on != 0;
     return CFS_SUCCESS;
 }
 
 int cfs_profile_read(cfs_problem *p, double *solve_kernel_ms, double *gemm_kernel_ms, int *solves)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    HIPCHK(hipSetDevice(p->device));
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    CFS_HIPCHK(hipSetDevice(p->device));
     double fused = 0.0, gemm = 0.0;
     const int n = (int)(p->ev.size() / 4);
     for (int k = 0; k < n; ++k) {
         float ms = 0.f;
-        HIPCHK(hipEventSynchronize(p->ev[4 * k + 3]));
-        HIPCHK(hipEventElapsedTime(&ms, p->ev[4 * k + 0], p->ev[4 * k + 1]));
+        CFS_HIPCHK(hipEventSynchronize(p->ev[4 * k + 3]));
+        CFS_HIPCHK(hipEventElapsedTime(&ms, p->ev[4 * k + 0], p->ev[4 * k + 1]));
         gemm += ms;
-        HIPCHK(hipEventElapsedTime(&ms, p->ev[4 * k + 2], p->ev[4 * k + 3]));
+        CFS_HIPCHK(hipEventElapsedTime(&ms, p->ev[4 * k + 2], p->ev[4 * k + 3]));
         fused += ms;
     }
     for (hipEvent_t e : p->ev) p->ev_free.push_back(e);
@@ -1164,99 +1024,35 @@ int cfs_profile_read(cfs_problem *p, double *solve_kernel_ms, double *gemm_kerne
     return CFS_SUCCESS;
 }
 
-int cfs_dist_arm(const cfs_robot *robot, int njoint, int N, const double *theta, int nobs, const double *obs,
-                 double *d, int *linkid, double *pos)
-{
-    int rc = check_robot(robot, njoint);
-    if (rc) return rc;
-    if (N < 0 || nobs < 0 || !theta || !obs || !d) return fail(CFS_ERR_INVALID_ARG, "bad argument");
-    if (N == 0 || nobs == 0) return CFS_SUCCESS;
-    if (have_device() == 0) return fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    HIPCHK(hipSetDevice(g_device));
-    DevRobot hr;
-    build_dev_robot(*robot, hr);
-    Stage st;
-    DistArmParams P;
-    P.rb = st.up(&hr, 1);
-    P.N = N; P.nobs = nobs; P.nj = njoint;
-    P.theta = st.up(theta, (size_t)N * njoint);
-    P.obs = st.up(obs, (size_t)nobs * 6);
-    P.d = st.up<double>(nullptr, (size_t)N * nobs);
-    P.linkid = st.up<int>(nullptr, (size_t)N * nobs);
-    P.pos = pos ? st.up<double>(nullptr, (size_t)N * njoint * 6) : nullptr;
-    P.grad = nullptr;
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
-    launch_dist_arm(P, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(nullptr));
-    st.down(d, P.d, (size_t)N * nobs);
-    st.down(linkid, P.linkid, (size_t)N * nobs);
-    if (pos) st.down(pos, P.pos, (size_t)N * njoint * 6);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
-}
-
-int cfs_dist_arm_grad(const cfs_robot *robot, int njoint, int N, const double *theta, int nobs, const double *obs,
-                      double *d, int *linkid, double *grad)
-{
-    int rc = check_robot(robot, njoint);
-    if (rc) return rc;
-    if (N < 0 || nobs < 0 || !theta || !obs || !d || !linkid || !grad) return fail(CFS_ERR_INVALID_ARG, "bad argument");
-    if (N == 0 || nobs == 0) return CFS_SUCCESS;
-    if (have_device() == 0) return fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    HIPCHK(hipSetDevice(g_device));
-    DevRobot hr;
-    build_dev_robot(*robot, hr);
-    Stage st;
-    DistArmParams P;
-    P.rb = st.up(&hr, 1);
-    P.N = N; P.nobs = nobs; P.nj = njoint;
-    P.theta = st.up(theta, (size_t)N * njoint);
-    P.obs = st.up(obs, (size_t)nobs * 6);
-    P.d = st.up<double>(nullptr, (size_t)N * nobs);
-    P.linkid = st.up<int>(nullptr, (size_t)N * nobs);
-    P.pos = nullptr;
-    P.grad = st.up<double>(nullptr, (size_t)N * nobs * njoint);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
-    launch_dist_arm_grad(P, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(nullptr));
-    st.down(d, P.d, (size_t)N * nobs);
-    st.down(linkid, P.linkid, (size_t)N * nobs);
-    st.down(grad, P.grad, (size_t)N * nobs * njoint);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
-}
-
 int cfs_problem_set_jacobian(cfs_problem *p, int mode)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    if (mode != CFS_JAC_FD_LITERAL && mode != CFS_JAC_ANALYTIC) return fail(CFS_ERR_INVALID_ARG, "unknown jacobian mode %d", mode);
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (mode != CFS_JAC_FD_LITERAL && mode != CFS_JAC_ANALYTIC) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown jacobian mode %d", mode);
     p->jac = mode;
     return CFS_SUCCESS;
 }
 
 int cfs_problem_get_jacobian(const cfs_problem *p, int *mode)
 {
-    if (!p || !mode) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p || !mode) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     *mode = p->jac;
     return CFS_SUCCESS;
 }
 
 int cfs_problem_set_infeasible_policy(cfs_problem *p, int policy, double weight)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    if (policy != CFS_INFEAS_STOP && policy != CFS_INFEAS_SOFTEN) return fail(CFS_ERR_INVALID_ARG, "unknown infeasible-QP policy %d", policy);
-    if (!std::isfinite(weight) || !(weight > 0.0)) return fail(CFS_ERR_INVALID_ARG, "soft weight %g is not finite and > 0", weight);
-    if (policy == CFS_INFEAS_SOFTEN && p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are not supported with CFS_INFEAS_SOFTEN");
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (policy != CFS_INFEAS_STOP && policy != CFS_INFEAS_SOFTEN) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown infeasible-QP policy %d", policy);
+    if (!std::isfinite(weight) || !(weight > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "soft weight %g is not finite and > 0", weight);
+    if (policy == CFS_INFEAS_SOFTEN && p->nmesh > 0) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh obstacles are not supported with CFS_INFEAS_SOFTEN");
     if (policy == CFS_INFEAS_SOFTEN && !p->soft_viol.p) {   // handle-owned result buffers, from the first SOFTEN on
-        HIPCHK(hipSetDevice(p->device));
+        CFS_HIPCHK(hipSetDevice(p->device));
         const size_t nv = (size_t)p->d.max_batch * std::max(p->d.MAX_O_ITER, 1);
         hipError_t e = p->soft_viol.alloc(nv);
         if (e == hipSuccess) e = p->soft_n.alloc(p->d.max_batch);
         if (e == hipSuccess) e = hipMemset(p->soft_viol.p, 0, nv * sizeof(double));
         if (e == hipSuccess) e = hipMemset(p->soft_n.p, 0, (size_t)p->d.max_batch * sizeof(int));
-        if (e != hipSuccess) { p->soft_viol.release(); p->soft_n.release(); return fail(CFS_ERR_HIP, "soft result buffers: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) { p->soft_viol.release(); p->soft_n.release(); return cfs_fail(CFS_ERR_HIP, "soft result buffers: %s", hipGetErrorString(e)); }
     }
     p->soft_weight = weight;
     p->infeas = policy;
@@ -1265,12 +1061,12 @@ int cfs_problem_set_infeasible_policy(cfs_problem *p, int policy, double weight)
 
 int cfs_problem_set_obstacle_motion(cfs_problem *p, int motion)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    if (motion != CFS_OBS_STATIC && motion != CFS_OBS_PER_WAYPOINT) return fail(CFS_ERR_INVALID_ARG, "unknown obstacle motion %d", motion);
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (motion != CFS_OBS_STATIC && motion != CFS_OBS_PER_WAYPOINT) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown obstacle motion %d", motion);
     if (motion == CFS_OBS_PER_WAYPOINT) {
-        if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "mesh obstacles are static: CFS_OBS_PER_WAYPOINT needs a handle without meshes");
-        if (!fused_fits_move(p->d.njoint, p->d.H, p->d.nobs, p->d.mode, limited(p)))
-            return fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d: the per-waypoint obstacle rows of a linearisation tile do not fit the "
+        if (p->nmesh > 0) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh obstacles are static: CFS_OBS_PER_WAYPOINT needs a handle without meshes");
+        if (!fused_keeps_tier(p->d.njoint, p->d.H, p->d.nobs, p->d.mode, true, limited(p)))
+            return cfs_fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d: the per-waypoint obstacle rows of a linearisation tile do not fit the "
                         "on-chip budget of the static plan's tier", p->d.H, p->d.nobs, p->d.njoint);
     }
     p->motion = motion;
@@ -1279,22 +1075,22 @@ int cfs_problem_set_obstacle_motion(cfs_problem *p, int motion)
 
 int cfs_problem_set_joint_limits(cfs_problem *p, const double *lo, const double *hi)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
     if (!lo && !hi) { p->limited = false; p->jlim.clear(); return CFS_SUCCESS; }
-    if (!lo || !hi) return fail(CFS_ERR_INVALID_ARG, "lo and hi are both given or both NULL");
+    if (!lo || !hi) return cfs_fail(CFS_ERR_INVALID_ARG, "lo and hi are both given or both NULL");
     const int nj = p->d.njoint;
     for (int c = 0; c < nj; ++c) {
-        if (std::isnan(lo[c]) || std::isnan(hi[c])) return fail(CFS_ERR_INVALID_ARG, "joint %d: NaN limit", c);
-        if (!(lo[c] < hi[c])) return fail(CFS_ERR_INVALID_ARG, "joint %d: lo %g >= hi %g", c, lo[c], hi[c]);
+        if (std::isnan(lo[c]) || std::isnan(hi[c])) return cfs_fail(CFS_ERR_INVALID_ARG, "joint %d: NaN limit", c);
+        if (!(lo[c] < hi[c])) return cfs_fail(CFS_ERR_INVALID_ARG, "joint %d: lo %g >= hi %g", c, lo[c], hi[c]);
     }
-    if (!fused_fits_lim(nj, p->d.H, p->d.nobs, p->d.mode, moving(p)))
-        return fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d: the LDS plan with joint limits does not fit every tier of the fused solver "
+    if (!fused_keeps_tier(nj, p->d.H, p->d.nobs, p->d.mode, cfs_moving(p), true))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "H=%d x nobs=%d x njoint=%d: the LDS plan with joint limits does not fit every tier of the fused solver "
                     "that the plan without them fits", p->d.H, p->d.nobs, nj);
     std::vector<double> v(lo, lo + nj);
     v.insert(v.end(), hi, hi + nj);
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());      // a solve in flight may still be reading the previous limits
-    HIPCHK(hipMemcpy(p->lim.p + nj, v.data(), 2 * (size_t)nj * sizeof(double), hipMemcpyHostToDevice));
+    CFS_HIPCHK(hipSetDevice(p->device));
+    CFS_HIPCHK(hipDeviceSynchronize());      // a solve in flight may still be reading the previous limits
+    CFS_HIPCHK(hipMemcpy(p->lim.p + nj, v.data(), 2 * (size_t)nj * sizeof(double), hipMemcpyHostToDevice));
     p->jlim = v;
     p->limited = true;
     return CFS_SUCCESS;
@@ -1302,7 +1098,7 @@ int cfs_problem_set_joint_limits(cfs_problem *p, const double *lo, const double 
 
 int cfs_problem_get_joint_limits(const cfs_problem *p, int *on, double *lo, double *hi)
 {
-    if (!p || !on) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p || !on) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     const int nj = p->d.njoint;
     *on = p->limited ? 1 : 0;
     for (int c = 0; c < nj; ++c) {
@@ -1314,14 +1110,14 @@ int cfs_problem_get_joint_limits(const cfs_problem *p, int *on, double *lo, doub
 
 int cfs_problem_get_obstacle_motion(const cfs_problem *p, int *motion)
 {
-    if (!p || !motion) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p || !motion) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     *motion = p->motion;
     return CFS_SUCCESS;
 }
 
 int cfs_problem_get_infeasible_policy(const cfs_problem *p, int *policy, double *weight)
 {
-    if (!p || !policy || !weight) return fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (!p || !policy || !weight) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     *policy = p->infeas;
     *weight = p->soft_weight;
     return CFS_SUCCESS;
@@ -1329,25 +1125,18 @@ int cfs_problem_get_infeasible_policy(const cfs_problem *p, int *policy, double 
 
 int cfs_soft_results(cfs_problem *p, int B, double *viol_all, int *n_soft)
 {
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (int rc = cfs_check_batch(p, B)) return rc;
     const size_t nv = (size_t)B * p->d.MAX_O_ITER;
     if (!p->soft_viol.p) {               // never softened: nothing was
         if (viol_all) memset(viol_all, 0, nv * sizeof(double));
         if (n_soft) memset(n_soft, 0, (size_t)B * sizeof(int));
         return CFS_SUCCESS;
     }
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipDeviceSynchronize());      // the last solve may have been enqueued on any stream
-    if (viol_all && nv) HIPCHK(hipMemcpy(viol_all, p->soft_viol.p, nv * sizeof(double), hipMemcpyDeviceToHost));
-    if (n_soft) HIPCHK(hipMemcpy(n_soft, p->soft_n.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
-    return CFS_SUCCESS;
-}
-
-static int check_batch(const cfs_problem *p, int B)
-{
-    if (!p) return fail(CFS_ERR_INVALID_ARG, "NULL handle");
-    if (B < 1 || B > p->d.max_batch) return fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
+    CFS_HIPCHK(hipSetDevice(p->device));
+    CFS_HIPCHK(hipDeviceSynchronize());      // the last solve may have been enqueued on any stream
+    if (viol_all && nv) CFS_HIPCHK(hipMemcpy(viol_all, p->soft_viol.p, nv * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_soft) CFS_HIPCHK(hipMemcpy(n_soft, p->soft_n.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
     return CFS_SUCCESS;
 }
 
@@ -1360,19 +1149,13 @@ struct PieceBuffers {
 };
 static int stage_piece(cfs_problem *p, Stage &st, int B, const double *x_, const double *xR1, const double *obs, PieceBuffers &pb)
 {
-    const size_t nobs = obs_rows(p);
-    pb.x_ = st.up(x_, (size_t)B * p->nx);
-    pb.xR1 = st.up(xR1, (size_t)B * p->ns);
-    pb.ff = st.up<double>(nullptr, (size_t)B * p->nn);
-    pb.caug = st.up<double>(nullptr, (size_t)B);
-    pb.obs = st.up(obs, (size_t)B * nobs * 6);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
-    if (!x_) HIPCHK(hipMemset(pb.x_, 0, (size_t)B * p->nx * 8));
-    if (!xR1) HIPCHK(hipMemset(pb.xR1, 0, (size_t)B * p->ns * 8));
-    if (!obs) HIPCHK(hipMemset(pb.obs, 0, (size_t)B * nobs * 6 * 8));
-    HIPCHK(hipMemset(pb.ff, 0, (size_t)B * p->nn * 8));
-    HIPCHK(hipMemset(pb.caug, 0, (size_t)B * 8));
-    return CFS_SUCCESS;
+    auto in = [&](const double *h, size_t n) { return h ? st.up(h, n) : st.zeros<double>(n); };
+    pb.x_ = in(x_, (size_t)B * p->nx);
+    pb.xR1 = in(xR1, (size_t)B * p->ns);
+    pb.ff = st.zeros<double>((size_t)B * p->nn);
+    pb.caug = st.zeros<double>((size_t)B);
+    pb.obs = in(obs, (size_t)B * cfs_obs_rows(p) * 6);
+    return st.result("staging");
 }
 
 // linearisation of B trajectories into p->dist / p->grad (B x nobs x H [x nj]) and, optionally, linkid
@@ -1384,52 +1167,48 @@ static int linearize_piece(cfs_problem *p, int B, const PieceBuffers &pb, double
     fp.x_init = pb.x_; fp.xR1 = pb.xR1; fp.ff = pb.ff; fp.caug = pb.caug; fp.obs = pb.obs;
     fp.piece = 1;
     fp.dump_dist = d_dist; fp.dump_grad = d_grad; fp.dump_linkid = d_linkid;
-    if (d_linkid) HIPCHK(hipMemsetAsync(d_linkid, 0, (size_t)B * p->d.nobs * p->d.H * sizeof(int), nullptr));
+    if (d_linkid) CFS_HIPCHK(hipMemsetAsync(d_linkid, 0, (size_t)B * p->d.nobs * p->d.H * sizeof(int), nullptr));
     if (p->nmesh > 0) {          // rows of the mesh obstacles come from the hierarchy kernels, as in the whole solve
-        LinMeshParams lm;
-        lm.rb = p->rb.p; lm.B = B; lm.H = p->d.H; lm.nmesh = p->nmesh; lm.meshes = p->meshes_d.p;
-        lm.dist = p->dist.p; lm.grad = p->grad.p;
-        lm.ends = p->m_ends.p; lm.base_d = p->m_base.p; lm.upper_d = p->m_upper.p; lm.base_t = p->m_tri.p; lm.shift_d = p->m_shift.p; lm.near = p->m_near.p; lm.piece_d = p->m_pd.p; lm.piece_i = p->m_pi.p; lm.piece_nd = p->m_pnd.p;
+        LinMeshParams lm = lin_mesh_params(p, B);
         lm.x_ = pb.x_; lm.status_done = nullptr; lm.seed_prev = 0;
-        HIPCHK(launch_linearize_mesh(nj, lm, nullptr));
+        CFS_HIPCHK(launch_linearize_mesh(nj, lm, nullptr));
         fp.nmesh = p->nmesh; fp.ext_dist = p->dist.p; fp.ext_grad = p->grad.p;
     }
     SoftParams sp;
-    HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false), moving(p), limited(p)));
+    CFS_HIPCHK(launch_fused(nj, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false), cfs_moving(p), limited(p)));
     return CFS_SUCCESS;
 }
 
 int cfs_linearize(cfs_problem *p, int B, const double *x_, const double *obs, double *dist, int *linkid, double *grad)
 {
-    int rc = check_batch(p, B);
+    int rc = cfs_check_batch(p, B);
     if (rc) return rc;
-    if (!x_ || !obs || !dist || !grad) return fail(CFS_ERR_INVALID_ARG, "NULL array");
-    HIPCHK(hipSetDevice(p->device));
+    if (!x_ || !obs || !dist || !grad) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL array");
+    CFS_HIPCHK(hipSetDevice(p->device));
     const size_t nobs = p->d.nobs, H = p->d.H, nj = p->d.njoint;
     Stage st;
     PieceBuffers pb;
     rc = stage_piece(p, st, B, x_, nullptr, obs, pb);
     if (rc) return rc;
-    double *d_dist = st.up<double>(nullptr, (size_t)B * nobs * H);
-    double *d_grad = st.up<double>(nullptr, (size_t)B * nobs * H * nj);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
+    double *d_dist = st.out<double>((size_t)B * nobs * H);
+    double *d_grad = st.out<double>((size_t)B * nobs * H * nj);
+    if (st.err != hipSuccess) return st.result("staging");
     rc = linearize_piece(p, B, pb, d_dist, d_grad, p->linkid.p);
     if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
     st.down(dist, d_dist, (size_t)B * nobs * H);
     st.down(linkid, p->linkid.p, (size_t)B * nobs * H);
     st.down(grad, d_grad, (size_t)B * nobs * H * nj);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
+    return st.result("copy back");
 }
 
 int cfs_get_con(cfs_problem *p, int B, const double *x_, const double *u, const double *xR1, const double *obs,
                 double *Ainq, double *binq)
 {
-    int rc = check_batch(p, B);
+    int rc = cfs_check_batch(p, B);
     if (rc) return rc;
-    if (!x_ || !u || !xR1 || !obs || !Ainq || !binq) return fail(CFS_ERR_INVALID_ARG, "NULL array");
-    HIPCHK(hipSetDevice(p->device));
+    if (!x_ || !u || !xR1 || !obs || !Ainq || !binq) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL array");
+    CFS_HIPCHK(hipSetDevice(p->device));
     const size_t nobs = p->d.nobs, H = p->d.H, nj = p->d.njoint, nn = p->nn;
     const size_t rows = nobs * H * (1 + 2 * nj) + (limited(p) ? 2 * nn : 0);   // limited: + pos+ (i, c), pos- (i, c)
     Stage st;
@@ -1438,34 +1217,33 @@ int cfs_get_con(cfs_problem *p, int B, const double *x_, const double *u, const 
     if (rc) return rc;
     DenseConParams dc;
     dc.B = B; dc.H = p->d.H; dc.nj = p->d.njoint; dc.nobs = p->d.nobs; dc.dt = p->d.robot.delta_t;
-    double *d_dist = st.up<double>(nullptr, (size_t)B * nobs * H);
-    double *d_grad = st.up<double>(nullptr, (size_t)B * nobs * H * nj);
+    double *d_dist = st.out<double>((size_t)B * nobs * H);
+    double *d_grad = st.out<double>((size_t)B * nobs * H * nj);
     dc.dist = d_dist; dc.grad = d_grad;
     dc.u = st.up(u, (size_t)B * nn);
     dc.xR1 = pb.xR1;
     dc.lim = p->lim.p; dc.margin = p->margin.p;
     dc.plim = limited(p) ? p->lim.p + nj : nullptr;
-    dc.Ainq = st.up<double>(nullptr, (size_t)B * rows * nn);
-    dc.binq = st.up<double>(nullptr, (size_t)B * rows);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
+    dc.Ainq = st.out<double>((size_t)B * rows * nn);
+    dc.binq = st.out<double>((size_t)B * rows);
+    if (st.err != hipSuccess) return st.result("staging");
     rc = linearize_piece(p, B, pb, d_dist, d_grad, nullptr);
     if (rc) return rc;
     launch_dense_con(dc, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(nullptr));
+    CFS_HIPCHK(hipGetLastError());
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
     st.down(Ainq, dc.Ainq, (size_t)B * rows * nn);
     st.down(binq, dc.binq, (size_t)B * rows);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
+    return st.result("copy back");
 }
 
 int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const double *xR1,
            const double *dist, const double *grad, double *u, double *lambda, int *qp_iter, int *status)
 {
-    int rc = check_batch(p, B);
+    int rc = cfs_check_batch(p, B);
     if (rc) return rc;
-    if (!lin || !u_lin || !xR1 || !dist || !grad || !u) return fail(CFS_ERR_INVALID_ARG, "NULL array");
-    HIPCHK(hipSetDevice(p->device));
+    if (!lin || !u_lin || !xR1 || !dist || !grad || !u) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL array");
+    CFS_HIPCHK(hipSetDevice(p->device));
     const size_t nobs = p->d.nobs, H = p->d.H, nj = p->d.njoint, nn = p->nn;
     const size_t nlam = nobs * H + (limited(p) ? 6 : 4) * nn;   // [collision | vel+ | vel- | bound+ | bound- (| pos+ | pos-)]
     Stage st;
@@ -1476,9 +1254,9 @@ int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const 
     double *d_u = st.up(u_lin, (size_t)B * nn);
     double *d_dist = st.up(dist, (size_t)B * nobs * H);
     double *d_grad = st.up(grad, (size_t)B * nobs * H * nj);
-    double *d_lam = lambda ? st.up<double>(nullptr, (size_t)B * nlam) : nullptr;
-    int *d_it = st.up<int>(nullptr, (size_t)B), *d_st = st.up<int>(nullptr, (size_t)B);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
+    double *d_lam = lambda ? st.out<double>((size_t)B * nlam) : nullptr;
+    int *d_it = st.out<int>((size_t)B), *d_st = st.out<int>((size_t)B);
+    if (st.err != hipSuccess) return st.result("staging");
     FusedParams fp;
     fill_fused_family(p, fp, B);
     fp.x_init = pb.x_; fp.xR1 = pb.xR1; fp.ff = pb.ff; fp.caug = pb.caug; fp.obs = pb.obs;
@@ -1492,141 +1270,14 @@ int cfs_qp(cfs_problem *p, int B, const double *lin, const double *u_lin, const 
         fp.x0 = p->x0.p;
     } else fp.x0 = d_lin;
     SoftParams sp;
-    HIPCHK(launch_fused(p->d.njoint, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false), false, limited(p)));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(nullptr));
+    CFS_HIPCHK(launch_fused(p->d.njoint, fp, nullptr, force_w1(p), analytic(p), soft_params(p, sp, false), false, limited(p)));
+    CFS_HIPCHK(hipGetLastError());
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
     st.down(u, d_u, (size_t)B * nn);
     if (lambda) st.down(lambda, d_lam, (size_t)B * nlam);
     st.down(qp_iter, d_it, (size_t)B);
     st.down(status, d_st, (size_t)B);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
-}
-
-// ---- clearance audit (cfs_clear.hip) ----------------------------------------------------------------------------------------
-// Reads the family constants of the handle (robot, H, nobs, delta_t, obstacle motion) and nothing a solve writes.
-int cfs_clearance_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
-                         double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, void *stream)
-{
-    int rc = check_batch(p, B);
-    if (rc) return rc;
-    if (substeps < 1 || substeps > 64) return fail(CFS_ERR_INVALID_ARG, "substeps=%d outside 1..64", substeps);
-    if (!x_ || !u || !xR1 || !obs || !dist_wp || !dist_path || !dist_lower || !t_path || !link_path) return fail(CFS_ERR_INVALID_ARG, "NULL array");
-    if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "the clearance audit measures line obstacles only: this handle has %d mesh obstacles", p->nmesh);
-    HIPCHK(hipSetDevice(p->device));
-    ClearParams cp;
-    cp.rb = p->rb.p; cp.B = B; cp.H = p->d.H; cp.nj = p->d.njoint; cp.nobs = p->d.nobs; cp.S = substeps;
-    cp.move = moving(p) ? 1 : 0; cp.dt = p->d.robot.delta_t;
-    cp.x_ = x_; cp.u = u; cp.xR1 = xR1; cp.obs = obs;
-    cp.dist_wp = dist_wp; cp.dist_path = dist_path; cp.dist_lower = dist_lower; cp.t_path = t_path; cp.link_path = link_path;
-    cp.obs_stride = (int)obs_rows(p); cp.out_stride = p->d.nobs;
-    memcpy(cp.rho, p->rho, sizeof cp.rho);
-    HIPCHK(launch_clearance(cp, reinterpret_cast<hipStream_t>(stream)));
-    return CFS_SUCCESS;
-}
-
-int cfs_clearance(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
-                  double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path)
-{
-    int rc = check_batch(p, B);
-    if (rc) return rc;
-    if (substeps < 1 || substeps > 64) return fail(CFS_ERR_INVALID_ARG, "substeps=%d outside 1..64", substeps);
-    if (!x_ || !u || !xR1 || !obs || !dist_wp || !dist_path || !dist_lower || !t_path || !link_path) return fail(CFS_ERR_INVALID_ARG, "NULL array");
-    if (p->nmesh > 0) return fail(CFS_ERR_INVALID_ARG, "the clearance audit measures line obstacles only: this handle has %d mesh obstacles", p->nmesh);
-    HIPCHK(hipSetDevice(p->device));
-    const size_t n = (size_t)B * p->d.nobs;
-    Stage st;
-    const double *d_x = st.up(x_, (size_t)B * p->nx), *d_u = st.up(u, (size_t)B * p->nn), *d_x1 = st.up(xR1, (size_t)B * p->ns);
-    const double *d_obs = st.up(obs, (size_t)B * obs_rows(p) * 6);
-    double *d_wp = st.up<double>(nullptr, n), *d_path = st.up<double>(nullptr, n), *d_low = st.up<double>(nullptr, n), *d_t = st.up<double>(nullptr, n);
-    int *d_lk = st.up<int>(nullptr, n);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
-    rc = cfs_clearance_device(p, B, substeps, d_x, d_u, d_x1, d_obs, d_wp, d_path, d_low, d_t, d_lk, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    st.down(dist_wp, d_wp, n); st.down(dist_path, d_path, n); st.down(dist_lower, d_low, n); st.down(t_path, d_t, n);
-    st.down(link_path, d_lk, n);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
-}
-
-// ---- clearance audit with mesh obstacles (cfs_clear_mesh.hip) ---------------------------------------------------------------
-static int check_clearance_mesh(cfs_problem *p, int B, int substeps, const void *const *arrays, int n)
-{
-    int rc = check_batch(p, B);
-    if (rc) return rc;
-    if (substeps < 1 || substeps > 64) return fail(CFS_ERR_INVALID_ARG, "substeps=%d outside 1..64", substeps);
-    for (int i = 0; i < n; ++i)
-        if (!arrays[i]) return fail(CFS_ERR_INVALID_ARG, "NULL array");
-    if (p->nmesh < 1) return fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh needs a handle with mesh obstacles (cfs_problem_set_meshes): use cfs_clearance");
-    return CFS_SUCCESS;
-}
-
-int cfs_clearance_mesh_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1,
-                              const double *obs, double *dist_wp, double *dist_path, double *dist_lower, double *t_path,
-                              int *link_path, int *tri_path, void *stream)
-{
-    const void *arrays[] = {x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, tri_path};
-    int rc = check_clearance_mesh(p, B, substeps, arrays, 10);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(p->device));
-    const int nline = p->d.nobs - p->nmesh;
-    if (substeps > p->cm_S) {                        // grow the workspace (hipFree waits for whatever still reads the old one)
-        const size_t G = (size_t)p->d.H * substeps + 1, mb = (size_t)p->d.max_batch;
-        p->release_clear_mesh();
-        HIPCHK(p->cm_d.alloc(mb * G * p->nmesh)); HIPCHK(p->cm_L.alloc(mb * G));
-        HIPCHK(p->cm_lk.alloc(mb * G * p->nmesh)); HIPCHK(p->cm_tri.alloc(mb * G * p->nmesh));
-        HIPCHK(p->cm_seed.alloc(mb * (size_t)(p->d.H + 1) * p->d.njoint * p->nmesh));
-        HIPCHK(p->cm_rho.alloc(CFS_MAX_LINKS * CFS_MAX_LINKS));
-        HIPCHK(hipMemcpy(p->cm_rho.p, p->rho, sizeof p->rho, hipMemcpyHostToDevice));
-        p->cm_S = substeps;
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (nline > 0) {                                 // the line columns: cfs_clearance's kernel on the first nline rows and columns
-        ClearParams cp;
-        cp.rb = p->rb.p; cp.B = B; cp.H = p->d.H; cp.nj = p->d.njoint; cp.nobs = nline; cp.S = substeps;
-        cp.move = 0; cp.dt = p->d.robot.delta_t;
-        cp.x_ = x_; cp.u = u; cp.xR1 = xR1; cp.obs = obs;
-        cp.dist_wp = dist_wp; cp.dist_path = dist_path; cp.dist_lower = dist_lower; cp.t_path = t_path; cp.link_path = link_path;
-        cp.obs_stride = p->d.nobs; cp.out_stride = p->d.nobs;
-        memcpy(cp.rho, p->rho, sizeof cp.rho);
-        HIPCHK(launch_clearance(cp, s));
-    }
-    ClearMeshParams cm;
-    cm.rb = p->rb.p; cm.B = B; cm.H = p->d.H; cm.nj = p->d.njoint; cm.nobs = p->d.nobs; cm.nmesh = p->nmesh; cm.S = substeps;
-    cm.opt = ((p->dbg_mask & CFS_DBG_CLEAR_NO_BOUND) ? 0 : CLEAR_MESH_BOUND) | ((p->dbg_mask & CFS_DBG_CLEAR_SEED) ? CLEAR_MESH_SEED : 0);
-    cm.dt = p->d.robot.delta_t;
-    cm.meshes = p->meshes_d.p;
-    cm.x_ = x_; cm.u = u; cm.xR1 = xR1;
-    cm.dist_wp = dist_wp; cm.dist_path = dist_path; cm.dist_lower = dist_lower; cm.t_path = t_path;
-    cm.link_path = link_path; cm.tri_path = tri_path;
-    cm.ws_d = p->cm_d.p; cm.ws_L = p->cm_L.p; cm.ws_lk = p->cm_lk.p; cm.ws_tri = p->cm_tri.p; cm.ws_seed = p->cm_seed.p;
-    cm.rho = p->cm_rho.p;
-    HIPCHK(launch_clearance_mesh(cm, s));
-    return CFS_SUCCESS;
-}
-
-int cfs_clearance_mesh(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
-                       double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, int *tri_path)
-{
-    const void *arrays[] = {x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, tri_path};
-    int rc = check_clearance_mesh(p, B, substeps, arrays, 10);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(p->device));
-    const size_t n = (size_t)B * p->d.nobs;
-    Stage st;
-    const double *d_x = st.up(x_, (size_t)B * p->nx), *d_u = st.up(u, (size_t)B * p->nn), *d_x1 = st.up(xR1, (size_t)B * p->ns);
-    const double *d_obs = st.up(obs, n * 6);
-    double *d_wp = st.up<double>(nullptr, n), *d_path = st.up<double>(nullptr, n), *d_low = st.up<double>(nullptr, n), *d_t = st.up<double>(nullptr, n);
-    int *d_lk = st.up<int>(nullptr, n), *d_tri = st.up<int>(nullptr, n);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "staging failed: %s", hipGetErrorString(st.err));
-    rc = cfs_clearance_mesh_device(p, B, substeps, d_x, d_u, d_x1, d_obs, d_wp, d_path, d_low, d_t, d_lk, d_tri, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    st.down(dist_wp, d_wp, n); st.down(dist_path, d_path, n); st.down(dist_lower, d_low, n); st.down(t_path, d_t, n);
-    st.down(link_path, d_lk, n); st.down(tri_path, d_tri, n);
-    if (st.err != hipSuccess) return fail(CFS_ERR_HIP, "copy back failed: %s", hipGetErrorString(st.err));
-    return CFS_SUCCESS;
+    return st.result("copy back");
 }
 
 }  // extern "C"

@@ -260,15 +260,10 @@ bool chomp_fits(int nj, int H, int nobs) { return chomp_lds_doubles(nj, H, nobs)
 hipError_t launch_chomp(int nj, const ChompParams &p, hipStream_t s)
 {
     const size_t lds = chomp_lds_doubles(nj, p.H, p.nobs) * 8;
-    switch (nj) {
-    case 2: hipLaunchKernelGGL(cfs_chomp_kernel<2>, dim3(p.B), dim3(CT), lds, s, p); break;
-    case 3: hipLaunchKernelGGL(cfs_chomp_kernel<3>, dim3(p.B), dim3(CT), lds, s, p); break;
-    case 4: hipLaunchKernelGGL(cfs_chomp_kernel<4>, dim3(p.B), dim3(CT), lds, s, p); break;
-    case 5: hipLaunchKernelGGL(cfs_chomp_kernel<5>, dim3(p.B), dim3(CT), lds, s, p); break;
-    case 6: hipLaunchKernelGGL(cfs_chomp_kernel<6>, dim3(p.B), dim3(CT), lds, s, p); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return cfs_for_nj(nj, [&](auto N) {
+        hipLaunchKernelGGL(cfs_chomp_kernel<decltype(N)::value>, dim3(p.B), dim3(CT), lds, s, p);
+        return hipGetLastError();
+    });
 }
 
 // derivest's constant tables (see oracle/chomp_oracle.c for the same derivation): derivest.m:238, :282, :478-503, :512-528

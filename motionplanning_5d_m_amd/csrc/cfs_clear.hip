@@ -22,9 +22,10 @@
 // minimum over values that do not depend on P, on B or on the launch, so neither does the result.
 #include "cfs_clear_dev.h"
 #include "cfs_geom_dev.h"
-#include "cfs_host.h"
+#include "cfs_problem.h"
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 namespace {
 
@@ -218,4 +219,66 @@ hipError_t launch_clearance(const ClearParams &p, hipStream_t s)
     }
     hipLaunchKernelGGL(cfs_clearance_kernel, dim3(p.B), dim3(q.P), q.bytes, s, p, q);
     return hipGetLastError();
+}
+
+// ---- C ABI (include/cfs_hip.h, "clearance audit") ---------------------------------------------------------------------------
+// Reads the family constants of the handle (robot, H, nobs, delta_t, obstacle motion) and nothing a solve writes.
+int cfs_check_clearance(const cfs_problem *p, int B, int substeps, const ClearArrays &a, bool mesh)
+{
+    int rc = cfs_check_batch(p, B);
+    if (rc) return rc;
+    if (substeps < 1 || substeps > 64) return cfs_fail(CFS_ERR_INVALID_ARG, "substeps=%d outside 1..64", substeps);
+    if (!a.x_ || !a.u || !a.xR1 || !a.obs || !a.dist_wp || !a.dist_path || !a.dist_lower || !a.t_path || !a.link_path || (mesh && !a.tri_path))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "NULL array");
+    if (mesh && p->nmesh < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh needs a handle with mesh obstacles (cfs_problem_set_meshes): use cfs_clearance");
+    if (!mesh && p->nmesh > 0) return cfs_fail(CFS_ERR_INVALID_ARG, "the clearance audit measures line obstacles only: this handle has %d mesh obstacles", p->nmesh);
+    return CFS_SUCCESS;
+}
+
+hipError_t cfs_launch_clearance_lines(const cfs_problem *p, int B, int substeps, int nline, const ClearArrays &a, hipStream_t s)
+{
+    ClearParams cp;
+    cp.rb = p->rb.p; cp.B = B; cp.H = p->d.H; cp.nj = p->d.njoint; cp.nobs = nline; cp.S = substeps;
+    cp.move = cfs_moving(p) ? 1 : 0; cp.dt = p->d.robot.delta_t;             // a handle with meshes is static
+    cp.x_ = a.x_; cp.u = a.u; cp.xR1 = a.xR1; cp.obs = a.obs;
+    cp.dist_wp = a.dist_wp; cp.dist_path = a.dist_path; cp.dist_lower = a.dist_lower; cp.t_path = a.t_path; cp.link_path = a.link_path;
+    cp.obs_stride = (int)cfs_obs_rows(p); cp.out_stride = p->d.nobs;
+    memcpy(cp.rho, p->rho, sizeof cp.rho);
+    return launch_clearance(cp, s);
+}
+
+int cfs_clearance_host(cfs_problem *p, int B, int substeps, const ClearArrays &h, bool mesh)
+{
+    int rc = cfs_check_clearance(p, B, substeps, h, mesh);
+    if (rc) return rc;
+    CFS_HIPCHK(hipSetDevice(p->device));
+    const size_t nB = B, n = nB * p->d.nobs;
+    Stage st;
+    const ClearArrays a{st.up(h.x_, nB * p->nx), st.up(h.u, nB * p->nn), st.up(h.xR1, nB * p->ns), st.up(h.obs, nB * cfs_obs_rows(p) * 6),
+                        st.out<double>(n), st.out<double>(n), st.out<double>(n), st.out<double>(n), st.out<int>(n), mesh ? st.out<int>(n) : nullptr};
+    if (st.err != hipSuccess) return st.result("staging");
+    rc = mesh ? cfs_clearance_mesh_device(p, B, substeps, a.x_, a.u, a.xR1, a.obs, a.dist_wp, a.dist_path, a.dist_lower, a.t_path, a.link_path, a.tri_path, nullptr)
+              : cfs_clearance_device(p, B, substeps, a.x_, a.u, a.xR1, a.obs, a.dist_wp, a.dist_path, a.dist_lower, a.t_path, a.link_path, nullptr);
+    if (rc) return rc;
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
+    st.down(h.dist_wp, a.dist_wp, n); st.down(h.dist_path, a.dist_path, n); st.down(h.dist_lower, a.dist_lower, n); st.down(h.t_path, a.t_path, n);
+    st.down(h.link_path, a.link_path, n); st.down(h.tri_path, a.tri_path, n);
+    return st.result("copy back");
+}
+
+extern "C" int cfs_clearance_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
+                                    double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, void *stream)
+{
+    const ClearArrays a{x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, nullptr};
+    int rc = cfs_check_clearance(p, B, substeps, a, false);
+    if (rc) return rc;
+    CFS_HIPCHK(hipSetDevice(p->device));
+    CFS_HIPCHK(cfs_launch_clearance_lines(p, B, substeps, p->d.nobs, a, reinterpret_cast<hipStream_t>(stream)));
+    return CFS_SUCCESS;
+}
+
+extern "C" int cfs_clearance(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
+                             double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path)
+{
+    return cfs_clearance_host(p, B, substeps, ClearArrays{x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, nullptr}, false);
 }

@@ -25,6 +25,7 @@
 //          start before it descends (seed_tri of mesh_query).
 #include "cfs_clear_dev.h"
 #include "cfs_mesh_dev.h"
+#include "cfs_problem.h"
 
 namespace {
 
@@ -149,4 +150,46 @@ hipError_t launch_clearance_mesh(const ClearMeshParams &p, hipStream_t s)
     }
     hipLaunchKernelGGL(cfs_clear_mesh_scan_kernel, dim3(p.nmesh, p.B), dim3(CM_SCAN), 0, s, p);
     return hipGetLastError();
+}
+
+// ---- C ABI (include/cfs_hip.h, "clearance audit against mesh obstacles") ------------------------------------------------------
+extern "C" int cfs_clearance_mesh_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1,
+                                         const double *obs, double *dist_wp, double *dist_path, double *dist_lower, double *t_path,
+                                         int *link_path, int *tri_path, void *stream)
+{
+    const ClearArrays a{x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, tri_path};
+    int rc = cfs_check_clearance(p, B, substeps, a, true);
+    if (rc) return rc;
+    CFS_HIPCHK(hipSetDevice(p->device));
+    const int nline = p->d.nobs - p->nmesh;
+    if (substeps > p->cm_S) {                        // grow the workspace (hipFree waits for whatever still reads the old one)
+        const size_t G = (size_t)p->d.H * substeps + 1, mb = (size_t)p->d.max_batch;
+        p->release_clear_mesh();
+        CFS_HIPCHK(p->cm_d.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm_L.alloc(mb * G));
+        CFS_HIPCHK(p->cm_lk.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm_tri.alloc(mb * G * p->nmesh));
+        CFS_HIPCHK(p->cm_seed.alloc(mb * (size_t)(p->d.H + 1) * p->d.njoint * p->nmesh));
+        CFS_HIPCHK(p->cm_rho.alloc(CFS_MAX_LINKS * CFS_MAX_LINKS));
+        CFS_HIPCHK(hipMemcpy(p->cm_rho.p, p->rho, sizeof p->rho, hipMemcpyHostToDevice));
+        p->cm_S = substeps;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (nline > 0) CFS_HIPCHK(cfs_launch_clearance_lines(p, B, substeps, nline, a, s));   // the line columns: cfs_clearance's kernel
+    ClearMeshParams cm;
+    cm.rb = p->rb.p; cm.B = B; cm.H = p->d.H; cm.nj = p->d.njoint; cm.nobs = p->d.nobs; cm.nmesh = p->nmesh; cm.S = substeps;
+    cm.opt = ((p->dbg_mask & CFS_DBG_CLEAR_NO_BOUND) ? 0 : CLEAR_MESH_BOUND) | ((p->dbg_mask & CFS_DBG_CLEAR_SEED) ? CLEAR_MESH_SEED : 0);
+    cm.dt = p->d.robot.delta_t;
+    cm.meshes = p->meshes_d.p;
+    cm.x_ = x_; cm.u = u; cm.xR1 = xR1;
+    cm.dist_wp = dist_wp; cm.dist_path = dist_path; cm.dist_lower = dist_lower; cm.t_path = t_path;
+    cm.link_path = link_path; cm.tri_path = tri_path;
+    cm.ws_d = p->cm_d.p; cm.ws_L = p->cm_L.p; cm.ws_lk = p->cm_lk.p; cm.ws_tri = p->cm_tri.p; cm.ws_seed = p->cm_seed.p;
+    cm.rho = p->cm_rho.p;
+    CFS_HIPCHK(launch_clearance_mesh(cm, s));
+    return CFS_SUCCESS;
+}
+
+extern "C" int cfs_clearance_mesh(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
+                                  double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, int *tri_path)
+{
+    return cfs_clearance_host(p, B, substeps, ClearArrays{x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, tri_path}, true);
 }

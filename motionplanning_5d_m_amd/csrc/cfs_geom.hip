@@ -15,6 +15,7 @@
 // (variant x obstacle) segment pair on its own lane, and recombines the 2*NJ+1 minima per
 // (waypoint, obstacle).  Robot constants are staged in LDS because the link index is per-lane.
 #include "cfs_geom_dev.h"
+#include "cfs_host.h"
 
 namespace {
 
@@ -234,4 +235,48 @@ void launch_dense_con(const DenseConParams &p, hipStream_t s)
 {
     const dim3 grid(p.H * p.nj, p.B), block(256);
     hipLaunchKernelGGL(cfs_dense_con_kernel, grid, block, 0, s, p);
+}
+
+// ---- C ABI (include/cfs_hip.h): dist_arm for N poses against nobs line obstacles, host arrays; grad: the analytic gradient too ----
+static int dist_arm(const cfs_robot *robot, int njoint, int N, const double *theta, int nobs, const double *obs, double *d, int *linkid, double *pos,
+                    double *grad, bool with_grad)
+{
+    int rc = cfs_check_robot(robot, njoint);
+    if (rc) return rc;
+    if (N < 0 || nobs < 0 || !theta || !obs || !d || (with_grad && (!linkid || !grad))) return cfs_fail(CFS_ERR_INVALID_ARG, "bad argument");
+    if (N == 0 || nobs == 0) return CFS_SUCCESS;
+    rc = cfs_use_device(cfs_current_device());
+    if (rc) return rc;
+    DevRobot hr;
+    cfs_build_dev_robot(*robot, hr);
+    const size_t n = (size_t)N * nobs;
+    Stage st;
+    DistArmParams P;
+    P.rb = st.up(&hr, 1);
+    P.N = N; P.nobs = nobs; P.nj = njoint;
+    P.theta = st.up(theta, (size_t)N * njoint);
+    P.obs = st.up(obs, (size_t)nobs * 6);
+    P.d = st.out<double>(n);
+    P.linkid = st.out<int>(n);
+    P.pos = pos ? st.out<double>((size_t)N * njoint * 6) : nullptr;
+    P.grad = with_grad ? st.out<double>(n * njoint) : nullptr;
+    if (st.err != hipSuccess) return st.result("staging");
+    if (with_grad) launch_dist_arm_grad(P, nullptr);
+    else launch_dist_arm(P, nullptr);
+    CFS_HIPCHK(hipGetLastError());
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
+    st.down(d, P.d, n); st.down(linkid, P.linkid, n); st.down(pos, P.pos, (size_t)N * njoint * 6); st.down(grad, P.grad, n * njoint);
+    return st.result("copy back");
+}
+
+extern "C" int cfs_dist_arm(const cfs_robot *robot, int njoint, int N, const double *theta, int nobs, const double *obs,
+                            double *d, int *linkid, double *pos)
+{
+    return dist_arm(robot, njoint, N, theta, nobs, obs, d, linkid, pos, nullptr, false);
+}
+
+extern "C" int cfs_dist_arm_grad(const cfs_robot *robot, int njoint, int N, const double *theta, int nobs, const double *obs,
+                                 double *d, int *linkid, double *grad)
+{
+    return dist_arm(robot, njoint, N, theta, nobs, obs, d, linkid, nullptr, grad, true);
 }

@@ -1,20 +1,80 @@
 // cfs_host.h -- host-side helpers shared by the translation units of libcfs_hip.so (not part of the C ABI).
 #pragma once
 #include "cfs_device.h"
+#include <type_traits>
 #include <vector>
 
 int cfs_fail(int code, const char *fmt, ...);            // records the message of cfs_last_error(), returns code
 int cfs_current_device();                                // device chosen with cfs_set_device
+int cfs_use_device(int device);                          // CFS_ERR_NO_DEVICE unless a device is visible, then hipSetDevice(device)
 int cfs_check_robot(const cfs_robot *r, int nj);         // CFS_SUCCESS or an error code (message recorded)
 void cfs_build_dev_robot(const cfs_robot &r, DevRobot &d);
-struct ProblemShape { int device, max_batch, nn, nx, max_o_iter, infeas; };
-void cfs_problem_shape(const cfs_problem *p, ProblemShape *out);   // what entry points outside cfs_api.hip read of a handle
+// reads and / or zeroes a __device__ unsigned long long counter (its address) of the current device: cfs_debug_*_frontier_overflows
+int cfs_frontier_overflows(const void *symbol, unsigned long long *count, int reset);
 
 #define CFS_HIPCHK(call)                                                                                     \
     do {                                                                                                     \
         hipError_t e_ = (call);                                                                              \
         if (e_ != hipSuccess) return cfs_fail(CFS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));   \
     } while (0)
+
+// f(std::integral_constant<int, NJ>{}) for the runtime joint count nj = 2..6: how every launcher picks its kernel instantiation
+template <class F> hipError_t cfs_for_nj(int nj, F &&f)
+{
+    switch (nj) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+
+template <class T>
+struct DevBuf {                  // a device array that a handle owns
+    T *p = nullptr;
+    size_t n = 0;
+    hipError_t alloc(size_t count)
+    {
+        n = count;
+        return hipMalloc(reinterpret_cast<void **>(&p), (count ? count : 1) * sizeof(T));
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
+};
+
+// device staging of host arrays for the host-pointer entry points: the first error sticks and turns every later call into a no-op,
+// the destructor frees what was allocated
+struct Stage {
+    std::vector<void *> ptrs;
+    hipError_t err = hipSuccess;
+    template <class T> T *up(const T *h, size_t n)       // n elements (room for one when n is 0); h == nullptr: left uninitialised
+    {
+        if (err != hipSuccess) return nullptr;
+        void *d = nullptr;
+        err = hipMalloc(&d, (n ? n : 1) * sizeof(T));
+        if (err != hipSuccess) return nullptr;
+        ptrs.push_back(d);
+        if (h && n) err = hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
+        return static_cast<T *>(d);
+    }
+    template <class T> T *out(size_t n) { return up<T>(nullptr, n); }
+    template <class T> T *zeros(size_t n)
+    {
+        T *d = out<T>(n);
+        if (d && n) err = hipMemset(d, 0, n * sizeof(T));
+        return d;
+    }
+    template <class T> void down(T *h, const T *d, size_t n)   // h == nullptr (an optional output): nothing to do
+    {
+        if (err == hipSuccess && h && n) err = hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost);
+    }
+    int result(const char *what) const                   // CFS_SUCCESS, or CFS_ERR_HIP with "<what> failed: <HIP's message>"
+    {
+        return err == hipSuccess ? CFS_SUCCESS : cfs_fail(CFS_ERR_HIP, "%s failed: %s", what, hipGetErrorString(err));
+    }
+    ~Stage() { for (void *q : ptrs) (void)hipFree(q); }
+};
 
 // ---- mesh obstacles (cfs_mesh.hip) --------------------------------------------------------------
 struct BvhNode {                 // 128 B = one L2 line: an inner node carries the boxes of BOTH children, so a level costs one
@@ -136,6 +196,11 @@ struct RrtMeshArgs {
 };
 hipError_t launch_rrt_mesh(int nj, int variant, const RrtParams &p, const RrtMeshArgs &ma, hipStream_t s);
 size_t rrt_mesh_lds_bytes(int nj, int max_iter, int variant);      // rrt_lds_bytes + the variant's mesh scratch
+// The mesh table of a cfs_rrt_grow_mesh* / cfs_ik_solve_mesh* call -> kernel argument + variant (RRT_MESH_NONE when nmesh is 0); host
+// work only, nothing is launched or allocated.  min_nmesh: 0 (RRT) | 1 (IK).  The device of a mesh is compared last, so that every
+// other refusal is the same with and without a device.
+int cfs_check_mesh_table(int nobs, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int min_nmesh, int default_variant,
+                         RrtMeshArgs &ma, int &variant);
 // cfs_ik_solve_mesh* (cfs_ik.hip) runs the same two variants on its candidates; flags == 0: the variant the measurement of DESIGN.md
 // section 21 names
 constexpr int IK_MESH_DEFAULT = RRT_MESH_WAVE;

@@ -29,7 +29,6 @@
 #include "cfs_host.h"
 #include <cmath>
 #include <cstring>
-#include <vector>
 
 namespace {
 
@@ -462,19 +461,15 @@ __global__ __launch_bounds__(256) void cfs_tool_pose_kernel(const PoseParams P)
     }
 }
 
+template <int NJ, int MESH> hipError_t launch_ik_kernel(size_t lds, const IkArgs<MESH> &a, hipStream_t s)
+{
+    hipLaunchKernelGGL((cfs_ik_kernel<NJ, MESH>), dim3((a.P.T + IK_WAVES - 1) / IK_WAVES), dim3(WV * IK_WAVES), lds, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_ik(int nj, const IkParams &p, hipStream_t s)
 {
-    const dim3 grid((p.T + IK_WAVES - 1) / IK_WAVES), block(WV * IK_WAVES);
-    const IkArgs<RRT_MESH_NONE> a{p};
-    switch (nj) {
-    case 2: hipLaunchKernelGGL((cfs_ik_kernel<2, RRT_MESH_NONE>), grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((cfs_ik_kernel<3, RRT_MESH_NONE>), grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((cfs_ik_kernel<4, RRT_MESH_NONE>), grid, block, 0, s, a); break;
-    case 5: hipLaunchKernelGGL((cfs_ik_kernel<5, RRT_MESH_NONE>), grid, block, 0, s, a); break;
-    case 6: hipLaunchKernelGGL((cfs_ik_kernel<6, RRT_MESH_NONE>), grid, block, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return cfs_for_nj(nj, [&](auto N) { return launch_ik_kernel<decltype(N)::value, RRT_MESH_NONE>(0, {p}, s); });
 }
 
 size_t ik_mesh_lds_bytes(int variant)
@@ -485,35 +480,19 @@ size_t ik_mesh_lds_bytes(int variant)
 hipError_t launch_ik_mesh(int nj, int variant, const IkParams &p, const IkMeshArgs &m, hipStream_t s)
 {
     if (variant != RRT_MESH_PER_LANE && variant != RRT_MESH_WAVE) return hipErrorInvalidValue;
-    const dim3 grid((p.T + IK_WAVES - 1) / IK_WAVES), block(WV * IK_WAVES);
     const size_t lds = ik_mesh_lds_bytes(variant);
-    const IkArgs<RRT_MESH_PER_LANE> aa{p, m};
-    const IkArgs<RRT_MESH_WAVE> ab{p, m};
-#define IK_MESH_LAUNCH(NJ_)                                                                                          \
-    case NJ_:                                                                                                        \
-        if (variant == RRT_MESH_PER_LANE) hipLaunchKernelGGL((cfs_ik_kernel<NJ_, RRT_MESH_PER_LANE>), grid, block, lds, s, aa); \
-        else hipLaunchKernelGGL((cfs_ik_kernel<NJ_, RRT_MESH_WAVE>), grid, block, lds, s, ab);                        \
-        break;
-    switch (nj) {
-        IK_MESH_LAUNCH(2) IK_MESH_LAUNCH(3) IK_MESH_LAUNCH(4) IK_MESH_LAUNCH(5) IK_MESH_LAUNCH(6)
-    default: return hipErrorInvalidValue;
-    }
-#undef IK_MESH_LAUNCH
-    return hipGetLastError();
+    return cfs_for_nj(nj, [&](auto N) {
+        constexpr int NJ = decltype(N)::value;
+        return variant == RRT_MESH_PER_LANE ? launch_ik_kernel<NJ, RRT_MESH_PER_LANE>(lds, {p, m}, s) : launch_ik_kernel<NJ, RRT_MESH_WAVE>(lds, {p, m}, s);
+    });
 }
 
 hipError_t launch_tool_pose(int nj, const PoseParams &p, hipStream_t s)
 {
-    const dim3 grid((p.N + 255) / 256), block(256);
-    switch (nj) {
-    case 2: hipLaunchKernelGGL(cfs_tool_pose_kernel<2>, grid, block, 0, s, p); break;
-    case 3: hipLaunchKernelGGL(cfs_tool_pose_kernel<3>, grid, block, 0, s, p); break;
-    case 4: hipLaunchKernelGGL(cfs_tool_pose_kernel<4>, grid, block, 0, s, p); break;
-    case 5: hipLaunchKernelGGL(cfs_tool_pose_kernel<5>, grid, block, 0, s, p); break;
-    case 6: hipLaunchKernelGGL(cfs_tool_pose_kernel<6>, grid, block, 0, s, p); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return cfs_for_nj(nj, [&](auto N) {
+        hipLaunchKernelGGL(cfs_tool_pose_kernel<decltype(N)::value>, dim3((p.N + 255) / 256), dim3(256), 0, s, p);
+        return hipGetLastError();
+    });
 }
 
 // ---- C ABI (include/cfs_hip.h, "inverse kinematics") ----------------------------------------------------------------------------
@@ -572,32 +551,14 @@ void ik_point(IkParams &P, const double *obs, const double *D, const double *tar
     P.cand_theta = o->cand_theta; P.cand_status = o->cand_status; P.cand_iter = o->cand_iter;
 }
 
-// the meshes of a cfs_ik_solve_mesh* call -> kernel argument + variant; host work only, nothing is launched or allocated.  The device
-// of a handle is compared last, so that every other refusal is the same with and without a device.
+// the meshes of a cfs_ik_solve_mesh* call -> kernel argument + variant: RRT's table, then the margins for the winner's clearance
 struct IkMeshCall { int nmesh; const cfs_mesh *const *meshes; const double *D_mesh; int flags; };
 int check_ik_mesh(const cfs_ik_desc *d, const IkMeshCall &c, IkMeshArgs &m, int &variant)
 {
-    variant = RRT_MESH_NONE;
     memset(&m, 0, sizeof m);
-    if (c.nmesh < 1 || d->nobs + c.nmesh > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d + nmesh %d outside 1..%d", d->nobs, c.nmesh, CFS_MAX_OBS);
-    if (c.flags & ~(CFS_IK_MESH_PER_LANE | CFS_IK_MESH_WAVE | CFS_IK_MESH_SMALL_FRONTIER)) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown flags 0x%x", c.flags);
-    if ((c.flags & CFS_IK_MESH_PER_LANE) && (c.flags & (CFS_IK_MESH_WAVE | CFS_IK_MESH_SMALL_FRONTIER)))
-        return cfs_fail(CFS_ERR_INVALID_ARG, "CFS_IK_MESH_PER_LANE excludes the other flags");
-    if (!c.meshes || !c.D_mesh) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes / D_mesh must be given");
-    for (int j = 0; j < c.nmesh; ++j) {
-        if (!c.meshes[j]) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d is NULL", j);
-        if (!std::isfinite(c.D_mesh[j]) || !(c.D_mesh[j] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "D_mesh[%d] must be finite and > 0", j);
-    }
-    for (int j = 0; j < c.nmesh; ++j) {
-        if (c.meshes[j]->device != cfs_current_device())
-            return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d lives on device %d, the current device is %d", j, c.meshes[j]->device, cfs_current_device());
-        m.MA.m[j].nodes = c.meshes[j]->nodes_d; m.MA.m[j].tri = c.meshes[j]->tri_d; m.MA.m[j].nt = c.meshes[j]->nt;
-        m.MA.m[j].thr = c.D_mesh[j] > 0.0001 ? c.D_mesh[j] : 0.0001;                   // dist_arm_surf_200i.m:22-24 folded into the threshold
-        m.D[j] = c.D_mesh[j];
-    }
-    m.MA.nmesh = c.nmesh;
-    variant = (c.flags & CFS_IK_MESH_PER_LANE) ? RRT_MESH_PER_LANE : (c.flags & (CFS_IK_MESH_WAVE | CFS_IK_MESH_SMALL_FRONTIER)) ? RRT_MESH_WAVE : IK_MESH_DEFAULT;
-    m.MA.cap = (c.flags & CFS_IK_MESH_SMALL_FRONTIER) ? RRT_FRONTIER_SMALL : RRT_FRONTIER_CAP;
+    int rc = cfs_check_mesh_table(d->nobs, c.nmesh, c.meshes, c.D_mesh, c.flags, 1, IK_MESH_DEFAULT, m.MA, variant);
+    if (rc) return rc;
+    for (int j = 0; j < c.nmesh; ++j) m.D[j] = c.D_mesh[j];
     return CFS_SUCCESS;
 }
 
@@ -616,8 +577,8 @@ int ik_device(const cfs_ik_desc *d, const IkMeshCall *mc, int T, const double *t
         rc = check_ik_mesh(d, *mc, M, variant);
         if (rc) return rc;
     }
-    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
+    rc = cfs_use_device(cfs_current_device());
+    if (rc) return rc;
     ik_point(P, d->obs, d->D, target_pos, target_axis, theta_ref, out);
     hipError_t e = mc ? launch_ik_mesh(d->njoint, variant, P, M, reinterpret_cast<hipStream_t>(stream))
                       : launch_ik(d->njoint, P, reinterpret_cast<hipStream_t>(stream));
@@ -647,48 +608,34 @@ int ik_host(const cfs_ik_desc *d, const IkMeshCall *mc, int T, const double *tar
             if (!(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis row %d is zero", t);
         }
     }
-    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
-    std::vector<void *> bufs;
-    hipError_t err = hipSuccess;
-    auto up = [&](const void *h, size_t bytes) -> void * {
-        if (err != hipSuccess) return nullptr;
-        void *p = nullptr;
-        err = hipMalloc(&p, bytes ? bytes : 8);
-        if (err != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        if (h && bytes) err = hipMemcpy(p, h, bytes, hipMemcpyHostToDevice);
-        return p;
-    };
+    rc = cfs_use_device(cfs_current_device());
+    if (rc) return rc;
+    const size_t nT = T;
+    Stage st;
     cfs_ik_out o;
     memset(&o, 0, sizeof o);
-    const double *obs_d = (const double *)up(d->obs, nobs * 6 * 8), *D_d = (const double *)up(d->D, nobs * 8);
-    const double *tp_d = (const double *)up(target_pos, (size_t)T * 3 * 8);
-    const double *ta_d = d->use_axis ? (const double *)up(target_axis, (size_t)T * 3 * 8) : nullptr;
-    const double *tr_d = (const double *)up(theta_ref, (size_t)T * nj * 8);
-    o.theta = (double *)up(nullptr, (size_t)T * nj * 8); o.status = (int *)up(nullptr, (size_t)T * 4);
-    if (out->selected) o.selected = (int *)up(nullptr, (size_t)T * 4);
-    if (out->n_ok) o.n_ok = (int *)up(nullptr, (size_t)T * 4);
-    if (out->err_pos) o.err_pos = (double *)up(nullptr, (size_t)T * 8);
-    if (out->err_axis) o.err_axis = (double *)up(nullptr, (size_t)T * 8);
-    if (out->clearance) o.clearance = (double *)up(nullptr, (size_t)T * 8);
-    if (out->cand_theta) o.cand_theta = (double *)up(nullptr, (size_t)T * R * nj * 8);
-    if (out->cand_status) o.cand_status = (int *)up(nullptr, (size_t)T * R * 4);
-    if (out->cand_iter) o.cand_iter = (int *)up(nullptr, (size_t)T * R * 4);
-    if (err == hipSuccess) {
+    const double *obs_d = st.up(d->obs, nobs * 6), *D_d = st.up(d->D, nobs), *tp_d = st.up(target_pos, nT * 3);
+    const double *ta_d = d->use_axis ? st.up(target_axis, nT * 3) : nullptr;
+    const double *tr_d = st.up(theta_ref, nT * nj);
+    o.theta = st.out<double>(nT * nj); o.status = st.out<int>(nT);
+    if (out->selected) o.selected = st.out<int>(nT);
+    if (out->n_ok) o.n_ok = st.out<int>(nT);
+    if (out->err_pos) o.err_pos = st.out<double>(nT);
+    if (out->err_axis) o.err_axis = st.out<double>(nT);
+    if (out->clearance) o.clearance = st.out<double>(nT);
+    if (out->cand_theta) o.cand_theta = st.out<double>(nT * R * nj);
+    if (out->cand_status) o.cand_status = st.out<int>(nT * R);
+    if (out->cand_iter) o.cand_iter = st.out<int>(nT * R);
+    if (st.err == hipSuccess) {
         ik_point(P, obs_d, D_d, tp_d, ta_d, tr_d, &o);
-        err = mc ? launch_ik_mesh(d->njoint, variant, P, M, nullptr) : launch_ik(d->njoint, P, nullptr);
-        if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+        st.err = mc ? launch_ik_mesh(d->njoint, variant, P, M, nullptr) : launch_ik(d->njoint, P, nullptr);
+        if (st.err == hipSuccess) st.err = hipStreamSynchronize(nullptr);
     }
-    auto down = [&](void *h, const void *dv, size_t bytes) { if (err == hipSuccess && h) err = hipMemcpy(h, dv, bytes, hipMemcpyDeviceToHost); };
-    down(out->theta, o.theta, (size_t)T * nj * 8); down(out->status, o.status, (size_t)T * 4);
-    down(out->selected, o.selected, (size_t)T * 4); down(out->n_ok, o.n_ok, (size_t)T * 4);
-    down(out->err_pos, o.err_pos, (size_t)T * 8); down(out->err_axis, o.err_axis, (size_t)T * 8); down(out->clearance, o.clearance, (size_t)T * 8);
-    down(out->cand_theta, o.cand_theta, (size_t)T * R * nj * 8); down(out->cand_status, o.cand_status, (size_t)T * R * 4);
-    down(out->cand_iter, o.cand_iter, (size_t)T * R * 4);
-    for (void *p : bufs) (void)hipFree(p);
-    if (err != hipSuccess) return cfs_fail(CFS_ERR_HIP, "IK staging or launch failed: %s", hipGetErrorString(err));
-    return CFS_SUCCESS;
+    st.down(out->theta, o.theta, nT * nj); st.down(out->status, o.status, nT);
+    st.down(out->selected, o.selected, nT); st.down(out->n_ok, o.n_ok, nT);
+    st.down(out->err_pos, o.err_pos, nT); st.down(out->err_axis, o.err_axis, nT); st.down(out->clearance, o.clearance, nT);
+    st.down(out->cand_theta, o.cand_theta, nT * R * nj); st.down(out->cand_status, o.cand_status, nT * R); st.down(out->cand_iter, o.cand_iter, nT * R);
+    return st.result("IK staging or launch");
 }
 }  // namespace
 
@@ -721,16 +668,7 @@ extern "C" int cfs_ik_solve_mesh(const cfs_ik_desc *d, int nmesh, const cfs_mesh
 
 extern "C" int cfs_debug_ik_frontier_overflows(unsigned long long *count, int reset)
 {
-    if (!count && !reset) return cfs_fail(CFS_ERR_INVALID_ARG, "nothing to do: count is NULL and reset is 0");
-    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
-    CFS_HIPCHK(hipDeviceSynchronize());
-    if (count) CFS_HIPCHK(hipMemcpyFromSymbol(count, HIP_SYMBOL(g_ik_frontier_overflows), sizeof *count));
-    if (reset) {
-        const unsigned long long zero = 0ull;
-        CFS_HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_ik_frontier_overflows), &zero, sizeof zero));
-    }
-    return CFS_SUCCESS;
+    return cfs_frontier_overflows(&g_ik_frontier_overflows, count, reset);
 }
 
 extern "C" int cfs_tool_pose(const cfs_robot *robot, int njoint, const double *tool, const double *tool_axis, int N, const double *theta,
@@ -744,29 +682,19 @@ extern "C" int cfs_tool_pose(const cfs_robot *robot, int njoint, const double *t
     const double an = std::sqrt(tool_axis[0] * tool_axis[0] + tool_axis[1] * tool_axis[1] + tool_axis[2] * tool_axis[2]);
     if (!(an > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool_axis is zero");
     if (N == 0) return CFS_SUCCESS;
-    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
+    rc = cfs_use_device(cfs_current_device());
+    if (rc) return rc;
     PoseParams P;
     memset(&P, 0, sizeof P);
     cfs_build_dev_robot(*robot, P.rb);
     P.N = N;
     for (int q = 0; q < 3; ++q) { P.tool[q] = tool[q]; P.axis[q] = tool_axis[q] / an; }
-    const size_t nj = njoint;
-    double *th_d = nullptr, *pos_d = nullptr, *dir_d = nullptr, *jac_d = nullptr;
-    hipError_t err = hipMalloc(&th_d, (size_t)N * nj * 8);
-    if (err == hipSuccess) err = hipMalloc(&pos_d, (size_t)N * 3 * 8);
-    if (err == hipSuccess) err = hipMalloc(&dir_d, (size_t)N * 3 * 8);
-    if (err == hipSuccess && jac) err = hipMalloc(&jac_d, (size_t)N * 6 * nj * 8);
-    if (err == hipSuccess) err = hipMemcpy(th_d, theta, (size_t)N * nj * 8, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-        P.theta = th_d; P.pos = pos_d; P.dir = dir_d; P.jac = jac_d;
-        err = launch_tool_pose(njoint, P, nullptr);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
-    if (err == hipSuccess) err = hipMemcpy(pos, pos_d, (size_t)N * 3 * 8, hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(dir, dir_d, (size_t)N * 3 * 8, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && jac) err = hipMemcpy(jac, jac_d, (size_t)N * 6 * nj * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(th_d); (void)hipFree(pos_d); (void)hipFree(dir_d); (void)hipFree(jac_d);
-    if (err != hipSuccess) return cfs_fail(CFS_ERR_HIP, "cfs_tool_pose: %s", hipGetErrorString(err));
-    return CFS_SUCCESS;
+    const size_t nj = njoint, n = N;
+    Stage st;
+    P.theta = st.up(theta, n * nj); P.pos = st.out<double>(n * 3); P.dir = st.out<double>(n * 3);
+    if (jac) P.jac = st.out<double>(n * 6 * nj);
+    if (st.err == hipSuccess) st.err = launch_tool_pose(njoint, P, nullptr);
+    if (st.err == hipSuccess) st.err = hipStreamSynchronize(nullptr);
+    st.down(pos, P.pos, n * 3); st.down(dir, P.dir, n * 3); st.down(jac, P.jac, n * 6 * nj);
+    return st.result("cfs_tool_pose");
 }

@@ -691,14 +691,7 @@ static hipError_t launch_linearize_mesh_nj(const LinMeshParams &p, hipStream_t s
 
 hipError_t launch_linearize_mesh(int nj, const LinMeshParams &p, hipStream_t s)
 {
-    switch (nj) {
-    case 2: return launch_linearize_mesh_nj<2>(p, s);
-    case 3: return launch_linearize_mesh_nj<3>(p, s);
-    case 4: return launch_linearize_mesh_nj<4>(p, s);
-    case 5: return launch_linearize_mesh_nj<5>(p, s);
-    case 6: return launch_linearize_mesh_nj<6>(p, s);
-    default: return hipErrorInvalidValue;
-    }
+    return cfs_for_nj(nj, [&](auto N) { return launch_linearize_mesh_nj<decltype(N)::value>(p, s); });
 }
 
 // doubles / ints of workspace per (problem, waypoint) the pipeline needs
@@ -721,7 +714,7 @@ int cfs_mesh_create(const double *vertices, int nv, const int *triangles, int nt
     if (!out) return cfs_fail(CFS_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (!vertices || !triangles || nv < 3 || nt < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "a mesh needs vertices and at least one triangle");
-    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device");
+    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
     std::vector<double> tri9(9 * (size_t)nt);
     for (int i = 0; i < nt; ++i)
         for (int v = 0; v < 3; ++v) {
@@ -770,7 +763,7 @@ int cfs_mesh_load_stl(const char *path, double scale, int map_from_stl, cfs_mesh
         }
     }
     for (double &v : tri9) v *= scale;
-    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device");
+    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
     return upload_mesh(tri9, out);
 }
 
@@ -799,25 +792,15 @@ int cfs_mesh_segment_distance(const cfs_mesh *m, int n, const double *segs, doub
 {
     if (!m || !segs || !dis || n < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh/segs/dis must be given, n >= 1");
     CFS_HIPCHK(hipSetDevice(m->device));
-    double *d_seg = nullptr, *d_dis = nullptr, *d_pts = nullptr;
-    int *d_tri = nullptr;
-    int rc = CFS_SUCCESS;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_seg), (size_t)n * 48);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_dis), (size_t)n * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_pts), (size_t)n * 48);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tri), (size_t)n * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_seg, segs, (size_t)n * 48, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        SegQueryParams q{m->view(), n, d_seg, d_dis, d_pts, d_tri};
+    const size_t nn = n;
+    Stage st;
+    SegQueryParams q{m->view(), n, st.up(segs, nn * 6), st.out<double>(nn), st.out<double>(nn * 6), st.out<int>(nn)};
+    if (st.err == hipSuccess) {
         hipLaunchKernelGGL(cfs_mesh_seg_kernel, dim3((n + MESH_THREADS - 1) / MESH_THREADS), dim3(MESH_THREADS), 0, nullptr, q);
-        e = hipGetLastError();
+        st.err = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpy(dis, d_dis, (size_t)n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && points) e = hipMemcpy(points, d_pts, (size_t)n * 48, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && tri) e = hipMemcpy(tri, d_tri, (size_t)n * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = cfs_fail(CFS_ERR_HIP, "cfs_mesh_segment_distance: %s", hipGetErrorString(e));
-    (void)hipFree(d_seg); (void)hipFree(d_dis); (void)hipFree(d_pts); (void)hipFree(d_tri);
-    return rc;
+    st.down(dis, q.dis, nn); st.down(points, q.pts, nn * 6); st.down(tri, q.tri, nn);
+    return st.result("cfs_mesh_segment_distance");
 }
 
 // dist_arm_surf_200i for N poses (host arrays): d[N], linkid[N] (1-based, may be NULL), points[N x 6] (may be NULL)
@@ -830,28 +813,16 @@ int cfs_dist_arm_mesh(const cfs_robot *robot, int njoint, int N, const double *t
     CFS_HIPCHK(hipSetDevice(m->device));
     DevRobot hr;
     cfs_build_dev_robot(*robot, hr);
-    DevRobot *d_rb = nullptr;
-    double *d_th = nullptr, *d_d = nullptr, *d_pts = nullptr;
-    int *d_id = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_rb), sizeof(DevRobot));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_th), (size_t)N * njoint * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_d), (size_t)N * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_pts), (size_t)N * 48);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_id), (size_t)N * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_rb, &hr, sizeof hr, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_th, theta, (size_t)N * njoint * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        ArmMeshParams q{d_rb, m->view(), N, njoint, d_th, d_d, d_id, d_pts};
+    const size_t n = N;
+    Stage st;
+    ArmMeshParams q{st.up(&hr, 1), m->view(), N, njoint, st.up(theta, n * njoint), st.out<double>(n), st.out<int>(n), st.out<double>(n * 6)};
+    if (st.err == hipSuccess) {
         const int per = MESH_THREADS / njoint;
         hipLaunchKernelGGL(cfs_dist_arm_mesh_kernel, dim3((N + per - 1) / per), dim3(MESH_THREADS), 0, nullptr, q);
-        e = hipGetLastError();
+        st.err = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpy(d, d_d, (size_t)N * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && linkid) e = hipMemcpy(linkid, d_id, (size_t)N * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && points) e = hipMemcpy(points, d_pts, (size_t)N * 48, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = cfs_fail(CFS_ERR_HIP, "cfs_dist_arm_mesh: %s", hipGetErrorString(e));
-    (void)hipFree(d_rb); (void)hipFree(d_th); (void)hipFree(d_d); (void)hipFree(d_pts); (void)hipFree(d_id);
-    return rc;
+    st.down(d, q.d, n); st.down(linkid, q.linkid, n); st.down(points, q.pts, n * 6);
+    return st.result("cfs_dist_arm_mesh");
 }
 
 }  // extern "C"

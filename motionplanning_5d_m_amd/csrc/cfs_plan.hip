@@ -9,7 +9,7 @@
 // order (k is unique within a slot), so every lane ends with the same winner whatever the order of the exchanges: the result
 // depends on the slot's own K candidates alone, not on S, the launch or the other slots.  The wavefront then copies the
 // winner's rows with lane-strided loads and stores.  No atomics, no LDS.
-#include "cfs_host.h"
+#include "cfs_problem.h"
 
 namespace {
 
@@ -117,15 +117,13 @@ extern "C" int cfs_select_best_device(cfs_problem *p, int S, int K, const int *r
     if (!route_ok || !cand || !best || !selected || !has_solution) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     if (!out_complete(cand) || !out_complete(best)) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL array in cand or best");
     if (!cand_viol_all && best_viol_all) return cfs_fail(CFS_ERR_INVALID_ARG, "best_viol_all needs cand_viol_all");
-    ProblemShape sh;
-    cfs_problem_shape(p, &sh);
-    if ((long long)S * K > sh.max_batch)
-        return cfs_fail(CFS_ERR_INVALID_ARG, "S*K=%lld exceeds max_batch=%d", (long long)S * K, sh.max_batch);
-    if (sh.infeas == CFS_INFEAS_SOFTEN && !cand_viol_all)
+    if ((long long)S * K > p->d.max_batch)
+        return cfs_fail(CFS_ERR_INVALID_ARG, "S*K=%lld exceeds max_batch=%d", (long long)S * K, p->d.max_batch);
+    if (p->infeas == CFS_INFEAS_SOFTEN && !cand_viol_all)
         return cfs_fail(CFS_ERR_INVALID_ARG, "cand_viol_all is required on a CFS_INFEAS_SOFTEN handle");
-    CFS_HIPCHK(hipSetDevice(sh.device));
+    CFS_HIPCHK(hipSetDevice(p->device));
     SelectParams P;
-    P.S = S; P.K = K; P.nn = sh.nn; P.nx = sh.nx; P.mk = sh.max_o_iter;
+    P.S = S; P.K = K; P.nn = p->nn; P.nx = p->nx; P.mk = p->d.MAX_O_ITER;
     P.route_ok = route_ok; P.cand = *cand; P.best = *best;
     P.cand_viol = cand_viol_all; P.best_viol = best_viol_all;
     P.selected = selected; P.has_solution = has_solution;

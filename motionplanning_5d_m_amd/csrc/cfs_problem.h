@@ -1,0 +1,98 @@
+// cfs_problem.h -- the problem-family handle (device constants + workspace of cfs_problem_create).  Private to the translation units of
+// libcfs_hip.so that own an entry point taking a handle; not installed, not part of the C ABI.
+#pragma once
+#include "cfs_host.h"
+
+struct cfs_problem {
+    cfs_problem_desc d;
+    int device;
+    int nn, ns, nx;
+    double lmax_vel, lmax_H;
+    DevRobot hrobot;
+    DevBuf<DevRobot> rb;
+    DevBuf<double> QQ, Hinv, Hq, M1n, M2n, lim, maxin, margin;
+    DevBuf<double> F1, F2, Cq;   // per-problem cost terms from (x0, xg), set by cfs_set_state_cost
+    DevBuf<DevCost> cost;        // structure of QQ (handles created from the cost weights)
+    std::vector<double> QQ_host; // what cfs_problem_family hands back
+    // workspace (max_batch problems)
+    DevBuf<double> x0, qu, dist, grad, Yg, Pt, u_hist, qu_hist;
+    DevBuf<int> noise_row, linkid, pool_flag;
+    bool pool_dirty = false;   // a solve of this handle failed to enqueue: clear the spill-pool flags before the next one
+    int pool_n = 1;            // slots of the spill pool (Yg / Pt): one per workgroup that can be resident at once, never more than max_batch
+    DevBuf<int> order, okey;   // launch order of the fused solver, automatic: violation count of the initial trajectory -> rank
+    DevBuf<int> order_user;    // the caller's permutation (cfs_set_launch_order); a solve of another batch size falls back to the automatic order
+    int n_cu = 256;            // compute units of the handle's device: a batch of at most n_cu problems starts all at once
+    int order_mode = 0, order_n = 0;   // 0 automatic, 1 given (order_n entries), 2 identity
+    // mesh obstacles (cfs_problem_set_meshes): the last nmesh of the nobs obstacles
+    int nmesh = 0;
+    DevBuf<DevMesh> meshes_d;
+    DevBuf<double> st_cost, m_ends, m_base, m_shift, m_upper, m_pd, m_pnd;
+    DevBuf<int> st_done, m_tri, m_near, m_pi;
+    // cfs_clearance_mesh*: per-sample workspace for cm_S sub-steps (grown by the first audit that needs more) and rho on the device
+    DevBuf<double> cm_d, cm_L, cm_rho;
+    DevBuf<int> cm_lk, cm_tri, cm_seed;
+    int cm_S = 0;
+    // developer / test switches (cfs_debug_*, include/cfs_hip.h): per handle, no process-wide state
+    int dbg_mask = 0, dbg_warm_max = 0;
+    double dbg_polish_tol = 1e-11;        // = the constraint scan's own feasibility tolerance
+    DevBuf<unsigned long long> stamps;    // 12 cycle accumulators per problem
+    int stamps_B = 0;
+    DevBuf<double> trace;                 // 8 doubles per active-set step of problem trace_b
+    int trace_b = -1, trace_cap = 0;
+    DevBuf<double> u_log;                 // max_batch x MAX_O_ITER x nn: u after every outer iteration (both solvers)
+    int jac = CFS_JAC_FD_LITERAL;         // cfs_problem_set_jacobian: which linearisation every later launch of this handle runs
+    int infeas = CFS_INFEAS_STOP;         // cfs_problem_set_infeasible_policy
+    int motion = CFS_OBS_STATIC;          // cfs_problem_set_obstacle_motion: obs arrays are B x nobs x 6 | B x H x nobs x 6
+    bool limited = false;                 // cfs_problem_set_joint_limits: position rows in every QP (the LIM kernels); lim[nj, 3nj) = [lo; hi]
+    std::vector<double> jlim;             // [lo; hi] as set (2 nj; empty: no limits)
+    double rho[CFS_MAX_LINKS * CFS_MAX_LINKS];   // cfs_clearance*: reach of capsule k about the axis of joint m (cfs_clear_build_rho)
+    double soft_weight = 0.0;             // mu of CFS_INFEAS_SOFTEN (0: never set)
+    DevBuf<double> soft_viol;             // max_batch x MAX_O_ITER: viol_all of the last whole solve (allocated with SOFTEN)
+    DevBuf<int> soft_n;                   // max_batch: n_soft of the last whole solve
+    bool prof = false;
+    std::vector<hipEvent_t> ev;   // 4 per profiled solve: gemm start/stop, fused start/stop
+    std::vector<hipEvent_t> ev_free;   // recycled events: none is created inside a timed region once the pool is warm
+    void release_clear_mesh()
+    {
+        cm_d.release(); cm_L.release(); cm_rho.release(); cm_lk.release(); cm_tri.release(); cm_seed.release();
+        cm_S = 0;
+    }
+    void release_all()
+    {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev_free) (void)hipEventDestroy(e);
+        ev.clear(); ev_free.clear();
+        rb.release(); QQ.release(); Hinv.release(); Hq.release();
+        M1n.release(); M2n.release(); Pt.release(); u_hist.release(); qu_hist.release();
+        F1.release(); F2.release(); Cq.release(); cost.release();
+        lim.release(); maxin.release(); margin.release(); x0.release(); qu.release(); dist.release();
+        grad.release(); Yg.release(); noise_row.release(); order.release(); okey.release(); order_user.release();
+        linkid.release(); pool_flag.release(); meshes_d.release(); st_cost.release(); st_done.release();
+        m_ends.release(); m_base.release(); m_shift.release(); m_tri.release(); m_near.release(); m_upper.release();
+        m_pd.release(); m_pnd.release(); m_pi.release(); release_clear_mesh();
+        stamps.release(); trace.release(); u_log.release(); soft_viol.release(); soft_n.release();
+    }
+};
+
+inline bool cfs_moving(const cfs_problem *p) { return p->motion == CFS_OBS_PER_WAYPOINT; }
+// obstacle rows per problem in every obs array the handle reads: nobs (static) | H x nobs (per waypoint)
+inline size_t cfs_obs_rows(const cfs_problem *p) { return (size_t)p->d.nobs * (cfs_moving(p) ? (size_t)p->d.H : 1); }
+inline int cfs_check_batch(const cfs_problem *p, int B)
+{
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (B < 1 || B > p->d.max_batch) return cfs_fail(CFS_ERR_INVALID_ARG, "B=%d outside 1..max_batch=%d", B, p->d.max_batch);
+    return CFS_SUCCESS;
+}
+
+// ---- clearance audits (cfs_clear.hip, cfs_clear_mesh.hip): the arrays of one call, host or device ----------------------------------
+struct ClearArrays {
+    const double *x_, *u, *xR1, *obs;
+    double *dist_wp, *dist_path, *dist_lower, *t_path;
+    int *link_path, *tri_path;                           // tri_path: the mesh audit only
+};
+// what all four entries refuse, in one order; mesh: the handle must have meshes (otherwise: must have none) and tri_path is an output
+int cfs_check_clearance(const cfs_problem *p, int B, int substeps, const ClearArrays &a, bool mesh);
+// cfs_clearance's kernel on the first nline obstacle rows and output columns of the handle
+hipError_t cfs_launch_clearance_lines(const cfs_problem *p, int B, int substeps, int nline, const ClearArrays &a, hipStream_t s);
+// the host-array entry of either audit: stages the arrays, calls the _device entry on the NULL stream, copies back
+int cfs_clearance_host(cfs_problem *p, int B, int substeps, const ClearArrays &h, bool mesh);

@@ -50,7 +50,6 @@
 #include "cfs_host.h"
 #include <cmath>
 #include <cstring>
-#include <vector>
 
 namespace {
 
@@ -278,39 +277,58 @@ size_t rrt_mesh_lds_bytes(int nj, int max_iter, int variant)
     return b;
 }
 
+namespace {
+template <int NJ, int MESH> hipError_t launch_rrt_kernel(size_t lds, const RrtArgs<MESH> &a, hipStream_t s)
+{
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((cfs_rrt_kernel<NJ, MESH>), dim3(a.P.S), dim3(WV), lds, s, a);
+    return hipGetLastError();
+}
+}  // namespace
+
 hipError_t launch_rrt_mesh(int nj, int variant, const RrtParams &p, const RrtMeshArgs &ma, hipStream_t s)
 {
+    if (variant != RRT_MESH_PER_LANE && variant != RRT_MESH_WAVE) return hipErrorInvalidValue;
     const size_t lds = rrt_mesh_lds_bytes(nj, p.max_iter, variant);
-    if (lds > 64 * 1024 || (variant != RRT_MESH_PER_LANE && variant != RRT_MESH_WAVE)) return hipErrorInvalidValue;
-    const RrtArgs<RRT_MESH_PER_LANE> aa{p, ma};
-    const RrtArgs<RRT_MESH_WAVE> ab{p, ma};
-#define RRT_MESH_LAUNCH(NJ_)                                                                                                   \
-    case NJ_:                                                                                                                  \
-        if (variant == RRT_MESH_PER_LANE) hipLaunchKernelGGL((cfs_rrt_kernel<NJ_, RRT_MESH_PER_LANE>), dim3(p.S), dim3(WV), lds, s, aa); \
-        else hipLaunchKernelGGL((cfs_rrt_kernel<NJ_, RRT_MESH_WAVE>), dim3(p.S), dim3(WV), lds, s, ab);                           \
-        break;
-    switch (nj) {
-        RRT_MESH_LAUNCH(2) RRT_MESH_LAUNCH(3) RRT_MESH_LAUNCH(4) RRT_MESH_LAUNCH(5) RRT_MESH_LAUNCH(6)
-    default: return hipErrorInvalidValue;
-    }
-#undef RRT_MESH_LAUNCH
-    return hipGetLastError();
+    return cfs_for_nj(nj, [&](auto N) {
+        constexpr int NJ = decltype(N)::value;
+        return variant == RRT_MESH_PER_LANE ? launch_rrt_kernel<NJ, RRT_MESH_PER_LANE>(lds, {p, ma}, s) : launch_rrt_kernel<NJ, RRT_MESH_WAVE>(lds, {p, ma}, s);
+    });
 }
 
 hipError_t launch_rrt(int nj, const RrtParams &p, hipStream_t s)
 {
-    const size_t lds = rrt_lds_bytes(nj, p.max_iter);
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    const RrtArgs<RRT_MESH_NONE> a{p};
-    switch (nj) {
-    case 2: hipLaunchKernelGGL((cfs_rrt_kernel<2, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
-    case 3: hipLaunchKernelGGL((cfs_rrt_kernel<3, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
-    case 4: hipLaunchKernelGGL((cfs_rrt_kernel<4, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
-    case 5: hipLaunchKernelGGL((cfs_rrt_kernel<5, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
-    case 6: hipLaunchKernelGGL((cfs_rrt_kernel<6, RRT_MESH_NONE>), dim3(p.S), dim3(WV), lds, s, a); break;
-    default: return hipErrorInvalidValue;
+    return cfs_for_nj(nj, [&](auto N) { return launch_rrt_kernel<decltype(N)::value, RRT_MESH_NONE>(rrt_lds_bytes(nj, p.max_iter), {p}, s); });
+}
+
+static_assert(CFS_RRT_MESH_PER_LANE == CFS_IK_MESH_PER_LANE && CFS_RRT_MESH_WAVE == CFS_IK_MESH_WAVE && CFS_RRT_MESH_SMALL_FRONTIER == CFS_IK_MESH_SMALL_FRONTIER,
+              "cfs_check_mesh_table reads the flags of both families");
+int cfs_check_mesh_table(int nobs, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int min_nmesh, int default_variant,
+                         RrtMeshArgs &ma, int &variant)
+{
+    variant = RRT_MESH_NONE;
+    memset(&ma, 0, sizeof ma);
+    if (nmesh < min_nmesh || nobs + nmesh > CFS_MAX_OBS)
+        return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d + nmesh %d outside %d..%d", nobs, nmesh, min_nmesh, CFS_MAX_OBS);
+    if (flags & ~(CFS_RRT_MESH_PER_LANE | CFS_RRT_MESH_WAVE | CFS_RRT_MESH_SMALL_FRONTIER)) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if ((flags & CFS_RRT_MESH_PER_LANE) && (flags & (CFS_RRT_MESH_WAVE | CFS_RRT_MESH_SMALL_FRONTIER)))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "CFS_RRT_MESH_PER_LANE excludes the other flags");
+    if (nmesh == 0) return CFS_SUCCESS;
+    if (!meshes || !D_mesh) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes / D_mesh must be given");
+    for (int j = 0; j < nmesh; ++j) {
+        if (!meshes[j]) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d is NULL", j);
+        if (!std::isfinite(D_mesh[j]) || !(D_mesh[j] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "D_mesh[%d] must be finite and > 0", j);
     }
-    return hipGetLastError();
+    for (int j = 0; j < nmesh; ++j) {
+        if (meshes[j]->device != cfs_current_device())
+            return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d lives on device %d, the current device is %d", j, meshes[j]->device, cfs_current_device());
+        ma.m[j].nodes = meshes[j]->nodes_d; ma.m[j].tri = meshes[j]->tri_d; ma.m[j].nt = meshes[j]->nt;
+        ma.m[j].thr = D_mesh[j] > 0.0001 ? D_mesh[j] : 0.0001;                         // dist_arm_surf_200i.m:22-24 folded into the threshold
+    }
+    ma.nmesh = nmesh;
+    variant = (flags & CFS_RRT_MESH_PER_LANE) ? RRT_MESH_PER_LANE : (flags & (CFS_RRT_MESH_WAVE | CFS_RRT_MESH_SMALL_FRONTIER)) ? RRT_MESH_WAVE : default_variant;
+    ma.cap = (flags & CFS_RRT_MESH_SMALL_FRONTIER) ? RRT_FRONTIER_SMALL : RRT_FRONTIER_CAP;
+    return CFS_SUCCESS;
 }
 
 // ---- C ABI (include/cfs_hip.h, "RRT / RRT*") -----------------------------------------------------------------------------------
@@ -332,28 +350,11 @@ int check_rrt(const cfs_rrt_desc *d, int S)
     return CFS_SUCCESS;
 }
 
-// the meshes of a cfs_rrt_grow_mesh* call -> kernel argument + variant; nothing is launched or allocated here
+// cfs_check_mesh_table, then what only the tree kernels need: the tree and the variant's mesh scratch share the 64 KB of LDS
 int check_rrt_mesh(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, RrtMeshArgs &ma, int &variant)
 {
-    variant = RRT_MESH_NONE;
-    memset(&ma, 0, sizeof ma);
-    if (nmesh < 0 || d->nobs + nmesh > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d + nmesh %d outside 0..%d", d->nobs, nmesh, CFS_MAX_OBS);
-    if (flags & ~(CFS_RRT_MESH_PER_LANE | CFS_RRT_MESH_WAVE | CFS_RRT_MESH_SMALL_FRONTIER)) return cfs_fail(CFS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-    if ((flags & CFS_RRT_MESH_PER_LANE) && (flags & (CFS_RRT_MESH_WAVE | CFS_RRT_MESH_SMALL_FRONTIER)))
-        return cfs_fail(CFS_ERR_INVALID_ARG, "CFS_RRT_MESH_PER_LANE excludes the other flags");
-    if (nmesh == 0) return CFS_SUCCESS;
-    if (!meshes || !D_mesh) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes / D_mesh must be given");
-    for (int j = 0; j < nmesh; ++j) {
-        if (!meshes[j]) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d is NULL", j);
-        if (!std::isfinite(D_mesh[j]) || !(D_mesh[j] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "D_mesh[%d] must be finite and > 0", j);
-        if (meshes[j]->device != cfs_current_device())
-            return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d lives on device %d, the current device is %d", j, meshes[j]->device, cfs_current_device());
-        ma.m[j].nodes = meshes[j]->nodes_d; ma.m[j].tri = meshes[j]->tri_d; ma.m[j].nt = meshes[j]->nt;
-        ma.m[j].thr = D_mesh[j] > 0.0001 ? D_mesh[j] : 0.0001;                         // dist_arm_surf_200i.m:22-24 folded into the threshold
-    }
-    ma.nmesh = nmesh;
-    variant = (flags & CFS_RRT_MESH_PER_LANE) ? RRT_MESH_PER_LANE : (flags & (CFS_RRT_MESH_WAVE | CFS_RRT_MESH_SMALL_FRONTIER)) ? RRT_MESH_WAVE : RRT_MESH_DEFAULT;
-    ma.cap = (flags & CFS_RRT_MESH_SMALL_FRONTIER) ? RRT_FRONTIER_SMALL : RRT_FRONTIER_CAP;
+    int rc = cfs_check_mesh_table(d->nobs, nmesh, meshes, D_mesh, flags, 0, RRT_MESH_DEFAULT, ma, variant);
+    if (rc) return rc;
     if (rrt_mesh_lds_bytes(d->nstate, d->max_iter, variant) > 64 * 1024)
         return cfs_fail(CFS_ERR_INVALID_ARG, "MAX_ITER %d does not fit next to the mesh scratch (%zu B of LDS, limit 65536)", d->max_iter,
                         rrt_mesh_lds_bytes(d->nstate, d->max_iter, variant));
@@ -374,8 +375,8 @@ int grow_device(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes,
     rc = check_rrt_mesh(d, nmesh, meshes, D_mesh, flags, ma, variant);
     if (rc) return rc;
     if (!out_complete(out)) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL output array");
-    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
+    rc = cfs_use_device(cfs_current_device());
+    if (rc) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     RrtParams P;
     memset(&P, 0, sizeof P);
@@ -403,56 +404,32 @@ int grow_host(const cfs_rrt_desc *d, int nmesh, const cfs_mesh *const *meshes, c
         if (rc) return rc;
     }
     if (!out_complete(out)) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL output array");
-    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
-    const size_t nj = d->nstate, N = (size_t)d->max_iter + 1, per = d->per_tree ? (size_t)S : 1;
-    std::vector<void *> bufs;
-    hipError_t err = hipSuccess;
-    auto up = [&](const void *h, size_t bytes) -> void * {
-        if (err != hipSuccess) return nullptr;
-        void *p = nullptr;
-        err = hipMalloc(&p, bytes ? bytes : 8);
-        if (err != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        if (h) err = hipMemcpy(p, h, bytes, hipMemcpyHostToDevice);
-        return p;
-    };
+    rc = cfs_use_device(cfs_current_device());
+    if (rc) return rc;
+    const size_t nj = d->nstate, N = (size_t)d->max_iter + 1, per = d->per_tree ? (size_t)S : 1, nS = S, nee = nS * d->max_iter * 3;
+    Stage st;
     cfs_rrt_desc dd = *d;
-    dd.x0 = (const double *)up(d->x0, per * nj * 8); dd.goal = (const double *)up(d->goal, per * nj * 8); dd.goal_th = (const double *)up(d->goal_th, per * nj * 8);
-    dd.region_g = (const double *)up(d->region_g, nj * 8); dd.region_s = (const double *)up(d->region_s, nj * 8);
-    dd.sample_off = (const double *)up(d->sample_off, nj * 8); dd.ratial = (const double *)up(d->ratial, nj * 8);
-    dd.obs = (const double *)up(d->obs, (size_t)d->nobs * 6 * 8); dd.D = (const double *)up(d->D, (size_t)d->nobs * 8);
-    if (d->uniforms) dd.uniforms = (const double *)up(d->uniforms, (size_t)S * d->ndraw * 8);
+    dd.x0 = st.up(d->x0, per * nj); dd.goal = st.up(d->goal, per * nj); dd.goal_th = st.up(d->goal_th, per * nj);
+    dd.region_g = st.up(d->region_g, nj); dd.region_s = st.up(d->region_s, nj); dd.sample_off = st.up(d->sample_off, nj); dd.ratial = st.up(d->ratial, nj);
+    dd.obs = st.up(d->obs, (size_t)d->nobs * 6); dd.D = st.up(d->D, (size_t)d->nobs);
+    if (d->uniforms) dd.uniforms = st.up(d->uniforms, nS * d->ndraw);
     cfs_rrt_out o;
     memset(&o, 0, sizeof o);
-    o.node_num = (int *)up(nullptr, (size_t)S * 4); o.fail = (int *)up(nullptr, (size_t)S * 4); o.route_len = (int *)up(nullptr, (size_t)S * 4);
-    o.parent = (int *)up(nullptr, S * N * 4); o.nodes = (double *)up(nullptr, S * N * nj * 8); o.total_dis = (double *)up(nullptr, S * N * 8);
-    o.route = (double *)up(nullptr, S * N * nj * 8);
-    if (out->all_ee) o.all_ee = (double *)up(nullptr, (size_t)S * d->max_iter * 3 * 8);
-    if (out->draws_used) o.draws_used = (long long *)up(nullptr, (size_t)S * 8);
-    if (out->proposals) o.proposals = (long long *)up(nullptr, (size_t)S * 8);
-    if (err == hipSuccess) err = hipMemset(o.parent, 0, S * N * 4);
-    if (err == hipSuccess) err = hipMemset(o.nodes, 0, S * N * nj * 8);
-    if (err == hipSuccess) err = hipMemset(o.total_dis, 0, S * N * 8);
-    if (err == hipSuccess) err = hipMemset(o.route, 0, S * N * nj * 8);
-    if (err == hipSuccess && o.all_ee) err = hipMemset(o.all_ee, 0, (size_t)S * d->max_iter * 3 * 8);
-    if (err == hipSuccess) {
-        rc = grow_device(&dd, nmesh, meshes, D_mesh, flags, S, &o, nullptr);
-        if (rc == CFS_SUCCESS) err = hipStreamSynchronize(nullptr);
-    }
-    auto down = [&](void *h, const void *dv, size_t bytes) { if (err == hipSuccess && h) err = hipMemcpy(h, dv, bytes, hipMemcpyDeviceToHost); };
-    if (rc == CFS_SUCCESS) {
-        down(out->node_num, o.node_num, (size_t)S * 4); down(out->fail, o.fail, (size_t)S * 4); down(out->route_len, o.route_len, (size_t)S * 4);
-        down(out->parent, o.parent, S * N * 4); down(out->nodes, o.nodes, S * N * nj * 8); down(out->total_dis, o.total_dis, S * N * 8);
-        down(out->route, o.route, S * N * nj * 8);
-        if (out->all_ee) down(out->all_ee, o.all_ee, (size_t)S * d->max_iter * 3 * 8);
-        if (out->draws_used) down(out->draws_used, o.draws_used, (size_t)S * 8);
-        if (out->proposals) down(out->proposals, o.proposals, (size_t)S * 8);
-    }
-    for (void *p : bufs) (void)hipFree(p);
+    o.node_num = st.out<int>(nS); o.fail = st.out<int>(nS); o.route_len = st.out<int>(nS);
+    o.parent = st.zeros<int>(nS * N); o.nodes = st.zeros<double>(nS * N * nj); o.total_dis = st.zeros<double>(nS * N);
+    o.route = st.zeros<double>(nS * N * nj);
+    if (out->all_ee) o.all_ee = st.zeros<double>(nee);
+    if (out->draws_used) o.draws_used = st.out<long long>(nS);
+    if (out->proposals) o.proposals = st.out<long long>(nS);
+    if (st.err != hipSuccess) return st.result("RRT staging");
+    rc = grow_device(&dd, nmesh, meshes, D_mesh, flags, S, &o, nullptr);
     if (rc) return rc;
-    if (err != hipSuccess) return cfs_fail(CFS_ERR_HIP, "RRT staging failed: %s", hipGetErrorString(err));
-    return CFS_SUCCESS;
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
+    st.down(out->node_num, o.node_num, nS); st.down(out->fail, o.fail, nS); st.down(out->route_len, o.route_len, nS);
+    st.down(out->parent, o.parent, nS * N); st.down(out->nodes, o.nodes, nS * N * nj); st.down(out->total_dis, o.total_dis, nS * N);
+    st.down(out->route, o.route, nS * N * nj);
+    st.down(out->all_ee, o.all_ee, nee); st.down(out->draws_used, o.draws_used, nS); st.down(out->proposals, o.proposals, nS);
+    return st.result("RRT staging");
 }
 }  // namespace
 
@@ -480,14 +457,5 @@ extern "C" int cfs_rrt_grow_mesh(const cfs_rrt_desc *d, int nmesh, const cfs_mes
 
 extern "C" int cfs_debug_rrt_frontier_overflows(unsigned long long *count, int reset)
 {
-    if (!count && !reset) return cfs_fail(CFS_ERR_INVALID_ARG, "nothing to do: count is NULL and reset is 0");
-    if (cfs_device_count() <= 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-    CFS_HIPCHK(hipSetDevice(cfs_current_device()));
-    CFS_HIPCHK(hipDeviceSynchronize());
-    if (count) CFS_HIPCHK(hipMemcpyFromSymbol(count, HIP_SYMBOL(g_rrt_frontier_overflows), sizeof *count));
-    if (reset) {
-        const unsigned long long zero = 0ull;
-        CFS_HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_rrt_frontier_overflows), &zero, sizeof zero));
-    }
-    return CFS_SUCCESS;
+    return cfs_frontier_overflows(&g_rrt_frontier_overflows, count, reset);
 }

@@ -141,6 +141,43 @@ def test_one_restart_at_theta_ref_converges_without_an_iteration(gpu, O):
         assert sol.cand_theta.shape == (3, restarts, 5)
 
 
+def test_one_target_one_restart_position_only_without_the_optional_outputs(gpu, O):
+    """cfs_ik_solve's staging at its edges: nobs = 0 (zero-length obs / D), T = 1, restarts = 1, use_axis = 0 (target_axis NULL), every
+    optional output NULL.  The restart starts at theta_ref, the pose of its own target: theta_ref comes back bit for bit, as above."""
+    import ctypes as C
+    from motionplanning_5d_m_amd import _lib
+    arm, lim, q, tp, ta = _targets(O, gpu, "M200i", 5, 1, seed=41)
+    slv = gpu.IKSolver(gpu.robotproperty2("M200i"), restarts=1, tol_pos=TOL, tol_axis=TOL)
+    d = slv._desc(False, 3, slv.obs, slv.D)
+    assert d.nobs == 0 and d.use_axis == 0 and d.restarts == 1
+    theta, status = np.full((1, 5), 7.0), np.full(1, 7, np.int32)
+    o = _lib.cfs_ik_out()
+    o.theta, o.status = theta.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)
+    assert not (o.selected or o.n_ok or o.err_pos or o.err_axis or o.clearance or o.cand_theta or o.cand_status or o.cand_iter)
+    tp1, tr1 = np.ascontiguousarray(tp[:1]), np.ascontiguousarray(q[:1])
+    _lib.check(_lib.lib().cfs_ik_solve(C.byref(d), 1, tp1.ctypes.data_as(C.c_void_p), None, tr1.ctypes.data_as(C.c_void_p), C.byref(o)))
+    assert status[0] == 0
+    np.testing.assert_array_equal(theta, q[:1])
+
+
+def test_tool_pose_of_one_configuration(gpu, O):
+    """cfs_tool_pose with N = 1, with jac NULL and with jac given: test_tool_pose_parity's reference and tolerances"""
+    arm, lim, q, tp, ta = _targets(O, gpu, "M200i", 5, 1, seed=21)
+    robot = gpu.robotproperty2("M200i")
+    pos, dr = gpu.tool_pose(robot, q)
+    assert pos.shape == (1, 3) and np.abs(pos - tp).max() <= 1e-12 and np.abs(dr - ta).max() <= 1e-12
+    pos_j, dr_j, jac = gpu.tool_pose(robot, q, want_jac=True)
+    np.testing.assert_array_equal(pos_j, pos)
+    np.testing.assert_array_equal(dr_j, dr)
+    h = 1e-6
+    for c in range(5):
+        e = np.zeros(5)
+        e[c] = h
+        pp, ap = arm.pose(q[0] + e)
+        pm, am = arm.pose(q[0] - e)
+        assert np.abs(jac[0, :, c] - np.concatenate([pp - pm, ap - am]) / (2 * h)).max() <= 1e-7
+
+
 def test_parity_with_the_cpu_restatement_in_axis_mode(gpu):
     P = R.PARITY
     lim = gpu.robotproperty2(P["robot"]).thetamax[:P["nj"]]

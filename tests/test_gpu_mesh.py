@@ -38,6 +38,22 @@ def test_point2surface_dis_against_brute_force(gpu, O):
     m.close()
 
 
+def test_one_segment_against_one_triangle_without_the_optional_outputs(gpu, O):
+    """cfs_mesh_segment_distance with n = 1 on a one-triangle mesh, points and tri NULL: the brute-force distance"""
+    import ctypes as C
+    tri = np.array([[[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.2]]])
+    O.mesh_register(7, tri)
+    m = gpu.Mesh(tri=tri)
+    for seg in ([0.2, 0.3, 0.5, 0.9, 0.8, 0.7], [0.2, 0.2, -0.5, 0.3, 0.3, 0.6], [2.0, 2.0, 1.0, 2.0, 2.0, 1.0]):   # off, piercing, a point
+        seg = np.array([seg])
+        dis = np.full(1, 7.0)
+        gpu._lib.check(m._lib.cfs_mesh_segment_distance(m._h, 1, seg.ctypes.data_as(C.c_void_p), dis.ctypes.data_as(C.c_void_p), None, None))
+        od, _, _ = O.mesh_seg_distance(7, seg)
+        assert abs(dis[0] - od[0]) < TOL_DIST
+        np.testing.assert_array_equal(dis, m.point2surface_dis(seg)[0])      # and what the call with every output gives
+    m.close()
+
+
 def test_stl_loader_and_degenerate_inputs(gpu, O, tmp_path):
     M = gpu.mesh
     tri = np.concatenate([M.cylinder_mesh((3.6, 8.8), 0.08, 0.0, 0.9, nseg=16, nring=3),

@@ -134,6 +134,38 @@ def test_device_rrt_generator_per_tree_goals_and_exhaustion(gpu, O):
 
 
 @pytest.mark.gpu
+def test_one_short_tree_in_an_empty_cell_without_the_optional_outputs(gpu, O):
+    """cfs_rrt_grow's staging at its edges: nobs = 0 (zero-length obs / D), S = 1, MAX_ITER = 8, all_ee / draws_used / proposals
+    NULL.  The tree is the oracle's bit for bit, as in test_device_rrt_trees_match_oracle_node_for_node."""
+    import ctypes as C
+    from motionplanning_5d_m_amd import _lib
+    from oracle import rrt_oracle as R
+    pobs, s, g, region_g, region_s, off = gpu.RRTstar_problem()
+    planner = gpu.RRT_FANUC([], s, g, region_g, region_s, off, "M200i", "RRT")
+    planner.MAX_ITER = 8
+    N, nj = planner.MAX_ITER + 1, 5
+    U = np.ascontiguousarray(np.random.default_rng(1000).random((1, 6 * 8 * N)))
+    d, keep = planner._desc(lambda v: np.ascontiguousarray(np.asarray(v, float)))
+    assert d.nobs == 0
+    d.uniforms, d.ndraw = U.ctypes.data_as(C.c_void_p), U.shape[1]
+    r = dict(node_num=np.full(1, -7, np.int32), fail=np.full(1, -7, np.int32), route_len=np.full(1, -7, np.int32), parent=np.full((1, N), -7, np.int32),
+             nodes=np.full((1, N, nj), 7.0), total_dis=np.full((1, N), 7.0), route=np.full((1, N, nj), 7.0))
+    o = _lib.cfs_rrt_out()
+    for k, v in r.items():
+        setattr(o, k, v.ctypes.data_as(C.c_void_p))
+    assert not o.all_ee and not o.draws_used and not o.proposals
+    _lib.check(_lib.lib().cfs_rrt_grow(C.byref(d), 1, C.byref(o)))
+    robot, _, x0, goal, rg, rs, ratial = _setup(O)
+    w = R.find_route(robot, [], x0, goal, goal, rg, rs, np.zeros(5), ratial, R.ArrayRng(U[0]), "RRT", max_iter=planner.MAX_ITER)
+    n, L = int(r["node_num"][0]), int(r["route_len"][0])
+    assert n == w["node_num"] == N and int(r["fail"][0]) == w["fail_code"] == 1      # eight proposals do not reach the goal
+    np.testing.assert_array_equal(np.concatenate([r["parent"][0, :n, None].astype(float), r["nodes"][0, :n]], axis=1).T, w["all_nodes"])
+    np.testing.assert_array_equal(r["total_dis"][0, :n], w["total_dis"])
+    np.testing.assert_array_equal(r["route"][0, :L].T, w["route"])
+    assert (r["route"][0, L:] == 0).all()                                             # rows beyond the route are zero-filled
+
+
+@pytest.mark.gpu
 def test_ragged_routes_to_cfs_terms(gpu, O):
     """cfs_build_terms_from_ragged_routes_device: routes of different lengths, as the device RRT leaves them, resampled to
     H + 1 = 41 points (RRTstar_CFS.m:94-100) and turned into (x_init, xR1, ff, caug) on the device, against the oracle's
