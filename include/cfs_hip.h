@@ -667,6 +667,84 @@ int cfs_ik_solve_mesh_device(const cfs_ik_desc *d, int nmesh, const cfs_mesh *co
 int cfs_tool_pose(const cfs_robot *robot, int njoint, const double *tool, const double *tool_axis, int N, const double *theta,
                   double *pos, double *dir, double *jac);
 
+/* ---- Cartesian paths ----------------------------------------------------------------------------------
+ * "inverse kinematics" above orients the tool at a goal; this entry moves it there along a straight line.  For T targets at once,
+ * and for up to 64 start configurations per target (the candidates: cfs_ik_out.cand_theta with cand_status is accepted as it is),
+ * it traces the straight tool line from every start's own pose to the target in K steps and keeps, per target, the start nearest
+ * to a reference configuration whose line completes inside the joint limits, without a joint jump and free of the line obstacles.
+ * No handle.  pose, residual, Jacobian, steps 1-8, the collision rule (clearance < 0) and the cost are those of "inverse kinematics",
+ * word for word; fields of cfs_cart_desc that cfs_ik_desc also has keep their meaning.
+ * One wavefront per target, one lane per candidate r = 0..candidates-1, start_r = start[t][r]:
+ *   - no start: a coordinate of start_r is not finite or lies outside [lo, hi], or start_state is given and start_state[t][r] != 0:
+ *     state 5, end;
+ *   - (p0, a0) = pose(start_r); theta_0 = start_r; if theta_0 collides: state 2 with 0 steps done, end;
+ *   - for k = 1..K, with s = k/K (K = steps):
+ *       p_k = p0 + s*(target_pos - p0);  use_axis = 1: a_k = b/|b|, b = (1-s)*a0 + s*target_axis (every target_axis row is normalised
+ *       on entry); |b| <= 1e-6 (or not finite): state 3, end;
+ *       steps 1-8 of "inverse kinematics" towards (p_k, a_k), starting at theta_{k-1} with lambda = 1e-2 and it = 0; convergence is
+ *       tested before every step, so a point that is already on the line costs 0 iterations;
+ *       step 3 (it == max_iter): state 1, end;  step 1 or 4 failing: state 3, end;
+ *       otherwise theta_k = the converged configuration; max_c |theta_k,c - theta_{k-1},c| > max_joint_step: state 4, end;
+ *       otherwise theta_k collides: state 2, end;  otherwise step k is done;
+ *   - step K done: state 0.
+ * States of a candidate (cand_status): 0 complete | 1 a step did not converge | 2 collision | 3 numeric | 4 joint jump | 5 no start.
+ * Per target: among the candidates in state 0 the one with the smallest sum_c weight_c*((start_c - theta_ref_c)^2) wins -- the cost
+ * of "inverse kinematics" on the START, plain IEEE products and sums in joint order --, ties to the lowest candidate (a wave
+ * reduction on (cost, lane), no atomics; a cost that is not finite puts the candidate in state 3).  status: 0 solved | 1 some
+ * candidate had a start but none completed | 2 no candidate had a start.
+ * theta = the winner's start; path = the winner's theta_0..theta_K; selected = the winner or -1; n_ok = candidates in state 0;
+ * n_done = the largest number of steps any candidate completed; clearance = the minimum of min_j (d_j - D_j) over the winner's K+1
+ * configurations (+inf when nobs = 0).  Rows of targets with status != 0 hold NaN in theta, path and clearance, and selected = -1.
+ * cand_done = steps the candidate completed; cand_iter = its iterations summed over the steps; cand_end = the last configuration it
+ * reached or tried (theta_K; where the failing step's iteration ended; the theta_k that jumped or collides; NaN in state 5);
+ * cand_path = its accepted configurations theta_0..theta_cand_done and NaN in every later row (every row is NaN in state 5 and for
+ * a start that collides).  A target's results depend on neither T nor its position in the batch.
+ * The collision rule is evaluated at the K+1 configurations, not between them.
+ * CFS_ERR_INVALID_ARG, nothing written: everything cfs_ik_solve refuses about the shared fields (a NULL descriptor, out, out->theta
+ * or out->status; a robot / njoint cfs_dist_arm refuses or njoint < 2; use_axis not 0 / 1; max_iter outside 1..1000; nobs outside
+ * 0..CFS_MAX_OBS; tolerances, tool, lo, hi, weight that are not finite, lo >= hi, weight <= 0, tol <= 0; a tool_axis that is not
+ * finite or (use_axis = 1) zero; T < 1; NULL target_pos or theta_ref; use_axis = 1 with a NULL target_axis; nobs > 0 with NULL obs or
+ * D); candidates outside 1..64; steps outside 1..256; a max_joint_step that is not finite and > 0; a NULL start; in cfs_cart_path,
+ * whose arrays the host can read: a non-finite target_pos, target_axis, theta_ref, obs or D, a zero target_axis row (start is NOT
+ * checked: a bad start is state 5); in cfs_cart_path_device: out->path without out->cand_path (path is gathered from cand_path, the
+ * launch's workspace, and the device entry allocates nothing; cfs_cart_path stages one itself).
+ * cfs_cart_path: HOST pointers throughout, synchronises.  cfs_cart_path_device: lo, hi, weight stay HOST pointers; obs, D, start,
+ * start_state, target_pos, target_axis, theta_ref and every array of `out` are DEVICE pointers; enqueued on `stream`, no
+ * synchronisation.  A non-finite value in a device array ends the candidates that read it in state 3 (start: state 5). */
+typedef struct cfs_cart_desc {
+    cfs_robot robot;
+    int njoint;                 /* 2..6: the chain of cfs_dist_arm for robot.kind                                        */
+    double tool[3];             /* a point in the frame of link njoint                                                   */
+    double tool_axis[3];        /* a direction in the same frame (normalised on entry)                                   */
+    int use_axis;               /* 0: position only (3 rows) | 1: position + direction (6 rows)                          */
+    const double *lo, *hi;      /* njoint each, finite, lo < hi                                                          */
+    const double *weight;       /* njoint, > 0, or NULL = ones: the norm of "nearest to theta_ref"                       */
+    int candidates;             /* R, 1..64, one lane each                                                               */
+    int steps;                  /* K, 1..256 line points after the start                                                 */
+    int max_iter;               /* 1..1000, per step                                                                     */
+    double max_joint_step;      /* rad, finite, > 0: the largest move of a joint between two line points                 */
+    double tol_pos, tol_axis;   /* metres / norm of the direction difference; finite, > 0                                */
+    int nobs;                   /* 0..CFS_MAX_OBS line obstacles                                                         */
+    const double *obs;          /* nobs x 6: [obs{j}.l(:,1); obs{j}.l(:,2)]                                              */
+    const double *D;            /* nobs: obs{j}.D (Lib/RRT_FANUC.m:174)                                                  */
+} cfs_cart_desc;
+typedef struct cfs_cart_out {
+    double *theta;              /* T x njoint                                                                            */
+    int *status;                /* T                                                                                     */
+    double *path;               /* T x (steps+1) x njoint (may be NULL)                                                  */
+    int *selected, *n_ok, *n_done;            /* T (may be NULL)                                                         */
+    double *clearance;          /* T (may be NULL)                                                                       */
+    int *cand_status, *cand_done, *cand_iter; /* T x candidates (may be NULL)                                            */
+    double *cand_end;           /* T x candidates x njoint (may be NULL)                                                 */
+    double *cand_path;          /* T x candidates x (steps+1) x njoint (may be NULL)                                     */
+} cfs_cart_out;
+/* start: T x candidates x njoint; start_state: T x candidates or NULL (= every start is used); target_pos: T x 3; target_axis: T x 3
+ * (read when use_axis = 1; may be NULL otherwise); theta_ref: T x njoint */
+int cfs_cart_path(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
+                  const double *target_axis, const double *theta_ref, const cfs_cart_out *out);
+int cfs_cart_path_device(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
+                         const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream);
+
 /* ---- developer / test entry points -------------------------------------------------------------------
  * No caller of the path needs these; they exist so that every shortcut the solver takes can be switched off and compared
  * under pytest (tests/test_gpu_shortcuts.py), and for the cycle-stamp / step-trace probes under tools/.  All state is per

@@ -35,6 +35,8 @@ INFEASIBLE = {"stop": 0, "soften": 1}          # cfs_infeasible_policy
 OBSTACLES = {"static": 0, "per_waypoint": 1}    # cfs_obstacle_motion
 IK_STATUS = {0: "SOLVED", 1: "NOT_CONVERGED", 2: "IN_COLLISION"}                       # cfs_ik_out.status
 IK_CAND_STATUS = {0: "CONVERGED", 1: "MAX_ITER", 2: "IN_COLLISION", 3: "NUMERIC"}      # cfs_ik_out.cand_status
+CART_STATUS = {0: "SOLVED", 1: "NO_COMPLETE_LINE", 2: "NO_START"}                      # cfs_cart_out.status
+CART_CAND_STATUS = {0: "COMPLETE", 1: "MAX_ITER", 2: "IN_COLLISION", 3: "NUMERIC", 4: "JOINT_JUMP", 5: "NO_START"}   # cfs_cart_out.cand_status
 
 
 class CfsError(RuntimeError):
@@ -190,6 +192,45 @@ class cfs_ik_out(C.Structure):
     ]
 
 
+class cfs_cart_desc(C.Structure):
+    _fields_ = [
+        ("robot", cfs_robot),
+        ("njoint", C.c_int),
+        ("tool", C.c_double * 3),
+        ("tool_axis", C.c_double * 3),
+        ("use_axis", C.c_int),
+        ("lo", C.c_void_p),
+        ("hi", C.c_void_p),
+        ("weight", C.c_void_p),
+        ("candidates", C.c_int),
+        ("steps", C.c_int),
+        ("max_iter", C.c_int),
+        ("max_joint_step", C.c_double),
+        ("tol_pos", C.c_double),
+        ("tol_axis", C.c_double),
+        ("nobs", C.c_int),
+        ("obs", C.c_void_p),
+        ("D", C.c_void_p),
+    ]
+
+
+class cfs_cart_out(C.Structure):
+    _fields_ = [
+        ("theta", C.c_void_p),
+        ("status", C.c_void_p),
+        ("path", C.c_void_p),
+        ("selected", C.c_void_p),
+        ("n_ok", C.c_void_p),
+        ("n_done", C.c_void_p),
+        ("clearance", C.c_void_p),
+        ("cand_status", C.c_void_p),
+        ("cand_done", C.c_void_p),
+        ("cand_iter", C.c_void_p),
+        ("cand_end", C.c_void_p),
+        ("cand_path", C.c_void_p),
+    ]
+
+
 # every symbol include/cfs_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -257,6 +298,8 @@ SYMBOLS = [
     ("cfs_ik_solve_mesh", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out)]),
     ("cfs_ik_solve_mesh_device", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out), _P]),
     ("cfs_debug_ik_frontier_overflows", C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    ("cfs_cart_path", C.c_int, [C.POINTER(cfs_cart_desc), C.c_int, _P, _P, _P, _P, _P, C.POINTER(cfs_cart_out)]),
+    ("cfs_cart_path_device", C.c_int, [C.POINTER(cfs_cart_desc), C.c_int, _P, _P, _P, _P, _P, C.POINTER(cfs_cart_out), _P]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)

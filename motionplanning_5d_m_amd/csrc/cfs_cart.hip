@@ -1,0 +1,395 @@
+// cfs_cart.hip -- batched straight-line tool paths from IK candidates (include/cfs_hip.h, "Cartesian paths").
+//
+// The reference has no Cartesian moves: its drivers plan between joint vectors.  A pick ends with a straight tool move from a
+// pre-grasp pose into the grasp (a controller's LIN move); this unit asks, for every configuration inverse kinematics found for the
+// pre-grasp, whether that move exists inside the joint ranges, without a joint flip and free of the line obstacles, and keeps per
+// target the candidate nearest to a reference configuration whose line completes.
+//
+// MI355X mapping: cfs_ik_kernel's.  One 64-lane wavefront owns one target, one lane one candidate; four targets per 256-thread
+// workgroup; the robot, the obstacle rows and their margins are staged once per workgroup in LDS behind the only block barrier.  A
+// lane's path is a sequential chain (step k starts where step k-1 ended) and lanes need different iteration counts per step, so the
+// kernel is ONE loop whose pass is one damped least-squares iteration of the lane's current step (cfs_ik_dev.h: the contract's steps
+// 1-8 literally); finishing a step (joint jump, collision, the next line point, lambda and `it` reset) is bookkeeping at the head of
+// the same pass.  A wave therefore runs max over its lanes of the lanes' totals, not the sum over the steps of per-step maxima; the
+// arithmetic of a lane is that of the nested form (for every step: restart from theta_{k-1}).  Lanes that have ended idle under the
+// EXEC mask until a ballot says that none is running; the selection is IK's wave argmin on (cost, lane) by xor shuffles.  No atomics,
+// no block barrier after the staging, no host round trip.  Everything is fp64; every loop over joints is unrolled at compile time.
+#include "cfs_ik_dev.h"
+#include "cfs_host.h"
+#include <cmath>
+#include <cstring>
+
+namespace {
+
+constexpr int WV = 64;
+constexpr int CART_WAVES = 4;                                 // targets per workgroup
+constexpr int CART_MAX_STEPS = 256;
+constexpr double CART_AXIS_MIN = 1e-6;                        // |(1-s)*a0 + s*target_axis| at or below this: the interpolated axis is undefined
+
+struct CartParams {
+    DevRobot rb;                                              // by value, as in IkParams: no device allocation in the _device entry
+    int T, R, K, nobs, use_axis, max_iter;
+    double tool[3], axis[3];                                  // axis normalised on the host
+    double lo[6], hi[6], w[6];
+    double tol_pos, tol_axis, max_joint_step;
+    const double *obs, *D;                                    // nobs x 6, nobs
+    const double *start;                                      // T x R x NJ
+    const int *start_state;                                   // T x R or null
+    const double *target_pos, *target_axis, *theta_ref;       // T x 3, T x 3 (use_axis), T x NJ
+    double *theta;                                            // T x NJ
+    int *status;                                              // T
+    double *path;                                             // T x (K+1) x NJ
+    int *selected, *n_ok, *n_done;                            // T
+    double *clearance;                                        // T
+    int *cand_status, *cand_done, *cand_iter;                 // T x R
+    double *cand_end, *cand_path;                             // T x R x NJ, T x R x (K+1) x NJ
+};
+
+template <int NJ>
+__global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartParams P)
+{
+    __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
+    __shared__ double s_obs[CFS_MAX_OBS * 6];
+    __shared__ double s_D[CFS_MAX_OBS];
+    {
+        const double *src = reinterpret_cast<const double *>(&P.rb);
+        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += WV * CART_WAVES) s_rb[e] = src[e];
+        for (int e = threadIdx.x; e < P.nobs * 6; e += WV * CART_WAVES) s_obs[e] = P.obs[e];
+        for (int e = threadIdx.x; e < P.nobs; e += WV * CART_WAVES) s_D[e] = P.D[e];
+    }
+    __syncthreads();                                          // the only block barrier: whole waves may leave after it
+    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    const int lane = threadIdx.x % WV, t = blockIdx.x * CART_WAVES + threadIdx.x / WV;
+    if (t >= P.T) return;
+    const bool use_axis = P.use_axis != 0;
+    const bool active = lane < P.R;                           // lanes >= candidates never run and enter the reductions with neutral values
+    const size_t row = (size_t)t * P.R + (active ? lane : 0);
+    const size_t prow = row * (size_t)(P.K + 1);              // the candidate's first row of cand_path
+
+    double th[NJ];
+    int st = 5;                                               // -1: running
+    if (active) {
+        bool ok = !P.start_state || P.start_state[row] == 0;
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) {
+            th[c] = P.start[row * NJ + c];
+            ok = ok && th[c] >= P.lo[c] && th[c] <= P.hi[c];  // false for a NaN and for +-inf
+        }
+        if (ok) st = -1;
+    }
+    if (st != -1) {
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) th[c] = __builtin_nan("");
+    }
+
+    // step 0 is the start itself: its "line point" is its own pose, so its residual is zero and the first pass books it (collision
+    // test, row 0 of the path) like every later step
+    double p0[3] = {0.0, 0.0, 0.0}, a0[3] = {0.0, 0.0, 0.0}, pk[3], ak[3] = {0.0, 0.0, 0.0}, prev[NJ], r[6], F = 0.0, A[NJ * NJ], g[NJ];
+    double lam = IK_LAMBDA0, cmin = INFINITY;
+    int it = 0, itsum = 0, k = 0, done = 0, nrow = 0;         // nrow: rows of cand_path written (accepted configurations)
+#pragma unroll
+    for (int q = 0; q < 6; ++q) r[q] = 0.0;
+#pragma unroll
+    for (int c = 0; c < NJ; ++c) { prev[c] = th[c]; g[c] = 0.0; }
+#pragma unroll
+    for (int q = 0; q < NJ * NJ; ++q) A[q] = 0.0;
+    if (st < 0) {
+        double tw[NJ * 6];
+        ik_pose<NJ>(rb, P.tool, P.axis, th, p0, a0, tw);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { pk[q] = p0[q]; ak[q] = a0[q]; }
+
+    for (;;) {
+        // ---- head of the pass: a step whose point is reached is booked and the next one set up -----------------------------
+        if (st < 0) {
+            const double ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+            if (!(F < INFINITY)) st = 3;                                                        // step 1
+            else if (ep <= P.tol_pos && (!use_axis || ea <= P.tol_axis)) {                      // step 2: theta_k = th
+                if (k > 0) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NJ; ++c) s = fabs(th[c] - prev[c]) > s ? fabs(th[c] - prev[c]) : s;
+                    if (s > P.max_joint_step) st = 4;
+                }
+                if (st < 0) {
+                    const double c = ik_clearance<NJ>(rb, th, P.nobs, s_obs, s_D);
+                    if (!(c >= 0.0)) st = 2;
+                    else if (c < cmin) cmin = c;
+                }
+                if (st < 0) {
+                    done = k;
+                    nrow = k + 1;
+                    if (P.cand_path) {
+#pragma unroll
+                        for (int c = 0; c < NJ; ++c) P.cand_path[(prow + k) * NJ + c] = th[c];
+                    }
+                    if (k == P.K) st = 0;
+                    else {
+                        ++k;
+                        // the target is read again at every step rather than held: twelve registers the iteration needs
+                        const double s = (double)k / (double)P.K;
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) pk[q] = p0[q] + s * (P.target_pos[(size_t)t * 3 + q] - p0[q]);
+                        if (use_axis) {
+                            double ta[3], b[3];
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) ta[q] = P.target_axis[(size_t)t * 3 + q];
+                            const double tn = sqrt(ta[0] * ta[0] + ta[1] * ta[1] + ta[2] * ta[2]);
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) b[q] = (1.0 - s) * a0[q] + s * (ta[q] / tn);
+                            const double n = sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+                            if (!(n > CART_AXIS_MIN)) st = 3;
+                            else { ak[0] = b[0] / n; ak[1] = b[1] / n; ak[2] = b[2] / n; }
+                        }
+                        if (st < 0) {                                                           // the restart of step k from theta_{k-1}
+                            double p[3], a[3], tw[NJ * 6];
+#pragma unroll
+                            for (int c = 0; c < NJ; ++c) prev[c] = th[c];
+                            ik_pose<NJ>(rb, P.tool, P.axis, th, p, a, tw);
+                            ik_residual(p, a, pk, ak, use_axis, r, &F);
+                            ik_normal<NJ>(tw, p, a, r, use_axis, A, g);
+                            lam = IK_LAMBDA0;
+                            it = 0;
+                        }
+                    }
+                }
+            }
+        }
+        if (__ballot(st < 0) == 0ull) break;
+        // ---- one iteration of the current step (a step set up above is tested before it iterates) ---------------------------
+        if (st < 0) {
+            const double ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+            const bool conv = ep <= P.tol_pos && (!use_axis || ea <= P.tol_axis);
+            if (!(F < INFINITY)) st = 3;                                                        // step 1
+            else if (conv) {}                                                                   // step 2: the next pass books it
+            else if (it >= P.max_iter) st = 1;                                                  // step 3
+            else {
+                double delta[NJ], trial[NJ];
+                if (!ik_solve_step<NJ>(A, g, lam, delta)) st = 3;                               // step 4
+                else {
+                    double s = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NJ; ++c) s = fabs(delta[c]) > s ? fabs(delta[c]) : s;
+                    const double sc = s > IK_STEP_CAP ? IK_STEP_CAP / s : 1.0;                  // step 5
+#pragma unroll
+                    for (int c = 0; c < NJ; ++c) {
+                        const double x = th[c] + (s > IK_STEP_CAP ? delta[c] * sc : delta[c]);
+                        trial[c] = x < P.lo[c] ? P.lo[c] : (x > P.hi[c] ? P.hi[c] : x);        // step 6
+                    }
+                    double p2[3], a2[3], tw2[NJ * 6], r2[6], F2;
+                    ik_pose<NJ>(rb, P.tool, P.axis, trial, p2, a2, tw2);
+                    ik_residual(p2, a2, pk, ak, use_axis, r2, &F2);
+                    if (F2 < F) {                                                               // step 7
+#pragma unroll
+                        for (int c = 0; c < NJ; ++c) th[c] = trial[c];
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) r[q] = r2[q];
+                        F = F2;
+                        ik_normal<NJ>(tw2, p2, a2, r2, use_axis, A, g);
+                        lam = lam / 10.0 > IK_LAMBDA_MIN ? lam / 10.0 : IK_LAMBDA_MIN;
+                    } else {
+                        lam = lam * 10.0 < IK_LAMBDA_MAX ? lam * 10.0 : IK_LAMBDA_MAX;
+                    }
+                    ++it;                                                                       // step 8
+                    ++itsum;
+                }
+            }
+        }
+    }
+
+    // ---- cost of the START, candidate outputs, selection -------------------------------------------------------------------
+    const double nan = __builtin_nan("");
+    double cost = INFINITY;
+    if (st == 0) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) {                        // w*(d*d), summed in joint order, no FMA: the contract's cost to the last bit
+            const double dlt = P.start[row * NJ + c] - P.theta_ref[(size_t)t * NJ + c];
+            s = __dadd_rn(s, __dmul_rn(P.w[c], __dmul_rn(dlt, dlt)));
+        }
+        if (s < INFINITY) cost = s; else st = 3;
+    }
+    if (active) {
+        if (P.cand_status) P.cand_status[row] = st;
+        if (P.cand_done) P.cand_done[row] = done;
+        if (P.cand_iter) P.cand_iter[row] = itsum;
+        if (P.cand_end) {
+#pragma unroll
+            for (int c = 0; c < NJ; ++c) P.cand_end[row * NJ + c] = th[c];
+        }
+        if (P.cand_path) {
+            for (size_t e = (prow + nrow) * NJ; e < (prow + P.K + 1) * NJ; ++e) P.cand_path[e] = nan;
+        }
+    }
+    const int n_ok = __popcll(__ballot(st == 0));
+    const bool any_start = __ballot(st != 5) != 0ull;
+    double bc = cost;
+    int bl = lane, md = done;
+#pragma unroll
+    for (int m = 1; m < WV; m <<= 1) {
+        const double oc = __shfl_xor(bc, m, WV);
+        const int ol = __shfl_xor(bl, m, WV);
+        const int od = __shfl_xor(md, m, WV);
+        if (oc < bc || (oc == bc && ol < bl)) { bc = oc; bl = ol; }
+        if (od > md) md = od;
+    }
+    const bool ok = n_ok > 0;
+    if (ok ? lane == bl : lane == 0) {
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) P.theta[(size_t)t * NJ + c] = ok ? P.start[row * NJ + c] : nan;
+        P.status[t] = ok ? 0 : (any_start ? 1 : 2);
+        if (P.selected) P.selected[t] = ok ? lane : -1;
+        if (P.n_ok) P.n_ok[t] = n_ok;
+        if (P.n_done) P.n_done[t] = md;
+        if (P.clearance) P.clearance[t] = ok ? cmin : nan;
+    }
+    if (P.path) {
+        // the winner's rows of cand_path (the launch's workspace), copied by the whole wave: the fence makes the winner's stores
+        // visible to the other lanes of its wave
+        const size_t n = (size_t)(P.K + 1) * NJ;
+        double *dst = P.path + (size_t)t * n;
+        if (ok) {
+            __threadfence();
+            const double *src = P.cand_path + ((size_t)t * P.R + bl) * n;
+            for (size_t e = lane; e < n; e += WV) dst[e] = src[e];
+        } else {
+            for (size_t e = lane; e < n; e += WV) dst[e] = nan;
+        }
+    }
+}
+
+hipError_t launch_cart(int nj, const CartParams &p, hipStream_t s)
+{
+    return cfs_for_nj(nj, [&](auto N) {
+        hipLaunchKernelGGL(cfs_cart_kernel<decltype(N)::value>, dim3((p.T + CART_WAVES - 1) / CART_WAVES), dim3(WV * CART_WAVES), 0, s, p);
+        return hipGetLastError();
+    });
+}
+
+// ---- C ABI (include/cfs_hip.h, "Cartesian paths") --------------------------------------------------------------------------------
+bool finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+bool all_finite(const double *v, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+// everything of a call that is host memory in both entries; fills the by-value part of the kernel's parameter block
+int check_cart(const cfs_cart_desc *d, int T, const double *start, const double *target_pos, const double *target_axis, const double *theta_ref,
+               const cfs_cart_out *out, CartParams &P)
+{
+    if (!d) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL descriptor");
+    int rc = cfs_check_robot(&d->robot, d->njoint);
+    if (rc) return rc;
+    const int nj = d->njoint;
+    if (nj < 2) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", nj);
+    if (d->use_axis != 0 && d->use_axis != 1) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis must be 0 or 1, not %d", d->use_axis);
+    if (d->candidates < 1 || d->candidates > WV) return cfs_fail(CFS_ERR_INVALID_ARG, "candidates %d outside 1..%d", d->candidates, WV);
+    if (d->steps < 1 || d->steps > CART_MAX_STEPS) return cfs_fail(CFS_ERR_INVALID_ARG, "steps %d outside 1..%d", d->steps, CART_MAX_STEPS);
+    if (d->max_iter < 1 || d->max_iter > 1000) return cfs_fail(CFS_ERR_INVALID_ARG, "max_iter %d outside 1..1000", d->max_iter);
+    if (!(std::isfinite(d->max_joint_step) && d->max_joint_step > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "max_joint_step must be finite and > 0");
+    if (d->nobs < 0 || d->nobs > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d outside 0..%d", d->nobs, CFS_MAX_OBS);
+    if (d->nobs > 0 && (!d->obs || !d->D)) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be given");
+    if (!(std::isfinite(d->tol_pos) && d->tol_pos > 0.0 && std::isfinite(d->tol_axis) && d->tol_axis > 0.0))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "tol_pos / tol_axis must be finite and > 0");
+    if (!finite3(d->tool) || !finite3(d->tool_axis)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool / tool_axis must be finite");
+    const double an = std::sqrt(d->tool_axis[0] * d->tool_axis[0] + d->tool_axis[1] * d->tool_axis[1] + d->tool_axis[2] * d->tool_axis[2]);
+    if (d->use_axis && !(an > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool_axis is zero");
+    if (!d->lo || !d->hi) return cfs_fail(CFS_ERR_INVALID_ARG, "lo / hi must be given");
+    for (int c = 0; c < nj; ++c) {
+        if (!std::isfinite(d->lo[c]) || !std::isfinite(d->hi[c]) || !(d->lo[c] < d->hi[c]))
+            return cfs_fail(CFS_ERR_INVALID_ARG, "joint %d: lo / hi must be finite with lo < hi", c);
+        if (d->weight && !(std::isfinite(d->weight[c]) && d->weight[c] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "weight[%d] must be finite and > 0", c);
+    }
+    if (T < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "at least one target is needed");
+    if (!start || !target_pos || !theta_ref) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL start / target_pos / theta_ref");
+    if (d->use_axis && !target_axis) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis = 1 needs target_axis");
+    if (!out || !out->theta || !out->status) return cfs_fail(CFS_ERR_INVALID_ARG, "out, out->theta and out->status must be given");
+    memset(&P, 0, sizeof P);
+    cfs_build_dev_robot(d->robot, P.rb);
+    P.T = T; P.R = d->candidates; P.K = d->steps; P.nobs = d->nobs; P.use_axis = d->use_axis; P.max_iter = d->max_iter;
+    for (int q = 0; q < 3; ++q) { P.tool[q] = d->tool[q]; P.axis[q] = an > 0.0 ? d->tool_axis[q] / an : 0.0; }
+    for (int c = 0; c < nj; ++c) { P.lo[c] = d->lo[c]; P.hi[c] = d->hi[c]; P.w[c] = d->weight ? d->weight[c] : 1.0; }
+    P.tol_pos = d->tol_pos; P.tol_axis = d->tol_axis; P.max_joint_step = d->max_joint_step;
+    return CFS_SUCCESS;
+}
+
+void cart_point(CartParams &P, const double *obs, const double *D, const double *start, const int *start_state, const double *target_pos,
+                const double *target_axis, const double *theta_ref, const cfs_cart_out *o)
+{
+    P.obs = obs; P.D = D; P.start = start; P.start_state = start_state;
+    P.target_pos = target_pos; P.target_axis = target_axis; P.theta_ref = theta_ref;
+    P.theta = o->theta; P.status = o->status; P.path = o->path; P.selected = o->selected; P.n_ok = o->n_ok; P.n_done = o->n_done;
+    P.clearance = o->clearance; P.cand_status = o->cand_status; P.cand_done = o->cand_done; P.cand_iter = o->cand_iter;
+    P.cand_end = o->cand_end; P.cand_path = o->cand_path;
+}
+}  // namespace
+
+extern "C" int cfs_cart_path_device(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
+                                    const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream)
+{
+    static_assert(sizeof(CartParams) <= 4096, "the parameter block travels as a kernel argument");
+    CartParams P;
+    int rc = check_cart(d, T, start, target_pos, target_axis, theta_ref, out, P);
+    if (rc) return rc;
+    if (out->path && !out->cand_path)
+        return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_cart_path_device: out->path needs out->cand_path, the launch's workspace (nothing is allocated here)");
+    rc = cfs_use_device(cfs_current_device());
+    if (rc) return rc;
+    cart_point(P, d->obs, d->D, start, start_state, target_pos, target_axis, theta_ref, out);
+    const hipError_t e = launch_cart(d->njoint, P, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return cfs_fail(CFS_ERR_HIP, "Cartesian path launch failed: %s", hipGetErrorString(e));
+    return CFS_SUCCESS;
+}
+
+extern "C" int cfs_cart_path(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
+                             const double *target_axis, const double *theta_ref, const cfs_cart_out *out)
+{
+    CartParams P;
+    int rc = check_cart(d, T, start, target_pos, target_axis, theta_ref, out, P);
+    if (rc) return rc;
+    const size_t nj = d->njoint, R = d->candidates, K1 = (size_t)d->steps + 1, nobs = d->nobs, nT = T;
+    if (!all_finite(target_pos, nT * 3) || !all_finite(theta_ref, nT * nj)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_pos / theta_ref must be finite");
+    if (nobs && (!all_finite(d->obs, nobs * 6) || !all_finite(d->D, nobs))) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be finite");
+    if (d->use_axis) {
+        if (!all_finite(target_axis, nT * 3)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis must be finite");
+        for (int t = 0; t < T; ++t) {
+            const double *v = target_axis + (size_t)t * 3;
+            if (!(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis row %d is zero", t);
+        }
+    }
+    rc = cfs_use_device(cfs_current_device());
+    if (rc) return rc;
+    Stage st;
+    cfs_cart_out o;
+    memset(&o, 0, sizeof o);
+    const double *obs_d = st.up(d->obs, nobs * 6), *D_d = st.up(d->D, nobs), *s_d = st.up(start, nT * R * nj);
+    const int *ss_d = start_state ? st.up(start_state, nT * R) : nullptr;
+    const double *tp_d = st.up(target_pos, nT * 3);
+    const double *ta_d = d->use_axis ? st.up(target_axis, nT * 3) : nullptr;
+    const double *tr_d = st.up(theta_ref, nT * nj);
+    o.theta = st.out<double>(nT * nj); o.status = st.out<int>(nT);
+    if (out->path) o.path = st.out<double>(nT * K1 * nj);
+    if (out->selected) o.selected = st.out<int>(nT);
+    if (out->n_ok) o.n_ok = st.out<int>(nT);
+    if (out->n_done) o.n_done = st.out<int>(nT);
+    if (out->clearance) o.clearance = st.out<double>(nT);
+    if (out->cand_status) o.cand_status = st.out<int>(nT * R);
+    if (out->cand_done) o.cand_done = st.out<int>(nT * R);
+    if (out->cand_iter) o.cand_iter = st.out<int>(nT * R);
+    if (out->cand_end) o.cand_end = st.out<double>(nT * R * nj);
+    if (out->cand_path || out->path) o.cand_path = st.out<double>(nT * R * K1 * nj);           // also the workspace behind `path`
+    if (st.err == hipSuccess) {
+        cart_point(P, obs_d, D_d, s_d, ss_d, tp_d, ta_d, tr_d, &o);
+        st.err = launch_cart(d->njoint, P, nullptr);
+        if (st.err == hipSuccess) st.err = hipStreamSynchronize(nullptr);
+    }
+    st.down(out->theta, o.theta, nT * nj); st.down(out->status, o.status, nT); st.down(out->path, o.path, nT * K1 * nj);
+    st.down(out->selected, o.selected, nT); st.down(out->n_ok, o.n_ok, nT); st.down(out->n_done, o.n_done, nT);
+    st.down(out->clearance, o.clearance, nT);
+    st.down(out->cand_status, o.cand_status, nT * R); st.down(out->cand_done, o.cand_done, nT * R); st.down(out->cand_iter, o.cand_iter, nT * R);
+    st.down(out->cand_end, o.cand_end, nT * R * nj); st.down(out->cand_path, o.cand_path, nT * R * K1 * nj);
+    return st.result("Cartesian path staging or launch");
+}

@@ -26,6 +26,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import _lib
+from .cart import MAX_STEPS, CartesianPath
 from .ik import IKSolver
 from .rrt import RRT_FANUC
 from .robotproperty2 import robotproperty2
@@ -176,7 +177,8 @@ class RRTCFSPlanner:
         return t.contiguous()
 
     # ---- Cartesian goals ---------------------------------------------------------------------------------------------------
-    def plan_to_pose(self, x0, target_pos, target_axis=None, seed=0, ik_options=None, ik_meshes=False, **plan_kwargs):
+    def plan_to_pose(self, x0, target_pos, target_axis=None, seed=0, ik_options=None, ik_meshes=False, approach=None, approach_dir=None,
+                     approach_steps=16, approach_options=None, **plan_kwargs):
         """plan() towards Cartesian targets: one inverse-kinematics launch (ik.IKSolver.solve_device: theta_ref = x0, the planner's
         obstacles with their D -- its line obstacles, and with ik_meshes=True its mesh obstacles too --, the planner's joint_limits if
         it has them, else robot.thetamax; generator seed `seed`), then
@@ -190,7 +192,31 @@ class RRTCFSPlanner:
         ik_meshes: False (the default) keeps the line-only IK collision test, and a planner with mesh obstacles then refuses;
         True builds the solver from the planner's whole cell -- the lines with their D and the meshes with their D, the numbers
         cfs_rrt_grow_mesh_device gets -- so that goals are free of the meshes too (cfs_ik_solve_mesh_device).  On a planner without
-        meshes ik_meshes=True is the default path."""
+        meshes ik_meshes=True is the default path.
+        approach: None (the default: everything above, bit for bit) or a distance > 0 in metres, a number or (S,): the plan then ends
+        at a pre-grasp pose `approach` metres back from target_pos and the tool enters the grasp along a straight line
+        (cart.CartesianPath; needs target_axis; refused on a planner with mesh obstacles).  approach_dir: (S, 3), (3,) or None (=
+        target_axis): the world direction the tool travels on that line.  One IK launch at target_pos - approach*unit(dir) with its
+        candidates kept, one trace_device launch from every candidate (cand_theta / cand_status) to target_pos on the same stream
+        (approach_steps line points; approach_options: CartesianPath's max_iter, max_joint_step; tool, tolerances and weight are
+        ik_options'), then plan() with the winners' starts as goals: per slot the IK candidate nearest to x0 whose line completes.
+        The result gains approach_path (S, approach_steps+1, 5), grasp (= approach_path[:, -1]), approach_status (CartesianPath's
+        status), approach_clearance, approach_selected and ik_goal (IK's own winner); goal is the configuration planned to.  A slot
+        whose IK solved but whose approach did not gets status = -3 and is masked like -2."""
+        if approach is None:
+            if approach_dir is not None or approach_options is not None:
+                raise ValueError("approach_dir / approach_options need approach")
+        else:
+            if self._meshes:
+                raise ValueError("plan_to_pose(approach=...) on a planner with mesh obstacles: the straight-line trace reads line obstacles only")
+            if target_axis is None:
+                raise ValueError("approach needs target_axis: the tool keeps its direction along the line")
+            if approach_options is None:
+                approach_options = {}
+            if not isinstance(approach_options, dict) or set(approach_options) - {"max_iter", "max_joint_step"}:
+                raise ValueError("approach_options must be a dict of CartesianPath's max_iter, max_joint_step")
+        if not _is_int(approach_steps) or not 1 <= approach_steps <= MAX_STEPS:
+            raise ValueError(f"approach_steps must be an integer in 1..{MAX_STEPS}, not {approach_steps!r}")
         if not isinstance(ik_meshes, bool):
             raise ValueError(f"ik_meshes must be True or False, not {ik_meshes!r}")
         if self._meshes and not ik_meshes:
@@ -228,9 +254,27 @@ class RRTCFSPlanner:
         args = [conv(x0, "x0", self.nj), conv(target_pos, "target_pos", 3)]
         if target_axis is not None:
             args.append(conv(target_axis, "target_axis", 3, nonzero=True))
-        rows = {a.shape[0] for a in args if a.ndim == 2}
+        adir = dist = None
+        if approach is not None:
+            adir = args[2] if approach_dir is None else conv(approach_dir, "approach_dir", 3, nonzero=True)
+            if torch is not None and isinstance(approach, torch.Tensor):
+                if approach.device != self.device or not approach.dtype.is_floating_point or approach.ndim > 1:
+                    raise ValueError(f"approach must be a floating-point tensor of shape () or (S,) on {self.device}")
+                dist = approach.to(torch.float64)
+            else:
+                if isinstance(approach, (bool, str)):
+                    raise ValueError(f"approach must be a distance > 0 or (S,) distances, not {approach!r}")
+                try:
+                    dist = np.array(approach, dtype=float)
+                except (TypeError, ValueError):
+                    raise ValueError(f"approach must be a distance > 0 or (S,) distances, not {approach!r}") from None
+                if dist.ndim > 1 or not np.isfinite(dist).all() or not (dist > 0).all():
+                    raise ValueError(f"approach must be a finite distance > 0 or (S,) of them, not {approach!r}")
+        rows = {a.shape[0] for a in args + ([adir] if adir is not None else []) if a.ndim == 2}
+        if dist is not None and dist.ndim == 1:
+            rows.add(dist.shape[0])
         if len(rows) > 1:
-            raise ValueError(f"x0, target_pos and target_axis disagree on S: {sorted(rows)}")
+            raise ValueError(f"x0, target_pos, target_axis, approach and approach_dir disagree on S: {sorted(rows)}")
         S = rows.pop() if rows else 1
         if S < 1 or S > self.max_slots:
             raise ValueError(f"S={S} outside 1..max_slots={self.max_slots}")
@@ -239,8 +283,35 @@ class RRTCFSPlanner:
             self._ik[key] = IKSolver(self._sys_rrt.robot, [o for o in self._pobs], joint_limits=self._ik_limits, njoint=self.nj,
                                      device=self.device, **ik_options)
         ik = self._ik[key]
+        if approach is not None:
+            ckey = ("approach", key, int(approach_steps), tuple(sorted((k, repr(v)) for k, v in approach_options.items())))
+            if ckey not in self._ik:                                                # validates approach_options; no device call
+                shared = {k: v for k, v in ik_options.items() if k in ("tool", "tool_axis", "tol_pos", "tol_axis", "weight")}
+                self._ik[ckey] = CartesianPath(self._sys_rrt.robot, [o for o in self._pobs], joint_limits=self._ik_limits, njoint=self.nj,
+                                               device=self.device, steps=int(approach_steps), **shared, **approach_options)
+            cart = self._ik[ckey]
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
+        if approach is not None:
+            with torch.cuda.device(self.device), torch.cuda.stream(stream):
+                dev = [self._on_device(a, S) for a in args]
+                u = self._on_device(adir, S)
+                u = u / torch.linalg.norm(u, dim=1, keepdim=True)
+                dd = dist if isinstance(dist, torch.Tensor) else torch.tensor(dist, dtype=torch.float64, device=self.device)
+                pre = (dev[1] - dd.reshape(-1, 1) * u).contiguous()
+                sol = ik.solve_device(pre, dev[2], dev[0], seed=int(seed), want_candidates=True, stream=stream)
+                tr = cart.trace_device(sol.cand_theta, dev[1], dev[2], dev[0], start_state=sol.cand_status, stream=stream)
+                ik_ok, ok = sol.status == 0, tr.status == 0
+                goal = torch.where(ok[:, None], tr.theta, dev[0])
+                res = self.plan(dev[0], goal, seed, **dict(plan_kwargs, stream=stream))
+                masked = torch.where(ik_ok, torch.full_like(res.status, -3), torch.full_like(res.status, -2))
+                res.status = torch.where(ok, res.status, masked)
+                res.has_solution = torch.where(ok, res.has_solution, torch.zeros_like(res.has_solution))
+                res.selected = torch.where(ok, res.selected, torch.full_like(res.selected, -1))
+                res.goal, res.ik_goal, res.ik_status, res.ik_err_pos, res.ik_clearance = tr.theta, sol.theta, sol.status, sol.err_pos, sol.clearance
+                res.approach_path, res.grasp, res.approach_status = tr.path, tr.path[:, -1], tr.status
+                res.approach_clearance, res.approach_selected = tr.clearance, tr.selected
+            return res
         with torch.cuda.device(self.device), torch.cuda.stream(stream):
             dev = [self._on_device(a, S) for a in args]
             sol = ik.solve_device(dev[1], dev[2] if len(dev) > 2 else None, dev[0], seed=int(seed), stream=stream)
