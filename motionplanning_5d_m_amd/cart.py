@@ -10,14 +10,12 @@ per candidate; this module packs arguments and unpacks results, the tracing and 
 from __future__ import annotations
 
 import ctypes as C
-from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib
-from .ik import IKSolver, _is_int, _real
-from .robotproperty2 import to_c_robot
-from .solvers import _f64, _ptr
+from . import _args, _lib
+from ._args import f64 as _f64, ptr as _ptr
+from .ik import _ToolSolver
 
 try:
     import torch
@@ -29,7 +27,7 @@ MAX_STEPS = 256
 MAX_ITER = 1000
 
 
-class CartesianPath:
+class CartesianPath(_ToolSolver):
     """Straight tool lines for one robot, one set of line obstacles and one set of joint ranges.
 
     robot, obs, joint_limits, tool, tool_axis, tol_pos, tol_axis, weight, device, njoint: as for IKSolver, except that a mesh entry
@@ -43,37 +41,15 @@ class CartesianPath:
         for j, o in enumerate(obs):
             if isinstance(o, dict) and "mesh" in o:
                 raise ValueError(f"obs[{j}] is a mesh obstacle: CartesianPath reads line obstacles only")
-        if not _is_int(steps) or not 1 <= steps <= MAX_STEPS:
-            raise ValueError(f"steps must be an integer in 1..{MAX_STEPS}, not {steps!r}")
-        if not _is_int(max_iter) or not 1 <= max_iter <= MAX_ITER:
-            raise ValueError(f"max_iter must be an integer in 1..{MAX_ITER}, not {max_iter!r}")
-        # the shared arguments are IKSolver's, checked by IKSolver's own code
-        base = IKSolver(robot, obs, joint_limits=joint_limits, tool=tool, tool_axis=tool_axis, restarts=1, max_iter=int(max_iter),
-                        tol_pos=tol_pos, tol_axis=tol_axis, weight=weight, device=device, njoint=njoint)
-        self.robot, self.nj, self.lo, self.hi = base.robot, base.nj, base.lo, base.hi
-        self.tool, self.tool_axis, self.weight = base.tool, base.tool_axis, base.weight
-        self.tol_pos, self.tol_axis, self.obs, self.D, self.device = base.tol_pos, base.tol_axis, base.obs, base.D, base.device
-        self._targets = base._targets
-        self.steps, self.max_iter = int(steps), int(max_iter)
-        self.max_joint_step = _real(max_joint_step, "max_joint_step")
-        self._dev = None                                      # obstacle rows on the device (trace_device)
+        self.steps = _args.int_in(steps, "steps", 1, MAX_STEPS)
+        self.max_iter = _args.int_in(max_iter, "max_iter", 1, MAX_ITER)
+        super().__init__(robot, obs, joint_limits, tool, tool_axis, tol_pos, tol_axis, weight, device, njoint)
+        self.max_joint_step = _args.real(max_joint_step, "max_joint_step")
 
     def _desc(self, use_axis, R, obs, D):
-        d = _lib.cfs_cart_desc()
-        d.robot = to_c_robot(self.robot)
-        d.njoint, d.use_axis = self.nj, int(use_axis)
-        for q in range(3):
-            d.tool[q], d.tool_axis[q] = float(self.tool[q]), float(self.tool_axis[q])
-        d.lo, d.hi, d.weight = _ptr(self.lo), _ptr(self.hi), _ptr(self.weight)
+        d = self._fill_desc(_lib.cfs_cart_desc(), use_axis, obs, D)
         d.candidates, d.steps, d.max_iter, d.max_joint_step = int(R), self.steps, self.max_iter, self.max_joint_step
-        d.tol_pos, d.tol_axis = self.tol_pos, self.tol_axis
-        d.nobs = int(self.obs.shape[0])
-        d.obs, d.D = (_ptr(obs), _ptr(D)) if d.nobs else (None, None)
         return d
-
-    def _names(self, want_candidates):
-        return ("theta", "status", "path", "selected", "n_ok", "n_done", "clearance") + (
-            ("cand_status", "cand_done", "cand_iter", "cand_end", "cand_path") if want_candidates else ())
 
     def _shapes(self, T, R):
         nj, K1 = self.nj, self.steps + 1
@@ -118,11 +94,8 @@ class CartesianPath:
                 raise ValueError(f"start_state must be an integer array of shape ({T}, {R}), not {ss.dtype} {ss.shape}")
             ss = np.ascontiguousarray(ss.astype(np.int32))
         s = _f64(s)
-        shapes = self._shapes(T, R)
-        r = SimpleNamespace(**{k: np.zeros(*shapes[k]) for k in self._names(want_candidates)})
-        o = _lib.cfs_cart_out()
-        for k in vars(r):
-            setattr(o, k, _ptr(getattr(r, k)))
+        r = self._results(self._shapes(T, R), want_candidates)
+        o = _args.fill(_lib.cfs_cart_out(), r)
         d = self._desc(ta is not None, R, self.obs, self.D)
         _lib.check(_lib.lib().cfs_cart_path(C.byref(d), T, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o)))
         return r
@@ -136,51 +109,25 @@ class CartesianPath:
         if torch is None:
             raise ValueError("trace_device needs torch")
         nj = self.nj
-
-        def chk(t, name, shape, dtype=None):
-            dtype = torch.float64 if dtype is None else dtype
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-                raise ValueError(f"{name} must be a {str(dtype).replace('torch.', '')} CUDA tensor")
-            if t.ndim != len(shape) or any(w is not None and v != w for v, w in zip(t.shape, shape)):
-                raise ValueError(f"{name} must have shape {tuple('T' if w is None else w for w in shape)}, not {tuple(t.shape)}")
-            if self.device is not None and t.device != self.device:
-                raise ValueError(f"{name} is on {t.device}, the solver on {self.device}")
-            return t.contiguous()
-        s = chk(start, "start", (None, None, nj))
+        s = _args.cuda_tensor(start, "start", (None, None, nj), device=self.device)
         T, R, dev = s.shape[0], s.shape[1], s.device
         if T < 1 or not 1 <= R <= MAX_CANDIDATES:
             raise ValueError(f"start must have shape (T, R, {nj}) with T >= 1 and R in 1..{MAX_CANDIDATES}, not {tuple(s.shape)}")
-        tp = chk(target_pos, "target_pos", (T, 3))
-        ta = None if target_axis is None else chk(target_axis, "target_axis", (T, 3))
-        if theta_ref is None:
-            tr = torch.tensor(0.5 * (self.lo + self.hi), dtype=torch.float64, device=dev).unsqueeze(0).expand(T, -1).contiguous()
-        else:
-            tr = chk(theta_ref, "theta_ref", (T, nj))
-        ss = None if start_state is None else chk(start_state, "start_state", (T, R), torch.int32)
-        for t, name in ((tp, "target_pos"), (ta, "target_axis"), (tr, "theta_ref"), (ss, "start_state")):
-            if t is not None and t.device != dev:
-                raise ValueError(f"{name} must be on {dev}")
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        elif not isinstance(stream, torch.cuda.Stream):
-            raise ValueError("stream must be a torch.cuda.Stream")
-        if self._dev is None or self._dev[0] != dev:
-            self._dev = (dev, torch.tensor(self.obs, dtype=torch.float64, device=dev), torch.tensor(self.D, dtype=torch.float64, device=dev))
+        tp = _args.cuda_tensor(target_pos, "target_pos", (T, 3), device=dev)
+        ta = None if target_axis is None else _args.cuda_tensor(target_axis, "target_axis", (T, 3), device=dev)
+        tr = self._theta_ref(theta_ref, T, dev)
+        ss = None if start_state is None else _args.cuda_tensor(start_state, "start_state", (T, R), torch.int32, device=dev)
+        stream, obs, D = self._on(dev, stream)
         shapes = self._shapes(T, R)
         with torch.cuda.device(dev), torch.cuda.stream(stream):
-            z = lambda k: torch.zeros(*shapes[k][0], dtype=torch.float64 if shapes[k][1] is np.float64 else torch.int32, device=dev)  # noqa: E731
-            r = SimpleNamespace(**{k: z(k) for k in self._names(want_candidates)})
-            o = _lib.cfs_cart_out()
-            for k in vars(r):
-                setattr(o, k, _ptr(getattr(r, k)))
+            r = self._results(shapes, want_candidates, dev)
+            o = _args.fill(_lib.cfs_cart_out(), r)
             work = None
             if not want_candidates:                           # `path` is gathered from cand_path: the launch's workspace
-                work = z("cand_path")
+                work = _args.zeros_on(dev)(*shapes["cand_path"])
                 o.cand_path = _ptr(work)
-            d = self._desc(ta is not None, R, self._dev[1], self._dev[2])
+            d = self._desc(ta is not None, R, obs, D)
             _lib.check(_lib.lib().cfs_cart_path_device(C.byref(d), T, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o),
                                                        C.c_void_p(stream.cuda_stream)))
-            for t in (s, ss, tp, ta, tr, work, self._dev[1], self._dev[2]):
-                if t is not None:
-                    t.record_stream(stream)
+            self._record(stream, s, ss, tp, ta, tr, work)
         return r

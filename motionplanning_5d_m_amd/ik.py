@@ -17,16 +17,15 @@ closer to mesh j than ``max(D_j, 1e-4)`` -- the decision of ``cfs_rrt_grow_mesh`
 from __future__ import annotations
 
 import ctypes as C
-import math
-import numbers
 from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import f64 as _f64, is_int as _is_int, ptr as _ptr
 from .robotproperty2 import to_c_robot
 from .mesh import Mesh
-from .solvers import _f64, _joint_limits_array, _ptr, obs_meshes, obs_to_array
+from .solvers import _joint_limits_array
 
 try:
     import torch
@@ -35,16 +34,6 @@ except Exception:  # pragma: no cover
 
 MAX_RESTARTS = 64            # one wavefront lane per restart
 MAX_ITER = 1000
-
-
-def _is_int(v):
-    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
-
-
-def _real(v, name, positive=True):
-    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (positive and not v > 0):
-        raise ValueError(f"{name} must be a finite real number{' > 0' if positive else ''}, not {v!r}")
-    return float(v)
 
 
 def _vec3(v, name, nonzero=False):
@@ -98,22 +87,11 @@ def tool_pose(robot, theta, njoint=None, tool=None, tool_axis=None, want_jac=Fal
     return (pos, dr, jac) if want_jac else (pos, dr)
 
 
-class IKSolver:
-    """Batched inverse kinematics for one robot, one set of obstacles and one set of joint ranges.
+class _ToolSolver:
+    """What IKSolver and CartesianPath share: the chain (robot, njoint, joint ranges, tool point and axis), the tolerances and the
+    weight, the obstacles, the device, the checks of the targets and the plumbing of their device entries."""
 
-    robot: robotproperty2(id).  obs: None or an obs cell of line obstacles (dict(l=3x2, D=...)), which may end with mesh obstacles
-    (dict(mesh=Mesh, D=...), D finite and > 0); a mesh before a line obstacle is refused.  mesh_variant: None (the library's
-    default) or a key of _lib.IK_MESH ("per_lane" | "wave" | "small_frontier"): the developer switch of cfs_ik_solve_mesh*, with
-    bit-identical results under every value.
-    joint_limits: "robot" (robot.thetamax[:njoint]) or an (njoint, 2) array of finite [lo, hi].  tool / tool_axis: a point and a
-    direction in the frame of link njoint (defaults: default_tool).  restarts: 1..64 starts per target, restart 0 at theta_ref,
-    the others drawn in the joint ranges from `seed`.  tol_pos (m) / tol_axis (norm of the difference of unit vectors): what
-    "reached" means.  weight: njoint weights > 0 of the distance to theta_ref (None: ones).  njoint: joints of the chain (default: 5
-    for the M200i, the joints the reference plans; otherwise every link that has a capsule, at most 6).
-    Arguments are validated here, before anything touches the device."""
-
-    def __init__(self, robot, obs=None, joint_limits="robot", tool=None, tool_axis=None, restarts=64, max_iter=100, tol_pos=1e-6,
-                 tol_axis=1e-6, weight=None, device=None, njoint=None, mesh_variant=None):
+    def __init__(self, robot, obs, joint_limits, tool, tool_axis, tol_pos, tol_axis, weight, device, njoint):
         self.robot, self.nj = robot, _njoint(robot, njoint)
         nj = self.nj
         if joint_limits is None:
@@ -126,12 +104,7 @@ class IKSolver:
         self.tool = t0 if tool is None else _vec3(tool, "tool")
         self.tool_axis = a0 if tool_axis is None else _vec3(tool_axis, "tool_axis", nonzero=True)
         self.tool_axis = self.tool_axis / np.linalg.norm(self.tool_axis)
-        if not _is_int(restarts) or not 1 <= restarts <= MAX_RESTARTS:
-            raise ValueError(f"restarts must be an integer in 1..{MAX_RESTARTS}, not {restarts!r}")
-        if not _is_int(max_iter) or not 1 <= max_iter <= MAX_ITER:
-            raise ValueError(f"max_iter must be an integer in 1..{MAX_ITER}, not {max_iter!r}")
-        self.restarts, self.max_iter = int(restarts), int(max_iter)
-        self.tol_pos, self.tol_axis = _real(tol_pos, "tol_pos"), _real(tol_axis, "tol_axis")
+        self.tol_pos, self.tol_axis = _args.real(tol_pos, "tol_pos"), _args.real(tol_axis, "tol_axis")
         if weight is None:
             self.weight = None
         else:
@@ -145,42 +118,26 @@ class IKSolver:
         obs = [] if obs is None else list(obs)
         if len(obs) > _lib.CFS_MAX_OBS:
             raise ValueError(f"{len(obs)} obstacles: at most {_lib.CFS_MAX_OBS}")
-        self._meshes = obs_meshes(obs)                        # ValueError when a mesh precedes a line obstacle
-        for j, o in enumerate(obs):
+        _args.obs_meshes(obs)                                 # ValueError when a mesh precedes a line obstacle
+        for j, o in enumerate(obs):                           # the meshes first, then the lines
             if "mesh" not in o:
                 continue
             if not isinstance(o["mesh"], Mesh):
                 raise ValueError(f"obs[{j}]['mesh'] must be a Mesh, not {type(o['mesh']).__name__}")
-            if isinstance(o.get("D"), bool) or not isinstance(o.get("D"), numbers.Real) or not math.isfinite(o["D"]) or not o["D"] > 0:
-                raise ValueError(f"obs[{j}]['D'] (a mesh obstacle) must be a finite real number > 0")
-        self._D_mesh = _f64([o["D"] for o in obs if "mesh" in o])
-        if mesh_variant is not None and (not isinstance(mesh_variant, str) or mesh_variant not in _lib.IK_MESH):
-            raise ValueError(f"mesh_variant must be None or one of {sorted(_lib.IK_MESH)}, not {mesh_variant!r}")
-        self.mesh_variant = mesh_variant
-        obs = [o for o in obs if "mesh" not in o]
+            _args.real(o.get("D"), f"obs[{j}]['D'] (a mesh obstacle)")
         for j, o in enumerate(obs):
+            if "mesh" in o:
+                continue
             if np.shape(o["l"]) != (3, 2) or not np.isfinite(np.asarray(o["l"], float)).all():
                 raise ValueError(f"obs[{j}]['l'] must be a finite 3x2 array")
-            if isinstance(o.get("D"), bool) or not isinstance(o.get("D"), numbers.Real) or not math.isfinite(o["D"]):
-                raise ValueError(f"obs[{j}]['D'] must be a finite real number")
-        self.obs = obs_to_array(obs) if obs else np.zeros((0, 6))
-        self.D = _f64([o["D"] for o in obs])
+            _args.real(o.get("D"), f"obs[{j}]['D']", positive=False)
+        self.obs, self.D, self._meshes, self._D_mesh = _args.split_obs(obs)
         if device is not None:
             if torch is None:
                 raise ValueError("device= needs torch")
-            device = torch.device("cuda", int(device)) if _is_int(device) else torch.device(device)
-            if device.type != "cuda":
-                raise ValueError(f"device must be a CUDA (HIP) device, not {device}")
-            if device.index is None:
-                device = torch.device("cuda", 0)
+            device = _args.cuda_device(device)
         self.device = device
-        self._dev = None                                      # obstacle rows on the device (solve_device)
-
-    # ---- argument checks ---------------------------------------------------------------------------------------------------
-    def _seed(self, seed):
-        if not _is_int(seed) or not 0 <= seed < 2 ** 64:
-            raise ValueError(f"seed must be an integer in 0..2^64-1, not {seed!r}")
-        return int(seed)
+        self._dev = None                                      # (device, obstacle rows, D) uploaded by the device entry
 
     def _targets(self, target_pos, target_axis, theta_ref):
         """host arrays (T, 3), (T, 3) | None, (T, nj), validated"""
@@ -219,23 +176,77 @@ class IKSolver:
                 raise ValueError("theta_ref must be finite")
         return T, _f64(tp), (None if ta is None else _f64(ta)), _f64(tr)
 
-    def _desc(self, use_axis, seed, obs, D):
-        d = _lib.cfs_ik_desc()
+    def _fill_desc(self, d, use_axis, obs, D):
+        """the fields cfs_ik_desc and cfs_cart_desc share"""
         d.robot = to_c_robot(self.robot)
         d.njoint, d.use_axis = self.nj, int(use_axis)
         for q in range(3):
             d.tool[q], d.tool_axis[q] = float(self.tool[q]), float(self.tool_axis[q])
         d.lo, d.hi, d.weight = _ptr(self.lo), _ptr(self.hi), _ptr(self.weight)
-        d.restarts, d.max_iter, d.tol_pos, d.tol_axis = self.restarts, self.max_iter, self.tol_pos, self.tol_axis
+        d.tol_pos, d.tol_axis = self.tol_pos, self.tol_axis
         d.nobs = int(self.obs.shape[0])
         d.obs, d.D = (_ptr(obs), _ptr(D)) if d.nobs else (None, None)
-        d.seed = seed
         return d
 
-    def _mesh_args(self):
-        """(nmesh, handle array, D_mesh pointer, flags) of cfs_ik_solve_mesh*"""
-        arr = (C.c_void_p * len(self._meshes))(*[m._h for m in self._meshes])
-        return len(self._meshes), arr, _ptr(self._D_mesh), 0 if self.mesh_variant is None else _lib.IK_MESH[self.mesh_variant]
+    def _results(self, shapes, want_candidates, dev=None):
+        """the result namespace of a shapes table (field -> (shape, dtype), in the order of the out struct; the cand_ fields only
+        with want_candidates): numpy arrays, or tensors on `dev`"""
+        z = _args.zeros_on(dev)
+        return SimpleNamespace(**{k: z(*sd) for k, sd in shapes.items() if want_candidates or not k.startswith("cand_")})
+
+    # ---- the device entries: what follows the check of the first tensor, whose device `dev` is the launch's -------------
+    def _theta_ref(self, theta_ref, T, dev):
+        if theta_ref is None:
+            return torch.tensor(0.5 * (self.lo + self.hi), dtype=torch.float64, device=dev).unsqueeze(0).expand(T, -1).contiguous()
+        return _args.cuda_tensor(theta_ref, "theta_ref", (T, self.nj), device=dev)
+
+    def _on(self, dev, stream):
+        """(the torch stream of the launch, obstacle rows on dev, their D on dev); the obstacles are uploaded once per device"""
+        stream = _args.as_stream(stream, dev)
+        if self._dev is None or self._dev[0] != dev:
+            self._dev = (dev, torch.tensor(self.obs, dtype=torch.float64, device=dev), torch.tensor(self.D, dtype=torch.float64, device=dev))
+        return stream, self._dev[1], self._dev[2]
+
+    def _record(self, stream, *tensors):
+        for t in tensors + self._dev[1:]:
+            if t is not None:
+                t.record_stream(stream)
+
+
+class IKSolver(_ToolSolver):
+    """Batched inverse kinematics for one robot, one set of obstacles and one set of joint ranges.
+
+    robot: robotproperty2(id).  obs: None or an obs cell of line obstacles (dict(l=3x2, D=...)), which may end with mesh obstacles
+    (dict(mesh=Mesh, D=...), D finite and > 0); a mesh before a line obstacle is refused.  mesh_variant: None (the library's
+    default) or a key of _lib.IK_MESH ("per_lane" | "wave" | "small_frontier"): the developer switch of cfs_ik_solve_mesh*, with
+    bit-identical results under every value.
+    joint_limits: "robot" (robot.thetamax[:njoint]) or an (njoint, 2) array of finite [lo, hi].  tool / tool_axis: a point and a
+    direction in the frame of link njoint (defaults: default_tool).  restarts: 1..64 starts per target, restart 0 at theta_ref,
+    the others drawn in the joint ranges from `seed`.  tol_pos (m) / tol_axis (norm of the difference of unit vectors): what
+    "reached" means.  weight: njoint weights > 0 of the distance to theta_ref (None: ones).  njoint: joints of the chain (default: 5
+    for the M200i, the joints the reference plans; otherwise every link that has a capsule, at most 6).
+    Arguments are validated here, before anything touches the device."""
+
+    def __init__(self, robot, obs=None, joint_limits="robot", tool=None, tool_axis=None, restarts=64, max_iter=100, tol_pos=1e-6,
+                 tol_axis=1e-6, weight=None, device=None, njoint=None, mesh_variant=None):
+        super().__init__(robot, obs, joint_limits, tool, tool_axis, tol_pos, tol_axis, weight, device, njoint)
+        self.restarts = _args.int_in(restarts, "restarts", 1, MAX_RESTARTS)
+        self.max_iter = _args.int_in(max_iter, "max_iter", 1, MAX_ITER)
+        self.mesh_variant = None if mesh_variant is None else _args.one_of(_lib.IK_MESH, mesh_variant, "mesh_variant")
+
+    def _desc(self, use_axis, seed, obs, D):
+        d = self._fill_desc(_lib.cfs_ik_desc(), use_axis, obs, D)
+        d.restarts, d.max_iter, d.seed = self.restarts, self.max_iter, seed
+        return d
+
+    def _shapes(self, T):
+        nj, R = self.nj, self.restarts
+        f, i = np.float64, np.int32
+        return dict(theta=((T, nj), f), status=((T,), i), selected=((T,), i), n_ok=((T,), i), err_pos=((T,), f), err_axis=((T,), f),
+                    clearance=((T,), f), cand_theta=((T, R, nj), f), cand_status=((T, R), i), cand_iter=((T, R), i))
+
+    def _mesh_table(self):
+        return _args.mesh_table(self._meshes, self._D_mesh, 0 if self.mesh_variant is None else _lib.IK_MESH[self.mesh_variant])
 
     # ---- host arrays in and out (cfs_ik_solve) -----------------------------------------------------------------------------
     def solve(self, target_pos, target_axis=None, theta_ref=None, seed=0, want_candidates=False):
@@ -245,20 +256,13 @@ class IKSolver:
         -1 without one), n_ok, err_pos, err_axis, clearance (min over the obstacles, meshes included, of distance - D; +inf without
         obstacles); rows
         of unsolved targets hold NaN.  want_candidates: also cand_theta (T, restarts, njoint), cand_status, cand_iter."""
-        seed = self._seed(seed)
+        seed = _args.int_in(seed, "seed", 0, 2 ** 64 - 1)
         T, tp, ta, tr = self._targets(target_pos, target_axis, theta_ref)
-        nj, R = self.nj, self.restarts
-        r = SimpleNamespace(theta=np.zeros((T, nj)), status=np.zeros(T, np.int32), selected=np.zeros(T, np.int32), n_ok=np.zeros(T, np.int32),
-                            err_pos=np.zeros(T), err_axis=np.zeros(T), clearance=np.zeros(T))
-        if want_candidates:
-            r.cand_theta, r.cand_status, r.cand_iter = np.zeros((T, R, nj)), np.zeros((T, R), np.int32), np.zeros((T, R), np.int32)
-        o = _lib.cfs_ik_out()
-        for k in vars(r):
-            setattr(o, k, _ptr(getattr(r, k)))
+        r = self._results(self._shapes(T), want_candidates)
+        o = _args.fill(_lib.cfs_ik_out(), r)
         d = self._desc(ta is not None, seed, self.obs, self.D)
         if self._meshes:
-            nm, arr, Dm, fl = self._mesh_args()
-            _lib.check(_lib.lib().cfs_ik_solve_mesh(C.byref(d), nm, arr, Dm, fl, T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o)))
+            _lib.check(_lib.lib().cfs_ik_solve_mesh(C.byref(d), *self._mesh_table(), T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o)))
         else:
             _lib.check(_lib.lib().cfs_ik_solve(C.byref(d), T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o)))
         return r
@@ -268,54 +272,24 @@ class IKSolver:
         """solve() on float64 CUDA tensors of the solver's device (target_pos (T, 3), target_axis (T, 3) or None, theta_ref
         (T, njoint)), enqueued on `stream` (a torch.cuda.Stream; default: the current one) without a host synchronisation.  The
         values of device tensors cannot be checked on the host: a non-finite one ends the restarts that read it in state 3."""
-        seed = self._seed(seed)
+        seed = _args.int_in(seed, "seed", 0, 2 ** 64 - 1)
         if torch is None:
             raise ValueError("solve_device needs torch")
-        nj, R = self.nj, self.restarts
-
-        def chk(t, name, cols):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
-                raise ValueError(f"{name} must be a float64 CUDA tensor")
-            if t.ndim != 2 or t.shape[1] != cols:
-                raise ValueError(f"{name} must have shape (T, {cols}), not {tuple(t.shape)}")
-            if self.device is not None and t.device != self.device:
-                raise ValueError(f"{name} is on {t.device}, the solver on {self.device}")
-            return t.contiguous()
-        tp = chk(target_pos, "target_pos", 3)
+        tp = _args.cuda_tensor(target_pos, "target_pos", (None, 3), device=self.device)
         T, dev = tp.shape[0], tp.device
         if T < 1:
             raise ValueError("at least one target is needed")
-        ta = None if target_axis is None else chk(target_axis, "target_axis", 3)
-        if theta_ref is None:
-            tr = torch.tensor(0.5 * (self.lo + self.hi), dtype=torch.float64, device=dev).unsqueeze(0).expand(T, -1).contiguous()
-        else:
-            tr = chk(theta_ref, "theta_ref", nj)
-        for t, name in ((ta, "target_axis"), (tr, "theta_ref")):
-            if t is not None and (t.shape[0] != T or t.device != dev):
-                raise ValueError(f"{name} must have {T} rows on {dev}")
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        elif not isinstance(stream, torch.cuda.Stream):
-            raise ValueError("stream must be a torch.cuda.Stream")
-        if self._dev is None or self._dev[0] != dev:
-            self._dev = (dev, torch.tensor(self.obs, dtype=torch.float64, device=dev), torch.tensor(self.D, dtype=torch.float64, device=dev))
+        ta = None if target_axis is None else _args.cuda_tensor(target_axis, "target_axis", (T, 3), device=dev)
+        tr = self._theta_ref(theta_ref, T, dev)
+        stream, obs, D = self._on(dev, stream)
         with torch.cuda.device(dev), torch.cuda.stream(stream):
-            z = lambda *sh, dt=torch.float64: torch.zeros(*sh, dtype=dt, device=dev)  # noqa: E731
-            r = SimpleNamespace(theta=z(T, nj), status=z(T, dt=torch.int32), selected=z(T, dt=torch.int32), n_ok=z(T, dt=torch.int32),
-                                err_pos=z(T), err_axis=z(T), clearance=z(T))
-            if want_candidates:
-                r.cand_theta, r.cand_status, r.cand_iter = z(T, R, nj), z(T, R, dt=torch.int32), z(T, R, dt=torch.int32)
-            o = _lib.cfs_ik_out()
-            for k in vars(r):
-                setattr(o, k, _ptr(getattr(r, k)))
-            d = self._desc(ta is not None, seed, self._dev[1], self._dev[2])
+            r = self._results(self._shapes(T), want_candidates, dev)
+            o = _args.fill(_lib.cfs_ik_out(), r)
+            d = self._desc(ta is not None, seed, obs, D)
+            tail = (T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o), C.c_void_p(stream.cuda_stream))
             if self._meshes:
-                nm, arr, Dm, fl = self._mesh_args()
-                _lib.check(_lib.lib().cfs_ik_solve_mesh_device(C.byref(d), nm, arr, Dm, fl, T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o),
-                                                               C.c_void_p(stream.cuda_stream)))
+                _lib.check(_lib.lib().cfs_ik_solve_mesh_device(C.byref(d), *self._mesh_table(), *tail))
             else:
-                _lib.check(_lib.lib().cfs_ik_solve_device(C.byref(d), T, _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o), C.c_void_p(stream.cuda_stream)))
-            for t in (tp, ta, tr, self._dev[1], self._dev[2]):
-                if t is not None:
-                    t.record_stream(stream)
+                _lib.check(_lib.lib().cfs_ik_solve_device(C.byref(d), *tail))
+            self._record(stream, tp, ta, tr)
         return r

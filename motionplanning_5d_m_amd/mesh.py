@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._args import ptr as _ptr
 from .robotproperty2 import to_c_robot
 
 _REC = np.dtype([("n", "<3f4"), ("v", "<9f4"), ("a", "<u2")])
@@ -135,28 +136,31 @@ def assembly_line(base, n_target=10000, seed=0):
 
 
 # ---- device mesh ---------------------------------------------------------------------------------------
+def _lib_on(device):
+    """the library, with `device` (None: as it is) made current"""
+    lib = _lib.lib()
+    if device is not None:
+        _lib.check(lib.cfs_set_device(int(device)))
+    return lib
+
+
 class Mesh:
     """A triangle mesh resident on the GPU with its hierarchy (cfs_mesh_create / cfs_mesh_load_stl)."""
 
     def __init__(self, tri=None, vertices=None, faces=None, device=None):
-        lib = _lib.lib()
-        if device is not None:
-            _lib.check(lib.cfs_set_device(int(device)))
+        lib = _lib_on(device)
         if tri is not None:
             tri = np.ascontiguousarray(tri, np.float64).reshape(-1, 3, 3)
             vertices, faces = tri.reshape(-1, 3), np.arange(3 * tri.shape[0], dtype=np.int32).reshape(-1, 3)
         vertices = np.ascontiguousarray(vertices, np.float64)
         faces = np.ascontiguousarray(faces, np.int32)
         h = C.c_void_p()
-        _lib.check(lib.cfs_mesh_create(vertices.ctypes.data_as(C.c_void_p), vertices.shape[0],
-                                       faces.ctypes.data_as(C.c_void_p), faces.shape[0], C.byref(h)))
+        _lib.check(lib.cfs_mesh_create(_ptr(vertices), vertices.shape[0], _ptr(faces), faces.shape[0], C.byref(h)))
         self._h, self._lib = h, lib
 
     @classmethod
     def from_stl(cls, path, scale=1.0, map_from_stl=False, device=None):
-        lib = _lib.lib()
-        if device is not None:
-            _lib.check(lib.cfs_set_device(int(device)))
+        lib = _lib_on(device)
         self = cls.__new__(cls)
         h = C.c_void_p()
         _lib.check(lib.cfs_mesh_load_stl(str(path).encode(), float(scale), 1 if map_from_stl else 0, C.byref(h)))
@@ -174,8 +178,7 @@ class Mesh:
         segs = np.ascontiguousarray(np.atleast_2d(segs), np.float64)
         n = segs.shape[0]
         dis, pts, tri = np.zeros(n), np.zeros((n, 6)), np.zeros(n, np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _lib.check(self._lib.cfs_mesh_segment_distance(self._h, n, p(segs), p(dis), p(pts), p(tri)))
+        _lib.check(self._lib.cfs_mesh_segment_distance(self._h, n, _ptr(segs), _ptr(dis), _ptr(pts), _ptr(tri)))
         return dis, pts, tri
 
     def close(self):
@@ -193,6 +196,5 @@ def dist_arm_surf(robot, theta, mesh):
     N, nj = theta.shape
     d, lid, pts = np.zeros(N), np.zeros(N, np.int32), np.zeros((N, 6))
     rb = to_c_robot(robot)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    _lib.check(_lib.lib().cfs_dist_arm_mesh(C.byref(rb), nj, N, p(theta), mesh._h, p(d), p(lid), p(pts)))
+    _lib.check(_lib.lib().cfs_dist_arm_mesh(C.byref(rb), nj, N, _ptr(theta), mesh._h, _ptr(d), _ptr(lid), _ptr(pts)))
     return d, lid, pts

@@ -25,12 +25,13 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr as _ptr
 from .cart import MAX_STEPS, CartesianPath
 from .ik import IKSolver
 from .rrt import RRT_FANUC
 from .robotproperty2 import robotproperty2
-from .solvers import CFSBatch, _infeasible_args, _jacobian_code, _joint_limits_array, _ptr, _substeps, obs_meshes, obs_to_array
+from .solvers import SOLVE_OUT, CFSBatch, _infeasible_args, _joint_limits_array, obs_meshes, obs_to_array
 from .sysinfo import RRTstar_CFS_problem
 
 try:
@@ -43,25 +44,13 @@ MAX_SEEDS = 64               # one wavefront lane per candidate in cfs_select_be
 ROUND_SEED_STRIDE = 1_000_003  # R: the trees of round r use the generator seed `seed + r*R`
 
 
-def _batch_out(o):
-    b = _lib.cfs_batch_out()
-    b.u, b.x_, b.cost_all, b.e_cost_all, b.e_u_all = _ptr(o.u), _ptr(o.x_), _ptr(o.cost_all), _ptr(o.e_cost_all), _ptr(o.e_u_all)
-    b.iter_O, b.total_iter, b.status = _ptr(o.iter_O), _ptr(o.total_iter), _ptr(o.status)
-    return b
-
-
-def _is_int(v):
-    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
-
-
 def select_best_device(cfs, S, K, route_ok, cand, best, selected, has_solution, cand_viol_all=None, best_viol_all=None, stream=None):
     """cfs_select_best_device on CUDA tensors: cand / best are CFSBatch.alloc_outputs-style namespaces of S*K / S rows,
     route_ok (S*K,) int32, selected / has_solution (S,) int32, viol_all (rows, MAX_O_ITER) float64 or None."""
-    if stream is None:
-        stream = torch.cuda.current_stream(route_ok.device).cuda_stream
-    _lib.check(cfs._lib.cfs_select_best_device(cfs._h, int(S), int(K), _ptr(route_ok), C.byref(_batch_out(cand)), _ptr(cand_viol_all),
-                                               C.byref(_batch_out(best)), _ptr(best_viol_all), _ptr(selected), _ptr(has_solution),
-                                               C.c_void_p(stream)))
+    stream = _args.stream_ptr(stream, route_ok.device)
+    cand, best = _args.fill(_lib.cfs_batch_out(), cand), _args.fill(_lib.cfs_batch_out(), best)
+    _lib.check(cfs._lib.cfs_select_best_device(cfs._h, int(S), int(K), _ptr(route_ok), C.byref(cand), _ptr(cand_viol_all), C.byref(best),
+                                               _ptr(best_viol_all), _ptr(selected), _ptr(has_solution), C.c_void_p(stream)))
 
 
 class RRTCFSPlanner:
@@ -87,21 +76,17 @@ class RRTCFSPlanner:
     def __init__(self, pobs, sys_rrt, region_g, region_s, sample_off, ROBOT="M200i", rrt_solver="RRT", num_seed=6, mode="CFS",
                  select="best", on_infeasible="stop", soft_weight=None, jacobian="fd_literal", max_slots=256, device=None,
                  joint_limits=None, min_clearance=None, audit_substeps=16):
-        if select not in SELECT:
-            raise ValueError(f"select must be one of {SELECT}, not {select!r}")
-        if not _is_int(num_seed) or not 1 <= num_seed <= MAX_SEEDS:
-            raise ValueError(f"num_seed must be an integer in 1..{MAX_SEEDS}, not {num_seed!r}")
-        if not _is_int(max_slots) or max_slots < 1:
-            raise ValueError(f"max_slots must be a positive integer, not {max_slots!r}")
-        if not isinstance(mode, str) or mode not in _lib.MODE:
-            raise ValueError(f"mode must be one of {sorted(_lib.MODE)}, not {mode!r}")
+        _args.one_of(SELECT, select, "select")
+        _args.int_in(num_seed, "num_seed", 1, MAX_SEEDS)
+        _args.int_in(max_slots, "max_slots", 1)
+        _args.one_of(_lib.MODE, mode, "mode")
         if rrt_solver not in ("RRT", "RRT*"):
             raise ValueError(f"rrt_solver must be 'RRT' or 'RRT*', not {rrt_solver!r}")
         if ROBOT != "M200i":
             raise ValueError(f"the cost family is RRTstar_CFS.m's (M200i); ROBOT={ROBOT!r} is not supported")
         if int(getattr(sys_rrt, "nstate", 0)) != 5:
             raise ValueError("sys_rrt.nstate must be 5 (the M200i's joints)")
-        _jacobian_code(jacobian)
+        _args.code(_lib.JACOBIAN, jacobian, "jacobian")
         _infeasible_args(on_infeasible, soft_weight)
         lim = _joint_limits_array(joint_limits, robotproperty2("M200i"), 5)
         self._ik_limits = lim if lim is not None else "robot"                       # plan_to_pose: the planner's ranges, else robot.thetamax
@@ -112,21 +97,13 @@ class RRTCFSPlanner:
         for o in pobs:
             if "mesh" in o and not all(isinstance(o.get(k), numbers.Real) and math.isfinite(o[k]) and o[k] > 0 for k in ("D", "epsilon")):
                 raise ValueError("a mesh obstacle needs finite D and epsilon > 0")
-        if min_clearance is not None:
-            if isinstance(min_clearance, bool) or not isinstance(min_clearance, numbers.Real) or not math.isfinite(min_clearance) or min_clearance < 0:
-                raise ValueError(f"min_clearance must be None or a finite slack >= 0 in metres, not {min_clearance!r}")
+        if min_clearance is not None and _args.real(min_clearance, "min_clearance", positive=False) < 0:
+            raise ValueError(f"min_clearance must be None or a finite slack >= 0 in metres, not {min_clearance!r}")
         self.min_clearance = None if min_clearance is None else float(min_clearance)
-        self.audit_substeps = _substeps(audit_substeps, "audit_substeps")
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch is not None and torch.cuda.is_available() else torch.device("cuda", 0)
-        elif _is_int(device):
-            device = torch.device("cuda", int(device))
-        else:
-            device = torch.device(device)
-            if device.type != "cuda":
-                raise ValueError(f"device must be a CUDA (HIP) device, not {device}")
-            if device.index is None:
-                device = torch.device("cuda", 0)
+        self.audit_substeps = _args.int_in(audit_substeps, "audit_substeps", 1, 64)
+        if device is None:                                                          # torch's current device
+            device = torch.cuda.current_device() if torch is not None and torch.cuda.is_available() else 0
+        device = _args.cuda_device(device)
         self.select, self.K, self.max_slots, self.mode = select, int(num_seed), int(max_slots), mode
         self.on_infeasible, self.device, self.nj = on_infeasible, device, 5
         self.rrt = RRT_FANUC(pobs, sys_rrt, sys_rrt.goal_th, region_g, region_s, sample_off, ROBOT, rrt_solver)
@@ -145,22 +122,30 @@ class RRTCFSPlanner:
         self.cfs.close()
 
     # ---- argument checks (no GPU call before they pass) --------------------------------------------------------------------
+    def _conv(self, v, name, cols, nonzero=False):
+        """v as a float64 tensor (given a tensor on the planner's device) or a finite numpy array (goes to the device once validated)
+        of shape (cols,) or (S, cols); nonzero: no row of an array may be zero"""
+        if torch is not None and isinstance(v, torch.Tensor):
+            if v.device != self.device:
+                raise ValueError(f"{name} is on {v.device}, the planner on {self.device}")
+            if not v.dtype.is_floating_point:
+                raise ValueError(f"{name} must be a floating-point tensor, not {v.dtype}")
+            t = v.to(torch.float64)
+        else:
+            try:
+                t = np.array(v, dtype=float)
+            except (TypeError, ValueError):
+                raise ValueError(f"{name} must be numeric") from None
+            if not np.isfinite(t).all():
+                raise ValueError(f"{name} must be finite")
+            if nonzero and t.ndim in (1, 2) and t.shape[-1] == cols and not (np.linalg.norm(t.reshape(-1, cols), axis=1) > 0).all():
+                raise ValueError(f"a {name} row is zero")
+        if t.ndim not in (1, 2) or t.shape[-1] != cols:
+            raise ValueError(f"{name} must have shape ({cols},) or (S, {cols}), not {tuple(t.shape)}")
+        return t
+
     def _pair(self, x0, goal):
-        def conv(v, name):
-            if torch is not None and isinstance(v, torch.Tensor):
-                if v.device != self.device:
-                    raise ValueError(f"{name} is on {v.device}, the planner on {self.device}")
-                if not v.dtype.is_floating_point:
-                    raise ValueError(f"{name} must be a floating-point tensor, not {v.dtype}")
-                t = v.to(torch.float64)
-            else:
-                t = np.asarray(v, dtype=float)          # goes to the device once validated
-                if not np.isfinite(t).all():
-                    raise ValueError(f"{name} must be finite")
-            if tuple(t.shape[-1:]) != (self.nj,) or t.ndim not in (1, 2):
-                raise ValueError(f"{name} must have shape ({self.nj},) or (S, {self.nj}), not {tuple(t.shape)}")
-            return t
-        x0, goal = conv(x0, "x0"), conv(goal, "goal")
+        x0, goal = self._conv(x0, "x0", self.nj), self._conv(goal, "goal", self.nj)
         S = max(x0.shape[0] if x0.ndim == 2 else 1, goal.shape[0] if goal.ndim == 2 else 1)
         for t, name in ((x0, "x0"), (goal, "goal")):
             if t.ndim == 2 and t.shape[0] != S:
@@ -215,48 +200,26 @@ class RRTCFSPlanner:
                 approach_options = {}
             if not isinstance(approach_options, dict) or set(approach_options) - {"max_iter", "max_joint_step"}:
                 raise ValueError("approach_options must be a dict of CartesianPath's max_iter, max_joint_step")
-        if not _is_int(approach_steps) or not 1 <= approach_steps <= MAX_STEPS:
-            raise ValueError(f"approach_steps must be an integer in 1..{MAX_STEPS}, not {approach_steps!r}")
+        _args.int_in(approach_steps, "approach_steps", 1, MAX_STEPS)
         if not isinstance(ik_meshes, bool):
             raise ValueError(f"ik_meshes must be True or False, not {ik_meshes!r}")
         if self._meshes and not ik_meshes:
             raise ValueError("plan_to_pose on a planner with mesh obstacles needs ik_meshes=True: the default IK collision test reads "
                              "line obstacles only")
-        if not _is_int(seed) or seed < 0:
-            raise ValueError(f"seed must be a non-negative integer, not {seed!r}")
+        _args.int_in(seed, "seed", 0)
         if ik_options is None:
             ik_options = {}
         if not isinstance(ik_options, dict) or set(ik_options) - {"tool", "tool_axis", "restarts", "max_iter", "tol_pos", "tol_axis", "weight"}:
             raise ValueError("ik_options must be a dict of IKSolver's tool, tool_axis, restarts, max_iter, tol_pos, tol_axis, weight")
         stream = plan_kwargs.get("stream")
-        if stream is not None and not isinstance(stream, torch.cuda.Stream):
-            raise ValueError("stream must be a torch.cuda.Stream")
-
-        def conv(v, name, cols, nonzero=False):
-            if torch is not None and isinstance(v, torch.Tensor):
-                if v.device != self.device:
-                    raise ValueError(f"{name} is on {v.device}, the planner on {self.device}")
-                if not v.dtype.is_floating_point:
-                    raise ValueError(f"{name} must be a floating-point tensor, not {v.dtype}")
-                t = v.to(torch.float64)
-            else:
-                try:
-                    t = np.array(v, dtype=float)
-                except (TypeError, ValueError):
-                    raise ValueError(f"{name} must be numeric") from None
-                if not np.isfinite(t).all():
-                    raise ValueError(f"{name} must be finite")
-                if nonzero and t.ndim in (1, 2) and t.shape[-1] == cols and not (np.linalg.norm(t.reshape(-1, cols), axis=1) > 0).all():
-                    raise ValueError(f"a {name} row is zero")
-            if t.ndim not in (1, 2) or t.shape[-1] != cols:
-                raise ValueError(f"{name} must have shape ({cols},) or (S, {cols}), not {tuple(t.shape)}")
-            return t
-        args = [conv(x0, "x0", self.nj), conv(target_pos, "target_pos", 3)]
+        if stream is not None:
+            _args.as_stream(stream, self.device)
+        args = [self._conv(x0, "x0", self.nj), self._conv(target_pos, "target_pos", 3)]
         if target_axis is not None:
-            args.append(conv(target_axis, "target_axis", 3, nonzero=True))
+            args.append(self._conv(target_axis, "target_axis", 3, nonzero=True))
         adir = dist = None
         if approach is not None:
-            adir = args[2] if approach_dir is None else conv(approach_dir, "approach_dir", 3, nonzero=True)
+            adir = args[2] if approach_dir is None else self._conv(approach_dir, "approach_dir", 3, nonzero=True)
             if torch is not None and isinstance(approach, torch.Tensor):
                 if approach.device != self.device or not approach.dtype.is_floating_point or approach.ndim > 1:
                     raise ValueError(f"approach must be a floating-point tensor of shape () or (S,) on {self.device}")
@@ -290,38 +253,34 @@ class RRTCFSPlanner:
                 self._ik[ckey] = CartesianPath(self._sys_rrt.robot, [o for o in self._pobs], joint_limits=self._ik_limits, njoint=self.nj,
                                                device=self.device, steps=int(approach_steps), **shared, **approach_options)
             cart = self._ik[ckey]
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
-        if approach is not None:
-            with torch.cuda.device(self.device), torch.cuda.stream(stream):
-                dev = [self._on_device(a, S) for a in args]
+        stream = _args.as_stream(stream, self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            dev = [self._on_device(a, S) for a in args]
+            x0, tp, ta = dev[0], dev[1], dev[2] if len(dev) > 2 else None
+            if approach is None:                              # `src` supplies ok and goal: the IK launch, or the trace behind it
+                src = sol = ik.solve_device(tp, ta, x0, seed=int(seed), stream=stream)
+                more = {}
+            else:
                 u = self._on_device(adir, S)
                 u = u / torch.linalg.norm(u, dim=1, keepdim=True)
                 dd = dist if isinstance(dist, torch.Tensor) else torch.tensor(dist, dtype=torch.float64, device=self.device)
-                pre = (dev[1] - dd.reshape(-1, 1) * u).contiguous()
-                sol = ik.solve_device(pre, dev[2], dev[0], seed=int(seed), want_candidates=True, stream=stream)
-                tr = cart.trace_device(sol.cand_theta, dev[1], dev[2], dev[0], start_state=sol.cand_status, stream=stream)
-                ik_ok, ok = sol.status == 0, tr.status == 0
-                goal = torch.where(ok[:, None], tr.theta, dev[0])
-                res = self.plan(dev[0], goal, seed, **dict(plan_kwargs, stream=stream))
-                masked = torch.where(ik_ok, torch.full_like(res.status, -3), torch.full_like(res.status, -2))
-                res.status = torch.where(ok, res.status, masked)
-                res.has_solution = torch.where(ok, res.has_solution, torch.zeros_like(res.has_solution))
-                res.selected = torch.where(ok, res.selected, torch.full_like(res.selected, -1))
-                res.goal, res.ik_goal, res.ik_status, res.ik_err_pos, res.ik_clearance = tr.theta, sol.theta, sol.status, sol.err_pos, sol.clearance
-                res.approach_path, res.grasp, res.approach_status = tr.path, tr.path[:, -1], tr.status
-                res.approach_clearance, res.approach_selected = tr.clearance, tr.selected
-            return res
-        with torch.cuda.device(self.device), torch.cuda.stream(stream):
-            dev = [self._on_device(a, S) for a in args]
-            sol = ik.solve_device(dev[1], dev[2] if len(dev) > 2 else None, dev[0], seed=int(seed), stream=stream)
-            ok = sol.status == 0
-            goal = torch.where(ok[:, None], sol.theta, dev[0])
-            res = self.plan(dev[0], goal, seed, **dict(plan_kwargs, stream=stream))
-            res.status = torch.where(ok, res.status, torch.full_like(res.status, -2))
+                pre = (tp - dd.reshape(-1, 1) * u).contiguous()
+                sol = ik.solve_device(pre, ta, x0, seed=int(seed), want_candidates=True, stream=stream)
+                src = cart.trace_device(sol.cand_theta, tp, ta, x0, start_state=sol.cand_status, stream=stream)
+                ik_ok = sol.status == 0
+                more = dict(ik_goal=sol.theta, approach_path=src.path, grasp=src.path[:, -1], approach_status=src.status,
+                            approach_clearance=src.clearance, approach_selected=src.selected)
+            ok = src.status == 0
+            goal = torch.where(ok[:, None], src.theta, x0)
+            res = self.plan(x0, goal, seed, **dict(plan_kwargs, stream=stream))
+            masked = torch.full_like(res.status, -2)          # a slot without a goal is masked: -2 no IK solution, -3 no approach
+            if approach is not None:
+                masked = torch.where(ik_ok, torch.full_like(res.status, -3), masked)
+            res.status = torch.where(ok, res.status, masked)
             res.has_solution = torch.where(ok, res.has_solution, torch.zeros_like(res.has_solution))
             res.selected = torch.where(ok, res.selected, torch.full_like(res.selected, -1))
-            res.goal, res.ik_status, res.ik_err_pos, res.ik_clearance = sol.theta, sol.status, sol.err_pos, sol.clearance
+            res.goal, res.ik_status, res.ik_err_pos, res.ik_clearance = src.theta, sol.status, sol.err_pos, sol.clearance
+            vars(res).update(more)
         return res
 
     # ---- the pipeline ----------------------------------------------------------------------------------------------------
@@ -338,19 +297,14 @@ class RRTCFSPlanner:
         want_candidates: also .candidates -- the S*K solve outputs (select="best"), route, route_len, route_ok of every seed.
         timings: a dict to receive the milliseconds of the grow / build / solve / select parts (events on the stream; with
         min_clearance also audit)."""
-        if not _is_int(seed) or seed < 0:
-            raise ValueError(f"seed must be a non-negative integer, not {seed!r}")
-        if not _is_int(max_rounds) or max_rounds < 1:
-            raise ValueError(f"max_rounds must be a positive integer, not {max_rounds!r}")
-        if max_draws is not None and (not _is_int(max_draws) or max_draws < 1):
-            raise ValueError(f"max_draws must be a positive integer, not {max_draws!r}")
+        _args.int_in(seed, "seed", 0)
+        _args.int_in(max_rounds, "max_rounds", 1)
+        if max_draws is not None:
+            _args.int_in(max_draws, "max_draws", 1)
         if timings is not None and not isinstance(timings, dict):
             raise ValueError("timings must be a dict")
         S, x0, goal = self._pair(x0, goal)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
-        elif not isinstance(stream, torch.cuda.Stream):
-            raise ValueError("stream must be a torch.cuda.Stream")
+        stream = _args.as_stream(stream, self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(stream):
             return self._plan(S, self._on_device(x0, S), self._on_device(goal, S), int(seed), int(max_rounds), stream,
                               want_candidates, max_draws, timings)
@@ -435,7 +389,7 @@ class RRTCFSPlanner:
             # candidate, without a solution (cfs_select_best_device itself is unchanged)
             best, plain = pick(rows_ok * clear_ok.to(torch.int32)), pick(rows_ok)
             fall = (best.selected < 0) & (plain.selected >= 0)
-            for name in ("u", "x_", "cost_all", "e_cost_all", "e_u_all", "iter_O", "total_iter", "status", "selected") + (("viol",) if viol is not None else ()):
+            for name in tuple(SOLVE_OUT) + ("selected",) + (("viol",) if viol is not None else ()):
                 a, b2 = getattr(best, name), getattr(plain, name)
                 setattr(best, name, torch.where(fall.view(-1, *([1] * (a.ndim - 1))), b2, a))
             best.has_solution = torch.where(fall, torch.zeros_like(best.has_solution), best.has_solution)
@@ -467,8 +421,7 @@ class RRTCFSPlanner:
         if want_candidates:
             c = SimpleNamespace(route=route, route_len=route_len, route_ok=route_ok)
             if self.select == "best":
-                c.u, c.x_, c.cost_all, c.e_cost_all, c.e_u_all = cand.u, cand.x_, cand.cost_all, cand.e_cost_all, cand.e_u_all
-                c.iter_O, c.total_iter, c.status = cand.iter_O, cand.total_iter, cand.status
+                vars(c).update({k: getattr(cand, k) for k in SOLVE_OUT})
                 if viol is not None:
                     c.viol_all, c.n_soft = viol, n_soft
                 if aud is not None:

@@ -28,9 +28,9 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import f64 as _f64, ptr as _ptr
 from .robotproperty2 import to_c_robot
-from .solvers import _f64, _ptr, obs_meshes, obs_to_array
 
 try:
     import torch
@@ -52,11 +52,7 @@ class RRT_FANUC:
         self.ROBOT, self.SOLVER = ROBOT, SOLVER
         if SOLVER not in ("RRT", "RRT*"):
             raise ValueError("SOLVER must be 'RRT' or 'RRT*'")
-        self._meshes = obs_meshes(obs)                       # ValueError when a mesh precedes a line obstacle
-        lines = [o for o in obs if "mesh" not in o]
-        self._obs_arr = obs_to_array(lines) if len(lines) else np.zeros((0, 6))
-        self._D = _f64([o["D"] for o in lines])
-        self._D_mesh = _f64([o["D"] for o in obs if "mesh" in o])
+        self._obs_arr, self._D, self._meshes, self._D_mesh = _args.split_obs(obs)  # ValueError when a mesh precedes a line obstacle
         if self._meshes:
             if not (np.isfinite(self._D_mesh).all() and (self._D_mesh > 0).all()):
                 raise ValueError("the D of a mesh obstacle must be finite and > 0")
@@ -75,17 +71,15 @@ class RRT_FANUC:
                     goal_th=s.goal_th if goal_th is None else goal_th, region_g=self.region_g, region_s=self.region_s,
                     sample_off=self.sample_off, ratial=s.ratial, obs=self._obs_arr, D=self._D)
         keep = {k: conv(v) for k, v in arrs.items()}
-        for k, v in keep.items():
-            setattr(d, k, _ptr(v))
+        _args.fill(d, SimpleNamespace(**keep))
         d.nobs = int(self._obs_arr.shape[0])
         return d, keep
 
-    def _mesh_args(self, mesh_flags):
-        """(nmesh, handle array, D_mesh pointer, flags) of cfs_rrt_grow_mesh*"""
-        if isinstance(mesh_flags, bool) or not isinstance(mesh_flags, (int, np.integer)) or mesh_flags & ~sum(_lib.RRT_MESH.values()):
+    def _mesh_table(self, mesh_flags):
+        """the mesh table of cfs_rrt_grow_mesh*"""
+        if not _args.is_int(mesh_flags) or mesh_flags & ~sum(_lib.RRT_MESH.values()):
             raise ValueError(f"mesh_flags must be an OR of {_lib.RRT_MESH}, not {mesh_flags!r}")
-        arr = (C.c_void_p * len(self._meshes))(*[m._h for m in self._meshes])
-        return len(self._meshes), arr, _ptr(self._D_mesh), int(mesh_flags)
+        return _args.mesh_table(self._meshes, self._D_mesh, mesh_flags)
 
     # ---- S trees, host arrays in and out (cfs_rrt_grow / cfs_rrt_grow_mesh) ------------------------------------------------
     def grow(self, rngs=None, *, uniforms=None, seed=None, S=None, ndraw=None, max_draws=None, x0=None, goal=None, goal_th=None,
@@ -118,12 +112,10 @@ class RRT_FANUC:
                             nodes=np.zeros((S, N, nj)), total_dis=np.zeros((S, N)), all_ee=np.zeros((S, self.MAX_ITER, 3)),
                             route_len=np.zeros(S, np.int32), route=np.zeros((S, N, nj)), draws_used=np.zeros(S, np.int64),
                             proposals=np.zeros(S, np.int64))
-        o = _lib.cfs_rrt_out()
-        for k in ("node_num", "fail", "parent", "nodes", "total_dis", "all_ee", "route_len", "route", "draws_used", "proposals"):
-            setattr(o, k, _ptr(getattr(r, k)))
+        o = _args.fill(_lib.cfs_rrt_out(), r)
         if self._meshes:
-            nm, arr, Dm, fl = self._mesh_args(mesh_flags)
-            _lib.check(_lib.lib().cfs_rrt_grow_mesh(C.byref(d), nm, arr, Dm, fl, S, C.byref(o)))
+            table = self._mesh_table(mesh_flags)              # refuses bad flags before the library is looked up
+            _lib.check(_lib.lib().cfs_rrt_grow_mesh(C.byref(d), *table, S, C.byref(o)))
         else:
             _lib.check(_lib.lib().cfs_rrt_grow(C.byref(d), S, C.byref(o)))
         out = []
@@ -153,14 +145,11 @@ class RRT_FANUC:
         z = lambda *sh, dt=torch.float64: torch.zeros(*sh, dtype=dt, device=device)  # noqa: E731
         r = SimpleNamespace(node_num=z(S, dt=torch.int32), fail=z(S, dt=torch.int32), route_len=z(S, dt=torch.int32), parent=z(S, N, dt=torch.int32),
                             nodes=z(S, N, nj), total_dis=z(S, N), route=z(S, N, nj), proposals=z(S, dt=torch.int64), _keep=keep)
-        o = _lib.cfs_rrt_out()
-        for k in ("node_num", "fail", "parent", "nodes", "total_dis", "route_len", "route", "proposals"):
-            setattr(o, k, _ptr(getattr(r, k)))
-        if stream is None:
-            stream = torch.cuda.current_stream(device).cuda_stream
+        o = _args.fill(_lib.cfs_rrt_out(), r)
+        stream = _args.stream_ptr(stream, device)
         if self._meshes:
-            nm, arr, Dm, fl = self._mesh_args(mesh_flags)
-            _lib.check(_lib.lib().cfs_rrt_grow_mesh_device(C.byref(d), nm, arr, Dm, fl, S, C.byref(o), C.c_void_p(stream)))
+            table = self._mesh_table(mesh_flags)
+            _lib.check(_lib.lib().cfs_rrt_grow_mesh_device(C.byref(d), *table, S, C.byref(o), C.c_void_p(stream)))
         else:
             _lib.check(_lib.lib().cfs_rrt_grow_device(C.byref(d), S, C.byref(o), C.c_void_p(stream)))
         if not want_tree:

@@ -15,25 +15,14 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import f64 as _f64, obs_meshes, ptr as _ptr  # noqa: F401  (other modules and tests import them from here)
 from .robotproperty2 import to_c_robot
 
 try:
     import torch
 except Exception:  # pragma: no cover
     torch = None
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _ptr(a):
-    if a is None:
-        return None
-    if torch is not None and isinstance(a, torch.Tensor):
-        return C.c_void_p(a.data_ptr())
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def obs_to_array(obs):
@@ -64,26 +53,6 @@ def obs_traj_to_array(obs, H):
     return _f64(out)
 
 
-def obs_meshes(obs):
-    """The Mesh objects of an obs cell; mesh obstacles must come after the line obstacles (cfs_problem_set_meshes)."""
-    flags = ["mesh" in o for o in obs]
-    if any(flags) and flags != sorted(flags):
-        raise ValueError("mesh obstacles must follow the line-segment obstacles in the obs cell")
-    return [o["mesh"] for o in obs if "mesh" in o]
-
-
-def _jacobian_code(jacobian):
-    if not isinstance(jacobian, str) or jacobian not in _lib.JACOBIAN:
-        raise ValueError(f"jacobian must be one of {sorted(_lib.JACOBIAN)}, not {jacobian!r}")
-    return _lib.JACOBIAN[jacobian]
-
-
-def _motion_code(obstacles):
-    if not isinstance(obstacles, str) or obstacles not in _lib.OBSTACLES:
-        raise ValueError(f"obstacles must be one of {sorted(_lib.OBSTACLES)}, not {obstacles!r}")
-    return _lib.OBSTACLES[obstacles]
-
-
 def _joint_limits_array(joint_limits, robot, nj):
     """None | (nj, 2) float64 [lo, hi] from CFSBatch's joint_limits=: None (no position rows), "robot" (robot.thetamax[:nj]) or an
     (nj, 2) array.  ValueError for anything malformed (wrong shape, NaN, lo >= hi), before the device is touched."""
@@ -109,28 +78,34 @@ def _joint_limits_array(joint_limits, robot, nj):
     return np.ascontiguousarray(a)
 
 
-def _substeps(substeps, name="substeps"):
-    """sub-steps per interval of the clearance audit (cfs_clearance): an integer in 1..64, else ValueError"""
-    if isinstance(substeps, bool) or not isinstance(substeps, (int, np.integer)) or not 1 <= substeps <= 64:
-        raise ValueError(f"{name} must be an integer in 1..64, not {substeps!r}")
-    return int(substeps)
-
-
 def _infeasible_args(on_infeasible, soft_weight):
     """(policy code, weight) for cfs_problem_set_infeasible_policy; ValueError for anything malformed.  "soften" needs a finite
     soft_weight > 0; "stop" ignores a (valid) weight and passes 1.0 when there is none."""
-    if not isinstance(on_infeasible, str) or on_infeasible not in _lib.INFEASIBLE:
-        raise ValueError(f"on_infeasible must be one of {sorted(_lib.INFEASIBLE)}, not {on_infeasible!r}")
+    policy = _args.code(_lib.INFEASIBLE, on_infeasible, "on_infeasible")
     if soft_weight is None:
         if on_infeasible == "soften":
             raise ValueError('on_infeasible="soften" needs soft_weight= (cost units per m^2 of slack, finite and > 0)')
-        return _lib.INFEASIBLE[on_infeasible], 1.0
+        return policy, 1.0
     if isinstance(soft_weight, bool) or not isinstance(soft_weight, (int, float, np.integer, np.floating)):
         raise ValueError(f"soft_weight must be a real number, not {soft_weight!r}")
     w = float(soft_weight)
     if not (math.isfinite(w) and w > 0.0):
         raise ValueError(f"soft_weight must be finite and > 0, not {soft_weight!r}")
-    return _lib.INFEASIBLE[on_infeasible], w
+    return policy, w
+
+
+# cfs_batch_out: field -> (the handle's attribute that holds its row length, None for one entry per problem; dtype)
+SOLVE_OUT = dict(u=("nn", np.float64), x_=("nx", np.float64), cost_all=("K", np.float64), e_cost_all=("K", np.float64),
+                 e_u_all=("K", np.float64), iter_O=(None, np.int32), total_iter=(None, np.int32), status=(None, np.int32))
+# the (B, nobs) outputs of the clearance audits in argument order; tri_path is cfs_clearance_mesh*'s alone
+AUDIT_OUT = dict(dist_wp=np.float64, dist_path=np.float64, dist_lower=np.float64, t_path=np.float64, link_path=np.int32,
+                 tri_path=np.int32)
+
+
+def _batch_in(B, x_init, xR1, ff, caug, obs, noise=None):
+    """cfs_batch_in over host arrays or CUDA tensors"""
+    return _lib.cfs_batch_in(B=B, x_init=_ptr(x_init), xR1=_ptr(xR1), ff=_ptr(ff), caug=_ptr(caug), obs=_ptr(obs), noise=_ptr(noise),
+                             noise_rows=0 if noise is None else noise.shape[1])
 
 
 class CFSBatch:
@@ -156,9 +131,9 @@ class CFSBatch:
         with cfs_problem_family) and alpha agrees; a sys_info whose QQ / Baug were edited after build_sys_info is solved
         through the dense path with the dynamics check, exactly as given."""
         s = sys_info
-        _jacobian_code(jacobian)                         # validated before anything touches the device
+        _args.code(_lib.JACOBIAN, jacobian, "jacobian")  # validated before anything touches the device
         _infeasible_args(on_infeasible, soft_weight)
-        _motion_code(obstacles)
+        _args.code(_lib.OBSTACLES, obstacles, "obstacles")
         jl = _joint_limits_array(joint_limits, s.robot, int(s.njoint))
         self.mode = mode
         self.H, self.nj = int(s.H), int(s.njoint)
@@ -249,14 +224,13 @@ class CFSBatch:
 
     def set_obstacle_motion(self, obstacles):
         """obstacles of the following solves and pieces: "static" | "per_waypoint" (cfs_problem_set_obstacle_motion)."""
-        code = _motion_code(obstacles)
-        _lib.check(self._lib.cfs_problem_set_obstacle_motion(self._h, code))
+        _lib.check(self._lib.cfs_problem_set_obstacle_motion(self._h, _args.code(_lib.OBSTACLES, obstacles, "obstacles")))
 
     @property
     def obstacle_motion(self):
         m = C.c_int(0)
         _lib.check(self._lib.cfs_problem_get_obstacle_motion(self._h, C.byref(m)))
-        return {v: k for k, v in _lib.OBSTACLES.items()}[m.value]
+        return _args.name_of(_lib.OBSTACLES, m.value)
 
     def _check_obs(self, obs, B):
         """obs must be (B, nobs, 6) on a static handle (assert, as ever) and (B, H, nobs, 6) on a per-waypoint one (ValueError)."""
@@ -276,7 +250,7 @@ class CFSBatch:
         """(policy, soft_weight) as last set; the weight is None under "stop"."""
         m, w = C.c_int(0), C.c_double(0.0)
         _lib.check(self._lib.cfs_problem_get_infeasible_policy(self._h, C.byref(m), C.byref(w)))
-        name = {v: k for k, v in _lib.INFEASIBLE.items()}[m.value]
+        name = _args.name_of(_lib.INFEASIBLE, m.value)
         return name, (w.value if name == "soften" else None)
 
     def soft_results(self, B):
@@ -287,13 +261,13 @@ class CFSBatch:
 
     def set_jacobian(self, jacobian):
         """linearisation of the line obstacles for the following solves and pieces: "fd_literal" | "analytic"."""
-        _lib.check(self._lib.cfs_problem_set_jacobian(self._h, _jacobian_code(jacobian)))
+        _lib.check(self._lib.cfs_problem_set_jacobian(self._h, _args.code(_lib.JACOBIAN, jacobian, "jacobian")))
 
     @property
     def jacobian(self):
         m = C.c_int(0)
         _lib.check(self._lib.cfs_problem_get_jacobian(self._h, C.byref(m)))
-        return {v: k for k, v in _lib.JACOBIAN.items()}[m.value]
+        return _args.name_of(_lib.JACOBIAN, m.value)
 
     def _weights_match(self, s):
         """does the QQ (and alpha) the library assembled from sys_info.weights equal what sys_info carries?"""
@@ -353,10 +327,14 @@ class CFSBatch:
         if len(meshes) and self.obstacle_motion == "per_waypoint":
             raise ValueError("mesh obstacles are static: not supported on a per-waypoint handle")
         self._meshes = list(meshes)                      # keep them alive as long as the handle uses them
-        arr = (C.c_void_p * max(len(self._meshes), 1))(*[m._h for m in self._meshes])
-        _lib.check(self._lib.cfs_problem_set_meshes(self._h, len(self._meshes), arr))
+        _lib.check(self._lib.cfs_problem_set_meshes(self._h, *_args.mesh_table(self._meshes)[:2]))
 
     # ---- whole solve ------------------------------------------------------------------------------
+    def _outputs(self, B, device=None):
+        """the cfs_batch_out namespace for B problems: numpy arrays, or torch tensors on `device`"""
+        z = _args.zeros_on(device)
+        return SimpleNamespace(**{k: z((B,) if n is None else (B, getattr(self, n)), dt) for k, (n, dt) in SOLVE_OUT.items()})
+
     def solve(self, x_init, xR1, ff, caug, obs, noise=None):
         """Host arrays in, host arrays out (cfs_solve_batch)."""
         x_init, xR1, ff, caug, obs = _f64(x_init), _f64(xR1), _f64(ff), _f64(caug).reshape(-1), _f64(obs)
@@ -364,29 +342,18 @@ class CFSBatch:
         assert x_init.shape == (B, self.nx) and xR1.shape == (B, self.ns) and ff.shape == (B, self.nn)
         assert caug.shape == (B,)
         self._check_obs(obs, B)
-        i = _lib.cfs_batch_in()
-        i.B = B
-        i.x_init, i.xR1, i.ff, i.caug, i.obs = _ptr(x_init), _ptr(xR1), _ptr(ff), _ptr(caug), _ptr(obs)
         if noise is not None:
             noise = _f64(noise)
             assert noise.ndim == 3 and noise.shape[0] == B and noise.shape[2] == self.nn
-            i.noise, i.noise_rows = _ptr(noise), noise.shape[1]
-        r = SimpleNamespace(u=np.zeros((B, self.nn)), x_=np.zeros((B, self.nx)), cost_all=np.zeros((B, self.K)),
-                            e_cost_all=np.zeros((B, self.K)), e_u_all=np.zeros((B, self.K)),
-                            iter_O=np.zeros(B, np.int32), total_iter=np.zeros(B, np.int32), status=np.zeros(B, np.int32))
-        o = _lib.cfs_batch_out()
-        o.u, o.x_, o.cost_all, o.e_cost_all, o.e_u_all = _ptr(r.u), _ptr(r.x_), _ptr(r.cost_all), _ptr(r.e_cost_all), _ptr(r.e_u_all)
-        o.iter_O, o.total_iter, o.status = _ptr(r.iter_O), _ptr(r.total_iter), _ptr(r.status)
+        r = self._outputs(B)
+        i, o = _batch_in(B, x_init, xR1, ff, caug, obs, noise), _args.fill(_lib.cfs_batch_out(), r)
         _lib.check(self._lib.cfs_solve_batch(self._h, C.byref(i), C.byref(o)))
         r.viol_all, r.n_soft = self.soft_results(B)
         return r
 
     def alloc_outputs(self, B, device):
         """Device-resident output buffers (torch CUDA tensors) for solve_device."""
-        z = lambda *shape, dt=torch.float64: torch.zeros(*shape, dtype=dt, device=device)  # noqa: E731
-        return SimpleNamespace(u=z(B, self.nn), x_=z(B, self.nx), cost_all=z(B, self.K), e_cost_all=z(B, self.K),
-                               e_u_all=z(B, self.K), iter_O=z(B, dt=torch.int32), total_iter=z(B, dt=torch.int32),
-                               status=z(B, dt=torch.int32))
+        return self._outputs(B, device)
 
     def solve_device(self, x_init, xR1, ff, caug, obs, noise=None, out=None, stream=None):
         """torch CUDA tensors in/out; enqueues on `stream` (default: torch's current stream) and
@@ -397,70 +364,50 @@ class CFSBatch:
         self._check_obs(obs, B)
         if out is None:
             out = self.alloc_outputs(B, x_init.device)
-        i = _lib.cfs_batch_in()
-        i.B = B
-        i.x_init, i.xR1, i.ff, i.caug, i.obs = _ptr(x_init), _ptr(xR1), _ptr(ff), _ptr(caug), _ptr(obs)
-        if noise is not None:
-            i.noise, i.noise_rows = _ptr(noise), noise.shape[1]
-        o = _lib.cfs_batch_out()
-        o.u, o.x_, o.cost_all, o.e_cost_all, o.e_u_all = _ptr(out.u), _ptr(out.x_), _ptr(out.cost_all), _ptr(out.e_cost_all), _ptr(out.e_u_all)
-        o.iter_O, o.total_iter, o.status = _ptr(out.iter_O), _ptr(out.total_iter), _ptr(out.status)
-        if stream is None:
-            stream = torch.cuda.current_stream(x_init.device).cuda_stream
+        i, o = _batch_in(B, x_init, xR1, ff, caug, obs, noise), _args.fill(_lib.cfs_batch_out(), out)
+        stream = _args.stream_ptr(stream, x_init.device)
         _lib.check(self._lib.cfs_solve_batch_device(self._h, C.byref(i), C.byref(o), C.c_void_p(stream)))
         return out
 
-    # ---- clearance audit between the waypoints ---------------------------------------------------------
-    def _check_audit(self, substeps):
-        S = _substeps(substeps)
-        if getattr(self, "_meshes", None):
+    # ---- clearance audit between the waypoints, against line obstacles or with mesh obstacles -------------------------
+    def _audit(self, mesh, device, x_, u, xR1, obs, substeps, out=None, stream=None):
+        """the four audit entries: cfs_clearance[_mesh][_device].  The line audit takes the obs shape of the handle's obstacle
+        motion (_check_obs); the mesh audit is static, (B, nobs, 6), and never asks the handle."""
+        S = _args.int_in(substeps, "substeps", 1, 64)
+        if mesh and not getattr(self, "_meshes", None):
+            raise ValueError("clearance_mesh needs a handle with mesh obstacles (set_meshes): use clearance for line obstacles")
+        if not mesh and getattr(self, "_meshes", None):
             raise ValueError("the clearance audit measures line obstacles only: this handle has mesh obstacles")
-        return S
-
-    def clearance(self, x_, u, xR1, obs, substeps=16):
-        """Clearance of B trajectories (x_, u as a solve returns them; xR1, obs as given to it) along the motion between the
-        waypoints, `substeps` samples per interval (cfs_clearance, include/cfs_hip.h); host arrays in and out.  Returns a
-        namespace of (B, nobs) arrays dist_wp (min at the waypoints), dist_path (min over all samples), dist_lower (certified
-        lower bound over continuous time), t_path (s) / link_path (1-based) of the first path minimum, and short_by (B,) =
-        max_j(margin_j - dist_path[:, j]): how far the motion falls short of the handle's margins (<= 0: it keeps them)."""
-        S = self._check_audit(substeps)
-        x_, u, xR1, obs = _f64(x_), _f64(u), _f64(xR1), _f64(obs)
-        B = x_.shape[0]
-        if x_.shape != (B, self.nx) or u.shape != (B, self.nn) or xR1.shape != (B, self.ns):
-            raise ValueError(f"x_, u, xR1 must have shapes {(B, self.nx)}, {(B, self.nn)}, {(B, self.ns)}, not {x_.shape}, {u.shape}, {xR1.shape}")
-        self._check_obs(obs, B)
-        z = lambda dt=np.float64: np.zeros((B, self.nobs), dt)  # noqa: E731
-        r = SimpleNamespace(dist_wp=z(), dist_path=z(), dist_lower=z(), t_path=z(), link_path=z(np.int32))
-        _lib.check(self._lib.cfs_clearance(self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs), _ptr(r.dist_wp), _ptr(r.dist_path),
-                                           _ptr(r.dist_lower), _ptr(r.t_path), _ptr(r.link_path)))
-        r.short_by = (self.margin[None, :] - r.dist_path).max(axis=1)
-        return r
-
-    def alloc_clearance(self, B, device):
-        """Device-resident output buffers (torch CUDA tensors) for clearance_device."""
-        z = lambda dt=torch.float64: torch.zeros(B, self.nobs, dtype=dt, device=device)  # noqa: E731
-        return SimpleNamespace(dist_wp=z(), dist_path=z(), dist_lower=z(), t_path=z(), link_path=z(torch.int32))
-
-    def clearance_device(self, x_, u, xR1, obs, substeps=16, out=None, stream=None):
-        """clearance() on torch CUDA tensors; enqueues on `stream` (default: torch's current stream) and returns without
-        synchronising (cfs_clearance_device).  out: an alloc_clearance namespace to write into."""
-        S = self._check_audit(substeps)
-        B = x_.shape[0]
-        for t in (x_, u, xR1, obs):
-            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-        if tuple(x_.shape) != (B, self.nx) or tuple(u.shape) != (B, self.nn) or tuple(xR1.shape) != (B, self.ns):
-            raise ValueError(f"x_, u, xR1 must have shapes {(B, self.nx)}, {(B, self.nn)}, {(B, self.ns)}")
-        self._check_obs(obs, B)
-        if out is None:
-            out = self.alloc_clearance(B, x_.device)
-        for t, dt in ((out.dist_wp, torch.float64), (out.dist_path, torch.float64), (out.dist_lower, torch.float64),
-                      (out.t_path, torch.float64), (out.link_path, torch.int32)):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (B, self.nobs)
+        if device:
+            B = x_.shape[0]
+            for t in (x_, u, xR1, obs):
+                assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+        else:
+            x_, u, xR1, obs = _f64(x_), _f64(u), _f64(xR1), _f64(obs)
+            B = x_.shape[0]
+        want = [(B, self.nx), (B, self.nn), (B, self.ns)] + ([(B, self.nobs, 6)] if mesh else [])
+        got = [tuple(t.shape) for t in (x_, u, xR1, obs)[:len(want)]]
+        if got != want:
+            raise ValueError(f"x_, u, xR1{', obs' if mesh else ''} must have shapes {want}, not {got}")
+        if not mesh:
+            self._check_obs(obs, B)
+        names = [k for k in AUDIT_OUT if mesh or k != "tri_path"]
+        if not device:
+            out = SimpleNamespace(**{k: np.zeros((B, self.nobs), AUDIT_OUT[k]) for k in names})
+        elif out is None:
+            out = (self.alloc_clearance_mesh if mesh else self.alloc_clearance)(B, x_.device)
+        args = [self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs)] + [_ptr(getattr(out, k)) for k in names]
+        entry = "cfs_clearance_mesh" if mesh else "cfs_clearance"
+        if not device:
+            _lib.check(getattr(self._lib, entry)(*args))
+            out.short_by = (self.margin[None, :] - out.dist_path).max(axis=1)
+            return out
+        for k in names:
+            t = getattr(out, k)
+            assert t.is_cuda and t.dtype == getattr(torch, np.dtype(AUDIT_OUT[k]).name) and t.is_contiguous() and tuple(t.shape) == (B, self.nobs)
         cur = torch.cuda.current_stream(x_.device)
         sp = cur.cuda_stream if stream is None else int(stream)
-        _lib.check(self._lib.cfs_clearance_device(self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs), _ptr(out.dist_wp),
-                                                  _ptr(out.dist_path), _ptr(out.dist_lower), _ptr(out.t_path), _ptr(out.link_path),
-                                                  C.c_void_p(sp)))
+        _lib.check(getattr(self._lib, entry + "_device")(*args, C.c_void_p(sp)))
         if sp == cur.cuda_stream:
             ts = cur
         else:                            # pointer 0 is the default stream: ExternalStream does not wrap it
@@ -469,31 +416,30 @@ class CFSBatch:
             out.short_by = (self._margin_on(x_.device)[None, :] - out.dist_path).amax(dim=1)
         return out
 
-    # ---- clearance audit with mesh obstacles --------------------------------------------------------------
-    def _check_audit_mesh(self, substeps):
-        S = _substeps(substeps)
-        if not getattr(self, "_meshes", None):
-            raise ValueError("clearance_mesh needs a handle with mesh obstacles (set_meshes): use clearance for line obstacles")
-        return S
+    def clearance(self, x_, u, xR1, obs, substeps=16):
+        """Clearance of B trajectories (x_, u as a solve returns them; xR1, obs as given to it) along the motion between the
+        waypoints, `substeps` samples per interval (cfs_clearance, include/cfs_hip.h); host arrays in and out.  Returns a
+        namespace of (B, nobs) arrays dist_wp (min at the waypoints), dist_path (min over all samples), dist_lower (certified
+        lower bound over continuous time), t_path (s) / link_path (1-based) of the first path minimum, and short_by (B,) =
+        max_j(margin_j - dist_path[:, j]): how far the motion falls short of the handle's margins (<= 0: it keeps them)."""
+        return self._audit(False, False, x_, u, xR1, obs, substeps)
+
+    def alloc_clearance(self, B, device):
+        """Device-resident output buffers (torch CUDA tensors) for clearance_device."""
+        z = _args.zeros_on(device)
+        return SimpleNamespace(**{k: z((B, self.nobs), dt) for k, dt in AUDIT_OUT.items() if k != "tri_path"})
+
+    def clearance_device(self, x_, u, xR1, obs, substeps=16, out=None, stream=None):
+        """clearance() on torch CUDA tensors; enqueues on `stream` (default: torch's current stream) and returns without
+        synchronising (cfs_clearance_device).  out: an alloc_clearance namespace to write into."""
+        return self._audit(False, True, x_, u, xR1, obs, substeps, out, stream)
 
     def clearance_mesh(self, x_, u, xR1, obs, substeps=16):
         """clearance() for a handle with mesh obstacles (cfs_clearance_mesh, include/cfs_hip.h); host arrays in and out.  The
         (B, nobs) arrays are in the handle's obstacle order (lines first, then the meshes): dist_wp, dist_path, dist_lower,
         t_path, link_path as in clearance(), and tri_path, the index in the caller's triangle list of a closest triangle at the
         dist_path sample (-1 in line columns); short_by (B,) = max_j(margin_j - dist_path[:, j]) over all columns."""
-        S = self._check_audit_mesh(substeps)
-        x_, u, xR1, obs = _f64(x_), _f64(u), _f64(xR1), _f64(obs)
-        B = x_.shape[0]
-        if x_.shape != (B, self.nx) or u.shape != (B, self.nn) or xR1.shape != (B, self.ns) or obs.shape != (B, self.nobs, 6):
-            raise ValueError(f"x_, u, xR1, obs must have shapes {(B, self.nx)}, {(B, self.nn)}, {(B, self.ns)}, {(B, self.nobs, 6)}, "
-                             f"not {x_.shape}, {u.shape}, {xR1.shape}, {obs.shape}")
-        z = lambda dt=np.float64: np.zeros((B, self.nobs), dt)  # noqa: E731
-        r = SimpleNamespace(dist_wp=z(), dist_path=z(), dist_lower=z(), t_path=z(), link_path=z(np.int32), tri_path=z(np.int32))
-        _lib.check(self._lib.cfs_clearance_mesh(self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs), _ptr(r.dist_wp),
-                                                _ptr(r.dist_path), _ptr(r.dist_lower), _ptr(r.t_path), _ptr(r.link_path),
-                                                _ptr(r.tri_path)))
-        r.short_by = (self.margin[None, :] - r.dist_path).max(axis=1)
-        return r
+        return self._audit(True, False, x_, u, xR1, obs, substeps)
 
     def alloc_clearance_mesh(self, B, device):
         """Device-resident output buffers (torch CUDA tensors) for clearance_mesh_device."""
@@ -504,30 +450,7 @@ class CFSBatch:
     def clearance_mesh_device(self, x_, u, xR1, obs, substeps=16, out=None, stream=None):
         """clearance_mesh() on torch CUDA tensors; enqueues on `stream` (default: torch's current stream) and returns without
         synchronising (cfs_clearance_mesh_device).  out: an alloc_clearance_mesh namespace to write into."""
-        S = self._check_audit_mesh(substeps)
-        B = x_.shape[0]
-        for t in (x_, u, xR1, obs):
-            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-        if (tuple(x_.shape) != (B, self.nx) or tuple(u.shape) != (B, self.nn) or tuple(xR1.shape) != (B, self.ns)
-                or tuple(obs.shape) != (B, self.nobs, 6)):
-            raise ValueError(f"x_, u, xR1, obs must have shapes {(B, self.nx)}, {(B, self.nn)}, {(B, self.ns)}, {(B, self.nobs, 6)}")
-        if out is None:
-            out = self.alloc_clearance_mesh(B, x_.device)
-        for t, dt in ((out.dist_wp, torch.float64), (out.dist_path, torch.float64), (out.dist_lower, torch.float64),
-                      (out.t_path, torch.float64), (out.link_path, torch.int32), (out.tri_path, torch.int32)):
-            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (B, self.nobs)
-        cur = torch.cuda.current_stream(x_.device)
-        sp = cur.cuda_stream if stream is None else int(stream)
-        _lib.check(self._lib.cfs_clearance_mesh_device(self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs), _ptr(out.dist_wp),
-                                                       _ptr(out.dist_path), _ptr(out.dist_lower), _ptr(out.t_path),
-                                                       _ptr(out.link_path), _ptr(out.tri_path), C.c_void_p(sp)))
-        if sp == cur.cuda_stream:
-            ts = cur
-        else:                            # pointer 0 is the default stream: ExternalStream does not wrap it
-            ts = torch.cuda.default_stream(x_.device) if sp == 0 else torch.cuda.ExternalStream(sp, device=x_.device)
-        with torch.cuda.stream(ts):      # short_by on the same stream, after the audit
-            out.short_by = (self._margin_on(x_.device)[None, :] - out.dist_path).amax(dim=1)
-        return out
+        return self._audit(True, True, x_, u, xR1, obs, substeps, out, stream)
 
     def _margin_on(self, device):
         """the handle's margins as a tensor on `device` (uploaded once: no copy is enqueued by later audits)"""
@@ -546,15 +469,8 @@ class CFSBatch:
         B = x_init.shape[0]
         assert x_init.shape == (B, self.nx) and u0.shape == (B, self.nn) and obs.shape == (B, self.nobs, 6)
         assert D.size == self.nobs and epsilon.size == self.nobs
-        i = _lib.cfs_batch_in()
-        i.B = B
-        i.x_init, i.xR1, i.ff, i.caug, i.obs = _ptr(x_init), _ptr(xR1), _ptr(ff), _ptr(caug), _ptr(obs)
-        r = SimpleNamespace(u=np.zeros((B, self.nn)), x_=np.zeros((B, self.nx)), cost_all=np.zeros((B, self.K)),
-                            e_cost_all=np.zeros((B, self.K)), e_u_all=np.zeros((B, self.K)),
-                            iter_O=np.zeros(B, np.int32), total_iter=np.zeros(B, np.int32), status=np.zeros(B, np.int32))
-        o = _lib.cfs_batch_out()
-        o.u, o.x_, o.cost_all, o.e_cost_all, o.e_u_all = _ptr(r.u), _ptr(r.x_), _ptr(r.cost_all), _ptr(r.e_cost_all), _ptr(r.e_u_all)
-        o.iter_O, o.total_iter, o.status = _ptr(r.iter_O), _ptr(r.total_iter), _ptr(r.status)
+        r = self._outputs(B)
+        i, o = _batch_in(B, x_init, xR1, ff, caug, obs), _args.fill(_lib.cfs_batch_out(), r)
         _lib.check(self._lib.cfs_chomp_batch(self._h, C.byref(i), _ptr(u0), _ptr(D), _ptr(epsilon), C.byref(o)))
         return r
 
@@ -565,30 +481,28 @@ class CFSBatch:
         assert q.shape == (self.nx, self.nx)
         _lib.check(self._lib.cfs_set_state_cost(self._h, _ptr(q)))
 
+    def _terms(self, B, device, stream):
+        """((x_init, xR1, ff, caug) uninitialised on `device`, the tail of a build_terms*_device call: their pointers and the stream)"""
+        z = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=device)  # noqa: E731
+        terms = z(B, self.nx), z(B, self.ns), z(B, self.nn), z(B)
+        return terms, [_ptr(t) for t in terms] + [C.c_void_p(_args.stream_ptr(stream, device))]
+
     def build_terms_device(self, x0, xg, stream=None):
         """(x_init, xR1, ff, caug) as CUDA tensors for B (start, goal) pairs given as CUDA tensors (B, njoint)."""
         B = x0.shape[0]
         assert x0.is_cuda and xg.is_cuda and x0.dtype == torch.float64 and x0.is_contiguous() and xg.is_contiguous()
-        z = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=x0.device)  # noqa: E731
-        x_init, xR1, ff, caug = z(B, self.nx), z(B, self.ns), z(B, self.nn), z(B)
-        if stream is None:
-            stream = torch.cuda.current_stream(x0.device).cuda_stream
-        _lib.check(self._lib.cfs_build_terms_device(self._h, B, _ptr(x0), _ptr(xg), _ptr(x_init), _ptr(xR1), _ptr(ff), _ptr(caug),
-                                                    C.c_void_p(stream)))
-        return x_init, xR1, ff, caug
+        terms, tail = self._terms(B, x0.device, stream)
+        _lib.check(self._lib.cfs_build_terms_device(self._h, B, _ptr(x0), _ptr(xg), *tail))
+        return terms
 
     def build_terms_from_routes_device(self, routes, stream=None):
         """(x_init, xR1, ff, caug) for B RRT routes given as a CUDA tensor (B, nwp, njoint): cubic zero-velocity
         resampling to H+1 samples + cost terms, on the device (RRTstar_CFS.m:94-110, 159-163)."""
         B, nwp = routes.shape[0], routes.shape[1]
         assert routes.is_cuda and routes.dtype == torch.float64 and routes.is_contiguous() and routes.shape[2] == self.nj
-        z = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=routes.device)  # noqa: E731
-        x_init, xR1, ff, caug = z(B, self.nx), z(B, self.ns), z(B, self.nn), z(B)
-        if stream is None:
-            stream = torch.cuda.current_stream(routes.device).cuda_stream
-        _lib.check(self._lib.cfs_build_terms_from_routes_device(self._h, B, _ptr(routes), nwp, _ptr(x_init), _ptr(xR1), _ptr(ff),
-                                                                _ptr(caug), C.c_void_p(stream)))
-        return x_init, xR1, ff, caug
+        terms, tail = self._terms(B, routes.device, stream)
+        _lib.check(self._lib.cfs_build_terms_from_routes_device(self._h, B, _ptr(routes), nwp, *tail))
+        return terms
 
     def build_terms_from_ragged_routes_device(self, routes, nwp, stream=None):
         """The same for routes of different lengths as cfs_rrt_grow_device leaves them: routes (B, nwp_stride, njoint) CUDA
@@ -596,13 +510,9 @@ class CFSBatch:
         B, stride = routes.shape[0], routes.shape[1]
         assert routes.is_cuda and routes.dtype == torch.float64 and routes.is_contiguous() and routes.shape[2] == self.nj
         assert nwp.is_cuda and nwp.dtype == torch.int32 and nwp.is_contiguous() and nwp.shape == (B,)
-        z = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=routes.device)  # noqa: E731
-        x_init, xR1, ff, caug = z(B, self.nx), z(B, self.ns), z(B, self.nn), z(B)
-        if stream is None:
-            stream = torch.cuda.current_stream(routes.device).cuda_stream
-        _lib.check(self._lib.cfs_build_terms_from_ragged_routes_device(self._h, B, _ptr(routes), stride, _ptr(nwp), _ptr(x_init), _ptr(xR1),
-                                                                       _ptr(ff), _ptr(caug), C.c_void_p(stream)))
-        return x_init, xR1, ff, caug
+        terms, tail = self._terms(B, routes.device, stream)
+        _lib.check(self._lib.cfs_build_terms_from_ragged_routes_device(self._h, B, _ptr(routes), stride, _ptr(nwp), *tail))
+        return terms
 
     # ---- measurement ------------------------------------------------------------------------------
     def profile(self, on=True):
@@ -729,14 +639,12 @@ def dist_arm(robot, theta, obs_l, want_pos=False, want_grad=False):
     lid = np.zeros((N, nobs), np.int32)
     pos = np.zeros((N, nj, 2, 3)) if want_pos else None
     rb = to_c_robot(robot)
+    grad = np.zeros((N, nobs, nj)) if want_grad else None
     if want_grad:
-        grad = np.zeros((N, nobs, nj))
         _lib.check(_lib.lib().cfs_dist_arm_grad(C.byref(rb), nj, N, _ptr(theta), nobs, _ptr(obs_l), _ptr(d), _ptr(lid), _ptr(grad)))
-        if want_pos:
-            _lib.check(_lib.lib().cfs_dist_arm(C.byref(rb), nj, N, _ptr(theta), nobs, _ptr(obs_l), _ptr(d), _ptr(lid), _ptr(pos)))
-        return (d, lid, pos, grad) if want_pos else (d, lid, grad)
-    _lib.check(_lib.lib().cfs_dist_arm(C.byref(rb), nj, N, _ptr(theta), nobs, _ptr(obs_l), _ptr(d), _ptr(lid), _ptr(pos)))
-    return (d, lid, pos) if want_pos else (d, lid)
+    if want_pos or not want_grad:
+        _lib.check(_lib.lib().cfs_dist_arm(C.byref(rb), nj, N, _ptr(theta), nobs, _ptr(obs_l), _ptr(d), _ptr(lid), _ptr(pos)))
+    return (d, lid) + ((pos,) if want_pos else ()) + ((grad,) if want_grad else ())
 
 
 class EVAL:
@@ -811,22 +719,23 @@ class _SolverBase:
         on_infeasible: "stop" (the default) | "soften" with soft_weight= (CFSBatch); after optimizer(), viol_all and n_soft.
         obs{j}["l"] may be 3x2xH (shape (3, 2, H): the obstacle's axis at waypoints 1..H); any such entry makes the handle
         per-waypoint, and the 3x2 entries are then held over the horizon (obs_traj_to_array)."""
-        _jacobian_code(jacobian)
+        _args.code(_lib.JACOBIAN, jacobian, "jacobian")
         _infeasible_args(on_infeasible, soft_weight)
         _joint_limits_array(joint_limits, sys_info.robot, int(sys_info.njoint))
-        self.audit = None if audit is None else _substeps(audit, "audit")
-        if self.audit is not None and obs_meshes(obs):
+        self.audit = None if audit is None else _args.int_in(audit, "audit", 1, 64)
+        meshes = obs_meshes(obs)
+        if self.audit is not None and meshes:
             raise ValueError("audit= measures line obstacles only: the obs cell holds mesh obstacles")
         self.clearance = None
-        self.audit_mesh = None if audit_mesh is None else _substeps(audit_mesh, "audit_mesh")
-        if self.audit_mesh is not None and not obs_meshes(obs):
+        self.audit_mesh = None if audit_mesh is None else _args.int_in(audit_mesh, "audit_mesh", 1, 64)
+        if self.audit_mesh is not None and not meshes:
             raise ValueError("audit_mesh= needs an obs cell with at least one mesh obstacle: audit= measures line obstacles")
         self.clearance_mesh = None
-        if on_infeasible == "soften" and obs_meshes(obs):
+        if on_infeasible == "soften" and meshes:
             raise ValueError('on_infeasible="soften" does not support mesh obstacles')
         self._moving = obs_moving(obs)
         if self._moving:
-            if obs_meshes(obs):
+            if meshes:
                 raise ValueError("mesh obstacles are static: an obs cell with 3x2xH axes cannot hold meshes")
             obs_traj_to_array(obs, sys_info.H)          # shapes checked before anything touches the device
         self.obs, self.sys_info, self.ROBOT = obs, sys_info, ROBOT
@@ -842,7 +751,6 @@ class _SolverBase:
                                device=device, jacobian=jacobian, on_infeasible=on_infeasible, soft_weight=soft_weight,
                                obstacles="per_waypoint" if self._moving else "static", joint_limits=joint_limits)
         self.viol_all, self.n_soft = np.zeros(0), 0
-        meshes = obs_meshes(obs)
         if meshes:
             self._batch.set_meshes(meshes)
 
@@ -870,15 +778,11 @@ class _SolverBase:
         self.viol_all, self.n_soft = r.viol_all[0, :n], int(r.n_soft[0])
         self.eval.cost_new = float(r.cost_all[0, n - 1]) if n > 0 else float(self.sys_info.caug)
         self.eval.x_ = self.x_
-        if self.audit is not None:
-            c = self._batch.clearance(r.x_, r.u, xR1, obs, substeps=self.audit)
-            self.clearance = SimpleNamespace(dist_wp=c.dist_wp[0], dist_path=c.dist_path[0], dist_lower=c.dist_lower[0],
-                                             t_path=c.t_path[0], link_path=c.link_path[0], short_by=float(c.short_by[0]))
+        row0 = lambda c: SimpleNamespace(**{k: float(v[0]) if v.ndim == 1 else v[0] for k, v in vars(c).items()})  # noqa: E731
+        if self.audit is not None:                       # the one problem's row of every field; short_by (B,) becomes a float
+            self.clearance = row0(self._batch.clearance(r.x_, r.u, xR1, obs, substeps=self.audit))
         if self.audit_mesh is not None:
-            c = self._batch.clearance_mesh(r.x_, r.u, xR1, obs, substeps=self.audit_mesh)
-            self.clearance_mesh = SimpleNamespace(dist_wp=c.dist_wp[0], dist_path=c.dist_path[0], dist_lower=c.dist_lower[0],
-                                                  t_path=c.t_path[0], link_path=c.link_path[0], tri_path=c.tri_path[0],
-                                                  short_by=float(c.short_by[0]))
+            self.clearance_mesh = row0(self._batch.clearance_mesh(r.x_, r.u, xR1, obs, substeps=self.audit_mesh))
         if self.status == 0:
             print(f"Converged at step{self.iter_O}")  # EVAL.m:66
         elif self.status == 1:

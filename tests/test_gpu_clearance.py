@@ -250,3 +250,26 @@ def test_device_entry_behind_a_solve_on_one_stream(gpu, c3, solved3):
     want = h.clearance(r.x_, r.u, bt.xR1, bt.obs, substeps=16)
     for k in OUT + ("short_by",):
         np.testing.assert_array_equal(getattr(aud, k).cpu().numpy(), getattr(want, k), err_msg=k)
+
+
+def test_device_entry_on_a_stream_that_is_not_torchs_current_one(gpu, c3, solved3):
+    """the two stream branches behind short_by: (a) a side stream's pointer while torch's current stream is the default one (the
+    ExternalStream branch), (b) pointer 0 inside a side stream's context (the default-stream branch)"""
+    import torch
+    s, bt = c3
+    h, r = solved3["CFS"]
+    dev = torch.device("cuda:0")
+    t = lambda a: torch.tensor(np.ascontiguousarray(a[:4]), dtype=torch.float64, device=dev)  # noqa: E731
+    args = [t(a) for a in (r.x_, r.u, bt.xR1, bt.obs)]
+    outs = [h.alloc_clearance(4, dev) for _ in range(2)]                 # zeroed before the launches, which run on other streams
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(device=dev)
+    assert torch.cuda.current_stream(dev) == torch.cuda.default_stream(dev)
+    a = h.clearance_device(*args, substeps=16, out=outs[0], stream=side.cuda_stream)
+    with torch.cuda.stream(side):
+        b = h.clearance_device(*args, substeps=16, out=outs[1], stream=0)
+    torch.cuda.synchronize()
+    want = h.clearance(r.x_[:4], r.u[:4], bt.xR1[:4], bt.obs[:4], substeps=16)
+    for got in (a, b):
+        for k in OUT + ("short_by",):
+            np.testing.assert_array_equal(getattr(got, k).cpu().numpy(), getattr(want, k), err_msg=k)
