@@ -745,6 +745,42 @@ int cfs_cart_path(const cfs_cart_desc *d, int T, const double *start, const int 
 int cfs_cart_path_device(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
                          const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream);
 
+/* ---- Cartesian paths against mesh obstacles ---------------------------------------------------------------
+ * "Cartesian paths" above in a cell that also holds mesh obstacles.  (nmesh, meshes, D_mesh, flags) is the table of cfs_ik_solve_mesh*,
+ * with its rules: nmesh >= 1 handles created on the current device that outlive the launch, D_mesh HOST memory in both entries, nmesh
+ * margins, finite and > 0, d->nobs + nmesh <= CFS_MAX_OBS, flags 0 or CFS_IK_MESH_PER_LANE / CFS_IK_MESH_WAVE / CFS_IK_MESH_SMALL_FRONTIER
+ * with IK's values and meaning (results are bit-identical under every value).  cfs_cart_desc and cfs_cart_out are unchanged.
+ * The result is defined from the line-only call, so the trace itself never depends on the meshes.  Let (st_L, done_L, iter_L, end_L,
+ * path_L) be what cfs_cart_path gives a candidate on the same inputs; rows 0..nrow_L-1 of path_L are its accepted configurations.
+ *   1. Row k of path_L is mesh-rejected when some triangle of some mesh j lies strictly closer than thr_j = max(D_mesh[j], 1e-4) to
+ *      some link axis of that configuration: exactly the decision of cfs_ik_solve_mesh and cfs_rrt_grow_mesh, an existence test that
+ *      does not depend on the traversal order.
+ *   2. Let m be the smallest mesh-rejected row among the accepted rows.  If there is none, the candidate's outputs are the line-only
+ *      ones, bit for bit.
+ *   3. Otherwise cand_status = 2, cand_done = max(m-1, 0), cand_end = row m of path_L (the colliding configuration, as for a line
+ *      collision), and rows >= m of cand_path are NaN (m = 0: every row, as for a start that collides with a line).
+ *   4. cand_iter = iter_L always.
+ *      For state, cand_done, cand_end and cand_path this equals testing the meshes right after the line test at every booked step: the
+ *      first event in step order decides (a line-only joint jump at step j with a mesh hit at m < j is state 2).  A candidate the
+ *      meshes reject early still traces its whole line.
+ *   5. Selection, status, n_ok and n_done follow the rules of "Cartesian paths" on the new states: the smallest cost of the START among
+ *      the candidates in state 0, ties to the lowest candidate, the cost taken to the last bit as cfs_cart_path computes it.
+ *   6. clearance of a target with a winner = the minimum over the winner's K+1 configurations of min(line clearance, min_j (dm_j -
+ *      D_mesh[j])), dm_j = the exact, unbounded mesh distance of the nearest link axis (the functions of cfs_dist_arm_mesh, evaluated
+ *      WITH FMA contraction as there); NaN without a winner.  A threshold decision within rounding may differ from cfs_rrt_grow_mesh's.
+ * CFS_ERR_INVALID_ARG, nothing written: everything cfs_cart_path (cfs_cart_path_mesh) or cfs_cart_path_device
+ * (cfs_cart_path_mesh_device) refuses, and everything cfs_ik_solve_mesh* refuses about the mesh table; in cfs_cart_path_mesh_device
+ * also a NULL out->cand_path, with or without out->path: it is the workspace between the three launches (the trace, the mesh walk, the
+ * selection) and the device entry allocates nothing; cfs_cart_path_mesh stages one itself.  Pointers are HOST / DEVICE as in
+ * cfs_cart_path / cfs_cart_path_device; the device entry enqueues on `stream` and synchronises nothing.  A target's results depend
+ * on neither T nor its position in the batch; there are no atomics on the normal path. */
+int cfs_cart_path_mesh(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
+                       const double *start, const int *start_state, const double *target_pos, const double *target_axis,
+                       const double *theta_ref, const cfs_cart_out *out);
+int cfs_cart_path_mesh_device(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh /* HOST, nmesh */,
+                              int flags, int T, const double *start, const int *start_state, const double *target_pos,
+                              const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream);
+
 /* ---- developer / test entry points -------------------------------------------------------------------
  * No caller of the path needs these; they exist so that every shortcut the solver takes can be switched off and compared
  * under pytest (tests/test_gpu_shortcuts.py), and for the cycle-stamp / step-trace probes under tools/.  All state is per
@@ -786,6 +822,8 @@ int cfs_debug_read_u_log(cfs_problem *p, int B, double *out);
 int cfs_debug_rrt_frontier_overflows(unsigned long long *count, int reset);
 /* cfs_ik_solve_mesh*, variant B: the same counter for candidate poses (restarts) whose frontier overflowed */
 int cfs_debug_ik_frontier_overflows(unsigned long long *count, int reset);
+/* cfs_cart_path_mesh*, variant B: the same counter for the poses (rows of a traced line) that variant A decided for it */
+int cfs_debug_cart_frontier_overflows(unsigned long long *count, int reset);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,10 @@
 //        refused; opts (optional struct): lo, hi, tool, tool_axis, weight, tol_pos, tol_axis as for 'ik', steps (16), max_iter (20),
 //        max_joint_step (0.2).  theta njoint x T (the winner's start; NaN columns where status ~= 0), path njoint x ((steps+1)*T)
 //        (reshape(path, njoint, steps+1, T)), the others 1 x T; selected is 1-based (0: none)
+//   [theta, status, path, clearance, selected, n_ok, n_done] = cfs_mex('cart_path_mesh', obs, robot, ROBOT, start, start_state, target_pos, target_axis, theta_ref, opts)
+//        'cart_path' in a cell that ends with mesh obstacles (obs{j}.mesh, obs{j}.D), received as 'ik_mesh' receives them:
+//        cfs_cart_path_mesh.  A line also ends at the first configuration whose link axes come closer to mesh j than max(D_j, 1e-4);
+//        clearance counts the meshes
 //   Cost_b = cfs_mex('cost_b', sys_info, ROBOT)                    % EVAL.get_Cost_b (Lib/EVAL.m:75-78, main_FANUC.m:131-132)
 //   h = cfs_mex('mesh_load_stl', path, scale, map_from_stl)        % Lib/functions/MapFromSTL.m
 //   [dis, points] = cfs_mex('mesh_segment_distance', h, seg6)      % point2surface_dis (M200i/dist_arm_surf_200i.m:21)
@@ -573,6 +577,89 @@ static void cart_path(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]
     for (int k = 0; k < 7; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
 }
 
+// 'cart_path' in a cell that ends with mesh obstacles (cfs_cart_path_mesh): the same arguments and outputs, the obs cell as 'rrt' takes it
+static void cart_path_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs < 9) mexErrMsgTxt("[theta, status, path, clearance, selected, n_ok, n_done] = cfs_mex('cart_path_mesh', obs, robot, ROBOT, start, start_state, target_pos, target_axis, theta_ref [, opts])");
+    const mxArray *obs = prhs[1], *robot = prhs[2], *opts = nrhs > 9 ? prhs[9] : nullptr;
+    const std::string ROBOT = mxArrayToString(prhs[3]);
+    const int nj = (int)mxGetM(prhs[8]), T = (int)mxGetN(prhs[6]);
+    if (mxGetM(prhs[6]) != 3 || (int)mxGetN(prhs[8]) != T || T < 1) mexErrMsgTxt("target_pos must be 3 x T and theta_ref njoint x T");
+    const bool use_axis = !mxIsEmpty(prhs[7]);
+    if (use_axis && (mxGetM(prhs[7]) != 3 || (int)mxGetN(prhs[7]) != T)) mexErrMsgTxt("target_axis must be 3 x T or []");
+    const int R = (int)(mxGetN(prhs[4]) / T);                                         // mxGetN of njoint x R x T is R*T
+    if ((int)mxGetM(prhs[4]) != nj || R < 1 || (int)mxGetN(prhs[4]) != R * T) mexErrMsgTxt("start must be njoint x R x T");
+    std::vector<int> state;
+    if (!mxIsEmpty(prhs[5])) {
+        if ((int)mxGetNumberOfElements(prhs[5]) != R * T) mexErrMsgTxt("start_state must be R x T or []");
+        state.resize((size_t)R * T);
+        for (int e = 0; e < R * T; ++e) state[e] = (int)mxGetPr(prhs[5])[e];
+    }
+    cfs_cart_desc d;
+    memset(&d, 0, sizeof d);
+    fill_robot(robot, ROBOT.c_str(), nj, d.robot);
+    d.njoint = nj; d.use_axis = use_axis ? 1 : 0;
+    auto opt = [&](const char *name) -> const mxArray * { const mxArray *f = opts ? mxGetField(opts, 0, name) : nullptr; return f && !mxIsEmpty(f) ? f : nullptr; };
+    auto num = [&](const char *name, double dflt) { const mxArray *f = opt(name); return f ? mxGetScalar(f) : dflt; };
+    std::vector<double> lo(nj), hi(nj);
+    const mxArray *tm = mxGetField(robot, 0, "thetamax");
+    for (int c = 0; c < nj; ++c) {
+        if (opt("lo") && opt("hi")) { lo[c] = mxGetPr(opt("lo"))[c]; hi[c] = mxGetPr(opt("hi"))[c]; }
+        else if (tm && (int)mxGetM(tm) >= nj) { lo[c] = mxGetPr(tm)[c]; hi[c] = mxGetPr(tm)[mxGetM(tm) + c]; }
+        else mexErrMsgTxt("joint ranges: give opts.lo and opts.hi, or robot.thetamax");
+    }
+    d.lo = lo.data(); d.hi = hi.data();
+    d.weight = opt("weight") ? mxGetPr(opt("weight")) : nullptr;
+    const double *cp = d.robot.cap + 6 * (nj - 1);
+    double ax[3] = {cp[3] - cp[0], cp[4] - cp[1], cp[5] - cp[2]};
+    if (ax[0] == 0.0 && ax[1] == 0.0 && ax[2] == 0.0) ax[2] = 1.0;
+    for (int q = 0; q < 3; ++q) {
+        d.tool[q] = opt("tool") ? mxGetPr(opt("tool"))[q] : cp[q];
+        d.tool_axis[q] = opt("tool_axis") ? mxGetPr(opt("tool_axis"))[q] : ax[q];
+    }
+    d.candidates = R; d.steps = (int)num("steps", 16); d.max_iter = (int)num("max_iter", 20);
+    d.max_joint_step = num("max_joint_step", 0.2);
+    d.tol_pos = num("tol_pos", 1e-6); d.tol_axis = num("tol_axis", 1e-6);
+    if (d.steps < 1 || d.steps > 256) mexErrMsgTxt("opts.steps must be in 1..256");
+    // line obstacles (.l, .D) first, then mesh obstacles (.mesh = a handle of cfs_mex('mesh_load_stl' ...), .D), as in 'rrt'
+    std::vector<double> obs6, D, D_mesh;
+    std::vector<const cfs_mesh *> meshes;
+    const int ncell = (int)mxGetNumberOfElements(obs);
+    for (int j = 0; j < ncell; ++j) {
+        const mxArray *o = mxGetCell(obs, j), *fl = o ? mxGetField(o, 0, "l") : nullptr, *fD = o ? mxGetField(o, 0, "D") : nullptr;
+        const mxArray *mh = o ? mxGetField(o, 0, "mesh") : nullptr;
+        if (mh) {
+            if (!fD) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .mesh and .D", j + 1);
+            meshes.push_back(mesh_of(mh));
+            D_mesh.push_back(mxGetScalar(fD));
+            continue;
+        }
+        if (!meshes.empty()) mexErrMsgTxt("mesh obstacles must come last in the obs cell");
+        if (!fl || !fD || mxGetNumberOfElements(fl) != 6) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .l (3x2) and .D", j + 1);
+        obs6.insert(obs6.end(), mxGetPr(fl), mxGetPr(fl) + 6);
+        D.push_back(mxGetScalar(fD));
+    }
+    if (meshes.empty()) mexErrMsgTxt("'cart_path_mesh' needs at least one mesh obstacle at the end of the obs cell: use 'cart_path' for line obstacles only");
+    d.nobs = (int)D.size(); d.obs = obs6.data(); d.D = D.data();
+    mxArray *o_th = mxCreateDoubleMatrix(nj, T, mxREAL);                              // T x njoint row-major = njoint x T column-major
+    mxArray *o_path = mxCreateDoubleMatrix(nj, (size_t)(d.steps + 1) * T, mxREAL);    // T x (steps+1) x njoint row-major
+    mxArray *o_cl = mxCreateDoubleMatrix(1, T, mxREAL);
+    std::vector<int> status(T), selected(T), n_ok(T), n_done(T);
+    cfs_cart_out o;
+    memset(&o, 0, sizeof o);
+    o.theta = mxGetPr(o_th); o.status = status.data(); o.path = mxGetPr(o_path); o.selected = selected.data(); o.n_ok = n_ok.data();
+    o.n_done = n_done.data(); o.clearance = mxGetPr(o_cl);
+    check(cfs_cart_path_mesh(&d, (int)meshes.size(), meshes.data(), D_mesh.data(), 0, T, mxGetPr(prhs[4]), state.empty() ? nullptr : state.data(),
+                             mxGetPr(prhs[6]), use_axis ? mxGetPr(prhs[7]) : nullptr, mxGetPr(prhs[8]), &o));
+    mxArray *o_i[4] = {mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL),
+                       mxCreateDoubleMatrix(1, T, mxREAL)};
+    for (int t = 0; t < T; ++t) {
+        mxGetPr(o_i[0])[t] = status[t]; mxGetPr(o_i[1])[t] = selected[t] + 1; mxGetPr(o_i[2])[t] = n_ok[t]; mxGetPr(o_i[3])[t] = n_done[t];
+    }
+    mxArray *outs[7] = {o_th, o_i[0], o_path, o_cl, o_i[1], o_i[2], o_i[3]};
+    for (int k = 0; k < 7; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
+}
+
 static void cost_b(mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs < 3) mexErrMsgTxt("Cost_b = cfs_mex('cost_b', sys_info, ROBOT)");
@@ -618,6 +705,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         ik_mesh(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "cart_path") {
         cart_path(nlhs, plhs, nrhs, prhs);
+    } else if (cmd == "cart_path_mesh") {
+        cart_path_mesh(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "cost_b") {
         cost_b(plhs, nrhs, prhs);
     } else if (cmd == "mesh_load_stl") {

@@ -6,6 +6,11 @@ retreat is the same move in reverse).  ``CartesianPath`` traces that line from e
 pre-grasp (``cand_theta`` / ``cand_status``, accepted as they are) and keeps, per target, the candidate nearest to ``theta_ref`` whose
 line completes inside the joint ranges, without a joint jump and free of the line obstacles.  One wavefront per target, one lane
 per candidate; this module packs arguments and unpacks results, the tracing and the selection are a HIP kernel (csrc/cfs_cart.hip).
+
+Mesh obstacles are opt-in: ``CartesianPath(..., meshes=True)`` takes an obs cell that ends with ``dict(mesh=Mesh, D=...)`` entries
+and routes ``trace`` / ``trace_device`` to ``cfs_cart_path_mesh*`` (include/cfs_hip.h, "Cartesian paths against mesh obstacles";
+DESIGN.md section 24): every accepted configuration of every line is also tested against the meshes with the decision of
+``cfs_ik_solve_mesh``, and the clearance counts them.
 """
 from __future__ import annotations
 
@@ -31,16 +36,30 @@ class CartesianPath(_ToolSolver):
     """Straight tool lines for one robot, one set of line obstacles and one set of joint ranges.
 
     robot, obs, joint_limits, tool, tool_axis, tol_pos, tol_axis, weight, device, njoint: as for IKSolver, except that a mesh entry
-    in `obs` is refused (line obstacles only).  steps: K line points after the start, 1..256.  max_iter: iterations per step,
-    1..1000.  max_joint_step (rad): the largest move of a joint between two line points; a larger one is a joint flip and ends the
-    candidate.  Arguments are validated here, before anything touches the device."""
+    in `obs` is refused (line obstacles only) unless meshes=True.  steps: K line points after the start, 1..256.  max_iter:
+    iterations per step, 1..1000.  max_joint_step (rad): the largest move of a joint between two line points; a larger one is a
+    joint flip and ends the candidate.  meshes: False, or True for an obs cell that ends with mesh obstacles (dict(mesh=Mesh, D=...),
+    D finite and > 0; at least one): a line then also ends, in state 2, at the first configuration whose link axes come closer to
+    mesh j than max(D_j, 1e-4).  mesh_variant: as for IKSolver (None or "per_lane" | "wave" | "small_frontier", bit-identical
+    results); needs meshes=True.  Arguments are validated here, before anything touches the device."""
 
     def __init__(self, robot, obs=None, joint_limits="robot", tool=None, tool_axis=None, steps=16, max_iter=20, max_joint_step=0.2,
-                 tol_pos=1e-6, tol_axis=1e-6, weight=None, device=None, njoint=None):
+                 tol_pos=1e-6, tol_axis=1e-6, weight=None, device=None, njoint=None, meshes=False, mesh_variant=None):
         obs = [] if obs is None else list(obs)
+        if not isinstance(meshes, bool):
+            raise ValueError(f"meshes must be True or False, not {meshes!r}")
+        has_mesh = False
         for j, o in enumerate(obs):
             if isinstance(o, dict) and "mesh" in o:
-                raise ValueError(f"obs[{j}] is a mesh obstacle: CartesianPath reads line obstacles only")
+                has_mesh = True
+                if not meshes:
+                    raise ValueError(f"obs[{j}] is a mesh obstacle: CartesianPath reads line obstacles only unless meshes=True")
+        if meshes and not has_mesh:
+            raise ValueError("meshes=True needs at least one mesh obstacle (dict(mesh=Mesh, D=...)) at the end of obs")
+        if mesh_variant is not None and not meshes:
+            raise ValueError("mesh_variant needs meshes=True")
+        self.meshes = meshes
+        self.mesh_variant = None if mesh_variant is None else _args.one_of(_lib.IK_MESH, mesh_variant, "mesh_variant")
         self.steps = _args.int_in(steps, "steps", 1, MAX_STEPS)
         self.max_iter = _args.int_in(max_iter, "max_iter", 1, MAX_ITER)
         super().__init__(robot, obs, joint_limits, tool, tool_axis, tol_pos, tol_axis, weight, device, njoint)
@@ -50,6 +69,9 @@ class CartesianPath(_ToolSolver):
         d = self._fill_desc(_lib.cfs_cart_desc(), use_axis, obs, D)
         d.candidates, d.steps, d.max_iter, d.max_joint_step = int(R), self.steps, self.max_iter, self.max_joint_step
         return d
+
+    def _mesh_table(self):
+        return _args.mesh_table(self._meshes, self._D_mesh, 0 if self.mesh_variant is None else _lib.IK_MESH[self.mesh_variant])
 
     def _shapes(self, T, R):
         nj, K1 = self.nj, self.steps + 1
@@ -97,7 +119,11 @@ class CartesianPath(_ToolSolver):
         r = self._results(self._shapes(T, R), want_candidates)
         o = _args.fill(_lib.cfs_cart_out(), r)
         d = self._desc(ta is not None, R, self.obs, self.D)
-        _lib.check(_lib.lib().cfs_cart_path(C.byref(d), T, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o)))
+        tail = (T, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o))
+        if self.meshes:
+            _lib.check(_lib.lib().cfs_cart_path_mesh(C.byref(d), *self._mesh_table(), *tail))
+        else:
+            _lib.check(_lib.lib().cfs_cart_path(C.byref(d), *tail))
         return r
 
     # ---- CUDA tensors in and out (cfs_cart_path_device) --------------------------------------------------------------------
@@ -127,7 +153,10 @@ class CartesianPath(_ToolSolver):
                 work = _args.zeros_on(dev)(*shapes["cand_path"])
                 o.cand_path = _ptr(work)
             d = self._desc(ta is not None, R, obs, D)
-            _lib.check(_lib.lib().cfs_cart_path_device(C.byref(d), T, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o),
-                                                       C.c_void_p(stream.cuda_stream)))
+            tail = (T, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o), C.c_void_p(stream.cuda_stream))
+            if self.meshes:
+                _lib.check(_lib.lib().cfs_cart_path_mesh_device(C.byref(d), *self._mesh_table(), *tail))
+            else:
+                _lib.check(_lib.lib().cfs_cart_path_device(C.byref(d), *tail))
             self._record(stream, s, ss, tp, ta, tr, work)
         return r

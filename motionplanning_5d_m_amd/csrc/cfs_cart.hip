@@ -14,6 +14,21 @@
 // arithmetic of a lane is that of the nested form (for every step: restart from theta_{k-1}).  Lanes that have ended idle under the
 // EXEC mask until a ballot says that none is running; the selection is IK's wave argmin on (cost, lane) by xor shuffles.  No atomics,
 // no block barrier after the staging, no host round trip.  Everything is fp64; every loop over joints is unrolled at compile time.
+//
+// Mesh obstacles (cfs_cart_path_mesh*).  The trace does not depend on collisions, so the meshes are tested BEHIND
+// it on the same stream, in two more launches that read what it left in cand_path (the workspace between the launches):
+//   cfs_cart_mesh_kernel<NJ, MESH>   one wavefront per (target, candidate), one wavefront per workgroup.  For the candidate's accepted
+//                                    rows in ascending order: lane-uniform FK (ik_clearance<NJ, true> hands out the link ends, into LDS), then
+//                                    the threshold test of cfs_mesh_hit_dev.h with the whole wave on that one pose (variant A, or
+//                                    variant B with variant A deciding a pose whose frontier overflows).  The first hit ends the walk
+//                                    and rewrites the candidate's outputs: state 2, done = max(m-1, 0), end = row m, rows >= m NaN.
+//   cfs_cart_select_kernel<NJ>       one wavefront per target, one lane per candidate.  A candidate is complete when all K+1 rows of
+//                                    its cand_path are numbers (accepted rows are a prefix and hold no NaN), so the states are read
+//                                    off cand_path alone and the optional cand_status / cand_done need not exist.  Cost of the start,
+//                                    the xor-shuffle argmin, then the winner's clearance: the (row, mesh, link) triples strided over
+//                                    the lanes, one exact unbounded mesh_query each, a wave min with the line clearance of the rows.
+// cfs_cart_kernel is untouched: at 256 VGPR + 253 AGPR for NJ = 5 a hierarchy walk inside its pass would put the iteration in scratch.
+#include "cfs_mesh_hit_dev.h"
 #include "cfs_ik_dev.h"
 #include "cfs_host.h"
 #include <cmath>
@@ -267,6 +282,205 @@ hipError_t launch_cart(int nj, const CartParams &p, hipStream_t s)
     });
 }
 
+// ---- mesh obstacles behind the trace -----------------------------------------------------------------------------------------
+// dynamic LDS of a mesh wave: the private stacks of variant A and of the exact queries (MESH_STACK*64 ints + as many floats = 10 KB),
+// then variant B's frontier (RRT_FRONTIER_CAP pairs + as many nodes = 4 KB)
+constexpr int CART_STACK_WORDS = 2 * MESH_STACK * WV, CART_FRONTIER_WORDS = 2 * RRT_FRONTIER_CAP;
+
+// the mesh table of a cfs_cart_path_mesh* call: RRT's (thresholds, frontier capacity) and the margins for the winner's clearance
+struct CartMeshArgs {
+    CartParams P;
+    RrtMeshArgs MA;
+    double D[CFS_MAX_OBS];
+};
+
+// poses of variant B whose frontier overflowed and that variant A decided (cfs_debug_cart_frontier_overflows): one vector atomic by
+// lane 0 per such pose, none on the normal path
+__device__ unsigned long long g_cart_frontier_overflows = 0ull;
+
+// one wavefront = one workgroup = one (target, candidate); everything below is wave-uniform
+template <int NJ, int MESH>
+__global__ __launch_bounds__(WV) void cfs_cart_mesh_kernel(const CartMeshArgs A_)
+{
+    const CartParams &P = A_.P;
+    __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
+    __shared__ double s_ends[NJ * 6];                         // the pose's link ends: wave-uniform, so they need no registers
+    extern __shared__ __attribute__((aligned(16))) int s_mesh[];
+    {
+        const double *src = reinterpret_cast<const double *>(&P.rb);
+        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += WV) s_rb[e] = src[e];
+    }
+    __syncthreads();
+    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    const int lane = threadIdx.x;
+    const size_t row = blockIdx.x;                            // t * R + r; the grid is exactly T * R
+    const size_t prow = row * (size_t)(P.K + 1);
+    int *s_stack = s_mesh;
+    float *s_lbs = reinterpret_cast<float *>(s_stack + MESH_STACK * WV);
+    [[maybe_unused]] int *s_fpair = s_mesh + CART_STACK_WORDS, *s_fnode = s_fpair + RRT_FRONTIER_CAP;
+    const RrtMeshArgs &MA = A_.MA;
+
+    for (int k = 0; k <= P.K; ++k) {
+        double th[NJ];
+        double *ends = s_ends;
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) th[c] = P.cand_path[(prow + k) * NJ + c];     // one address for the wave
+        if (th[0] != th[0]) return;                           // the accepted rows are a prefix: nothing after the first NaN row
+        ik_clearance<NJ, true>(rb, th, 0, nullptr, nullptr, ends);                 // every lane stores the same values and reads its own
+        bool hit;
+        if constexpr (MESH == RRT_MESH_PER_LANE) {
+            hit = mesh_hit_per_lane<NJ>(MA, ends, lane, s_stack, s_lbs);
+        } else {
+            const int h = mesh_hit_wave<NJ>(MA, ends, lane, s_fpair, s_fnode);
+            if (h < 0 && lane == 0) atomicAdd(&g_cart_frontier_overflows, 1ull);
+            hit = h < 0 ? mesh_hit_per_lane<NJ>(MA, ends, lane, s_stack, s_lbs) : h != 0;
+        }
+        if (!hit) continue;
+        // row k is the first mesh-rejected row: state 2, as for a line collision at step k
+        if (lane == 0) {
+            if (P.cand_status) P.cand_status[row] = 2;
+            if (P.cand_done) P.cand_done[row] = k > 0 ? k - 1 : 0;
+            if (P.cand_end) {
+#pragma unroll
+                for (int c = 0; c < NJ; ++c) P.cand_end[row * NJ + c] = th[c];
+            }
+        }
+        const double nan = __builtin_nan("");
+        for (size_t e = (prow + k) * NJ + lane; e < (prow + P.K + 1) * NJ; e += WV) P.cand_path[e] = nan;
+        return;
+    }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(WV) void cfs_cart_select_kernel(const CartMeshArgs A_)
+{
+    const CartParams &P = A_.P;
+    __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
+    __shared__ double s_obs[CFS_MAX_OBS * 6];
+    __shared__ double s_D[CFS_MAX_OBS];
+    extern __shared__ __attribute__((aligned(16))) int s_mesh[];
+    {
+        const double *src = reinterpret_cast<const double *>(&P.rb);
+        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += WV) s_rb[e] = src[e];
+        for (int e = threadIdx.x; e < P.nobs * 6; e += WV) s_obs[e] = P.obs[e];
+        for (int e = threadIdx.x; e < P.nobs; e += WV) s_D[e] = P.D[e];
+    }
+    __syncthreads();
+    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    const int lane = threadIdx.x, t = blockIdx.x;
+    const bool active = lane < P.R;
+    const size_t row = (size_t)t * P.R + (active ? lane : 0);
+    const size_t prow = row * (size_t)(P.K + 1);
+    const double nan = __builtin_nan("");
+
+    // the candidate's state, read off its inputs and its rows of cand_path: no start (the trace's test) | accepted rows
+    bool has_start = false;
+    int nrow = 0;
+    double cost = INFINITY;
+    if (active) {
+        has_start = !P.start_state || P.start_state[row] == 0;
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) {
+            const double v = P.start[row * NJ + c];
+            has_start = has_start && v >= P.lo[c] && v <= P.hi[c];
+        }
+        if (has_start) {
+            for (int k = 0; k <= P.K; ++k) {
+                const double v = P.cand_path[(prow + k) * NJ];
+                if (v != v) break;
+                ++nrow;
+            }
+        }
+        if (nrow == P.K + 1) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < NJ; ++c) {                    // cfs_cart_kernel's chain: w*(d*d), summed in joint order, no FMA
+                const double dlt = P.start[row * NJ + c] - P.theta_ref[(size_t)t * NJ + c];
+                s = __dadd_rn(s, __dmul_rn(P.w[c], __dmul_rn(dlt, dlt)));
+            }
+            if (s < INFINITY) cost = s;
+        }
+    }
+    const bool good = cost < INFINITY;
+    const int n_ok = __popcll(__ballot(good));
+    const bool any_start = __ballot(has_start) != 0ull;
+    double bc = cost;
+    int bl = lane, md = nrow > 1 ? nrow - 1 : 0;
+#pragma unroll
+    for (int m = 1; m < WV; m <<= 1) {
+        const double oc = __shfl_xor(bc, m, WV);
+        const int ol = __shfl_xor(bl, m, WV);
+        const int od = __shfl_xor(md, m, WV);
+        if (oc < bc || (oc == bc && ol < bl)) { bc = oc; bl = ol; }
+        if (od > md) md = od;
+    }
+    const bool ok = n_ok > 0;
+    const size_t n = (size_t)(P.K + 1) * NJ;
+    const double *src = P.cand_path + ((size_t)t * P.R + (ok ? bl : 0)) * n;
+
+    // the winner's clearance: triple = (row, mesh, link), one exact unbounded query each; the lane that holds a row's first triple
+    // also takes the row's line clearance
+    double mm = INFINITY;
+    if (ok && P.clearance) {
+        int *s_stack = s_mesh;
+        float *s_lbs = reinterpret_cast<float *>(s_stack + MESH_STACK * WV);
+        const RrtMeshArgs &MA = A_.MA;
+        const int per = MA.nmesh * NJ, ntrip = (P.K + 1) * per;
+        for (int q = lane; q < ntrip; q += WV) {
+            const int k = q / per, pr = q - k * per, j = pr / NJ, l = pr - j * NJ;
+            double th[NJ], ends[NJ * 6], a6[6];
+#pragma unroll
+            for (int c = 0; c < NJ; ++c) th[c] = src[(size_t)k * NJ + c];
+            const double cl = ik_clearance<NJ, true>(rb, th, pr == 0 ? P.nobs : 0, s_obs, s_D, ends);
+            if (cl < mm) mm = cl;
+            pick_link<NJ>(ends, l, a6);
+            const DevMesh m{MA.m[j].nodes, MA.m[j].tri, nullptr, 0, MA.m[j].nt, nullptr, nullptr, 0, 0};
+            Best b;
+            mesh_query<WV, false>(m, a6, a6 + 3, -1, s_stack + lane, s_lbs + lane, b, nullptr);
+            const double v = b.d - A_.D[j];
+            if (v < mm) mm = v;
+        }
+#pragma unroll
+        for (int m = 1; m < WV; m <<= 1) {
+            const double om = __shfl_xor(mm, m, WV);
+            if (om < mm) mm = om;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) P.theta[(size_t)t * NJ + c] = ok ? P.start[((size_t)t * P.R + bl) * NJ + c] : nan;
+        P.status[t] = ok ? 0 : (any_start ? 1 : 2);
+        if (P.selected) P.selected[t] = ok ? bl : -1;
+        if (P.n_ok) P.n_ok[t] = n_ok;
+        if (P.n_done) P.n_done[t] = md;
+        if (P.clearance) P.clearance[t] = ok ? mm : nan;
+    }
+    if (P.path) {
+        double *dst = P.path + (size_t)t * n;
+        for (size_t e = lane; e < n; e += WV) dst[e] = ok ? src[e] : nan;
+    }
+}
+
+size_t cart_mesh_lds_bytes(int variant) { return (size_t)(CART_STACK_WORDS + (variant == RRT_MESH_WAVE ? CART_FRONTIER_WORDS : 0)) * 4; }
+
+// the two launches behind the trace
+hipError_t launch_cart_mesh(int nj, int variant, const CartMeshArgs &a, hipStream_t s)
+{
+    if (variant != RRT_MESH_PER_LANE && variant != RRT_MESH_WAVE) return hipErrorInvalidValue;
+    return cfs_for_nj(nj, [&](auto N) {
+        constexpr int NJ = decltype(N)::value;
+        const dim3 grid((unsigned)((size_t)a.P.T * a.P.R));
+        if (variant == RRT_MESH_PER_LANE)
+            hipLaunchKernelGGL((cfs_cart_mesh_kernel<NJ, RRT_MESH_PER_LANE>), grid, dim3(WV), cart_mesh_lds_bytes(variant), s, a);
+        else
+            hipLaunchKernelGGL((cfs_cart_mesh_kernel<NJ, RRT_MESH_WAVE>), grid, dim3(WV), cart_mesh_lds_bytes(variant), s, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cfs_cart_select_kernel<NJ>, dim3(a.P.T), dim3(WV), cart_mesh_lds_bytes(RRT_MESH_PER_LANE), s, a);
+        return hipGetLastError();
+    });
+}
+
 // ---- C ABI (include/cfs_hip.h, "Cartesian paths") --------------------------------------------------------------------------------
 bool finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 bool all_finite(const double *v, size_t n)
@@ -325,31 +539,66 @@ void cart_point(CartParams &P, const double *obs, const double *D, const double 
     P.clearance = o->clearance; P.cand_status = o->cand_status; P.cand_done = o->cand_done; P.cand_iter = o->cand_iter;
     P.cand_end = o->cand_end; P.cand_path = o->cand_path;
 }
-}  // namespace
 
-extern "C" int cfs_cart_path_device(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
-                                    const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream)
+// the meshes of a cfs_cart_path_mesh* call
+struct CartMeshCall { int nmesh; const cfs_mesh *const *meshes; const double *D_mesh; int flags; };
+int check_cart_mesh(const cfs_cart_desc *d, const CartMeshCall &c, CartMeshArgs &a, int &variant)
+{
+    int rc = cfs_check_mesh_table(d->nobs, c.nmesh, c.meshes, c.D_mesh, c.flags, 1, CART_MESH_DEFAULT, a.MA, variant);
+    if (rc) return rc;
+    memset(a.D, 0, sizeof a.D);
+    for (int j = 0; j < c.nmesh; ++j) a.D[j] = c.D_mesh[j];
+    return CFS_SUCCESS;
+}
+
+// the trace, then (mc given) the mesh walk and the selection over it, all on stream s.  The trace's own selection would only be
+// overwritten, so it is not asked for: its optional target outputs are withheld from the first launch.
+hipError_t launch_cart_all(int nj, int variant, CartMeshArgs &a, bool mesh, hipStream_t s)
+{
+    if (!mesh) return launch_cart(nj, a.P, s);
+    CartParams first = a.P;
+    first.path = nullptr; first.selected = nullptr; first.n_ok = nullptr; first.n_done = nullptr; first.clearance = nullptr;
+    const hipError_t e = launch_cart(nj, first, s);
+    return e != hipSuccess ? e : launch_cart_mesh(nj, variant, a, s);
+}
+
+// mc == nullptr: the line-only call
+int cart_device(const cfs_cart_desc *d, const CartMeshCall *mc, int T, const double *start, const int *start_state, const double *target_pos,
+                const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream)
 {
     static_assert(sizeof(CartParams) <= 4096, "the parameter block travels as a kernel argument");
-    CartParams P;
-    int rc = check_cart(d, T, start, target_pos, target_axis, theta_ref, out, P);
+    static_assert(sizeof(CartMeshArgs) <= 4096, "the parameter block and the mesh table travel as a kernel argument");
+    CartMeshArgs A;
+    int rc = check_cart(d, T, start, target_pos, target_axis, theta_ref, out, A.P);
     if (rc) return rc;
-    if (out->path && !out->cand_path)
+    int variant = RRT_MESH_NONE;
+    if (mc) {
+        rc = check_cart_mesh(d, *mc, A, variant);
+        if (rc) return rc;
+        if (!out->cand_path)
+            return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_cart_path_mesh_device: out->cand_path must be given, the workspace between the launches (nothing is allocated here)");
+    } else if (out->path && !out->cand_path)
         return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_cart_path_device: out->path needs out->cand_path, the launch's workspace (nothing is allocated here)");
     rc = cfs_use_device(cfs_current_device());
     if (rc) return rc;
-    cart_point(P, d->obs, d->D, start, start_state, target_pos, target_axis, theta_ref, out);
-    const hipError_t e = launch_cart(d->njoint, P, reinterpret_cast<hipStream_t>(stream));
+    cart_point(A.P, d->obs, d->D, start, start_state, target_pos, target_axis, theta_ref, out);
+    const hipError_t e = launch_cart_all(d->njoint, variant, A, mc != nullptr, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return cfs_fail(CFS_ERR_HIP, "Cartesian path launch failed: %s", hipGetErrorString(e));
     return CFS_SUCCESS;
 }
 
-extern "C" int cfs_cart_path(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
-                             const double *target_axis, const double *theta_ref, const cfs_cart_out *out)
+int cart_host(const cfs_cart_desc *d, const CartMeshCall *mc, int T, const double *start, const int *start_state, const double *target_pos,
+              const double *target_axis, const double *theta_ref, const cfs_cart_out *out)
 {
-    CartParams P;
+    CartMeshArgs A;
+    CartParams &P = A.P;
     int rc = check_cart(d, T, start, target_pos, target_axis, theta_ref, out, P);
     if (rc) return rc;
+    int variant = RRT_MESH_NONE;
+    if (mc) {   // refuse before anything is staged on the device
+        rc = check_cart_mesh(d, *mc, A, variant);
+        if (rc) return rc;
+    }
     const size_t nj = d->njoint, R = d->candidates, K1 = (size_t)d->steps + 1, nobs = d->nobs, nT = T;
     if (!all_finite(target_pos, nT * 3) || !all_finite(theta_ref, nT * nj)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_pos / theta_ref must be finite");
     if (nobs && (!all_finite(d->obs, nobs * 6) || !all_finite(d->D, nobs))) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be finite");
@@ -380,10 +629,10 @@ extern "C" int cfs_cart_path(const cfs_cart_desc *d, int T, const double *start,
     if (out->cand_done) o.cand_done = st.out<int>(nT * R);
     if (out->cand_iter) o.cand_iter = st.out<int>(nT * R);
     if (out->cand_end) o.cand_end = st.out<double>(nT * R * nj);
-    if (out->cand_path || out->path) o.cand_path = st.out<double>(nT * R * K1 * nj);           // also the workspace behind `path`
+    if (out->cand_path || out->path || mc) o.cand_path = st.out<double>(nT * R * K1 * nj);     // also the workspace behind `path` and between the launches
     if (st.err == hipSuccess) {
         cart_point(P, obs_d, D_d, s_d, ss_d, tp_d, ta_d, tr_d, &o);
-        st.err = launch_cart(d->njoint, P, nullptr);
+        st.err = launch_cart_all(d->njoint, variant, A, mc != nullptr, nullptr);
         if (st.err == hipSuccess) st.err = hipStreamSynchronize(nullptr);
     }
     st.down(out->theta, o.theta, nT * nj); st.down(out->status, o.status, nT); st.down(out->path, o.path, nT * K1 * nj);
@@ -392,4 +641,38 @@ extern "C" int cfs_cart_path(const cfs_cart_desc *d, int T, const double *start,
     st.down(out->cand_status, o.cand_status, nT * R); st.down(out->cand_done, o.cand_done, nT * R); st.down(out->cand_iter, o.cand_iter, nT * R);
     st.down(out->cand_end, o.cand_end, nT * R * nj); st.down(out->cand_path, o.cand_path, nT * R * K1 * nj);
     return st.result("Cartesian path staging or launch");
+}
+}  // namespace
+
+extern "C" int cfs_cart_path_device(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
+                                    const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream)
+{
+    return cart_device(d, nullptr, T, start, start_state, target_pos, target_axis, theta_ref, out, stream);
+}
+
+extern "C" int cfs_cart_path(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
+                             const double *target_axis, const double *theta_ref, const cfs_cart_out *out)
+{
+    return cart_host(d, nullptr, T, start, start_state, target_pos, target_axis, theta_ref, out);
+}
+
+extern "C" int cfs_cart_path_mesh_device(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
+                                         const double *start, const int *start_state, const double *target_pos, const double *target_axis,
+                                         const double *theta_ref, const cfs_cart_out *out, void *stream)
+{
+    const CartMeshCall mc{nmesh, meshes, D_mesh, flags};
+    return cart_device(d, &mc, T, start, start_state, target_pos, target_axis, theta_ref, out, stream);
+}
+
+extern "C" int cfs_cart_path_mesh(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
+                                  const double *start, const int *start_state, const double *target_pos, const double *target_axis,
+                                  const double *theta_ref, const cfs_cart_out *out)
+{
+    const CartMeshCall mc{nmesh, meshes, D_mesh, flags};
+    return cart_host(d, &mc, T, start, start_state, target_pos, target_axis, theta_ref, out);
+}
+
+extern "C" int cfs_debug_cart_frontier_overflows(unsigned long long *count, int reset)
+{
+    return cfs_frontier_overflows(&g_cart_frontier_overflows, count, reset);
 }

@@ -204,3 +204,6 @@ int cfs_check_mesh_table(int nobs, int nmesh, const cfs_mesh *const *meshes, con
 // cfs_ik_solve_mesh* (cfs_ik.hip) runs the same two variants on its candidates; flags == 0: the variant the measurement of DESIGN.md
 // section 21 names
 constexpr int IK_MESH_DEFAULT = RRT_MESH_WAVE;
+// cfs_cart_path_mesh* (cfs_cart.hip) runs them on the rows of a traced line; flags == 0: variant B on the strength of DESIGN.md section
+// 19, as section 21 does (section 24 says which measurement is owed)
+constexpr int CART_MESH_DEFAULT = RRT_MESH_WAVE;

@@ -163,7 +163,7 @@ class RRTCFSPlanner:
 
     # ---- Cartesian goals ---------------------------------------------------------------------------------------------------
     def plan_to_pose(self, x0, target_pos, target_axis=None, seed=0, ik_options=None, ik_meshes=False, approach=None, approach_dir=None,
-                     approach_steps=16, approach_options=None, **plan_kwargs):
+                     approach_steps=16, approach_options=None, approach_meshes=False, **plan_kwargs):
         """plan() towards Cartesian targets: one inverse-kinematics launch (ik.IKSolver.solve_device: theta_ref = x0, the planner's
         obstacles with their D -- its line obstacles, and with ik_meshes=True its mesh obstacles too --, the planner's joint_limits if
         it has them, else robot.thetamax; generator seed `seed`), then
@@ -180,20 +180,25 @@ class RRTCFSPlanner:
         meshes ik_meshes=True is the default path.
         approach: None (the default: everything above, bit for bit) or a distance > 0 in metres, a number or (S,): the plan then ends
         at a pre-grasp pose `approach` metres back from target_pos and the tool enters the grasp along a straight line
-        (cart.CartesianPath; needs target_axis; refused on a planner with mesh obstacles).  approach_dir: (S, 3), (3,) or None (=
-        target_axis): the world direction the tool travels on that line.  One IK launch at target_pos - approach*unit(dir) with its
-        candidates kept, one trace_device launch from every candidate (cand_theta / cand_status) to target_pos on the same stream
+        (cart.CartesianPath; needs target_axis; on a planner with mesh obstacles it needs approach_meshes=True).  approach_dir:
+        (S, 3), (3,) or None (= target_axis): the world direction the tool travels on that line.  One IK launch at
+        target_pos - approach*unit(dir) with its candidates kept, one trace_device launch from every candidate (cand_theta / cand_status) to target_pos on the same stream
         (approach_steps line points; approach_options: CartesianPath's max_iter, max_joint_step; tool, tolerances and weight are
         ik_options'), then plan() with the winners' starts as goals: per slot the IK candidate nearest to x0 whose line completes.
         The result gains approach_path (S, approach_steps+1, 5), grasp (= approach_path[:, -1]), approach_status (CartesianPath's
         status), approach_clearance, approach_selected and ik_goal (IK's own winner); goal is the configuration planned to.  A slot
-        whose IK solved but whose approach did not gets status = -3 and is masked like -2."""
+        whose IK solved but whose approach did not gets status = -3 and is masked like -2.
+        approach_meshes: False (the default) keeps the line-only trace, and a planner with mesh obstacles then refuses an approach;
+        True (needs ik_meshes=True on such a planner) builds the CartesianPath from the planner's whole cell with meshes=True -- the
+        D that cfs_rrt_grow_mesh_device gets --, so that every configuration of the line is free of the meshes too
+        (cfs_cart_path_mesh_device).  On a planner without meshes it is the line-only path."""
         if approach is None:
             if approach_dir is not None or approach_options is not None:
                 raise ValueError("approach_dir / approach_options need approach")
         else:
-            if self._meshes:
-                raise ValueError("plan_to_pose(approach=...) on a planner with mesh obstacles: the straight-line trace reads line obstacles only")
+            if self._meshes and approach_meshes is not True:
+                raise ValueError("plan_to_pose(approach=...) on a planner with mesh obstacles: the straight-line trace reads line obstacles only "
+                                 "unless approach_meshes=True")
             if target_axis is None:
                 raise ValueError("approach needs target_axis: the tool keeps its direction along the line")
             if approach_options is None:
@@ -203,6 +208,10 @@ class RRTCFSPlanner:
         _args.int_in(approach_steps, "approach_steps", 1, MAX_STEPS)
         if not isinstance(ik_meshes, bool):
             raise ValueError(f"ik_meshes must be True or False, not {ik_meshes!r}")
+        if not isinstance(approach_meshes, bool):
+            raise ValueError(f"approach_meshes must be True or False, not {approach_meshes!r}")
+        if approach_meshes and approach is None:
+            raise ValueError("approach_meshes needs approach")
         if self._meshes and not ik_meshes:
             raise ValueError("plan_to_pose on a planner with mesh obstacles needs ik_meshes=True: the default IK collision test reads "
                              "line obstacles only")
@@ -247,11 +256,12 @@ class RRTCFSPlanner:
                                      device=self.device, **ik_options)
         ik = self._ik[key]
         if approach is not None:
-            ckey = ("approach", key, int(approach_steps), tuple(sorted((k, repr(v)) for k, v in approach_options.items())))
+            with_meshes = bool(approach_meshes and self._meshes)                    # without meshes: the line-only path
+            ckey = ("approach", key, int(approach_steps), with_meshes, tuple(sorted((k, repr(v)) for k, v in approach_options.items())))
             if ckey not in self._ik:                                                # validates approach_options; no device call
                 shared = {k: v for k, v in ik_options.items() if k in ("tool", "tool_axis", "tol_pos", "tol_axis", "weight")}
                 self._ik[ckey] = CartesianPath(self._sys_rrt.robot, [o for o in self._pobs], joint_limits=self._ik_limits, njoint=self.nj,
-                                               device=self.device, steps=int(approach_steps), **shared, **approach_options)
+                                               device=self.device, steps=int(approach_steps), meshes=with_meshes, **shared, **approach_options)
             cart = self._ik[ckey]
         stream = _args.as_stream(stream, self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(stream):
