@@ -70,6 +70,15 @@ constexpr double DEP_TOL_F = 1e-8;       // dependent if delta <= tol * n'H^{-1}
 // CT_POSP / CT_POSM: joint position rows theta0 + (i+1) dt v0 + (Bpos u)[i,c] <= hi_c | >= lo_c (LIM kernels only)
 enum { CT_COL = 0, CT_VELP = 1, CT_VELM = 2, CT_BNDP = 3, CT_BNDM = 4, CT_POSP = 5, CT_POSM = 6 };
 __device__ __forceinline__ int mk_code(int type, int i, int jc) { return (type << 16) | (i << 8) | jc; }
+// Work-item decode of the linearisation without an integer division: e / d = umulhi(2 e, rcp31(d)), exact while e * d < 2^31
+// (d = 1 included, which a 32-bit reciprocal of 2^32 / d cannot carry).  The divisors are the obstacle count and obstacles x tile
+// width: launch_fused_tier computes their reciprocals once per launch (FusedParams::rc_*) and checks the range.
+__host__ __device__ constexpr unsigned rcp31(unsigned d) { return (unsigned)(0x80000000ull / d) + 1u; }
+__device__ __forceinline__ int rcp_div(int e, unsigned rc) { return (int)__umulhi((unsigned)e << 1, rc); }
+// Only the tiers with two workgroups per CU decode this way.  The whole-CU tier, one wavefront per SIMD with nothing to hide the
+// dependent multiplies behind, was measured 1-1.6 % slower with it and keeps the divisions: its objects
+// are compiled from the statements they had before.
+#define CFS_RCP_DECODE (CFS_WG_PER_CU > 1)
 
 // ---- DPP helpers (gfx9 row shifts / row broadcasts) ---------------------------------------------
 template <int CTRL, int RM>
@@ -831,6 +840,12 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
 #define S_OBW (s_bd + W * NJ * nseg)
                 for (int w0 = 0; w0 < H; w0 += W) {
                     const int Wc = min(W, H - w0);
+#if CFS_RCP_DECODE
+                    // reciprocals of nseg and of nseg * Wc, read per tile: the empty asm keeps the compiler from carrying them, and what it
+                    // derives from them, in registers around the whole outer loop (2 more spilled VGPRs otherwise)
+                    unsigned rc_n = P.rc_nseg, rc_t = Wc == W ? P.rc_tile : P.rc_last;
+                    asm volatile("" : "+s"(rc_n), "+s"(rc_t));
+#endif
                     if (w0 == 0) prep(0);
                     if constexpr (MOVE)                          // rows w0 .. w0+Wc-1 of problem b: contiguous (nseg == nobs)
                         for (int e = tid; e < Wc * nseg * 6; e += FT) S_OBW[e] = P.obs[((size_t)b * H + w0) * nobs * 6 + e];
@@ -849,7 +864,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     __syncthreads();
                     STAMP(10);                                  // 10: sincos + the chain
                     for (int e = tid; e < NJ * Wc * nseg; e += FT) {
+#if CFS_RCP_DECODE
+                        const int q = rcp_div(e, rc_n), j = e - q * nseg, k0 = rcp_div(e, rc_t), wi = q - k0 * Wc;
+#else
                         const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
+#endif
                         if constexpr (MOVE) s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, S_OBW + (wi * nseg + j) * 6);
                         else s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, s_ob + j * 6);
                     }
@@ -857,7 +876,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     __syncthreads();
                     STAMP(0);                                   // 0: base distances
                     for (int e = tid; e < Wc * nseg; e += FT) {
+#if CFS_RCP_DECODE
+                        const int wi = rcp_div(e, rc_n), j = e - wi * nseg;
+#else
                         const int j = e % nseg, wi = e / nseg;
+#endif
                         double m0 = INFINITY;
                         int lk = 0;
 #pragma unroll
@@ -894,6 +917,12 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                 int *s_cnt = s_free;                             // candidates per link (the QP's free-slot stack is idle here)
                 for (int w0 = 0; w0 < H; w0 += W) {
                     const int Wc = min(W, H - w0);
+#if CFS_RCP_DECODE
+                    // reciprocals of nseg and of nseg * Wc, read per tile: the empty asm keeps the compiler from carrying them, and what it
+                    // derives from them, in registers around the whole outer loop (2 more spilled VGPRs otherwise)
+                    unsigned rc_n = P.rc_nseg, rc_t = Wc == W ? P.rc_tile : P.rc_last;
+                    asm volatile("" : "+s"(rc_n), "+s"(rc_t));
+#endif
                     if (w0 == 0) prep(0);
                     if constexpr (MOVE)                          // (the previous tile's last read of them is behind its pair-phase barrier)
                         for (int e = tid; e < Wc * nseg * 6; e += FT) S_OBW[e] = P.obs[((size_t)b * H + w0) * nobs * 6 + e];
@@ -937,7 +966,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     // Base-pose distance of every link (dist_arm_3D_200i_2.m:16-26), link index slow so the point /
                     // segment branch of distLinSeg is wave-uniform.
                     for (int e = tid; e < NJ * Wc * nseg; e += FT) {
+#if CFS_RCP_DECODE
+                        const int q = rcp_div(e, rc_n), j = e - q * nseg, k0 = rcp_div(e, rc_t), wi = q - k0 * Wc;
+#else
                         const int j = e % nseg, wi = (e / nseg) % Wc, k0 = e / (nseg * Wc);
+#endif
                         if constexpr (MOVE) s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NVT + kvoff(k0 + 1)) * 6, S_OBW + (wi * nseg + j) * 6);
                         else s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NVT + kvoff(k0 + 1)) * 6, s_ob + j * 6);
                     }
@@ -948,7 +981,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     // max(min, 1e-4) by prune_tol can neither become the minimum nor reach the near-zero surrogate at any
                     // of them (see DevRobot::prune_tol), so only the other links are evaluated there: same minima, bit for bit.
                     for (int e = tid; e < Wc * nseg; e += FT) {
+#if CFS_RCP_DECODE
+                        const int wi = rcp_div(e, rc_n), j = e - wi * nseg;
+#else
                         const int j = e % nseg, wi = e / nseg;
+#endif
                         double bk[NJ], m0 = INFINITY;
                         int lk = 0;
 #pragma unroll
@@ -971,6 +1008,16 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
 #pragma unroll
                         for (int k1 = 1; k1 <= NJ; ++k1) offs[k1] = offs[k1 - 1] + s_cnt[k1 - 1] * 2 * k1;
                         for (int e = tid; e < offs[NJ]; e += FT) {
+#if CFS_RCP_DECODE
+                            // the link whose range holds e is the last one that starts at or before e (empty ranges start where the
+                            // next one does): one compare per link selects its start and the reciprocal of its 2 k1 variants
+                            int k1 = 1, lo = 0;
+                            unsigned rc = 0x80000001u;                    // 2^32 / 2 + 1
+#pragma unroll
+                            for (int kk = 2; kk <= NJ; ++kk)
+                                if (e >= offs[kk - 1]) { k1 = kk; lo = offs[kk - 1]; rc = (unsigned)(0x100000000ull / (2 * kk)) + 1u; }
+                            const int r_ = e - lo, ent = (int)__umulhi((unsigned)r_, rc), v = r_ - ent * (2 * k1) + 1;   // exact: r_ * 2 k1 < 2^32
+#else
                             int k1 = 1, ent = 0, v = 1;
 #pragma unroll
                             for (int kk = 1; kk <= NJ; ++kk)
@@ -978,6 +1025,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                                     const int r_ = e - offs[kk - 1];
                                     k1 = kk; ent = r_ / (2 * kk); v = r_ - ent * (2 * kk) + 1;
                                 }
+#endif
                             const int item = s_list[(k1 - 1) * W * nseg + ent], wi = item >> 8, j = item & 255;
                             double dis;
                             if constexpr (MOVE) dis = seg_seg_dist(s_en + (wi * NVT + kvoff(k1) + v) * 6, S_OBW + (wi * nseg + j) * 6);
@@ -992,7 +1040,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     __syncthreads();
                     STAMP(11);                                  // 11: segment pairs of the shifted poses
                     for (int e = tid; e < Wc * nseg; e += FT) {
+#if CFS_RCP_DECODE
+                        const int wi = rcp_div(e, rc_n), j = e - wi * nseg;
+#else
                         const int j = e % nseg, wi = e / nseg;
+#endif
                         double dev[NE];
 #pragma unroll
                         for (int ev = 0; ev < NE; ++ev) dev[ev] = s_dv[e * NE + ev];
@@ -1921,6 +1973,16 @@ hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftPar
     w = (p.H + (p.H + w - 1) / w - 1) / ((p.H + w - 1) / w);   // equal tiles: ceil(H / number of tiles)
     p.qy = qy;
     p.lin_w = w;
+    {   // reciprocals for the linearisation's work-item decode (rcp_div): items e < nj * w * nseg, divisors nseg and nseg * tile width
+        const int nseg = p.nobs - p.nmesh, wl = p.H - (p.H - 1) / w * w;   // wl: width of the last tile
+        p.rc_nseg = p.rc_tile = p.rc_last = 0;                             // unused without line obstacles
+        if (nseg > 0) {
+            // rcp_div needs item x divisor < 2^31.  A tile's base distances alone are nj * w * nseg doubles of at most 160 KB of LDS, so
+            // the product stays below 20 480 x 10 240 for every plan that reaches this line; the test guards the arithmetic, not a shape
+            if ((unsigned long long)nj * w * nseg * ((unsigned long long)w * nseg) >= 0x80000000ull) return hipErrorInvalidValue;
+            p.rc_nseg = rcp31(nseg); p.rc_tile = rcp31(nseg * w); p.rc_last = rcp31(nseg * wl);
+        }
+    }
     size_t need = std::max((size_t)L.total_fixed + (size_t)qy * nn, (size_t)L.lin + (size_t)w * q.per_wp);
     if constexpr (LIM) {
         // the LIM layout, with the Y rows in LDS and the tile width of the plan without limits: the same split of Y between LDS and
