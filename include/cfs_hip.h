@@ -326,8 +326,8 @@ int cfs_soft_results(cfs_problem *p, int B, double *viol_all, int *n_soft);
  *     B x H x nobs x 6; row [b][i][j] is obstacle j's [l(:,1); l(:,2)] at waypoint i+1, i.e. row i of x_, at time (i+1)*delta_t.
  *     Margins stay per obstacle.  With the same row at every waypoint, every result is bit for bit the static handle's.  The
  *     automatic launch order measures waypoint i against row i.
- * CFS_ERR_INVALID_ARG, nothing changes: NULL handle; unknown motion; PER_WAYPOINT on a handle with meshes (nmesh > 0: meshes stay
- * static); PER_WAYPOINT for a shape whose per-waypoint linearisation tiles (nobs*6 more doubles of LDS per waypoint) do not fit
+ * CFS_ERR_INVALID_ARG, nothing changes: NULL handle; unknown motion; PER_WAYPOINT on a handle with meshes (nmesh > 0: meshes move by
+ * cfs_problem_set_mesh_motion, next to static lines); PER_WAYPOINT for a shape whose per-waypoint linearisation tiles (nobs*6 more doubles of LDS per waypoint) do not fit
  * every tier of the fused solver that the static shape fits (checked here, not at launch).  On a PER_WAYPOINT handle
  * cfs_problem_set_meshes with nmesh > 0 and cfs_chomp_batch give CFS_ERR_INVALID_ARG.  Not affected: cfs_qp (it reads no
  * obstacles), cfs_dist_arm*, RRT, cfs_select_best_device, the cfs_build_terms* entry points.  Set it between solves. */
@@ -386,6 +386,30 @@ int cfs_dist_arm_mesh(const cfs_robot *robot, int njoint, int N, const double *t
  * above, rows ordered as get_con orders obstacles (Lib/CFS_FANUC.m:111).  nmesh = 0 restores line obstacles only.
  * The meshes must outlive the solves. */
 int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *meshes);
+
+/* ---- moving meshes ------------------------------------------------------------------------------------
+ * A rigid pose per waypoint for every mesh of the handle: a carrier on a conveyor, a part on a belt.  Collision row (j, i) of
+ * get_con depends on waypoint i's pose and on obstacle j only (see "moving obstacles"), so mesh row (j, i) of cfs_solve_batch,
+ * cfs_solve_batch_device, cfs_linearize and cfs_get_con becomes the mesh contract's distance between waypoint i's link axes and
+ * mesh j placed by pose [j][i]; the near-zero surrogate and the first minimum over the links are unchanged, and the Jacobian stays
+ * the literal num_jac, taken on that same distance.  The QP, the certificate, the rollout, the costs and the stop tests are those
+ * of a static handle.
+ * poses: HOST, nmesh x H x 12.  Entry [j][i] is the row-major 3x4 matrix [R | t] that places mesh j (vertices as given to
+ * cfs_mesh_create / cfs_mesh_load_stl) in the world at waypoint i+1 (row i of x_, time (i+1)*delta_t):
+ * x_world = R x_mesh + t.  NULL: the meshes are static again.
+ * Evaluation: no hierarchy is rebuilt.  The distance from a link axis to a mesh placed by [R | t] equals the distance from the
+ * inverse-transformed axis to the mesh as stored; the library inverts each pose on the host in double (R', -R't), keeps
+ * nmesh x H x 12 on the device, and the linearisation kernels measure transformed end points against the stored mesh.  With
+ * identity poses the transform is exact (x*1 + y*0 + z*0 + 0), so every result is bit for bit the static handle's.
+ * The poses belong to the handle and are shared by every problem of a batch, as the meshes are; every call of
+ * cfs_problem_set_meshes resets the handle to static.  Line obstacles of such a handle are static (meshes stay refused on a
+ * CFS_OBS_PER_WAYPOINT handle), and meshes stay refused with CFS_INFEAS_SOFTEN and in cfs_chomp_batch.  cfs_clearance_mesh and
+ * cfs_clearance_mesh_device give CFS_ERR_INVALID_ARG on a handle with mesh motion: their certified bound assumes v_obs = 0 in the
+ * mesh columns, and auditing a moving mesh between waypoints needs pose interpolation and a surface-speed term.
+ * CFS_ERR_INVALID_ARG, nothing changes: NULL handle; a handle without meshes (nmesh == 0); a pose that is not finite; a pose with
+ * max|RR' - I| > 1e-9 or det R <= 0 (scaling or mirroring would break the isometry every bound of the traversal relies on).
+ * Synchronises the device; set it between solves. */
+int cfs_problem_set_mesh_motion(cfs_problem *p, const double *poses);
 
 /* ---- CHOMP_FANUC ----------------------------------------------------------
  * self = CHOMP_FANUC(obs_, sys_info, uref, ROBOT); self = self.optimizer()  (Lib/CHOMP_FANUC.m:34-69) for B problems of
@@ -536,7 +560,8 @@ int cfs_clearance(cfs_problem *p, int B, int substeps, const double *x_, const d
                   double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path);
 
 /* ---- clearance audit with mesh obstacles -----------------------------------------------------------------
- * The audit above for a handle whose last nmesh >= 1 obstacles are meshes (cfs_problem_set_meshes; such a handle is static).  Time
+ * The audit above for a handle whose last nmesh >= 1 obstacles are meshes (cfs_problem_set_meshes) and do not move (a handle with
+ * cfs_problem_set_mesh_motion is refused; its line obstacles are static in any case).  Time
  * line, samples, first-minimum rule, t_path and link_path are the contract above word for word; all outputs are B x nobs in the
  * handle's obstacle order (line obstacles first, the last nmesh columns are the meshes).  obs: B x nobs x 6, the rows of the mesh
  * obstacles are not read (as in every solve of such a handle).

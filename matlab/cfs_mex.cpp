@@ -125,6 +125,8 @@ static void make_family(Family &f, int mode, const mxArray *obs, int first, int 
     const size_t nrow = per_wp ? H : 1;                    // obstacle rows per obstacle
     f.margin.assign(nobs, 0.0); f.obs6.assign(6 * (size_t)nobs * nrow, 0.0); f.Dv.assign(nobs, 0.0); f.epsv.assign(nobs, 0.0);
     std::vector<const cfs_mesh *> meshes;
+    std::vector<double> poses;                             // nmesh x H x 12, row-major [R | t] per waypoint (cfs_problem_set_mesh_motion)
+    bool posed = false;                                    // some mesh entry carries .pose
     for (int j = 0; j < nobs; ++j) {
         const mxArray *o = mxGetCell(obs, first + j);
         if (!o) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} is empty", first + j + 1);
@@ -138,7 +140,28 @@ static void make_family(Family &f, int mode, const mxArray *obs, int first, int 
         f.epsv[j] = fE ? mxGetScalar(fE) : 0.0;
         f.margin[j] = mode == CFS_MODE_CFS ? f.epsv[j] : f.Dv[j];
         const mxArray *mh = mxGetField(o, 0, "mesh");
-        if (mh) meshes.push_back(mesh_of(mh));
+        if (mh) {
+            meshes.push_back(mesh_of(mh));
+            // optional obs{j}.pose: 3x4xH or 4x4xH (page i = the mesh's pose at waypoint i), or one 3x4 / 4x4 held over the horizon;
+            // a mesh entry without it is held still (identity)
+            const size_t at = poses.size();
+            poses.resize(at + 12 * H, 0.0);
+            for (size_t i = 0; i < H; ++i) poses[at + 12 * i] = poses[at + 12 * i + 5] = poses[at + 12 * i + 10] = 1.0;
+            if (const mxArray *fp = mxGetField(o, 0, "pose")) {
+                if (!moving) mexErrMsgIdAndTxt("cfs:obs", "obs{%d}.pose: only 'solve' and 'get_con' place a mesh per waypoint", first + j + 1);
+                const size_t rows = mxGetM(fp), ne = mxGetNumberOfElements(fp);
+                if (mxIsChar(fp) || (rows != 3 && rows != 4) || (ne != 4 * rows && ne != 4 * rows * H))
+                    mexErrMsgIdAndTxt("cfs:obs", "obs{%d}.pose must be 3x4xH or 4x4xH (or one 3x4 / 4x4)", first + j + 1);
+                for (size_t i = 0; i < H; ++i) {
+                    const double *pg = mxGetPr(fp) + (ne == 4 * rows ? 0 : 4 * rows * i);   // column-major page
+                    for (size_t r = 0; r < 3; ++r)
+                        for (size_t c = 0; c < 4; ++c) poses[at + 12 * i + 4 * r + c] = pg[c * rows + r];
+                    if (rows == 4 && !(pg[3] == 0.0 && pg[7] == 0.0 && pg[11] == 0.0 && pg[15] == 1.0))
+                        mexErrMsgIdAndTxt("cfs:obs", "obs{%d}.pose: the last row of a 4x4 pose must be [0 0 0 1]", first + j + 1);
+                }
+                posed = true;
+            }
+        }
         else if (!meshes.empty()) mexErrMsgTxt("mesh obstacles must come last in the obs cell");
         else {
             const mxArray *fl = mxGetField(o, 0, "l");
@@ -154,6 +177,7 @@ static void make_family(Family &f, int mode, const mxArray *obs, int first, int 
     check(cfs_problem_create(&d, &f.p));
     if (per_wp) check(cfs_problem_set_obstacle_motion(f.p, CFS_OBS_PER_WAYPOINT));
     if (!meshes.empty()) check(cfs_problem_set_meshes(f.p, (int)meshes.size(), meshes.data()));
+    if (posed) check(cfs_problem_set_mesh_motion(f.p, poses.data()));   // rigidity is the library's check
     // optional sys_info.jacobian = 'fd_literal' (num_jac.m, the default) | 'analytic' (cfs_problem_set_jacobian)
     if (const mxArray *fj = mxGetField(S, 0, "jacobian")) {
         if (!mxIsChar(fj)) mexErrMsgIdAndTxt("cfs:field", "sys_info.jacobian must be 'fd_literal' or 'analytic'");
@@ -327,6 +351,7 @@ static void rrt(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         const mxArray *o = mxGetCell(obs, j), *fD = o ? mxGetField(o, 0, "D") : nullptr, *mh = o ? mxGetField(o, 0, "mesh") : nullptr;
         if (mh) {
             if (!fD) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .mesh and .D", j + 1);
+            if (mxGetField(o, 0, "pose")) mexErrMsgIdAndTxt("cfs:obs", "obs{%d}.pose: a moving mesh needs a time axis ('solve', 'get_con')", j + 1);
             meshes.push_back(mesh_of(mh));
             D_mesh.push_back(mxGetScalar(fD));
             continue;
@@ -477,6 +502,7 @@ static void ik_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         const mxArray *mh = o ? mxGetField(o, 0, "mesh") : nullptr;
         if (mh) {
             if (!fD) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .mesh and .D", j + 1);
+            if (mxGetField(o, 0, "pose")) mexErrMsgIdAndTxt("cfs:obs", "obs{%d}.pose: a moving mesh needs a time axis ('solve', 'get_con')", j + 1);
             meshes.push_back(mesh_of(mh));
             D_mesh.push_back(mxGetScalar(fD));
             continue;
@@ -630,6 +656,7 @@ static void cart_path_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *p
         const mxArray *mh = o ? mxGetField(o, 0, "mesh") : nullptr;
         if (mh) {
             if (!fD) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .mesh and .D", j + 1);
+            if (mxGetField(o, 0, "pose")) mexErrMsgIdAndTxt("cfs:obs", "obs{%d}.pose: a moving mesh needs a time axis ('solve', 'get_con')", j + 1);
             meshes.push_back(mesh_of(mh));
             D_mesh.push_back(mxGetScalar(fD));
             continue;

@@ -119,11 +119,16 @@ def cuda_tensor(t, name, shape, dtype=None, device=None):
 
 
 # ---- obs cells ---------------------------------------------------------------------------------------------------------------
-def obs_meshes(obs):
-    """The Mesh objects of an obs cell; mesh obstacles must come after the line obstacles (cfs_problem_set_meshes)."""
+def obs_meshes(obs, poses=False):
+    """The Mesh objects of an obs cell; mesh obstacles must come after the line obstacles (cfs_problem_set_meshes).  A mesh entry
+    with a pose (a moving mesh, cfs_problem_set_mesh_motion) is refused unless poses=True: only the trajectory solvers have a time
+    axis to place it on, and everything else would silently measure the mesh as stored."""
     flags = ["mesh" in o for o in obs]
     if any(flags) and flags != sorted(flags):
         raise ValueError("mesh obstacles must follow the line-segment obstacles in the obs cell")
+    if not poses and any("mesh" in o and "pose" in o for o in obs):
+        raise ValueError("a mesh obstacle with a pose moves along a trajectory's waypoints: only CFS_FANUC and PSGCFS_FANUC take one "
+                         "(RRT, IK, Cartesian paths and the RRT-CFS planner have no time axis; pass the mesh without pose)")
     return [o["mesh"] for o in obs if "mesh" in o]
 
 

@@ -261,6 +261,7 @@ SYMBOLS = [
     ("cfs_mesh_segment_distance", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("cfs_dist_arm_mesh", C.c_int, [C.POINTER(cfs_robot), C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     ("cfs_problem_set_meshes", C.c_int, [_P, C.c_int, _P]),
+    ("cfs_problem_set_mesh_motion", C.c_int, [_P, _P]),
     ("cfs_chomp_batch", C.c_int, [_P, C.POINTER(cfs_batch_in), _P, _P, _P, C.POINTER(cfs_batch_out)]),
     ("cfs_build_terms_from_ragged_routes_device", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("cfs_rrt_grow", C.c_int, [C.POINTER(cfs_rrt_desc), C.c_int, C.POINTER(cfs_rrt_out)]),

@@ -540,6 +540,7 @@ static LinMeshParams lin_mesh_params(const cfs_problem *p, int B)
 {
     LinMeshParams lm;
     lm.rb = p->rb.p; lm.B = B; lm.H = p->d.H; lm.nmesh = p->nmesh; lm.meshes = p->meshes_d.p;
+    lm.mesh_pose = p->mesh_pose.p;
     lm.dist = p->dist.p; lm.grad = p->grad.p;
     lm.ends = p->m_ends.p; lm.base_d = p->m_base.p; lm.upper_d = p->m_upper.p; lm.base_t = p->m_tri.p; lm.shift_d = p->m_shift.p;
     lm.near = p->m_near.p; lm.piece_d = p->m_pd.p; lm.piece_i = p->m_pi.p; lm.piece_nd = p->m_pnd.p;
@@ -976,7 +977,7 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
         if (meshes[i]->device != p->device) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes[%d] lives on device %d, the problem on %d", i, meshes[i]->device, p->device);
         v[i] = meshes[i]->view();
     }
-    p->meshes_d.release(); p->st_cost.release(); p->st_done.release();
+    p->meshes_d.release(); p->mesh_pose.release(); p->st_cost.release(); p->st_done.release();   // and the meshes are static again
     p->m_ends.release(); p->m_base.release(); p->m_shift.release(); p->m_tri.release(); p->m_near.release(); p->m_upper.release();
     p->m_pd.release(); p->m_pnd.release(); p->m_pi.release(); p->release_clear_mesh();
     p->nmesh = 0;
@@ -992,6 +993,50 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
         CFS_HIPCHK(hipMemcpy(p->meshes_d.p, v.data(), sizeof(DevMesh) * nmesh, hipMemcpyHostToDevice));
         p->nmesh = nmesh;
     }
+    return CFS_SUCCESS;
+}
+
+int cfs_problem_set_mesh_motion(cfs_problem *p, const double *poses)
+{
+    if (!p) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL handle");
+    if (p->nmesh < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh motion needs a handle with mesh obstacles (cfs_problem_set_meshes)");
+    CFS_HIPCHK(hipSetDevice(p->device));
+    if (!poses) {
+        CFS_HIPCHK(hipDeviceSynchronize());  // a solve in flight may still be reading the poses
+        p->mesh_pose.release();
+        return CFS_SUCCESS;
+    }
+    // [R | t] -> [R' | -R't] in double: the kernels map link ends into the frame each mesh is stored in.  Only a rigid motion keeps
+    // the distances (and with them every bound, pruning radius and near-tie margin) of the stored mesh valid.
+    const size_t n = (size_t)p->nmesh * p->d.H;
+    std::vector<double> inv(n * 12);
+    for (size_t e = 0; e < n; ++e) {
+        const double *T = poses + e * 12;
+        const int jm = (int)(e / p->d.H), wp = (int)(e % p->d.H);
+        for (int q = 0; q < 12; ++q)
+            if (!std::isfinite(T[q])) return cfs_fail(CFS_ERR_INVALID_ARG, "pose of mesh %d at waypoint %d is not finite", jm, wp + 1);
+        double dev = 0.0;
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                const double g = T[4 * r] * T[4 * c] + T[4 * r + 1] * T[4 * c + 1] + T[4 * r + 2] * T[4 * c + 2];
+                dev = std::max(dev, std::fabs(g - (r == c ? 1.0 : 0.0)));
+            }
+        const double det = T[0] * (T[5] * T[10] - T[6] * T[9]) - T[1] * (T[4] * T[10] - T[6] * T[8]) + T[2] * (T[4] * T[9] - T[5] * T[8]);
+        if (dev > 1e-9 || !(det > 0.0))
+            return cfs_fail(CFS_ERR_INVALID_ARG, "pose of mesh %d at waypoint %d is not a rigid motion (max|RR' - I| = %.3g, det R = %.3g)",
+                            jm, wp + 1, dev, det);
+        double *o = inv.data() + e * 12;
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) o[4 * r + c] = T[4 * c + r];
+            o[4 * r + 3] = 0.0 - (T[r] * T[3] + T[4 + r] * T[7] + T[8 + r] * T[11]);   // 0 - x: +0 for the identity
+        }
+    }
+    CFS_HIPCHK(hipDeviceSynchronize());
+    if (!p->mesh_pose.p) {
+        const hipError_t e = p->mesh_pose.alloc(n * 12);
+        if (e != hipSuccess) { p->mesh_pose.release(); return cfs_fail(CFS_ERR_HIP, "mesh poses: %s", hipGetErrorString(e)); }
+    }
+    CFS_HIPCHK(hipMemcpy(p->mesh_pose.p, inv.data(), n * 12 * sizeof(double), hipMemcpyHostToDevice));
     return CFS_SUCCESS;
 }
 

@@ -231,6 +231,7 @@ int cfs_check_clearance(const cfs_problem *p, int B, int substeps, const ClearAr
     if (!a.x_ || !a.u || !a.xR1 || !a.obs || !a.dist_wp || !a.dist_path || !a.dist_lower || !a.t_path || !a.link_path || (mesh && !a.tri_path))
         return cfs_fail(CFS_ERR_INVALID_ARG, "NULL array");
     if (mesh && p->nmesh < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh needs a handle with mesh obstacles (cfs_problem_set_meshes): use cfs_clearance");
+    if (mesh && p->mesh_pose.p) return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh audits static meshes (its bound takes v_obs = 0 in the mesh columns): this handle has mesh motion");
     if (!mesh && p->nmesh > 0) return cfs_fail(CFS_ERR_INVALID_ARG, "the clearance audit measures line obstacles only: this handle has %d mesh obstacles", p->nmesh);
     return CFS_SUCCESS;
 }

@@ -108,7 +108,7 @@ struct LinMeshParams {           // distance + literal finite-difference Jacobia
     int B, H, nmesh;
     const DevMesh *meshes;       // device array [nmesh]
     const double *x_;            // B x (H*2*NJ)
-    const int *status_done;      // B, may be null: problems whose entry is non-zero have finished and are skipped
+    const int *status_done;     // B, may be null: problems whose entry is non-zero have finished and are skipped
     int seed_prev;               // base_t holds the winning triangles of the previous outer iteration of the same problems: their
                                  // distance to the moved link is one more upper bound (the trajectory moves little between iterations)
     double *dist;                // B x nmesh x H
@@ -122,6 +122,8 @@ struct LinMeshParams {           // distance + literal finite-difference Jacobia
     int *near;                   // [NJ][nmesh][1+cap] count (-1: overflow) + triangles within the shift margin of the base minimum
     double *piece_d, *piece_nd;  // per piece of a link axis: record / near-list distances (sizes from linearize_mesh_workspace)
     int *piece_i;
+    const double *mesh_pose;     // nmesh x H x 12, may be null (static meshes): the INVERSE of each waypoint's pose [R | t] of a mesh,
+                                 // row-major [R' | -R't]; the kernels measure link ends mapped by it against the mesh as stored
 };
 hipError_t launch_linearize_mesh(int nj, const LinMeshParams &p, hipStream_t s);
 void linearize_mesh_workspace(int nj, int nmesh, size_t *ends, size_t *base, size_t *shift, size_t *near, size_t *piece_d, size_t *piece_i,

@@ -146,7 +146,31 @@ __device__ double mesh_greedy_upper(const DevMesh &m, const double *P0, const do
     }
 }
 
-template <int NJ>
+// End points of link variant `var` at (b, wp), in the frame mesh jm is stored in.  A static handle (mesh_pose null) reads them as
+// mesh_fk_kernel wrote them.  With mesh motion (cfs_problem_set_mesh_motion) both go through the inverse pose of (mesh, waypoint):
+// a rigid map, so every distance, bound and near-tie margin downstream holds unchanged, and equal end points (a point link) stay
+// equal.  POSED is the launch's: a static handle runs the instantiations without the transform, its code is what it always was.
+template <int NVT, bool POSED>
+__device__ __forceinline__ void mesh_link_ends(const LinMeshParams &P, int b, int wp, int var, int jm, double *a6)
+{
+    const double *src = P.ends + (((size_t)b * P.H + wp) * NVT + var) * 6;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) a6[q] = src[q];
+    if constexpr (POSED) {
+        const double *T = P.mesh_pose + ((size_t)jm * P.H + wp) * 12;   // row-major [R' | -R't]
+        double t[12];
+#pragma unroll
+        for (int q = 0; q < 12; ++q) t[q] = T[q];
+#pragma unroll
+        for (int e = 0; e < 6; e += 3) {
+            const double x = a6[e], y = a6[e + 1], z = a6[e + 2];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) a6[e + r] = t[4 * r] * x + t[4 * r + 1] * y + t[4 * r + 2] * z + t[4 * r + 3];
+        }
+    }
+}
+
+template <int NJ, bool POSED>
 __global__ __launch_bounds__(MESH_THREADS, 2) void mesh_upper_kernel(LinMeshParams P)
 {
     constexpr int NVT = nvt(NJ);
@@ -155,8 +179,7 @@ __global__ __launch_bounds__(MESH_THREADS, 2) void mesh_upper_kernel(LinMeshPara
     const int wp = e % P.H, b = (e / P.H) % P.B, jm = (e / (P.H * P.B)) % P.nmesh, k0 = e / (P.H * P.B * P.nmesh);
     if (P.status_done && P.status_done[b] != 0) return;
     double a6[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) a6[q] = P.ends[(((size_t)b * P.H + wp) * NVT + kvoff(k0 + 1)) * 6 + q];
+    mesh_link_ends<NVT, POSED>(P, b, wp, kvoff(k0 + 1), jm, a6);
     const size_t o = (((size_t)b * P.H + wp) * NJ + k0) * P.nmesh + jm;
     double up = mesh_greedy_upper(P.meshes[jm], a6, a6 + 3);
     if (P.seed_prev) {
@@ -344,7 +367,7 @@ __device__ bool mesh_query_coop(const DevMesh &m, const double *P0, const double
     return true;
 }
 
-template <int NJ>
+template <int NJ, bool POSED>
 __global__ __launch_bounds__(64) void mesh_base_kernel(LinMeshParams P)
 {
     constexpr int NVT = nvt(NJ);
@@ -370,8 +393,7 @@ __global__ __launch_bounds__(64) void mesh_base_kernel(LinMeshParams P)
         o = (((size_t)b * P.H + wp) * NJ + k0) * P.nmesh + jm;
         if (live) {
             double a6[6], d[3];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) a6[q] = P.ends[(((size_t)b * P.H + wp) * NVT + kvoff(k0 + 1)) * 6 + q];
+            mesh_link_ends<NVT, POSED>(P, b, wp, kvoff(k0 + 1), jm, a6);
             sub3(a6 + 3, a6, d);
             point = dot3(d, d) == 0.0;                           // M200i links 1 and 3 are points: one "piece"
 #pragma unroll
@@ -456,7 +478,7 @@ __global__ __launch_bounds__(64) void mesh_base_kernel(LinMeshParams P)
 }
 
 // pieces -> link: lexicographic minimum (distance, parameter), surrogate, and the union of the pieces' near lists
-template <int NJ>
+template <int NJ, bool POSED>
 __global__ __launch_bounds__(MESH_THREADS) void mesh_reduce_kernel(LinMeshParams P)
 {
     constexpr int NVT = nvt(NJ);
@@ -474,7 +496,9 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_reduce_kernel(LinMeshParams
     }
     int *near = P.near + o * (NEAR_CAP + 1);
     if (bq.tri < 0) { P.base_d[o] = INFINITY; P.base_t[o] = -1; near[0] = 0; return; }   // farther than the bound: never the minimum, never a candidate
+    double t6[6];                                            // the closest point is in the mesh's frame: so must the link end be
     const double *a6 = P.ends + (((size_t)b * P.H + wp) * NVT + kvoff(k0 + 1)) * 6;
+    if constexpr (POSED) { mesh_link_ends<NVT, true>(P, b, wp, kvoff(k0 + 1), jm, t6); a6 = t6; }
     P.base_d[o] = with_surrogate(bq, a6);
     P.base_t[o] = bq.tri;
     const double lim = bq.d + 4.0 * P.rb->shift_bound;
@@ -499,7 +523,7 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_reduce_kernel(LinMeshParams
     near[0] = over ? -1 : n;                                 // < 0: too many ties, the shifted poses traverse instead
 }
 
-template <int NJ>
+template <int NJ, bool POSED>
 __global__ __launch_bounds__(MESH_THREADS, 2) void mesh_shift_kernel(LinMeshParams P)
 {
     constexpr int NVT = nvt(NJ), NSV = NVT - NJ;
@@ -524,8 +548,7 @@ __global__ __launch_bounds__(MESH_THREADS, 2) void mesh_shift_kernel(LinMeshPara
     double out = INFINITY;
     if (P.base_d[bo + (size_t)(k1 - 1) * P.nmesh] < thr) {
         double a6[6];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) a6[q] = P.ends[(((size_t)b * P.H + wp) * NVT + kvoff(k1) + v) * 6 + q];
+        mesh_link_ends<NVT, POSED>(P, b, wp, kvoff(k1) + v, jm, a6);
         Best bq;
         const size_t ob = bo + (size_t)(k1 - 1) * P.nmesh;
         const int *near = P.near + ob * (NEAR_CAP + 1);
@@ -673,7 +696,7 @@ int upload_mesh(const std::vector<double> &tri9, cfs_mesh **out)
 
 }  // namespace
 
-template <int NJ>
+template <int NJ, bool POSED>
 static hipError_t launch_linearize_mesh_nj(const LinMeshParams &p, hipStream_t s)
 {
     constexpr int NVT = nvt(NJ), NE = 2 * NJ + 1;
@@ -681,17 +704,18 @@ static hipError_t launch_linearize_mesh_nj(const LinMeshParams &p, hipStream_t s
     auto blocks = [](size_t n) { return dim3((unsigned)((n + MESH_THREADS - 1) / MESH_THREADS)); };
     const size_t bh = (size_t)p.B * p.H;
     hipLaunchKernelGGL(mesh_fk_kernel<NJ>, blocks(bh * NE), block, 0, s, p);
-    hipLaunchKernelGGL(mesh_upper_kernel<NJ>, blocks(bh * NJ * p.nmesh), block, 0, s, p);
-    hipLaunchKernelGGL(mesh_base_kernel<NJ>, dim3((unsigned)((bh * NJ * p.nmesh * MESH_PIECES + CO_QPW - 1) / CO_QPW)), dim3(64), 0, s, p);
-    hipLaunchKernelGGL(mesh_reduce_kernel<NJ>, blocks(bh * NJ * p.nmesh), block, 0, s, p);
-    hipLaunchKernelGGL(mesh_shift_kernel<NJ>, blocks(bh * p.nmesh * (NVT - NJ)), block, 0, s, p);
+    hipLaunchKernelGGL((mesh_upper_kernel<NJ, POSED>), blocks(bh * NJ * p.nmesh), block, 0, s, p);
+    hipLaunchKernelGGL((mesh_base_kernel<NJ, POSED>), dim3((unsigned)((bh * NJ * p.nmesh * MESH_PIECES + CO_QPW - 1) / CO_QPW)), dim3(64), 0, s, p);
+    hipLaunchKernelGGL((mesh_reduce_kernel<NJ, POSED>), blocks(bh * NJ * p.nmesh), block, 0, s, p);
+    hipLaunchKernelGGL((mesh_shift_kernel<NJ, POSED>), blocks(bh * p.nmesh * (NVT - NJ)), block, 0, s, p);
     hipLaunchKernelGGL(mesh_fd_kernel<NJ>, blocks(bh * p.nmesh), block, 0, s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_linearize_mesh(int nj, const LinMeshParams &p, hipStream_t s)
 {
-    return cfs_for_nj(nj, [&](auto N) { return launch_linearize_mesh_nj<decltype(N)::value>(p, s); });
+    if (p.mesh_pose) return cfs_for_nj(nj, [&](auto N) { return launch_linearize_mesh_nj<decltype(N)::value, true>(p, s); });
+    return cfs_for_nj(nj, [&](auto N) { return launch_linearize_mesh_nj<decltype(N)::value, false>(p, s); });
 }
 
 // doubles / ints of workspace per (problem, waypoint) the pipeline needs

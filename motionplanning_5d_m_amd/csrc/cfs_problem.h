@@ -26,6 +26,7 @@ struct cfs_problem {
     // mesh obstacles (cfs_problem_set_meshes): the last nmesh of the nobs obstacles
     int nmesh = 0;
     DevBuf<DevMesh> meshes_d;
+    DevBuf<double> mesh_pose;    // cfs_problem_set_mesh_motion: nmesh x H x 12 inverse poses (null: the meshes are static)
     DevBuf<double> st_cost, m_ends, m_base, m_shift, m_upper, m_pd, m_pnd;
     DevBuf<int> st_done, m_tri, m_near, m_pi;
     // cfs_clearance_mesh*: per-sample workspace for cm_S sub-steps (grown by the first audit that needs more) and rho on the device
@@ -67,7 +68,7 @@ struct cfs_problem {
         F1.release(); F2.release(); Cq.release(); cost.release();
         lim.release(); maxin.release(); margin.release(); x0.release(); qu.release(); dist.release();
         grad.release(); Yg.release(); noise_row.release(); order.release(); okey.release(); order_user.release();
-        linkid.release(); pool_flag.release(); meshes_d.release(); st_cost.release(); st_done.release();
+        linkid.release(); pool_flag.release(); meshes_d.release(); mesh_pose.release(); st_cost.release(); st_done.release();
         m_ends.release(); m_base.release(); m_shift.release(); m_tri.release(); m_near.release(); m_upper.release();
         m_pd.release(); m_pnd.release(); m_pi.release(); release_clear_mesh();
         stamps.release(); trace.release(); u_log.release(); soft_viol.release(); soft_n.release();

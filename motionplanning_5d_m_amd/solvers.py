@@ -53,6 +53,43 @@ def obs_traj_to_array(obs, H):
     return _f64(out)
 
 
+def mesh_pose_array(pose, H):
+    """A mesh's rigid poses -> (H, 12): row i = the row-major 3x4 [R | t] that places the mesh in the world at waypoint i+1
+    (cfs_problem_set_mesh_motion).  pose: (H, 4, 4) or (H, 3, 4), or one (4, 4) / (3, 4) held over the horizon.  ValueError for any
+    other shape, a last row that is not [0, 0, 0, 1], a value that is not finite, and a pose that is not a rigid motion by the
+    library's own rule (max|RR' - I| > 1e-9 or det R <= 0: scaled, sheared or mirrored)."""
+    H = int(H)
+    try:
+        T = np.array(pose, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"a mesh pose must be an array of 3x4 or 4x4 matrices, not {pose!r}") from None
+    if T.shape in ((4, 4), (3, 4)):
+        T = np.broadcast_to(T, (H,) + T.shape)
+    if T.shape not in ((H, 4, 4), (H, 3, 4)):
+        raise ValueError(f"a mesh pose has shape {T.shape}: expected (H, 4, 4), (H, 3, 4), (4, 4) or (3, 4) with H={H}")
+    if not np.isfinite(T).all():
+        raise ValueError("a mesh pose holds a value that is not finite")
+    if T.shape[1] == 4 and not (T[:, 3, :] == np.array([0.0, 0.0, 0.0, 1.0])).all():
+        raise ValueError("the last row of a 4x4 mesh pose must be [0, 0, 0, 1]")
+    R = T[:, :3, :3]
+    dev = np.abs(R @ R.transpose(0, 2, 1) - np.eye(3)).max(axis=(1, 2))
+    det = np.linalg.det(R)
+    bad = np.nonzero((dev > 1e-9) | ~(det > 0.0))[0]
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"the mesh pose at waypoint {i + 1} is not a rigid motion: max|RR' - I| = {dev[i]:.3g}, det R = {det[i]:.3g}")
+    return _f64(T[:, :3, :].reshape(H, 12))
+
+
+def obs_mesh_poses(obs, H):
+    """None when no mesh entry of the obs cell carries a pose, else (nmesh, H, 12): mesh_pose_array of every mesh entry in cell
+    order, the identity for an entry without one (it is held still)."""
+    entries = [o for o in obs if "mesh" in o]
+    if not any("pose" in o for o in entries):
+        return None
+    return _f64(np.stack([mesh_pose_array(o["pose"] if "pose" in o else np.eye(4), H) for o in entries]))
+
+
 def _joint_limits_array(joint_limits, robot, nj):
     """None | (nj, 2) float64 [lo, hi] from CFSBatch's joint_limits=: None (no position rows), "robot" (robot.thetamax[:nj]) or an
     (nj, 2) array.  ValueError for anything malformed (wrong shape, NaN, lo >= hi), before the device is touched."""
@@ -327,7 +364,27 @@ class CFSBatch:
         if len(meshes) and self.obstacle_motion == "per_waypoint":
             raise ValueError("mesh obstacles are static: not supported on a per-waypoint handle")
         self._meshes = list(meshes)                      # keep them alive as long as the handle uses them
+        self._mesh_motion = False                        # cfs_problem_set_meshes resets the handle to static meshes
         _lib.check(self._lib.cfs_problem_set_meshes(self._h, *_args.mesh_table(self._meshes)[:2]))
+
+    def set_mesh_motion(self, poses):
+        """A rigid pose per waypoint for every mesh of the handle (cfs_problem_set_mesh_motion, include/cfs_hip.h): poses is
+        (nmesh, H, 12), (nmesh, H, 3, 4) or (nmesh, H, 4, 4), or a sequence of nmesh entries that mesh_pose_array accepts;
+        entry [j][i] places mesh j in the world at waypoint i+1.  None: the meshes are static again.  The poses belong to the
+        handle and are shared by every problem of a batch."""
+        meshes = getattr(self, "_meshes", None)
+        if not meshes:
+            raise ValueError("set_mesh_motion needs a handle with mesh obstacles (set_meshes)")
+        if poses is None:
+            _lib.check(self._lib.cfs_problem_set_mesh_motion(self._h, None))
+            self._mesh_motion = False
+            return
+        if len(poses) != len(meshes):
+            raise ValueError(f"set_mesh_motion needs one pose sequence per mesh: {len(meshes)}, not {len(poses)}")
+        arr = _f64(np.stack([mesh_pose_array(np.asarray(p, float).reshape(self.H, 3, 4) if np.shape(p) == (self.H, 12) else p, self.H)
+                             for p in poses]))
+        _lib.check(self._lib.cfs_problem_set_mesh_motion(self._h, _ptr(arr)))
+        self._mesh_motion = True
 
     # ---- whole solve ------------------------------------------------------------------------------
     def _outputs(self, B, device=None):
@@ -378,6 +435,8 @@ class CFSBatch:
             raise ValueError("clearance_mesh needs a handle with mesh obstacles (set_meshes): use clearance for line obstacles")
         if not mesh and getattr(self, "_meshes", None):
             raise ValueError("the clearance audit measures line obstacles only: this handle has mesh obstacles")
+        if mesh and getattr(self, "_mesh_motion", False):
+            raise ValueError("clearance_mesh audits static meshes (its bound takes v_obs = 0): this handle has mesh motion")
         if device:
             B = x_.shape[0]
             for t in (x_, u, xR1, obs):
@@ -718,12 +777,14 @@ class _SolverBase:
         joint_limits: None (the default) | "robot" | an (njoint, 2) array of [lo, hi] (CFSBatch); get_con then has the position rows.
         on_infeasible: "stop" (the default) | "soften" with soft_weight= (CFSBatch); after optimizer(), viol_all and n_soft.
         obs{j}["l"] may be 3x2xH (shape (3, 2, H): the obstacle's axis at waypoints 1..H); any such entry makes the handle
-        per-waypoint, and the 3x2 entries are then held over the horizon (obs_traj_to_array)."""
+        per-waypoint, and the 3x2 entries are then held over the horizon (obs_traj_to_array).
+        A mesh entry may carry "pose" (mesh_pose_array: the rigid pose of the mesh at waypoints 1..H); mesh entries without one
+        are then held still, the line obstacles of such a cell are static, and audit_mesh= is refused."""
         _args.code(_lib.JACOBIAN, jacobian, "jacobian")
         _infeasible_args(on_infeasible, soft_weight)
         _joint_limits_array(joint_limits, sys_info.robot, int(sys_info.njoint))
         self.audit = None if audit is None else _args.int_in(audit, "audit", 1, 64)
-        meshes = obs_meshes(obs)
+        meshes = obs_meshes(obs, poses=True)
         if self.audit is not None and meshes:
             raise ValueError("audit= measures line obstacles only: the obs cell holds mesh obstacles")
         self.clearance = None
@@ -731,6 +792,9 @@ class _SolverBase:
         if self.audit_mesh is not None and not meshes:
             raise ValueError("audit_mesh= needs an obs cell with at least one mesh obstacle: audit= measures line obstacles")
         self.clearance_mesh = None
+        self._mesh_poses = obs_mesh_poses(obs, sys_info.H)   # checked before anything touches the device
+        if self.audit_mesh is not None and self._mesh_poses is not None:
+            raise ValueError("audit_mesh= audits static meshes: a mesh entry of the obs cell carries a pose")
         if on_infeasible == "soften" and meshes:
             raise ValueError('on_infeasible="soften" does not support mesh obstacles')
         self._moving = obs_moving(obs)
@@ -753,6 +817,8 @@ class _SolverBase:
         self.viol_all, self.n_soft = np.zeros(0), 0
         if meshes:
             self._batch.set_meshes(meshes)
+        if self._mesh_poses is not None:
+            self._batch.set_mesh_motion(self._mesh_poses)
 
     def _args(self):
         s = self.sys_info

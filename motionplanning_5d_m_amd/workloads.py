@@ -169,6 +169,22 @@ def config5(B=256, seed=20260105, H=50, n_tri=10000, margin=0.12, tri=None):
     return s, batch, tri
 
 
+def config5_traveller(B=256, seed=20260105, H=50, n_tri=10000, margin=0.12, travel=1.0):
+    """Config 5 with a carrier travelling through the cell (cfs_problem_set_mesh_motion): the map of config5, held still, plus a
+    second mesh, a box riding the conveyor of ``mesh.assembly_line`` along +y at constant velocity, `travel` metres over the
+    horizon (it starts at the belt's -y end and stays on the belt).  Returns (family, batch, [map, carrier], poses (2, H, 4, 4));
+    the batch has nobs = 2, both of them meshes."""
+    from .mesh import box_mesh
+    s, bt, tri = config5(B=B, seed=seed, H=H, n_tri=n_tri, margin=margin)
+    bx, by, bz = s.robot.base
+    carrier = box_mesh([bx + 0.70, by - 0.75, bz + 0.125], [bx + 0.90, by - 0.55, bz + 0.275], n=4)
+    poses = np.tile(np.eye(4), (2, H, 1, 1))
+    poses[1, :, 1, 3] = travel * np.arange(1, H + 1) / H                  # waypoint i+1 at time (i+1)*delta_t: constant velocity
+    bt.nobs, bt.obs = 2, np.zeros((B, 2, 6))
+    bt.margin_cfs, bt.margin_psg = np.full(2, margin), np.full(2, margin)
+    return s, bt, [tri, carrier], poses
+
+
 def config5_reference_map(B=256, seed=20260105, H=50, fixture=None):
     """BASELINE config 5 on the REFERENCE's own triangles: the cell of map/assembly line_Assem1.STL around robot.base after
     Lib/functions/MapFromSTL.m:6-10 and mm -> m (tests/golden/assembly_line_cell.npz, a data fixture made in the build
