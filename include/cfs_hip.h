@@ -405,7 +405,7 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
  * cfs_problem_set_meshes resets the handle to static.  Line obstacles of such a handle are static (meshes stay refused on a
  * CFS_OBS_PER_WAYPOINT handle), and meshes stay refused with CFS_INFEAS_SOFTEN and in cfs_chomp_batch.  cfs_clearance_mesh and
  * cfs_clearance_mesh_device give CFS_ERR_INVALID_ARG on a handle with mesh motion: their certified bound assumes v_obs = 0 in the
- * mesh columns, and auditing a moving mesh between waypoints needs pose interpolation and a surface-speed term.
+ * mesh columns; cfs_clearance_mesh_motion audits such a handle, with pose interpolation and a surface-speed term in its bound.
  * CFS_ERR_INVALID_ARG, nothing changes: NULL handle; a handle without meshes (nmesh == 0); a pose that is not finite; a pose with
  * max|RR' - I| > 1e-9 or det R <= 0 (scaling or mirroring would break the isometry every bound of the traversal relies on).
  * Synchronises the device; set it between solves. */
@@ -590,6 +590,46 @@ int cfs_clearance_mesh_device(cfs_problem *p, int B, int substeps, const double 
                               int *link_path, int *tri_path, void *stream);
 int cfs_clearance_mesh(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
                        double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, int *tri_path);
+
+/* ---- clearance audit with moving meshes -------------------------------------------------------------------
+ * The audit above for a handle whose meshes move (cfs_problem_set_mesh_motion).  Arguments, outputs, column order, time line,
+ * samples, first-minimum rule, t_path, link_path and tri_path are those of cfs_clearance_mesh word for word; what is new is where
+ * a mesh stands at a sample between two waypoints, and the term its motion adds to the bound.
+ *   static handle   meshes and no motion: the static path runs, every result is bit for bit cfs_clearance_mesh's.
+ *   moving handle   pose [j][i] belongs to waypoint i+1 (row i of x_).  Interval 0 has no earlier pose: pose [j][0] is held over
+ *                   it (as the line audit holds row 0 there).  In interval i >= 1 the sample at k = S uses the stored inverse pose
+ *                   [j][i] exactly as the linearisation reads it, so dist_wp is measured where get_con measures it.  If poses
+ *                   i-1 and i are bitwise equal, the stored pose [j][i] is used over the whole interval and the mesh speed is 0:
+ *                   constant or identity poses give bit for bit the static audit.
+ *   interpolation   otherwise, at s = k/S mesh j is placed by p -> R(s)(p - c_j) + c_w(s).  c_j = (min + max)/2 of the bounding
+ *                   box of mesh j's stored vertices.  R(s) = Rod(a, s*theta) R_{i-1}, the rotation about the unit axis a by the
+ *                   angle s*theta applied after pose i-1's, with a and theta from R_rel = R_i R_{i-1}': w = vee(R_rel - R_rel')/2,
+ *                   theta = atan2(|w|, (tr R_rel - 1)/2), a = w/|w| (a pure translation has theta = 0 and R(s) = R_{i-1}).
+ *                   c_w(s) is the straight line from R_{i-1} c_j + t_{i-1} to R_i c_j + t_i.  No hierarchy is rebuilt: the link
+ *                   ends go into the stored frame by the inverse, w -> c_j + R(s)'(w - c_w(s)); the near-zero surrogate and the
+ *                   closest point live in the mesh's frame (an isometry keeps every distance).
+ *   dist_lower      the formula of cfs_clearance with L = L_arm + v_mesh[j][i] on the sub-intervals of interval i,
+ *                   v_mesh[j][i] = (theta*r_j + |c_w(1) - c_w(0)|)/delta_t, r_j = max over the stored vertices of |v - c_j|;
+ *                   0 in interval 0 and in held intervals.  No surface point moves faster than that under the interpolation
+ *                   above; the distance is a minimum over pairs of points, each Lipschitz with the sum of the two speeds, so the
+ *                   GUARANTEE of cfs_clearance holds for the interpolated motion.
+ *   line columns    the lines of such a handle are static: bit for bit cfs_clearance's.
+ * The inverse transforms of the H*substeps + 1 distinct samples of every mesh do not depend on the problem: a small kernel writes
+ * them once into a table on the handle, rebuilt only when substeps or the poses change.  Deterministic (no atomics); a problem's
+ * results depend on neither B nor its position in the batch.
+ * CFS_ERR_INVALID_ARG, nothing written: everything cfs_clearance_mesh refuses other than the motion itself (NULL handle or array,
+ * B outside 1..max_batch, substeps outside 1..64, a handle without meshes); a mesh whose poses at two consecutive waypoints
+ * differ by more than a quarter turn (tr R_rel < 1, theta > pi/2: towards pi the axis taken from the skew part loses accuracy and
+ * theta*r_j certifies nothing; the message names the mesh and the waypoint).  cfs_clearance_mesh and cfs_clearance_mesh_device
+ * keep refusing a handle with mesh motion.
+ * cfs_clearance_mesh_motion_device: DEVICE pointers, enqueued on `stream`, no synchronisation once the workspace and the table
+ * exist.  cfs_clearance_mesh_motion: HOST pointers, synchronises. */
+int cfs_clearance_mesh_motion_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1,
+                                     const double *obs, double *dist_wp, double *dist_path, double *dist_lower, double *t_path,
+                                     int *link_path, int *tri_path, void *stream);
+int cfs_clearance_mesh_motion(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1,
+                              const double *obs, double *dist_wp, double *dist_path, double *dist_lower, double *t_path,
+                              int *link_path, int *tri_path);
 
 /* ---- inverse kinematics -------------------------------------------------------------------------------
  * Every entry point above that takes a goal takes a joint vector, as the reference's drivers type it in (xg, main_FANUC.m:30,

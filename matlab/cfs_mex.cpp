@@ -14,6 +14,9 @@
 //   [dist_path, dist_lower, dist_wp, t_path, link_path, tri_path] = cfs_mex('clearance_mesh', mode, obs, sys_info, ROBOT, x_, u, substeps)
 //        the same for an obs cell with at least one mesh obstacle (cfs_clearance_mesh): every column, and per mesh column the closest
 //        triangle of the mesh's list at the path minimum (1-based; 0 in line columns)
+//   [dist_path, dist_lower, dist_wp, t_path, link_path, tri_path] = cfs_mex('clearance_mesh_motion', mode, obs, sys_info, ROBOT, x_, u, substeps)
+//        the same where mesh entries carry obs{j}.pose (cfs_clearance_mesh_motion): the meshes are placed by the interpolated pose
+//        between the waypoints and dist_lower carries their surface speed; 'clearance_mesh' itself keeps refusing the field
 //   [u, x_, cost_all, e_cost_all, e_u_all, iter_O] = cfs_mex('chomp', obs_, sys_info, ROBOT, uref)   % CHOMP_FANUC.optimizer (Lib/CHOMP_FANUC.m:54-69);
 //        obs_ = the reference's cell: obs_{1}.num_obs followed by the obstacles (M16iB/CHOMP.m:26-29)
 //   [d, linkid, grad] = cfs_mex('dist_arm', theta, obs_l, robot, ROBOT)  % dist_arm_3D_200i_2 / dist_arm_3D_Heu_2 / dist_arm_2L(theta, base, obs_l, robot)
@@ -272,6 +275,25 @@ static void clearance_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *p
     std::vector<int> link(nobs, 0), tri(nobs, -1);
     check(cfs_clearance_mesh(f.p, 1, S, mxGetPr(prhs[5]), mxGetPr(prhs[6]), field_ptr(prhs[3], "xR"), f.obs6.data(), mxGetPr(o[2]), mxGetPr(o[0]),
                              mxGetPr(o[1]), mxGetPr(o[3]), link.data(), tri.data()));
+    for (int j = 0; j < nobs; ++j) { mxGetPr(o[4])[j] = link[j]; mxGetPr(o[5])[j] = tri[j] + 1; }
+    for (int k = 0; k < 6; ++k) { if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]); }
+}
+
+// the same for an obs cell whose meshes may carry obs{j}.pose (cfs_clearance_mesh_motion): between two waypoints a mesh is placed
+// by the interpolated pose and its surface speed enters dist_lower; a cell without poses gives 'clearance_mesh's results
+static void clearance_mesh_motion(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs < 7) mexErrMsgTxt("[dist_path, dist_lower, dist_wp, t_path, link_path, tri_path] = cfs_mex('clearance_mesh_motion', mode, obs, sys_info, ROBOT, x_, u [, substeps])");
+    const int mode = (int)mxGetScalar(prhs[1]);
+    const std::string ROBOT = mxArrayToString(prhs[4]);
+    Family f;
+    make_family(f, mode, prhs[2], 0, (int)mxGetNumberOfElements(prhs[2]), prhs[3], ROBOT.c_str(), false, true);
+    const int nobs = f.d.nobs, S = nrhs > 7 ? (int)mxGetScalar(prhs[7]) : 16;
+    mxArray *o[6];
+    for (int k = 0; k < 6; ++k) o[k] = mxCreateDoubleMatrix(nobs, 1, mxREAL);
+    std::vector<int> link(nobs, 0), tri(nobs, -1);
+    check(cfs_clearance_mesh_motion(f.p, 1, S, mxGetPr(prhs[5]), mxGetPr(prhs[6]), field_ptr(prhs[3], "xR"), f.obs6.data(), mxGetPr(o[2]),
+                                    mxGetPr(o[0]), mxGetPr(o[1]), mxGetPr(o[3]), link.data(), tri.data()));
     for (int j = 0; j < nobs; ++j) { mxGetPr(o[4])[j] = link[j]; mxGetPr(o[5])[j] = tri[j] + 1; }
     for (int k = 0; k < 6; ++k) { if (k < nlhs || k == 0) plhs[k] = o[k]; else mxDestroyArray(o[k]); }
 }
@@ -720,6 +742,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         clearance(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "clearance_mesh") {
         clearance_mesh(nlhs, plhs, nrhs, prhs);
+    } else if (cmd == "clearance_mesh_motion") {
+        clearance_mesh_motion(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "chomp") {
         chomp(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "dist_arm") {

@@ -293,6 +293,8 @@ SYMBOLS = [
     ("cfs_clearance", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("cfs_clearance_mesh_device", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("cfs_clearance_mesh", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("cfs_clearance_mesh_motion_device", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("cfs_clearance_mesh_motion", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("cfs_ik_solve", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out)]),
     ("cfs_ik_solve_device", C.c_int, [C.POINTER(cfs_ik_desc), C.c_int, _P, _P, _P, C.POINTER(cfs_ik_out), _P]),
     ("cfs_tool_pose", C.c_int, [C.POINTER(cfs_robot), C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),

@@ -977,7 +977,8 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
         if (meshes[i]->device != p->device) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes[%d] lives on device %d, the problem on %d", i, meshes[i]->device, p->device);
         v[i] = meshes[i]->view();
     }
-    p->meshes_d.release(); p->mesh_pose.release(); p->st_cost.release(); p->st_done.release();   // and the meshes are static again
+    p->meshes_d.release(); p->release_mesh_motion(); p->st_cost.release(); p->st_done.release();   // and the meshes are static again
+    p->meshes_h.clear(); p->mesh_frame.clear();
     p->m_ends.release(); p->m_base.release(); p->m_shift.release(); p->m_tri.release(); p->m_near.release(); p->m_upper.release();
     p->m_pd.release(); p->m_pnd.release(); p->m_pi.release(); p->release_clear_mesh();
     p->nmesh = 0;
@@ -991,9 +992,46 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
         CFS_HIPCHK(p->st_cost.alloc(2 * (size_t)p->d.max_batch));
         CFS_HIPCHK(p->st_done.alloc(p->d.max_batch));
         CFS_HIPCHK(hipMemcpy(p->meshes_d.p, v.data(), sizeof(DevMesh) * nmesh, hipMemcpyHostToDevice));
+        p->meshes_h = v;
         p->nmesh = nmesh;
     }
     return CFS_SUCCESS;
+}
+
+// The H interval records (CLEAR_ITV doubles each, cfs_host.h) of one mesh for the audit between the waypoints, in double: T is its
+// H x 12 poses, frame = (c_j, r_j).  Interval i joins poses i-1 and i; interval 0 and an interval whose two poses are bitwise equal are
+// held.  The first interval that turns by more than a quarter (tr R_rel < 1) is reported in (turn_mesh, turn_wp): the audit refuses it.
+static void mesh_motion_intervals(const double *T, int H, double dt, const double *frame, double *itv, int jm, int &turn_mesh, int &turn_wp)
+{
+    for (int i = 0; i < H; ++i) {
+        double *q = itv + (size_t)i * CLEAR_ITV;
+        const double *T1 = T + (size_t)i * 12, *T0 = T + (size_t)(i > 0 ? i - 1 : 0) * 12;
+        for (int r = 0; r < 3; ++r) q[20 + r] = frame[r];
+        if (i == 0 || memcmp(T0, T1, 12 * sizeof(double)) == 0) continue;      // held: q[0] = 0, v_mesh = 0
+        double Rr[9], c0[3], c1[3];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) Rr[3 * r + c] = T1[4 * r] * T0[4 * c] + T1[4 * r + 1] * T0[4 * c + 1] + T1[4 * r + 2] * T0[4 * c + 2];
+        const double tr = Rr[0] + Rr[4] + Rr[8];
+        if (tr < 1.0) {
+            if (turn_mesh < 0) { turn_mesh = jm; turn_wp = i; }
+            continue;
+        }
+        const double w[3] = {(Rr[7] - Rr[5]) / 2.0, (Rr[2] - Rr[6]) / 2.0, (Rr[3] - Rr[1]) / 2.0};
+        const double nw = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), theta = std::atan2(nw, (tr - 1.0) / 2.0);
+        for (int r = 0; r < 3; ++r) {
+            c0[r] = T0[4 * r] * frame[0] + T0[4 * r + 1] * frame[1] + T0[4 * r + 2] * frame[2] + T0[4 * r + 3];
+            c1[r] = T1[4 * r] * frame[0] + T1[4 * r + 1] * frame[1] + T1[4 * r + 2] * frame[2] + T1[4 * r + 3];
+        }
+        const double dx = c1[0] - c0[0], dy = c1[1] - c0[1], dz = c1[2] - c0[2];
+        q[0] = 1.0;
+        for (int r = 0; r < 3; ++r) {
+            q[1 + r] = nw > 0.0 ? w[r] / nw : 0.0;
+            for (int c = 0; c < 3; ++c) q[5 + 3 * r + c] = T0[4 * r + c];
+            q[14 + r] = c0[r]; q[17 + r] = c1[r];
+        }
+        q[4] = theta;
+        q[23] = (theta * frame[3] + std::sqrt(dx * dx + dy * dy + dz * dz)) / dt;
+    }
 }
 
 int cfs_problem_set_mesh_motion(cfs_problem *p, const double *poses)
@@ -1003,7 +1041,7 @@ int cfs_problem_set_mesh_motion(cfs_problem *p, const double *poses)
     CFS_HIPCHK(hipSetDevice(p->device));
     if (!poses) {
         CFS_HIPCHK(hipDeviceSynchronize());  // a solve in flight may still be reading the poses
-        p->mesh_pose.release();
+        p->release_mesh_motion();
         return CFS_SUCCESS;
     }
     // [R | t] -> [R' | -R't] in double: the kernels map link ends into the frame each mesh is stored in.  Only a rigid motion keeps
@@ -1032,11 +1070,41 @@ int cfs_problem_set_mesh_motion(cfs_problem *p, const double *poses)
         }
     }
     CFS_HIPCHK(hipDeviceSynchronize());
+    // what the audit between the waypoints needs per (mesh, interval) (cfs_clearance_mesh_motion, cfs_host.h CLEAR_ITV)
+    std::vector<double> itv(n * CLEAR_ITV, 0.0);
+    int turn_mesh = -1, turn_wp = 0;
+    if (p->mesh_frame.empty()) {             // c_j and r_j of the stored vertices, once per cfs_problem_set_meshes
+        std::vector<double> frame(4 * (size_t)p->nmesh);
+        for (int jm = 0; jm < p->nmesh; ++jm) {
+            const DevMesh &m = p->meshes_h[jm];
+            std::vector<double> tri(9 * (size_t)m.nt);
+            CFS_HIPCHK(hipMemcpy(tri.data(), m.tri, tri.size() * sizeof(double), hipMemcpyDeviceToHost));
+            double *f = frame.data() + 4 * jm, r2 = 0.0;
+            for (int r = 0; r < 3; ++r) {
+                double lo = INFINITY, hi = -INFINITY;
+                for (size_t v = 0; v < 3 * (size_t)m.nt; ++v) { lo = std::min(lo, tri[3 * v + r]); hi = std::max(hi, tri[3 * v + r]); }
+                f[r] = (lo + hi) / 2.0;
+            }
+            for (size_t v = 0; v < 3 * (size_t)m.nt; ++v) {
+                const double x = tri[3 * v] - f[0], y = tri[3 * v + 1] - f[1], z = tri[3 * v + 2] - f[2];
+                r2 = std::max(r2, x * x + y * y + z * z);
+            }
+            f[3] = std::sqrt(r2);
+        }
+        p->mesh_frame = frame;
+    }
+    for (int jm = 0; jm < p->nmesh; ++jm)
+        mesh_motion_intervals(poses + (size_t)jm * p->d.H * 12, p->d.H, p->d.robot.delta_t, p->mesh_frame.data() + 4 * jm,
+                              itv.data() + (size_t)jm * p->d.H * CLEAR_ITV, jm, turn_mesh, turn_wp);
     if (!p->mesh_pose.p) {
-        const hipError_t e = p->mesh_pose.alloc(n * 12);
-        if (e != hipSuccess) { p->mesh_pose.release(); return cfs_fail(CFS_ERR_HIP, "mesh poses: %s", hipGetErrorString(e)); }
+        hipError_t e = p->mesh_pose.alloc(n * 12);
+        if (e == hipSuccess) e = p->mesh_itv.alloc(n * CLEAR_ITV);
+        if (e != hipSuccess) { p->release_mesh_motion(); return cfs_fail(CFS_ERR_HIP, "mesh poses: %s", hipGetErrorString(e)); }
     }
     CFS_HIPCHK(hipMemcpy(p->mesh_pose.p, inv.data(), n * 12 * sizeof(double), hipMemcpyHostToDevice));
+    CFS_HIPCHK(hipMemcpy(p->mesh_itv.p, itv.data(), itv.size() * sizeof(double), hipMemcpyHostToDevice));
+    p->turn_mesh = turn_mesh; p->turn_wp = turn_wp;
+    ++p->motion_gen;                         // the audit's pose table belongs to the poses before
     return CFS_SUCCESS;
 }
 

@@ -223,15 +223,20 @@ hipError_t launch_clearance(const ClearParams &p, hipStream_t s)
 
 // ---- C ABI (include/cfs_hip.h, "clearance audit") ---------------------------------------------------------------------------
 // Reads the family constants of the handle (robot, H, nobs, delta_t, obstacle motion) and nothing a solve writes.
-int cfs_check_clearance(const cfs_problem *p, int B, int substeps, const ClearArrays &a, bool mesh)
+int cfs_check_clearance(const cfs_problem *p, int B, int substeps, const ClearArrays &a, bool mesh, bool motion)
 {
     int rc = cfs_check_batch(p, B);
     if (rc) return rc;
     if (substeps < 1 || substeps > 64) return cfs_fail(CFS_ERR_INVALID_ARG, "substeps=%d outside 1..64", substeps);
     if (!a.x_ || !a.u || !a.xR1 || !a.obs || !a.dist_wp || !a.dist_path || !a.dist_lower || !a.t_path || !a.link_path || (mesh && !a.tri_path))
         return cfs_fail(CFS_ERR_INVALID_ARG, "NULL array");
-    if (mesh && p->nmesh < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh needs a handle with mesh obstacles (cfs_problem_set_meshes): use cfs_clearance");
-    if (mesh && p->mesh_pose.p) return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh audits static meshes (its bound takes v_obs = 0 in the mesh columns): this handle has mesh motion");
+    if (mesh && p->nmesh < 1)
+        return cfs_fail(CFS_ERR_INVALID_ARG, "%s needs a handle with mesh obstacles (cfs_problem_set_meshes): use cfs_clearance",
+                        motion ? "cfs_clearance_mesh_motion" : "cfs_clearance_mesh");
+    if (mesh && motion && p->mesh_pose.p && p->turn_mesh >= 0)
+        return cfs_fail(CFS_ERR_INVALID_ARG, "the poses of mesh %d at waypoints %d and %d are more than a quarter turn apart: the audit does not interpolate them",
+                        p->turn_mesh, p->turn_wp, p->turn_wp + 1);
+    if (mesh && !motion && p->mesh_pose.p) return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh audits static meshes (its bound takes v_obs = 0 in the mesh columns): this handle has mesh motion");
     if (!mesh && p->nmesh > 0) return cfs_fail(CFS_ERR_INVALID_ARG, "the clearance audit measures line obstacles only: this handle has %d mesh obstacles", p->nmesh);
     return CFS_SUCCESS;
 }
@@ -248,9 +253,9 @@ hipError_t cfs_launch_clearance_lines(const cfs_problem *p, int B, int substeps,
     return launch_clearance(cp, s);
 }
 
-int cfs_clearance_host(cfs_problem *p, int B, int substeps, const ClearArrays &h, bool mesh)
+int cfs_clearance_host(cfs_problem *p, int B, int substeps, const ClearArrays &h, bool mesh, bool motion)
 {
-    int rc = cfs_check_clearance(p, B, substeps, h, mesh);
+    int rc = cfs_check_clearance(p, B, substeps, h, mesh, motion);
     if (rc) return rc;
     CFS_HIPCHK(hipSetDevice(p->device));
     const size_t nB = B, n = nB * p->d.nobs;
@@ -258,7 +263,8 @@ int cfs_clearance_host(cfs_problem *p, int B, int substeps, const ClearArrays &h
     const ClearArrays a{st.up(h.x_, nB * p->nx), st.up(h.u, nB * p->nn), st.up(h.xR1, nB * p->ns), st.up(h.obs, nB * cfs_obs_rows(p) * 6),
                         st.out<double>(n), st.out<double>(n), st.out<double>(n), st.out<double>(n), st.out<int>(n), mesh ? st.out<int>(n) : nullptr};
     if (st.err != hipSuccess) return st.result("staging");
-    rc = mesh ? cfs_clearance_mesh_device(p, B, substeps, a.x_, a.u, a.xR1, a.obs, a.dist_wp, a.dist_path, a.dist_lower, a.t_path, a.link_path, a.tri_path, nullptr)
+    rc = motion ? cfs_clearance_mesh_motion_device(p, B, substeps, a.x_, a.u, a.xR1, a.obs, a.dist_wp, a.dist_path, a.dist_lower, a.t_path, a.link_path, a.tri_path, nullptr)
+       : mesh ? cfs_clearance_mesh_device(p, B, substeps, a.x_, a.u, a.xR1, a.obs, a.dist_wp, a.dist_path, a.dist_lower, a.t_path, a.link_path, a.tri_path, nullptr)
               : cfs_clearance_device(p, B, substeps, a.x_, a.u, a.xR1, a.obs, a.dist_wp, a.dist_path, a.dist_lower, a.t_path, a.link_path, nullptr);
     if (rc) return rc;
     CFS_HIPCHK(hipStreamSynchronize(nullptr));

@@ -2,8 +2,9 @@
 //
 // The contract is cfs_clear.hip's (time line, samples, first minimum, t_path, link_path, lower bound) with the distance of
 // cfs_dist_arm_mesh: same FK, the exact segment-triangle minimum over the hierarchy (cfs_mesh_dev.h), the near-zero surrogate of
-// dist_arm_surf_200i.m:22-24, first-minimum link.  A mesh does not move, so the bound's v_obs is 0: the distance from a segment to
-// a fixed closed set is 1-Lipschitz in the segment's end points, which is all the argument of DESIGN.md section 17 uses.
+// dist_arm_surf_200i.m:22-24, first-minimum link.  A static mesh does not move, so the bound's v_obs is 0: the distance from a segment
+// to a fixed closed set is 1-Lipschitz in the segment's end points, which is all the argument of DESIGN.md section 17 uses.  A mesh
+// with a pose per waypoint (cfs_clearance_mesh_motion_device) is measured through the POSED instantiations further down.
 //
 // MI355X mapping.  A sample costs nj * nmesh hierarchy traversals of unequal length -- three orders of
 // magnitude more than a line sample -- so a problem is spread over ceil(G / 64) workgroups instead of one, and the per-sample
@@ -35,7 +36,49 @@ constexpr int CM_SCAN = 256;
 // which samples a launch of the sample kernel covers
 enum { CM_ALL = 0, CM_WAYPOINTS = 1, CM_BETWEEN = 2 };
 
-template <bool BOUND>
+// Moving meshes (cfs_clearance_mesh_motion*).  Where mesh jm stands at sample g does not depend on the problem,
+// so the inverse transform of every (mesh, sample) is written once per (sub-steps, poses) by this kernel, one lane each, and the sample
+// kernel's POSED instantiations only apply it.  A waypoint sample (k = S), interval 0 and a held interval copy the 12 stored doubles
+// the linearisation reads (cfs_mesh.hip, mesh_link_ends): dist_wp is measured where get_con measures it, and constant poses give the
+// static audit's bits.  Otherwise, at s = k/S: R(s) = Rod(a, s*theta) R_{i-1}, c_w(s) on the straight line, and the row-major record
+// [R(s)' | c_j - R(s)'c_w(s)] maps a world point into the frame the mesh is stored in.
+__global__ __launch_bounds__(CM_THREADS) void cfs_clear_mesh_pose_kernel(int nmesh, int H, int S, const double *itv, const double *inv,
+                                                                         double *out_pose, double *out_v)
+{
+    const int G = H * S + 1, e = blockIdx.x * CM_THREADS + threadIdx.x;
+    if (e >= nmesh * G) return;
+    const int jm = e / G, g = e % G;
+    int i, k;
+    clear_sample_ik(g, S, i, k);
+    const double *q = itv + ((size_t)jm * H + i) * CLEAR_ITV;
+    double *o = out_pose + (size_t)e * 12;
+    if (g < H) out_v[(size_t)jm * H + g] = itv[((size_t)jm * H + g) * CLEAR_ITV + 23];
+    if (k == S || q[0] == 0.0) {                     // g = 0 is interval 0, which is held
+        const double *src = inv + ((size_t)jm * H + i) * 12;
+        for (int r = 0; r < 12; ++r) o[r] = src[r];
+        return;
+    }
+    const double s = (double)k / (double)S;
+    double sn, cs;
+    sincos(s * q[4], &sn, &cs);
+    const double ax = q[1], ay = q[2], az = q[3], c1 = 1.0 - cs;
+    const double Q[9] = {cs + c1 * ax * ax, c1 * ax * ay - sn * az, c1 * ax * az + sn * ay,       // Rodrigues: I + sin K + (1 - cos) K^2
+                         c1 * ay * ax + sn * az, cs + c1 * ay * ay, c1 * ay * az - sn * ax,
+                         c1 * az * ax - sn * ay, c1 * az * ay + sn * ax, cs + c1 * az * az};
+    double R[9], cw[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = Q[3 * r] * q[5 + c] + Q[3 * r + 1] * q[8 + c] + Q[3 * r + 2] * q[11 + c];
+        cw[r] = q[14 + r] + s * (q[17 + r] - q[14 + r]);
+    }
+    for (int r = 0; r < 3; ++r) {                    // row r of R': column r of R
+        o[4 * r] = R[r]; o[4 * r + 1] = R[3 + r]; o[4 * r + 2] = R[6 + r];
+        o[4 * r + 3] = q[20 + r] - (R[r] * cw[0] + R[3 + r] * cw[1] + R[6 + r] * cw[2]);
+    }
+}
+
+// POSED: the link ends go through table row (mesh, sample) before the query; the surrogate's closest point and the link's far end both
+// live in the mesh's frame.  The static instantiations keep the statements they always had.
+template <bool BOUND, bool POSED>
 __global__ __launch_bounds__(CM_THREADS) void cfs_clear_mesh_sample_kernel(ClearMeshParams C, int phase)
 {
     __shared__ int s_stack[MESH_STACK * CM_THREADS];
@@ -73,11 +116,23 @@ __global__ __launch_bounds__(CM_THREADS) void cfs_clear_mesh_sample_kernel(Clear
             const double cur = w_d[(size_t)jm * G];
             const int seed = seeded ? w_seed[kk * nmesh + jm] : -1;
             Best bq;
-            mesh_query<CM_THREADS, false>(C.meshes[jm], e6, e6 + 3, seed, s_stack + t, s_lbs + t, bq, nullptr,
+            double m6[POSED ? 6 : 1];
+            const double *a6 = e6;                   // the link's ends in the frame mesh jm is stored in
+            if constexpr (POSED) {
+                const double *T = C.pose + ((size_t)jm * G + g) * 12;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const double t0 = T[4 * r], t1 = T[4 * r + 1], t2 = T[4 * r + 2], t3 = T[4 * r + 3];
+                    m6[r] = t0 * e6[0] + t1 * e6[1] + t2 * e6[2] + t3;
+                    m6[3 + r] = t0 * e6[3] + t1 * e6[4] + t2 * e6[5] + t3;
+                }
+                a6 = m6;
+            }
+            mesh_query<CM_THREADS, false>(C.meshes[jm], a6, a6 + 3, seed, s_stack + t, s_lbs + t, bq, nullptr,
                                           BOUND ? fmax(cur, 0.0001) : INFINITY);
             if (seeding) w_seed[kk * nmesh + jm] = bq.tri;
             if (bq.tri < 0) continue;                // nothing closer than the bound: not the minimum
-            const double dis = with_surrogate(bq, e6);
+            const double dis = with_surrogate(bq, a6);
             if (dis < cur) {                         // first minimum wins
                 w_d[(size_t)jm * G] = dis; w_lk[(size_t)jm * G] = kk + 1; w_tri[(size_t)jm * G] = C.meshes[jm].orig[bq.tri];
             }
@@ -89,6 +144,8 @@ __global__ __launch_bounds__(CM_THREADS) void cfs_clear_mesh_sample_kernel(Clear
     if (g < G - 1) C.ws_L[(size_t)b * G + g] = clear_arm_speed(x, u, x1, C.rho, nj, S, C.dt, g);
 }
 
+// POSED: L of sub-interval g carries the surface speed of mesh jm in its interval g / S (0 where the mesh is held: L + 0 is L)
+template <bool POSED>
 __global__ __launch_bounds__(CM_SCAN) void cfs_clear_mesh_scan_kernel(ClearMeshParams C)
 {
     __shared__ double r_wp[CM_SCAN], r_path[CM_SCAN], r_low[CM_SCAN];
@@ -102,7 +159,11 @@ __global__ __launch_bounds__(CM_SCAN) void cfs_clear_mesh_scan_kernel(ClearMeshP
         const double d0 = d[g];
         if (d0 < a_path) { a_path = d0; a_g = g; }
         if (g > 0 && g % S == 0) a_wp = fmin(a_wp, d0);
-        if (g + 1 < G) a_low = fmin(a_low, (d0 + d[g + 1]) / 2.0 - L[g] * C.dt / (2.0 * (double)S));   // v_obs = 0
+        if constexpr (POSED) {
+            if (g + 1 < G) a_low = fmin(a_low, (d0 + d[g + 1]) / 2.0 - (L[g] + C.v_mesh[(size_t)jm * C.H + g / S]) * C.dt / (2.0 * (double)S));
+        } else {
+            if (g + 1 < G) a_low = fmin(a_low, (d0 + d[g + 1]) / 2.0 - L[g] * C.dt / (2.0 * (double)S));   // v_obs = 0
+        }
     }
     r_wp[t] = a_wp; r_path[t] = a_path; r_low[t] = a_low; r_g[t] = a_g;
     __syncthreads();
@@ -128,27 +189,71 @@ __global__ __launch_bounds__(CM_SCAN) void cfs_clear_mesh_scan_kernel(ClearMeshP
         for (int j = t; j < nline; j += CM_SCAN) C.tri_path[(size_t)b * C.nobs + j] = -1;
 }
 
-template <bool BOUND>
+template <bool BOUND, bool POSED>
 void launch_samples(const ClearMeshParams &p, int phase, int n, hipStream_t s)
 {
     if (n <= 0) return;
-    hipLaunchKernelGGL(cfs_clear_mesh_sample_kernel<BOUND>, dim3((n + CM_THREADS - 1) / CM_THREADS, p.B), dim3(CM_THREADS), 0, s, p, phase);
+    hipLaunchKernelGGL((cfs_clear_mesh_sample_kernel<BOUND, POSED>), dim3((n + CM_THREADS - 1) / CM_THREADS, p.B), dim3(CM_THREADS), 0, s, p, phase);
 }
 
-}  // namespace
-
-hipError_t launch_clearance_mesh(const ClearMeshParams &p, hipStream_t s)
+template <bool POSED>
+hipError_t launch_clearance_mesh_as(const ClearMeshParams &p, hipStream_t s)
 {
     const int G = p.H * p.S + 1;
     const bool bound = (p.opt & CLEAR_MESH_BOUND) != 0;
-    auto samples = [&](int phase, int n) { if (bound) launch_samples<true>(p, phase, n, s); else launch_samples<false>(p, phase, n, s); };
+    auto samples = [&](int phase, int n) { if (bound) launch_samples<true, POSED>(p, phase, n, s); else launch_samples<false, POSED>(p, phase, n, s); };
     if (p.opt & CLEAR_MESH_SEED) {
         samples(CM_WAYPOINTS, p.H + 1);
         samples(CM_BETWEEN, p.H * (p.S - 1));
     } else {
         samples(CM_ALL, G);
     }
-    hipLaunchKernelGGL(cfs_clear_mesh_scan_kernel, dim3(p.nmesh, p.B), dim3(CM_SCAN), 0, s, p);
+    hipLaunchKernelGGL(cfs_clear_mesh_scan_kernel<POSED>, dim3(p.nmesh, p.B), dim3(CM_SCAN), 0, s, p);
+    return hipGetLastError();
+}
+
+// the workspace of an audit with `substeps` sub-steps (grown by the first audit that needs more) and the launch, shared by the static
+// and the moving entry; pose / v_mesh: the pose table of a moving handle, null for static meshes
+int clearance_mesh_enqueue(cfs_problem *p, int B, int substeps, const ClearArrays &a, const double *pose, const double *v_mesh, hipStream_t s)
+{
+    const int nline = p->d.nobs - p->nmesh;
+    if (substeps > p->cm_S) {                        // grow the workspace (hipFree waits for whatever still reads the old one)
+        const size_t G = (size_t)p->d.H * substeps + 1, mb = (size_t)p->d.max_batch;
+        p->release_clear_mesh();
+        CFS_HIPCHK(p->cm_d.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm_L.alloc(mb * G));
+        CFS_HIPCHK(p->cm_lk.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm_tri.alloc(mb * G * p->nmesh));
+        CFS_HIPCHK(p->cm_seed.alloc(mb * (size_t)(p->d.H + 1) * p->d.njoint * p->nmesh));
+        CFS_HIPCHK(p->cm_rho.alloc(CFS_MAX_LINKS * CFS_MAX_LINKS));
+        CFS_HIPCHK(hipMemcpy(p->cm_rho.p, p->rho, sizeof p->rho, hipMemcpyHostToDevice));
+        p->cm_S = substeps;
+    }
+    if (nline > 0) CFS_HIPCHK(cfs_launch_clearance_lines(p, B, substeps, nline, a, s));   // the line columns: cfs_clearance's kernel
+    ClearMeshParams cm;
+    cm.rb = p->rb.p; cm.B = B; cm.H = p->d.H; cm.nj = p->d.njoint; cm.nobs = p->d.nobs; cm.nmesh = p->nmesh; cm.S = substeps;
+    cm.opt = ((p->dbg_mask & CFS_DBG_CLEAR_NO_BOUND) ? 0 : CLEAR_MESH_BOUND) | ((p->dbg_mask & CFS_DBG_CLEAR_SEED) ? CLEAR_MESH_SEED : 0);
+    cm.dt = p->d.robot.delta_t;
+    cm.meshes = p->meshes_d.p;
+    cm.x_ = a.x_; cm.u = a.u; cm.xR1 = a.xR1;
+    cm.dist_wp = a.dist_wp; cm.dist_path = a.dist_path; cm.dist_lower = a.dist_lower; cm.t_path = a.t_path;
+    cm.link_path = a.link_path; cm.tri_path = a.tri_path;
+    cm.ws_d = p->cm_d.p; cm.ws_L = p->cm_L.p; cm.ws_lk = p->cm_lk.p; cm.ws_tri = p->cm_tri.p; cm.ws_seed = p->cm_seed.p;
+    cm.rho = p->cm_rho.p;
+    cm.pose = pose; cm.v_mesh = v_mesh;
+    CFS_HIPCHK(launch_clearance_mesh(cm, s));
+    return CFS_SUCCESS;
+}
+
+}  // namespace
+
+hipError_t launch_clearance_mesh(const ClearMeshParams &p, hipStream_t s)
+{
+    return p.pose ? launch_clearance_mesh_as<true>(p, s) : launch_clearance_mesh_as<false>(p, s);
+}
+
+hipError_t launch_clear_mesh_poses(int nmesh, int H, int S, const double *itv, const double *inv, double *out_pose, double *out_v, hipStream_t s)
+{
+    const int n = nmesh * (H * S + 1);
+    hipLaunchKernelGGL(cfs_clear_mesh_pose_kernel, dim3((n + CM_THREADS - 1) / CM_THREADS), dim3(CM_THREADS), 0, s, nmesh, H, S, itv, inv, out_pose, out_v);
     return hipGetLastError();
 }
 
@@ -161,35 +266,43 @@ extern "C" int cfs_clearance_mesh_device(cfs_problem *p, int B, int substeps, co
     int rc = cfs_check_clearance(p, B, substeps, a, true);
     if (rc) return rc;
     CFS_HIPCHK(hipSetDevice(p->device));
-    const int nline = p->d.nobs - p->nmesh;
-    if (substeps > p->cm_S) {                        // grow the workspace (hipFree waits for whatever still reads the old one)
-        const size_t G = (size_t)p->d.H * substeps + 1, mb = (size_t)p->d.max_batch;
-        p->release_clear_mesh();
-        CFS_HIPCHK(p->cm_d.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm_L.alloc(mb * G));
-        CFS_HIPCHK(p->cm_lk.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm_tri.alloc(mb * G * p->nmesh));
-        CFS_HIPCHK(p->cm_seed.alloc(mb * (size_t)(p->d.H + 1) * p->d.njoint * p->nmesh));
-        CFS_HIPCHK(p->cm_rho.alloc(CFS_MAX_LINKS * CFS_MAX_LINKS));
-        CFS_HIPCHK(hipMemcpy(p->cm_rho.p, p->rho, sizeof p->rho, hipMemcpyHostToDevice));
-        p->cm_S = substeps;
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (nline > 0) CFS_HIPCHK(cfs_launch_clearance_lines(p, B, substeps, nline, a, s));   // the line columns: cfs_clearance's kernel
-    ClearMeshParams cm;
-    cm.rb = p->rb.p; cm.B = B; cm.H = p->d.H; cm.nj = p->d.njoint; cm.nobs = p->d.nobs; cm.nmesh = p->nmesh; cm.S = substeps;
-    cm.opt = ((p->dbg_mask & CFS_DBG_CLEAR_NO_BOUND) ? 0 : CLEAR_MESH_BOUND) | ((p->dbg_mask & CFS_DBG_CLEAR_SEED) ? CLEAR_MESH_SEED : 0);
-    cm.dt = p->d.robot.delta_t;
-    cm.meshes = p->meshes_d.p;
-    cm.x_ = x_; cm.u = u; cm.xR1 = xR1;
-    cm.dist_wp = dist_wp; cm.dist_path = dist_path; cm.dist_lower = dist_lower; cm.t_path = t_path;
-    cm.link_path = link_path; cm.tri_path = tri_path;
-    cm.ws_d = p->cm_d.p; cm.ws_L = p->cm_L.p; cm.ws_lk = p->cm_lk.p; cm.ws_tri = p->cm_tri.p; cm.ws_seed = p->cm_seed.p;
-    cm.rho = p->cm_rho.p;
-    CFS_HIPCHK(launch_clearance_mesh(cm, s));
-    return CFS_SUCCESS;
+    return clearance_mesh_enqueue(p, B, substeps, a, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int cfs_clearance_mesh(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1, const double *obs,
                                   double *dist_wp, double *dist_path, double *dist_lower, double *t_path, int *link_path, int *tri_path)
 {
     return cfs_clearance_host(p, B, substeps, ClearArrays{x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, tri_path}, true);
+}
+
+// ---- C ABI (include/cfs_hip.h, "clearance audit with moving meshes") -----------------------------------------------------------
+extern "C" int cfs_clearance_mesh_motion_device(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1,
+                                                const double *obs, double *dist_wp, double *dist_path, double *dist_lower, double *t_path,
+                                                int *link_path, int *tri_path, void *stream)
+{
+    const ClearArrays a{x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, tri_path};
+    int rc = cfs_check_clearance(p, B, substeps, a, true, true);
+    if (rc) return rc;
+    CFS_HIPCHK(hipSetDevice(p->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!p->mesh_pose.p) return clearance_mesh_enqueue(p, B, substeps, a, nullptr, nullptr, s);   // static meshes: the static path
+    if (substeps > p->cmm_cap) {                     // grow the table (hipFree waits for whatever still reads the old one)
+        p->cmm_pose.release(); p->cmm_v.release();
+        p->cmm_cap = 0; p->cmm_gen = -1;
+        CFS_HIPCHK(p->cmm_pose.alloc((size_t)p->nmesh * ((size_t)p->d.H * substeps + 1) * 12));
+        CFS_HIPCHK(p->cmm_v.alloc((size_t)p->nmesh * p->d.H));
+        p->cmm_cap = substeps;
+    }
+    if (p->cmm_S != substeps || p->cmm_gen != p->motion_gen) {   // the table of another S or of other poses: rebuild it, ahead of the audit on its stream
+        CFS_HIPCHK(launch_clear_mesh_poses(p->nmesh, p->d.H, substeps, p->mesh_itv.p, p->mesh_pose.p, p->cmm_pose.p, p->cmm_v.p, s));
+        p->cmm_S = substeps; p->cmm_gen = p->motion_gen;
+    }
+    return clearance_mesh_enqueue(p, B, substeps, a, p->cmm_pose.p, p->cmm_v.p, s);
+}
+
+extern "C" int cfs_clearance_mesh_motion(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1,
+                                         const double *obs, double *dist_wp, double *dist_path, double *dist_lower, double *t_path,
+                                         int *link_path, int *tri_path)
+{
+    return cfs_clearance_host(p, B, substeps, ClearArrays{x_, u, xR1, obs, dist_wp, dist_path, dist_lower, t_path, link_path, tri_path}, true, true);
 }

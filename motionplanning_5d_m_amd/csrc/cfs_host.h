@@ -144,8 +144,17 @@ struct ClearMeshParams {
     double *ws_d, *ws_L;                                 // B x nmesh x G per-sample distance; B x G arm's share of the Lipschitz bound
     int *ws_lk, *ws_tri, *ws_seed;                       // B x nmesh x G closest link / triangle; B x (H+1) x nj x nmesh waypoint winners
     const double *rho;                                   // device, CFS_MAX_LINKS^2 (cfs_clear_build_rho)
+    // moving meshes (cfs_clearance_mesh_motion*), both null for static meshes: the table launch_clear_mesh_poses writes
+    const double *pose;                                  // nmesh x G x 12: row-major [R' | c_j - R'c_w] of (mesh, sample), world -> stored frame
+    const double *v_mesh;                                // nmesh x H: bound of the surface speed of a mesh in an interval
 };
 hipError_t launch_clearance_mesh(const ClearMeshParams &p, hipStream_t s);
+// One record per (mesh, interval) of a handle with mesh motion, derived on the host in double (cfs_problem_set_mesh_motion):
+// [0] 1: the interval is interpolated, 0: the stored pose of its waypoint is held over it (interval 0, bitwise equal poses);
+// [1..3] axis a, [4] theta, [5..13] R_{i-1} row-major, [14..16] c_w(0), [17..19] c_w(1), [20..22] c_j, [23] v_mesh
+constexpr int CLEAR_ITV = 24;
+// writes the pose table of S sub-steps: out_pose nmesh x (H*S + 1) x 12, out_v nmesh x H; inv: the stored inverse poses, nmesh x H x 12
+hipError_t launch_clear_mesh_poses(int nmesh, int H, int S, const double *itv, const double *inv, double *out_pose, double *out_v, hipStream_t s);
 
 // ---- CHOMP_FANUC (cfs_chomp.hip) -----------------------------------------------------------------------
 struct ChompParams {

@@ -33,6 +33,13 @@ struct cfs_problem {
     DevBuf<double> cm_d, cm_L, cm_rho;
     DevBuf<int> cm_lk, cm_tri, cm_seed;
     int cm_S = 0;
+    // cfs_clearance_mesh_motion*: what cfs_problem_set_mesh_motion derives per (mesh, interval) (CLEAR_ITV doubles each), and the pose
+    // table of the last audit, kept per (sub-steps, motion generation): rebuilt only when either changes
+    DevBuf<double> mesh_itv, cmm_pose, cmm_v;
+    std::vector<DevMesh> meshes_h;        // host copy of meshes_d (the stored triangles give c_j and r_j)
+    std::vector<double> mesh_frame;       // nmesh x 4: (c_j, r_j), filled by the first cfs_problem_set_mesh_motion after set_meshes
+    int motion_gen = 0, cmm_S = 0, cmm_cap = 0, cmm_gen = -1;
+    int turn_mesh = -1, turn_wp = 0;      // first (mesh, waypoint) whose pose is more than a quarter turn from the one before; -1: none
     // developer / test switches (cfs_debug_*, include/cfs_hip.h): per handle, no process-wide state
     int dbg_mask = 0, dbg_warm_max = 0;
     double dbg_polish_tol = 1e-11;        // = the constraint scan's own feasibility tolerance
@@ -58,6 +65,12 @@ struct cfs_problem {
         cm_d.release(); cm_L.release(); cm_rho.release(); cm_lk.release(); cm_tri.release(); cm_seed.release();
         cm_S = 0;
     }
+    void release_mesh_motion()            // the handle's meshes are static again
+    {
+        mesh_pose.release(); mesh_itv.release(); cmm_pose.release(); cmm_v.release();
+        cmm_S = cmm_cap = 0; cmm_gen = -1; turn_mesh = -1;
+        ++motion_gen;
+    }
     void release_all()
     {
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
@@ -68,7 +81,7 @@ struct cfs_problem {
         F1.release(); F2.release(); Cq.release(); cost.release();
         lim.release(); maxin.release(); margin.release(); x0.release(); qu.release(); dist.release();
         grad.release(); Yg.release(); noise_row.release(); order.release(); okey.release(); order_user.release();
-        linkid.release(); pool_flag.release(); meshes_d.release(); mesh_pose.release(); st_cost.release(); st_done.release();
+        linkid.release(); pool_flag.release(); meshes_d.release(); release_mesh_motion(); st_cost.release(); st_done.release();
         m_ends.release(); m_base.release(); m_shift.release(); m_tri.release(); m_near.release(); m_upper.release();
         m_pd.release(); m_pnd.release(); m_pi.release(); release_clear_mesh();
         stamps.release(); trace.release(); u_log.release(); soft_viol.release(); soft_n.release();
@@ -91,9 +104,10 @@ struct ClearArrays {
     double *dist_wp, *dist_path, *dist_lower, *t_path;
     int *link_path, *tri_path;                           // tri_path: the mesh audit only
 };
-// what all four entries refuse, in one order; mesh: the handle must have meshes (otherwise: must have none) and tri_path is an output
-int cfs_check_clearance(const cfs_problem *p, int B, int substeps, const ClearArrays &a, bool mesh);
+// what all six entries refuse, in one order; mesh: the handle must have meshes (otherwise: must have none) and tri_path is an output;
+// motion (cfs_clearance_mesh_motion*, with mesh): mesh motion is admitted, unless two consecutive poses are over a quarter turn apart
+int cfs_check_clearance(const cfs_problem *p, int B, int substeps, const ClearArrays &a, bool mesh, bool motion = false);
 // cfs_clearance's kernel on the first nline obstacle rows and output columns of the handle
 hipError_t cfs_launch_clearance_lines(const cfs_problem *p, int B, int substeps, int nline, const ClearArrays &a, hipStream_t s);
-// the host-array entry of either audit: stages the arrays, calls the _device entry on the NULL stream, copies back
-int cfs_clearance_host(cfs_problem *p, int B, int substeps, const ClearArrays &h, bool mesh);
+// the host-array entry of every audit: stages the arrays, calls the _device entry on the NULL stream, copies back
+int cfs_clearance_host(cfs_problem *p, int B, int substeps, const ClearArrays &h, bool mesh, bool motion = false);

@@ -427,15 +427,17 @@ class CFSBatch:
         return out
 
     # ---- clearance audit between the waypoints, against line obstacles or with mesh obstacles -------------------------
-    def _audit(self, mesh, device, x_, u, xR1, obs, substeps, out=None, stream=None):
-        """the four audit entries: cfs_clearance[_mesh][_device].  The line audit takes the obs shape of the handle's obstacle
-        motion (_check_obs); the mesh audit is static, (B, nobs, 6), and never asks the handle."""
+    def _audit(self, mesh, device, x_, u, xR1, obs, substeps, out=None, stream=None, motion=False):
+        """the six audit entries: cfs_clearance[_mesh[_motion]][_device].  The line audit takes the obs shape of the handle's
+        obstacle motion (_check_obs); the mesh audits take (B, nobs, 6) and never ask the handle.  motion: the entry that admits
+        a handle with mesh motion (set_mesh_motion)."""
         S = _args.int_in(substeps, "substeps", 1, 64)
         if mesh and not getattr(self, "_meshes", None):
-            raise ValueError("clearance_mesh needs a handle with mesh obstacles (set_meshes): use clearance for line obstacles")
+            raise ValueError(f"clearance_mesh{'_motion' if motion else ''} needs a handle with mesh obstacles (set_meshes): "
+                             "use clearance for line obstacles")
         if not mesh and getattr(self, "_meshes", None):
             raise ValueError("the clearance audit measures line obstacles only: this handle has mesh obstacles")
-        if mesh and getattr(self, "_mesh_motion", False):
+        if mesh and not motion and getattr(self, "_mesh_motion", False):
             raise ValueError("clearance_mesh audits static meshes (its bound takes v_obs = 0): this handle has mesh motion")
         if device:
             B = x_.shape[0]
@@ -456,7 +458,7 @@ class CFSBatch:
         elif out is None:
             out = (self.alloc_clearance_mesh if mesh else self.alloc_clearance)(B, x_.device)
         args = [self._h, B, S, _ptr(x_), _ptr(u), _ptr(xR1), _ptr(obs)] + [_ptr(getattr(out, k)) for k in names]
-        entry = "cfs_clearance_mesh" if mesh else "cfs_clearance"
+        entry = ("cfs_clearance_mesh_motion" if motion else "cfs_clearance_mesh") if mesh else "cfs_clearance"
         if not device:
             _lib.check(getattr(self._lib, entry)(*args))
             out.short_by = (self.margin[None, :] - out.dist_path).max(axis=1)
@@ -510,6 +512,18 @@ class CFSBatch:
         """clearance_mesh() on torch CUDA tensors; enqueues on `stream` (default: torch's current stream) and returns without
         synchronising (cfs_clearance_mesh_device).  out: an alloc_clearance_mesh namespace to write into."""
         return self._audit(True, True, x_, u, xR1, obs, substeps, out, stream)
+
+    def clearance_mesh_motion(self, x_, u, xR1, obs, substeps=16):
+        """clearance_mesh() for a handle whose meshes move (set_mesh_motion; cfs_clearance_mesh_motion, include/cfs_hip.h): the
+        same namespace.  Between two waypoints each mesh turns about one axis at a constant rate while the centre of its
+        bounding box travels a straight line, and dist_lower carries the mesh's surface speed; a handle with static meshes gives
+        clearance_mesh's results bit for bit."""
+        return self._audit(True, False, x_, u, xR1, obs, substeps, motion=True)
+
+    def clearance_mesh_motion_device(self, x_, u, xR1, obs, substeps=16, out=None, stream=None):
+        """clearance_mesh_motion() on torch CUDA tensors; enqueues on `stream` (default: torch's current stream) and returns
+        without synchronising (cfs_clearance_mesh_motion_device).  out: an alloc_clearance_mesh namespace to write into."""
+        return self._audit(True, True, x_, u, xR1, obs, substeps, out, stream, motion=True)
 
     def _margin_on(self, device):
         """the handle's margins as a tensor on `device` (uploaded once: no copy is enqueued by later audits)"""
@@ -767,13 +781,15 @@ class _SolverBase:
     MARGIN_KEY = "epsilon"
 
     def __init__(self, obs, sys_info, ROBOT="M16iB", device=None, jacobian="fd_literal", on_infeasible="stop", soft_weight=None,
-                 joint_limits=None, audit=None, audit_mesh=None):
+                 joint_limits=None, audit=None, audit_mesh=None, audit_mesh_motion=None):
         """jacobian: "fd_literal" (num_jac.m, the default) | "analytic" (CFSBatch).
         audit: None (the default: results are exactly those without the argument) | an integer S in 1..64: after optimizer(),
         .clearance holds CFSBatch.clearance of the returned trajectory with S sub-steps per interval (its one problem: arrays of
         shape (nobs,), short_by a float); line obstacles only.
         audit_mesh: the same for an obs cell with at least one mesh: None (the default) | S in 1..64: after optimizer(),
         .clearance_mesh holds CFSBatch.clearance_mesh of the returned trajectory (all columns, lines first, with tri_path).
+        audit_mesh_motion: None (the default) | S in 1..64: after optimizer(), .clearance_mesh_motion holds
+        CFSBatch.clearance_mesh_motion of the returned trajectory; the one audit that takes mesh entries with a "pose".
         joint_limits: None (the default) | "robot" | an (njoint, 2) array of [lo, hi] (CFSBatch); get_con then has the position rows.
         on_infeasible: "stop" (the default) | "soften" with soft_weight= (CFSBatch); after optimizer(), viol_all and n_soft.
         obs{j}["l"] may be 3x2xH (shape (3, 2, H): the obstacle's axis at waypoints 1..H); any such entry makes the handle
@@ -792,6 +808,10 @@ class _SolverBase:
         if self.audit_mesh is not None and not meshes:
             raise ValueError("audit_mesh= needs an obs cell with at least one mesh obstacle: audit= measures line obstacles")
         self.clearance_mesh = None
+        self.audit_mesh_motion = None if audit_mesh_motion is None else _args.int_in(audit_mesh_motion, "audit_mesh_motion", 1, 64)
+        if self.audit_mesh_motion is not None and not meshes:
+            raise ValueError("audit_mesh_motion= needs an obs cell with at least one mesh obstacle: audit= measures line obstacles")
+        self.clearance_mesh_motion = None
         self._mesh_poses = obs_mesh_poses(obs, sys_info.H)   # checked before anything touches the device
         if self.audit_mesh is not None and self._mesh_poses is not None:
             raise ValueError("audit_mesh= audits static meshes: a mesh entry of the obs cell carries a pose")
@@ -849,6 +869,8 @@ class _SolverBase:
             self.clearance = row0(self._batch.clearance(r.x_, r.u, xR1, obs, substeps=self.audit))
         if self.audit_mesh is not None:
             self.clearance_mesh = row0(self._batch.clearance_mesh(r.x_, r.u, xR1, obs, substeps=self.audit_mesh))
+        if self.audit_mesh_motion is not None:
+            self.clearance_mesh_motion = row0(self._batch.clearance_mesh_motion(r.x_, r.u, xR1, obs, substeps=self.audit_mesh_motion))
         if self.status == 0:
             print(f"Converged at step{self.iter_O}")  # EVAL.m:66
         elif self.status == 1:
@@ -871,7 +893,9 @@ class CHOMP_FANUC:
     """Lib/CHOMP_FANUC.m -- ``CHOMP_FANUC(obs_, sys_info, uref, ROBOT).optimizer()``.  ``obs_`` is the reference's cell:
     ``obs_[0] = dict(num_obs=n)`` followed by the n obstacles (``l``, ``D``, ``epsilon``) (M16iB/CHOMP.m:26-29)."""
 
-    def __init__(self, obs, sys_info, uu, ROBOT="M16iB", device=None, audit=None, audit_mesh=None):
+    def __init__(self, obs, sys_info, uu, ROBOT="M16iB", device=None, audit=None, audit_mesh=None, audit_mesh_motion=None):
+        if audit_mesh_motion is not None:
+            raise ValueError("CHOMP_FANUC has no clearance audit: audit_mesh_motion= is an option of CFS_FANUC and PSGCFS_FANUC")
         if audit is not None:
             raise ValueError("CHOMP_FANUC has no clearance audit: audit= is an option of CFS_FANUC and PSGCFS_FANUC")
         if audit_mesh is not None:
