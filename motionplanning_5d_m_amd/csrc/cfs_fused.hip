@@ -79,6 +79,11 @@ __device__ __forceinline__ int rcp_div(int e, unsigned rc) { return (int)__umulh
 // dependent multiplies behind, was measured 1-1.6 % slower with it and keeps the divisions: its objects
 // are compiled from the statements they had before.
 #define CFS_RCP_DECODE (CFS_WG_PER_CU > 1)
+// The tier of the identity Hessian (w2s, the one with CFS_P_LDS) places the work that rides on the linearisation (prep(1..3) of the
+// outer loop) on the wavefronts a phase leaves with a pass less (FusedParams::ride).  The other two keep every prep on wavefronts
+// 0, 1, 2 and are compiled from the statements they had before: w2m (CFS) was measured 0.7 % slower with it in every block
+// (DESIGN.md section 4.1), the whole-CU tier was not timed on its own.
+#define CFS_RIDE_IDLE (CFS_WG_PER_CU > 1 && CFS_P_LDS)
 
 // ---- DPP helpers (gfx9 row shifts / row broadcasts) ---------------------------------------------
 template <int CTRL, int RM>
@@ -212,13 +217,15 @@ __device__ __forceinline__ double half_scan_incl(double v)
 // (Bvel v, Bpos v) of the vector in buf[0..HN) -> buf[HN..2HN), buf[2HN..3HN).  Lane i of a wavefront
 // owns waypoint i (H <= 64); the workgroup's wavefronts share the joints.  Two DPP prefix sums per joint:
 // Bvel v = dt*cumsum(v), Bpos v = dt*cumsum(Bvel v) - dt/2 * Bvel v  (double integrator, robotproperty2.m:136-139).
+// `first`: the wavefronts from this one on share the joints (H <= 32; riding work of the linearisation, CFS_RIDE_IDLE below).
 template <int NJ>
-__device__ __forceinline__ void roll_lds(double *buf, int H, double dt, int tid)
+__device__ __forceinline__ void roll_lds(double *buf, int H, double dt, int tid, int first = 0)
 {
     const int HN = H * NJ;
     if (H <= 32) {                              // two joints per wavefront, one per half: all NJ <= 6 joints in one round of 3 wavefronts
         const int lane = tid & 31;
-        for (int c = tid >> 5; c < NJ; c += 2 * (FT / 64)) {
+        const int c0 = (tid >> 5) - 2 * first;  // (negative in a wavefront before `first`: no joint in any round)
+        for (int c = c0 < 0 ? NJ : c0; c < NJ; c += 2 * (FT / 64 - first)) {
             const double x = lane < H ? buf[lane * NJ + c] : 0.0;
             const double sv = dt * half_scan_incl(x);
             const double sp = dt * half_scan_incl(sv) - (0.5 * dt) * sv;
@@ -800,15 +807,28 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
         } else if (P.piece == 0) cost_old = cost_new;       // CFS_FANUC.m:67
         const int noise_row_now = noise_row;
         if (P.piece == 0 && P.mode == CFS_MODE_PSGCFS && !skip) ++noise_row;
-        auto prep = [&](int ph) {
+        // `riding`: prep(1..3) run on the wavefronts that the phase they ride on leaves with a pass less (FusedParams::ride, chosen by
+        // launch_fused_tier from the phase's item count): wavefronts `first` .. 3 share the joints of a rollout and the elements of the
+        // start vector.  Same statements per joint and per element wherever they run.  The field is read where it is used, behind an
+        // empty asm, so that nothing derived from it is carried in registers around the outer loop.
+        auto prep = [&](int ph, bool riding = false) {
             if (P.piece == 1) return;
+            int first = 0;
+#if CFS_RIDE_IDLE
+            if (riding) {
+                unsigned rd = P.ride;
+                asm volatile("" : "+s"(rd));
+                first = (int)((rd >> (4 * ph)) & 15u);
+            }
+#endif
             if (ph == 0) { for (int k = tid; k < HN; k += FT) xs[k] = s_u[k]; }
-            else if (ph == 1) roll_lds<NJ>(xs, H, dt, tid);
+            else if (ph == 1) roll_lds<NJ>(xs, H, dt, tid, first);
             else if (ph == 2) {
                 const bool psg = P.piece == 0 && P.mode == CFS_MODE_PSGCFS;
                 const double sc = (double)iter_O * (double)iter_O + 1.0;
                 const bool have = P.noise != nullptr && noise_row_now < P.noise_rows;
-                for (int k = tid; k < HN; k += FT) {
+                const int k0 = tid - 64 * first;            // (negative in a wavefront before `first`: no element)
+                for (int k = k0 < 0 ? HN : k0; k < HN; k += FT - 64 * first) {
                     s_up[k] = xs[2 * HN + k];
                     double v;
                     if (psg && skip) v = s_u[k];            // no step: x_ is the rollout of the unchanged u
@@ -818,7 +838,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     } else v = P.x0[(size_t)b * nn + k];    // CFS: -H^{-1} ff; cfs_qp: the caller's start point
                     xs[k] = v;
                 }
-            } else roll_lds<NJ>(xs, H, dt, tid);
+            } else roll_lds<NJ>(xs, H, dt, tid, first);
         };
         bool prepped = false;
         // =========================================================================================
@@ -860,7 +880,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     }
                     __syncthreads();
                     for (int wi = tid; wi < Wc; wi += FT) arm_chain(rb, NJ, s_sc + wi * NJ * 2, s_en + wi * NJ * 6, s_tw + wi * NJ * 6);
-                    if (w0 == 0) prep(1);
+                    if (w0 == 0) prep(1, true);
                     __syncthreads();
                     STAMP(10);                                  // 10: sincos + the chain
                     for (int e = tid; e < NJ * Wc * nseg; e += FT) {
@@ -872,7 +892,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         if constexpr (MOVE) s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, S_OBW + (wi * nseg + j) * 6);
                         else s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NJ + k0) * 6, s_ob + j * 6);
                     }
-                    if (w0 == 0) prep(2);
+                    if (w0 == 0) prep(2, true);
                     __syncthreads();
                     STAMP(0);                                   // 0: base distances
                     for (int e = tid; e < Wc * nseg; e += FT) {
@@ -896,7 +916,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                             else for (int m = 0; m < NJ; ++m) g[m] = 0.0;
                         }
                     }
-                    if (w0 == 0) { prep(3); prepped = true; }
+                    if (w0 == 0) { prep(3, true); prepped = true; }
                     // (the next tile's first phase only writes its sin / cos table, which this one no longer reads; MOVE: and its
                     // obstacle rows, which the tangent sweeps above still read)
                     if constexpr (MOVE) __syncthreads();
@@ -960,7 +980,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                             }
                         }
                     }
-                    if (w0 == 0) prep(1);
+                    if (w0 == 0) prep(1, true);
                     __syncthreads();
                     STAMP(10);                                  // 10: sincos + link transforms
                     // Base-pose distance of every link (dist_arm_3D_200i_2.m:16-26), link index slow so the point /
@@ -975,7 +995,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         else s_bd[(wi * NJ + k0) * nseg + j] = seg_seg_dist(s_en + (wi * NVT + kvoff(k0 + 1)) * 6, s_ob + j * 6);
                     }
                     if (tid < NJ) s_cnt[tid] = 0;
-                    if (w0 == 0) prep(2);
+                    if (w0 == 0) prep(2, true);
                     __syncthreads();
                     // num_jac only needs min over the links at 2nj shifted poses.  A link whose base distance exceeds
                     // max(min, 1e-4) by prune_tol can neither become the minimum nor reach the near-zero surrogate at any
@@ -999,7 +1019,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
 #pragma unroll
                         for (int ev = 1; ev < NE; ++ev) s_dv[e * NE + ev] = INFINITY;
                     }
-                    if (w0 == 0) { prep(3); prepped = true; }
+                    if (w0 == 0) { prep(3, true); prepped = true; }
                     __syncthreads();
                     STAMP(0);                                   // 0: base distances, candidate lists (+ the minima / differences below)
                     {
@@ -1982,6 +2002,20 @@ hipError_t launch_fused_tier(int nj, FusedParams p, hipStream_t s, const SoftPar
             if ((unsigned long long)nj * w * nseg * ((unsigned long long)w * nseg) >= 0x80000000ull) return hipErrorInvalidValue;
             p.rc_nseg = rcp31(nseg); p.rc_tile = rcp31(nseg * w); p.rc_last = rcp31(nseg * wl);
         }
+        // Where prep(1..3) ride (tile 0, the only one that carries them).  The phase's threads stride over n items, so wavefront v runs
+        // ceil((n - 64 v) / FT) passes, never more than the one before it: the wavefronts with a pass less than wavefront 0 are v .. 3
+        // for the first such v, and the riding work goes there.  0 = every wavefront, the mapping of a prep phase of its own: no
+        // wavefront is free, or H > 32 (one joint per wavefront in roll_lds), or nothing to ride on.  Filled for every tier; only the
+        // kernels compiled with CFS_RIDE_IDLE (the w2s objects) read it.
+        auto first_free = [](int n) {
+            const int p0 = (n + FT - 1) / FT;
+            for (int v = 1; v < FT / 64; ++v)
+                if ((n > 64 * v ? (n - 64 * v + FT - 1) / FT : 0) < p0) return (unsigned)v;
+            return 0u;
+        };
+        p.ride = 0;
+        if (nseg > 0 && p.H <= 32)
+            p.ride = first_free(JAC ? w : w * (2 * nj + 1)) << 4 | first_free(nj * w * nseg) << 8 | first_free(w * nseg) << 12;
     }
     size_t need = std::max((size_t)L.total_fixed + (size_t)qy * nn, (size_t)L.lin + (size_t)w * q.per_wp);
     if constexpr (LIM) {
