@@ -28,11 +28,11 @@
 //                                    the xor-shuffle argmin, then the winner's clearance: the (row, mesh, link) triples strided over
 //                                    the lanes, one exact unbounded mesh_query each, a wave min with the line clearance of the rows.
 // cfs_cart_kernel is untouched: at 256 VGPR + 253 AGPR for NJ = 5 a hierarchy walk inside its pass would put the iteration in scratch.
+// What the kernels here share with cfs_ik.hip is called, not restated: ik_stage, ik_converged, ik_cost, ik_argmin
+// (cfs_ik_dev.h), mesh_hit, mesh_pair_clearance, mesh_wave_min (cfs_mesh_hit_dev.h) and the descriptor checks of cfs_tool_host.h.
 #include "cfs_mesh_hit_dev.h"
 #include "cfs_ik_dev.h"
-#include "cfs_host.h"
-#include <cmath>
-#include <cstring>
+#include "cfs_tool_host.h"
 
 namespace {
 
@@ -66,14 +66,8 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartPar
     __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
     __shared__ double s_obs[CFS_MAX_OBS * 6];
     __shared__ double s_D[CFS_MAX_OBS];
-    {
-        const double *src = reinterpret_cast<const double *>(&P.rb);
-        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += WV * CART_WAVES) s_rb[e] = src[e];
-        for (int e = threadIdx.x; e < P.nobs * 6; e += WV * CART_WAVES) s_obs[e] = P.obs[e];
-        for (int e = threadIdx.x; e < P.nobs; e += WV * CART_WAVES) s_D[e] = P.D[e];
-    }
-    __syncthreads();                                          // the only block barrier: whole waves may leave after it
-    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    // the only block barrier is in there: whole waves may leave after it
+    const DevRobot *rb = ik_stage<WV * CART_WAVES>(P.rb, s_rb, P.nobs, P.obs, P.D, s_obs, s_D);
     const int lane = threadIdx.x % WV, t = blockIdx.x * CART_WAVES + threadIdx.x / WV;
     if (t >= P.T) return;
     const bool use_axis = P.use_axis != 0;
@@ -118,9 +112,8 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartPar
     for (;;) {
         // ---- head of the pass: a step whose point is reached is booked and the next one set up -----------------------------
         if (st < 0) {
-            const double ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
             if (!(F < INFINITY)) st = 3;                                                        // step 1
-            else if (ep <= P.tol_pos && (!use_axis || ea <= P.tol_axis)) {                      // step 2: theta_k = th
+            else if (ik_converged(r, use_axis, P.tol_pos, P.tol_axis)) {                        // step 2: theta_k = th
                 if (k > 0) {
                     double s = 0.0;
 #pragma unroll
@@ -174,12 +167,10 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartPar
         if (__ballot(st < 0) == 0ull) break;
         // ---- one iteration of the current step (a step set up above is tested before it iterates) ---------------------------
         if (st < 0) {
-            const double ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
-            const bool conv = ep <= P.tol_pos && (!use_axis || ea <= P.tol_axis);
             if (!(F < INFINITY)) st = 3;                                                        // step 1
-            else if (conv) {}                                                                   // step 2: the next pass books it
+            else if (ik_converged(r, use_axis, P.tol_pos, P.tol_axis)) {}                       // step 2: the next pass books it
             else if (it >= P.max_iter) st = 1;                                                  // step 3
-            else {
+            else {                                                                              // cfs_ik_kernel's steps 4-8, statement for statement
                 double delta[NJ], trial[NJ];
                 if (!ik_solve_step<NJ>(A, g, lam, delta)) st = 3;                               // step 4
                 else {
@@ -206,8 +197,7 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartPar
                     } else {
                         lam = lam * 10.0 < IK_LAMBDA_MAX ? lam * 10.0 : IK_LAMBDA_MAX;
                     }
-                    ++it;                                                                       // step 8
-                    ++itsum;
+                    ++it; ++itsum;                                                              // step 8
                 }
             }
         }
@@ -217,12 +207,7 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartPar
     const double nan = __builtin_nan("");
     double cost = INFINITY;
     if (st == 0) {
-        double s = 0.0;
-#pragma unroll
-        for (int c = 0; c < NJ; ++c) {                        // w*(d*d), summed in joint order, no FMA: the contract's cost to the last bit
-            const double dlt = P.start[row * NJ + c] - P.theta_ref[(size_t)t * NJ + c];
-            s = __dadd_rn(s, __dmul_rn(P.w[c], __dmul_rn(dlt, dlt)));
-        }
+        const double s = ik_cost<NJ>(P.w, P.start + row * NJ, P.theta_ref + (size_t)t * NJ);
         if (s < INFINITY) cost = s; else st = 3;
     }
     if (active) {
@@ -239,16 +224,8 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartPar
     }
     const int n_ok = __popcll(__ballot(st == 0));
     const bool any_start = __ballot(st != 5) != 0ull;
-    double bc = cost;
-    int bl = lane, md = done;
-#pragma unroll
-    for (int m = 1; m < WV; m <<= 1) {
-        const double oc = __shfl_xor(bc, m, WV);
-        const int ol = __shfl_xor(bl, m, WV);
-        const int od = __shfl_xor(md, m, WV);
-        if (oc < bc || (oc == bc && ol < bl)) { bc = oc; bl = ol; }
-        if (od > md) md = od;
-    }
+    int md = done;
+    const int bl = ik_argmin<true>(cost, lane, &md);
     const bool ok = n_ok > 0;
     if (ok ? lane == bl : lane == 0) {
 #pragma unroll
@@ -287,11 +264,9 @@ hipError_t launch_cart(int nj, const CartParams &p, hipStream_t s)
 // then variant B's frontier (RRT_FRONTIER_CAP pairs + as many nodes = 4 KB)
 constexpr int CART_STACK_WORDS = 2 * MESH_STACK * WV, CART_FRONTIER_WORDS = 2 * RRT_FRONTIER_CAP;
 
-// the mesh table of a cfs_cart_path_mesh* call: RRT's (thresholds, frontier capacity) and the margins for the winner's clearance
 struct CartMeshArgs {
     CartParams P;
-    RrtMeshArgs MA;
-    double D[CFS_MAX_OBS];
+    ToolMeshArgs M;                                           // the mesh table of a cfs_cart_path_mesh* call
 };
 
 // poses of variant B whose frontier overflowed and that variant A decided (cfs_debug_cart_frontier_overflows): one vector atomic by
@@ -306,19 +281,14 @@ __global__ __launch_bounds__(WV) void cfs_cart_mesh_kernel(const CartMeshArgs A_
     __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
     __shared__ double s_ends[NJ * 6];                         // the pose's link ends: wave-uniform, so they need no registers
     extern __shared__ __attribute__((aligned(16))) int s_mesh[];
-    {
-        const double *src = reinterpret_cast<const double *>(&P.rb);
-        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += WV) s_rb[e] = src[e];
-    }
-    __syncthreads();
-    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    const DevRobot *rb = ik_stage<WV>(P.rb, s_rb);
     const int lane = threadIdx.x;
     const size_t row = blockIdx.x;                            // t * R + r; the grid is exactly T * R
     const size_t prow = row * (size_t)(P.K + 1);
     int *s_stack = s_mesh;
     float *s_lbs = reinterpret_cast<float *>(s_stack + MESH_STACK * WV);
-    [[maybe_unused]] int *s_fpair = s_mesh + CART_STACK_WORDS, *s_fnode = s_fpair + RRT_FRONTIER_CAP;
-    const RrtMeshArgs &MA = A_.MA;
+    int *s_fpair = s_mesh + CART_STACK_WORDS, *s_fnode = s_fpair + RRT_FRONTIER_CAP;
+    const RrtMeshArgs &MA = A_.M.MA;
 
     for (int k = 0; k <= P.K; ++k) {
         double th[NJ];
@@ -327,15 +297,7 @@ __global__ __launch_bounds__(WV) void cfs_cart_mesh_kernel(const CartMeshArgs A_
         for (int c = 0; c < NJ; ++c) th[c] = P.cand_path[(prow + k) * NJ + c];     // one address for the wave
         if (th[0] != th[0]) return;                           // the accepted rows are a prefix: nothing after the first NaN row
         ik_clearance<NJ, true>(rb, th, 0, nullptr, nullptr, ends);                 // every lane stores the same values and reads its own
-        bool hit;
-        if constexpr (MESH == RRT_MESH_PER_LANE) {
-            hit = mesh_hit_per_lane<NJ>(MA, ends, lane, s_stack, s_lbs);
-        } else {
-            const int h = mesh_hit_wave<NJ>(MA, ends, lane, s_fpair, s_fnode);
-            if (h < 0 && lane == 0) atomicAdd(&g_cart_frontier_overflows, 1ull);
-            hit = h < 0 ? mesh_hit_per_lane<NJ>(MA, ends, lane, s_stack, s_lbs) : h != 0;
-        }
-        if (!hit) continue;
+        if (!mesh_hit<NJ, MESH>(MA, ends, lane, s_stack, s_lbs, s_fpair, s_fnode, &g_cart_frontier_overflows)) continue;
         // row k is the first mesh-rejected row: state 2, as for a line collision at step k
         if (lane == 0) {
             if (P.cand_status) P.cand_status[row] = 2;
@@ -359,14 +321,7 @@ __global__ __launch_bounds__(WV) void cfs_cart_select_kernel(const CartMeshArgs 
     __shared__ double s_obs[CFS_MAX_OBS * 6];
     __shared__ double s_D[CFS_MAX_OBS];
     extern __shared__ __attribute__((aligned(16))) int s_mesh[];
-    {
-        const double *src = reinterpret_cast<const double *>(&P.rb);
-        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += WV) s_rb[e] = src[e];
-        for (int e = threadIdx.x; e < P.nobs * 6; e += WV) s_obs[e] = P.obs[e];
-        for (int e = threadIdx.x; e < P.nobs; e += WV) s_D[e] = P.D[e];
-    }
-    __syncthreads();
-    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    const DevRobot *rb = ik_stage<WV>(P.rb, s_rb, P.nobs, P.obs, P.D, s_obs, s_D);
     const int lane = threadIdx.x, t = blockIdx.x;
     const bool active = lane < P.R;
     const size_t row = (size_t)t * P.R + (active ? lane : 0);
@@ -392,28 +347,15 @@ __global__ __launch_bounds__(WV) void cfs_cart_select_kernel(const CartMeshArgs 
             }
         }
         if (nrow == P.K + 1) {
-            double s = 0.0;
-#pragma unroll
-            for (int c = 0; c < NJ; ++c) {                    // cfs_cart_kernel's chain: w*(d*d), summed in joint order, no FMA
-                const double dlt = P.start[row * NJ + c] - P.theta_ref[(size_t)t * NJ + c];
-                s = __dadd_rn(s, __dmul_rn(P.w[c], __dmul_rn(dlt, dlt)));
-            }
+            const double s = ik_cost<NJ>(P.w, P.start + row * NJ, P.theta_ref + (size_t)t * NJ);      // cfs_cart_kernel's cost
             if (s < INFINITY) cost = s;
         }
     }
     const bool good = cost < INFINITY;
     const int n_ok = __popcll(__ballot(good));
     const bool any_start = __ballot(has_start) != 0ull;
-    double bc = cost;
-    int bl = lane, md = nrow > 1 ? nrow - 1 : 0;
-#pragma unroll
-    for (int m = 1; m < WV; m <<= 1) {
-        const double oc = __shfl_xor(bc, m, WV);
-        const int ol = __shfl_xor(bl, m, WV);
-        const int od = __shfl_xor(md, m, WV);
-        if (oc < bc || (oc == bc && ol < bl)) { bc = oc; bl = ol; }
-        if (od > md) md = od;
-    }
+    int md = nrow > 1 ? nrow - 1 : 0;
+    const int bl = ik_argmin<true>(cost, lane, &md);
     const bool ok = n_ok > 0;
     const size_t n = (size_t)(P.K + 1) * NJ;
     const double *src = P.cand_path + ((size_t)t * P.R + (ok ? bl : 0)) * n;
@@ -424,27 +366,19 @@ __global__ __launch_bounds__(WV) void cfs_cart_select_kernel(const CartMeshArgs 
     if (ok && P.clearance) {
         int *s_stack = s_mesh;
         float *s_lbs = reinterpret_cast<float *>(s_stack + MESH_STACK * WV);
-        const RrtMeshArgs &MA = A_.MA;
+        const RrtMeshArgs &MA = A_.M.MA;
         const int per = MA.nmesh * NJ, ntrip = (P.K + 1) * per;
         for (int q = lane; q < ntrip; q += WV) {
-            const int k = q / per, pr = q - k * per, j = pr / NJ, l = pr - j * NJ;
-            double th[NJ], ends[NJ * 6], a6[6];
+            const int k = q / per, pr = q - k * per;
+            double th[NJ], ends[NJ * 6];
 #pragma unroll
             for (int c = 0; c < NJ; ++c) th[c] = src[(size_t)k * NJ + c];
             const double cl = ik_clearance<NJ, true>(rb, th, pr == 0 ? P.nobs : 0, s_obs, s_D, ends);
             if (cl < mm) mm = cl;
-            pick_link<NJ>(ends, l, a6);
-            const DevMesh m{MA.m[j].nodes, MA.m[j].tri, nullptr, 0, MA.m[j].nt, nullptr, nullptr, 0, 0};
-            Best b;
-            mesh_query<WV, false>(m, a6, a6 + 3, -1, s_stack + lane, s_lbs + lane, b, nullptr);
-            const double v = b.d - A_.D[j];
+            const double v = mesh_pair_clearance<NJ>(MA, A_.M.D, ends, pr, s_stack + lane, s_lbs + lane);
             if (v < mm) mm = v;
         }
-#pragma unroll
-        for (int m = 1; m < WV; m <<= 1) {
-            const double om = __shfl_xor(mm, m, WV);
-            if (om < mm) mm = om;
-        }
+        mm = mesh_wave_min(mm);
     }
     if (lane == 0) {
 #pragma unroll
@@ -482,51 +416,21 @@ hipError_t launch_cart_mesh(int nj, int variant, const CartMeshArgs &a, hipStrea
 }
 
 // ---- C ABI (include/cfs_hip.h, "Cartesian paths") --------------------------------------------------------------------------------
-bool finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-bool all_finite(const double *v, size_t n)
-{
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
-// everything of a call that is host memory in both entries; fills the by-value part of the kernel's parameter block
+// everything of a call that is host memory in both entries (cfs_tool_host.h); fills the by-value part of the kernel's parameter block
 int check_cart(const cfs_cart_desc *d, int T, const double *start, const double *target_pos, const double *target_axis, const double *theta_ref,
                const cfs_cart_out *out, CartParams &P)
 {
-    if (!d) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL descriptor");
-    int rc = cfs_check_robot(&d->robot, d->njoint);
+    int rc = check_tool_head(d);
     if (rc) return rc;
-    const int nj = d->njoint;
-    if (nj < 2) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", nj);
-    if (d->use_axis != 0 && d->use_axis != 1) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis must be 0 or 1, not %d", d->use_axis);
     if (d->candidates < 1 || d->candidates > WV) return cfs_fail(CFS_ERR_INVALID_ARG, "candidates %d outside 1..%d", d->candidates, WV);
     if (d->steps < 1 || d->steps > CART_MAX_STEPS) return cfs_fail(CFS_ERR_INVALID_ARG, "steps %d outside 1..%d", d->steps, CART_MAX_STEPS);
-    if (d->max_iter < 1 || d->max_iter > 1000) return cfs_fail(CFS_ERR_INVALID_ARG, "max_iter %d outside 1..1000", d->max_iter);
+    if ((rc = check_tool_max_iter(d->max_iter))) return rc;
     if (!(std::isfinite(d->max_joint_step) && d->max_joint_step > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "max_joint_step must be finite and > 0");
-    if (d->nobs < 0 || d->nobs > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d outside 0..%d", d->nobs, CFS_MAX_OBS);
-    if (d->nobs > 0 && (!d->obs || !d->D)) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be given");
-    if (!(std::isfinite(d->tol_pos) && d->tol_pos > 0.0 && std::isfinite(d->tol_axis) && d->tol_axis > 0.0))
-        return cfs_fail(CFS_ERR_INVALID_ARG, "tol_pos / tol_axis must be finite and > 0");
-    if (!finite3(d->tool) || !finite3(d->tool_axis)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool / tool_axis must be finite");
-    const double an = std::sqrt(d->tool_axis[0] * d->tool_axis[0] + d->tool_axis[1] * d->tool_axis[1] + d->tool_axis[2] * d->tool_axis[2]);
-    if (d->use_axis && !(an > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool_axis is zero");
-    if (!d->lo || !d->hi) return cfs_fail(CFS_ERR_INVALID_ARG, "lo / hi must be given");
-    for (int c = 0; c < nj; ++c) {
-        if (!std::isfinite(d->lo[c]) || !std::isfinite(d->hi[c]) || !(d->lo[c] < d->hi[c]))
-            return cfs_fail(CFS_ERR_INVALID_ARG, "joint %d: lo / hi must be finite with lo < hi", c);
-        if (d->weight && !(std::isfinite(d->weight[c]) && d->weight[c] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "weight[%d] must be finite and > 0", c);
-    }
-    if (T < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "at least one target is needed");
+    if ((rc = check_tool_fields(d, T))) return rc;
     if (!start || !target_pos || !theta_ref) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL start / target_pos / theta_ref");
-    if (d->use_axis && !target_axis) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis = 1 needs target_axis");
-    if (!out || !out->theta || !out->status) return cfs_fail(CFS_ERR_INVALID_ARG, "out, out->theta and out->status must be given");
-    memset(&P, 0, sizeof P);
-    cfs_build_dev_robot(d->robot, P.rb);
-    P.T = T; P.R = d->candidates; P.K = d->steps; P.nobs = d->nobs; P.use_axis = d->use_axis; P.max_iter = d->max_iter;
-    for (int q = 0; q < 3; ++q) { P.tool[q] = d->tool[q]; P.axis[q] = an > 0.0 ? d->tool_axis[q] / an : 0.0; }
-    for (int c = 0; c < nj; ++c) { P.lo[c] = d->lo[c]; P.hi[c] = d->hi[c]; P.w[c] = d->weight ? d->weight[c] : 1.0; }
-    P.tol_pos = d->tol_pos; P.tol_axis = d->tol_axis; P.max_joint_step = d->max_joint_step;
+    if ((rc = check_tool_io(d, target_axis, out))) return rc;
+    fill_tool_params(d, T, P);
+    P.R = d->candidates; P.K = d->steps; P.max_joint_step = d->max_joint_step;
     return CFS_SUCCESS;
 }
 
@@ -538,17 +442,6 @@ void cart_point(CartParams &P, const double *obs, const double *D, const double 
     P.theta = o->theta; P.status = o->status; P.path = o->path; P.selected = o->selected; P.n_ok = o->n_ok; P.n_done = o->n_done;
     P.clearance = o->clearance; P.cand_status = o->cand_status; P.cand_done = o->cand_done; P.cand_iter = o->cand_iter;
     P.cand_end = o->cand_end; P.cand_path = o->cand_path;
-}
-
-// the meshes of a cfs_cart_path_mesh* call
-struct CartMeshCall { int nmesh; const cfs_mesh *const *meshes; const double *D_mesh; int flags; };
-int check_cart_mesh(const cfs_cart_desc *d, const CartMeshCall &c, CartMeshArgs &a, int &variant)
-{
-    int rc = cfs_check_mesh_table(d->nobs, c.nmesh, c.meshes, c.D_mesh, c.flags, 1, CART_MESH_DEFAULT, a.MA, variant);
-    if (rc) return rc;
-    memset(a.D, 0, sizeof a.D);
-    for (int j = 0; j < c.nmesh; ++j) a.D[j] = c.D_mesh[j];
-    return CFS_SUCCESS;
 }
 
 // the trace, then (mc given) the mesh walk and the selection over it, all on stream s.  The trace's own selection would only be
@@ -563,7 +456,7 @@ hipError_t launch_cart_all(int nj, int variant, CartMeshArgs &a, bool mesh, hipS
 }
 
 // mc == nullptr: the line-only call
-int cart_device(const cfs_cart_desc *d, const CartMeshCall *mc, int T, const double *start, const int *start_state, const double *target_pos,
+int cart_device(const cfs_cart_desc *d, const MeshCall *mc, int T, const double *start, const int *start_state, const double *target_pos,
                 const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream)
 {
     static_assert(sizeof(CartParams) <= 4096, "the parameter block travels as a kernel argument");
@@ -573,7 +466,7 @@ int cart_device(const cfs_cart_desc *d, const CartMeshCall *mc, int T, const dou
     if (rc) return rc;
     int variant = RRT_MESH_NONE;
     if (mc) {
-        rc = check_cart_mesh(d, *mc, A, variant);
+        rc = check_mesh_call(d->nobs, *mc, CART_MESH_DEFAULT, A.M, variant);
         if (rc) return rc;
         if (!out->cand_path)
             return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_cart_path_mesh_device: out->cand_path must be given, the workspace between the launches (nothing is allocated here)");
@@ -587,7 +480,7 @@ int cart_device(const cfs_cart_desc *d, const CartMeshCall *mc, int T, const dou
     return CFS_SUCCESS;
 }
 
-int cart_host(const cfs_cart_desc *d, const CartMeshCall *mc, int T, const double *start, const int *start_state, const double *target_pos,
+int cart_host(const cfs_cart_desc *d, const MeshCall *mc, int T, const double *start, const int *start_state, const double *target_pos,
               const double *target_axis, const double *theta_ref, const cfs_cart_out *out)
 {
     CartMeshArgs A;
@@ -596,19 +489,12 @@ int cart_host(const cfs_cart_desc *d, const CartMeshCall *mc, int T, const doubl
     if (rc) return rc;
     int variant = RRT_MESH_NONE;
     if (mc) {   // refuse before anything is staged on the device
-        rc = check_cart_mesh(d, *mc, A, variant);
+        rc = check_mesh_call(d->nobs, *mc, CART_MESH_DEFAULT, A.M, variant);
         if (rc) return rc;
     }
     const size_t nj = d->njoint, R = d->candidates, K1 = (size_t)d->steps + 1, nobs = d->nobs, nT = T;
-    if (!all_finite(target_pos, nT * 3) || !all_finite(theta_ref, nT * nj)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_pos / theta_ref must be finite");
-    if (nobs && (!all_finite(d->obs, nobs * 6) || !all_finite(d->D, nobs))) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be finite");
-    if (d->use_axis) {
-        if (!all_finite(target_axis, nT * 3)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis must be finite");
-        for (int t = 0; t < T; ++t) {
-            const double *v = target_axis + (size_t)t * 3;
-            if (!(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis row %d is zero", t);
-        }
-    }
+    rc = check_tool_arrays(d, T, target_pos, target_axis, theta_ref);
+    if (rc) return rc;
     rc = cfs_use_device(cfs_current_device());
     if (rc) return rc;
     Stage st;
@@ -660,7 +546,7 @@ extern "C" int cfs_cart_path_mesh_device(const cfs_cart_desc *d, int nmesh, cons
                                          const double *start, const int *start_state, const double *target_pos, const double *target_axis,
                                          const double *theta_ref, const cfs_cart_out *out, void *stream)
 {
-    const CartMeshCall mc{nmesh, meshes, D_mesh, flags};
+    const MeshCall mc{nmesh, meshes, D_mesh, flags};
     return cart_device(d, &mc, T, start, start_state, target_pos, target_axis, theta_ref, out, stream);
 }
 
@@ -668,7 +554,7 @@ extern "C" int cfs_cart_path_mesh(const cfs_cart_desc *d, int nmesh, const cfs_m
                                   const double *start, const int *start_state, const double *target_pos, const double *target_axis,
                                   const double *theta_ref, const cfs_cart_out *out)
 {
-    const CartMeshCall mc{nmesh, meshes, D_mesh, flags};
+    const MeshCall mc{nmesh, meshes, D_mesh, flags};
     return cart_host(d, &mc, T, start, start_state, target_pos, target_axis, theta_ref, out);
 }
 

@@ -10,7 +10,9 @@
 // the robot, the obstacle rows and their margins are staged once per workgroup (4 waves = 4 targets) in LDS.  Restarts of one
 // target end at different iterations: a lane that has ended idles under the EXEC mask until a ballot says that none is running,
 // so every lane reaches the selection, a wave argmin on (cost, lane) by xor shuffles.  No atomics, no block barrier after the
-// staging, no host round trip.  Everything is fp64.
+// staging, no host round trip.  Everything is fp64.  The staging, the convergence test, the cost and the argmin are
+// cfs_ik_dev.h's (ik_stage, ik_converged, ik_cost, ik_argmin), the same functions cfs_cart.hip runs; the mesh decision and the winner's
+// mesh clearance are cfs_mesh_hit_dev.h's (mesh_hit, mesh_pair_clearance); the checks of the descriptor are cfs_tool_host.h's.
 //
 // Mesh obstacles (cfs_ik_solve_mesh*).  cfs_ik_kernel<NJ, MESH> with MESH != RRT_MESH_NONE puts the decision of
 // cfs_rrt_grow_mesh between the line test and the cost: a restart that converged and passed the lines takes state 2 when some
@@ -26,9 +28,7 @@
 // cfs_rrt_grow_mesh; the clearance agrees with cfs_dist_arm_mesh (the same functions under the same flags).
 #include "cfs_mesh_hit_dev.h"
 #include "cfs_ik_dev.h"
-#include "cfs_host.h"
-#include <cmath>
-#include <cstring>
+#include "cfs_tool_host.h"
 
 namespace {
 
@@ -54,12 +54,7 @@ struct IkParams {
     int *cand_status, *cand_iter;                             // T x R
 };
 
-// the mesh table of a cfs_ik_solve_mesh* call: RRT's (thresholds, frontier capacity) and the margins for the winner's clearance
-struct IkMeshArgs {
-    RrtMeshArgs MA;
-    double D[CFS_MAX_OBS];
-};
-template <int MESH> struct IkArgs { IkParams P; IkMeshArgs M; };
+template <int MESH> struct IkArgs { IkParams P; ToolMeshArgs M; };          // M: the mesh table of a cfs_ik_solve_mesh* call
 template <> struct IkArgs<RRT_MESH_NONE> { IkParams P; };
 
 // candidates of variant B whose frontier overflowed and that variant A decided (cfs_debug_ik_frontier_overflows): one vector atomic
@@ -92,14 +87,8 @@ __global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkArgs<MESH
     __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
     __shared__ double s_obs[CFS_MAX_OBS * 6];
     __shared__ double s_D[CFS_MAX_OBS];
-    {
-        const double *src = reinterpret_cast<const double *>(&P.rb);
-        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += WV * IK_WAVES) s_rb[e] = src[e];
-        for (int e = threadIdx.x; e < P.nobs * 6; e += WV * IK_WAVES) s_obs[e] = P.obs[e];
-        for (int e = threadIdx.x; e < P.nobs; e += WV * IK_WAVES) s_D[e] = P.D[e];
-    }
-    __syncthreads();                                          // the only block barrier: whole waves may leave after it
-    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    // the only block barrier is in there: whole waves may leave after it
+    const DevRobot *rb = ik_stage<WV * IK_WAVES>(P.rb, s_rb, P.nobs, P.obs, P.D, s_obs, s_D);
     const int lane = threadIdx.x % WV, t = blockIdx.x * IK_WAVES + threadIdx.x / WV;
     if (t >= P.T) return;
     const bool use_axis = P.use_axis != 0;
@@ -132,29 +121,29 @@ __global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkArgs<MESH
     }
     for (;;) {
         if (st < 0) {
-            const double ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
             if (!(F < INFINITY)) st = 3;                                                        // step 1
-            else if (ep <= P.tol_pos && (!use_axis || ea <= P.tol_axis)) st = 0;                // step 2
+            else if (ik_converged(r, use_axis, P.tol_pos, P.tol_axis)) st = 0;                  // step 2
             else if (it >= P.max_iter) st = 1;                                                  // step 3
         }
         if (__ballot(st < 0) == 0ull) break;
         if (st < 0) {
+            // steps 4-8 stand here and in cfs_cart_kernel, statement for statement: as a shared function they cost both NJ = 5 kernels 2 %
             double delta[NJ], trial[NJ];
-            if (!ik_solve_step<NJ>(A, g, lam, delta)) st = 3;                                   // step 4
+            if (!ik_solve_step<NJ>(A, g, lam, delta)) st = 3;                               // step 4
             else {
                 double s = 0.0;
 #pragma unroll
                 for (int c = 0; c < NJ; ++c) s = fabs(delta[c]) > s ? fabs(delta[c]) : s;
-                const double sc = s > IK_STEP_CAP ? IK_STEP_CAP / s : 1.0;                      // step 5
+                const double sc = s > IK_STEP_CAP ? IK_STEP_CAP / s : 1.0;                  // step 5
 #pragma unroll
                 for (int c = 0; c < NJ; ++c) {
                     const double x = th[c] + (s > IK_STEP_CAP ? delta[c] * sc : delta[c]);
-                    trial[c] = x < P.lo[c] ? P.lo[c] : (x > P.hi[c] ? P.hi[c] : x);            // step 6
+                    trial[c] = x < P.lo[c] ? P.lo[c] : (x > P.hi[c] ? P.hi[c] : x);        // step 6
                 }
                 double p2[3], a2[3], tw2[NJ * 6], r2[6], F2;
                 ik_pose<NJ>(rb, P.tool, P.axis, trial, p2, a2, tw2);
                 ik_residual(p2, a2, tp, ta, use_axis, r2, &F2);
-                if (F2 < F) {                                                                   // step 7
+                if (F2 < F) {                                                               // step 7
 #pragma unroll
                     for (int c = 0; c < NJ; ++c) th[c] = trial[c];
 #pragma unroll
@@ -165,14 +154,14 @@ __global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkArgs<MESH
                 } else {
                     lam = lam * 10.0 < IK_LAMBDA_MAX ? lam * 10.0 : IK_LAMBDA_MAX;
                 }
-                ++it;                                                                           // step 8
+                ++it;                                                                       // step 8
             }
         }
     }
 
     // ---- collision, cost, selection ---------------------------------------------------------------------------------------
-    const double ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]), ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
-    double clear = INFINITY, cost = INFINITY;
+    double ep, ea, clear = INFINITY, cost = INFINITY;
+    ik_errors(r, &ep, &ea);
     [[maybe_unused]] double ends[MESH == RRT_MESH_NONE ? 1 : NJ * 6];          // the candidate's link ends (mesh kernels only)
     if constexpr (MESH == RRT_MESH_NONE) {
         if (st == 0) {
@@ -200,24 +189,12 @@ __global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkArgs<MESH
             double pe[NJ * 6];
 #pragma unroll
             for (int q = 0; q < NJ * 6; ++q) pe[q] = ik_bcast(ends[q], l);
-            bool hit;
-            if constexpr (MESH == RRT_MESH_PER_LANE) {
-                hit = mesh_hit_per_lane<NJ>(MA, pe, lane, s_stack, s_lbs);
-            } else {
-                const int h = mesh_hit_wave<NJ>(MA, pe, lane, s_fpair, s_fnode);
-                if (h < 0 && lane == 0) atomicAdd(&g_ik_frontier_overflows, 1ull);
-                hit = h < 0 ? mesh_hit_per_lane<NJ>(MA, pe, lane, s_stack, s_lbs) : h != 0;
-            }
+            const bool hit = mesh_hit<NJ, MESH>(MA, pe, lane, s_stack, s_lbs, s_fpair, s_fnode, &g_ik_frontier_overflows);
             if (hit && lane == l) st = 2;
         }
     }
     if (st == 0) {
-        double s = 0.0;
-#pragma unroll
-        for (int c = 0; c < NJ; ++c) {                        // w*(d*d), summed in joint order, no FMA: the contract's cost to the last bit
-            const double dlt = th[c] - tref[c];
-            s = __dadd_rn(s, __dmul_rn(P.w[c], __dmul_rn(dlt, dlt)));
-        }
+        const double s = ik_cost<NJ>(P.w, th, tref);
         if (s < INFINITY) cost = s; else st = 3;
     }
     if (active) {
@@ -231,17 +208,9 @@ __global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkArgs<MESH
     }
     const int n_ok = __popcll(__ballot(st == 0));
     const bool any_hit = __ballot(st == 2) != 0ull;
-    double bc = cost;
-    int bl = lane;
-#pragma unroll
-    for (int m = 1; m < WV; m <<= 1) {
-        const double oc = __shfl_xor(bc, m, WV);
-        const int ol = __shfl_xor(bl, m, WV);
-        if (oc < bc || (oc == bc && ol < bl)) { bc = oc; bl = ol; }
-    }
+    const int bl = ik_argmin(cost, lane);
     if constexpr (MESH != RRT_MESH_NONE) {
         // the winner's clearance: one exact, unbounded query per (mesh, link) pair, min_j (dm_j - D_mesh[j]) by a wave min
-        // (subtracting D_j is monotone, so the minimum over the links may be taken after it)
         if (n_ok > 0) {
             extern __shared__ __attribute__((aligned(16))) int s_mesh[];
             int *s_stack = s_mesh + (threadIdx.x / WV) * IK_STACK_WORDS;
@@ -252,20 +221,10 @@ __global__ __launch_bounds__(WV * IK_WAVES) void cfs_ik_kernel(const IkArgs<MESH
             for (int q = 0; q < NJ * 6; ++q) pe[q] = ik_bcast(ends[q], bl);
             double mm = INFINITY;
             for (int pr = lane; pr < MA.nmesh * NJ; pr += WV) {
-                const int j = pr / NJ, k = pr - j * NJ;
-                double a6[6];
-                pick_link<NJ>(pe, k, a6);
-                const DevMesh m{MA.m[j].nodes, MA.m[j].tri, nullptr, 0, MA.m[j].nt, nullptr, nullptr, 0, 0};
-                Best b;
-                mesh_query<WV, false>(m, a6, a6 + 3, -1, s_stack + lane, s_lbs + lane, b, nullptr);
-                const double v = b.d - A_.M.D[j];
+                const double v = mesh_pair_clearance<NJ>(MA, A_.M.D, pe, pr, s_stack + lane, s_lbs + lane);
                 if (v < mm) mm = v;
             }
-#pragma unroll
-            for (int m = 1; m < WV; m <<= 1) {
-                const double om = __shfl_xor(mm, m, WV);
-                if (om < mm) mm = om;
-            }
+            mm = mesh_wave_min(mm);
             if (mm < clear) clear = mm;                       // only the winner's `clear` is written
         }
     }
@@ -288,12 +247,7 @@ template <int NJ>
 __global__ __launch_bounds__(256) void cfs_tool_pose_kernel(const PoseParams P)
 {
     __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
-    {
-        const double *src = reinterpret_cast<const double *>(&P.rb);
-        for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += 256) s_rb[e] = src[e];
-    }
-    __syncthreads();
-    const DevRobot *rb = reinterpret_cast<const DevRobot *>(s_rb);
+    const DevRobot *rb = ik_stage<256>(P.rb, s_rb);
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= P.N) return;
     double th[NJ], p[3], a[3], tw[NJ * 6];
@@ -329,7 +283,7 @@ size_t ik_mesh_lds_bytes(int variant)
     return (size_t)IK_WAVES * (IK_STACK_WORDS + (variant == RRT_MESH_WAVE ? IK_FRONTIER_WORDS : 0)) * 4;
 }
 
-hipError_t launch_ik_mesh(int nj, int variant, const IkParams &p, const IkMeshArgs &m, hipStream_t s)
+hipError_t launch_ik_mesh(int nj, int variant, const IkParams &p, const ToolMeshArgs &m, hipStream_t s)
 {
     if (variant != RRT_MESH_PER_LANE && variant != RRT_MESH_WAVE) return hipErrorInvalidValue;
     const size_t lds = ik_mesh_lds_bytes(variant);
@@ -348,49 +302,18 @@ hipError_t launch_tool_pose(int nj, const PoseParams &p, hipStream_t s)
 }
 
 // ---- C ABI (include/cfs_hip.h, "inverse kinematics") ----------------------------------------------------------------------------
-bool finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-bool all_finite(const double *v, size_t n)
-{
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
-// everything of a call that is host memory in both entries; fills the by-value part of the kernel's parameter block
+// everything of a call that is host memory in both entries (cfs_tool_host.h); fills the by-value part of the kernel's parameter block
 int check_ik(const cfs_ik_desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref, const cfs_ik_out *out,
              IkParams &P)
 {
-    if (!d) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL descriptor");
-    int rc = cfs_check_robot(&d->robot, d->njoint);
+    int rc = check_tool_head(d);
     if (rc) return rc;
-    const int nj = d->njoint;
-    if (nj < 2) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", nj);
-    if (d->use_axis != 0 && d->use_axis != 1) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis must be 0 or 1, not %d", d->use_axis);
     if (d->restarts < 1 || d->restarts > WV) return cfs_fail(CFS_ERR_INVALID_ARG, "restarts %d outside 1..%d", d->restarts, WV);
-    if (d->max_iter < 1 || d->max_iter > 1000) return cfs_fail(CFS_ERR_INVALID_ARG, "max_iter %d outside 1..1000", d->max_iter);
-    if (d->nobs < 0 || d->nobs > CFS_MAX_OBS) return cfs_fail(CFS_ERR_INVALID_ARG, "nobs %d outside 0..%d", d->nobs, CFS_MAX_OBS);
-    if (d->nobs > 0 && (!d->obs || !d->D)) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be given");
-    if (!(std::isfinite(d->tol_pos) && d->tol_pos > 0.0 && std::isfinite(d->tol_axis) && d->tol_axis > 0.0))
-        return cfs_fail(CFS_ERR_INVALID_ARG, "tol_pos / tol_axis must be finite and > 0");
-    if (!finite3(d->tool) || !finite3(d->tool_axis)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool / tool_axis must be finite");
-    const double an = std::sqrt(d->tool_axis[0] * d->tool_axis[0] + d->tool_axis[1] * d->tool_axis[1] + d->tool_axis[2] * d->tool_axis[2]);
-    if (d->use_axis && !(an > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "tool_axis is zero");
-    if (!d->lo || !d->hi) return cfs_fail(CFS_ERR_INVALID_ARG, "lo / hi must be given");
-    for (int c = 0; c < nj; ++c) {
-        if (!std::isfinite(d->lo[c]) || !std::isfinite(d->hi[c]) || !(d->lo[c] < d->hi[c]))
-            return cfs_fail(CFS_ERR_INVALID_ARG, "joint %d: lo / hi must be finite with lo < hi", c);
-        if (d->weight && !(std::isfinite(d->weight[c]) && d->weight[c] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "weight[%d] must be finite and > 0", c);
-    }
-    if (T < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "at least one target is needed");
+    if ((rc = check_tool_max_iter(d->max_iter)) || (rc = check_tool_fields(d, T))) return rc;
     if (!target_pos || !theta_ref) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL target_pos / theta_ref");
-    if (d->use_axis && !target_axis) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis = 1 needs target_axis");
-    if (!out || !out->theta || !out->status) return cfs_fail(CFS_ERR_INVALID_ARG, "out, out->theta and out->status must be given");
-    memset(&P, 0, sizeof P);
-    cfs_build_dev_robot(d->robot, P.rb);
-    P.T = T; P.R = d->restarts; P.nobs = d->nobs; P.use_axis = d->use_axis; P.max_iter = d->max_iter;
-    for (int q = 0; q < 3; ++q) { P.tool[q] = d->tool[q]; P.axis[q] = an > 0.0 ? d->tool_axis[q] / an : 0.0; }
-    for (int c = 0; c < nj; ++c) { P.lo[c] = d->lo[c]; P.hi[c] = d->hi[c]; P.w[c] = d->weight ? d->weight[c] : 1.0; }
-    P.tol_pos = d->tol_pos; P.tol_axis = d->tol_axis; P.seed = d->seed;
+    if ((rc = check_tool_io(d, target_axis, out))) return rc;
+    fill_tool_params(d, T, P);
+    P.R = d->restarts; P.seed = d->seed;
     return CFS_SUCCESS;
 }
 
@@ -403,19 +326,8 @@ void ik_point(IkParams &P, const double *obs, const double *D, const double *tar
     P.cand_theta = o->cand_theta; P.cand_status = o->cand_status; P.cand_iter = o->cand_iter;
 }
 
-// the meshes of a cfs_ik_solve_mesh* call -> kernel argument + variant: RRT's table, then the margins for the winner's clearance
-struct IkMeshCall { int nmesh; const cfs_mesh *const *meshes; const double *D_mesh; int flags; };
-int check_ik_mesh(const cfs_ik_desc *d, const IkMeshCall &c, IkMeshArgs &m, int &variant)
-{
-    memset(&m, 0, sizeof m);
-    int rc = cfs_check_mesh_table(d->nobs, c.nmesh, c.meshes, c.D_mesh, c.flags, 1, IK_MESH_DEFAULT, m.MA, variant);
-    if (rc) return rc;
-    for (int j = 0; j < c.nmesh; ++j) m.D[j] = c.D_mesh[j];
-    return CFS_SUCCESS;
-}
-
 // mc == nullptr: the line-only call
-int ik_device(const cfs_ik_desc *d, const IkMeshCall *mc, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+int ik_device(const cfs_ik_desc *d, const MeshCall *mc, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
               const cfs_ik_out *out, void *stream)
 {
     static_assert(sizeof(IkParams) <= 4096, "the parameter block travels as a kernel argument");
@@ -423,10 +335,10 @@ int ik_device(const cfs_ik_desc *d, const IkMeshCall *mc, int T, const double *t
     IkParams P;
     int rc = check_ik(d, T, target_pos, target_axis, theta_ref, out, P);
     if (rc) return rc;
-    IkMeshArgs M;
+    ToolMeshArgs M;
     int variant = RRT_MESH_NONE;
     if (mc) {
-        rc = check_ik_mesh(d, *mc, M, variant);
+        rc = check_mesh_call(d->nobs, *mc, IK_MESH_DEFAULT, M, variant);
         if (rc) return rc;
     }
     rc = cfs_use_device(cfs_current_device());
@@ -438,31 +350,23 @@ int ik_device(const cfs_ik_desc *d, const IkMeshCall *mc, int T, const double *t
     return CFS_SUCCESS;
 }
 
-int ik_host(const cfs_ik_desc *d, const IkMeshCall *mc, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
+int ik_host(const cfs_ik_desc *d, const MeshCall *mc, int T, const double *target_pos, const double *target_axis, const double *theta_ref,
             const cfs_ik_out *out)
 {
     IkParams P;
     int rc = check_ik(d, T, target_pos, target_axis, theta_ref, out, P);
     if (rc) return rc;
-    IkMeshArgs M;
+    ToolMeshArgs M;
     int variant = RRT_MESH_NONE;
     if (mc) {   // refuse before anything is staged on the device
-        rc = check_ik_mesh(d, *mc, M, variant);
+        rc = check_mesh_call(d->nobs, *mc, IK_MESH_DEFAULT, M, variant);
         if (rc) return rc;
     }
-    const size_t nj = d->njoint, R = d->restarts, nobs = d->nobs;
-    if (!all_finite(target_pos, (size_t)T * 3) || !all_finite(theta_ref, (size_t)T * nj)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_pos / theta_ref must be finite");
-    if (nobs && (!all_finite(d->obs, nobs * 6) || !all_finite(d->D, nobs))) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be finite");
-    if (d->use_axis) {
-        if (!all_finite(target_axis, (size_t)T * 3)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis must be finite");
-        for (int t = 0; t < T; ++t) {
-            const double *v = target_axis + (size_t)t * 3;
-            if (!(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis row %d is zero", t);
-        }
-    }
+    rc = check_tool_arrays(d, T, target_pos, target_axis, theta_ref);
+    if (rc) return rc;
     rc = cfs_use_device(cfs_current_device());
     if (rc) return rc;
-    const size_t nT = T;
+    const size_t nT = T, nj = d->njoint, R = d->restarts, nobs = d->nobs;
     Stage st;
     cfs_ik_out o;
     memset(&o, 0, sizeof o);
@@ -507,14 +411,14 @@ extern "C" int cfs_ik_solve_mesh_device(const cfs_ik_desc *d, int nmesh, const c
                                         const double *target_pos, const double *target_axis, const double *theta_ref, const cfs_ik_out *out,
                                         void *stream)
 {
-    const IkMeshCall mc{nmesh, meshes, D_mesh, flags};
+    const MeshCall mc{nmesh, meshes, D_mesh, flags};
     return ik_device(d, &mc, T, target_pos, target_axis, theta_ref, out, stream);
 }
 
 extern "C" int cfs_ik_solve_mesh(const cfs_ik_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
                                  const double *target_pos, const double *target_axis, const double *theta_ref, const cfs_ik_out *out)
 {
-    const IkMeshCall mc{nmesh, meshes, D_mesh, flags};
+    const MeshCall mc{nmesh, meshes, D_mesh, flags};
     return ik_host(d, &mc, T, target_pos, target_axis, theta_ref, out);
 }
 

@@ -1,13 +1,33 @@
-// cfs_ik_dev.h -- device functions of the inverse-kinematics iteration (include/cfs_hip.h, "inverse kinematics": pose, residual,
-// analytic Jacobian, steps 4-7 of the damped least-squares iteration, the line-obstacle clearance), shared by cfs_ik.hip and
-// cfs_cart.hip.  Every loop over joints is unrolled at compile time: NJ is a template parameter.
+// cfs_ik_dev.h -- device functions of the inverse-kinematics iteration (include/cfs_hip.h, "inverse kinematics"), shared by cfs_ik.hip
+// and cfs_cart.hip: the leaves (pose, residual, analytic Jacobian, the damped step, the line-obstacle clearance) and what the kernels
+// of both units do with them -- the workgroup staging (ik_stage), the convergence test (ik_converged), the cost
+// (ik_cost) and the wave argmin of the selection (ik_argmin).  Steps 4-8 of the iteration stand in the two kernels themselves: as a
+// function here they moved the register allocation of both NJ = 5 kernels and cost them 2 %.  Every loop over
+// joints is unrolled at compile time: NJ is a template parameter.
 #pragma once
 #include "cfs_geom_dev.h"
 #include <cmath>
 
 namespace {
 
+constexpr int IK_WV = 64;                                     // lanes of a wavefront: one restart or candidate each
 constexpr double IK_LAMBDA0 = 1e-2, IK_LAMBDA_MIN = 1e-9, IK_LAMBDA_MAX = 1e9, IK_STEP_CAP = 0.5;
+
+// The robot and, with s_obs given, the nobs obstacle rows and their margins into the workgroup's LDS, by all WG threads, and the
+// block barrier behind it; returns the staged robot.
+template <int WG>
+__device__ __forceinline__ const DevRobot *ik_stage(const DevRobot &rb, double *s_rb, int nobs = 0, const double *obs = nullptr,
+                                                    const double *D = nullptr, double *s_obs = nullptr, double *s_D = nullptr)
+{
+    const double *src = reinterpret_cast<const double *>(&rb);
+    for (int e = threadIdx.x; e < (int)(sizeof(DevRobot) / 8); e += WG) s_rb[e] = src[e];
+    if (s_obs) {
+        for (int e = threadIdx.x; e < nobs * 6; e += WG) s_obs[e] = obs[e];
+        for (int e = threadIdx.x; e < nobs; e += WG) s_D[e] = D[e];
+    }
+    __syncthreads();
+    return reinterpret_cast<const DevRobot *>(s_rb);
+}
 
 // lane l's value in every lane (l is wave-uniform): two v_readlane
 __device__ __forceinline__ double ik_bcast(double v, int l)
@@ -121,6 +141,55 @@ __device__ __forceinline__ void ik_residual(const double *p, const double *a, co
     r[0] = p[0] - tp[0]; r[1] = p[1] - tp[1]; r[2] = p[2] - tp[2];
     r[3] = use_axis ? a[0] - ta[0] : 0.0; r[4] = use_axis ? a[1] - ta[1] : 0.0; r[5] = use_axis ? a[2] - ta[2] : 0.0;
     *F = (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) + (r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+}
+
+// the position and the axis error of a residual
+__device__ __forceinline__ void ik_errors(const double *r, double *ep, double *ea)
+{
+    *ep = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    *ea = sqrt(r[3] * r[3] + r[4] * r[4] + r[5] * r[5]);
+}
+
+// step 2: the pose is reached.  Both comparisons are made before they are combined: with `&&` / `||` the compiler moves the second
+// norm into a branch of its own, and cfs_cart_kernel<6>, the one kernel with scratch, then takes 16 B per lane more of it.
+__device__ __forceinline__ bool ik_converged(const double *r, bool use_axis, double tol_pos, double tol_axis)
+{
+    double ep, ea;
+    ik_errors(r, &ep, &ea);
+    const bool bp = ep <= tol_pos, ba = ea <= tol_axis;
+    return bp & (!use_axis | ba);
+}
+
+// sum_c w[c] * (a[c] - b[c])^2 in joint order, no FMA: the contract's cost to the last bit
+template <int NJ>
+__device__ __forceinline__ double ik_cost(const double *w, const double *a, const double *b)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < NJ; ++c) {
+        const double dlt = a[c] - b[c];
+        s = __dadd_rn(s, __dmul_rn(w[c], __dmul_rn(dlt, dlt)));
+    }
+    return s;
+}
+
+// the selection: the lane of the wave's smallest cost, the lowest such lane on a tie, by xor shuffles; every lane returns it.
+// WITH_MAX: the wave's maximum of *vmax rides in the same loop.
+template <bool WITH_MAX = false>
+__device__ __forceinline__ int ik_argmin(double bc, int lane, [[maybe_unused]] int *vmax = nullptr)
+{
+    int bl = lane;
+#pragma unroll
+    for (int m = 1; m < IK_WV; m <<= 1) {
+        const double oc = __shfl_xor(bc, m, IK_WV);
+        const int ol = __shfl_xor(bl, m, IK_WV);
+        if constexpr (WITH_MAX) {
+            const int ov = __shfl_xor(*vmax, m, IK_WV);
+            if (ov > *vmax) *vmax = ov;
+        }
+        if (oc < bc || (oc == bc && ol < bl)) { bc = oc; bl = ol; }
+    }
+    return bl;
 }
 
 // min_j (d_j - D_j), d_j = cfs_dist_arm's distance to obstacle j; +inf without obstacles.  ENDS: the NJ x 6 link ends go to ends_out

@@ -1,6 +1,7 @@
 // cfs_mesh_hit_dev.h -- the threshold test of link axes against mesh hierarchies, shared by the translation units that ask the
-// existence question of DESIGN.md section 19 with a whole wavefront (cfs_rrt.hip: a proposal; cfs_ik.hip: a converged restart):
-// does SOME triangle of SOME mesh j lie strictly closer than thr_j to SOME link axis?  Two variants with the same decision:
+// existence question of DESIGN.md section 19 with a whole wavefront (cfs_rrt.hip: a proposal; cfs_ik.hip: a converged restart;
+// cfs_cart.hip: a row of a traced line): does SOME triangle of SOME mesh j lie strictly closer than thr_j to SOME link axis?
+// mesh_hit is what the units call; mesh_pair_clearance and mesh_wave_min measure a winner's clearance.  Two variants with the same decision:
 //   A (mesh_hit_per_lane)  lane p < nmesh*NJ owns one (mesh, link) pair and runs mesh_query<64, false>(bound = thr_j); the vote
 //                          is a ballot of b.tri >= 0.  Private stacks in LDS (MESH_STACK*64*8 B = 10 KB).
 //   B (mesh_hit_wave)      one frontier of (pair, inner node) entries in LDS shared by the wave: each round the lanes take up to
@@ -111,6 +112,47 @@ __device__ __forceinline__ int mesh_hit_wave(const RrtMeshArgs &MA, const double
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     return 0;
+}
+
+// The decision under the unit's variant MESH (RRT_MESH_PER_LANE | RRT_MESH_WAVE): variant B, and a pose whose frontier overflows is
+// counted in *overflows (the unit's cfs_debug_*_frontier_overflows counter: one vector atomic by lane 0, none on the normal path)
+// and decided by variant A.
+template <int NJ, int MESH>
+__device__ __forceinline__ bool mesh_hit(const RrtMeshArgs &MA, const double *ends, int lane, int *stack, float *lbs, int *f_pair, int *f_node,
+                                         unsigned long long *overflows)
+{
+    if constexpr (MESH == RRT_MESH_PER_LANE) {
+        return mesh_hit_per_lane<NJ>(MA, ends, lane, stack, lbs);
+    } else {
+        const int h = mesh_hit_wave<NJ>(MA, ends, lane, f_pair, f_node);
+        if (h < 0 && lane == 0) atomicAdd(overflows, 1ull);
+        return h < 0 ? mesh_hit_per_lane<NJ>(MA, ends, lane, stack, lbs) : h != 0;
+    }
+}
+
+// The clearance of one (mesh, link) pair pr = j * NJ + k of the pose in `ends`: one exact, unbounded query, dm_j - D[j] (subtracting
+// D_j is monotone, so a minimum over the links may be taken after it).  stack / lbs: the lane's own slots.
+template <int NJ>
+__device__ __forceinline__ double mesh_pair_clearance(const RrtMeshArgs &MA, const double *D, const double *ends, int pr, int *stack, float *lbs)
+{
+    const int j = pr / NJ, k = pr - j * NJ;
+    double a6[6];
+    pick_link<NJ>(ends, k, a6);
+    const DevMesh m{MA.m[j].nodes, MA.m[j].tri, nullptr, 0, MA.m[j].nt, nullptr, nullptr, 0, 0};
+    Best b;
+    mesh_query<MESH_HIT_WV, false>(m, a6, a6 + 3, -1, stack, lbs, b, nullptr);
+    return b.d - D[j];
+}
+
+// the wave's minimum in every lane
+__device__ __forceinline__ double mesh_wave_min(double v)
+{
+#pragma unroll
+    for (int m = 1; m < MESH_HIT_WV; m <<= 1) {
+        const double o = __shfl_xor(v, m, MESH_HIT_WV);
+        if (o < v) v = o;
+    }
+    return v;
 }
 
 }  // namespace

@@ -191,14 +191,8 @@ __global__ __launch_bounds__(WV) void cfs_rrt_kernel(const RrtArgs<MESH> A)
                 hit = hit || (dis < P.D[j]);
             }
             bool infeasible = __ballot(hit) != 0ull;
-            if constexpr (MESH == RRT_MESH_PER_LANE) {
-                if (!infeasible) infeasible = mesh_hit_per_lane<NJ>(A.MA, ends, lane, s_stack, s_lbs);
-            } else if constexpr (MESH == RRT_MESH_WAVE) {
-                if (!infeasible) {
-                    const int h = mesh_hit_wave<NJ>(A.MA, ends, lane, s_fpair, s_fnode);
-                    if (h < 0 && lane == 0) atomicAdd(&g_rrt_frontier_overflows, 1ull);
-                    infeasible = h < 0 ? mesh_hit_per_lane<NJ>(A.MA, ends, lane, s_stack, s_lbs) : h != 0;
-                }
+            if constexpr (MESH != RRT_MESH_NONE) {
+                if (!infeasible) infeasible = mesh_hit<NJ, MESH>(A.MA, ends, lane, s_stack, s_lbs, s_fpair, s_fnode, &g_rrt_frontier_overflows);
             }
             e_first[0] = ends[(NJ - 1) * 6]; e_first[1] = ends[(NJ - 1) * 6 + 1]; e_first[2] = ends[(NJ - 1) * 6 + 2];   // pos{nstate}.p(:,1) (:186)
             if (!infeasible) break;
