@@ -487,7 +487,7 @@ int cfs_problem_create_from_weights(const cfs_problem_desc *desc, const cfs_cost
 static void fill_fused_family(const cfs_problem *p, FusedParams &fp, int B)
 {
     memset(&fp, 0, sizeof fp);
-    fp.rb = p->rb.p; fp.B = B; fp.H = p->d.H; fp.nobs = p->d.nobs; fp.mode = p->d.mode;
+    fp.rb = p->rb.p; fp.kind = p->d.robot.kind; fp.B = B; fp.H = p->d.H; fp.nobs = p->d.nobs; fp.mode = p->d.mode;
     fp.has_bounds = p->d.mode == CFS_MODE_CFS; fp.max_o_iter = p->d.MAX_O_ITER;
     fp.dt = p->d.robot.delta_t; fp.alpha = p->d.alpha; fp.epsilon_O = p->d.epsilon_O; fp.lmax_vel = p->lmax_vel; fp.lmax_H = p->lmax_H;
     fp.M1 = p->M1n.p; fp.M2 = p->M2n.p; fp.M3 = p->Hq.p; fp.QQ = p->QQ.p; fp.cost = p->cost.p;

@@ -115,6 +115,7 @@ struct FusedParams {
                                  // times the tile width / the last tile's width, for the linearisation's work-item decode
     unsigned ride;               // filled by launch_fused: first wavefront that carries prep(ph) while it rides on the linearisation,
                                  // 4 bits at 4 * ph (0: all of them, as a prep phase of its own)
+    int kind;                    // rb->kind, as a kernel argument: uniform, read as a scalar where the chain phase selects its link transform
     double dt, alpha, epsilon_O;
     double lmax_vel;             // rigorous upper bound of lambda_max(D'HD/dt^2): curvature of the QP objective in velocity space
     double polish_tol;           // relative drift |slack| / (1 + |bound|) of an active row at the optimum that triggers the projection

@@ -84,6 +84,17 @@ __device__ __forceinline__ int rcp_div(int e, unsigned rc) { return (int)__umulh
 // 0, 1, 2 and are compiled from the statements they had before: w2m (CFS) was measured 0.7 % slower with it in every block
 // (DESIGN.md section 4.1), the whole-CU tier was not timed on its own.
 #define CFS_RIDE_IDLE (CFS_WG_PER_CU > 1 && CFS_P_LDS)
+// The kinematic chains of the literal linearisation read their operands ahead of the arithmetic that uses them (chain_item below)
+// instead of in dependent LDS round trips, in the tier of the identity Hessian (w2s).  w2m (CFS) was timed with it and did not gain,
+// the whole-CU tier was not timed: both are compiled from the statements they had before.
+#ifndef CFS_CHAIN_AHEAD
+#define CFS_CHAIN_AHEAD (CFS_WG_PER_CU > 1 && CFS_P_LDS)
+#endif
+// The kernels of the identity Hessian keep the problem's ff in LDS, in the block that only the input-bound rows of a CFS solve read
+// (FusedLayout::racc), in the tier of the identity Hessian (w2s); the whole-CU tier was not timed with it.
+#ifndef CFS_FF_LDS
+#define CFS_FF_LDS (CFS_WG_PER_CU > 1 && CFS_P_LDS)
+#endif
 
 // ---- DPP helpers (gfx9 row shifts / row broadcasts) ---------------------------------------------
 template <int CTRL, int RM>
@@ -635,6 +646,84 @@ __host__ __device__ inline FusedLayout fused_layout(int NJ, int H, int nobs, int
     return L;
 }
 
+#if CFS_CHAIN_AHEAD
+// One work item of the literal scheme's chain phase for a DH robot: the kinematic chain of evaluation point ev of num_jac at one
+// waypoint.  The expressions are fk_step's and link_ends' (cfs_geom_dev.h), term for term; what differs is where their operands
+// come from.  The caller reads the robot's kind once per tile, as a scalar, so no link reads it from LDS and branches on it; the
+// operands of link k1 + 1 -- sin / cos of the item's variant, ca, sa, a, d -- are read into locals before the products of link
+// k1, and a link's capsule points and the base are read before and outside the `ev <= 2 k1` test, which guards the store alone.
+// fk_step reads in three dependent LDS round trips per link (kind and sin / cos, then the constants, then the capsule points
+// behind the test); here every link waits once, with the next link's reads in flight behind its products.  The two-link arm
+// (`t2l` transforms) stays on fk_step: compiled as a form of its own it did not reproduce fk_step's end points bit for bit.
+struct LinkOps { double sn, cs, ca, sa, a, d; };
+__device__ __forceinline__ LinkOps link_ops(const DevRobot *rb, const double *sc2, int k)
+{
+    LinkOps o;
+    o.sn = sc2[0]; o.cs = sc2[1];
+    o.ca = rb->ca[k]; o.sa = rb->sa[k]; o.a = rb->dh_a[k]; o.d = rb->dh_d[k];
+    return o;
+}
+// sc: [NJ][3][2] sin, cos of the waypoint's joints at theta, theta+eps/2, theta-eps/2; en: [NVT][6] its link end points
+template <int NJ>
+__device__ __forceinline__ void chain_item(const DevRobot *rb, const double *sc, int ev, double *en)
+{
+    const double b0 = rb->base[0], b1 = rb->base[1], b2 = rb->base[2];
+    double M[12], Mn[12];
+    LinkOps nx = link_ops(rb, sc + ((ev == 1) ? 1 : (ev >= 2 ? 2 : 0)) * 2, 0);
+#pragma unroll
+    for (int k1 = 1; k1 <= NJ; ++k1) {
+        const LinkOps o = nx;
+        double cp[6];
+#pragma unroll
+        for (int qq = 0; qq < 6; ++qq) cp[qq] = rb->cap[(k1 - 1) * 6 + qq];
+        if (k1 < NJ) {
+            const int avar = (ev == 2 * k1 + 1) ? 1 : (ev >= 2 * k1 + 2 ? 2 : 0);
+            nx = link_ops(rb, sc + (k1 * 3 + avar) * 2, k1);
+        }
+        const double st = o.sn, ct = o.cs, ca = o.ca, sa = o.sa, a = o.a, d = o.d;
+        double R[12];
+        R[0] = ct;  R[1] = -st * ca; R[2] = st * sa;   R[3] = a * ct;
+        R[4] = st;  R[5] = ct * ca;  R[6] = -ct * sa;  R[7] = a * st;
+        R[8] = 0.0; R[9] = sa;       R[10] = ca;       R[11] = d;
+        // (the empty asm: fk_step's R entries reach its products through the merge of its two branches, so the compiler contracts
+        // `p0 * R[c] + p1 * R[4 + c] + p2 * R[8 + c]` without seeing what an entry is made of.  With the negations and products
+        // of the DH form in view it picks another of the three products as the one that is rounded on its own, and the end
+        // points move in the last place.)
+        asm volatile("" : "+v"(R[1]), "+v"(R[2]), "+v"(R[3]), "+v"(R[5]), "+v"(R[6]), "+v"(R[7]));
+        if (k1 == 1) {                             // M{1} = eye(4)
+#pragma unroll
+            for (int e = 0; e < 12; ++e) M[e] = R[e];
+        } else {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const double p0 = M[r * 4 + 0], p1 = M[r * 4 + 1], p2 = M[r * 4 + 2], p3 = M[r * 4 + 3];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    double s = p0 * R[c] + p1 * R[4 + c] + p2 * R[8 + c];
+                    if (c == 3) s += p3;
+                    Mn[r * 4 + c] = s;
+                }
+            }
+#pragma unroll
+            for (int qq = 0; qq < 12; ++qq) M[qq] = Mn[qq];
+        }
+        double e6[6];
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const double *p = cp + kk * 3;
+            e6[kk * 3 + 0] = (M[0] * p[0] + M[1] * p[1] + M[2] * p[2]) + M[3] + b0;
+            e6[kk * 3 + 1] = (M[4] * p[0] + M[5] * p[1] + M[6] * p[2]) + M[7] + b1;
+            e6[kk * 3 + 2] = (M[8] * p[0] + M[9] * p[1] + M[10] * p[2]) + M[11] + b2;
+        }
+        if (ev <= 2 * k1) {
+            double *dstE = en + (kvoff(k1) + ev) * 6;
+#pragma unroll
+            for (int qq = 0; qq < 6; ++qq) dstE[qq] = e6[qq];
+        }
+    }
+}
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // IDENT: the QP Hessian is the identity (PSGCFS projection); JAC: analytic Jacobian (CFS_JAC_ANALYTIC handles); MOVE: obstacles
 // per waypoint (CFS_OBS_PER_WAYPOINT handles: P.obs is B x H x nobs x 6, no mesh obstacles); LIM: joint position rows (handles
@@ -671,6 +760,17 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
     double *s_plim = s_margin + nobs;               // LIM: [lo; hi] of the joint positions (2 NJ)
     double *s_mx = lds + L.mx;
     double *s_racc = lds + L.racc;
+    // FF_LDS: the problem's ff stays in LDS for the whole solve, in the block of s_racc.  That block is written and read only under
+    // P.has_bounds, which is mode == CFS, and an IDENT kernel runs PSGCFS solves alone (launch_fused_inst refuses anything else), so
+    // the block is dead there and the layout does not grow.  prep(2) and the cost product read it instead of global memory.
+    // Only the kernels of at most 160 rows and 5 joints: the register allocator answered the change with 4 to 16 B more scratch in
+    // the others (every 6-joint kernel, <4,256>), which keep the global loads and the statements they had.
+#if CFS_FF_LDS
+    constexpr bool FF_LDS = IDENT && NJ <= 5 && QB <= P_LDS_MAX_QB;
+#else
+    constexpr bool FF_LDS = false;
+#endif
+    const double *s_ff = s_racc;
     // Spill space (columns [PR,QB) of P as [b-PR][a], rows of Y beyond the LDS capacity) comes from a POOL of P.pool_n slots, one per
     // workgroup that can be resident at once (2 per compute unit), not one per problem of the batch: a workgroup takes a free slot
     // when it starts (one atomicCAS by thread 0) and gives it back when it ends.  With fewer slots than resident workgroups a
@@ -732,6 +832,9 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
             for (int e = tid; e < nobs * 6; e += FT) s_ob[e] = P.obs[(size_t)b * nobs * 6 + e];
         for (int e = tid; e < NX; e += FT) s_x[e] = P.x_init[(size_t)b * NX + e];
         for (int e = tid; e < HN; e += FT) { s_u[e] = 0.0; s_qu[e] = 0.0; s_mx[e] = P.has_bounds ? P.maxin[e] : 0.0; }
+        if constexpr (FF_LDS)
+            if (P.piece == 0 && !P.has_bounds)
+                for (int e = tid; e < HN; e += FT) s_racc[e] = P.ff[(size_t)b * nn + e];
         if (tid < NJ) {
             s_lim[tid] = P.lim[tid];
             s_v0[tid] = P.xR1[(size_t)b * NS + NJ + tid];
@@ -834,7 +937,9 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     if (psg && skip) v = s_u[k];            // no step: x_ is the rollout of the unchanged u
                     else if (psg) {
                         const double nz = have ? P.noise[((size_t)b * P.noise_rows + noise_row_now) * nn + k] : 0.0;
-                        v = s_u[k] - P.alpha * ((s_qu[k] + P.ff[(size_t)b * nn + k]) + 10.0 * nz / sc);   // PSGCFS_FANUC.m:109
+                        double fk;
+                        if constexpr (FF_LDS) fk = s_ff[k]; else fk = P.ff[(size_t)b * nn + k];
+                        v = s_u[k] - P.alpha * ((s_qu[k] + fk) + 10.0 * nz / sc);   // PSGCFS_FANUC.m:109
                     } else v = P.x0[(size_t)b * nn + k];    // CFS: -H^{-1} ff; cfs_qp: the caller's start point
                     xs[k] = v;
                 }
@@ -943,6 +1048,11 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     unsigned rc_n = P.rc_nseg, rc_t = Wc == W ? P.rc_tile : P.rc_last;
                     asm volatile("" : "+s"(rc_n), "+s"(rc_t));
 #endif
+#if CFS_CHAIN_AHEAD
+                    // the robot's kind, a kernel argument read per tile (never from LDS per joint); the empty asm as above
+                    int rkind = P.kind;
+                    asm volatile("" : "+s"(rkind));
+#endif
                     if (w0 == 0) prep(0);
                     if constexpr (MOVE)                          // (the previous tile's last read of them is behind its pair-phase barrier)
                         for (int e = tid; e < Wc * nseg * 6; e += FT) S_OBW[e] = P.obs[((size_t)b * H + w0) * nobs * 6 + e];
@@ -964,6 +1074,10 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     // evaluation ev is variant min(ev, 2k); the thread with ev <= 2k is the one that stores it.
                     for (int e = tid; e < Wc * NE; e += FT) {
                         const int ev = e % NE, wi = e / NE;
+#if CFS_CHAIN_AHEAD
+                        // DH robots: operands read ahead (chain_item); the two-link arm keeps fk_step / link_ends below
+                        if (rkind != CFS_ROBOT_2L) { chain_item<NJ>(rb, s_sc + wi * NJ * 6, ev, s_en + wi * NVT * 6); continue; }
+#endif
                         double M[12], Mn[12], e6[6];
 #pragma unroll
                         for (int k1 = 1; k1 <= NJ; ++k1) {
@@ -1794,7 +1908,14 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
         // final here (a skipped PSG step left the rollout of the unchanged u in it), so everything below reads xs; s_u is refreshed
         // at the end of the phase for the next iteration.
         double du2 = 0.0, dx2 = 0.0, cpart = 0.0;
-        for (int k = tid; k < HN; k += FT) {
+        // POST_FRESH: the phase derives its element and lane indices from a copy of the thread index behind an empty asm, so that the
+        // LDS addresses built from them are computed here (a few integer operations) and not outside the outer loop, from where
+        // they came back one spilled register at a time, each reload with a wait of its own in the middle of the scans
+        int pt = tid;
+#if CFS_FF_LDS
+        asm volatile("" : "+v"(pt));
+#endif
+        for (int k = pt; k < HN; k += FT) {
             const int i = k / NJ, c = k - i * NJ;
             const double un = xs[k], e = s_u[k] - un;
             du2 += e * e;
@@ -1820,9 +1941,9 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                 // sums along the horizon (DPP scans over reversed lanes) -- no pass over the dense nn x nn matrix
                 const DevCost *ck = reinterpret_cast<const DevCost *>(lds + L.cost);
                 const bool two = H <= 32;
-                const int lane = two ? (tid & 31) : (tid & 63), iR = H - 1 - lane;
+                const int lane = two ? (pt & 31) : (pt & 63), iR = H - 1 - lane;
                 const int cstep = two ? 2 * (FT / 64) : FT / 64;
-                for (int c = two ? (tid >> 5) : (tid >> 6); c < NJ; c += cstep) {
+                for (int c = two ? (pt >> 5) : (pt >> 6); c < NJ; c += cstep) {
                     double Rp = 0.0, Rv = 0.0;
                     if (lane < H) {
                         const double wi = iR == H - 1 ? ck->wt : ck->ws;
@@ -1839,7 +1960,7 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                     const double cmb = (dt * dt) * S1 + Rv;
                     const double S2V = two ? half_scan_incl(cmb) : wave_scan_incl(cmb);
                     const double y_rev = S2V - (0.5 * dt * dt) * S1;
-                    const int src = (lane < H ? H - 1 - lane : lane) + (two ? (tid & 32) : 0);
+                    const int src = (lane < H ? H - 1 - lane : lane) + (two ? (pt & 32) : 0);
                     const double y = __shfl(y_rev, src, 64);
                     if (lane < H) {
                         const int k = lane * NJ + c;
@@ -1848,11 +1969,13 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                         for (int c2 = 0; c2 < NJ; ++c2) ru += ck->Rs[c + c2 * NJ] * xs[lane * NJ + c2];
                         const double sq = y + ru;
                         s_qu[k] = sq;
-                        cpart += xs[k] * (0.5 * sq + P.ff[(size_t)b * nn + k]);
+                        double fk;
+                        if constexpr (FF_LDS) fk = s_ff[k]; else fk = P.ff[(size_t)b * nn + k];
+                        cpart += xs[k] * (0.5 * sq + fk);
                     }
                 }
             } else
-            for (int k = tid; k < HN; k += FT) {
+            for (int k = pt; k < HN; k += FT) {
                 double sa[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
                 int c = 0;
                 for (; c + MV_BATCH <= HN; c += MV_BATCH) {   // independent L2 loads in flight per thread
@@ -1865,7 +1988,9 @@ __global__ __launch_bounds__(FT, CFS_WG_PER_CU) void cfs_solve_fused_kernel(Fuse
                 for (; c < HN; ++c) sa[0] += P.QQ[k + (size_t)c * nn] * xs[c];
                 const double s = ((sa[0] + sa[1]) + (sa[2] + sa[3])) + ((sa[4] + sa[5]) + (sa[6] + sa[7]));
                 s_qu[k] = s;
-                cpart += xs[k] * (0.5 * s + P.ff[(size_t)b * nn + k]);
+                double fk;
+                if constexpr (FF_LDS) fk = s_ff[k]; else fk = P.ff[(size_t)b * nn + k];
+                cpart += xs[k] * (0.5 * s + fk);
             }
         }
         block_sum3(du2, dx2, cpart, red, tid);
@@ -1935,6 +2060,7 @@ template <int NJ, int QB, bool JAC, bool SOFT, bool MOVE, bool LIM>
 hipError_t launch_fused_inst(const FusedParams &p, size_t lds, hipStream_t s, const SoftParams *sp)
 {
     const bool ident = p.mode == CFS_MODE_PSGCFS;
+    if (ident && p.has_bounds) return hipErrorInvalidValue;   // the identity kernels keep ff where the input-bound rows keep s_racc (FF_LDS)
 #if CFS_IDENT_SET != 0
     if (ident) return launch_fused_inst2<NJ, QB, true, JAC, SOFT, MOVE, LIM>(p, lds, s, sp);
 #endif
