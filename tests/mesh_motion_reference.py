@@ -2,13 +2,13 @@
 oracle's own primitives in the way tests/moving_reference.py is.  Collision row (j, i) of get_con depends only on waypoint i's pose
 and on obstacle j, so for waypoint i every moving mesh is registered with the oracle where pose [j][i] puts it (its triangles
 transformed on the host in double: no inverse pose, no hierarchy), one oracle get_con is taken, and waypoint i's rows are kept.  The
-oracle's mesh registry is global, so this runs sequentially.  The outer loop is moving_reference.optimizer_moving's with this
-get_con.  Used by tests/test_mesh_motion_reference.py (which validates it and vets the cases) and tests/test_gpu_mesh_motion.py."""
+oracle's mesh registry is global, so this runs sequentially.  The outer loop is tests/reference_loop.py's with this get_con.
+Used by tests/test_mesh_motion_reference.py (which validates it and vets the cases) and tests/test_gpu_mesh_motion.py."""
 from types import SimpleNamespace
 
 import numpy as np
 
-import moving_reference as MR
+import reference_loop as RL
 
 D_MARGIN, EPS_MARGIN = 0.2, 0.25                 # main_FANUC's margins: obs.D (PSGCFS) and obs.epsilon (CFS)
 C_POST = (3.356, 8.963)                          # the vertical the post stands on
@@ -129,16 +129,10 @@ def get_con_posed(O, ROBOT, s, lines, tris, poses, x_, u, mode):
 
 
 def optimizer_posed(O, ROBOT, s, lines, tris, poses, mode, x_init, noise=None):
-    """CFS_FANUC / PSGCFS_FANUC .optimizer() of one problem against meshes placed per waypoint: optimizer_moving's loop, its
-    get_con replaced by get_con_posed"""
-    margin = np.full(len(lines) + len(tris), EPS_MARGIN if mode == "CFS" else D_MARGIN)
-    real = MR.get_con_moving                             # the loop looks its get_con up in its module: swap it for this call
-    MR.get_con_moving = lambda O_, R_, s2, obs_traj, mg, x_, u, md: get_con_posed(O, R_, s2, lines, tris, poses, x_, u, md)
-    try:
-        return MR.optimizer_moving(O, ROBOT, s, np.zeros((s.H, len(margin), 6)), margin, mode, x_init, s.xR1, s.ff, s.caug,
-                                   noise=noise)
-    finally:
-        MR.get_con_moving = real
+    """CFS_FANUC / PSGCFS_FANUC .optimizer() of one problem against meshes placed per waypoint: reference_loop.optimizer with
+    get_con_posed"""
+    return RL.optimizer(O, ROBOT, s, mode, lambda s2, x_, u: get_con_posed(O, ROBOT, s2, lines, tris, poses, x_, u, mode),
+                        x_init, s.xR1, s.ff, s.caug, noise=noise)
 
 
 def clearance_where_it_is(O, s, tris, poses, x_):

@@ -1,10 +1,10 @@
 """The placement rule of the fused solver's riding work (launch_fused_tier, FusedParams::ride; restated in
-tests/wave_balance_cases.py) and the index arithmetic of the loops that follow it (roll_lds and prep(2) of csrc/cfs_fused.hip),
+tests/fused_recorded.py) and the index arithmetic of the loops that follow it (roll_lds and prep(2) of csrc/cfs_fused.hip),
 simulated thread by thread: the chosen wavefronts really have a pass less, and every joint / element is still computed exactly once."""
 import numpy as np
 import pytest
 
-import wave_balance_cases as W
+import fused_recorded as W
 
 FT, WAVE = 256, 64
 
