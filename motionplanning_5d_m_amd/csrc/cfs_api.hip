@@ -22,70 +22,6 @@ int have_device()
     return n;
 }
 
-// symmetric positive definite inverse in extended precision (once per problem family)
-// lambda_max(G) <= ||G^(2^k)||_inf^(1/2^k) for symmetric G: five squarings are within n^(1/32) of it (+ margin for fp64 rounding)
-double lambda_max_upper(int nn, std::vector<double> G)
-{
-    std::vector<double> T2((size_t)nn * nn);
-    double logscale = 0.0;
-    for (int it = 0; it < 5; ++it) {
-        double nrm = 0.0;
-        for (int i = 0; i < nn; ++i) { double s = 0.0; for (int j = 0; j < nn; ++j) s += fabs(G[i + (size_t)j * nn]); if (s > nrm) nrm = s; }
-        if (!(nrm > 0.0)) return 0.0;
-        for (auto &v : G) v /= nrm;
-        logscale = 2.0 * (logscale + log(nrm));
-        for (int i = 0; i < nn; ++i)
-            for (int j = 0; j < nn; ++j) { double s = 0.0; for (int k = 0; k < nn; ++k) s += G[i + (size_t)k * nn] * G[k + (size_t)j * nn]; T2[i + (size_t)j * nn] = s; }
-        G.swap(T2);
-    }
-    double nrm = 0.0;
-    for (int i = 0; i < nn; ++i) { double s = 0.0; for (int j = 0; j < nn; ++j) s += fabs(G[i + (size_t)j * nn]); if (s > nrm) nrm = s; }
-    return exp((logscale + log(nrm)) / 32.0) * 1.001;
-}
-
-// (QQ + QQ') / 2: quadprog symmetrises its Hessian silently
-std::vector<double> symmetrise(int nn, const double *QQ)
-{
-    std::vector<double> sym((size_t)nn * nn);
-    for (int j = 0; j < nn; ++j)
-        for (int i = 0; i < nn; ++i) sym[i + (size_t)j * nn] = 0.5 * (QQ[i + (size_t)j * nn] + QQ[j + (size_t)i * nn]);
-    return sym;
-}
-
-bool spd_inverse(int n, const double *Asym, std::vector<double> &inv, std::vector<long double> &Li)
-{
-    std::vector<long double> L((size_t)n * n, 0.0L);
-    Li.assign((size_t)n * n, 0.0L);
-    for (int j = 0; j < n; ++j) {
-        long double s = Asym[j + (size_t)j * n];
-        for (int k = 0; k < j; ++k) s -= L[j + (size_t)k * n] * L[j + (size_t)k * n];
-        if (!(s > 0)) return false;
-        const long double ljj = sqrtl(s);
-        L[j + (size_t)j * n] = ljj;
-        for (int i = j + 1; i < n; ++i) {
-            long double t = Asym[i + (size_t)j * n];
-            for (int k = 0; k < j; ++k) t -= L[i + (size_t)k * n] * L[j + (size_t)k * n];
-            L[i + (size_t)j * n] = t / ljj;
-        }
-    }
-    for (int j = 0; j < n; ++j) {          // Li = L^{-1}, lower
-        Li[j + (size_t)j * n] = 1.0L / L[j + (size_t)j * n];
-        for (int i = j + 1; i < n; ++i) {
-            long double s = 0.0L;
-            for (int k = j; k < i; ++k) s -= L[i + (size_t)k * n] * Li[k + (size_t)j * n];
-            Li[i + (size_t)j * n] = s / L[i + (size_t)i * n];
-        }
-    }
-    inv.assign((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j <= i; ++j) {     // A^{-1} = Li' Li
-            long double s = 0.0L;
-            for (int k = i; k < n; ++k) s += Li[k + (size_t)i * n] * Li[k + (size_t)j * n];
-            inv[i + (size_t)j * n] = inv[j + (size_t)i * n] = (double)s;
-        }
-    return true;
-}
-
 }  // namespace
 
 int cfs_fail(int code, const char *fmt, ...)
@@ -238,88 +174,10 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
     if (!(dt > 0)) return cfs_fail(CFS_ERR_INVALID_ARG, "robot.delta_t must be positive");
     const int nn = H * nj, ns = 2 * nj, nx = H * ns;
 
-    // sys_info.Aaug / Baug must be the double integrator of robot.A / robot.B
-    // (robotproperty2.m:136-139, main_FANUC.m:79-86): the kernels roll out with prefix sums.
-    if (desc->Baug) {
-        for (int i = 0; i < H; ++i)
-            for (int k = 0; k < H; ++k)
-                for (int r = 0; r < ns; ++r)
-                    for (int c = 0; c < nj; ++c) {
-                        double want = 0.0;
-                        if (k <= i && (r % nj) == c) want = r < nj ? ((double)(i - k) + 0.5) * dt * dt : dt;
-                        const double got = desc->Baug[(i * ns + r) + (size_t)(k * nj + c) * nx];
-                        if (fabs(got - want) > 1e-12 * (1.0 + fabs(want)))
-                            return cfs_fail(CFS_ERR_DYNAMICS, "Baug(%d,%d)=%.17g, double integrator expects %.17g", i * ns + r + 1, k * nj + c + 1, got, want);
-                    }
-    }
-    if (desc->Aaug) {
-        for (int i = 0; i < H; ++i)
-            for (int r = 0; r < ns; ++r)
-                for (int c = 0; c < ns; ++c) {
-                    double want = (r == c) ? 1.0 : 0.0;
-                    if (r < nj && c == r + nj) want = (double)(i + 1) * dt;
-                    const double got = desc->Aaug[(i * ns + r) + (size_t)c * nx];
-                    if (fabs(got - want) > 1e-12 * (1.0 + fabs(want)))
-                        return cfs_fail(CFS_ERR_DYNAMICS, "Aaug(%d,%d)=%.17g, double integrator expects %.17g", i * ns + r + 1, c + 1, got, want);
-                }
-    }
+    if (FamilyRefusal r = check_double_integrator(nj, H, dt, desc->Aaug, desc->Baug)) return cfs_fail(r.code, "%s", r.text);
     if (have_device() == 0) return cfs_fail(CFS_ERR_NO_DEVICE, "no HIP device visible");
-
-    // H^{-1} of the QP Hessian: QQ symmetrised (quadprog does so silently) for CFS, identity for the
-    // PSGCFS projection (PSGCFS_FANUC.m:117)
-    std::vector<double> Hinv;
-    std::vector<long double> Li;            // L^{-1} (lower), H = L L'
-    const std::vector<double> sym = symmetrise(nn, desc->QQ);
-    if (!spd_inverse(nn, sym.data(), Hinv, Li)) return cfs_fail(CFS_ERR_NOT_SPD, "QQ is not positive definite");
-    std::vector<double> Hq;   // Hessian inverse used by the QP
-    if (desc->mode == CFS_MODE_CFS) Hq = Hinv;
-    else {
-        Hq.assign((size_t)nn * nn, 0.0);
-        for (int i = 0; i < nn; ++i) Hq[i + (size_t)i * nn] = 1.0;
-    }
-    // Family matrices H^{-1}Bpos', H^{-1}Bvel' (columns = constraint position (i, c), natural row order): extended-precision
-    // sums over the entries of the ONE rounded matrix Hq, on purpose.  Every product n_a'H^{-1}n_p the kernel forms is then
-    // exactly symmetric in (a, p) -- the QP is solved for a Hessian inverse that differs from the true one by 1 ulp per entry,
-    // which is harmless -- whereas columns taken from a more accurate solve L^{-T}(L^{-1}Bpos') disagree with the rounded Hq
-    // columns of the bound rows by eps*cond(H) ~ 1e-10: the step refinement then never reaches its residual target and runs
-    // all its passes (measured: CFS mode 30 % slower, same answers).
-    std::vector<double> M1n((size_t)nn * nn), M2n((size_t)nn * nn);
-    {
-        std::vector<long double> a1(nn), a2(nn);
-        for (int c = 0; c < nj; ++c)
-            for (int i = 0; i < H; ++i) {
-                for (int r = 0; r < nn; ++r) {
-                    long double s1 = 0.0L, s2 = 0.0L;
-                    for (int k = 0; k <= i; ++k) {
-                        const long double h = Hq[r + (size_t)(k * nj + c) * nn];
-                        s1 += ((long double)(i - k) + 0.5L) * (long double)dt * (long double)dt * h;
-                        s2 += (long double)dt * h;
-                    }
-                    a1[r] = s1; a2[r] = s2;
-                }
-                const int col = i * nj + c;
-                for (int r = 0; r < nn; ++r) { M1n[r + (size_t)col * nn] = (double)a1[r]; M2n[r + (size_t)col * nn] = (double)a2[r]; }
-            }
-    }
-
-    // rigorous upper bounds of lambda_max(H) and of lambda_max(G), G = D'HD/dt^2 (D = first difference along the waypoints, so
-    // that u = D s/dt for s = Bvel u), H = the QP Hessian (QQ symmetrised | I): the early infeasibility test of the fused kernel
-    double lmax_vel = 0.0, lmax_H = 1.0;
-    {
-        const std::vector<double> &Hs = desc->mode == CFS_MODE_CFS ? sym : Hq;   // Hq is the identity for PSGCFS
-        std::vector<double> G;
-        auto Dt = [&](std::vector<double> &M, bool left) {     // M <- D'M (left) or M D (right): row/col k minus row/col k+nj
-            for (int o = 0; o < nn; ++o)
-                for (int k = 0; k + nj < nn; ++k) {
-                    if (left) M[k + (size_t)o * nn] -= M[(k + nj) + (size_t)o * nn];
-                    else M[o + (size_t)k * nn] -= M[o + (size_t)(k + nj) * nn];
-                }
-        };
-        G = Hs; Dt(G, true); Dt(G, false);
-        for (auto &v : G) v /= (double)(dt * dt);
-        lmax_vel = lambda_max_upper(nn, G);
-        if (desc->mode == CFS_MODE_CFS) lmax_H = lambda_max_upper(nn, Hs);   // not 1/alpha: alpha is the caller's PSGCFS step
-    }
+    FamilyMatrices fm;                       // H^{-1}, the QP's Hessian inverse, H^{-1}Bpos', H^{-1}Bvel' and the two eigenvalue bounds (cfs_family.cpp)
+    if (FamilyRefusal r = family_matrices(nj, H, dt, desc->mode, desc->QQ, fm)) return cfs_fail(r.code, "%s", r.text);
     cfs_problem *p = new (std::nothrow) cfs_problem();
     if (!p) return cfs_fail(CFS_ERR_ALLOC, "out of host memory");
     p->d = *desc;
@@ -327,7 +185,7 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
     p->d.QQ = p->d.Aaug = p->d.Baug = p->d.lim = p->d.MAX_input = p->d.margin = nullptr;
     p->device = g_device;
     if (hipDeviceGetAttribute(&p->n_cu, hipDeviceAttributeMultiprocessorCount, g_device) != hipSuccess || p->n_cu < 1) p->n_cu = 256;
-    p->nn = nn; p->ns = ns; p->nx = nx; p->lmax_vel = lmax_vel; p->lmax_H = lmax_H;
+    p->nn = nn; p->ns = ns; p->nx = nx; p->lmax_vel = fm.lmax_vel; p->lmax_H = fm.lmax_H;
     cfs_build_dev_robot(desc->robot, p->hrobot);
     cfs_clear_build_rho(p->hrobot, nj, p->rho);
     const size_t Bm = (size_t)desc->max_batch;
@@ -336,25 +194,23 @@ int cfs_problem_create(const cfs_problem_desc *desc, cfs_problem **out)
     p->pool_n = (int)std::min<size_t>(Bm, (size_t)2 * p->n_cu);
     const size_t Pn = (size_t)p->pool_n;
     hipError_t e = hipSetDevice(p->device);
-#define A_(buf, count) if (e == hipSuccess) e = p->buf.alloc(count)
-    A_(rb, 1); A_(QQ, (size_t)nn * nn); A_(Hinv, (size_t)nn * nn);
-    A_(M1n, (size_t)nn * nn); A_(M2n, (size_t)nn * nn); A_(Hq, (size_t)nn * nn); A_(Pt, Pn * pt_stride(nn)); A_(lim, 3 * (size_t)nj); A_(maxin, nn); A_(margin, desc->nobs);
-    A_(x0, Bm * nn); A_(qu, Bm * nn); A_(dist, Bm * desc->nobs * H); A_(grad, Bm * desc->nobs * H * nj);
-    A_(Yg, Pn * nn * nn); A_(pool_flag, Pn * 16);
-    if (desc->mode == CFS_MODE_CFS) { A_(u_hist, Bm * (size_t)desc->MAX_O_ITER * nn); A_(qu_hist, Bm * (size_t)desc->MAX_O_ITER * nn); }
-    A_(noise_row, Bm); A_(linkid, Bm * desc->nobs * H); A_(order, Bm); A_(okey, Bm); A_(order_user, Bm);
-#undef A_
-#define U_(buf, src, count) if (e == hipSuccess) e = hipMemcpy(p->buf.p, src, (count) * sizeof(*p->buf.p), hipMemcpyHostToDevice)
-    U_(rb, &p->hrobot, 1); U_(QQ, desc->QQ, (size_t)nn * nn); U_(Hinv, Hinv.data(), (size_t)nn * nn);
-    U_(M1n, M1n.data(), (size_t)nn * nn); U_(M2n, M2n.data(), (size_t)nn * nn); U_(Hq, Hq.data(), (size_t)nn * nn);
-    U_(lim, desc->lim, nj); U_(margin, desc->margin, desc->nobs);
-    if (desc->mode == CFS_MODE_CFS) { U_(maxin, desc->MAX_input, nn); }
-    else if (e == hipSuccess) e = hipMemset(p->maxin.p, 0, nn * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(p->pool_flag.p, 0, Pn * 16 * sizeof(int));
-#undef U_
+    auto up = [&](auto &buf, const auto *src, size_t count) { if (e == hipSuccess) e = buf.upload(src, count); };
+    auto room = [&](auto &buf, size_t count) { if (e == hipSuccess) e = buf.alloc(count); };
+    up(p->rb, &p->hrobot, 1); up(p->QQ, desc->QQ, (size_t)nn * nn); up(p->Hinv, fm.Hinv.data(), (size_t)nn * nn);
+    up(p->M1n, fm.M1n.data(), (size_t)nn * nn); up(p->M2n, fm.M2n.data(), (size_t)nn * nn); up(p->Hq, fm.Hq.data(), (size_t)nn * nn);
+    room(p->Pt, Pn * pt_stride(nn));
+    room(p->lim, 3 * (size_t)nj);            // [lim | lo | hi]: the last two are written by cfs_problem_set_joint_limits
+    if (e == hipSuccess) e = hipMemcpy(p->lim.p, desc->lim, nj * sizeof(double), hipMemcpyHostToDevice);
+    if (desc->mode == CFS_MODE_CFS) up(p->maxin, desc->MAX_input, nn);
+    else if (e == hipSuccess) e = p->maxin.zeros(nn);
+    up(p->margin, desc->margin, desc->nobs);
+    room(p->x0, Bm * nn); room(p->qu, Bm * nn); room(p->dist, Bm * desc->nobs * H); room(p->grad, Bm * desc->nobs * H * nj);
+    room(p->Yg, Pn * nn * nn);
+    if (e == hipSuccess) e = p->pool_flag.zeros(Pn * 16);
+    if (desc->mode == CFS_MODE_CFS) { room(p->u_hist, Bm * (size_t)desc->MAX_O_ITER * nn); room(p->qu_hist, Bm * (size_t)desc->MAX_O_ITER * nn); }
+    room(p->noise_row, Bm); room(p->linkid, Bm * desc->nobs * H); room(p->order, Bm); room(p->okey, Bm); room(p->order_user, Bm);
     if (e != hipSuccess) {
-        p->release_all();
-        delete p;
+        delete p;                            // its device was selected above
         return cfs_fail(CFS_ERR_HIP, "device setup failed: %s", hipGetErrorString(e));
     }
     *out = p;
@@ -365,7 +221,6 @@ void cfs_problem_destroy(cfs_problem *p)
 {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    p->release_all();
     delete p;
 }
 
@@ -377,38 +232,6 @@ int cfs_problem_family(const cfs_problem *p, double *QQ, double *alpha)
     return CFS_SUCCESS;
 }
 
-// largest eigenvalue of a symmetric matrix by cyclic Jacobi rotations (once per family, n <= 384)
-static double sym_lambda_max(int n, std::vector<double> A)
-{
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0, dia = 0.0;
-        for (int j = 0; j < n; ++j)
-            for (int i = 0; i < n; ++i) (i == j ? dia : off) += A[i + (size_t)j * n] * A[i + (size_t)j * n];
-        if (off <= 1e-30 * dia) break;
-        for (int p_ = 0; p_ < n - 1; ++p_)
-            for (int q_ = p_ + 1; q_ < n; ++q_) {
-                const double apq = A[p_ + (size_t)q_ * n];
-                if (apq == 0.0) continue;
-                const double theta = (A[q_ + (size_t)q_ * n] - A[p_ + (size_t)p_ * n]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-                for (int k = 0; k < n; ++k) {               // columns p, q
-                    const double akp = A[k + (size_t)p_ * n], akq = A[k + (size_t)q_ * n];
-                    A[k + (size_t)p_ * n] = c * akp - sn * akq;
-                    A[k + (size_t)q_ * n] = sn * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {               // rows p, q
-                    const double apk = A[p_ + (size_t)k * n], aqk = A[q_ + (size_t)k * n];
-                    A[p_ + (size_t)k * n] = c * apk - sn * aqk;
-                    A[q_ + (size_t)k * n] = sn * apk + c * aqk;
-                }
-            }
-    }
-    double m = A[0];
-    for (int i = 1; i < n; ++i) m = std::max(m, A[i + (size_t)i * n]);
-    return m;
-}
-
 int cfs_problem_create_from_weights(const cfs_problem_desc *desc, const cfs_cost_weights *w, cfs_problem **out)
 {
     if (!desc || !w || !out) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
@@ -418,64 +241,27 @@ int cfs_problem_create_from_weights(const cfs_problem_desc *desc, const cfs_cost
     if (nj < 2 || nj > 6 || H < 1 || H > CFS_MAX_H) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d / H %d unsupported", nj, H);
     const double dt = desc->robot.delta_t;
     if (!(dt > 0)) return cfs_fail(CFS_ERR_INVALID_ARG, "robot.delta_t must be positive");
-    const int ns = 2 * nj, nn = H * nj, nx = H * ns;
-    // Q = [Qp qc*I; qc*I Qv] (main_FANUC.m:65-77), Qaug = blkdiag(Q*w_stage, ..., Q*w_terminal) (:81-84)
-    std::vector<double> Q((size_t)ns * ns, 0.0), Qaug((size_t)nx * nx, 0.0);
-    for (int c = 0; c < nj; ++c)
-        for (int r = 0; r < nj; ++r) {
-            Q[r + (size_t)c * ns] = w->Qp[r + c * nj];
-            Q[(nj + r) + (size_t)(nj + c) * ns] = w->Qv[r + c * nj];
-            if (r == c) { Q[r + (size_t)(nj + c) * ns] = w->q_cross; Q[(nj + r) + (size_t)c * ns] = w->q_cross; }
-        }
-    for (int i = 0; i < H; ++i) {
-        const double wi = i == H - 1 ? w->w_terminal : w->w_stage;
-        for (int c = 0; c < ns; ++c)
-            for (int r = 0; r < ns; ++r) Qaug[(i * ns + r) + (size_t)(i * ns + c) * nx] = Q[r + (size_t)c * ns] * wi;
-    }
-    // T = Qaug*Baug (block rows), QQ = Baug'*T + cR*(R + R')  (:96-97); Baug(i,k) = [((i-k)+1/2) dt^2 I; dt I] for k <= i
-    std::vector<double> T((size_t)nx * nn, 0.0), QQ((size_t)nn * nn, 0.0);
-    for (int k = 0; k < H; ++k)
-        for (int c = 0; c < nj; ++c) {
-            const int col = k * nj + c;
-            for (int i = k; i < H; ++i) {
-                const double bp = ((double)(i - k) + 0.5) * dt * dt, bv = dt;
-                for (int r = 0; r < ns; ++r)
-                    T[(i * ns + r) + (size_t)col * nx] = Qaug[(i * ns + r) + (size_t)(i * ns + c) * nx] * bp + Qaug[(i * ns + r) + (size_t)(i * ns + nj + c) * nx] * bv;
-            }
-        }
-    for (int col = 0; col < nn; ++col)
-        for (int k = 0; k < H; ++k)
-            for (int c = 0; c < nj; ++c) {
-                double sacc = 0.0;
-                for (int i = k; i < H; ++i)
-                    sacc += (((double)(i - k) + 0.5) * dt * dt) * T[(i * ns + c) + (size_t)col * nx] + dt * T[(i * ns + nj + c) + (size_t)col * nx];
-                QQ[(k * nj + c) + (size_t)col * nn] = sacc;
-            }
+    WeightFamily wf;                         // Qaug, QQ, cR*(Rblk + Rblk') and alpha = 1/max(svd(QQ)) when the caller left it 0 (cfs_family.cpp)
+    family_from_weights(nj, H, dt, w, desc->alpha == 0.0 && desc->mode == CFS_MODE_PSGCFS, wf);
     DevCost hc;
     memset(&hc, 0, sizeof hc);
     for (int c = 0; c < nj; ++c)
         for (int r = 0; r < nj; ++r) {
             hc.Qp[r + c * nj] = w->Qp[r + c * nj];
             hc.Qv[r + c * nj] = w->Qv[r + c * nj];
-            hc.Rs[r + c * nj] = (w->Rblk[r + c * nj] + w->Rblk[c + r * nj]) * w->cR;
         }
+    memcpy(hc.Rs, wf.Rs, sizeof hc.Rs);
     hc.qc = w->q_cross; hc.ws = w->w_stage; hc.wt = w->w_terminal;
-    for (int i = 0; i < H; ++i)
-        for (int c = 0; c < nj; ++c)
-            for (int r = 0; r < nj; ++r) QQ[(i * nj + r) + (size_t)(i * nj + c) * nn] += hc.Rs[r + c * nj];
     cfs_problem_desc d2 = *desc;
-    d2.QQ = QQ.data();
+    d2.QQ = wf.QQ.data();
     d2.Aaug = d2.Baug = nullptr;                           // implied: the double integrator
-    if (d2.alpha == 0.0 && d2.mode == CFS_MODE_PSGCFS) {   // alpha = 1/max(svd(QQ))  (main_FANUC.m:120)
-        d2.alpha = 1.0 / sym_lambda_max(nn, symmetrise(nn, QQ.data()));
-    }
+    if (d2.alpha == 0.0 && d2.mode == CFS_MODE_PSGCFS) d2.alpha = wf.alpha;   // main_FANUC.m:120
     cfs_problem *p = nullptr;
     int rc = cfs_problem_create(&d2, &p);
     if (rc) return rc;
-    rc = cfs_set_state_cost(p, Qaug.data());
+    rc = cfs_set_state_cost(p, wf.Qaug.data());
     if (rc == CFS_SUCCESS) {
-        hipError_t e = p->cost.alloc(1);
-        if (e == hipSuccess) e = hipMemcpy(p->cost.p, &hc, sizeof hc, hipMemcpyHostToDevice);
+        const hipError_t e = p->cost.upload(&hc, 1);
         if (e != hipSuccess) rc = cfs_fail(CFS_ERR_HIP, "device setup failed: %s", hipGetErrorString(e));
     }
     if (rc) { cfs_problem_destroy(p); return rc; }
@@ -539,11 +325,11 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
 static LinMeshParams lin_mesh_params(const cfs_problem *p, int B)
 {
     LinMeshParams lm;
-    lm.rb = p->rb.p; lm.B = B; lm.H = p->d.H; lm.nmesh = p->nmesh; lm.meshes = p->meshes_d.p;
-    lm.mesh_pose = p->mesh_pose.p;
+    lm.rb = p->rb.p; lm.B = B; lm.H = p->d.H; lm.nmesh = p->nmesh; lm.meshes = p->mesh.meshes_d.p;
+    lm.mesh_pose = p->mm.mesh_pose.p;
     lm.dist = p->dist.p; lm.grad = p->grad.p;
-    lm.ends = p->m_ends.p; lm.base_d = p->m_base.p; lm.upper_d = p->m_upper.p; lm.base_t = p->m_tri.p; lm.shift_d = p->m_shift.p;
-    lm.near = p->m_near.p; lm.piece_d = p->m_pd.p; lm.piece_i = p->m_pi.p; lm.piece_nd = p->m_pnd.p;
+    lm.ends = p->mesh.m_ends.p; lm.base_d = p->mesh.m_base.p; lm.upper_d = p->mesh.m_upper.p; lm.base_t = p->mesh.m_tri.p; lm.shift_d = p->mesh.m_shift.p;
+    lm.near = p->mesh.m_near.p; lm.piece_d = p->mesh.m_pd.p; lm.piece_i = p->mesh.m_pi.p; lm.piece_nd = p->mesh.m_pnd.p;
     return lm;
 }
 
@@ -628,10 +414,10 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
         // launch is enqueued up front; finished problems return at once, so there is still no host round trip.
         LinMeshParams lm = lin_mesh_params(p, B);
         fp.nmesh = p->nmesh; fp.ext_dist = p->dist.p; fp.ext_grad = p->grad.p; fp.max_launch_iters = 1;
-        fp.st_qu = p->qu.p; fp.st_cost = p->st_cost.p; fp.st_noise = p->noise_row.p; fp.st_done = p->st_done.p;
+        fp.st_qu = p->qu.p; fp.st_cost = p->mesh.st_cost.p; fp.st_noise = p->noise_row.p; fp.st_done = p->mesh.st_done.p;
         for (int it = 0; it < std::max(K, 1); ++it) {
             lm.x_ = it == 0 ? in->x_init : out->x_;
-            lm.status_done = it == 0 ? nullptr : p->st_done.p;
+            lm.status_done = it == 0 ? nullptr : p->mesh.st_done.p;
             lm.seed_prev = it > 0;
             CFS_HIPCHK(launch_linearize_mesh(nj, lm, s));
             fp.resume = it > 0;
@@ -793,8 +579,7 @@ int cfs_debug_stamps(cfs_problem *p, int B, unsigned long long *out)
     p->stamps.release(); p->stamps_B = 0;
     if (B <= 0) return CFS_SUCCESS;
     if (B > p->d.max_batch) return cfs_fail(CFS_ERR_INVALID_ARG, "B=%d exceeds max_batch=%d", B, p->d.max_batch);
-    CFS_HIPCHK(p->stamps.alloc((size_t)B * 12));
-    CFS_HIPCHK(hipMemset(p->stamps.p, 0, (size_t)B * 12 * 8));
+    CFS_HIPCHK(p->stamps.zeros((size_t)B * 12));
     p->stamps_B = B;
     return CFS_SUCCESS;
 }
@@ -806,8 +591,7 @@ int cfs_debug_trace_begin(cfs_problem *p, int b, int cap)
     CFS_HIPCHK(hipDeviceSynchronize());
     p->trace.release(); p->trace_b = -1; p->trace_cap = 0;
     if (cap <= 0) return CFS_SUCCESS;
-    CFS_HIPCHK(p->trace.alloc((size_t)(cap + 1) * 8));
-    CFS_HIPCHK(hipMemset(p->trace.p, 0, (size_t)(cap + 1) * 8 * sizeof(double)));
+    CFS_HIPCHK(p->trace.zeros((size_t)(cap + 1) * 8));
     p->trace_b = b; p->trace_cap = cap;
     return CFS_SUCCESS;
 }
@@ -830,8 +614,7 @@ int cfs_debug_log_u(cfs_problem *p, int on)
     p->u_log.release();
     if (!on || p->d.MAX_O_ITER < 1) return CFS_SUCCESS;
     const size_t n = (size_t)p->d.max_batch * p->d.MAX_O_ITER * p->nn;
-    CFS_HIPCHK(p->u_log.alloc(n));
-    CFS_HIPCHK(hipMemset(p->u_log.p, 0, n * sizeof(double)));
+    CFS_HIPCHK(p->u_log.zeros(n));
     return CFS_SUCCESS;
 }
 
@@ -850,42 +633,9 @@ int cfs_set_state_cost(cfs_problem *p, const double *Qaug)
 {
     if (!p || !Qaug) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
     CFS_HIPCHK(hipSetDevice(p->device));
-    const int H = p->d.H, nj = p->d.njoint, ns = 2 * nj, nn = p->nn, nx = p->nx;
-    const double dt = p->d.robot.delta_t;
-    // E = [Aaug(:,1:nj), -G] (nx x 2nj): state error per unit of x0 / xg;  QE = Qaug*E;  F = Baug'*QE;  Cq = E'*QE
-    std::vector<long double> E((size_t)nx * 2 * nj, 0.0L), QE((size_t)nx * 2 * nj, 0.0L);
-    for (int i = 0; i < H; ++i)
-        for (int c = 0; c < nj; ++c) {
-            E[(i * ns + c) + (size_t)c * nx] = 1.0L;                      // A^i(1:nj,1:nj) = I  (x0 has zero velocity)
-            E[(i * ns + c) + (size_t)(nj + c) * nx] = -1.0L;              // -gaug
-        }
-    for (int col = 0; col < 2 * nj; ++col)
-        for (int r = 0; r < nx; ++r) {
-            long double s = 0.0L;
-            for (int k = 0; k < nx; ++k) s += (long double)Qaug[r + (size_t)k * nx] * E[k + (size_t)col * nx];
-            QE[r + (size_t)col * nx] = s;
-        }
-    std::vector<double> F1((size_t)nn * nj), F2((size_t)nn * nj), Cq((size_t)4 * nj * nj);
-    for (int col = 0; col < 2 * nj; ++col) {
-        for (int k = 0; k < H; ++k)
-            for (int c = 0; c < nj; ++c) {                              // row (k,c) of Baug': sum over waypoints i >= k
-                long double s = 0.0L;
-                for (int i = k; i < H; ++i)
-                    s += ((long double)(i - k) + 0.5L) * dt * dt * QE[(i * ns + c) + (size_t)col * nx] + (long double)dt * QE[(i * ns + nj + c) + (size_t)col * nx];
-                if (col < nj) F1[(k * nj + c) + (size_t)col * nn] = (double)s;
-                else F2[(k * nj + c) + (size_t)(col - nj) * nn] = (double)(-s);   // ff = F1*x0 - F2*xg
-            }
-        for (int r = 0; r < 2 * nj; ++r) {
-            long double s = 0.0L;
-            for (int k = 0; k < nx; ++k) s += E[k + (size_t)r * nx] * QE[k + (size_t)col * nx];
-            Cq[r + (size_t)col * 2 * nj] = (double)s;
-        }
-    }
-    p->F1.release(); p->F2.release(); p->Cq.release();
-    CFS_HIPCHK(p->F1.alloc(F1.size())); CFS_HIPCHK(p->F2.alloc(F2.size())); CFS_HIPCHK(p->Cq.alloc(Cq.size()));
-    CFS_HIPCHK(hipMemcpy(p->F1.p, F1.data(), F1.size() * 8, hipMemcpyHostToDevice));
-    CFS_HIPCHK(hipMemcpy(p->F2.p, F2.data(), F2.size() * 8, hipMemcpyHostToDevice));
-    CFS_HIPCHK(hipMemcpy(p->Cq.p, Cq.data(), Cq.size() * 8, hipMemcpyHostToDevice));
+    std::vector<double> F1, F2, Cq;
+    state_cost_terms(p->d.njoint, p->d.H, p->d.robot.delta_t, Qaug, F1, F2, Cq);
+    CFS_HIPCHK(p->F1.upload(F1.data(), F1.size())); CFS_HIPCHK(p->F2.upload(F2.data(), F2.size())); CFS_HIPCHK(p->Cq.upload(Cq.data(), Cq.size()));
     return CFS_SUCCESS;
 }
 
@@ -977,61 +727,21 @@ int cfs_problem_set_meshes(cfs_problem *p, int nmesh, const cfs_mesh *const *mes
         if (meshes[i]->device != p->device) return cfs_fail(CFS_ERR_INVALID_ARG, "meshes[%d] lives on device %d, the problem on %d", i, meshes[i]->device, p->device);
         v[i] = meshes[i]->view();
     }
-    p->meshes_d.release(); p->release_mesh_motion(); p->st_cost.release(); p->st_done.release();   // and the meshes are static again
-    p->meshes_h.clear(); p->mesh_frame.clear();
-    p->m_ends.release(); p->m_base.release(); p->m_shift.release(); p->m_tri.release(); p->m_near.release(); p->m_upper.release();
-    p->m_pd.release(); p->m_pnd.release(); p->m_pi.release(); p->release_clear_mesh();
+    p->mesh = MeshSet{}; p->reset_mesh_motion(); p->cm = ClearMeshWork{};   // the old set goes before the new one is allocated; the meshes are static again
     p->nmesh = 0;
     if (nmesh > 0) {
         size_t we, wb, ws, wn, wpd, wpi, wpn;
         linearize_mesh_workspace(p->d.njoint, nmesh, &we, &wb, &ws, &wn, &wpd, &wpi, &wpn);
         const size_t bh = (size_t)p->d.max_batch * p->d.H;
-        CFS_HIPCHK(p->m_ends.alloc(bh * we)); CFS_HIPCHK(p->m_base.alloc(bh * wb)); CFS_HIPCHK(p->m_upper.alloc(bh * wb)); CFS_HIPCHK(p->m_tri.alloc(bh * wb)); CFS_HIPCHK(p->m_shift.alloc(bh * ws)); CFS_HIPCHK(p->m_near.alloc(bh * wn));
-        CFS_HIPCHK(p->m_pd.alloc(bh * wpd)); CFS_HIPCHK(p->m_pi.alloc(bh * wpi)); CFS_HIPCHK(p->m_pnd.alloc(bh * wpn));
-        CFS_HIPCHK(p->meshes_d.alloc(nmesh));
-        CFS_HIPCHK(p->st_cost.alloc(2 * (size_t)p->d.max_batch));
-        CFS_HIPCHK(p->st_done.alloc(p->d.max_batch));
-        CFS_HIPCHK(hipMemcpy(p->meshes_d.p, v.data(), sizeof(DevMesh) * nmesh, hipMemcpyHostToDevice));
-        p->meshes_h = v;
+        CFS_HIPCHK(p->mesh.m_ends.alloc(bh * we)); CFS_HIPCHK(p->mesh.m_base.alloc(bh * wb)); CFS_HIPCHK(p->mesh.m_upper.alloc(bh * wb)); CFS_HIPCHK(p->mesh.m_tri.alloc(bh * wb)); CFS_HIPCHK(p->mesh.m_shift.alloc(bh * ws)); CFS_HIPCHK(p->mesh.m_near.alloc(bh * wn));
+        CFS_HIPCHK(p->mesh.m_pd.alloc(bh * wpd)); CFS_HIPCHK(p->mesh.m_pi.alloc(bh * wpi)); CFS_HIPCHK(p->mesh.m_pnd.alloc(bh * wpn));
+        CFS_HIPCHK(p->mesh.st_cost.alloc(2 * (size_t)p->d.max_batch));
+        CFS_HIPCHK(p->mesh.st_done.alloc(p->d.max_batch));
+        CFS_HIPCHK(p->mesh.meshes_d.upload(v.data(), nmesh));
+        p->mesh.meshes_h = v;
         p->nmesh = nmesh;
     }
     return CFS_SUCCESS;
-}
-
-// The H interval records (CLEAR_ITV doubles each, cfs_host.h) of one mesh for the audit between the waypoints, in double: T is its
-// H x 12 poses, frame = (c_j, r_j).  Interval i joins poses i-1 and i; interval 0 and an interval whose two poses are bitwise equal are
-// held.  The first interval that turns by more than a quarter (tr R_rel < 1) is reported in (turn_mesh, turn_wp): the audit refuses it.
-static void mesh_motion_intervals(const double *T, int H, double dt, const double *frame, double *itv, int jm, int &turn_mesh, int &turn_wp)
-{
-    for (int i = 0; i < H; ++i) {
-        double *q = itv + (size_t)i * CLEAR_ITV;
-        const double *T1 = T + (size_t)i * 12, *T0 = T + (size_t)(i > 0 ? i - 1 : 0) * 12;
-        for (int r = 0; r < 3; ++r) q[20 + r] = frame[r];
-        if (i == 0 || memcmp(T0, T1, 12 * sizeof(double)) == 0) continue;      // held: q[0] = 0, v_mesh = 0
-        double Rr[9], c0[3], c1[3];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) Rr[3 * r + c] = T1[4 * r] * T0[4 * c] + T1[4 * r + 1] * T0[4 * c + 1] + T1[4 * r + 2] * T0[4 * c + 2];
-        const double tr = Rr[0] + Rr[4] + Rr[8];
-        if (tr < 1.0) {
-            if (turn_mesh < 0) { turn_mesh = jm; turn_wp = i; }
-            continue;
-        }
-        const double w[3] = {(Rr[7] - Rr[5]) / 2.0, (Rr[2] - Rr[6]) / 2.0, (Rr[3] - Rr[1]) / 2.0};
-        const double nw = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), theta = std::atan2(nw, (tr - 1.0) / 2.0);
-        for (int r = 0; r < 3; ++r) {
-            c0[r] = T0[4 * r] * frame[0] + T0[4 * r + 1] * frame[1] + T0[4 * r + 2] * frame[2] + T0[4 * r + 3];
-            c1[r] = T1[4 * r] * frame[0] + T1[4 * r + 1] * frame[1] + T1[4 * r + 2] * frame[2] + T1[4 * r + 3];
-        }
-        const double dx = c1[0] - c0[0], dy = c1[1] - c0[1], dz = c1[2] - c0[2];
-        q[0] = 1.0;
-        for (int r = 0; r < 3; ++r) {
-            q[1 + r] = nw > 0.0 ? w[r] / nw : 0.0;
-            for (int c = 0; c < 3; ++c) q[5 + 3 * r + c] = T0[4 * r + c];
-            q[14 + r] = c0[r]; q[17 + r] = c1[r];
-        }
-        q[4] = theta;
-        q[23] = (theta * frame[3] + std::sqrt(dx * dx + dy * dy + dz * dz)) / dt;
-    }
 }
 
 int cfs_problem_set_mesh_motion(cfs_problem *p, const double *poses)
@@ -1041,69 +751,38 @@ int cfs_problem_set_mesh_motion(cfs_problem *p, const double *poses)
     CFS_HIPCHK(hipSetDevice(p->device));
     if (!poses) {
         CFS_HIPCHK(hipDeviceSynchronize());  // a solve in flight may still be reading the poses
-        p->release_mesh_motion();
+        p->reset_mesh_motion();
         return CFS_SUCCESS;
     }
-    // [R | t] -> [R' | -R't] in double: the kernels map link ends into the frame each mesh is stored in.  Only a rigid motion keeps
-    // the distances (and with them every bound, pruning radius and near-tie margin) of the stored mesh valid.
+    // [R | t] -> [R' | -R't]; only rigid motions are admitted (cfs_family.cpp)
     const size_t n = (size_t)p->nmesh * p->d.H;
-    std::vector<double> inv(n * 12);
-    for (size_t e = 0; e < n; ++e) {
-        const double *T = poses + e * 12;
-        const int jm = (int)(e / p->d.H), wp = (int)(e % p->d.H);
-        for (int q = 0; q < 12; ++q)
-            if (!std::isfinite(T[q])) return cfs_fail(CFS_ERR_INVALID_ARG, "pose of mesh %d at waypoint %d is not finite", jm, wp + 1);
-        double dev = 0.0;
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) {
-                const double g = T[4 * r] * T[4 * c] + T[4 * r + 1] * T[4 * c + 1] + T[4 * r + 2] * T[4 * c + 2];
-                dev = std::max(dev, std::fabs(g - (r == c ? 1.0 : 0.0)));
-            }
-        const double det = T[0] * (T[5] * T[10] - T[6] * T[9]) - T[1] * (T[4] * T[10] - T[6] * T[8]) + T[2] * (T[4] * T[9] - T[5] * T[8]);
-        if (dev > 1e-9 || !(det > 0.0))
-            return cfs_fail(CFS_ERR_INVALID_ARG, "pose of mesh %d at waypoint %d is not a rigid motion (max|RR' - I| = %.3g, det R = %.3g)",
-                            jm, wp + 1, dev, det);
-        double *o = inv.data() + e * 12;
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) o[4 * r + c] = T[4 * c + r];
-            o[4 * r + 3] = 0.0 - (T[r] * T[3] + T[4 + r] * T[7] + T[8 + r] * T[11]);   // 0 - x: +0 for the identity
-        }
-    }
+    std::vector<double> inv;
+    if (FamilyRefusal r = invert_mesh_poses(p->nmesh, p->d.H, poses, inv)) return cfs_fail(r.code, "%s", r.text);
     CFS_HIPCHK(hipDeviceSynchronize());
-    // what the audit between the waypoints needs per (mesh, interval) (cfs_clearance_mesh_motion, cfs_host.h CLEAR_ITV)
+    // what the audit between the waypoints needs per (mesh, interval) (cfs_clearance_mesh_motion, cfs_family.h CLEAR_ITV)
     std::vector<double> itv(n * CLEAR_ITV, 0.0);
     int turn_mesh = -1, turn_wp = 0;
-    if (p->mesh_frame.empty()) {             // c_j and r_j of the stored vertices, once per cfs_problem_set_meshes
+    if (p->mesh.mesh_frame.empty()) {             // c_j and r_j of the stored vertices, once per cfs_problem_set_meshes
         std::vector<double> frame(4 * (size_t)p->nmesh);
         for (int jm = 0; jm < p->nmesh; ++jm) {
-            const DevMesh &m = p->meshes_h[jm];
+            const DevMesh &m = p->mesh.meshes_h[jm];
             std::vector<double> tri(9 * (size_t)m.nt);
             CFS_HIPCHK(hipMemcpy(tri.data(), m.tri, tri.size() * sizeof(double), hipMemcpyDeviceToHost));
-            double *f = frame.data() + 4 * jm, r2 = 0.0;
-            for (int r = 0; r < 3; ++r) {
-                double lo = INFINITY, hi = -INFINITY;
-                for (size_t v = 0; v < 3 * (size_t)m.nt; ++v) { lo = std::min(lo, tri[3 * v + r]); hi = std::max(hi, tri[3 * v + r]); }
-                f[r] = (lo + hi) / 2.0;
-            }
-            for (size_t v = 0; v < 3 * (size_t)m.nt; ++v) {
-                const double x = tri[3 * v] - f[0], y = tri[3 * v + 1] - f[1], z = tri[3 * v + 2] - f[2];
-                r2 = std::max(r2, x * x + y * y + z * z);
-            }
-            f[3] = std::sqrt(r2);
+            mesh_frame(tri.data(), m.nt, frame.data() + 4 * jm);
         }
-        p->mesh_frame = frame;
+        p->mesh.mesh_frame = frame;
     }
     for (int jm = 0; jm < p->nmesh; ++jm)
-        mesh_motion_intervals(poses + (size_t)jm * p->d.H * 12, p->d.H, p->d.robot.delta_t, p->mesh_frame.data() + 4 * jm,
+        mesh_motion_intervals(poses + (size_t)jm * p->d.H * 12, p->d.H, p->d.robot.delta_t, p->mesh.mesh_frame.data() + 4 * jm,
                               itv.data() + (size_t)jm * p->d.H * CLEAR_ITV, jm, turn_mesh, turn_wp);
-    if (!p->mesh_pose.p) {
-        hipError_t e = p->mesh_pose.alloc(n * 12);
-        if (e == hipSuccess) e = p->mesh_itv.alloc(n * CLEAR_ITV);
-        if (e != hipSuccess) { p->release_mesh_motion(); return cfs_fail(CFS_ERR_HIP, "mesh poses: %s", hipGetErrorString(e)); }
+    if (!p->mm.mesh_pose.p) {
+        hipError_t e = p->mm.mesh_pose.alloc(n * 12);
+        if (e == hipSuccess) e = p->mm.mesh_itv.alloc(n * CLEAR_ITV);
+        if (e != hipSuccess) { p->reset_mesh_motion(); return cfs_fail(CFS_ERR_HIP, "mesh poses: %s", hipGetErrorString(e)); }
     }
-    CFS_HIPCHK(hipMemcpy(p->mesh_pose.p, inv.data(), n * 12 * sizeof(double), hipMemcpyHostToDevice));
-    CFS_HIPCHK(hipMemcpy(p->mesh_itv.p, itv.data(), itv.size() * sizeof(double), hipMemcpyHostToDevice));
-    p->turn_mesh = turn_mesh; p->turn_wp = turn_wp;
+    CFS_HIPCHK(hipMemcpy(p->mm.mesh_pose.p, inv.data(), n * 12 * sizeof(double), hipMemcpyHostToDevice));
+    CFS_HIPCHK(hipMemcpy(p->mm.mesh_itv.p, itv.data(), itv.size() * sizeof(double), hipMemcpyHostToDevice));
+    p->mm.turn_mesh = turn_mesh; p->mm.turn_wp = turn_wp;
     ++p->motion_gen;                         // the audit's pose table belongs to the poses before
     return CFS_SUCCESS;
 }
@@ -1161,10 +840,8 @@ int cfs_problem_set_infeasible_policy(cfs_problem *p, int policy, double weight)
     if (policy == CFS_INFEAS_SOFTEN && !p->soft_viol.p) {   // handle-owned result buffers, from the first SOFTEN on
         CFS_HIPCHK(hipSetDevice(p->device));
         const size_t nv = (size_t)p->d.max_batch * std::max(p->d.MAX_O_ITER, 1);
-        hipError_t e = p->soft_viol.alloc(nv);
-        if (e == hipSuccess) e = p->soft_n.alloc(p->d.max_batch);
-        if (e == hipSuccess) e = hipMemset(p->soft_viol.p, 0, nv * sizeof(double));
-        if (e == hipSuccess) e = hipMemset(p->soft_n.p, 0, (size_t)p->d.max_batch * sizeof(int));
+        hipError_t e = p->soft_viol.zeros(nv);
+        if (e == hipSuccess) e = p->soft_n.zeros(p->d.max_batch);
         if (e != hipSuccess) { p->soft_viol.release(); p->soft_n.release(); return cfs_fail(CFS_ERR_HIP, "soft result buffers: %s", hipGetErrorString(e)); }
     }
     p->soft_weight = weight;

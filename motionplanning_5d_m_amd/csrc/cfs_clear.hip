@@ -233,10 +233,10 @@ int cfs_check_clearance(const cfs_problem *p, int B, int substeps, const ClearAr
     if (mesh && p->nmesh < 1)
         return cfs_fail(CFS_ERR_INVALID_ARG, "%s needs a handle with mesh obstacles (cfs_problem_set_meshes): use cfs_clearance",
                         motion ? "cfs_clearance_mesh_motion" : "cfs_clearance_mesh");
-    if (mesh && motion && p->mesh_pose.p && p->turn_mesh >= 0)
+    if (mesh && motion && p->mm.mesh_pose.p && p->mm.turn_mesh >= 0)
         return cfs_fail(CFS_ERR_INVALID_ARG, "the poses of mesh %d at waypoints %d and %d are more than a quarter turn apart: the audit does not interpolate them",
-                        p->turn_mesh, p->turn_wp, p->turn_wp + 1);
-    if (mesh && !motion && p->mesh_pose.p) return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh audits static meshes (its bound takes v_obs = 0 in the mesh columns): this handle has mesh motion");
+                        p->mm.turn_mesh, p->mm.turn_wp, p->mm.turn_wp + 1);
+    if (mesh && !motion && p->mm.mesh_pose.p) return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_clearance_mesh audits static meshes (its bound takes v_obs = 0 in the mesh columns): this handle has mesh motion");
     if (!mesh && p->nmesh > 0) return cfs_fail(CFS_ERR_INVALID_ARG, "the clearance audit measures line obstacles only: this handle has %d mesh obstacles", p->nmesh);
     return CFS_SUCCESS;
 }

@@ -217,27 +217,26 @@ hipError_t launch_clearance_mesh_as(const ClearMeshParams &p, hipStream_t s)
 int clearance_mesh_enqueue(cfs_problem *p, int B, int substeps, const ClearArrays &a, const double *pose, const double *v_mesh, hipStream_t s)
 {
     const int nline = p->d.nobs - p->nmesh;
-    if (substeps > p->cm_S) {                        // grow the workspace (hipFree waits for whatever still reads the old one)
+    if (substeps > p->cm.S) {                        // grow the workspace (the old one is freed first, which waits for whatever still reads it)
         const size_t G = (size_t)p->d.H * substeps + 1, mb = (size_t)p->d.max_batch;
-        p->release_clear_mesh();
-        CFS_HIPCHK(p->cm_d.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm_L.alloc(mb * G));
-        CFS_HIPCHK(p->cm_lk.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm_tri.alloc(mb * G * p->nmesh));
-        CFS_HIPCHK(p->cm_seed.alloc(mb * (size_t)(p->d.H + 1) * p->d.njoint * p->nmesh));
-        CFS_HIPCHK(p->cm_rho.alloc(CFS_MAX_LINKS * CFS_MAX_LINKS));
-        CFS_HIPCHK(hipMemcpy(p->cm_rho.p, p->rho, sizeof p->rho, hipMemcpyHostToDevice));
-        p->cm_S = substeps;
+        p->cm = ClearMeshWork{};
+        CFS_HIPCHK(p->cm.cm_d.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm.cm_L.alloc(mb * G));
+        CFS_HIPCHK(p->cm.cm_lk.alloc(mb * G * p->nmesh)); CFS_HIPCHK(p->cm.cm_tri.alloc(mb * G * p->nmesh));
+        CFS_HIPCHK(p->cm.cm_seed.alloc(mb * (size_t)(p->d.H + 1) * p->d.njoint * p->nmesh));
+        CFS_HIPCHK(p->cm.cm_rho.upload(p->rho, CFS_MAX_LINKS * CFS_MAX_LINKS));
+        p->cm.S = substeps;
     }
     if (nline > 0) CFS_HIPCHK(cfs_launch_clearance_lines(p, B, substeps, nline, a, s));   // the line columns: cfs_clearance's kernel
     ClearMeshParams cm;
     cm.rb = p->rb.p; cm.B = B; cm.H = p->d.H; cm.nj = p->d.njoint; cm.nobs = p->d.nobs; cm.nmesh = p->nmesh; cm.S = substeps;
     cm.opt = ((p->dbg_mask & CFS_DBG_CLEAR_NO_BOUND) ? 0 : CLEAR_MESH_BOUND) | ((p->dbg_mask & CFS_DBG_CLEAR_SEED) ? CLEAR_MESH_SEED : 0);
     cm.dt = p->d.robot.delta_t;
-    cm.meshes = p->meshes_d.p;
+    cm.meshes = p->mesh.meshes_d.p;
     cm.x_ = a.x_; cm.u = a.u; cm.xR1 = a.xR1;
     cm.dist_wp = a.dist_wp; cm.dist_path = a.dist_path; cm.dist_lower = a.dist_lower; cm.t_path = a.t_path;
     cm.link_path = a.link_path; cm.tri_path = a.tri_path;
-    cm.ws_d = p->cm_d.p; cm.ws_L = p->cm_L.p; cm.ws_lk = p->cm_lk.p; cm.ws_tri = p->cm_tri.p; cm.ws_seed = p->cm_seed.p;
-    cm.rho = p->cm_rho.p;
+    cm.ws_d = p->cm.cm_d.p; cm.ws_L = p->cm.cm_L.p; cm.ws_lk = p->cm.cm_lk.p; cm.ws_tri = p->cm.cm_tri.p; cm.ws_seed = p->cm.cm_seed.p;
+    cm.rho = p->cm.cm_rho.p;
     cm.pose = pose; cm.v_mesh = v_mesh;
     CFS_HIPCHK(launch_clearance_mesh(cm, s));
     return CFS_SUCCESS;
@@ -285,19 +284,18 @@ extern "C" int cfs_clearance_mesh_motion_device(cfs_problem *p, int B, int subst
     if (rc) return rc;
     CFS_HIPCHK(hipSetDevice(p->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!p->mesh_pose.p) return clearance_mesh_enqueue(p, B, substeps, a, nullptr, nullptr, s);   // static meshes: the static path
-    if (substeps > p->cmm_cap) {                     // grow the table (hipFree waits for whatever still reads the old one)
-        p->cmm_pose.release(); p->cmm_v.release();
-        p->cmm_cap = 0; p->cmm_gen = -1;
-        CFS_HIPCHK(p->cmm_pose.alloc((size_t)p->nmesh * ((size_t)p->d.H * substeps + 1) * 12));
-        CFS_HIPCHK(p->cmm_v.alloc((size_t)p->nmesh * p->d.H));
-        p->cmm_cap = substeps;
+    if (!p->mm.mesh_pose.p) return clearance_mesh_enqueue(p, B, substeps, a, nullptr, nullptr, s);   // static meshes: the static path
+    if (substeps > p->mm.cmm_cap) {                     // grow the table (alloc frees the old one first, which waits for whatever still reads it)
+        p->mm.cmm_cap = 0; p->mm.cmm_gen = -1;
+        CFS_HIPCHK(p->mm.cmm_pose.alloc((size_t)p->nmesh * ((size_t)p->d.H * substeps + 1) * 12));
+        CFS_HIPCHK(p->mm.cmm_v.alloc((size_t)p->nmesh * p->d.H));
+        p->mm.cmm_cap = substeps;
     }
-    if (p->cmm_S != substeps || p->cmm_gen != p->motion_gen) {   // the table of another S or of other poses: rebuild it, ahead of the audit on its stream
-        CFS_HIPCHK(launch_clear_mesh_poses(p->nmesh, p->d.H, substeps, p->mesh_itv.p, p->mesh_pose.p, p->cmm_pose.p, p->cmm_v.p, s));
-        p->cmm_S = substeps; p->cmm_gen = p->motion_gen;
+    if (p->mm.cmm_S != substeps || p->mm.cmm_gen != p->motion_gen) {   // the table of another S or of other poses: rebuild it, ahead of the audit on its stream
+        CFS_HIPCHK(launch_clear_mesh_poses(p->nmesh, p->d.H, substeps, p->mm.mesh_itv.p, p->mm.mesh_pose.p, p->mm.cmm_pose.p, p->mm.cmm_v.p, s));
+        p->mm.cmm_S = substeps; p->mm.cmm_gen = p->motion_gen;
     }
-    return clearance_mesh_enqueue(p, B, substeps, a, p->cmm_pose.p, p->cmm_v.p, s);
+    return clearance_mesh_enqueue(p, B, substeps, a, p->mm.cmm_pose.p, p->mm.cmm_v.p, s);
 }
 
 extern "C" int cfs_clearance_mesh_motion(cfs_problem *p, int B, int substeps, const double *x_, const double *u, const double *xR1,

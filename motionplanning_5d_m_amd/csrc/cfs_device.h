@@ -186,11 +186,6 @@ template <FusedTier T> bool fused_fits_tier(int nj, int H, int nobs, bool move =
 hipError_t launch_fused(int nj, FusedParams p, hipStream_t s, bool force_w1 = false, bool analytic = false, const SoftParams *soft = nullptr,
                         bool move = false, bool lim = false);
 bool fused_fits(int nj, int H, int nobs);
-// does the per-waypoint plan fit every tier the static one fits for this mode (same tier, hence the same arithmetic)?  lim: the
-// plan with joint limits as well
-bool fused_fits_move(int nj, int H, int nobs, int mode, bool lim = false);
-// does the plan with joint limits (and per-waypoint obstacles when move) fit every tier the plain static plan fits for this mode?
-bool fused_fits_lim(int nj, int H, int nobs, int mode, bool move);
 
 struct CostHistParams {          // EVAL.get_cost / store_result for a logged u history (CFS mode)
     int B, nn, max_o_iter;

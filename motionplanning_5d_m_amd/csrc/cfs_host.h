@@ -1,6 +1,7 @@
 // cfs_host.h -- host-side helpers shared by the translation units of libcfs_hip.so (not part of the C ABI).
 #pragma once
 #include "cfs_device.h"
+#include "cfs_family.h"                                  // CLEAR_ITV, the record cfs_clear_mesh.hip reads
 #include <type_traits>
 #include <vector>
 
@@ -31,16 +32,40 @@ template <class F> hipError_t cfs_for_nj(int nj, F &&f)
     }
 }
 
+// a device array that a handle owns: freed by release(), by the next alloc() and by the destructor; movable, not copyable
 template <class T>
-struct DevBuf {                  // a device array that a handle owns
+struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
-    hipError_t alloc(size_t count)
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
     {
+        if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t count)                       // the old block goes first (hipFree waits for whatever still reads it)
+    {
+        release();
         n = count;
         return hipMalloc(reinterpret_cast<void **>(&p), (count ? count : 1) * sizeof(T));
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
+    hipError_t upload(const T *h, size_t count)          // alloc + copy of count elements from the host
+    {
+        hipError_t e = alloc(count);
+        if (e == hipSuccess && count) e = hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
+    hipError_t zeros(size_t count)                       // alloc + zero fill
+    {
+        hipError_t e = alloc(count);
+        if (e == hipSuccess && count) e = hipMemset(p, 0, count * sizeof(T));
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
 };
 
 // device staging of host arrays for the host-pointer entry points: the first error sticks and turns every later call into a no-op,
@@ -95,12 +120,12 @@ struct DevMesh {                 // device view of one mesh
 struct cfs_mesh {
     int device = 0, nt = 0, nnodes = 0, depth = 0;
     double bbox[6] = {0, 0, 0, 0, 0, 0};
-    BvhNode *nodes_d = nullptr;
-    double *tri_d = nullptr;
-    int *orig_d = nullptr;
-    int *cut_d = nullptr;        // ncut node indices, then ncut_tri triangle indices
+    DevBuf<BvhNode> nodes;
+    DevBuf<double> tri;
+    DevBuf<int> orig;
+    DevBuf<int> cut;             // ncut node indices, then ncut_tri triangle indices
     int ncut = 0, ncut_tri = 0;
-    DevMesh view() const { return DevMesh{nodes_d, tri_d, orig_d, nnodes, nt, cut_d, cut_d + ncut, ncut, ncut_tri}; }
+    DevMesh view() const { return DevMesh{nodes.p, tri.p, orig.p, nnodes, nt, cut.p, cut.p + ncut, ncut, ncut_tri}; }
 };
 
 struct LinMeshParams {           // distance + literal finite-difference Jacobian against mesh obstacles
@@ -149,10 +174,6 @@ struct ClearMeshParams {
     const double *v_mesh;                                // nmesh x H: bound of the surface speed of a mesh in an interval
 };
 hipError_t launch_clearance_mesh(const ClearMeshParams &p, hipStream_t s);
-// One record per (mesh, interval) of a handle with mesh motion, derived on the host in double (cfs_problem_set_mesh_motion):
-// [0] 1: the interval is interpolated, 0: the stored pose of its waypoint is held over it (interval 0, bitwise equal poses);
-// [1..3] axis a, [4] theta, [5..13] R_{i-1} row-major, [14..16] c_w(0), [17..19] c_w(1), [20..22] c_j, [23] v_mesh
-constexpr int CLEAR_ITV = 24;
 // writes the pose table of S sub-steps: out_pose nmesh x (H*S + 1) x 12, out_v nmesh x H; inv: the stored inverse poses, nmesh x H x 12
 hipError_t launch_clear_mesh_poses(int nmesh, int H, int S, const double *itv, const double *inv, double *out_pose, double *out_v, hipStream_t s);
 

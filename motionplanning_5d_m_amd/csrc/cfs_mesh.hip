@@ -663,12 +663,9 @@ int upload_mesh(const std::vector<double> &tri9, cfs_mesh **out)
     m->nt = nt; m->nnodes = (int)bd.nodes.size(); m->depth = bd.depth;
     for (int r = 0; r < 3; ++r) { m->bbox[r] = rlo[r]; m->bbox[3 + r] = rhi[r]; }
     hipError_t e = hipSetDevice(m->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->nodes_d), bd.nodes.size() * sizeof(BvhNode));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->tri_d), tri_o.size() * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->orig_d), (size_t)nt * 4);
-    if (e == hipSuccess) e = hipMemcpy(m->nodes_d, bd.nodes.data(), bd.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->tri_d, tri_o.data(), tri_o.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->orig_d, bd.order.data(), (size_t)nt * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = m->nodes.upload(bd.nodes.data(), bd.nodes.size());
+    if (e == hipSuccess) e = m->tri.upload(tri_o.data(), tri_o.size());
+    if (e == hipSuccess) e = m->orig.upload(bd.order.data(), (size_t)nt);
     // the cut a cooperative traversal starts from: open the hierarchy level by level while the inner nodes fit a wavefront
     std::vector<int> cut{0}, cut_tri;
     while (!cut.empty() && cut.size() <= 32) {
@@ -683,8 +680,7 @@ int upload_mesh(const std::vector<double> &tri9, cfs_mesh **out)
     }
     m->ncut = (int)cut.size(); m->ncut_tri = (int)cut_tri.size();
     cut.insert(cut.end(), cut_tri.begin(), cut_tri.end());
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->cut_d), (cut.size() + 1) * 4);
-    if (e == hipSuccess && !cut.empty()) e = hipMemcpy(m->cut_d, cut.data(), cut.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = m->cut.upload(cut.data(), cut.size());
     if (e != hipSuccess) {
         const int rc = cfs_fail(cfs_device_count() > 0 ? CFS_ERR_HIP : CFS_ERR_NO_DEVICE, "mesh upload failed: %s", hipGetErrorString(e));
         cfs_mesh_destroy(m);
@@ -804,10 +800,6 @@ int cfs_mesh_info(const cfs_mesh *m, int *ntri, int *nnodes, int *depth, double 
 void cfs_mesh_destroy(cfs_mesh *m)
 {
     if (!m) return;
-    if (m->nodes_d) (void)hipFree(m->nodes_d);
-    if (m->tri_d) (void)hipFree(m->tri_d);
-    if (m->orig_d) (void)hipFree(m->orig_d);
-    if (m->cut_d) (void)hipFree(m->cut_d);
     delete m;
 }
 

@@ -3,6 +3,27 @@
 #pragma once
 #include "cfs_host.h"
 
+// State of the handle that is reset as a whole: resetting one is assigning a fresh one (the buffers free what they held).
+struct MeshSet {                          // cfs_problem_set_meshes: the meshes and the workspace of their linearisation
+    DevBuf<DevMesh> meshes_d;
+    std::vector<DevMesh> meshes_h;        // host copy of meshes_d (the stored triangles give c_j and r_j)
+    std::vector<double> mesh_frame;       // nmesh x 4: (c_j, r_j), filled by the first cfs_problem_set_mesh_motion after set_meshes
+    DevBuf<double> st_cost, m_ends, m_base, m_shift, m_upper, m_pd, m_pnd;
+    DevBuf<int> st_done, m_tri, m_near, m_pi;
+};
+struct MeshMotion {                       // cfs_problem_set_mesh_motion, and what cfs_clearance_mesh_motion* keeps of it
+    DevBuf<double> mesh_pose;             // nmesh x H x 12 inverse poses (null: the meshes are static)
+    DevBuf<double> mesh_itv;              // per (mesh, interval), CLEAR_ITV doubles each
+    DevBuf<double> cmm_pose, cmm_v;       // the pose table of the last audit, kept per (sub-steps, motion generation): rebuilt only when either changes
+    int cmm_S = 0, cmm_cap = 0, cmm_gen = -1;
+    int turn_mesh = -1, turn_wp = 0;      // first (mesh, waypoint) whose pose is more than a quarter turn from the one before; -1: none
+};
+struct ClearMeshWork {                    // cfs_clearance_mesh*: per-sample workspace for S sub-steps (grown by the first audit that needs more) and rho on the device
+    DevBuf<double> cm_d, cm_L, cm_rho;
+    DevBuf<int> cm_lk, cm_tri, cm_seed;
+    int S = 0;
+};
+
 struct cfs_problem {
     cfs_problem_desc d;
     int device;
@@ -25,21 +46,10 @@ struct cfs_problem {
     int order_mode = 0, order_n = 0;   // 0 automatic, 1 given (order_n entries), 2 identity
     // mesh obstacles (cfs_problem_set_meshes): the last nmesh of the nobs obstacles
     int nmesh = 0;
-    DevBuf<DevMesh> meshes_d;
-    DevBuf<double> mesh_pose;    // cfs_problem_set_mesh_motion: nmesh x H x 12 inverse poses (null: the meshes are static)
-    DevBuf<double> st_cost, m_ends, m_base, m_shift, m_upper, m_pd, m_pnd;
-    DevBuf<int> st_done, m_tri, m_near, m_pi;
-    // cfs_clearance_mesh*: per-sample workspace for cm_S sub-steps (grown by the first audit that needs more) and rho on the device
-    DevBuf<double> cm_d, cm_L, cm_rho;
-    DevBuf<int> cm_lk, cm_tri, cm_seed;
-    int cm_S = 0;
-    // cfs_clearance_mesh_motion*: what cfs_problem_set_mesh_motion derives per (mesh, interval) (CLEAR_ITV doubles each), and the pose
-    // table of the last audit, kept per (sub-steps, motion generation): rebuilt only when either changes
-    DevBuf<double> mesh_itv, cmm_pose, cmm_v;
-    std::vector<DevMesh> meshes_h;        // host copy of meshes_d (the stored triangles give c_j and r_j)
-    std::vector<double> mesh_frame;       // nmesh x 4: (c_j, r_j), filled by the first cfs_problem_set_mesh_motion after set_meshes
-    int motion_gen = 0, cmm_S = 0, cmm_cap = 0, cmm_gen = -1;
-    int turn_mesh = -1, turn_wp = 0;      // first (mesh, waypoint) whose pose is more than a quarter turn from the one before; -1: none
+    MeshSet mesh;
+    MeshMotion mm;
+    int motion_gen = 0;                   // counts every change of the poses, across resets of mm: the pose table of mm.cmm_gen is rebuilt when they differ
+    ClearMeshWork cm;
     // developer / test switches (cfs_debug_*, include/cfs_hip.h): per handle, no process-wide state
     int dbg_mask = 0, dbg_warm_max = 0;
     double dbg_polish_tol = 1e-11;        // = the constraint scan's own feasibility tolerance
@@ -60,31 +70,11 @@ struct cfs_problem {
     bool prof = false;
     std::vector<hipEvent_t> ev;   // 4 per profiled solve: gemm start/stop, fused start/stop
     std::vector<hipEvent_t> ev_free;   // recycled events: none is created inside a timed region once the pool is warm
-    void release_clear_mesh()
-    {
-        cm_d.release(); cm_L.release(); cm_rho.release(); cm_lk.release(); cm_tri.release(); cm_seed.release();
-        cm_S = 0;
-    }
-    void release_mesh_motion()            // the handle's meshes are static again
-    {
-        mesh_pose.release(); mesh_itv.release(); cmm_pose.release(); cmm_v.release();
-        cmm_S = cmm_cap = 0; cmm_gen = -1; turn_mesh = -1;
-        ++motion_gen;
-    }
-    void release_all()
+    void reset_mesh_motion() { mm = MeshMotion{}; ++motion_gen; }   // the handle's meshes are static again
+    ~cfs_problem()                        // the caller has selected `device`; the buffers free themselves
     {
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_free) (void)hipEventDestroy(e);
-        ev.clear(); ev_free.clear();
-        rb.release(); QQ.release(); Hinv.release(); Hq.release();
-        M1n.release(); M2n.release(); Pt.release(); u_hist.release(); qu_hist.release();
-        F1.release(); F2.release(); Cq.release(); cost.release();
-        lim.release(); maxin.release(); margin.release(); x0.release(); qu.release(); dist.release();
-        grad.release(); Yg.release(); noise_row.release(); order.release(); okey.release(); order_user.release();
-        linkid.release(); pool_flag.release(); meshes_d.release(); release_mesh_motion(); st_cost.release(); st_done.release();
-        m_ends.release(); m_base.release(); m_shift.release(); m_tri.release(); m_near.release(); m_upper.release();
-        m_pd.release(); m_pnd.release(); m_pi.release(); release_clear_mesh();
-        stamps.release(); trace.release(); u_log.release(); soft_viol.release(); soft_n.release();
     }
 };
 

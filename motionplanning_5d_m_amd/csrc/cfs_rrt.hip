@@ -316,7 +316,7 @@ int cfs_check_mesh_table(int nobs, int nmesh, const cfs_mesh *const *meshes, con
     for (int j = 0; j < nmesh; ++j) {
         if (meshes[j]->device != cfs_current_device())
             return cfs_fail(CFS_ERR_INVALID_ARG, "mesh %d lives on device %d, the current device is %d", j, meshes[j]->device, cfs_current_device());
-        ma.m[j].nodes = meshes[j]->nodes_d; ma.m[j].tri = meshes[j]->tri_d; ma.m[j].nt = meshes[j]->nt;
+        ma.m[j].nodes = meshes[j]->nodes.p; ma.m[j].tri = meshes[j]->tri.p; ma.m[j].nt = meshes[j]->nt;
         ma.m[j].thr = D_mesh[j] > 0.0001 ? D_mesh[j] : 0.0001;                         // dist_arm_surf_200i.m:22-24 folded into the threshold
     }
     ma.nmesh = nmesh;

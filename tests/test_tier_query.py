@@ -122,7 +122,7 @@ def test_bad_arguments_are_refused_and_nothing_is_written():
 
 
 def test_per_waypoint_and_limited_handles_run_the_static_tier_or_are_refused():
-    """the rule of fused_fits_move / fused_fits_lim: a variant handle never changes the tier of its shape"""
+    """the rule of fused_keeps_tier: a variant handle never changes the tier of its shape"""
     refused = same = 0
     for (nj, H, nobs), mode in itertools.product(_sweep(), MODES):
         plain = _tier_or_none(nj, H, nobs, mode)
