@@ -846,6 +846,61 @@ int cfs_cart_path_mesh_device(const cfs_cart_desc *d, int nmesh, const cfs_mesh 
                               int flags, int T, const double *start, const int *start_state, const double *target_pos,
                               const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream);
 
+/* ---- Tool paths --------------------------------------------------------------------------------------------
+ * "Cartesian paths" above moves the tool along one straight line; these entries move it along a polyline of M tool poses (a chain of
+ * straight moves: a bead, a seam, "down - across - up").  For T targets at once, and for up to 64 start configurations per target (the
+ * candidates: cfs_ik_out.cand_theta with cand_status of an inverse-kinematics call at the first pose is accepted as it is), they follow
+ * the target's whole polyline from every start and keep, per target, the start nearest to a reference configuration whose path
+ * completes inside the joint limits, without a joint jump and free of the line obstacles.  No handle.  cfs_cart_desc and cfs_cart_out
+ * are unchanged, with these meanings: d->steps = K is the number of sub-steps per segment, npts = M the number of poses of the
+ * polyline; a path has N = (M-1)*K + 1 rows, and every "steps+1" in cfs_cart_out reads N.  path_pos: T x M x 3, the points P_0..P_{M-1}
+ * of every target; path_axis: T x M x 3, the tool directions A_0..A_{M-1}, read when use_axis = 1 (may be NULL otherwise); every row
+ * is normalised where it is read, as target_axis is above.
+ * The contract is "Cartesian paths" word for word -- pose, residual, Jacobian, steps 1-8, the collision rule (clearance < 0) and the
+ * cost are those of "inverse kinematics" --, with these changes.
+ *   Rows.  Row 0 is (P_0, A_0).  Row n >= 1 lies on segment i = (n-1) div K, with k = n - i*K and s = k/K: its point is
+ *     p_n = P_i + s*(P_{i+1} - P_i), its axis (use_axis = 1) a_n = b/|b|, b = (1-s)*A_i + s*A_{i+1}; |b| <= 1e-6 (or not finite):
+ *     state 3, end.  Two consecutive axes that are opposite therefore end a candidate at the middle of that segment (or, for odd K,
+ *     not at all: no row lies there).  A segment of length zero is followed like any other.
+ *   No start (state 5): as in cfs_cart_path.
+ *   Every row n = 0..N-1, row 0 included: steps 1-8 of "inverse kinematics" towards (p_n, a_n), with lambda = 1e-2 and it = 0,
+ *     starting at the configuration before it, theta_{n-1} (for row 0: the start).  Convergence is tested before every step, so a start
+ *     that solves (P_0, A_0) costs 0 iterations and row 0 of its path is then the start, bit for bit.
+ *     step 3 (it == max_iter): state 1, end;  step 1 or 4 failing: state 3, end;
+ *     otherwise theta_n = the converged configuration; max_c |theta_n,c - theta_{n-1},c| > max_joint_step: state 4, end -- ROW 0 IS
+ *     TESTED AGAINST THE START, so a start far from the first pose is a joint jump;
+ *     otherwise theta_n collides: state 2, end;  otherwise row n is accepted.
+ *   Row N-1 accepted: state 0.
+ * States of a candidate: those of cfs_cart_path (0 complete | 1 a row did not converge | 2 collision | 3 numeric | 4 joint jump | 5 no
+ * start).  cand_done, cand_end, cand_iter and cand_path keep cfs_cart_path's conventions exactly, with K replaced by N-1: cand_done =
+ * the index of the last accepted row, 0 when none was accepted; cand_iter = the iterations summed over the rows, row 0's included;
+ * cand_end = the last configuration reached or tried (NaN in state 5); cand_path = the accepted configurations theta_0..theta_cand_done
+ * and NaN in every later row (every row when none was accepted).
+ * The cost, the selection, theta (the winner's START, not row 0 of its path), status, selected, n_ok, n_done, path and clearance (the
+ * minimum over the winner's N configurations) are cfs_cart_path's.  The collision rule is evaluated at the N configurations, not
+ * between them.  A target's results depend on neither T nor its position in the batch.
+ * cfs_cart_follow_mesh*: rules 1-6 of "Cartesian paths against mesh obstacles" applied to the line-only answer of cfs_cart_follow on
+ * the same inputs, with K+1 read as N; the mesh table, its flags and its refusals are those of cfs_cart_path_mesh*.
+ * CFS_ERR_INVALID_ARG, nothing written: everything cfs_cart_path* / cfs_cart_path_mesh* refuse about the shared fields (path_pos in
+ * the place of target_pos, path_axis in the place of target_axis), including, in the device entries, out->path without out->cand_path
+ * (cfs_cart_follow_device) and a NULL out->cand_path (cfs_cart_follow_mesh_device); npts outside 2..257; (npts-1)*steps > 256; a NULL
+ * path_pos; use_axis = 1 with a NULL path_axis; in the host entries, whose arrays the host can read: a non-finite path_pos or
+ * path_axis, a zero path_axis row (start is NOT checked: a bad start is state 5).
+ * cfs_cart_follow / cfs_cart_follow_mesh: HOST pointers throughout, synchronise.  The _device entries: lo, hi, weight (and D_mesh) stay
+ * HOST pointers; obs, D, start, start_state, path_pos, path_axis, theta_ref and every array of `out` are DEVICE pointers; enqueued on
+ * `stream`, no synchronisation.  A non-finite value in a device array ends the candidates that read it in state 3 (start: state 5). */
+/* start: T x candidates x njoint; start_state: T x candidates or NULL; path_pos, path_axis: T x npts x 3; theta_ref: T x njoint */
+int cfs_cart_follow(const cfs_cart_desc *d, int T, int npts, const double *start, const int *start_state, const double *path_pos,
+                    const double *path_axis, const double *theta_ref, const cfs_cart_out *out);
+int cfs_cart_follow_device(const cfs_cart_desc *d, int T, int npts, const double *start, const int *start_state, const double *path_pos,
+                           const double *path_axis, const double *theta_ref, const cfs_cart_out *out, void *stream);
+int cfs_cart_follow_mesh(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T, int npts,
+                         const double *start, const int *start_state, const double *path_pos, const double *path_axis,
+                         const double *theta_ref, const cfs_cart_out *out);
+int cfs_cart_follow_mesh_device(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh /* HOST, nmesh */,
+                                int flags, int T, int npts, const double *start, const int *start_state, const double *path_pos,
+                                const double *path_axis, const double *theta_ref, const cfs_cart_out *out, void *stream);
+
 /* ---- developer / test entry points -------------------------------------------------------------------
  * No caller of the path needs these; they exist so that every shortcut the solver takes can be switched off and compared
  * under pytest (tests/test_gpu_shortcuts.py), and for the cycle-stamp / step-trace probes under tools/.  All state is per

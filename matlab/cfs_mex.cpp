@@ -53,6 +53,13 @@
 //        'cart_path' in a cell that ends with mesh obstacles (obs{j}.mesh, obs{j}.D), received as 'ik_mesh' receives them:
 //        cfs_cart_path_mesh.  A line also ends at the first configuration whose link axes come closer to mesh j than max(D_j, 1e-4);
 //        clearance counts the meshes
+//   [theta, status, path, clearance, selected, n_ok, n_done] = cfs_mex('cart_follow', obs, robot, ROBOT, start, start_state, path_pos, path_axis, theta_ref, opts)
+//        polylines of tool poses from IK candidates (cfs_cart_follow, include/cfs_hip.h "Tool paths"): the arguments, options and
+//        outputs of 'cart_path', parsed by the same code, with path_pos 3 x M x T (or 3 x (M*T)) and path_axis the same shape or [] in
+//        the place of the target; opts.steps (16) is the number of sub-steps per segment, so a path has N = (M-1)*steps + 1 <= 257 rows
+//        and path is njoint x (N*T) (reshape(path, njoint, N, T)).  Row 1 of a path is a pose to reach, not the start: theta is the start
+//   [theta, status, path, clearance, selected, n_ok, n_done] = cfs_mex('cart_follow_mesh', obs, robot, ROBOT, start, start_state, path_pos, path_axis, theta_ref, opts)
+//        'cart_follow' in a cell that ends with mesh obstacles, received as 'cart_path_mesh' receives them: cfs_cart_follow_mesh
 //   Cost_b = cfs_mex('cost_b', sys_info, ROBOT)                    % EVAL.get_Cost_b (Lib/EVAL.m:75-78, main_FANUC.m:131-132)
 //   h = cfs_mex('mesh_load_stl', path, scale, map_from_stl)        % Lib/functions/MapFromSTL.m
 //   [dis, points] = cfs_mex('mesh_segment_distance', h, seg6)      % point2surface_dis (M200i/dist_arm_surf_200i.m:21)
@@ -552,16 +559,21 @@ static void ik_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
 }
 
 // Cost_b = EVAL(sys_info).get_Cost_b()  (Lib/EVAL.m:75-78)
-// straight tool lines from IK candidates (cfs_cart_path): the approach move of a pick, which the reference's drivers do not have
-static void cart_path(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+// straight tool lines from IK candidates (cfs_cart_path): the approach move of a pick, which the reference's drivers do not have.
+// follow: the verb 'cart_follow' (cfs_cart_follow), polylines of tool poses through the same arguments
+static void cart_path(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[], bool follow = false)
 {
     if (nrhs < 9) mexErrMsgTxt("[theta, status, path, clearance, selected, n_ok, n_done] = cfs_mex('cart_path', obs, robot, ROBOT, start, start_state, target_pos, target_axis, theta_ref [, opts])");
     const mxArray *obs = prhs[1], *robot = prhs[2], *opts = nrhs > 9 ? prhs[9] : nullptr;
     const std::string ROBOT = mxArrayToString(prhs[3]);
-    const int nj = (int)mxGetM(prhs[8]), T = (int)mxGetN(prhs[6]);
-    if (mxGetM(prhs[6]) != 3 || (int)mxGetN(prhs[8]) != T || T < 1) mexErrMsgTxt("target_pos must be 3 x T and theta_ref njoint x T");
+    // follow: target_pos / target_axis are the polylines path_pos / path_axis, 3 x M x T (mxGetN of it is M*T), and T is theta_ref's
+    const int nj = (int)mxGetM(prhs[8]), T = (int)mxGetN(follow ? prhs[8] : prhs[6]);
+    const int M = T > 0 ? (int)(mxGetN(prhs[6]) / T) : 0;
+    if (mxGetM(prhs[6]) != 3 || (int)mxGetN(prhs[8]) != T || T < 1 || (int)mxGetN(prhs[6]) != M * T || (follow && M < 2))
+        mexErrMsgTxt(follow ? "path_pos must be 3 x M x T with M >= 2 and theta_ref njoint x T" : "target_pos must be 3 x T and theta_ref njoint x T");
     const bool use_axis = !mxIsEmpty(prhs[7]);
-    if (use_axis && (mxGetM(prhs[7]) != 3 || (int)mxGetN(prhs[7]) != T)) mexErrMsgTxt("target_axis must be 3 x T or []");
+    if (use_axis && (mxGetM(prhs[7]) != 3 || (int)mxGetN(prhs[7]) != M * T))
+        mexErrMsgTxt(follow ? "path_axis must be 3 x M x T or []" : "target_axis must be 3 x T or []");
     const int R = (int)(mxGetN(prhs[4]) / T);                                         // mxGetN of njoint x R x T is R*T
     if ((int)mxGetM(prhs[4]) != nj || R < 1 || (int)mxGetN(prhs[4]) != R * T) mexErrMsgTxt("start must be njoint x R x T");
     std::vector<int> state;
@@ -596,26 +608,34 @@ static void cart_path(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]
     d.max_joint_step = num("max_joint_step", 0.2);
     d.tol_pos = num("tol_pos", 1e-6); d.tol_axis = num("tol_axis", 1e-6);
     if (d.steps < 1 || d.steps > 256) mexErrMsgTxt("opts.steps must be in 1..256");
+    if (follow && (M - 1) * d.steps > 256) mexErrMsgTxt("(M-1)*opts.steps must be at most 256: the rows of a path after row 0");
+    const int rows = (follow ? (M - 1) * d.steps : d.steps) + 1;                       // of a path
     std::vector<double> obs6, D;
     const int ncell = (int)mxGetNumberOfElements(obs);
     for (int j = 0; j < ncell; ++j) {
         const mxArray *o = mxGetCell(obs, j), *fl = o ? mxGetField(o, 0, "l") : nullptr, *fD = o ? mxGetField(o, 0, "D") : nullptr;
-        if (o && mxGetField(o, 0, "mesh")) mexErrMsgTxt("'cart_path' reads line obstacles only: mesh obstacles are not supported");
+        if (o && mxGetField(o, 0, "mesh"))
+            mexErrMsgTxt(follow ? "'cart_follow' reads line obstacles only: use 'cart_follow_mesh' for a cell that ends with mesh obstacles"
+                                : "'cart_path' reads line obstacles only: mesh obstacles are not supported");
         if (!fl || !fD || mxGetNumberOfElements(fl) != 6) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .l (3x2) and .D", j + 1);
         obs6.insert(obs6.end(), mxGetPr(fl), mxGetPr(fl) + 6);
         D.push_back(mxGetScalar(fD));
     }
     d.nobs = (int)D.size(); d.obs = obs6.data(); d.D = D.data();
     mxArray *o_th = mxCreateDoubleMatrix(nj, T, mxREAL);                              // T x njoint row-major = njoint x T column-major
-    mxArray *o_path = mxCreateDoubleMatrix(nj, (size_t)(d.steps + 1) * T, mxREAL);    // T x (steps+1) x njoint row-major
+    mxArray *o_path = mxCreateDoubleMatrix(nj, (size_t)rows * T, mxREAL);             // T x rows x njoint row-major
     mxArray *o_cl = mxCreateDoubleMatrix(1, T, mxREAL);
     std::vector<int> status(T), selected(T), n_ok(T), n_done(T);
     cfs_cart_out o;
     memset(&o, 0, sizeof o);
     o.theta = mxGetPr(o_th); o.status = status.data(); o.path = mxGetPr(o_path); o.selected = selected.data(); o.n_ok = n_ok.data();
     o.n_done = n_done.data(); o.clearance = mxGetPr(o_cl);
-    check(cfs_cart_path(&d, T, mxGetPr(prhs[4]), state.empty() ? nullptr : state.data(), mxGetPr(prhs[6]), use_axis ? mxGetPr(prhs[7]) : nullptr,
-                        mxGetPr(prhs[8]), &o));
+    if (follow)
+        check(cfs_cart_follow(&d, T, M, mxGetPr(prhs[4]), state.empty() ? nullptr : state.data(), mxGetPr(prhs[6]),
+                              use_axis ? mxGetPr(prhs[7]) : nullptr, mxGetPr(prhs[8]), &o));
+    else
+        check(cfs_cart_path(&d, T, mxGetPr(prhs[4]), state.empty() ? nullptr : state.data(), mxGetPr(prhs[6]), use_axis ? mxGetPr(prhs[7]) : nullptr,
+                            mxGetPr(prhs[8]), &o));
     mxArray *o_i[4] = {mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL),
                        mxCreateDoubleMatrix(1, T, mxREAL)};
     for (int t = 0; t < T; ++t) {
@@ -626,15 +646,20 @@ static void cart_path(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]
 }
 
 // 'cart_path' in a cell that ends with mesh obstacles (cfs_cart_path_mesh): the same arguments and outputs, the obs cell as 'rrt' takes it
-static void cart_path_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+// follow: the verb 'cart_follow_mesh' (cfs_cart_follow_mesh)
+static void cart_path_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[], bool follow = false)
 {
     if (nrhs < 9) mexErrMsgTxt("[theta, status, path, clearance, selected, n_ok, n_done] = cfs_mex('cart_path_mesh', obs, robot, ROBOT, start, start_state, target_pos, target_axis, theta_ref [, opts])");
     const mxArray *obs = prhs[1], *robot = prhs[2], *opts = nrhs > 9 ? prhs[9] : nullptr;
     const std::string ROBOT = mxArrayToString(prhs[3]);
-    const int nj = (int)mxGetM(prhs[8]), T = (int)mxGetN(prhs[6]);
-    if (mxGetM(prhs[6]) != 3 || (int)mxGetN(prhs[8]) != T || T < 1) mexErrMsgTxt("target_pos must be 3 x T and theta_ref njoint x T");
+    // follow: target_pos / target_axis are the polylines path_pos / path_axis, 3 x M x T (mxGetN of it is M*T), and T is theta_ref's
+    const int nj = (int)mxGetM(prhs[8]), T = (int)mxGetN(follow ? prhs[8] : prhs[6]);
+    const int M = T > 0 ? (int)(mxGetN(prhs[6]) / T) : 0;
+    if (mxGetM(prhs[6]) != 3 || (int)mxGetN(prhs[8]) != T || T < 1 || (int)mxGetN(prhs[6]) != M * T || (follow && M < 2))
+        mexErrMsgTxt(follow ? "path_pos must be 3 x M x T with M >= 2 and theta_ref njoint x T" : "target_pos must be 3 x T and theta_ref njoint x T");
     const bool use_axis = !mxIsEmpty(prhs[7]);
-    if (use_axis && (mxGetM(prhs[7]) != 3 || (int)mxGetN(prhs[7]) != T)) mexErrMsgTxt("target_axis must be 3 x T or []");
+    if (use_axis && (mxGetM(prhs[7]) != 3 || (int)mxGetN(prhs[7]) != M * T))
+        mexErrMsgTxt(follow ? "path_axis must be 3 x M x T or []" : "target_axis must be 3 x T or []");
     const int R = (int)(mxGetN(prhs[4]) / T);                                         // mxGetN of njoint x R x T is R*T
     if ((int)mxGetM(prhs[4]) != nj || R < 1 || (int)mxGetN(prhs[4]) != R * T) mexErrMsgTxt("start must be njoint x R x T");
     std::vector<int> state;
@@ -669,6 +694,8 @@ static void cart_path_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *p
     d.max_joint_step = num("max_joint_step", 0.2);
     d.tol_pos = num("tol_pos", 1e-6); d.tol_axis = num("tol_axis", 1e-6);
     if (d.steps < 1 || d.steps > 256) mexErrMsgTxt("opts.steps must be in 1..256");
+    if (follow && (M - 1) * d.steps > 256) mexErrMsgTxt("(M-1)*opts.steps must be at most 256: the rows of a path after row 0");
+    const int rows = (follow ? (M - 1) * d.steps : d.steps) + 1;                       // of a path
     // line obstacles (.l, .D) first, then mesh obstacles (.mesh = a handle of cfs_mex('mesh_load_stl' ...), .D), as in 'rrt'
     std::vector<double> obs6, D, D_mesh;
     std::vector<const cfs_mesh *> meshes;
@@ -688,18 +715,25 @@ static void cart_path_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *p
         obs6.insert(obs6.end(), mxGetPr(fl), mxGetPr(fl) + 6);
         D.push_back(mxGetScalar(fD));
     }
-    if (meshes.empty()) mexErrMsgTxt("'cart_path_mesh' needs at least one mesh obstacle at the end of the obs cell: use 'cart_path' for line obstacles only");
+    if (meshes.empty())
+        mexErrMsgTxt(follow ? "'cart_follow_mesh' needs at least one mesh obstacle at the end of the obs cell: use 'cart_follow' for line obstacles only"
+                            : "'cart_path_mesh' needs at least one mesh obstacle at the end of the obs cell: use 'cart_path' for line obstacles only");
     d.nobs = (int)D.size(); d.obs = obs6.data(); d.D = D.data();
     mxArray *o_th = mxCreateDoubleMatrix(nj, T, mxREAL);                              // T x njoint row-major = njoint x T column-major
-    mxArray *o_path = mxCreateDoubleMatrix(nj, (size_t)(d.steps + 1) * T, mxREAL);    // T x (steps+1) x njoint row-major
+    mxArray *o_path = mxCreateDoubleMatrix(nj, (size_t)rows * T, mxREAL);             // T x rows x njoint row-major
     mxArray *o_cl = mxCreateDoubleMatrix(1, T, mxREAL);
     std::vector<int> status(T), selected(T), n_ok(T), n_done(T);
     cfs_cart_out o;
     memset(&o, 0, sizeof o);
     o.theta = mxGetPr(o_th); o.status = status.data(); o.path = mxGetPr(o_path); o.selected = selected.data(); o.n_ok = n_ok.data();
     o.n_done = n_done.data(); o.clearance = mxGetPr(o_cl);
-    check(cfs_cart_path_mesh(&d, (int)meshes.size(), meshes.data(), D_mesh.data(), 0, T, mxGetPr(prhs[4]), state.empty() ? nullptr : state.data(),
-                             mxGetPr(prhs[6]), use_axis ? mxGetPr(prhs[7]) : nullptr, mxGetPr(prhs[8]), &o));
+    if (follow)
+        check(cfs_cart_follow_mesh(&d, (int)meshes.size(), meshes.data(), D_mesh.data(), 0, T, M, mxGetPr(prhs[4]),
+                                   state.empty() ? nullptr : state.data(), mxGetPr(prhs[6]), use_axis ? mxGetPr(prhs[7]) : nullptr,
+                                   mxGetPr(prhs[8]), &o));
+    else
+        check(cfs_cart_path_mesh(&d, (int)meshes.size(), meshes.data(), D_mesh.data(), 0, T, mxGetPr(prhs[4]), state.empty() ? nullptr : state.data(),
+                                 mxGetPr(prhs[6]), use_axis ? mxGetPr(prhs[7]) : nullptr, mxGetPr(prhs[8]), &o));
     mxArray *o_i[4] = {mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL), mxCreateDoubleMatrix(1, T, mxREAL),
                        mxCreateDoubleMatrix(1, T, mxREAL)};
     for (int t = 0; t < T; ++t) {
@@ -758,6 +792,10 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         cart_path(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "cart_path_mesh") {
         cart_path_mesh(nlhs, plhs, nrhs, prhs);
+    } else if (cmd == "cart_follow") {
+        cart_path(nlhs, plhs, nrhs, prhs, true);
+    } else if (cmd == "cart_follow_mesh") {
+        cart_path_mesh(nlhs, plhs, nrhs, prhs, true);
     } else if (cmd == "cost_b") {
         cost_b(plhs, nrhs, prhs);
     } else if (cmd == "mesh_load_stl") {

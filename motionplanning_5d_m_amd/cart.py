@@ -73,8 +73,9 @@ class CartesianPath(_ToolSolver):
     def _mesh_table(self):
         return _args.mesh_table(self._meshes, self._D_mesh, 0 if self.mesh_variant is None else _lib.IK_MESH[self.mesh_variant])
 
-    def _shapes(self, T, R):
-        nj, K1 = self.nj, self.steps + 1
+    def _shapes(self, T, R, rows=None):
+        """rows: the rows of a path (default: a straight line's steps + 1)"""
+        nj, K1 = self.nj, self.steps + 1 if rows is None else rows
         f, i = np.float64, np.int32
         return dict(theta=((T, nj), f), status=((T,), i), path=((T, K1, nj), f), selected=((T,), i), n_ok=((T,), i), n_done=((T,), i),
                     clearance=((T,), f), cand_status=((T, R), i), cand_done=((T, R), i), cand_iter=((T, R), i), cand_end=((T, R, nj), f),
@@ -91,31 +92,12 @@ class CartesianPath(_ToolSolver):
         over the path's configurations); rows of unsolved targets hold NaN.  want_candidates: also cand_status (0 complete | 1 a
         step did not converge | 2 collision | 3 numeric | 4 joint jump | 5 no start), cand_done, cand_iter (T, R), cand_end
         (T, R, njoint) and cand_path (T, R, steps+1, njoint; NaN after cand_done)."""
-        nj = self.nj
-        try:
-            s = np.array(start, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError(f"start must be an array of shape (T, R, {nj}) or (R, {nj})") from None
-        if s.ndim == 2:
-            s = s[None]
-        if s.ndim != 3 or s.shape[2] != nj or s.shape[0] < 1 or not 1 <= s.shape[1] <= MAX_CANDIDATES:
-            raise ValueError(f"start must have shape (T, R, {nj}) with T >= 1 and R in 1..{MAX_CANDIDATES}, not {s.shape}")
+        s = self._starts(start)
         T, tp, ta, tr = self._targets(target_pos, target_axis, theta_ref)
         if s.shape[0] != T:
             raise ValueError(f"start has {s.shape[0]} targets, target_pos {T}")
         R = s.shape[1]
-        ss = None
-        if start_state is not None:
-            try:
-                ss = np.array(start_state)
-            except (TypeError, ValueError):
-                raise ValueError("start_state must be an integer array") from None
-            if ss.ndim == 1:
-                ss = ss[None]
-            if ss.dtype.kind not in "iu" or ss.shape != (T, R):
-                raise ValueError(f"start_state must be an integer array of shape ({T}, {R}), not {ss.dtype} {ss.shape}")
-            ss = np.ascontiguousarray(ss.astype(np.int32))
-        s = _f64(s)
+        ss = self._start_state(start_state, T, R)
         r = self._results(self._shapes(T, R), want_candidates)
         o = _args.fill(_lib.cfs_cart_out(), r)
         d = self._desc(ta is not None, R, self.obs, self.D)
@@ -126,6 +108,33 @@ class CartesianPath(_ToolSolver):
             _lib.check(_lib.lib().cfs_cart_path(C.byref(d), *tail))
         return r
 
+    def _starts(self, start):
+        """the host array (T, R, nj) of the starts, validated (values are not: a bad start is state 5)"""
+        nj = self.nj
+        try:
+            s = np.array(start, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"start must be an array of shape (T, R, {nj}) or (R, {nj})") from None
+        if s.ndim == 2:
+            s = s[None]
+        if s.ndim != 3 or s.shape[2] != nj or s.shape[0] < 1 or not 1 <= s.shape[1] <= MAX_CANDIDATES:
+            raise ValueError(f"start must have shape (T, R, {nj}) with T >= 1 and R in 1..{MAX_CANDIDATES}, not {s.shape}")
+        return _f64(s)
+
+    @staticmethod
+    def _start_state(start_state, T, R):
+        if start_state is None:
+            return None
+        try:
+            ss = np.array(start_state)
+        except (TypeError, ValueError):
+            raise ValueError("start_state must be an integer array") from None
+        if ss.ndim == 1:
+            ss = ss[None]
+        if ss.dtype.kind not in "iu" or ss.shape != (T, R):
+            raise ValueError(f"start_state must be an integer array of shape ({T}, {R}), not {ss.dtype} {ss.shape}")
+        return np.ascontiguousarray(ss.astype(np.int32))
+
     # ---- CUDA tensors in and out (cfs_cart_path_device) --------------------------------------------------------------------
     def trace_device(self, start, target_pos, target_axis=None, theta_ref=None, start_state=None, want_candidates=False, stream=None):
         """trace() on CUDA tensors of the solver's device: start (T, R, njoint), target_pos (T, 3), target_axis (T, 3) or None,
@@ -134,17 +143,29 @@ class CartesianPath(_ToolSolver):
         one ends the candidates that read it in state 3 (a start: state 5)."""
         if torch is None:
             raise ValueError("trace_device needs torch")
+        return self._device(start, target_pos, target_axis, theta_ref, start_state, want_candidates, stream, None)
+
+    def _device(self, start, pos, axis, theta_ref, start_state, want_candidates, stream, table):
+        """trace_device (table None: pos / axis are target_pos / target_axis, (T, 3)) and follow_device (table True: they are
+        path_pos / path_axis, (T, M, 3)): the tensors checked, the results and the cand_path workspace allocated, one launch on the
+        stream, the tensors recorded on it"""
         nj = self.nj
         s = _args.cuda_tensor(start, "start", (None, None, nj), device=self.device)
         T, R, dev = s.shape[0], s.shape[1], s.device
         if T < 1 or not 1 <= R <= MAX_CANDIDATES:
             raise ValueError(f"start must have shape (T, R, {nj}) with T >= 1 and R in 1..{MAX_CANDIDATES}, not {tuple(s.shape)}")
-        tp = _args.cuda_tensor(target_pos, "target_pos", (T, 3), device=dev)
-        ta = None if target_axis is None else _args.cuda_tensor(target_axis, "target_axis", (T, 3), device=dev)
+        if table is None:
+            M, rows, entry = (), None, "cfs_cart_path"
+            tp = _args.cuda_tensor(pos, "target_pos", (T, 3), device=dev)
+            ta = None if axis is None else _args.cuda_tensor(axis, "target_axis", (T, 3), device=dev)
+        else:
+            tp = _args.cuda_tensor(pos, "path_pos", (T, None, 3), device=dev)
+            M, rows, entry = (self._npts(tp.shape[1]),), (tp.shape[1] - 1) * self.steps + 1, "cfs_cart_follow"
+            ta = None if axis is None else _args.cuda_tensor(axis, "path_axis", (T, M[0], 3), device=dev)
         tr = self._theta_ref(theta_ref, T, dev)
         ss = None if start_state is None else _args.cuda_tensor(start_state, "start_state", (T, R), torch.int32, device=dev)
         stream, obs, D = self._on(dev, stream)
-        shapes = self._shapes(T, R)
+        shapes = self._shapes(T, R, rows)
         with torch.cuda.device(dev), torch.cuda.stream(stream):
             r = self._results(shapes, want_candidates, dev)
             o = _args.fill(_lib.cfs_cart_out(), r)
@@ -153,10 +174,77 @@ class CartesianPath(_ToolSolver):
                 work = _args.zeros_on(dev)(*shapes["cand_path"])
                 o.cand_path = _ptr(work)
             d = self._desc(ta is not None, R, obs, D)
-            tail = (T, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o), C.c_void_p(stream.cuda_stream))
+            tail = (T, *M, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o), C.c_void_p(stream.cuda_stream))
             if self.meshes:
-                _lib.check(_lib.lib().cfs_cart_path_mesh_device(C.byref(d), *self._mesh_table(), *tail))
+                _lib.check(getattr(_lib.lib(), entry + "_mesh_device")(C.byref(d), *self._mesh_table(), *tail))
             else:
-                _lib.check(_lib.lib().cfs_cart_path_device(C.byref(d), *tail))
+                _lib.check(getattr(_lib.lib(), entry + "_device")(C.byref(d), *tail))
             self._record(stream, s, ss, tp, ta, tr, work)
         return r
+
+    # ---- polylines of tool poses (cfs_cart_follow*; include/cfs_hip.h, "Tool paths") -----------------------------------------
+    def _npts(self, M):
+        if not 2 <= M <= MAX_STEPS + 1:
+            raise ValueError(f"path_pos must hold 2..{MAX_STEPS + 1} poses per target, not {M}")
+        if (M - 1) * self.steps > MAX_STEPS:
+            raise ValueError(f"(poses - 1) * steps = {(M - 1) * self.steps}: a path has at most {MAX_STEPS} rows after row 0")
+        return int(M)
+
+    def follow(self, start, path_pos, path_axis=None, theta_ref=None, start_state=None, want_candidates=False):
+        """Follow T polylines of tool poses: path_pos (T, M, 3), or (M, 3) for one target, the points the tool passes in order;
+        path_axis the same shape or None (position only), the tool direction at every point.  Consecutive poses are joined by
+        straight moves of `steps` sub-steps each (the solver's steps, max_iter, max_joint_step, meshes= and mesh_variant= apply as
+        they do to trace), so a path has N = (M-1)*steps + 1 rows, at most 257.  start, theta_ref, start_state: as for trace -- the
+        candidates of an inverse-kinematics call at the first pose.  Unlike trace, row 0 is a pose to reach: a start that does not
+        solve the first pose iterates towards it, and a start farther from its solution than max_joint_step is a joint jump.
+        Returns trace's namespace with N rows in path and cand_path; theta is the winner's start."""
+        s = self._starts(start)
+        try:
+            pp = np.array(path_pos, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("path_pos must be an array of shape (T, M, 3) or (M, 3)") from None
+        if pp.ndim == 2:
+            pp = pp[None]
+        if pp.ndim != 3 or pp.shape[2] != 3 or pp.shape[0] < 1:
+            raise ValueError(f"path_pos must have shape (T, M, 3) with T >= 1 or (M, 3), not {pp.shape}")
+        T, M = pp.shape[0], self._npts(pp.shape[1])
+        if not np.isfinite(pp).all():
+            raise ValueError("path_pos must be finite")
+        pa = None
+        if path_axis is not None:
+            try:
+                pa = np.array(path_axis, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("path_axis must be an array of the shape of path_pos, or None") from None
+            if pa.ndim == 2:
+                pa = pa[None]
+            if pa.shape != (T, M, 3):
+                raise ValueError(f"path_axis must have the shape of path_pos, ({T}, {M}, 3), not {pa.shape}")
+            if not np.isfinite(pa).all():
+                raise ValueError("path_axis must be finite")
+            if not (np.linalg.norm(pa, axis=2) > 0).all():
+                raise ValueError("a path_axis row is zero")
+            pa = _f64(pa)
+        tr = self._ref(theta_ref, T)
+        if s.shape[0] != T:
+            raise ValueError(f"start has {s.shape[0]} targets, path_pos {T}")
+        R = s.shape[1]
+        ss = self._start_state(start_state, T, R)
+        pp = _f64(pp)
+        r = self._results(self._shapes(T, R, (M - 1) * self.steps + 1), want_candidates)
+        o = _args.fill(_lib.cfs_cart_out(), r)
+        d = self._desc(pa is not None, R, self.obs, self.D)
+        tail = (T, M, _ptr(s), _ptr(ss), _ptr(pp), _ptr(pa), _ptr(tr), C.byref(o))
+        if self.meshes:
+            _lib.check(_lib.lib().cfs_cart_follow_mesh(C.byref(d), *self._mesh_table(), *tail))
+        else:
+            _lib.check(_lib.lib().cfs_cart_follow(C.byref(d), *tail))
+        return r
+
+    def follow_device(self, start, path_pos, path_axis=None, theta_ref=None, start_state=None, want_candidates=False, stream=None):
+        """follow() on CUDA tensors of the solver's device: start (T, R, njoint), path_pos (T, M, 3), path_axis (T, M, 3) or None,
+        theta_ref (T, njoint) or None float64; start_state (T, R) int32 or None; enqueued on `stream` like trace_device, without a
+        host synchronisation.  A non-finite value or a zero path_axis row ends the candidates that read it in state 3."""
+        if torch is None:
+            raise ValueError("follow_device needs torch")
+        return self._device(start, path_pos, path_axis, theta_ref, start_state, want_candidates, stream, True)

@@ -28,6 +28,11 @@
 //                                    the xor-shuffle argmin, then the winner's clearance: the (row, mesh, link) triples strided over
 //                                    the lanes, one exact unbounded mesh_query each, a wave min with the line clearance of the rows.
 // cfs_cart_kernel is untouched: at 256 VGPR + 253 AGPR for NJ = 5 a hierarchy walk inside its pass would put the iteration in scratch.
+//
+// Tool paths (cfs_cart_follow*): cfs_cart_follow_kernel<NJ> is the same mapping and the same one-loop pass for a
+// polyline of tool poses per target.  Row 0 is a pose to reach like every later row and is jump-tested against the start; the head of
+// a pass reads the two poses of the lane's segment from the target's table instead of holding a line origin.  Its outputs keep
+// cfs_cart_kernel's conventions with K = rows - 1, so the two mesh kernels above run behind it unchanged.
 // What the kernels here share with cfs_ik.hip is called, not restated: ik_stage, ik_converged, ik_cost, ik_argmin
 // (cfs_ik_dev.h), mesh_hit, mesh_pair_clearance, mesh_wave_min (cfs_mesh_hit_dev.h) and the descriptor checks of cfs_tool_host.h.
 #include "cfs_mesh_hit_dev.h"
@@ -251,10 +256,221 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartPar
     }
 }
 
-hipError_t launch_cart(int nj, const CartParams &p, hipStream_t s)
+// ---- tool paths: polylines of tool poses (cfs_cart_follow*) -------------------------------------------------
+// (p_n, a_n) of row n >= 1 of a polyline, on segment i with ksub sub-steps: both poses of the segment are read from the target's table
+// here, where they are needed, and not held (the table is the wave's, so lanes on the same segment read the same addresses).  False:
+// the interpolated axis is undefined.
+__device__ __forceinline__ bool follow_row(const double *pos, const double *axs, int n, int i, int ksub, bool use_axis, double *pk, double *ak)
+{
+    const double s = (double)(n - i * ksub) / (double)ksub;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) pk[q] = pos[i * 3 + q] + s * (pos[i * 3 + 3 + q] - pos[i * 3 + q]);
+    if (!use_axis) return true;
+    double u[3], v[3], b[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { u[q] = axs[i * 3 + q]; v[q] = axs[i * 3 + 3 + q]; }
+    const double un = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), vn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) b[q] = (1.0 - s) * (u[q] / un) + s * (v[q] / vn);
+    const double bn = sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+    if (!(bn > CART_AXIS_MIN)) return false;
+    ak[0] = b[0] / bn; ak[1] = b[1] / bn; ak[2] = b[2] / bn;
+    return true;
+}
+
+// cfs_cart_kernel's mapping and its one-loop pass for a polyline: P.target_pos / P.target_axis are the tables (T x M x 3), P.K + 1 = N
+// the rows of a path, ksub the sub-steps of a segment.  What differs from cfs_cart_kernel: row 0 is a pose to reach like every later
+// row (set up before the loop, jump-tested against the start), and there is no per-candidate line origin, so nothing of the line is
+// held across the iteration: the lane keeps the row's pose (pk, ak), its row and its segment.
+template <int NJ>
+__global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_follow_kernel(const CartParams P, const int ksub)
+{
+    __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
+    __shared__ double s_obs[CFS_MAX_OBS * 6];
+    __shared__ double s_D[CFS_MAX_OBS];
+    // the only block barrier is in there: whole waves may leave after it
+    const DevRobot *rb = ik_stage<WV * CART_WAVES>(P.rb, s_rb, P.nobs, P.obs, P.D, s_obs, s_D);
+    const int lane = threadIdx.x % WV, t = blockIdx.x * CART_WAVES + threadIdx.x / WV;
+    if (t >= P.T) return;
+    const bool use_axis = P.use_axis != 0;
+    const bool active = lane < P.R;                           // lanes >= candidates never run and enter the reductions with neutral values
+    const size_t row = (size_t)t * P.R + (active ? lane : 0);
+    const size_t prow = row * (size_t)(P.K + 1);              // the candidate's first row of cand_path
+    const size_t tab = (size_t)t * (size_t)(P.K / ksub + 1) * 3;                                // the target's rows of the two tables
+
+    double th[NJ];
+    int st = 5;                                               // -1: running
+    if (active) {
+        bool ok = !P.start_state || P.start_state[row] == 0;
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) {
+            th[c] = P.start[row * NJ + c];
+            ok = ok && th[c] >= P.lo[c] && th[c] <= P.hi[c];  // false for a NaN and for +-inf
+        }
+        if (ok) st = -1;
+    }
+    if (st != -1) {
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) th[c] = __builtin_nan("");
+    }
+
+    double pk[3] = {0.0, 0.0, 0.0}, ak[3] = {0.0, 0.0, 0.0}, prev[NJ], r[6], F = 0.0, A[NJ * NJ], g[NJ];
+    double lam = IK_LAMBDA0, cmin = INFINITY;
+    int it = 0, itsum = 0, seg = 0, nrow = 0;                 // nrow: rows of cand_path written = the row the lane works on
+#pragma unroll
+    for (int q = 0; q < 6; ++q) r[q] = 0.0;
+#pragma unroll
+    for (int c = 0; c < NJ; ++c) { prev[c] = th[c]; g[c] = 0.0; }
+#pragma unroll
+    for (int q = 0; q < NJ * NJ; ++q) A[q] = 0.0;
+    // row 0 is (P_0, A_0 normalised): set up from the start like any later row from the row before it
+    if (st < 0) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) pk[q] = P.target_pos[tab + q];
+        if (use_axis) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) ak[q] = P.target_axis[tab + q];
+            const double an = sqrt(ak[0] * ak[0] + ak[1] * ak[1] + ak[2] * ak[2]);
+            ak[0] /= an; ak[1] /= an; ak[2] /= an;            // a zero or non-finite row: NaN, which step 1 turns into state 3
+        }
+        double p[3], a[3], tw[NJ * 6];
+        ik_pose<NJ>(rb, P.tool, P.axis, th, p, a, tw);
+        ik_residual(p, a, pk, ak, use_axis, r, &F);
+        ik_normal<NJ>(tw, p, a, r, use_axis, A, g);
+    }
+
+    for (;;) {
+        // ---- head of the pass: a row whose pose is reached is booked and the next one set up --------------------------------
+        if (st < 0) {
+            if (!(F < INFINITY)) st = 3;                                                        // step 1
+            else if (ik_converged(r, use_axis, P.tol_pos, P.tol_axis)) {                        // step 2: theta_n = th
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < NJ; ++c) s = fabs(th[c] - prev[c]) > s ? fabs(th[c] - prev[c]) : s;
+                if (s > P.max_joint_step) st = 4;                                               // row 0: against the start
+                if (st < 0) {
+                    const double c = ik_clearance<NJ>(rb, th, P.nobs, s_obs, s_D);
+                    if (!(c >= 0.0)) st = 2;
+                    else if (c < cmin) cmin = c;
+                }
+                if (st < 0) {
+                    if (P.cand_path) {
+#pragma unroll
+                        for (int c = 0; c < NJ; ++c) P.cand_path[(prow + nrow) * NJ + c] = th[c];
+                    }
+                    if (nrow == P.K) { st = 0; ++nrow; }
+                    else {
+                        ++nrow;
+                        if (nrow - seg * ksub > ksub) ++seg;                                    // row nrow lies on segment (nrow-1) div ksub
+                        if (!follow_row(P.target_pos + tab, P.target_axis + tab, nrow, seg, ksub, use_axis, pk, ak)) st = 3;
+                        if (st < 0) {                                                           // the restart of row nrow from theta_{nrow-1}
+                            double p[3], a[3], tw[NJ * 6];
+#pragma unroll
+                            for (int c = 0; c < NJ; ++c) prev[c] = th[c];
+                            ik_pose<NJ>(rb, P.tool, P.axis, th, p, a, tw);
+                            ik_residual(p, a, pk, ak, use_axis, r, &F);
+                            ik_normal<NJ>(tw, p, a, r, use_axis, A, g);
+                            lam = IK_LAMBDA0;
+                            it = 0;
+                        }
+                    }
+                }
+            }
+        }
+        if (__ballot(st < 0) == 0ull) break;
+        // ---- one iteration of the current row (a row set up above is tested before it iterates) -----------------------------
+        if (st < 0) {
+            if (!(F < INFINITY)) st = 3;                                                        // step 1
+            else if (ik_converged(r, use_axis, P.tol_pos, P.tol_axis)) {}                       // step 2: the next pass books it
+            else if (it >= P.max_iter) st = 1;                                                  // step 3
+            else {                                                                              // cfs_ik_kernel's steps 4-8, statement for statement
+                double delta[NJ], trial[NJ];
+                if (!ik_solve_step<NJ>(A, g, lam, delta)) st = 3;                               // step 4
+                else {
+                    double s = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NJ; ++c) s = fabs(delta[c]) > s ? fabs(delta[c]) : s;
+                    const double sc = s > IK_STEP_CAP ? IK_STEP_CAP / s : 1.0;                  // step 5
+#pragma unroll
+                    for (int c = 0; c < NJ; ++c) {
+                        const double x = th[c] + (s > IK_STEP_CAP ? delta[c] * sc : delta[c]);
+                        trial[c] = x < P.lo[c] ? P.lo[c] : (x > P.hi[c] ? P.hi[c] : x);        // step 6
+                    }
+                    double p2[3], a2[3], tw2[NJ * 6], r2[6], F2;
+                    ik_pose<NJ>(rb, P.tool, P.axis, trial, p2, a2, tw2);
+                    ik_residual(p2, a2, pk, ak, use_axis, r2, &F2);
+                    if (F2 < F) {                                                               // step 7
+#pragma unroll
+                        for (int c = 0; c < NJ; ++c) th[c] = trial[c];
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) r[q] = r2[q];
+                        F = F2;
+                        ik_normal<NJ>(tw2, p2, a2, r2, use_axis, A, g);
+                        lam = lam / 10.0 > IK_LAMBDA_MIN ? lam / 10.0 : IK_LAMBDA_MIN;
+                    } else {
+                        lam = lam * 10.0 < IK_LAMBDA_MAX ? lam * 10.0 : IK_LAMBDA_MAX;
+                    }
+                    ++it; ++itsum;                                                              // step 8
+                }
+            }
+        }
+    }
+
+    // ---- cost of the START, candidate outputs, selection: cfs_cart_kernel's, with K = N - 1 ---------------------------------
+    const double nan = __builtin_nan("");
+    double cost = INFINITY;
+    if (st == 0) {
+        const double s = ik_cost<NJ>(P.w, P.start + row * NJ, P.theta_ref + (size_t)t * NJ);
+        if (s < INFINITY) cost = s; else st = 3;
+    }
+    int md = nrow > 1 ? nrow - 1 : 0;                         // the last accepted row
+    if (active) {
+        if (P.cand_status) P.cand_status[row] = st;
+        if (P.cand_done) P.cand_done[row] = md;
+        if (P.cand_iter) P.cand_iter[row] = itsum;
+        if (P.cand_end) {
+#pragma unroll
+            for (int c = 0; c < NJ; ++c) P.cand_end[row * NJ + c] = th[c];
+        }
+        if (P.cand_path) {
+            for (size_t e = (prow + nrow) * NJ; e < (prow + P.K + 1) * NJ; ++e) P.cand_path[e] = nan;
+        }
+    }
+    const int n_ok = __popcll(__ballot(st == 0));
+    const bool any_start = __ballot(st != 5) != 0ull;
+    const int bl = ik_argmin<true>(cost, lane, &md);
+    const bool ok = n_ok > 0;
+    if (ok ? lane == bl : lane == 0) {
+#pragma unroll
+        for (int c = 0; c < NJ; ++c) P.theta[(size_t)t * NJ + c] = ok ? P.start[row * NJ + c] : nan;
+        P.status[t] = ok ? 0 : (any_start ? 1 : 2);
+        if (P.selected) P.selected[t] = ok ? lane : -1;
+        if (P.n_ok) P.n_ok[t] = n_ok;
+        if (P.n_done) P.n_done[t] = md;
+        if (P.clearance) P.clearance[t] = ok ? cmin : nan;
+    }
+    if (P.path) {
+        // the winner's rows of cand_path (the launch's workspace), copied by the whole wave: the fence makes the winner's stores
+        // visible to the other lanes of its wave
+        const size_t n = (size_t)(P.K + 1) * NJ;
+        double *dst = P.path + (size_t)t * n;
+        if (ok) {
+            __threadfence();
+            const double *src = P.cand_path + ((size_t)t * P.R + bl) * n;
+            for (size_t e = lane; e < n; e += WV) dst[e] = src[e];
+        } else {
+            for (size_t e = lane; e < n; e += WV) dst[e] = nan;
+        }
+    }
+}
+
+// ksub == 0: the straight line of cfs_cart_path; otherwise the polyline kernel with ksub sub-steps per segment
+hipError_t launch_cart(int nj, const CartParams &p, int ksub, hipStream_t s)
 {
     return cfs_for_nj(nj, [&](auto N) {
-        hipLaunchKernelGGL(cfs_cart_kernel<decltype(N)::value>, dim3((p.T + CART_WAVES - 1) / CART_WAVES), dim3(WV * CART_WAVES), 0, s, p);
+        const dim3 grid((p.T + CART_WAVES - 1) / CART_WAVES), block(WV * CART_WAVES);
+        if (ksub) hipLaunchKernelGGL(cfs_cart_follow_kernel<decltype(N)::value>, grid, block, 0, s, p, ksub);
+        else hipLaunchKernelGGL(cfs_cart_kernel<decltype(N)::value>, grid, block, 0, s, p);
         return hipGetLastError();
     });
 }
@@ -415,22 +631,31 @@ hipError_t launch_cart_mesh(int nj, int variant, const CartMeshArgs &a, hipStrea
     });
 }
 
-// ---- C ABI (include/cfs_hip.h, "Cartesian paths") --------------------------------------------------------------------------------
+// ---- C ABI (include/cfs_hip.h, "Cartesian paths", "Tool paths") -------------------------------------------------------------------
+// Every entry comes through the functions below.  `npts` is the optional path table: nullptr for the straight line of cfs_cart_path*
+// (target_pos / target_axis are T x 3), else the number M of poses of cfs_cart_follow*'s polylines (they are the T x M x 3 tables
+// path_pos / path_axis, and a path has (M-1)*steps + 1 rows).
+const char *cart_pos_name(const int *npts) { return npts ? "path_pos" : "target_pos"; }
+const char *cart_axis_name(const int *npts) { return npts ? "path_axis" : "target_axis"; }
+
 // everything of a call that is host memory in both entries (cfs_tool_host.h); fills the by-value part of the kernel's parameter block
-int check_cart(const cfs_cart_desc *d, int T, const double *start, const double *target_pos, const double *target_axis, const double *theta_ref,
-               const cfs_cart_out *out, CartParams &P)
+int check_cart(const cfs_cart_desc *d, const int *npts, int T, const double *start, const double *target_pos, const double *target_axis,
+               const double *theta_ref, const cfs_cart_out *out, CartParams &P)
 {
     int rc = check_tool_head(d);
     if (rc) return rc;
     if (d->candidates < 1 || d->candidates > WV) return cfs_fail(CFS_ERR_INVALID_ARG, "candidates %d outside 1..%d", d->candidates, WV);
     if (d->steps < 1 || d->steps > CART_MAX_STEPS) return cfs_fail(CFS_ERR_INVALID_ARG, "steps %d outside 1..%d", d->steps, CART_MAX_STEPS);
+    if (npts && (*npts < 2 || *npts > CART_MAX_STEPS + 1)) return cfs_fail(CFS_ERR_INVALID_ARG, "npts %d outside 2..%d", *npts, CART_MAX_STEPS + 1);
+    if (npts && (*npts - 1) * d->steps > CART_MAX_STEPS)
+        return cfs_fail(CFS_ERR_INVALID_ARG, "(npts-1)*steps = %d: a path has at most %d rows after row 0", (*npts - 1) * d->steps, CART_MAX_STEPS);
     if ((rc = check_tool_max_iter(d->max_iter))) return rc;
     if (!(std::isfinite(d->max_joint_step) && d->max_joint_step > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "max_joint_step must be finite and > 0");
     if ((rc = check_tool_fields(d, T))) return rc;
-    if (!start || !target_pos || !theta_ref) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL start / target_pos / theta_ref");
-    if ((rc = check_tool_io(d, target_axis, out))) return rc;
+    if (!start || !target_pos || !theta_ref) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL start / %s / theta_ref", cart_pos_name(npts));
+    if ((rc = check_tool_io(d, target_axis, out, cart_axis_name(npts)))) return rc;
     fill_tool_params(d, T, P);
-    P.R = d->candidates; P.K = d->steps; P.max_joint_step = d->max_joint_step;
+    P.R = d->candidates; P.K = npts ? (*npts - 1) * d->steps : d->steps; P.max_joint_step = d->max_joint_step;
     return CFS_SUCCESS;
 }
 
@@ -446,54 +671,56 @@ void cart_point(CartParams &P, const double *obs, const double *D, const double 
 
 // the trace, then (mc given) the mesh walk and the selection over it, all on stream s.  The trace's own selection would only be
 // overwritten, so it is not asked for: its optional target outputs are withheld from the first launch.
-hipError_t launch_cart_all(int nj, int variant, CartMeshArgs &a, bool mesh, hipStream_t s)
+hipError_t launch_cart_all(int nj, int variant, CartMeshArgs &a, int ksub, bool mesh, hipStream_t s)
 {
-    if (!mesh) return launch_cart(nj, a.P, s);
+    if (!mesh) return launch_cart(nj, a.P, ksub, s);
     CartParams first = a.P;
     first.path = nullptr; first.selected = nullptr; first.n_ok = nullptr; first.n_done = nullptr; first.clearance = nullptr;
-    const hipError_t e = launch_cart(nj, first, s);
+    const hipError_t e = launch_cart(nj, first, ksub, s);
     return e != hipSuccess ? e : launch_cart_mesh(nj, variant, a, s);
 }
 
 // mc == nullptr: the line-only call
-int cart_device(const cfs_cart_desc *d, const MeshCall *mc, int T, const double *start, const int *start_state, const double *target_pos,
+int cart_device(const cfs_cart_desc *d, const MeshCall *mc, const int *npts, int T, const double *start, const int *start_state, const double *target_pos,
                 const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream)
 {
     static_assert(sizeof(CartParams) <= 4096, "the parameter block travels as a kernel argument");
     static_assert(sizeof(CartMeshArgs) <= 4096, "the parameter block and the mesh table travel as a kernel argument");
     CartMeshArgs A;
-    int rc = check_cart(d, T, start, target_pos, target_axis, theta_ref, out, A.P);
+    int rc = check_cart(d, npts, T, start, target_pos, target_axis, theta_ref, out, A.P);
     if (rc) return rc;
     int variant = RRT_MESH_NONE;
     if (mc) {
         rc = check_mesh_call(d->nobs, *mc, CART_MESH_DEFAULT, A.M, variant);
         if (rc) return rc;
         if (!out->cand_path)
-            return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_cart_path_mesh_device: out->cand_path must be given, the workspace between the launches (nothing is allocated here)");
+            return cfs_fail(CFS_ERR_INVALID_ARG, "%s: out->cand_path must be given, the workspace between the launches (nothing is allocated here)",
+                            npts ? "cfs_cart_follow_mesh_device" : "cfs_cart_path_mesh_device");
     } else if (out->path && !out->cand_path)
-        return cfs_fail(CFS_ERR_INVALID_ARG, "cfs_cart_path_device: out->path needs out->cand_path, the launch's workspace (nothing is allocated here)");
+        return cfs_fail(CFS_ERR_INVALID_ARG, "%s: out->path needs out->cand_path, the launch's workspace (nothing is allocated here)",
+                        npts ? "cfs_cart_follow_device" : "cfs_cart_path_device");
     rc = cfs_use_device(cfs_current_device());
     if (rc) return rc;
     cart_point(A.P, d->obs, d->D, start, start_state, target_pos, target_axis, theta_ref, out);
-    const hipError_t e = launch_cart_all(d->njoint, variant, A, mc != nullptr, reinterpret_cast<hipStream_t>(stream));
+    const hipError_t e = launch_cart_all(d->njoint, variant, A, npts ? d->steps : 0, mc != nullptr, reinterpret_cast<hipStream_t>(stream));
     if (e != hipSuccess) return cfs_fail(CFS_ERR_HIP, "Cartesian path launch failed: %s", hipGetErrorString(e));
     return CFS_SUCCESS;
 }
 
-int cart_host(const cfs_cart_desc *d, const MeshCall *mc, int T, const double *start, const int *start_state, const double *target_pos,
+int cart_host(const cfs_cart_desc *d, const MeshCall *mc, const int *npts, int T, const double *start, const int *start_state, const double *target_pos,
               const double *target_axis, const double *theta_ref, const cfs_cart_out *out)
 {
     CartMeshArgs A;
     CartParams &P = A.P;
-    int rc = check_cart(d, T, start, target_pos, target_axis, theta_ref, out, P);
+    int rc = check_cart(d, npts, T, start, target_pos, target_axis, theta_ref, out, P);
     if (rc) return rc;
     int variant = RRT_MESH_NONE;
     if (mc) {   // refuse before anything is staged on the device
         rc = check_mesh_call(d->nobs, *mc, CART_MESH_DEFAULT, A.M, variant);
         if (rc) return rc;
     }
-    const size_t nj = d->njoint, R = d->candidates, K1 = (size_t)d->steps + 1, nobs = d->nobs, nT = T;
-    rc = check_tool_arrays(d, T, target_pos, target_axis, theta_ref);
+    const size_t nj = d->njoint, R = d->candidates, K1 = (size_t)P.K + 1, nobs = d->nobs, nT = T, M = npts ? *npts : 1;
+    rc = check_tool_arrays(d, T, target_pos, target_axis, theta_ref, M, cart_pos_name(npts), cart_axis_name(npts));
     if (rc) return rc;
     rc = cfs_use_device(cfs_current_device());
     if (rc) return rc;
@@ -502,8 +729,8 @@ int cart_host(const cfs_cart_desc *d, const MeshCall *mc, int T, const double *s
     memset(&o, 0, sizeof o);
     const double *obs_d = st.up(d->obs, nobs * 6), *D_d = st.up(d->D, nobs), *s_d = st.up(start, nT * R * nj);
     const int *ss_d = start_state ? st.up(start_state, nT * R) : nullptr;
-    const double *tp_d = st.up(target_pos, nT * 3);
-    const double *ta_d = d->use_axis ? st.up(target_axis, nT * 3) : nullptr;
+    const double *tp_d = st.up(target_pos, nT * M * 3);
+    const double *ta_d = d->use_axis ? st.up(target_axis, nT * M * 3) : nullptr;
     const double *tr_d = st.up(theta_ref, nT * nj);
     o.theta = st.out<double>(nT * nj); o.status = st.out<int>(nT);
     if (out->path) o.path = st.out<double>(nT * K1 * nj);
@@ -518,7 +745,7 @@ int cart_host(const cfs_cart_desc *d, const MeshCall *mc, int T, const double *s
     if (out->cand_path || out->path || mc) o.cand_path = st.out<double>(nT * R * K1 * nj);     // also the workspace behind `path` and between the launches
     if (st.err == hipSuccess) {
         cart_point(P, obs_d, D_d, s_d, ss_d, tp_d, ta_d, tr_d, &o);
-        st.err = launch_cart_all(d->njoint, variant, A, mc != nullptr, nullptr);
+        st.err = launch_cart_all(d->njoint, variant, A, npts ? d->steps : 0, mc != nullptr, nullptr);
         if (st.err == hipSuccess) st.err = hipStreamSynchronize(nullptr);
     }
     st.down(out->theta, o.theta, nT * nj); st.down(out->status, o.status, nT); st.down(out->path, o.path, nT * K1 * nj);
@@ -533,13 +760,13 @@ int cart_host(const cfs_cart_desc *d, const MeshCall *mc, int T, const double *s
 extern "C" int cfs_cart_path_device(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
                                     const double *target_axis, const double *theta_ref, const cfs_cart_out *out, void *stream)
 {
-    return cart_device(d, nullptr, T, start, start_state, target_pos, target_axis, theta_ref, out, stream);
+    return cart_device(d, nullptr, nullptr, T, start, start_state, target_pos, target_axis, theta_ref, out, stream);
 }
 
 extern "C" int cfs_cart_path(const cfs_cart_desc *d, int T, const double *start, const int *start_state, const double *target_pos,
                              const double *target_axis, const double *theta_ref, const cfs_cart_out *out)
 {
-    return cart_host(d, nullptr, T, start, start_state, target_pos, target_axis, theta_ref, out);
+    return cart_host(d, nullptr, nullptr, T, start, start_state, target_pos, target_axis, theta_ref, out);
 }
 
 extern "C" int cfs_cart_path_mesh_device(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
@@ -547,7 +774,7 @@ extern "C" int cfs_cart_path_mesh_device(const cfs_cart_desc *d, int nmesh, cons
                                          const double *theta_ref, const cfs_cart_out *out, void *stream)
 {
     const MeshCall mc{nmesh, meshes, D_mesh, flags};
-    return cart_device(d, &mc, T, start, start_state, target_pos, target_axis, theta_ref, out, stream);
+    return cart_device(d, &mc, nullptr, T, start, start_state, target_pos, target_axis, theta_ref, out, stream);
 }
 
 extern "C" int cfs_cart_path_mesh(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
@@ -555,7 +782,36 @@ extern "C" int cfs_cart_path_mesh(const cfs_cart_desc *d, int nmesh, const cfs_m
                                   const double *theta_ref, const cfs_cart_out *out)
 {
     const MeshCall mc{nmesh, meshes, D_mesh, flags};
-    return cart_host(d, &mc, T, start, start_state, target_pos, target_axis, theta_ref, out);
+    return cart_host(d, &mc, nullptr, T, start, start_state, target_pos, target_axis, theta_ref, out);
+}
+
+// ---- tool paths (include/cfs_hip.h, "Tool paths"): the same two functions with the path table ---------------------------------------
+extern "C" int cfs_cart_follow_device(const cfs_cart_desc *d, int T, int npts, const double *start, const int *start_state, const double *path_pos,
+                                      const double *path_axis, const double *theta_ref, const cfs_cart_out *out, void *stream)
+{
+    return cart_device(d, nullptr, &npts, T, start, start_state, path_pos, path_axis, theta_ref, out, stream);
+}
+
+extern "C" int cfs_cart_follow(const cfs_cart_desc *d, int T, int npts, const double *start, const int *start_state, const double *path_pos,
+                               const double *path_axis, const double *theta_ref, const cfs_cart_out *out)
+{
+    return cart_host(d, nullptr, &npts, T, start, start_state, path_pos, path_axis, theta_ref, out);
+}
+
+extern "C" int cfs_cart_follow_mesh_device(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T,
+                                           int npts, const double *start, const int *start_state, const double *path_pos, const double *path_axis,
+                                           const double *theta_ref, const cfs_cart_out *out, void *stream)
+{
+    const MeshCall mc{nmesh, meshes, D_mesh, flags};
+    return cart_device(d, &mc, &npts, T, start, start_state, path_pos, path_axis, theta_ref, out, stream);
+}
+
+extern "C" int cfs_cart_follow_mesh(const cfs_cart_desc *d, int nmesh, const cfs_mesh *const *meshes, const double *D_mesh, int flags, int T, int npts,
+                                    const double *start, const int *start_state, const double *path_pos, const double *path_axis,
+                                    const double *theta_ref, const cfs_cart_out *out)
+{
+    const MeshCall mc{nmesh, meshes, D_mesh, flags};
+    return cart_host(d, &mc, &npts, T, start, start_state, path_pos, path_axis, theta_ref, out);
 }
 
 extern "C" int cfs_debug_cart_frontier_overflows(unsigned long long *count, int reset)

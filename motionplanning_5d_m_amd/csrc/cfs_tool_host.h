@@ -69,9 +69,9 @@ template <class Desc> int check_tool_fields(const Desc *d, int T)
 }
 
 // Out: cfs_ik_out | cfs_cart_out
-template <class Desc, class Out> int check_tool_io(const Desc *d, const double *target_axis, const Out *out)
+template <class Desc, class Out> int check_tool_io(const Desc *d, const double *target_axis, const Out *out, const char *axis_name = "target_axis")
 {
-    if (d->use_axis && !target_axis) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis = 1 needs target_axis");
+    if (d->use_axis && !target_axis) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis = 1 needs %s", axis_name);
     if (!out || !out->theta || !out->status) return cfs_fail(CFS_ERR_INVALID_ARG, "out, out->theta and out->status must be given");
     return CFS_SUCCESS;
 }
@@ -88,18 +88,21 @@ template <class Desc, class Params> void fill_tool_params(const Desc *d, int T, 
     P.tol_pos = d->tol_pos; P.tol_axis = d->tol_axis;
 }
 
-// the values of the host arrays of such a call (the host-pointer entries only: a _device entry cannot read its inputs)
+// the values of the host arrays of such a call (the host-pointer entries only: a _device entry cannot read its inputs).  npts poses per
+// target (cfs_cart_follow*'s tables; 1 elsewhere), named in the messages as the entry names them
 template <class Desc>
-int check_tool_arrays(const Desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref)
+int check_tool_arrays(const Desc *d, int T, const double *target_pos, const double *target_axis, const double *theta_ref, size_t npts = 1,
+                      const char *pos_name = "target_pos", const char *axis_name = "target_axis")
 {
     const size_t nT = T, nj = d->njoint, nobs = d->nobs;
-    if (!all_finite(target_pos, nT * 3) || !all_finite(theta_ref, nT * nj)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_pos / theta_ref must be finite");
+    if (!all_finite(target_pos, nT * npts * 3) || !all_finite(theta_ref, nT * nj))
+        return cfs_fail(CFS_ERR_INVALID_ARG, "%s / theta_ref must be finite", pos_name);
     if (nobs && (!all_finite(d->obs, nobs * 6) || !all_finite(d->D, nobs))) return cfs_fail(CFS_ERR_INVALID_ARG, "obs / D must be finite");
     if (d->use_axis) {
-        if (!all_finite(target_axis, nT * 3)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis must be finite");
-        for (int t = 0; t < T; ++t) {
-            const double *v = target_axis + (size_t)t * 3;
-            if (!(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "target_axis row %d is zero", t);
+        if (!all_finite(target_axis, nT * npts * 3)) return cfs_fail(CFS_ERR_INVALID_ARG, "%s must be finite", axis_name);
+        for (size_t t = 0; t < nT * npts; ++t) {
+            const double *v = target_axis + t * 3;
+            if (!(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] > 0.0)) return cfs_fail(CFS_ERR_INVALID_ARG, "%s row %d is zero", axis_name, (int)t);
         }
     }
     return CFS_SUCCESS;

@@ -164,6 +164,11 @@ class _ToolSolver:
                 raise ValueError("target_axis must be finite")
             if not (np.linalg.norm(ta, axis=1) > 0).all():
                 raise ValueError("a target_axis row is zero")
+        return T, _f64(tp), (None if ta is None else _f64(ta)), self._ref(theta_ref, T)
+
+    def _ref(self, theta_ref, T):
+        """the host array (T, nj) of theta_ref, validated; None: the middle of the joint ranges"""
+        nj = self.nj
         if theta_ref is None:
             tr = np.broadcast_to(0.5 * (self.lo + self.hi)[None, :], (T, nj))
         else:
@@ -174,7 +179,7 @@ class _ToolSolver:
                 raise ValueError(f"theta_ref must have shape ({T}, {nj}) or ({nj},), not {tr.shape}")
             if not np.isfinite(tr).all():
                 raise ValueError("theta_ref must be finite")
-        return T, _f64(tp), (None if ta is None else _f64(ta)), _f64(tr)
+        return _f64(tr)
 
     def _fill_desc(self, d, use_axis, obs, D):
         """the fields cfs_ik_desc and cfs_cart_desc share"""

@@ -122,9 +122,10 @@ class RRTCFSPlanner:
         self.cfs.close()
 
     # ---- argument checks (no GPU call before they pass) --------------------------------------------------------------------
-    def _conv(self, v, name, cols, nonzero=False):
+    def _conv(self, v, name, cols, nonzero=False, table=False):
         """v as a float64 tensor (given a tensor on the planner's device) or a finite numpy array (goes to the device once validated)
-        of shape (cols,) or (S, cols); nonzero: no row of an array may be zero"""
+        of shape (cols,) or (S, cols) -- table: (M, cols) or (S, M, cols), M rows per slot --; nonzero: no row of an array may be zero"""
+        dims = (2, 3) if table else (1, 2)
         if torch is not None and isinstance(v, torch.Tensor):
             if v.device != self.device:
                 raise ValueError(f"{name} is on {v.device}, the planner on {self.device}")
@@ -138,10 +139,11 @@ class RRTCFSPlanner:
                 raise ValueError(f"{name} must be numeric") from None
             if not np.isfinite(t).all():
                 raise ValueError(f"{name} must be finite")
-            if nonzero and t.ndim in (1, 2) and t.shape[-1] == cols and not (np.linalg.norm(t.reshape(-1, cols), axis=1) > 0).all():
+            if nonzero and t.ndim in dims and t.shape[-1] == cols and not (np.linalg.norm(t.reshape(-1, cols), axis=1) > 0).all():
                 raise ValueError(f"a {name} row is zero")
-        if t.ndim not in (1, 2) or t.shape[-1] != cols:
-            raise ValueError(f"{name} must have shape ({cols},) or (S, {cols}), not {tuple(t.shape)}")
+        if t.ndim not in dims or t.shape[-1] != cols:
+            want = f"(M, {cols}) or (S, M, {cols})" if table else f"({cols},) or (S, {cols})"
+            raise ValueError(f"{name} must have shape {want}, not {tuple(t.shape)}")
         return t
 
     def _pair(self, x0, goal):
@@ -291,6 +293,97 @@ class RRTCFSPlanner:
             res.selected = torch.where(ok, res.selected, torch.full_like(res.selected, -1))
             res.goal, res.ik_status, res.ik_err_pos, res.ik_clearance = src.theta, sol.status, sol.err_pos, sol.clearance
             vars(res).update(more)
+        return res
+
+    # ---- tool paths ----------------------------------------------------------------------------------------------------------
+    def plan_to_path(self, x0, path_pos, path_axis, seed=0, ik_options=None, ik_meshes=False, path_steps=4, path_options=None,
+                     path_meshes=False, **plan_kwargs):
+        """plan() to the start of a tool path that can be followed to its end: path_pos (S, M, 3) or (M, 3), the points the tool
+        passes, path_axis the same shape, the tool direction at each (cart.CartesianPath.follow; include/cfs_hip.h, "Tool paths").
+        One IK launch at the first pose (path_pos[:, 0], path_axis[:, 0]) with its candidates kept (theta_ref = x0, ik_options as
+        for plan_to_pose), one follow_device launch from every candidate (cand_theta / cand_status) along the whole polyline on the
+        same stream (path_steps sub-steps per segment; path_options: CartesianPath's max_iter, max_joint_step; tool, tolerances
+        and weight are ik_options'; theta_ref = x0), then plan(x0, goal, seed, **plan_kwargs) with row 0 of the winners' paths as
+        goals: per slot the IK candidate nearest to x0 from which the whole path exists inside the joint ranges, without a joint
+        jump and free of the cell.
+        Returns plan()'s namespace plus tool_path (S, N, 5; N = (M-1)*path_steps + 1), tool_path_status (CartesianPath's status),
+        tool_path_clearance, tool_path_selected, ik_goal (IK's own winner), ik_status, ik_err_pos, ik_clearance and goal (the
+        configuration planned to: tool_path[:, 0]; NaN rows without one).  A slot without an IK solution is planned with goal = x0
+        and masked with status = -2, a slot with one but with no candidate that follows the path with status = -3 (has_solution =
+        0, selected = -1), exactly as plan_to_pose masks them.
+        A planner with mesh obstacles refuses unless ik_meshes=True and path_meshes=True; both solvers are then built from the
+        planner's whole cell, as plan_to_pose(..., approach_meshes=True) builds them.  On a planner without meshes they are the
+        line-only paths."""
+        for flag, name in ((ik_meshes, "ik_meshes"), (path_meshes, "path_meshes")):
+            if not isinstance(flag, bool):
+                raise ValueError(f"{name} must be True or False, not {flag!r}")
+        if self._meshes and not ik_meshes:
+            raise ValueError("plan_to_path on a planner with mesh obstacles needs ik_meshes=True: the default IK collision test reads "
+                             "line obstacles only")
+        if self._meshes and not path_meshes:
+            raise ValueError("plan_to_path on a planner with mesh obstacles needs path_meshes=True: the default path test reads line "
+                             "obstacles only")
+        _args.int_in(path_steps, "path_steps", 1, MAX_STEPS)
+        _args.int_in(seed, "seed", 0)
+        if ik_options is None:
+            ik_options = {}
+        if not isinstance(ik_options, dict) or set(ik_options) - {"tool", "tool_axis", "restarts", "max_iter", "tol_pos", "tol_axis", "weight"}:
+            raise ValueError("ik_options must be a dict of IKSolver's tool, tool_axis, restarts, max_iter, tol_pos, tol_axis, weight")
+        if path_options is None:
+            path_options = {}
+        if not isinstance(path_options, dict) or set(path_options) - {"max_iter", "max_joint_step"}:
+            raise ValueError("path_options must be a dict of CartesianPath's max_iter, max_joint_step")
+        stream = plan_kwargs.get("stream")
+        if stream is not None:
+            _args.as_stream(stream, self.device)
+        x0 = self._conv(x0, "x0", self.nj)
+        if path_axis is None:
+            raise ValueError("plan_to_path needs path_axis: the tool direction at every pose of the path")
+        pp, pa = self._conv(path_pos, "path_pos", 3, table=True), self._conv(path_axis, "path_axis", 3, nonzero=True, table=True)
+        if tuple(pp.shape) != tuple(pa.shape):
+            raise ValueError(f"path_pos and path_axis disagree: {tuple(pp.shape)} vs {tuple(pa.shape)}")
+        M = pp.shape[-2]
+        if not 2 <= M <= MAX_STEPS + 1 or (M - 1) * int(path_steps) > MAX_STEPS:
+            raise ValueError(f"a path holds 2..{MAX_STEPS + 1} poses and (poses - 1) * path_steps <= {MAX_STEPS}, not {M} poses x {path_steps} steps")
+        rows = {a.shape[0] for a, nd in ((x0, 2), (pp, 3)) if a.ndim == nd}
+        if len(rows) > 1:
+            raise ValueError(f"x0 and path_pos disagree on S: {sorted(rows)}")
+        S = rows.pop() if rows else 1
+        if S < 1 or S > self.max_slots:
+            raise ValueError(f"S={S} outside 1..max_slots={self.max_slots}")
+        key = tuple(sorted((k, repr(v)) for k, v in ik_options.items()))
+        if key not in self._ik:                                                     # validates ik_options; no device call
+            self._ik[key] = IKSolver(self._sys_rrt.robot, [o for o in self._pobs], joint_limits=self._ik_limits, njoint=self.nj,
+                                     device=self.device, **ik_options)
+        ik = self._ik[key]
+        with_meshes = bool(path_meshes and self._meshes)                            # without meshes: the line-only path
+        ckey = ("path", key, int(path_steps), with_meshes, tuple(sorted((k, repr(v)) for k, v in path_options.items())))
+        if ckey not in self._ik:                                                    # validates path_options; no device call
+            shared = {k: v for k, v in ik_options.items() if k in ("tool", "tool_axis", "tol_pos", "tol_axis", "weight")}
+            self._ik[ckey] = CartesianPath(self._sys_rrt.robot, [o for o in self._pobs], joint_limits=self._ik_limits, njoint=self.nj,
+                                           device=self.device, steps=int(path_steps), meshes=with_meshes, **shared, **path_options)
+        cart = self._ik[ckey]
+        stream = _args.as_stream(stream, self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            x0 = self._on_device(x0, S)
+            tabs = []
+            for t in (pp, pa):
+                if not isinstance(t, torch.Tensor):
+                    t = torch.tensor(t, dtype=torch.float64, device=self.device)
+                tabs.append((t.unsqueeze(0).expand(S, -1, -1) if t.ndim == 2 else t).contiguous())
+            pp, pa = tabs
+            sol = ik.solve_device(pp[:, 0].contiguous(), pa[:, 0].contiguous(), x0, seed=int(seed), want_candidates=True, stream=stream)
+            src = cart.follow_device(sol.cand_theta, pp, pa, x0, start_state=sol.cand_status, stream=stream)
+            ok, ik_ok = src.status == 0, sol.status == 0
+            first = src.path[:, 0]
+            goal = torch.where(ok[:, None], first, x0)
+            res = self.plan(x0, goal, seed, **dict(plan_kwargs, stream=stream))
+            masked = torch.where(ik_ok, torch.full_like(res.status, -3), torch.full_like(res.status, -2))
+            res.status = torch.where(ok, res.status, masked)
+            res.has_solution = torch.where(ok, res.has_solution, torch.zeros_like(res.has_solution))
+            res.selected = torch.where(ok, res.selected, torch.full_like(res.selected, -1))
+            res.goal, res.ik_goal, res.ik_status, res.ik_err_pos, res.ik_clearance = first, sol.theta, sol.status, sol.err_pos, sol.clearance
+            res.tool_path, res.tool_path_status, res.tool_path_clearance, res.tool_path_selected = src.path, src.status, src.clearance, src.selected
         return res
 
     # ---- the pipeline ----------------------------------------------------------------------------------------------------
