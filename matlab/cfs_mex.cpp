@@ -60,12 +60,21 @@
 //        and path is njoint x (N*T) (reshape(path, njoint, N, T)).  Row 1 of a path is a pose to reach, not the start: theta is the start
 //   [theta, status, path, clearance, selected, n_ok, n_done] = cfs_mex('cart_follow_mesh', obs, robot, ROBOT, start, start_state, path_pos, path_axis, theta_ref, opts)
 //        'cart_follow' in a cell that ends with mesh obstacles, received as 'cart_path_mesh' receives them: cfs_cart_follow_mesh
+//   [time, sdot, duration, status, selected, group_status] = cfs_mex('path_time', robot, ROBOT, paths, dims, state, vmax, amax, opts)
+//        a clock on joint paths (cfs_path_time, include/cfs_hip.h "Path timing"): paths njoint x N x R x G -- reshape(path, njoint, N, 1, T)
+//        of 'cart_follow' / 'cart_path', or their candidates --, dims = [N R G] (a 4-D array arrives as njoint x (N*R*G)), state R x G
+//        or [] (a path is timed only where its entry is 0), vmax / amax njoint x 1 (rad/s, rad/s^2).  opts: feed (m/s; default Inf: no
+//        cap), tool (3 x 1; default the end effector), curve_share (default 0.5), stop_every (default 0: rest at the two ends only; k >= 2:
+//        also at every row that is a multiple of k, counted from 0).  time and sdot are N x (R*G) (reshape(time, N, R, G)), duration and
+//        status R x G (0 timed | 1 not timed | 2 numeric | 3 stalled | 4 repeated row; NaN rows where not 0), selected 1 x G (1-based, 0
+//        without a timed path), group_status 1 x G
 //   Cost_b = cfs_mex('cost_b', sys_info, ROBOT)                    % EVAL.get_Cost_b (Lib/EVAL.m:75-78, main_FANUC.m:131-132)
 //   h = cfs_mex('mesh_load_stl', path, scale, map_from_stl)        % Lib/functions/MapFromSTL.m
 //   [dis, points] = cfs_mex('mesh_segment_distance', h, seg6)      % point2surface_dis (M200i/dist_arm_surf_200i.m:21)
 //   cfs_mex('mesh_destroy', h)
 #include "mex.h"
 #include "cfs_hip.h"
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -743,6 +752,54 @@ static void cart_path_mesh(int nlhs, mxArray *plhs[], int nrhs, const mxArray *p
     for (int k = 0; k < 7; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
 }
 
+// a clock on joint paths (cfs_path_time): options through the same two lambdas as the other tool verbs
+static void path_time(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs < 8) mexErrMsgTxt("[time, sdot, duration, status, selected, group_status] = cfs_mex('path_time', robot, ROBOT, paths, dims, state, vmax, amax [, opts])");
+    const mxArray *robot = prhs[1], *opts = nrhs > 8 ? prhs[8] : nullptr;
+    const std::string ROBOT = mxArrayToString(prhs[2]);
+    if (mxGetNumberOfElements(prhs[4]) != 3) mexErrMsgTxt("dims must be [N R G]");
+    for (int q = 0; q < 3; ++q) {                                                     // whole numbers that an int holds, before any cast
+        const double v = mxGetPr(prhs[4])[q];
+        if (!(v >= 1.0 && v <= 1e6) || v != std::floor(v)) mexErrMsgTxt("dims must be three whole numbers [N R G], each in 1..1e6");
+    }
+    const int nj = (int)mxGetM(prhs[3]), N = (int)mxGetPr(prhs[4])[0], R = (int)mxGetPr(prhs[4])[1], G = (int)mxGetPr(prhs[4])[2];
+    if (nj < 2 || nj > 6) mexErrMsgTxt("paths must have 2..6 rows (njoint)");
+    if ((double)R * G > 2147483647.0 || mxGetNumberOfElements(prhs[3]) != (size_t)nj * N * R * G)
+        mexErrMsgTxt("paths must be njoint x N x R x G with dims = [N R G]");
+    if ((int)mxGetNumberOfElements(prhs[6]) != nj || (int)mxGetNumberOfElements(prhs[7]) != nj) mexErrMsgTxt("vmax and amax must be njoint x 1");
+    std::vector<int> state;
+    if (!mxIsEmpty(prhs[5])) {
+        if ((int)mxGetNumberOfElements(prhs[5]) != R * G) mexErrMsgTxt("state must be R x G or []");
+        state.resize((size_t)R * G);
+        for (int e = 0; e < R * G; ++e) state[e] = (int)mxGetPr(prhs[5])[e];
+    }
+    cfs_time_desc d;
+    memset(&d, 0, sizeof d);
+    fill_robot(robot, ROBOT.c_str(), nj, d.robot);
+    d.njoint = nj;
+    auto opt = [&](const char *name) -> const mxArray * { const mxArray *f = opts ? mxGetField(opts, 0, name) : nullptr; return f && !mxIsEmpty(f) ? f : nullptr; };
+    auto num = [&](const char *name, double dflt) { const mxArray *f = opt(name); return f ? mxGetScalar(f) : dflt; };
+    const double *cp = d.robot.cap + 6 * (nj - 1);
+    for (int q = 0; q < 3; ++q) d.tool[q] = opt("tool") ? mxGetPr(opt("tool"))[q] : cp[q];
+    d.vmax = mxGetPr(prhs[6]); d.amax = mxGetPr(prhs[7]);
+    d.feed = num("feed", HUGE_VAL); d.curve_share = num("curve_share", 0.5); d.stop_every = (int)num("stop_every", 0);
+    const size_t np = (size_t)R * G;
+    mxArray *o_t = mxCreateDoubleMatrix(N, np, mxREAL), *o_s = mxCreateDoubleMatrix(N, np, mxREAL);   // G x R x N row-major = N x (R*G) column-major
+    mxArray *o_d = mxCreateDoubleMatrix(R, G, mxREAL);
+    std::vector<int> status(np), selected(G), gstatus(G);
+    cfs_time_out o;
+    memset(&o, 0, sizeof o);
+    o.time = mxGetPr(o_t); o.sdot = mxGetPr(o_s); o.duration = mxGetPr(o_d); o.status = status.data(); o.selected = selected.data();
+    o.group_status = gstatus.data();
+    check(cfs_path_time(&d, G, R, N, mxGetPr(prhs[3]), state.empty() ? nullptr : state.data(), &o));
+    mxArray *o_st = mxCreateDoubleMatrix(R, G, mxREAL), *o_sel = mxCreateDoubleMatrix(1, G, mxREAL), *o_gs = mxCreateDoubleMatrix(1, G, mxREAL);
+    for (size_t e = 0; e < np; ++e) mxGetPr(o_st)[e] = status[e];
+    for (int g = 0; g < G; ++g) { mxGetPr(o_sel)[g] = selected[g] + 1; mxGetPr(o_gs)[g] = gstatus[g]; }
+    mxArray *outs[6] = {o_t, o_s, o_d, o_st, o_sel, o_gs};
+    for (int k = 0; k < 6; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
+}
+
 static void cost_b(mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs < 3) mexErrMsgTxt("Cost_b = cfs_mex('cost_b', sys_info, ROBOT)");
@@ -796,6 +853,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         cart_path(nlhs, plhs, nrhs, prhs, true);
     } else if (cmd == "cart_follow_mesh") {
         cart_path_mesh(nlhs, plhs, nrhs, prhs, true);
+    } else if (cmd == "path_time") {
+        path_time(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "cost_b") {
         cost_b(plhs, nrhs, prhs);
     } else if (cmd == "mesh_load_stl") {

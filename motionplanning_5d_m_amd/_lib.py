@@ -37,6 +37,7 @@ IK_STATUS = {0: "SOLVED", 1: "NOT_CONVERGED", 2: "IN_COLLISION"}                
 IK_CAND_STATUS = {0: "CONVERGED", 1: "MAX_ITER", 2: "IN_COLLISION", 3: "NUMERIC"}      # cfs_ik_out.cand_status
 CART_STATUS = {0: "SOLVED", 1: "NO_COMPLETE_LINE", 2: "NO_START"}                      # cfs_cart_out.status
 CART_CAND_STATUS = {0: "COMPLETE", 1: "MAX_ITER", 2: "IN_COLLISION", 3: "NUMERIC", 4: "JOINT_JUMP", 5: "NO_START"}   # cfs_cart_out.cand_status
+TIME_STATUS = {0: "TIMED", 1: "NOT_TIMED", 2: "NUMERIC", 3: "STALLED", 4: "REPEATED_ROW"}                            # cfs_time_out.status
 
 
 class CfsError(RuntimeError):
@@ -231,6 +232,30 @@ class cfs_cart_out(C.Structure):
     ]
 
 
+class cfs_time_desc(C.Structure):
+    _fields_ = [
+        ("robot", cfs_robot),
+        ("njoint", C.c_int),
+        ("tool", C.c_double * 3),
+        ("vmax", C.c_void_p),
+        ("amax", C.c_void_p),
+        ("feed", C.c_double),
+        ("curve_share", C.c_double),
+        ("stop_every", C.c_int),
+    ]
+
+
+class cfs_time_out(C.Structure):
+    _fields_ = [
+        ("time", C.c_void_p),
+        ("sdot", C.c_void_p),
+        ("duration", C.c_void_p),
+        ("status", C.c_void_p),
+        ("selected", C.c_void_p),
+        ("group_status", C.c_void_p),
+    ]
+
+
 # every symbol include/cfs_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -313,6 +338,8 @@ SYMBOLS = [
                                        C.POINTER(cfs_cart_out)]),
     ("cfs_cart_follow_mesh_device", C.c_int, [C.POINTER(cfs_cart_desc), C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,
                                               C.POINTER(cfs_cart_out), _P]),
+    ("cfs_path_time", C.c_int, [C.POINTER(cfs_time_desc), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(cfs_time_out)]),
+    ("cfs_path_time_device", C.c_int, [C.POINTER(cfs_time_desc), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(cfs_time_out), _P]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)

@@ -1,5 +1,6 @@
 // cfs_tool_host.h -- what the entries of cfs_ik.hip and cfs_cart.hip share on the host (not part of the C ABI): the checks of the
 // descriptor fields that cfs_ik_desc and cfs_cart_desc have in common, with one set of messages, and the mesh table of a *_mesh* call.
+// cfs_time.hip takes the check of the chain (check_tool_chain) and the array helpers from here.
 // The order of the refusals is observable through cfs_last_error(): a unit calls check_tool_head, makes its own refusals (restarts |
 // candidates, steps), then check_tool_max_iter, its own again (max_joint_step), check_tool_fields, its own pointer check,
 // check_tool_io, and fill_tool_params last.
@@ -32,13 +33,21 @@ inline int check_mesh_call(int nobs, const MeshCall &c, int default_variant, Too
     return CFS_SUCCESS;
 }
 
-// Desc: cfs_ik_desc | cfs_cart_desc
-template <class Desc> int check_tool_head(const Desc *d)
+// the robot and the joint count of a descriptor (cfs_time_desc has these and no tool direction)
+template <class Desc> int check_tool_chain(const Desc *d)
 {
     if (!d) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL descriptor");
     int rc = cfs_check_robot(&d->robot, d->njoint);
     if (rc) return rc;
     if (d->njoint < 2) return cfs_fail(CFS_ERR_INVALID_ARG, "njoint %d unsupported (2..6)", d->njoint);
+    return CFS_SUCCESS;
+}
+
+// Desc: cfs_ik_desc | cfs_cart_desc
+template <class Desc> int check_tool_head(const Desc *d)
+{
+    int rc = check_tool_chain(d);
+    if (rc) return rc;
     if (d->use_axis != 0 && d->use_axis != 1) return cfs_fail(CFS_ERR_INVALID_ARG, "use_axis must be 0 or 1, not %d", d->use_axis);
     return CFS_SUCCESS;
 }

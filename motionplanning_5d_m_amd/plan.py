@@ -30,6 +30,7 @@ from ._args import ptr as _ptr
 from .cart import MAX_STEPS, CartesianPath
 from .ik import IKSolver
 from .rrt import RRT_FANUC
+from .timing import MAX_ROWS, MIN_ROWS, PathTimer
 from .robotproperty2 import robotproperty2
 from .solvers import SOLVE_OUT, CFSBatch, _infeasible_args, _joint_limits_array, obs_meshes, obs_to_array
 from .sysinfo import RRTstar_CFS_problem
@@ -165,7 +166,7 @@ class RRTCFSPlanner:
 
     # ---- Cartesian goals ---------------------------------------------------------------------------------------------------
     def plan_to_pose(self, x0, target_pos, target_axis=None, seed=0, ik_options=None, ik_meshes=False, approach=None, approach_dir=None,
-                     approach_steps=16, approach_options=None, approach_meshes=False, **plan_kwargs):
+                     approach_steps=16, approach_options=None, approach_meshes=False, approach_timing=None, **plan_kwargs):
         """plan() towards Cartesian targets: one inverse-kinematics launch (ik.IKSolver.solve_device: theta_ref = x0, the planner's
         obstacles with their D -- its line obstacles, and with ik_meshes=True its mesh obstacles too --, the planner's joint_limits if
         it has them, else robot.thetamax; generator seed `seed`), then
@@ -193,10 +194,15 @@ class RRTCFSPlanner:
         approach_meshes: False (the default) keeps the line-only trace, and a planner with mesh obstacles then refuses an approach;
         True (needs ik_meshes=True on such a planner) builds the CartesianPath from the planner's whole cell with meshes=True -- the
         D that cfs_rrt_grow_mesh_device gets --, so that every configuration of the line is free of the meshes too
-        (cfs_cart_path_mesh_device).  On a planner without meshes it is the line-only path."""
+        (cfs_cart_path_mesh_device).  On a planner without meshes it is the line-only path.
+        approach_timing: None (the default: everything above, bit for bit) or a dict of timing.PathTimer's vmax, amax (both needed),
+        feed, stops, curve_share: the winners' approach paths are then timed on the same stream (stops="corners" reads
+        approach_steps), and the result gains approach_time, approach_sdot (S, approach_steps+1), approach_duration and
+        approach_time_status (PathTimer's status; a slot without an approach path: NaN rows and status 1).  Needs approach and
+        approach_steps >= 2."""
         if approach is None:
-            if approach_dir is not None or approach_options is not None:
-                raise ValueError("approach_dir / approach_options need approach")
+            if approach_dir is not None or approach_options is not None or approach_timing is not None:
+                raise ValueError("approach_dir / approach_options / approach_timing need approach")
         else:
             if self._meshes and approach_meshes is not True:
                 raise ValueError("plan_to_pose(approach=...) on a planner with mesh obstacles: the straight-line trace reads line obstacles only "
@@ -265,6 +271,7 @@ class RRTCFSPlanner:
                 self._ik[ckey] = CartesianPath(self._sys_rrt.robot, [o for o in self._pobs], joint_limits=self._ik_limits, njoint=self.nj,
                                                device=self.device, steps=int(approach_steps), meshes=with_meshes, **shared, **approach_options)
             cart = self._ik[ckey]
+        timer = self._timer(approach_timing, "approach_timing", ik_options, int(approach_steps), int(approach_steps) + 1)
         stream = _args.as_stream(stream, self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(stream):
             dev = [self._on_device(a, S) for a in args]
@@ -282,6 +289,9 @@ class RRTCFSPlanner:
                 ik_ok = sol.status == 0
                 more = dict(ik_goal=sol.theta, approach_path=src.path, grasp=src.path[:, -1], approach_status=src.status,
                             approach_clearance=src.clearance, approach_selected=src.selected)
+                if timer is not None:
+                    tm = timer.time_device(src.path, state=src.status, steps=int(approach_steps), stream=stream)
+                    more.update(approach_time=tm.time, approach_sdot=tm.sdot, approach_duration=tm.duration, approach_time_status=tm.status)
             ok = src.status == 0
             goal = torch.where(ok[:, None], src.theta, x0)
             res = self.plan(x0, goal, seed, **dict(plan_kwargs, stream=stream))
@@ -297,7 +307,7 @@ class RRTCFSPlanner:
 
     # ---- tool paths ----------------------------------------------------------------------------------------------------------
     def plan_to_path(self, x0, path_pos, path_axis, seed=0, ik_options=None, ik_meshes=False, path_steps=4, path_options=None,
-                     path_meshes=False, **plan_kwargs):
+                     path_meshes=False, path_timing=None, **plan_kwargs):
         """plan() to the start of a tool path that can be followed to its end: path_pos (S, M, 3) or (M, 3), the points the tool
         passes, path_axis the same shape, the tool direction at each (cart.CartesianPath.follow; include/cfs_hip.h, "Tool paths").
         One IK launch at the first pose (path_pos[:, 0], path_axis[:, 0]) with its candidates kept (theta_ref = x0, ik_options as
@@ -313,7 +323,12 @@ class RRTCFSPlanner:
         0, selected = -1), exactly as plan_to_pose masks them.
         A planner with mesh obstacles refuses unless ik_meshes=True and path_meshes=True; both solvers are then built from the
         planner's whole cell, as plan_to_pose(..., approach_meshes=True) builds them.  On a planner without meshes they are the
-        line-only paths."""
+        line-only paths.
+        path_timing: None (the default: everything above, bit for bit) or a dict of timing.PathTimer's vmax, amax (both needed),
+        feed, stops, curve_share (the tool point is ik_options'): the winners' paths are then timed on the same stream
+        (stops="corners": at rest at every pose of the polyline, which needs path_steps >= 2), and the result gains tool_path_time,
+        tool_path_sdot (S, N), tool_path_duration and tool_path_time_status (PathTimer's status).  A slot masked -2 / -3 holds NaN
+        rows and status 1.  Needs N >= 3."""
         for flag, name in ((ik_meshes, "ik_meshes"), (path_meshes, "path_meshes")):
             if not isinstance(flag, bool):
                 raise ValueError(f"{name} must be True or False, not {flag!r}")
@@ -363,6 +378,7 @@ class RRTCFSPlanner:
             self._ik[ckey] = CartesianPath(self._sys_rrt.robot, [o for o in self._pobs], joint_limits=self._ik_limits, njoint=self.nj,
                                            device=self.device, steps=int(path_steps), meshes=with_meshes, **shared, **path_options)
         cart = self._ik[ckey]
+        timer = self._timer(path_timing, "path_timing", ik_options, int(path_steps), (M - 1) * int(path_steps) + 1)
         stream = _args.as_stream(stream, self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(stream):
             x0 = self._on_device(x0, S)
@@ -384,7 +400,24 @@ class RRTCFSPlanner:
             res.selected = torch.where(ok, res.selected, torch.full_like(res.selected, -1))
             res.goal, res.ik_goal, res.ik_status, res.ik_err_pos, res.ik_clearance = first, sol.theta, sol.status, sol.err_pos, sol.clearance
             res.tool_path, res.tool_path_status, res.tool_path_clearance, res.tool_path_selected = src.path, src.status, src.clearance, src.selected
+            if timer is not None:
+                tm = timer.time_device(src.path, state=src.status, steps=int(path_steps), stream=stream)
+                res.tool_path_time, res.tool_path_sdot, res.tool_path_duration, res.tool_path_time_status = tm.time, tm.sdot, tm.duration, tm.status
         return res
+
+    def _timer(self, timing, name, ik_options, steps, rows):
+        """the PathTimer of a path_timing / approach_timing dict (None: no timing), validated without a device call"""
+        if timing is None:
+            return None
+        if not isinstance(timing, dict) or set(timing) - {"vmax", "amax", "feed", "stops", "curve_share"} or not {"vmax", "amax"} <= set(timing):
+            raise ValueError(f"{name} must be a dict of PathTimer's vmax and amax, and optionally feed, stops, curve_share")
+        if not MIN_ROWS <= rows <= MAX_ROWS:
+            raise ValueError(f"{name}: a timed path has {MIN_ROWS}..{MAX_ROWS} rows, not {rows}")
+        key = (name, repr(ik_options.get("tool")), tuple(sorted((k, repr(v)) for k, v in timing.items())))
+        if key not in self._ik:
+            self._ik[key] = PathTimer(self._sys_rrt.robot, njoint=self.nj, device=self.device, tool=ik_options.get("tool"), **timing)
+        self._ik[key]._stop_every(steps)                                            # stops="corners" with one sub-step is refused here
+        return self._ik[key]
 
     # ---- the pipeline ----------------------------------------------------------------------------------------------------
     def plan(self, x0, goal, seed, max_rounds=50, stream=None, want_candidates=False, max_draws=None, timings=None):
