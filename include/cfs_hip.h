@@ -372,7 +372,11 @@ int cfs_mesh_info(const cfs_mesh *m, int *ntri, int *nnodes, int *depth, double 
 void cfs_mesh_destroy(cfs_mesh *m);
 
 /* point2surface_dis for n segments (HOST pointers): segs n x 6 = [p(:,1); p(:,2)]; dis n;
- * points n x 6 (may be NULL); tri n = index of the closest triangle in the caller's list (may be NULL) */
+ * points n x 6 (may be NULL); tri n = index of the closest triangle in the caller's list (may be NULL).
+ * The geometry is evaluated WITHOUT FMA contraction (as cfs_rrt_grow_mesh evaluates it; cfs_dist_arm_mesh, the solvers, the
+ * clearance audits, cfs_ik_solve_mesh and cfs_cart_path_mesh contract): it rounds like the CPU statement of the contract, so
+ * that distances equal in exact arithmetic (a segment in the surface, parallel to a wall or to an edge) resolve to the same
+ * point there and here.  A distance may differ in its last bits from cfs_dist_arm_mesh's for the same link axis. */
 int cfs_mesh_segment_distance(const cfs_mesh *m, int n, const double *segs, double *dis, double *points, int *tri);
 
 /* dist_arm_surf_200i (M200i/dist_arm_surf_200i.m:1-29) for N poses (HOST pointers): theta N x njoint;
@@ -1011,6 +1015,10 @@ int cfs_debug_rrt_frontier_overflows(unsigned long long *count, int reset);
 int cfs_debug_ik_frontier_overflows(unsigned long long *count, int reset);
 /* cfs_cart_path_mesh*, variant B: the same counter for the poses (rows of a traced line) that variant A decided for it */
 int cfs_debug_cart_frontier_overflows(unsigned long long *count, int reset);
+/* cfs_mesh_segment_distance, arguments and outputs alike, evaluated WITH FMA contraction: the build of the hierarchy traversal
+ * and of the exact geometry that cfs_dist_arm_mesh, the solvers' linearisation, the clearance audits, cfs_ik_solve_mesh and
+ * cfs_cart_path_mesh run, made reachable for arbitrary segments (tests/test_gpu_mesh_geometry.py) */
+int cfs_debug_mesh_segment_distance_contracted(const cfs_mesh *m, int n, const double *segs, double *dis, double *points, int *tri);
 
 #ifdef __cplusplus
 }

@@ -332,6 +332,7 @@ SYMBOLS = [
     ("cfs_cart_path_mesh_device", C.c_int, [C.POINTER(cfs_cart_desc), C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.POINTER(cfs_cart_out),
                                             _P]),
     ("cfs_debug_cart_frontier_overflows", C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    ("cfs_debug_mesh_segment_distance_contracted", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("cfs_cart_follow", C.c_int, [C.POINTER(cfs_cart_desc), C.c_int, C.c_int, _P, _P, _P, _P, _P, C.POINTER(cfs_cart_out)]),
     ("cfs_cart_follow_device", C.c_int, [C.POINTER(cfs_cart_desc), C.c_int, C.c_int, _P, _P, _P, _P, _P, C.POINTER(cfs_cart_out), _P]),
     ("cfs_cart_follow_mesh", C.c_int, [C.POINTER(cfs_cart_desc), C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,

@@ -10,6 +10,7 @@
 // its distance exceeds the incumbent.
 #include "cfs_mesh_dev.h"
 #include "cfs_host.h"
+#include "cfs_mesh_query_dev.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -21,26 +22,8 @@ namespace {
 // ---- device geometry, the traversal (mesh_query) and the near-zero surrogate: cfs_mesh_dev.h ----------------------
 
 // ---- kernels ------------------------------------------------------------------------------------------
-struct SegQueryParams { DevMesh m; int n; const double *segs; double *dis, *pts; int *tri; };
-
-__global__ __launch_bounds__(MESH_THREADS) void cfs_mesh_seg_kernel(SegQueryParams P)
-{
-    __shared__ int s_stack[MESH_STACK * MESH_THREADS];
-    __shared__ float s_lbs[MESH_STACK * MESH_THREADS];
-    const int i = blockIdx.x * MESH_THREADS + threadIdx.x;
-    if (i >= P.n) return;
-    double seg[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) seg[r] = P.segs[(size_t)i * 6 + r];
-    Best b;
-    mesh_query<MESH_THREADS, false>(P.m, seg, seg + 3, -1, s_stack + threadIdx.x, s_lbs + threadIdx.x, b, nullptr);
-    P.dis[i] = b.d;
-    if (P.pts)
-#pragma unroll
-        for (int r = 0; r < 6; ++r) P.pts[(size_t)i * 6 + r] = b.pts[r];
-    if (P.tri) P.tri[i] = b.tri >= 0 ? P.m.orig[b.tri] : -1;
-}
-
+// point2surface_dis (cfs_mesh_seg_kernel): cfs_mesh_query_dev.h.  The public entry is cfs_mesh_query.hip's build of it (no FMA
+// contraction); this unit's build is cfs_debug_mesh_segment_distance_contracted
 // dist_arm over a mesh (M200i/dist_arm_surf_200i.m:1-29): one thread per (pose, link), min over links in LDS
 struct ArmMeshParams { const DevRobot *rb; DevMesh m; int N, nj; const double *theta; double *d; int *linkid; double *pts; };
 
@@ -803,20 +786,11 @@ void cfs_mesh_destroy(cfs_mesh *m)
     delete m;
 }
 
-// point2surface_dis for n segments (host arrays): dis[n], points[n x 6] (may be NULL), tri[n] (may be NULL)
-int cfs_mesh_segment_distance(const cfs_mesh *m, int n, const double *segs, double *dis, double *points, int *tri)
+// cfs_mesh_segment_distance in this unit's arithmetic (FMA contraction on, as in every kernel below and in the clearance, IK
+// and Cartesian units): the hierarchy and the exact geometry of cfs_mesh_dev.h as the solvers run them, for arbitrary segments
+int cfs_debug_mesh_segment_distance_contracted(const cfs_mesh *m, int n, const double *segs, double *dis, double *points, int *tri)
 {
-    if (!m || !segs || !dis || n < 1) return cfs_fail(CFS_ERR_INVALID_ARG, "mesh/segs/dis must be given, n >= 1");
-    CFS_HIPCHK(hipSetDevice(m->device));
-    const size_t nn = n;
-    Stage st;
-    SegQueryParams q{m->view(), n, st.up(segs, nn * 6), st.out<double>(nn), st.out<double>(nn * 6), st.out<int>(nn)};
-    if (st.err == hipSuccess) {
-        hipLaunchKernelGGL(cfs_mesh_seg_kernel, dim3((n + MESH_THREADS - 1) / MESH_THREADS), dim3(MESH_THREADS), 0, nullptr, q);
-        st.err = hipGetLastError();
-    }
-    st.down(dis, q.dis, nn); st.down(points, q.pts, nn * 6); st.down(tri, q.tri, nn);
-    return st.result("cfs_mesh_segment_distance");
+    return mesh_segment_query(m, n, segs, dis, points, tri, "cfs_debug_mesh_segment_distance_contracted");
 }
 
 // dist_arm_surf_200i for N poses (host arrays): d[N], linkid[N] (1-based, may be NULL), points[N x 6] (may be NULL)

@@ -9,7 +9,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-TOL_DIST = 1e-12      # metres: same formulas, fp64, only FMA contraction differs
+TOL_DIST = 1e-12      # metres: same formulas, fp64; dist_arm and the linearisation contract multiply-adds (the query does not)
 TOL_RAD = 1e-7        # waypoints of a whole solve (bar: 1e-5)
 
 
