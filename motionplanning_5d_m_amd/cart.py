@@ -92,20 +92,29 @@ class CartesianPath(_ToolSolver):
         over the path's configurations); rows of unsolved targets hold NaN.  want_candidates: also cand_status (0 complete | 1 a
         step did not converge | 2 collision | 3 numeric | 4 joint jump | 5 no start), cand_done, cand_iter (T, R), cand_end
         (T, R, njoint) and cand_path (T, R, steps+1, njoint; NaN after cand_done)."""
+        return self._host(start, target_pos, target_axis, theta_ref, start_state, want_candidates, None)
+
+    def _host(self, start, pos, axis, theta_ref, start_state, want_candidates, table):
+        """trace (table None: pos / axis are target_pos / target_axis) and follow (table True: they are path_pos / path_axis): the
+        arrays checked, the results allocated, one call of the host-array entry"""
         s = self._starts(start)
-        T, tp, ta, tr = self._targets(target_pos, target_axis, theta_ref)
+        if table is None:
+            T, tp, ta, tr = self._targets(pos, axis, theta_ref)
+            M, rows, entry, name = (), None, "cfs_cart_path", "target_pos"
+        else:
+            T, npts, tp, ta = self._table(pos, axis)
+            tr = self._ref(theta_ref, T)
+            M, rows, entry, name = (npts,), (npts - 1) * self.steps + 1, "cfs_cart_follow", "path_pos"
         if s.shape[0] != T:
-            raise ValueError(f"start has {s.shape[0]} targets, target_pos {T}")
+            raise ValueError(f"start has {s.shape[0]} targets, {name} {T}")
         R = s.shape[1]
         ss = self._start_state(start_state, T, R)
-        r = self._results(self._shapes(T, R), want_candidates)
+        r = self._results(self._shapes(T, R, rows), want_candidates)
         o = _args.fill(_lib.cfs_cart_out(), r)
         d = self._desc(ta is not None, R, self.obs, self.D)
-        tail = (T, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o))
-        if self.meshes:
-            _lib.check(_lib.lib().cfs_cart_path_mesh(C.byref(d), *self._mesh_table(), *tail))
-        else:
-            _lib.check(_lib.lib().cfs_cart_path(C.byref(d), *tail))
+        tail = (T, *M, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o))
+        mesh = self._mesh_table() if self.meshes else ()
+        _lib.check(getattr(_lib.lib(), entry + ("_mesh" if self.meshes else ""))(C.byref(d), *mesh, *tail))
         return r
 
     def _starts(self, start):
@@ -175,10 +184,8 @@ class CartesianPath(_ToolSolver):
                 o.cand_path = _ptr(work)
             d = self._desc(ta is not None, R, obs, D)
             tail = (T, *M, _ptr(s), _ptr(ss), _ptr(tp), _ptr(ta), _ptr(tr), C.byref(o), C.c_void_p(stream.cuda_stream))
-            if self.meshes:
-                _lib.check(getattr(_lib.lib(), entry + "_mesh_device")(C.byref(d), *self._mesh_table(), *tail))
-            else:
-                _lib.check(getattr(_lib.lib(), entry + "_device")(C.byref(d), *tail))
+            mesh = self._mesh_table() if self.meshes else ()
+            _lib.check(getattr(_lib.lib(), entry + ("_mesh_device" if self.meshes else "_device"))(C.byref(d), *mesh, *tail))
             self._record(stream, s, ss, tp, ta, tr, work)
         return r
 
@@ -198,7 +205,10 @@ class CartesianPath(_ToolSolver):
         candidates of an inverse-kinematics call at the first pose.  Unlike trace, row 0 is a pose to reach: a start that does not
         solve the first pose iterates towards it, and a start farther from its solution than max_joint_step is a joint jump.
         Returns trace's namespace with N rows in path and cand_path; theta is the winner's start."""
-        s = self._starts(start)
+        return self._host(start, path_pos, path_axis, theta_ref, start_state, want_candidates, True)
+
+    def _table(self, path_pos, path_axis):
+        """the host arrays of the path tables, validated: (T, M, path_pos (T, M, 3), path_axis (T, M, 3) | None)"""
         try:
             pp = np.array(path_pos, dtype=np.float64)
         except (TypeError, ValueError):
@@ -225,21 +235,7 @@ class CartesianPath(_ToolSolver):
             if not (np.linalg.norm(pa, axis=2) > 0).all():
                 raise ValueError("a path_axis row is zero")
             pa = _f64(pa)
-        tr = self._ref(theta_ref, T)
-        if s.shape[0] != T:
-            raise ValueError(f"start has {s.shape[0]} targets, path_pos {T}")
-        R = s.shape[1]
-        ss = self._start_state(start_state, T, R)
-        pp = _f64(pp)
-        r = self._results(self._shapes(T, R, (M - 1) * self.steps + 1), want_candidates)
-        o = _args.fill(_lib.cfs_cart_out(), r)
-        d = self._desc(pa is not None, R, self.obs, self.D)
-        tail = (T, M, _ptr(s), _ptr(ss), _ptr(pp), _ptr(pa), _ptr(tr), C.byref(o))
-        if self.meshes:
-            _lib.check(_lib.lib().cfs_cart_follow_mesh(C.byref(d), *self._mesh_table(), *tail))
-        else:
-            _lib.check(_lib.lib().cfs_cart_follow(C.byref(d), *tail))
-        return r
+        return T, M, _f64(pp), pa
 
     def follow_device(self, start, path_pos, path_axis=None, theta_ref=None, start_state=None, want_candidates=False, stream=None):
         """follow() on CUDA tensors of the solver's device: start (T, R, njoint), path_pos (T, M, 3), path_axis (T, M, 3) or None,

@@ -1,9 +1,11 @@
-// cfs_cart.hip -- batched straight-line tool paths from IK candidates (include/cfs_hip.h, "Cartesian paths").
+// cfs_cart.hip -- batched tool paths from IK candidates: straight lines (include/cfs_hip.h, "Cartesian paths") and
+// polylines of tool poses ("Tool paths"; section 27), traced by one kernel, cfs_cart_kernel<NJ, POLY>.
 //
 // The reference has no Cartesian moves: its drivers plan between joint vectors.  A pick ends with a straight tool move from a
 // pre-grasp pose into the grasp (a controller's LIN move); this unit asks, for every configuration inverse kinematics found for the
 // pre-grasp, whether that move exists inside the joint ranges, without a joint flip and free of the line obstacles, and keeps per
-// target the candidate nearest to a reference configuration whose line completes.
+// target the candidate nearest to a reference configuration whose line completes.  A glue bead or a weld seam is a chain of such moves:
+// a polyline of tool poses per target, asked the same question as a whole.
 //
 // MI355X mapping: cfs_ik_kernel's.  One 64-lane wavefront owns one target, one lane one candidate; four targets per 256-thread
 // workgroup; the robot, the obstacle rows and their margins are staged once per workgroup in LDS behind the only block barrier.  A
@@ -14,6 +16,10 @@
 // arithmetic of a lane is that of the nested form (for every step: restart from theta_{k-1}).  Lanes that have ended idle under the
 // EXEC mask until a ballot says that none is running; the selection is IK's wave argmin on (cost, lane) by xor shuffles.  No atomics,
 // no block barrier after the staging, no host round trip.  Everything is fp64; every loop over joints is unrolled at compile time.
+// The start load, the pass and the epilogue are one text for both kinds of path; `if constexpr (POLY)` stands only where they differ.  A
+// line's row 0 is the start itself and the lane holds the start's pose, the line's origin, for the whole run.  A polyline's row 0 is a
+// pose to reach like every later row and is jump-tested against the start; the head of a pass reads the two poses of the lane's segment
+// from the target's table (follow_row) and nothing of the path is held.  The outputs have one convention, K = rows - 1.
 //
 // Mesh obstacles (cfs_cart_path_mesh*).  The trace does not depend on collisions, so the meshes are tested BEHIND
 // it on the same stream, in two more launches that read what it left in cand_path (the workspace between the launches):
@@ -27,12 +33,9 @@
 //                                    off cand_path alone and the optional cand_status / cand_done need not exist.  Cost of the start,
 //                                    the xor-shuffle argmin, then the winner's clearance: the (row, mesh, link) triples strided over
 //                                    the lanes, one exact unbounded mesh_query each, a wave min with the line clearance of the rows.
-// cfs_cart_kernel is untouched: at 256 VGPR + 253 AGPR for NJ = 5 a hierarchy walk inside its pass would put the iteration in scratch.
+// They run behind either instantiation of the trace.  The trace itself holds no mesh walk: at 256 VGPR + 249 AGPR for the line with
+// NJ = 5 a hierarchy walk inside its pass would put the iteration in scratch.
 //
-// Tool paths (cfs_cart_follow*): cfs_cart_follow_kernel<NJ> is the same mapping and the same one-loop pass for a
-// polyline of tool poses per target.  Row 0 is a pose to reach like every later row and is jump-tested against the start; the head of
-// a pass reads the two poses of the lane's segment from the target's table instead of holding a line origin.  Its outputs keep
-// cfs_cart_kernel's conventions with K = rows - 1, so the two mesh kernels above run behind it unchanged.
 // What the kernels here share with cfs_ik.hip is called, not restated: ik_stage, ik_converged, ik_cost, ik_argmin
 // (cfs_ik_dev.h), mesh_hit, mesh_pair_clearance, mesh_wave_min (cfs_mesh_hit_dev.h) and the descriptor checks of cfs_tool_host.h.
 #include "cfs_mesh_hit_dev.h"
@@ -65,198 +68,6 @@ struct CartParams {
     double *cand_end, *cand_path;                             // T x R x NJ, T x R x (K+1) x NJ
 };
 
-template <int NJ>
-__global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartParams P)
-{
-    __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
-    __shared__ double s_obs[CFS_MAX_OBS * 6];
-    __shared__ double s_D[CFS_MAX_OBS];
-    // the only block barrier is in there: whole waves may leave after it
-    const DevRobot *rb = ik_stage<WV * CART_WAVES>(P.rb, s_rb, P.nobs, P.obs, P.D, s_obs, s_D);
-    const int lane = threadIdx.x % WV, t = blockIdx.x * CART_WAVES + threadIdx.x / WV;
-    if (t >= P.T) return;
-    const bool use_axis = P.use_axis != 0;
-    const bool active = lane < P.R;                           // lanes >= candidates never run and enter the reductions with neutral values
-    const size_t row = (size_t)t * P.R + (active ? lane : 0);
-    const size_t prow = row * (size_t)(P.K + 1);              // the candidate's first row of cand_path
-
-    double th[NJ];
-    int st = 5;                                               // -1: running
-    if (active) {
-        bool ok = !P.start_state || P.start_state[row] == 0;
-#pragma unroll
-        for (int c = 0; c < NJ; ++c) {
-            th[c] = P.start[row * NJ + c];
-            ok = ok && th[c] >= P.lo[c] && th[c] <= P.hi[c];  // false for a NaN and for +-inf
-        }
-        if (ok) st = -1;
-    }
-    if (st != -1) {
-#pragma unroll
-        for (int c = 0; c < NJ; ++c) th[c] = __builtin_nan("");
-    }
-
-    // step 0 is the start itself: its "line point" is its own pose, so its residual is zero and the first pass books it (collision
-    // test, row 0 of the path) like every later step
-    double p0[3] = {0.0, 0.0, 0.0}, a0[3] = {0.0, 0.0, 0.0}, pk[3], ak[3] = {0.0, 0.0, 0.0}, prev[NJ], r[6], F = 0.0, A[NJ * NJ], g[NJ];
-    double lam = IK_LAMBDA0, cmin = INFINITY;
-    int it = 0, itsum = 0, k = 0, done = 0, nrow = 0;         // nrow: rows of cand_path written (accepted configurations)
-#pragma unroll
-    for (int q = 0; q < 6; ++q) r[q] = 0.0;
-#pragma unroll
-    for (int c = 0; c < NJ; ++c) { prev[c] = th[c]; g[c] = 0.0; }
-#pragma unroll
-    for (int q = 0; q < NJ * NJ; ++q) A[q] = 0.0;
-    if (st < 0) {
-        double tw[NJ * 6];
-        ik_pose<NJ>(rb, P.tool, P.axis, th, p0, a0, tw);
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { pk[q] = p0[q]; ak[q] = a0[q]; }
-
-    for (;;) {
-        // ---- head of the pass: a step whose point is reached is booked and the next one set up -----------------------------
-        if (st < 0) {
-            if (!(F < INFINITY)) st = 3;                                                        // step 1
-            else if (ik_converged(r, use_axis, P.tol_pos, P.tol_axis)) {                        // step 2: theta_k = th
-                if (k > 0) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int c = 0; c < NJ; ++c) s = fabs(th[c] - prev[c]) > s ? fabs(th[c] - prev[c]) : s;
-                    if (s > P.max_joint_step) st = 4;
-                }
-                if (st < 0) {
-                    const double c = ik_clearance<NJ>(rb, th, P.nobs, s_obs, s_D);
-                    if (!(c >= 0.0)) st = 2;
-                    else if (c < cmin) cmin = c;
-                }
-                if (st < 0) {
-                    done = k;
-                    nrow = k + 1;
-                    if (P.cand_path) {
-#pragma unroll
-                        for (int c = 0; c < NJ; ++c) P.cand_path[(prow + k) * NJ + c] = th[c];
-                    }
-                    if (k == P.K) st = 0;
-                    else {
-                        ++k;
-                        // the target is read again at every step rather than held: twelve registers the iteration needs
-                        const double s = (double)k / (double)P.K;
-#pragma unroll
-                        for (int q = 0; q < 3; ++q) pk[q] = p0[q] + s * (P.target_pos[(size_t)t * 3 + q] - p0[q]);
-                        if (use_axis) {
-                            double ta[3], b[3];
-#pragma unroll
-                            for (int q = 0; q < 3; ++q) ta[q] = P.target_axis[(size_t)t * 3 + q];
-                            const double tn = sqrt(ta[0] * ta[0] + ta[1] * ta[1] + ta[2] * ta[2]);
-#pragma unroll
-                            for (int q = 0; q < 3; ++q) b[q] = (1.0 - s) * a0[q] + s * (ta[q] / tn);
-                            const double n = sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
-                            if (!(n > CART_AXIS_MIN)) st = 3;
-                            else { ak[0] = b[0] / n; ak[1] = b[1] / n; ak[2] = b[2] / n; }
-                        }
-                        if (st < 0) {                                                           // the restart of step k from theta_{k-1}
-                            double p[3], a[3], tw[NJ * 6];
-#pragma unroll
-                            for (int c = 0; c < NJ; ++c) prev[c] = th[c];
-                            ik_pose<NJ>(rb, P.tool, P.axis, th, p, a, tw);
-                            ik_residual(p, a, pk, ak, use_axis, r, &F);
-                            ik_normal<NJ>(tw, p, a, r, use_axis, A, g);
-                            lam = IK_LAMBDA0;
-                            it = 0;
-                        }
-                    }
-                }
-            }
-        }
-        if (__ballot(st < 0) == 0ull) break;
-        // ---- one iteration of the current step (a step set up above is tested before it iterates) ---------------------------
-        if (st < 0) {
-            if (!(F < INFINITY)) st = 3;                                                        // step 1
-            else if (ik_converged(r, use_axis, P.tol_pos, P.tol_axis)) {}                       // step 2: the next pass books it
-            else if (it >= P.max_iter) st = 1;                                                  // step 3
-            else {                                                                              // cfs_ik_kernel's steps 4-8, statement for statement
-                double delta[NJ], trial[NJ];
-                if (!ik_solve_step<NJ>(A, g, lam, delta)) st = 3;                               // step 4
-                else {
-                    double s = 0.0;
-#pragma unroll
-                    for (int c = 0; c < NJ; ++c) s = fabs(delta[c]) > s ? fabs(delta[c]) : s;
-                    const double sc = s > IK_STEP_CAP ? IK_STEP_CAP / s : 1.0;                  // step 5
-#pragma unroll
-                    for (int c = 0; c < NJ; ++c) {
-                        const double x = th[c] + (s > IK_STEP_CAP ? delta[c] * sc : delta[c]);
-                        trial[c] = x < P.lo[c] ? P.lo[c] : (x > P.hi[c] ? P.hi[c] : x);        // step 6
-                    }
-                    double p2[3], a2[3], tw2[NJ * 6], r2[6], F2;
-                    ik_pose<NJ>(rb, P.tool, P.axis, trial, p2, a2, tw2);
-                    ik_residual(p2, a2, pk, ak, use_axis, r2, &F2);
-                    if (F2 < F) {                                                               // step 7
-#pragma unroll
-                        for (int c = 0; c < NJ; ++c) th[c] = trial[c];
-#pragma unroll
-                        for (int q = 0; q < 6; ++q) r[q] = r2[q];
-                        F = F2;
-                        ik_normal<NJ>(tw2, p2, a2, r2, use_axis, A, g);
-                        lam = lam / 10.0 > IK_LAMBDA_MIN ? lam / 10.0 : IK_LAMBDA_MIN;
-                    } else {
-                        lam = lam * 10.0 < IK_LAMBDA_MAX ? lam * 10.0 : IK_LAMBDA_MAX;
-                    }
-                    ++it; ++itsum;                                                              // step 8
-                }
-            }
-        }
-    }
-
-    // ---- cost of the START, candidate outputs, selection -------------------------------------------------------------------
-    const double nan = __builtin_nan("");
-    double cost = INFINITY;
-    if (st == 0) {
-        const double s = ik_cost<NJ>(P.w, P.start + row * NJ, P.theta_ref + (size_t)t * NJ);
-        if (s < INFINITY) cost = s; else st = 3;
-    }
-    if (active) {
-        if (P.cand_status) P.cand_status[row] = st;
-        if (P.cand_done) P.cand_done[row] = done;
-        if (P.cand_iter) P.cand_iter[row] = itsum;
-        if (P.cand_end) {
-#pragma unroll
-            for (int c = 0; c < NJ; ++c) P.cand_end[row * NJ + c] = th[c];
-        }
-        if (P.cand_path) {
-            for (size_t e = (prow + nrow) * NJ; e < (prow + P.K + 1) * NJ; ++e) P.cand_path[e] = nan;
-        }
-    }
-    const int n_ok = __popcll(__ballot(st == 0));
-    const bool any_start = __ballot(st != 5) != 0ull;
-    int md = done;
-    const int bl = ik_argmin<true>(cost, lane, &md);
-    const bool ok = n_ok > 0;
-    if (ok ? lane == bl : lane == 0) {
-#pragma unroll
-        for (int c = 0; c < NJ; ++c) P.theta[(size_t)t * NJ + c] = ok ? P.start[row * NJ + c] : nan;
-        P.status[t] = ok ? 0 : (any_start ? 1 : 2);
-        if (P.selected) P.selected[t] = ok ? lane : -1;
-        if (P.n_ok) P.n_ok[t] = n_ok;
-        if (P.n_done) P.n_done[t] = md;
-        if (P.clearance) P.clearance[t] = ok ? cmin : nan;
-    }
-    if (P.path) {
-        // the winner's rows of cand_path (the launch's workspace), copied by the whole wave: the fence makes the winner's stores
-        // visible to the other lanes of its wave
-        const size_t n = (size_t)(P.K + 1) * NJ;
-        double *dst = P.path + (size_t)t * n;
-        if (ok) {
-            __threadfence();
-            const double *src = P.cand_path + ((size_t)t * P.R + bl) * n;
-            for (size_t e = lane; e < n; e += WV) dst[e] = src[e];
-        } else {
-            for (size_t e = lane; e < n; e += WV) dst[e] = nan;
-        }
-    }
-}
-
-// ---- tool paths: polylines of tool poses (cfs_cart_follow*) -------------------------------------------------
 // (p_n, a_n) of row n >= 1 of a polyline, on segment i with ksub sub-steps: both poses of the segment are read from the target's table
 // here, where they are needed, and not held (the table is the wave's, so lanes on the same segment read the same addresses).  False:
 // the interpolated axis is undefined.
@@ -278,12 +89,17 @@ __device__ __forceinline__ bool follow_row(const double *pos, const double *axs,
     return true;
 }
 
-// cfs_cart_kernel's mapping and its one-loop pass for a polyline: P.target_pos / P.target_axis are the tables (T x M x 3), P.K + 1 = N
-// the rows of a path, ksub the sub-steps of a segment.  What differs from cfs_cart_kernel: row 0 is a pose to reach like every later
-// row (set up before the loop, jump-tested against the start), and there is no per-candidate line origin, so nothing of the line is
-// held across the iteration: the lane keeps the row's pose (pk, ak), its row and its segment.
-template <int NJ>
-__global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_follow_kernel(const CartParams P, const int ksub)
+// the start's own pose, a line's origin: the line instantiation holds it for the whole run, the polyline's has none
+template <bool POLY> struct CartOrigin { double p[3] = {0.0, 0.0, 0.0}, a[3] = {0.0, 0.0, 0.0}; };
+template <> struct CartOrigin<true> {};
+
+// The trace of both entries.  A path has P.K + 1 rows; a lane keeps the pose (pk, ak) of the row it works on and the number of rows it
+// has written.  POLY false, the straight line of cfs_cart_path*: P.target_pos / P.target_axis are T x 3, row 0 is the start itself
+// (its residual is zero, so the first pass books it) and the lane holds the start's pose, the line's origin o, for the whole run;
+// ksub is not read.  POLY true, the polyline of cfs_cart_follow*: they are the tables (T x M x 3), ksub the sub-steps of a segment,
+// row 0 a pose to reach like every later row (jump-tested against the start), and nothing of the path is held: the lane keeps its segment.
+template <int NJ, bool POLY>
+__global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_kernel(const CartParams P, const int ksub)
 {
     __shared__ __attribute__((aligned(16))) double s_rb[sizeof(DevRobot) / 8];
     __shared__ double s_obs[CFS_MAX_OBS * 6];
@@ -296,7 +112,8 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_follow_kernel(const 
     const bool active = lane < P.R;                           // lanes >= candidates never run and enter the reductions with neutral values
     const size_t row = (size_t)t * P.R + (active ? lane : 0);
     const size_t prow = row * (size_t)(P.K + 1);              // the candidate's first row of cand_path
-    const size_t tab = (size_t)t * (size_t)(P.K / ksub + 1) * 3;                                // the target's rows of the two tables
+    size_t tab = (size_t)t * 3;                               // the target's row of target_pos / target_axis,
+    if constexpr (POLY) tab *= (size_t)(P.K / ksub + 1);      // or its first row of the two tables
 
     double th[NJ];
     int st = 5;                                               // -1: running
@@ -315,16 +132,26 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_follow_kernel(const 
     }
 
     double pk[3] = {0.0, 0.0, 0.0}, ak[3] = {0.0, 0.0, 0.0}, prev[NJ], r[6], F = 0.0, A[NJ * NJ], g[NJ];
+    [[maybe_unused]] CartOrigin<POLY> o;
     double lam = IK_LAMBDA0, cmin = INFINITY;
-    int it = 0, itsum = 0, seg = 0, nrow = 0;                 // nrow: rows of cand_path written = the row the lane works on
+    int it = 0, itsum = 0, seg = 0, nrow = 0;                 // nrow: rows of cand_path written = the row the lane works on; seg: POLY
 #pragma unroll
     for (int q = 0; q < 6; ++q) r[q] = 0.0;
 #pragma unroll
     for (int c = 0; c < NJ; ++c) { prev[c] = th[c]; g[c] = 0.0; }
 #pragma unroll
     for (int q = 0; q < NJ * NJ; ++q) A[q] = 0.0;
-    // row 0 is (P_0, A_0 normalised): set up from the start like any later row from the row before it
-    if (st < 0) {
+    if constexpr (!POLY) {
+        // row 0 is the start itself: its pose is its own, so its residual is zero and the first pass books it (collision test, row 0
+        // of the path; the jump test against itself passes) like every later row
+        if (st < 0) {
+            double tw[NJ * 6];
+            ik_pose<NJ>(rb, P.tool, P.axis, th, o.p, o.a, tw);
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { pk[q] = o.p[q]; ak[q] = o.a[q]; }
+    } else if (st < 0) {
+        // row 0 is (P_0, A_0 normalised): set up from the start like any later row from the row before it
 #pragma unroll
         for (int q = 0; q < 3; ++q) pk[q] = P.target_pos[tab + q];
         if (use_axis) {
@@ -347,7 +174,7 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_follow_kernel(const 
                 double s = 0.0;
 #pragma unroll
                 for (int c = 0; c < NJ; ++c) s = fabs(th[c] - prev[c]) > s ? fabs(th[c] - prev[c]) : s;
-                if (s > P.max_joint_step) st = 4;                                               // row 0: against the start
+                if (s > P.max_joint_step) st = 4;                                               // row 0: against the start (a line's: itself)
                 if (st < 0) {
                     const double c = ik_clearance<NJ>(rb, th, P.nobs, s_obs, s_D);
                     if (!(c >= 0.0)) st = 2;
@@ -361,8 +188,26 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_follow_kernel(const 
                     if (nrow == P.K) { st = 0; ++nrow; }
                     else {
                         ++nrow;
-                        if (nrow - seg * ksub > ksub) ++seg;                                    // row nrow lies on segment (nrow-1) div ksub
-                        if (!follow_row(P.target_pos + tab, P.target_axis + tab, nrow, seg, ksub, use_axis, pk, ak)) st = 3;
+                        // the poses are read again at every row rather than held: twelve registers the iteration needs
+                        if constexpr (!POLY) {
+                            const double s = (double)nrow / (double)P.K;
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) pk[q] = o.p[q] + s * (P.target_pos[tab + q] - o.p[q]);
+                            if (use_axis) {
+                                double ta[3], b[3];
+#pragma unroll
+                                for (int q = 0; q < 3; ++q) ta[q] = P.target_axis[tab + q];
+                                const double tn = sqrt(ta[0] * ta[0] + ta[1] * ta[1] + ta[2] * ta[2]);
+#pragma unroll
+                                for (int q = 0; q < 3; ++q) b[q] = (1.0 - s) * o.a[q] + s * (ta[q] / tn);
+                                const double n = sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+                                if (!(n > CART_AXIS_MIN)) st = 3;
+                                else { ak[0] = b[0] / n; ak[1] = b[1] / n; ak[2] = b[2] / n; }
+                            }
+                        } else {
+                            if (nrow - seg * ksub > ksub) ++seg;                                // row nrow lies on segment (nrow-1) div ksub
+                            if (!follow_row(P.target_pos + tab, P.target_axis + tab, nrow, seg, ksub, use_axis, pk, ak)) st = 3;
+                        }
                         if (st < 0) {                                                           // the restart of row nrow from theta_{nrow-1}
                             double p[3], a[3], tw[NJ * 6];
 #pragma unroll
@@ -416,7 +261,7 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_follow_kernel(const 
         }
     }
 
-    // ---- cost of the START, candidate outputs, selection: cfs_cart_kernel's, with K = N - 1 ---------------------------------
+    // ---- cost of the START, candidate outputs, selection -------------------------------------------------------------------
     const double nan = __builtin_nan("");
     double cost = INFINITY;
     if (st == 0) {
@@ -464,13 +309,14 @@ __global__ __launch_bounds__(WV * CART_WAVES) void cfs_cart_follow_kernel(const 
     }
 }
 
-// ksub == 0: the straight line of cfs_cart_path; otherwise the polyline kernel with ksub sub-steps per segment
+// ksub == 0: the straight line of cfs_cart_path; otherwise the polyline with ksub sub-steps per segment
 hipError_t launch_cart(int nj, const CartParams &p, int ksub, hipStream_t s)
 {
     return cfs_for_nj(nj, [&](auto N) {
+        constexpr int NJ = decltype(N)::value;
         const dim3 grid((p.T + CART_WAVES - 1) / CART_WAVES), block(WV * CART_WAVES);
-        if (ksub) hipLaunchKernelGGL(cfs_cart_follow_kernel<decltype(N)::value>, grid, block, 0, s, p, ksub);
-        else hipLaunchKernelGGL(cfs_cart_kernel<decltype(N)::value>, grid, block, 0, s, p);
+        if (ksub) hipLaunchKernelGGL((cfs_cart_kernel<NJ, true>), grid, block, 0, s, p, ksub);
+        else hipLaunchKernelGGL((cfs_cart_kernel<NJ, false>), grid, block, 0, s, p, ksub);
         return hipGetLastError();
     });
 }

@@ -1,8 +1,9 @@
 // cfs_ik_dev.h -- device functions of the inverse-kinematics iteration (include/cfs_hip.h, "inverse kinematics"), shared by cfs_ik.hip
 // and cfs_cart.hip: the leaves (pose, residual, analytic Jacobian, the damped step, the line-obstacle clearance) and what the kernels
 // of both units do with them -- the workgroup staging (ik_stage), the convergence test (ik_converged), the cost
-// (ik_cost) and the wave argmin of the selection (ik_argmin).  Steps 4-8 of the iteration stand in the two kernels themselves: as a
-// function here they moved the register allocation of both NJ = 5 kernels and cost them 2 %.  Every loop over
+// (ik_cost) and the wave argmin of the selection (ik_argmin).  Steps 4-8 of the iteration stand in the two kernels themselves,
+// cfs_ik_kernel and cfs_cart_kernel: as a function here they moved the register allocation of the NJ = 5 instantiations and cost them
+// 2 %.  Every loop over
 // joints is unrolled at compile time: NJ is a template parameter.
 #pragma once
 #include "cfs_geom_dev.h"
@@ -151,7 +152,8 @@ __device__ __forceinline__ void ik_errors(const double *r, double *ep, double *e
 }
 
 // step 2: the pose is reached.  Both comparisons are made before they are combined: with `&&` / `||` the compiler moves the second
-// norm into a branch of its own, and cfs_cart_kernel<6>, the one kernel with scratch, then takes 16 B per lane more of it.
+// norm into a branch of its own, and the line instantiation of cfs_cart_kernel<6, *>, the kernels with scratch, then takes 16 B per
+// lane more of it.
 __device__ __forceinline__ bool ik_converged(const double *r, bool use_axis, double tol_pos, double tol_axis)
 {
     double ep, ea;

@@ -5,7 +5,8 @@ The statements are the ones that stood in both units, so every output must equal
 The recordings tests/golden/tool_solver_*.npy were written by `tests/tools/record_tool_solver.py` with the library built from the
 commit BEFORE the change; the inputs are recorded with them.  Comparisons are exact equality of the bytes of every output field of
 the host-array entries (NaN rows of unsolved targets and of unfinished paths included), one record per target.  Cases, shapes and
-flag settings: tests/tool_solver_cases.py."""
+flag settings: tests/tool_solver_cases.py.  The follow_* cases pin the polyline trace the same way: they were recorded with the library
+built from the commit BEFORE the line and the polyline kernel became cfs_cart_kernel<NJ, POLY> (DESIGN.md sections 23 and 27)."""
 import json
 import os
 

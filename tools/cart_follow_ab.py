@@ -12,6 +12,8 @@ launch (median, min, max), the share of started candidates that complete, the it
 per-lane cand_iter; and the ratio follow_m2 / trace of the medians, measured in the same run, next to the run-to-run spread of both.
 
     python tools/cart_follow_ab.py [--targets T] [--restarts R] [--approach M] [--side M] [--repeats N] [--warmup W] [--json out.json]
+                                   [--lib NAME.so]
+--lib: the build of the library to time (default libcfs_hip.so; a file next to it), for A/B runs against a build of another commit.
 """
 import argparse
 import json
@@ -25,6 +27,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import motionplanning_5d_m_amd as pkg  # noqa: E402
+from motionplanning_5d_m_amd import _lib  # noqa: E402
 from ik_ab import configs, timed  # noqa: E402
 import rrt_mesh_reference as M  # noqa: E402
 
@@ -38,7 +41,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "cart_follow_ab.json"))
+    ap.add_argument("--lib", default="libcfs_hip.so")
     a = ap.parse_args()
+    _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), a.lib)            # before the first lib() call
     dev = torch.device("cuda", 0)
     t = lambda x: torch.tensor(np.ascontiguousarray(x), dtype=torch.float64, device=dev)  # noqa: E731
     pobs, s, *_ = pkg.RRTstar_problem()
@@ -92,7 +97,7 @@ def main():
     print(json.dumps(ratios))
     if a.json:
         with open(a.json, "w") as f:
-            json.dump(dict(tool="tools/cart_follow_ab.py", device=torch.cuda.get_device_name(0), warmup=a.warmup, repeats=a.repeats,
+            json.dump(dict(tool="tools/cart_follow_ab.py", lib=a.lib, device=torch.cuda.get_device_name(0), warmup=a.warmup, repeats=a.repeats,
                            approach_m=a.approach, side_m=a.side, calls=rows, ratios=ratios), f, indent=1)
 
 
