@@ -1003,6 +1003,12 @@ int cfs_debug_stamps(cfs_problem *p, int B, unsigned long long *out);
  * cfs_debug_trace_read: out = (cap+1)*8 doubles (HOST), out[0] = number of records */
 int cfs_debug_trace_begin(cfs_problem *p, int b, int cap);
 int cfs_debug_trace_read(cfs_problem *p, double *out);
+/* the launch-order pre-pass alone (cfs_set_launch_order, automatic order), for B in 1..max_batch whatever the device's compute
+ * units: key[b] = (waypoint, line obstacle) pairs of x_init[b] whose clearance is below the obstacle's margin, order = the problems
+ * by descending key, ties by index, exactly as a solve of these inputs would compute them.  HOST pointers: x_init B x (H*nstate);
+ * obs B x nobs x 6 (B x H x nobs x 6 per waypoint); key, order: B each, either may be NULL, not both.  A handle without a line
+ * obstacle gives zero keys and the identity order.  Synchronises the device. */
+int cfs_debug_launch_order(cfs_problem *p, int B, const double *x_init, const double *obs, int *key, int *order);
 /* log of u after every outer iteration (either solver; the solve itself is unchanged): on != 0 allocates
  * max_batch x MAX_O_ITER x nn doubles; cfs_debug_read_u_log copies the first B problems to `out` (HOST) */
 int cfs_debug_log_u(cfs_problem *p, int on);

@@ -300,6 +300,7 @@ SYMBOLS = [
     ("cfs_debug_stamps", C.c_int, [_P, C.c_int, _P]),
     ("cfs_debug_trace_begin", C.c_int, [_P, C.c_int, C.c_int]),
     ("cfs_debug_trace_read", C.c_int, [_P, _P]),
+    ("cfs_debug_launch_order", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("cfs_debug_log_u", C.c_int, [_P, C.c_int]),
     ("cfs_debug_read_u_log", C.c_int, [_P, C.c_int, _P]),
     ("cfs_debug_rrt_frontier_overflows", C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),

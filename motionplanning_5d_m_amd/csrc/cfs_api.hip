@@ -321,6 +321,17 @@ int cfs_set_launch_order(cfs_problem *p, const int *order, int n)
 
 static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch_out *out, hipStream_t s, hipEvent_t *e4);
 
+// the launch-order pre-pass of B problems of this handle (x_init, obs: DEVICE): the line obstacles are the first nobs - nmesh of
+// every row of `obs`, a per-waypoint handle has one row per waypoint; read by enqueue_solve and by cfs_debug_launch_order
+static OrderParams order_params(const cfs_problem *p, int B, const double *x_init, const double *obs)
+{
+    OrderParams op;
+    op.rb = p->rb.p; op.B = B; op.H = p->d.H; op.nj = p->d.njoint; op.nobs = p->d.nobs - p->nmesh; op.obs_stride = p->d.nobs;
+    op.wp_stride = cfs_moving(p) ? p->d.nobs : 0;
+    op.x_init = x_init; op.obs = obs; op.margin = p->margin.p; op.key = p->okey.p; op.order = p->order.p;
+    return op;
+}
+
 // the handle's part of the mesh linearisation's parameter block (the caller sets x_, status_done and seed_prev)
 static LinMeshParams lin_mesh_params(const cfs_problem *p, int B)
 {
@@ -392,11 +403,7 @@ static int enqueue_solve(cfs_problem *p, const cfs_batch_in *in, const cfs_batch
     const int nline = p->d.nobs - p->nmesh;
     if (p->order_mode == 1 && p->order_n == B) fp.order = p->order_user.p;
     else if (p->order_mode != 2 && !(p->dbg_mask & CFS_DBG_NO_AUTO_ORDER) && B > p->n_cu && nline > 0) {   // also when a given order is for another batch size
-        OrderParams op;
-        op.rb = p->rb.p; op.B = B; op.H = p->d.H; op.nj = nj; op.nobs = nline; op.obs_stride = p->d.nobs;
-        op.wp_stride = cfs_moving(p) ? p->d.nobs : 0;
-        op.x_init = in->x_init; op.obs = in->obs; op.margin = p->margin.p; op.key = p->okey.p; op.order = p->order.p;
-        launch_order(op, s);
+        launch_order(order_params(p, B, in->x_init, in->obs), s);
         fp.order = p->order.p;
     }
     SoftParams sp;
@@ -604,6 +611,29 @@ int cfs_debug_trace_read(cfs_problem *p, double *out)
     CFS_HIPCHK(hipDeviceSynchronize());
     CFS_HIPCHK(hipMemcpy(out, p->trace.p, (size_t)(p->trace_cap + 1) * 8 * sizeof(double), hipMemcpyDeviceToHost));
     return CFS_SUCCESS;
+}
+
+int cfs_debug_launch_order(cfs_problem *p, int B, const double *x_init, const double *obs, int *key, int *order)
+{
+    if (!p || !x_init || !obs || (!key && !order)) return cfs_fail(CFS_ERR_INVALID_ARG, "NULL argument");
+    if (int rc = cfs_check_batch(p, B)) return rc;
+    if (p->d.nobs - p->nmesh == 0) {         // no line obstacle: nothing to count, and a solve launches no pre-pass
+        for (int b = 0; b < B; ++b) {
+            if (key) key[b] = 0;
+            if (order) order[b] = b;
+        }
+        return CFS_SUCCESS;
+    }
+    CFS_HIPCHK(hipSetDevice(p->device));
+    CFS_HIPCHK(hipDeviceSynchronize());      // a solve in flight may still be reading okey / order
+    Stage st;
+    const double *d_x = st.up(x_init, (size_t)B * p->nx), *d_obs = st.up(obs, (size_t)B * cfs_obs_rows(p) * 6);
+    if (st.err != hipSuccess) return st.result("staging");
+    launch_order(order_params(p, B, d_x, d_obs), nullptr);
+    CFS_HIPCHK(hipGetLastError());
+    CFS_HIPCHK(hipStreamSynchronize(nullptr));
+    st.down(key, p->okey.p, (size_t)B); st.down(order, p->order.p, (size_t)B);
+    return st.result("copy back");
 }
 
 int cfs_debug_log_u(cfs_problem *p, int on)

@@ -648,6 +648,18 @@ class CFSBatch:
         _lib.check(self._lib.cfs_debug_trace_read(self._h, _ptr(buf)))
         return buf[8:8 + 8 * int(buf[0])].reshape(-1, 8)
 
+    def launch_order_debug(self, x_init, obs):
+        """(key, order) of the launch-order pre-pass for these B problems, as a solve would compute them (cfs_debug_launch_order):
+        key[b] counts the (waypoint, line obstacle) pairs of x_init[b] closer than the margin, order lists the problems by
+        descending key, ties by index."""
+        x_init, obs = _f64(x_init), _f64(obs)
+        B = x_init.shape[0]
+        assert x_init.shape == (B, self.nx)
+        self._check_obs(obs, B)
+        key, order = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        _lib.check(self._lib.cfs_debug_launch_order(self._h, B, _ptr(x_init), _ptr(obs), _ptr(key), _ptr(order)))
+        return key, order
+
     def log_u(self, on=True):
         """log u after every outer iteration of the next solves (either solver; cfs_debug_log_u)."""
         _lib.check(self._lib.cfs_debug_log_u(self._h, 1 if on else 0))

@@ -104,6 +104,7 @@ def test_round3_entry_points_validate_before_the_device():
     assert lib.cfs_debug_stamps(None, 1, None) == -1
     assert lib.cfs_debug_trace_begin(None, 0, 8) == -1
     assert lib.cfs_debug_log_u(None, 1) == -1
+    assert lib.cfs_debug_launch_order(None, 1, p, p, p, p) == -1
     assert lib.cfs_build_terms_from_ragged_routes_device(None, 1, p, 4, p, p, p, p, p, None) == -1
     from motionplanning_5d_m_amd import rrt
     pobs, s, g, region_g, region_s, off = pkg.RRTstar_problem()

@@ -199,6 +199,16 @@ def test_cost_b_and_get_cost(want_u):
         _same(p, v)
 
 
+def test_launch_order_debug():
+    h, a = _Handle(), _inputs()
+    key, order = h.launch_order_debug(a["x_init"], a["obs"])
+    args = h._lib.only("cfs_debug_launch_order")
+    assert args[:2] == ("handle", B) and len(args) == 6 and len(h._lib.calls) == 1
+    for p, v in zip(args[2:], (a["x_init"], a["obs"], key, order)):
+        _same(p, v)
+    assert key.shape == order.shape == (B,) and key.dtype == order.dtype == np.int32 and key.ctypes.data != order.ctypes.data
+
+
 # ---- the entries without a handle: _lib.lib is the recorder ------------------------------------------------------------------
 IK7 = ("theta", "status", "selected", "n_ok", "err_pos", "err_axis", "clearance")
 IK_CAND = ("cand_theta", "cand_status", "cand_iter")
