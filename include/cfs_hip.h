@@ -972,6 +972,87 @@ int cfs_path_time(const cfs_time_desc *d, int G, int R, int N, const double *pat
 int cfs_path_time_device(const cfs_time_desc *d, int G, int R, int N, const double *paths, const int *state, const cfs_time_out *out,
                          void *stream);
 
+/* ---- Tool-path audit -------------------------------------------------------------------------------------------
+ * "Cartesian paths" and "Tool paths" evaluate their collision rule at the N rows of a path; a controller moves the joints linearly
+ * between the rows ("Path timing" assumes the same).  These entries measure that motion: for G groups of R paths of N rows each
+ * (cfs_cart_out's cand_path with cand_status is accepted as it is, G = T, R = candidates; `path` is the case R = 1) they return, per
+ * path, the clearance from the line obstacles and the deviation of the tool point from the chord, each sampled and each with a bound
+ * that holds between the samples.  No handle.
+ * Motion.  On segment n = 0..N-2 the motion is theta(sigma) = q_n + sigma*d_n, d_n = q_{n+1} - q_n, sigma in [0, 1].  The samples are
+ *   sigma_k = k/S, k = 0..S, S = d->substeps.  The sample sigma = 1 is row n+1 itself, read from the path and not recomputed.
+ * Clearance at a sample: min_j (d_j - D_j), d_j = cfs_dist_arm's distance to obstacle j with its near-zero surrogate: the clearance of
+ *   "inverse kinematics", the number cfs_cart_out.clearance reports.  +inf when nobs = 0.  A NaN sticks.
+ * Per path (all G x R):
+ *   clear_rows   the minimum over the N rows.  For the winner of cfs_cart_path / cfs_cart_follow this is its `clearance`: the same
+ *                expression of the same device functions, in a kernel compiled on its own, so NOT promised bit for bit; the two agree
+ *                to the parity tolerance below (on the shapes tested they are equal).
+ *   clear_path   the minimum over all (N-1)*S + 1 samples.
+ *   s_path, link_path, obs_path   where the first such minimum lies (lowest n, then lowest k): the path parameter n + k/S; the obstacle
+ *                j (0-based) with the smallest d_j - D_j there, the lowest on a tie; the link (1-based) closest to that obstacle,
+ *                cfs_dist_arm's first minimum.  With nobs = 0: s_path = 0, link_path = obs_path = -1.
+ *   clear_lower  the minimum over all sub-intervals [sigma_k, sigma_{k+1}] of every segment of (c_k + c_{k+1})/2 - L_n/(2S), c the
+ *                clearance at the two ends, L_n = max over links k of sum_{m<=k} |d_{n,m}|*rho[m][k], rho the matrix of "clearance
+ *                audit between the waypoints" (the reach of capsule k about the axis of joint m).
+ *                Guarantee: if clear_lower > 0, every capsule axis stays at least D_j + clear_lower away from every obstacle j for
+ *                all sigma of all segments; a positive bound also rules out the near-zero surrogate.  Nothing is claimed for a bound
+ *                that is not positive.  clear_path - clear_lower <= max_n L_n/(2S).
+ *   chord_err    the maximum over all samples of e = |p(theta(sigma_k)) - ((1-sigma_k)*p_n + sigma_k*p_{n+1})|, p the tool point of
+ *                "inverse kinematics" (pose(theta), `tool`), p_n and p_{n+1} the tool points of the two rows: the distance from the
+ *                point a linear Cartesian move commands at the same fraction, which bounds the distance to the chord from above.
+ *                e = 0 at the rows.
+ *   chord_upper  the maximum over the same sub-intervals of max(e_k, e_{k+1}) + A_n/(8*S*S),
+ *                A_n = sum_m sum_l |d_{n,m}|*|d_{n,l}|*rt[max(m,l)], rt[m] = sum_{j=m..njoint-1} len_j + |tool|, len_j the length of
+ *                the translation of link j as rho takes it.  A_n bounds |d^2 p / d sigma^2| on the segment; the second term is the
+ *                error of linear interpolation over a sub-interval of length 1/S.
+ *                Guarantee: the tool point never leaves the same-fraction chord point by more than chord_upper.
+ *   status       the first that applies: 1 not audited (state given and its entry != 0) | 2 a row holds a non-finite value | 0 audited.
+ *                Every floating-point output of a path with status != 0 holds NaN, link_path and obs_path hold -1.
+ *   state_out    the input state where it is non-zero; else 3 where status = 2; else 6 where clear_lower < min_clearance; else 7
+ *                where chord_upper > max_chord; else 0 (a NaN bound fails a threshold that is on).  6 and 7 extend the candidate
+ *                states 0..5 of cfs_cart_out.cand_status, so state_out goes into cfs_path_time's `state` as it is and the soonest
+ *                path is then chosen among those that pass.  With both thresholds off (-inf, +inf) state_out equals state on
+ *                finite paths.
+ * No atomics: the result is deterministic, and a path's results depend on neither G, R nor its position in the batch.
+ * CFS_ERR_INVALID_ARG, nothing written: a NULL descriptor; the robot / njoint refusals of cfs_ik_solve (njoint 2..6); G < 1; R outside
+ * 1..64; N outside 2..257 (a line traced with steps = 1 has two rows); substeps outside 1..64; nobs outside 0..CFS_MAX_OBS; nobs > 0
+ * with a NULL obs or D; a non-finite tool; min_clearance NaN or +inf; max_chord NaN or <= 0; NULL paths, out or out->status; in
+ * cfs_path_audit, whose arrays the host can read, a non-finite obs or D (values of `paths` are not refused: status 2).
+ * cfs_path_audit: HOST pointers throughout, synchronises.  cfs_path_audit_device: obs, D, paths, state and every array of `out` are
+ * DEVICE pointers; enqueued on `stream`, nothing allocated, no synchronisation.
+ * Parity: the device is compared with a CPU restatement within max(1000 x the movement of the restatement's
+ * own outputs under a change of 1e-12 rad in every entry of every row, 1e-10); status, state_out, link_path and obs_path are equal.
+ * Measured: one MI355X, M200i, two line obstacles, 1 024 x 64 paths of 17 rows: 1.91 ms per launch at S = 4,
+ * 2.36 ms at S = 8, 3.25 ms at S = 16. */
+typedef struct cfs_audit_desc {
+    cfs_robot robot;
+    int njoint;             /* 2..6 */
+    double tool[3];         /* tool point in the frame of link njoint */
+    int nobs;               /* 0..CFS_MAX_OBS line obstacles */
+    const double *obs;      /* nobs x 6, rows [l(:,1); l(:,2)] */
+    const double *D;        /* nobs margins */
+    int substeps;           /* S, 1..64 */
+    double min_clearance;   /* finite, or -inf: no test */
+    double max_chord;       /* > 0, or +inf: no test */
+} cfs_audit_desc;
+
+typedef struct cfs_audit_out {  /* G x R each; every array but status may be NULL */
+    double *clear_rows;
+    double *clear_path;
+    double *s_path;
+    double *clear_lower;
+    double *chord_err;
+    double *chord_upper;
+    int *link_path;
+    int *obs_path;
+    int *status;
+    int *state_out;
+} cfs_audit_out;
+
+/* paths: G x R x N x njoint; state: G x R or NULL */
+int cfs_path_audit(const cfs_audit_desc *d, int G, int R, int N, const double *paths, const int *state, const cfs_audit_out *out);
+int cfs_path_audit_device(const cfs_audit_desc *d, int G, int R, int N, const double *paths, const int *state, const cfs_audit_out *out,
+                          void *stream);
+
 /* ---- developer / test entry points -------------------------------------------------------------------
  * No caller of the path needs these; they exist so that every shortcut the solver takes can be switched off and compared
  * under pytest (tests/test_gpu_shortcuts.py), and for the cycle-stamp / step-trace probes under tools/.  All state is per

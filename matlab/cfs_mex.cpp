@@ -68,6 +68,15 @@
 //        also at every row that is a multiple of k, counted from 0).  time and sdot are N x (R*G) (reshape(time, N, R, G)), duration and
 //        status R x G (0 timed | 1 not timed | 2 numeric | 3 stalled | 4 repeated row; NaN rows where not 0), selected 1 x G (1-based, 0
 //        without a timed path), group_status 1 x G
+//   [clear_lower, chord_upper, state_out, status, clear_path, s_path, link_path, obs_path, clear_rows, chord_err] = ...
+//        cfs_mex('path_audit', obs, robot, ROBOT, paths, dims, state, opts)
+//        what joint paths do between their rows (cfs_path_audit, include/cfs_hip.h "Tool-path audit"): paths, dims = [N R G] and state as
+//        for 'path_time', with N >= 2; obs the cell of line obstacles (mesh obstacles are not audited).  opts: substeps (default 8),
+//        min_clearance (m; default -Inf: no test), max_chord (m; default Inf: no test), tool (3 x 1; default the end effector).  Every
+//        output is R x G: the certified clearance and chord deviation, state_out (state, else 3 non-finite | 6 clear_lower <
+//        min_clearance | 7 chord_upper > max_chord | 0: goes into 'path_time' as its state), status (0 audited | 1 not audited | 2
+//        non-finite; NaN where not 0), the sampled clearance with its place (s_path counts rows from 0; link_path 1-based; obs_path
+//        1-based, 0 without obstacles or where not audited), the clearance at the rows and the sampled chord deviation
 //   Cost_b = cfs_mex('cost_b', sys_info, ROBOT)                    % EVAL.get_Cost_b (Lib/EVAL.m:75-78, main_FANUC.m:131-132)
 //   h = cfs_mex('mesh_load_stl', path, scale, map_from_stl)        % Lib/functions/MapFromSTL.m
 //   [dis, points] = cfs_mex('mesh_segment_distance', h, seg6)      % point2surface_dis (M200i/dist_arm_surf_200i.m:21)
@@ -800,6 +809,66 @@ static void path_time(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]
     for (int k = 0; k < 6; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
 }
 
+// what joint paths do between their rows (cfs_path_audit): dims and state as 'path_time' reads them, the obs cell as 'ik' reads it
+static void path_audit(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
+{
+    if (nrhs < 7) mexErrMsgTxt("[clear_lower, chord_upper, state_out, status, clear_path, s_path, link_path, obs_path, clear_rows, chord_err] = cfs_mex('path_audit', obs, robot, ROBOT, paths, dims, state [, opts])");
+    const mxArray *obs = prhs[1], *robot = prhs[2], *opts = nrhs > 7 ? prhs[7] : nullptr;
+    const std::string ROBOT = mxArrayToString(prhs[3]);
+    if (mxGetNumberOfElements(prhs[5]) != 3) mexErrMsgTxt("dims must be [N R G]");
+    for (int q = 0; q < 3; ++q) {                                                     // whole numbers that an int holds, before any cast
+        const double v = mxGetPr(prhs[5])[q];
+        if (!(v >= 1.0 && v <= 1e6) || v != std::floor(v)) mexErrMsgTxt("dims must be three whole numbers [N R G], each in 1..1e6");
+    }
+    const int nj = (int)mxGetM(prhs[4]), N = (int)mxGetPr(prhs[5])[0], R = (int)mxGetPr(prhs[5])[1], G = (int)mxGetPr(prhs[5])[2];
+    if (nj < 2 || nj > 6) mexErrMsgTxt("paths must have 2..6 rows (njoint)");
+    if ((double)R * G > 2147483647.0 || mxGetNumberOfElements(prhs[4]) != (size_t)nj * N * R * G)
+        mexErrMsgTxt("paths must be njoint x N x R x G with dims = [N R G]");
+    std::vector<int> state;
+    if (!mxIsEmpty(prhs[6])) {
+        if ((int)mxGetNumberOfElements(prhs[6]) != R * G) mexErrMsgTxt("state must be R x G or []");
+        state.resize((size_t)R * G);
+        for (int e = 0; e < R * G; ++e) state[e] = (int)mxGetPr(prhs[6])[e];
+    }
+    cfs_audit_desc d;
+    memset(&d, 0, sizeof d);
+    fill_robot(robot, ROBOT.c_str(), nj, d.robot);
+    d.njoint = nj;
+    auto opt = [&](const char *name) -> const mxArray * { const mxArray *f = opts ? mxGetField(opts, 0, name) : nullptr; return f && !mxIsEmpty(f) ? f : nullptr; };
+    auto num = [&](const char *name, double dflt) { const mxArray *f = opt(name); return f ? mxGetScalar(f) : dflt; };
+    const double *cp = d.robot.cap + 6 * (nj - 1);
+    for (int q = 0; q < 3; ++q) d.tool[q] = opt("tool") ? mxGetPr(opt("tool"))[q] : cp[q];
+    d.substeps = (int)num("substeps", 8); d.min_clearance = num("min_clearance", -HUGE_VAL); d.max_chord = num("max_chord", HUGE_VAL);
+    std::vector<double> obs6, D;
+    const int ncell = (int)mxGetNumberOfElements(obs);
+    for (int j = 0; j < ncell; ++j) {
+        const mxArray *o = mxGetCell(obs, j), *fl = o ? mxGetField(o, 0, "l") : nullptr, *fD = o ? mxGetField(o, 0, "D") : nullptr;
+        if (o && mxGetField(o, 0, "mesh")) mexErrMsgTxt("'path_audit' reads line obstacles only: meshes are not audited");
+        if (!fl || !fD || mxGetNumberOfElements(fl) != 6) mexErrMsgIdAndTxt("cfs:obs", "obs{%d} needs .l (3x2) and .D", j + 1);
+        obs6.insert(obs6.end(), mxGetPr(fl), mxGetPr(fl) + 6);
+        D.push_back(mxGetScalar(fD));
+    }
+    d.nobs = (int)D.size(); d.obs = d.nobs ? obs6.data() : nullptr; d.D = d.nobs ? D.data() : nullptr;
+    const size_t np = (size_t)R * G;
+    mxArray *o_f[6];                                                                  // G x R row-major = R x G column-major
+    for (int k = 0; k < 6; ++k) o_f[k] = mxCreateDoubleMatrix(R, G, mxREAL);
+    std::vector<int> link(np), ob(np), status(np), sout(np);
+    cfs_audit_out o;
+    memset(&o, 0, sizeof o);
+    o.clear_lower = mxGetPr(o_f[0]); o.chord_upper = mxGetPr(o_f[1]); o.clear_path = mxGetPr(o_f[2]); o.s_path = mxGetPr(o_f[3]);
+    o.clear_rows = mxGetPr(o_f[4]); o.chord_err = mxGetPr(o_f[5]);
+    o.link_path = link.data(); o.obs_path = ob.data(); o.status = status.data(); o.state_out = sout.data();
+    check(cfs_path_audit(&d, G, R, N, mxGetPr(prhs[4]), state.empty() ? nullptr : state.data(), &o));
+    mxArray *o_i[4];
+    for (int k = 0; k < 4; ++k) o_i[k] = mxCreateDoubleMatrix(R, G, mxREAL);
+    for (size_t e = 0; e < np; ++e) {
+        mxGetPr(o_i[0])[e] = sout[e]; mxGetPr(o_i[1])[e] = status[e]; mxGetPr(o_i[2])[e] = link[e] > 0 ? link[e] : 0;
+        mxGetPr(o_i[3])[e] = ob[e] + 1;                                              // both 1-based; 0 without obstacles or where not audited
+    }
+    mxArray *outs[10] = {o_f[0], o_f[1], o_i[0], o_i[1], o_f[2], o_f[3], o_i[2], o_i[3], o_f[4], o_f[5]};
+    for (int k = 0; k < 10; ++k) { if (k < nlhs || k == 0) plhs[k] = outs[k]; else mxDestroyArray(outs[k]); }
+}
+
 static void cost_b(mxArray *plhs[], int nrhs, const mxArray *prhs[])
 {
     if (nrhs < 3) mexErrMsgTxt("Cost_b = cfs_mex('cost_b', sys_info, ROBOT)");
@@ -855,6 +924,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         cart_path_mesh(nlhs, plhs, nrhs, prhs, true);
     } else if (cmd == "path_time") {
         path_time(nlhs, plhs, nrhs, prhs);
+    } else if (cmd == "path_audit") {
+        path_audit(nlhs, plhs, nrhs, prhs);
     } else if (cmd == "cost_b") {
         cost_b(plhs, nrhs, prhs);
     } else if (cmd == "mesh_load_stl") {

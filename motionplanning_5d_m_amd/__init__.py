@@ -18,9 +18,11 @@ from .cart import CartesianPath  # noqa: F401
 from . import cart  # noqa: F401
 from .timing import PathTimer  # noqa: F401
 from . import timing  # noqa: F401
+from .audit import PathAudit  # noqa: F401
+from . import audit  # noqa: F401
 from .plan import RRTCFSPlanner  # noqa: F401
 from . import plan  # noqa: F401
 
 __all__ = ["CFS_FANUC", "PSGCFS_FANUC", "CHOMP_FANUC", "CFSBatch", "EVAL", "dist_arm", "robotproperty2", "build_sys_info",
            "line_reference", "cubic_resample", "cylinder", "main_FANUC_problem", "main_2L_problem",
-           "RRTstar_CFS_problem", "RRT_FANUC", "s_Parallel_rrt", "RRTstar_problem", "CfsError", "STATUS", "device_count", "lib", "obs_to_array", "obs_traj_to_array", "mesh_pose_array", "to_c_robot", "Mesh", "dist_arm_surf", "mesh", "RRTCFSPlanner", "plan", "IKSolver", "tool_pose", "ik", "CartesianPath", "cart", "PathTimer", "timing"]
+           "RRTstar_CFS_problem", "RRT_FANUC", "s_Parallel_rrt", "RRTstar_problem", "CfsError", "STATUS", "device_count", "lib", "obs_to_array", "obs_traj_to_array", "mesh_pose_array", "to_c_robot", "Mesh", "dist_arm_surf", "mesh", "RRTCFSPlanner", "plan", "IKSolver", "tool_pose", "ik", "CartesianPath", "cart", "PathTimer", "timing", "PathAudit", "audit"]

@@ -38,6 +38,9 @@ IK_CAND_STATUS = {0: "CONVERGED", 1: "MAX_ITER", 2: "IN_COLLISION", 3: "NUMERIC"
 CART_STATUS = {0: "SOLVED", 1: "NO_COMPLETE_LINE", 2: "NO_START"}                      # cfs_cart_out.status
 CART_CAND_STATUS = {0: "COMPLETE", 1: "MAX_ITER", 2: "IN_COLLISION", 3: "NUMERIC", 4: "JOINT_JUMP", 5: "NO_START"}   # cfs_cart_out.cand_status
 TIME_STATUS = {0: "TIMED", 1: "NOT_TIMED", 2: "NUMERIC", 3: "STALLED", 4: "REPEATED_ROW"}                            # cfs_time_out.status
+PATH_AUDIT_STATUS = {0: "AUDITED", 1: "NOT_AUDITED", 2: "NUMERIC"}                                                    # cfs_audit_out.status
+# cfs_audit_out.state_out: cfs_cart_out.cand_status, then what the audit adds
+PATH_AUDIT_STATE = {**CART_CAND_STATUS, 6: "CLEARANCE_NOT_CERTIFIED", 7: "CHORD_NOT_CERTIFIED"}
 
 
 class CfsError(RuntimeError):
@@ -256,6 +259,35 @@ class cfs_time_out(C.Structure):
     ]
 
 
+class cfs_audit_desc(C.Structure):
+    _fields_ = [
+        ("robot", cfs_robot),
+        ("njoint", C.c_int),
+        ("tool", C.c_double * 3),
+        ("nobs", C.c_int),
+        ("obs", C.c_void_p),
+        ("D", C.c_void_p),
+        ("substeps", C.c_int),
+        ("min_clearance", C.c_double),
+        ("max_chord", C.c_double),
+    ]
+
+
+class cfs_audit_out(C.Structure):
+    _fields_ = [
+        ("clear_rows", C.c_void_p),
+        ("clear_path", C.c_void_p),
+        ("s_path", C.c_void_p),
+        ("clear_lower", C.c_void_p),
+        ("chord_err", C.c_void_p),
+        ("chord_upper", C.c_void_p),
+        ("link_path", C.c_void_p),
+        ("obs_path", C.c_void_p),
+        ("status", C.c_void_p),
+        ("state_out", C.c_void_p),
+    ]
+
+
 # every symbol include/cfs_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -342,6 +374,8 @@ SYMBOLS = [
                                               C.POINTER(cfs_cart_out), _P]),
     ("cfs_path_time", C.c_int, [C.POINTER(cfs_time_desc), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(cfs_time_out)]),
     ("cfs_path_time_device", C.c_int, [C.POINTER(cfs_time_desc), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(cfs_time_out), _P]),
+    ("cfs_path_audit", C.c_int, [C.POINTER(cfs_audit_desc), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(cfs_audit_out)]),
+    ("cfs_path_audit_device", C.c_int, [C.POINTER(cfs_audit_desc), C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(cfs_audit_out), _P]),
 ]
 
 # cfs_debug_set_options mask bits (include/cfs_hip.h)

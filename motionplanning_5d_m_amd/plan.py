@@ -31,6 +31,7 @@ from .cart import MAX_STEPS, CartesianPath
 from .ik import IKSolver
 from .rrt import RRT_FANUC
 from .timing import MAX_ROWS, MIN_ROWS, PathTimer
+from .audit import MAX_SUBSTEPS, PathAudit
 from .robotproperty2 import robotproperty2
 from .solvers import SOLVE_OUT, CFSBatch, _infeasible_args, _joint_limits_array, obs_meshes, obs_to_array
 from .sysinfo import RRTstar_CFS_problem
@@ -166,7 +167,7 @@ class RRTCFSPlanner:
 
     # ---- Cartesian goals ---------------------------------------------------------------------------------------------------
     def plan_to_pose(self, x0, target_pos, target_axis=None, seed=0, ik_options=None, ik_meshes=False, approach=None, approach_dir=None,
-                     approach_steps=16, approach_options=None, approach_meshes=False, approach_timing=None, **plan_kwargs):
+                     approach_steps=16, approach_options=None, approach_meshes=False, approach_timing=None, approach_audit=None, **plan_kwargs):
         """plan() towards Cartesian targets: one inverse-kinematics launch (ik.IKSolver.solve_device: theta_ref = x0, the planner's
         obstacles with their D -- its line obstacles, and with ik_meshes=True its mesh obstacles too --, the planner's joint_limits if
         it has them, else robot.thetamax; generator seed `seed`), then
@@ -199,10 +200,18 @@ class RRTCFSPlanner:
         feed, stops, curve_share: the winners' approach paths are then timed on the same stream (stops="corners" reads
         approach_steps), and the result gains approach_time, approach_sdot (S, approach_steps+1), approach_duration and
         approach_time_status (PathTimer's status; a slot without an approach path: NaN rows and status 1).  Needs approach and
-        approach_steps >= 2."""
+        approach_steps >= 2.
+        approach_audit: None (the default: everything above, bit for bit) or a dict of substeps (default 8), min_clearance, max_chord
+        (audit.PathAudit's; a missing one is not tested): the line is then traced with every candidate kept, all of them are audited
+        between their rows on the same stream, and per slot the candidate nearest to x0 that passes is taken, as plan_to_path's
+        path_audit takes it: status -4 for a slot with a complete line none of which passes, and the result gains
+        approach_clear_lower, approach_clear_path, approach_chord_err, approach_chord_upper and approach_audit_state.  Needs approach;
+        a planner with meshes refuses."""
+        if approach_audit is not None and self._meshes:
+            raise ValueError("approach_audit on a planner with mesh obstacles: meshes are not audited between the rows (line obstacles only)")
         if approach is None:
-            if approach_dir is not None or approach_options is not None or approach_timing is not None:
-                raise ValueError("approach_dir / approach_options / approach_timing need approach")
+            if approach_dir is not None or approach_options is not None or approach_timing is not None or approach_audit is not None:
+                raise ValueError("approach_dir / approach_options / approach_timing / approach_audit need approach")
         else:
             if self._meshes and approach_meshes is not True:
                 raise ValueError("plan_to_pose(approach=...) on a planner with mesh obstacles: the straight-line trace reads line obstacles only "
@@ -272,6 +281,7 @@ class RRTCFSPlanner:
                                                device=self.device, steps=int(approach_steps), meshes=with_meshes, **shared, **approach_options)
             cart = self._ik[ckey]
         timer = self._timer(approach_timing, "approach_timing", ik_options, int(approach_steps), int(approach_steps) + 1)
+        auditor, asub = self._auditor(approach_audit, "approach_audit", ik_options)
         stream = _args.as_stream(stream, self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(stream):
             dev = [self._on_device(a, S) for a in args]
@@ -285,19 +295,26 @@ class RRTCFSPlanner:
                 dd = dist if isinstance(dist, torch.Tensor) else torch.tensor(dist, dtype=torch.float64, device=self.device)
                 pre = (tp - dd.reshape(-1, 1) * u).contiguous()
                 sol = ik.solve_device(pre, ta, x0, seed=int(seed), want_candidates=True, stream=stream)
-                src = cart.trace_device(sol.cand_theta, tp, ta, x0, start_state=sol.cand_status, stream=stream)
+                src = cart.trace_device(sol.cand_theta, tp, ta, x0, start_state=sol.cand_status, want_candidates=auditor is not None, stream=stream)
                 ik_ok = sol.status == 0
+                if auditor is not None:
+                    src, no_pass, audited = self._audit_choice(cart, auditor, asub, sol.cand_theta, src, x0, stream, "approach")
                 more = dict(ik_goal=sol.theta, approach_path=src.path, grasp=src.path[:, -1], approach_status=src.status,
                             approach_clearance=src.clearance, approach_selected=src.selected)
                 if timer is not None:
                     tm = timer.time_device(src.path, state=src.status, steps=int(approach_steps), stream=stream)
                     more.update(approach_time=tm.time, approach_sdot=tm.sdot, approach_duration=tm.duration, approach_time_status=tm.status)
             ok = src.status == 0
+            if approach is not None and auditor is not None:
+                ok = ok & ~no_pass
             goal = torch.where(ok[:, None], src.theta, x0)
             res = self.plan(x0, goal, seed, **dict(plan_kwargs, stream=stream))
             masked = torch.full_like(res.status, -2)          # a slot without a goal is masked: -2 no IK solution, -3 no approach
             if approach is not None:
                 masked = torch.where(ik_ok, torch.full_like(res.status, -3), masked)
+                if auditor is not None:
+                    masked = torch.where(no_pass, torch.full_like(res.status, -4), masked)
+                    more.update(audited)
             res.status = torch.where(ok, res.status, masked)
             res.has_solution = torch.where(ok, res.has_solution, torch.zeros_like(res.has_solution))
             res.selected = torch.where(ok, res.selected, torch.full_like(res.selected, -1))
@@ -307,7 +324,7 @@ class RRTCFSPlanner:
 
     # ---- tool paths ----------------------------------------------------------------------------------------------------------
     def plan_to_path(self, x0, path_pos, path_axis, seed=0, ik_options=None, ik_meshes=False, path_steps=4, path_options=None,
-                     path_meshes=False, path_timing=None, **plan_kwargs):
+                     path_meshes=False, path_timing=None, path_audit=None, **plan_kwargs):
         """plan() to the start of a tool path that can be followed to its end: path_pos (S, M, 3) or (M, 3), the points the tool
         passes, path_axis the same shape, the tool direction at each (cart.CartesianPath.follow; include/cfs_hip.h, "Tool paths").
         One IK launch at the first pose (path_pos[:, 0], path_axis[:, 0]) with its candidates kept (theta_ref = x0, ik_options as
@@ -328,7 +345,17 @@ class RRTCFSPlanner:
         feed, stops, curve_share (the tool point is ik_options'): the winners' paths are then timed on the same stream
         (stops="corners": at rest at every pose of the polyline, which needs path_steps >= 2), and the result gains tool_path_time,
         tool_path_sdot (S, N), tool_path_duration and tool_path_time_status (PathTimer's status).  A slot masked -2 / -3 holds NaN
-        rows and status 1.  Needs N >= 3."""
+        rows and status 1.  Needs N >= 3.
+        path_audit: None (the default: everything above, bit for bit) or a dict of substeps (default 8), min_clearance, max_chord
+        (audit.PathAudit's; a missing one is not tested; the tool point is ik_options'): the path is then followed with every
+        candidate kept, all of them are audited between their rows on the same stream (include/cfs_hip.h, "Tool-path audit"), and
+        per slot the candidate nearest to x0 -- follow's own cost -- among those that pass is taken: tool_path, tool_path_clearance,
+        tool_path_selected and goal are that candidate's.  A slot with a complete candidate none of which passes gets status = -4 and
+        is masked like -3; its tool_path stays follow's own winner, the path that failed.  The result gains tool_path_clear_lower,
+        tool_path_clear_path, tool_path_chord_err, tool_path_chord_upper and tool_path_audit_state (PathAudit's state_out) of the
+        path reported.  With both thresholds off every field equals the unaudited call's.  A planner with meshes refuses."""
+        if path_audit is not None and self._meshes:
+            raise ValueError("path_audit on a planner with mesh obstacles: meshes are not audited between the rows (line obstacles only)")
         for flag, name in ((ik_meshes, "ik_meshes"), (path_meshes, "path_meshes")):
             if not isinstance(flag, bool):
                 raise ValueError(f"{name} must be True or False, not {flag!r}")
@@ -379,6 +406,7 @@ class RRTCFSPlanner:
                                            device=self.device, steps=int(path_steps), meshes=with_meshes, **shared, **path_options)
         cart = self._ik[ckey]
         timer = self._timer(path_timing, "path_timing", ik_options, int(path_steps), (M - 1) * int(path_steps) + 1)
+        auditor, asub = self._auditor(path_audit, "path_audit", ik_options)
         stream = _args.as_stream(stream, self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(stream):
             x0 = self._on_device(x0, S)
@@ -389,21 +417,69 @@ class RRTCFSPlanner:
                 tabs.append((t.unsqueeze(0).expand(S, -1, -1) if t.ndim == 2 else t).contiguous())
             pp, pa = tabs
             sol = ik.solve_device(pp[:, 0].contiguous(), pa[:, 0].contiguous(), x0, seed=int(seed), want_candidates=True, stream=stream)
-            src = cart.follow_device(sol.cand_theta, pp, pa, x0, start_state=sol.cand_status, stream=stream)
+            src = cart.follow_device(sol.cand_theta, pp, pa, x0, start_state=sol.cand_status, want_candidates=auditor is not None, stream=stream)
+            if auditor is not None:
+                src, no_pass, audited = self._audit_choice(cart, auditor, asub, sol.cand_theta, src, x0, stream, "tool_path")
             ok, ik_ok = src.status == 0, sol.status == 0
             first = src.path[:, 0]
             goal = torch.where(ok[:, None], first, x0)
             res = self.plan(x0, goal, seed, **dict(plan_kwargs, stream=stream))
             masked = torch.where(ik_ok, torch.full_like(res.status, -3), torch.full_like(res.status, -2))
+            if auditor is not None:
+                masked = torch.where(no_pass, torch.full_like(res.status, -4), masked)
+                ok = ok & ~no_pass
             res.status = torch.where(ok, res.status, masked)
             res.has_solution = torch.where(ok, res.has_solution, torch.zeros_like(res.has_solution))
             res.selected = torch.where(ok, res.selected, torch.full_like(res.selected, -1))
             res.goal, res.ik_goal, res.ik_status, res.ik_err_pos, res.ik_clearance = first, sol.theta, sol.status, sol.err_pos, sol.clearance
             res.tool_path, res.tool_path_status, res.tool_path_clearance, res.tool_path_selected = src.path, src.status, src.clearance, src.selected
+            if auditor is not None:
+                vars(res).update(audited)
             if timer is not None:
                 tm = timer.time_device(src.path, state=src.status, steps=int(path_steps), stream=stream)
                 res.tool_path_time, res.tool_path_sdot, res.tool_path_duration, res.tool_path_time_status = tm.time, tm.sdot, tm.duration, tm.status
         return res
+
+    def _auditor(self, audit, name, ik_options):
+        """(the PathAudit, the sub-steps) of a path_audit / approach_audit dict ((None, None): no audit), validated without a device
+        call"""
+        if audit is None:
+            return None, None
+        if not isinstance(audit, dict) or set(audit) - {"substeps", "min_clearance", "max_chord"}:
+            raise ValueError(f"{name} must be a dict of substeps, min_clearance, max_chord")
+        substeps = _args.int_in(audit.get("substeps", 8), f"{name}['substeps']", 1, MAX_SUBSTEPS)
+        key = (name, repr(ik_options.get("tool")), repr(audit.get("min_clearance")), repr(audit.get("max_chord")))
+        if key not in self._ik:
+            self._ik[key] = PathAudit(self._sys_rrt.robot, [o for o in self._pobs], tool=ik_options.get("tool"), njoint=self.nj, device=self.device,
+                                      min_clearance=audit.get("min_clearance"), max_chord=audit.get("max_chord"))
+        return self._ik[key], substeps
+
+    def _audit_choice(self, cart, auditor, substeps, starts, src, x0, stream, prefix):
+        """Audits every candidate of a trace / follow result `src` (made with want_candidates) and takes, per slot, the passing
+        candidate of the smallest cost -- the kernels' own: sum_c w_c (start_c - x0_c)^2 in joint order, the lowest index on a tie.
+        Returns (src with theta, path, clearance and selected of that candidate where it is not the kernel's own winner, the slots
+        that have a complete candidate but none that passes, the audit's outputs of the path reported as a dict of result fields)."""
+        au = auditor.audit_device(src.cand_path, state=src.cand_status, substeps=substeps, stream=stream)
+        w = np.ones(self.nj) if cart.weight is None else cart.weight
+        cost = torch.zeros_like(au.clear_lower)
+        for c in range(self.nj):                              # one rounding per operation, as ik_cost has them
+            dl = starts[:, :, c] - x0[:, None, c]
+            cost = cost + float(w[c]) * (dl * dl)
+        passing = au.state_out == 0
+        idx = torch.where(passing, cost, torch.full_like(cost, math.inf)).argmin(dim=1)
+        passed = passing.any(dim=1)
+        complete = src.status == 0
+        take = passed & (idx != src.selected)                 # another candidate than the kernel's winner
+        pick = lambda t, i: t.gather(1, i.reshape((-1,) + (1,) * (t.ndim - 1)).expand((-1, 1) + tuple(t.shape[2:]))).squeeze(1)  # noqa: E731
+        out = SimpleNamespace(**vars(src))
+        out.theta = torch.where(take[:, None], pick(starts, idx), src.theta)
+        out.path = torch.where(take[:, None, None], pick(src.cand_path, idx), src.path)
+        out.clearance = torch.where(take, pick(au.clear_rows, idx), src.clearance)
+        out.selected = torch.where(take, idx.to(src.selected.dtype), src.selected)
+        shown = torch.where(passed, idx, src.selected.clamp(min=0).to(idx.dtype))
+        audited = {f"{prefix}_{k}": pick(getattr(au, k), shown) for k in ("clear_lower", "clear_path", "chord_err", "chord_upper")}
+        audited[f"{prefix}_audit_state"] = pick(au.state_out, shown)
+        return out, complete & ~passed, audited
 
     def _timer(self, timing, name, ik_options, steps, rows):
         """the PathTimer of a path_timing / approach_timing dict (None: no timing), validated without a device call"""
